@@ -36,6 +36,10 @@ Also reported on the same JSON line:
   ranks        who took part: backend, world size as the process group reports it, (rank, local rank, device, PCI bus id,
                uuid) of every rank gathered over that backend, RCCL version
   summary      LAST key of the line: roofline fraction of every config leg + all_verified, so that a truncated tail still says it
+
+`--dump-outputs DIR` writes the main leg's last output (rank 0) as float64 .npy files: hist.npy (what core.histogram would
+return for these inputs: the density when the config asks for one, else the counts / weighted sums) and bin_edges_<d>.npy.
+Inputs come from fixed seeds, so the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -57,7 +61,9 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md); ~6300 GB/s is 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; 200 for the sub-millisecond steps of --config c4)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps of the main leg, which `ms_per_step` reports (default 20; 200 for the sub-millisecond steps of "
+                         "--config c4); the legs that ride along in the default run (\"configs\", \"distributions\") keep step counts of their own")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 10; 50 for --config c4)")
     ap.add_argument("--samples", type=int, default=1_000_000_000, help="samples per GPU")
     ap.add_argument("--bins", type=int, default=100)
@@ -88,7 +94,14 @@ def parse():
     ap.add_argument("--dist", default="normal", choices=["normal", "uniform"],
                     help="c1 / c2 sample distribution for profiler passes and A/B runs: N(0,1) (the headline) or uniform[-4,4) (every bin equally likely)")
     ap.add_argument("--cpu-sample", type=int, default=400_000_000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the main leg's last step computed (the histogram a caller receives, "
+                         "and its bin edges) as DIR/<name>.npy in float64, so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
     # a C4 shard step is one 0.3 ms kernel: the first tens of launches after an idle GPU run 5-8 % slower (0.309 ms over steps
     # 6..25, 0.290 ms over steps 51..250 and beyond), so its default run is longer; every other config's kernel takes milliseconds
     # and does not care (profiles/r02_z_warmup.txt)
@@ -315,6 +328,28 @@ def host_inputs_leg(torch, core, dev, arrays, w, edges, n_host=200_000_000, chun
 
 
 VERIFY_RTOL = 1e-6  # north_star: float64 weighted sums / density within 1e-6 relative; int64 counts bit-exact
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, hist, edges):
+    """--dump-outputs: `hist` (a tensor, copied to the host here) and the bin edges as float64 .npy files in out_dir.
+    A histogram beyond DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its bins: hist_sample.npy holds their
+    values, hist_sample_index.npy their flat indices (sorted)."""
+    os.makedirs(out_dir, exist_ok=True)
+    h = hist.detach().cpu().numpy().astype(np.float64)
+    files = {"bin_edges_%d" % d: np.asarray(e, dtype=np.float64) for d, e in enumerate(edges)}
+    room = (DUMP_LIMIT_BYTES - sum(a.nbytes for a in files.values())) // 8
+    if h.size <= room:
+        files["hist"] = h
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(h.size, size=room // 2, replace=False))
+        files["hist_sample_index"] = idx.astype(np.float64)
+        files["hist_sample"] = h.reshape(-1)[idx]
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print("bench.py: wrote %s to %s" % (", ".join(sorted(n + ".npy" for n in files)), out_dir), file=sys.stderr)
 
 
 def compare_with_reference(torch, got, ref):
@@ -628,13 +663,15 @@ def measure_and_report(args, torch, dist, _native, core, wl, plan, dev, world, r
         total = float(out.sum().item())
         assert total > 0
         verdict = check_leg(out, dens[0], n_cols, weighted) if verify else None
-        # the exchange on its own: `steps` all-reduces of the partial, nothing else on the GPU
+        # the exchange on its own: `steps` all-reduces of a buffer of the partial's size, nothing else on the GPU (not of the
+        # result buffers themselves: `out` is the leg's result and stays what its last step computed)
         allreduce_ms = None
         if reduce_partials:
+            scratch = torch.zeros_like(outs[0])
             fence()
             t0 = time.perf_counter()
             for _ in range(steps):
-                dist.all_reduce(outs[0], op=dist.ReduceOp.SUM)
+                dist.all_reduce(scratch, op=dist.ReduceOp.SUM)
             sync()
             allreduce_ms = (time.perf_counter() - t0) / steps * 1e3
             fence()
@@ -651,6 +688,11 @@ def measure_and_report(args, torch, dist, _native, core, wl, plan, dev, world, r
     # sub-millisecond kernels (the C4 shard): the first launches after an idle GPU are reported next to the steady rate
     cold = 20 if (args.config == "c4" and not args.full and not args.selftest and not args.profiler_pass) else 0
     legs[main_leg] = run_leg(cols_weak if main_leg == "weak" else cols_strong, args.steps, args.warmup, cold=cold, time_first=not as_extra and not args.profiler_pass)
+    if getattr(args, "dump_outputs", None) and not as_extra and rank == 0:
+        # now: the legs below reuse the output buffers (and overwrite the samples in place)
+        m0 = legs[main_leg]
+        res = m0["dens"] if density else m0["last"]
+        dump_outputs(args.dump_outputs, res[0] if n_rows == 1 else res, edges)
     # the headline's 8 B/sample variant — north_star's target sentence is the 1-D 10^9-sample f64 histogram WITHOUT weights
     # (BASELINE.md section 3 "headline unweighted variant") — rides along on the same samples: `"unweighted": {...}`
     unweighted_leg = None

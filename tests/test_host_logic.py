@@ -114,8 +114,10 @@ def test_axis_and_argument_errors_raise_before_compute():
 
 
 def test_default_device_env(monkeypatch):
-    monkeypatch.delenv("XHIST_AMD_DEVICE", raising=False)
-    monkeypatch.delenv("LOCAL_RANK", raising=False)
+    for k in core.LOCAL_RANK_VARS:
+        monkeypatch.delenv(k, raising=False)
+    # a node of 8 GPUs, whatever this machine shows (a launcher's rank is taken modulo the visible count)
+    monkeypatch.setattr(_native, "device_count", lambda: 8)
     assert core.default_device() == 0
     monkeypatch.setenv("LOCAL_RANK", "3")
     assert core.default_device() == 3

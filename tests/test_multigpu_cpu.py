@@ -106,6 +106,7 @@ def test_small_host_inputs_stay_on_one_gpu(monkeypatch):
 
 
 def test_a_rank_of_a_launcher_keeps_to_its_gpu(monkeypatch):
+    monkeypatch.setattr(_native, "device_count", lambda: 8)  # a node of 8 GPUs, whatever this machine shows
     monkeypatch.setenv("LOCAL_RANK", "3")
     assert multigpu.get_devices() == [3]
     monkeypatch.setenv("XHIST_AMD_DEVICES", "1,2")
@@ -469,6 +470,7 @@ def test_a_launched_rank_keeps_to_its_gpu(monkeypatch, var):
         monkeypatch.delenv(k, raising=False)
     multigpu.set_devices(None)
     monkeypatch.setattr(multigpu, "visible_devices", lambda: [0, 1, 2, 3, 4, 5, 6, 7])
+    monkeypatch.setattr(_native, "device_count", lambda: 8)
     assert multigpu.get_devices() == [0, 1, 2, 3, 4, 5, 6, 7]
     monkeypatch.setenv(var, "5")
     assert core.default_device() == 5 and multigpu.get_devices() == [5]
