@@ -225,8 +225,7 @@ extern "C" int xhist_plan_execute(xhist_plan* p, const xhist_array* samples, con
   // threaded scheduler runs many blocks at once — then overlap one block's staging copy with another
   // block's kernel instead of queueing behind each other.
   Range r("xhist_plan_execute[host: stage + bin]");
-  static const bool null_stream = [] { const char* e = getenv("XHIST_AMD_HOST_STREAM"); return e && !strcmp(e, "null"); }();
-  return execute_host(p, samples, weights, n_rows, n_cols, out, accumulate, s ? s : (null_stream ? nullptr : hipStreamPerThread),
+  return execute_host(p, samples, weights, n_rows, n_cols, out, accumulate, s ? s : hipStreamPerThread,
                       mem_kind == XHIST_MEM_HOST_TO_DEVICE);
 }
 

@@ -49,11 +49,17 @@ static const void* advance(const void* base, int dt, int64_t elems) {
   return static_cast<const char*>(base) + elems * dtype_size(dt);
 }
 
+// The arrays a call reads, in order: samples[0 .. D), then the weights (index D) when there are any.
+static int n_arrays(int D, const xhist_array* weights) { return weights ? D + 1 : D; }
+static const xhist_array& array_at(const xhist_array* samples, const xhist_array* weights, int D, int d) {
+  return d < D ? samples[d] : *weights;
+}
+
 // Partitioned mode (xhist_partition.hip.h): count -> prefix -> scatter -> accumulate, all on
 // `stream`, scratch from the stream-ordered allocator (so concurrent callers never share it).
 static int execute_partitioned(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_cols, void* out,
                                hipStream_t stream, int sdt, int wdt, int scan, bool use_f32, const TableSet& tset, int shift,
-                               int n_parts, int profile, LaunchRecord& rec, bool first, bool last) {
+                               int n_parts, const PlanKnobs& kn, LaunchRecord& rec, bool first, bool last) {
   const int D = p->n_dims;
   const bool weighted = weights != nullptr;
   if (n_cols >= ((int64_t)1 << 40)) return XHIST_ERR_UNSUPPORTED;
@@ -148,7 +154,7 @@ static int execute_partitioned(xhist_plan* p, const xhist_array* samples, const 
   if (lds_acc > 48 * 1024) HIPR(hipFuncSetAttribute((const void*)k_acc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_acc));
 
   if (first)  // one timing record per execute: opened before the first row's kernels, closed after the last row's
-    if (int rrc = rec.begin(profile)) return release(rrc);
+    if (int rrc = rec.begin(kn.profile)) return release(rrc);
   XH_LAUNCH_PICKED(k_count, dim3(G), dim3(kPartBlock), lds_count, stream, kp, d_flat);
   HIPR(hipGetLastError());
   hipLaunchKernelGGL(part_prefix, dim3(1), dim3(1024), 0, stream, (const uint32_t*)d_counts, G, n_parts, grp, d_offsets, d_base);
@@ -229,12 +235,12 @@ struct RouteGeom {
   int block, spl;
 };
 // Table lookups (edges that are not arithmetic) take more registers than the arithmetic digitize: 24 there.
-static RouteGeom route_geom_for(const xhist_plan* p, int sdt, int wdt /* -1: counts */, int D, int scan) {
+static RouteGeom route_geom_for(const PlanKnobs& kn, int sdt, int wdt /* -1: counts */, int D, int scan) {
   RouteGeom g;
   g.block = 1024;
   // (route_long_tile_ok, xhist_pick.hip.h: the same rule decides which long-tile kernels exist; a forced 8 without one falls to 4)
   const bool long_ok = route_long_tile_ok(sdt == XHIST_F64 ? 8 : 4, wdt == XHIST_F64 ? 8 : wdt == XHIST_F32 ? 4 : 0, D, scan == kScanArith);
-  g.spl = p->route_spl == 4 ? 4 : (long_ok ? 8 : 4);
+  g.spl = kn.route_spl == 4 ? 4 : (long_ok ? 8 : 4);
   return g;
 }
 
@@ -254,7 +260,7 @@ static RouteGeom route_geom_for(const xhist_plan* p, int sdt, int wdt /* -1: cou
 // a few time steps of a big joint histogram cost one launch pair instead of one per row; rows * parts_per_row <= 128.
 static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_cols, void* out,
                                      hipStream_t stream, int sdt, int wdt, int scan, bool use_f32, const TableSet& tset, int shift,
-                                     int parts_per_row, int profile, LaunchRecord& rec, bool first, bool last, RouteGeom geom, int rows = 1) {
+                                     int parts_per_row, const PlanKnobs& kn, LaunchRecord& rec, bool first, bool last, RouteGeom geom, int rows = 1) {
   const int D = p->n_dims;
   const bool weighted = weights != nullptr;
   const int n_parts = parts_per_row * rows;
@@ -263,7 +269,7 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
   const int block = geom.block, spl = geom.spl;
   kernel_fn_route k_route = route_kernel(sdt, wdt, D, scan, rows > 1, block, spl);
   if (!k_route) return XHIST_ERR_UNSUPPORTED;
-  bool pack = weighted && wdt == XHIST_F64 && p->records48_pref >= 0 && !exact_records_env();
+  bool pack = weighted && wdt == XHIST_F64 && kn.records48_pref >= 0 && !exact_records_env();
   if (!p->mixed_hint) {  // pinned host words the GPU writes: [0] a call met weights of both signs, [1] a chunk pool ran dry
     std::lock_guard<std::mutex> lk(p->mu);
     if (!p->mixed_hint) {
@@ -272,23 +278,28 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
       else (void)hipGetLastError();
     }
   }
-  if (p->mixed_hint) {
+  int exch_skip;
+  {
     // An exchange kernel of an earlier call gave up IN FLIGHT (a wait that outlived its deadline, a placement other than 32
     // workgroups per XCD) and the classic passes took that call: the plan stays away from the mode for its next 16 eligible
     // calls, twice as many after every further abort (a second hang would cost its deadline again), and is admitted again after
     // that; a clean call resets the count.  (Workgroups that were not all resident at the START cost arrive_ticks, not the
     // deadline, and do not count: note[5].)  "exchange" set again forgets all of it.
     std::lock_guard<std::mutex> lk(p->mu);
-    if (p->mixed_hint[2] != p->exchange_aborts_seen) {
-      p->exchange_aborts_seen = p->mixed_hint[2];
-      p->exchange_skip = p->exchange_backoff;
-      p->exchange_backoff = std::min(p->exchange_backoff * 2, 4096);
-    } else if (p->exchange_skip > 0) {
-      p->exchange_skip -= 1;
-    } else if (p->exchange_ran_last) {
-      p->exchange_backoff = 16;
+    ExchangeState& xs = p->exch;
+    if (p->mixed_hint) {
+      if (p->mixed_hint[2] != xs.aborts_seen) {
+        xs.aborts_seen = p->mixed_hint[2];
+        xs.skip = xs.backoff;
+        xs.backoff = std::min(xs.backoff * 2, 4096);
+      } else if (xs.skip > 0) {
+        xs.skip -= 1;
+      } else if (xs.ran_last) {
+        xs.backoff = 16;
+      }
+      xs.ran_last = false;
     }
-    p->exchange_ran_last = false;
+    exch_skip = xs.skip;
   }
   if (pack && (!p->mixed_hint || *p->mixed_hint != 0u)) pack = false;  // (earlier calls met both signs: straight to exact records)
   kernel_fn_route k_route48 = pack ? route_kernel(sdt, kWdtPacked48, D, scan, rows > 1, block, spl) : nullptr;
@@ -299,13 +310,13 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
   //  3*10^8 samples, 2-3 inputs read 0.93-1.03 of the classic exact passes — whose own time moves by 10 % from process to process
   //  and size to size with the placement of their five streams, while this form does not: C5 4.14-4.18 ms in every process against
   //  4.09 | 4.50-4.53 — and ONE input reads 1.08-1.11: profiles/r06_e_*)
-  const bool xexact = weighted && wdt == XHIST_F64 && !pack && rows == 1 && (D >= 2 || p->exchange_pref > 0);
+  const bool xexact = weighted && wdt == XHIST_F64 && !pack && rows == 1 && (D >= 2 || kn.exchange_pref > 0);
   // an exchange kernel of ANOTHER stream may still hold the GPU: looked at before the scratch allocations below, and the lock is
   // kept until this call's own exchange kernel has been launched and its event recorded (two host threads that both saw "idle"
   // would otherwise both launch one)
   bool other_stream_busy = false;
   std::unique_lock<std::mutex> xfl_lock;
-  if ((pack || xexact) && p->exchange_pref >= 0) {
+  if ((pack || xexact) && kn.exchange_pref >= 0) {
     ExchInFlight& fl = exch_in_flight(p->device);
     xfl_lock = std::unique_lock<std::mutex>(fl.mu);
     if (fl.armed && fl.stream != stream && hipEventQuery(fl.ev) == hipErrorNotReady) other_stream_busy = true;
@@ -322,12 +333,6 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
   // (Round 4 also ran the adding-up pass of sample sub-batch k on a second stream under the routing pass of sub-batch k + 1:
   // 25-60 % slower, both passes scale with the compute units they get — DESIGN_HISTORY 4.2b, profiles/r04_b_*; removed in
   // round 5.)
-  int route_grid = 0, acc_grid = 0;
-  {
-    std::lock_guard<std::mutex> lk(p->mu);
-    route_grid = p->route_grid;
-    acc_grid = p->acc_grid;
-  }
   const int64_t n_piece = n_total;  // samples one routing pass sees
   const int64_t n_tiles = ((n_cols + tile - 1) / tile) * rows;
   // workgroups resident per CU: by LDS — and by registers: the routing pass is held to 128 per lane (waves_per_eu 4), so a
@@ -336,13 +341,11 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
   const int per_cu = std::max<int>(1, std::min<int>(std::min<int>(4, 1024 / block), (int)((size_t)160 * 1024 / lds_route)));
   int G = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)p->cus * per_cu, n_tiles));
   int Gb = (int)std::max<int64_t>(1, std::min<int64_t>(p->cus, (n_piece + 65535) / 65536));
-  if (route_grid) G = (int)std::min<int64_t>(route_grid, n_tiles);
-  if (acc_grid) Gb = acc_grid;
+  if (kn.route_grid) G = (int)std::min<int64_t>(kn.route_grid, n_tiles);
+  if (kn.acc_grid) Gb = kn.acc_grid;
   // chunk size: a workgroup files at most kRouteListCap chunks (its list lives in LDS), 2^10 .. 2^14 records each
   int lg = 10;
   while (lg < 14 && (((n_piece / G) + tile) >> lg) + n_parts + 16 > route_list_cap(block)) ++lg;
-  static const int lg_env = [] { const char* e = getenv("XHIST_AMD_ROUTE_CHUNK_LOG2"); return e && *e ? atoi(e) : 0; }();  // A/B runs only
-  if (lg_env >= 10 && lg_env <= 14 && lg_env > lg) lg = lg_env;
   const int64_t GP = (int64_t)G * n_parts;
   // Chunks that hold records: every chunk but the one in use by its (workgroup, partition) owner is full, and at most 7
   // padding records are added per owner.  Ids taken from the pool but never used: a workgroup's stock drops fewer ids than
@@ -351,7 +354,7 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
   const int64_t used = ((n_piece + 7 * GP) >> lg) + GP;
   int64_t pool_chunks = used + used / 6 + (int64_t)G * (2 * route_batch(n_parts, lg, tile) + 2 * route_max_need(lg, tile)) + 64;
   // "route_pool_pct" < 100 (tests): a pool too small on purpose — what finds no chunk goes straight into the output
-  if (p->route_pool_pct > 0 && p->route_pool_pct < 100) pool_chunks = std::max<int64_t>(1, pool_chunks * p->route_pool_pct / 100);
+  if (kn.route_pool_pct > 0 && kn.route_pool_pct < 100) pool_chunks = std::max<int64_t>(1, pool_chunks * kn.route_pool_pct / 100);
   if (pool_chunks >= ((int64_t)1 << 31) || (pool_chunks << lg) >= ((int64_t)1 << 44)) return XHIST_ERR_UNSUPPORTED;
 
   uint32_t *d_ctr = nullptr, *d_plist = nullptr, *d_cmeta = nullptr;
@@ -393,8 +396,8 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
   bool xch = false, xch_probe = false;
   kernel_fn_exch k_xch = nullptr, k_xprobe = nullptr;
   size_t lds_xch = 0;
-  if ((pack || xexact) && rows == 1 && p->exchange_pref >= 0 && (p->exchange_skip == 0 || p->exchange_pref > 0) && sdt == XHIST_F64 && p->arith && p->arith_pref >= 0 && D <= 3 && p->cus == kExchXcds * kExchRings &&
-      p->n_bins <= ((int64_t)1 << 23) /* (the side copy is zeroed per call) */ && (p->exchange_pref > 0 || n_cols >= ((int64_t)1 << 25))) {
+  if ((pack || xexact) && rows == 1 && kn.exchange_pref >= 0 && (exch_skip == 0 || kn.exchange_pref > 0) && sdt == XHIST_F64 && p->arith && kn.arith_pref >= 0 && D <= 3 && p->cus == kExchXcds * kExchRings &&
+      p->n_bins <= ((int64_t)1 << 23) /* (the side copy is zeroed per call) */ && (kn.exchange_pref > 0 || n_cols >= ((int64_t)1 << 25))) {
     const int64_t L = D >= 2 ? (int64_t)p->ts[0][0].dim[D - 1].nb : 256;
     const int64_t hist_rows = D >= 2 ? p->n_bins / L : (p->n_bins + 255) / 256;
     const int64_t units = (hist_rows + kExchUnitRows - 1) / kExchUnitRows;
@@ -411,12 +414,12 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
       xa.rows_per = (int32_t)rows_per;
       xa.local_bins = (int32_t)(rows_per * L);
       xa.n_units = (int32_t)units;
-      xa.force = p->exchange_pref > 0 ? 1 : 0;
+      xa.force = kn.exchange_pref > 0 ? 1 : 0;
       { int64_t p2 = 1; while (p2 * 2 <= L) p2 *= 2; xa.side_rot_mask = (int32_t)(p2 - 1); }
-      xa.min_ppm = p->exchange_min_pct > 0 ? p->exchange_min_pct * 10000 : kExchMinPpm;
+      xa.min_ppm = kn.exchange_min_pct > 0 ? kn.exchange_min_pct * 10000 : kExchMinPpm;
       xa.max_uneven_ppm = 1250000;
-      xa.budget_ticks = p->exchange_budget_ms < 0 ? 0 : (long long)(p->exchange_budget_ms ? p->exchange_budget_ms : 500) * 100000;
-      xa.arrive_ticks = (long long)(p->exchange_arrive_us > 0 ? p->exchange_arrive_us : 200) * 100;  // 200 us: the launch of 256 workgroups on a free chip takes a few
+      xa.budget_ticks = kn.exchange_budget_ms < 0 ? 0 : (long long)(kn.exchange_budget_ms ? kn.exchange_budget_ms : 500) * 100000;
+      xa.arrive_ticks = (long long)(kn.exchange_arrive_us > 0 ? kn.exchange_arrive_us : 200) * 100;  // 200 us: the launch of 256 workgroups on a free chip takes a few
       const size_t words_bytes = ((size_t)(units + kExchRings + 8 + 32) * 4 + 7) & ~(size_t)7;  // win[8], the cold arguments (32 words), the probe's counts (units, then owners)
       // one block for everything that is zeroed per call (one launch): control words | window, cold arguments, probe counts | side copy | rings
       const size_t ctl_bytes = sizeof(ExchCtl) * kExchXcds, side_bytes = (size_t)(hist_rows * L) * 8;  // (whole rows: exch_side_index rotates inside a row)
@@ -439,14 +442,21 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
       // every workgroup of the kernel must be resident (they wait for one another): one per compute unit is what its LDS and
       // registers must allow; asked once per plan and LDS size (a kernel of the host's that holds compute units at run time is
       // the deadline's business)
-      if (p->exchange_occ_lds != lds_xch) {
+      bool occ_known, occ_ok;
+      {
+        std::lock_guard<std::mutex> lk(p->mu);
+        occ_known = p->exch.occ_lds == lds_xch;
+        occ_ok = p->exch.occ_ok;
+      }
+      if (!occ_known) {
         int per_cu_x = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_x, (const void*)k_xch, kExchBlock, lds_xch) != hipSuccess) { per_cu_x = 0; (void)hipGetLastError(); }
+        occ_ok = per_cu_x >= 1;
         std::lock_guard<std::mutex> lk(p->mu);
-        p->exchange_occ_lds = lds_xch;
-        p->exchange_occ_ok = per_cu_x >= 1;
+        p->exch.occ_lds = lds_xch;
+        p->exch.occ_ok = occ_ok;
       }
-      if (!p->exchange_occ_ok) xch = false;
+      if (!occ_ok) xch = false;
     }
   }
 
@@ -462,7 +472,7 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
   }
 
   if (first)  // one timing record per execute: opened before the first row's kernels, closed after the last row's
-    if (int rrc = rec.begin(profile)) return release(rrc);
+    if (int rrc = rec.begin(kn.profile)) return release(rrc);
   const DimTable* dims = tset.dim;
   {
     Params kp;
@@ -542,7 +552,7 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
       }
       {
         std::lock_guard<std::mutex> lk(p->mu);
-        p->exchange_ran_last = true;
+        p->exch.ran_last = true;
       }
       ra.xgate = xa.win + 1;  // the classic packed kernels below return at once when the mode took the call
     }
@@ -598,8 +608,9 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
 // after transposing them into a [cols, rows] scratch.  Returns XHIST_ERR_UNSUPPORTED when the
 // shape is better served by the row-streaming kernels.
 static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_rows, int64_t n_cols,
-                         void* out, int accumulate, hipStream_t stream, bool prefer, int profile) {
+                         void* out, int accumulate, hipStream_t stream, const PlanKnobs& kn) {
   const int D = p->n_dims;
+  const bool prefer = kn.lanes > 0;
   const bool weighted = weights != nullptr;
   if (p->cmp != XHIST_CMP_F64 || D > 3 || n_cols >= ((int64_t)1 << 31) || p->n_bins >= (1 << 16) || p->huge) return XHIST_ERR_UNSUPPORTED;
   const int sdt = samples[0].dtype, wdt = weighted ? weights->dtype : -1;
@@ -612,9 +623,8 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
   // shape class of every array: natural (row stride 0/1, any column stride) or needs a transpose
   // (unit column stride, dense-ish rows)
   bool all_natural = true, all_rowmajor = true, grouped_any = false;
-  for (int d = 0; d <= D; ++d) {
-    if (d == D && !weighted) break;
-    const xhist_array& a = d < D ? samples[d] : *weights;
+  for (int d = 0; d < n_arrays(D, weights); ++d) {
+    const xhist_array& a = array_at(samples, weights, D, d);
     if (d < D && a.dtype != sdt) return XHIST_ERR_UNSUPPORTED;
     const bool bcast = a.row_stride == 0 || a.col_stride == 0;
     const bool natural = bcast || (a.row_stride == 1 && (a.inner_rows ? a.col_stride >= 1 : a.col_stride >= n_rows));
@@ -634,12 +644,10 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
   // row-per-lane and flat-rows kernels digitize sample by sample and feel every table read ((1825, 360, 720) float32 over
   // time, 50 geometric bins: 0.97 -> see profiles/r04_j_*)
   {
-    int pack_pref;
-    { std::lock_guard<std::mutex> lk(p->mu); pack_pref = p->pack_pref; }
     const int pk_np = small ? 0 : (sdt == XHIST_F64 ? p->pk_np : (use_f32 ? p->pk32_np : 0));
     // (only against the binary search: with 3-4 edges per bucket the two-level tables are AHEAD in these LDS-hungry kernels —
     //  400 random edges, float32: row-per-lane 0.62 against 0.89 ms, flat rows 0.95 against 1.60)
-    if (pk_np && pack_pref >= 0 && (scan == 0 || pack_pref > 0)) {
+    if (pk_np && kn.pack_pref >= 0 && (scan == 0 || kn.pack_pref > 0)) {
       picked = sdt == XHIST_F64 ? &p->ts_pk : &p->ts_pk32;
       scan = kScanPackG;
     }
@@ -657,19 +665,17 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
   const uint32_t flat_nbp = weighted ? (uint32_t)p->n_bins : (((uint32_t)p->n_bins + 1u) & ~1u);
   // (copies of a row's counters for the lanes of a wavefront to spread over — they read neighbouring samples, one or two
   // rows at a time — were measured and bought nothing: 10^6 rows of 365 float32, 1 / 2 / 4 / 8 copies 0.403 / 0.411 / 0.422 /
-  // 0.497 ms; rows of 200: 0.463 / 0.468 / 0.520 / 0.684; the kernel keeps the parameter, XHIST_AMD_FLAT_K_LOG2 sets it)
-  static const int flat_k_env = [] { const char* e = getenv("XHIST_AMD_FLAT_K_LOG2"); return e && *e ? atoi(e) : 0; }();
-  const int flat_k_log2 = std::max(0, std::min(3, flat_k_env));
+  // 0.497 ms; rows of 200: 0.463 / 0.468 / 0.520 / 0.684; the kernel keeps the parameter, at one copy here)
+  constexpr int flat_k_log2 = 0;
   const size_t flat_row_bytes = ((size_t)flat_nbp << flat_k_log2) * (weighted ? 8 : 2);  // LDS per row of a workgroup
   bool flat_ok = (D == 1 || D == 2) && !small && n_cols >= 1 && n_cols < 65536 && (sdt != XHIST_F32 || use_f32) && flat_row_bytes <= 4096 &&
                  (!weighted || wdt == XHIST_F32 || wdt == XHIST_F64);
-  for (int d = 0; d <= D && flat_ok; ++d) {
-    if (d == D && !weighted) break;
-    const xhist_array& a = d < D ? samples[d] : *weights;
+  for (int d = 0; d < n_arrays(D, weights) && flat_ok; ++d) {
+    const xhist_array& a = array_at(samples, weights, D, d);
     const size_t vec_bytes = (size_t)(16 / dtype_size(sdt)) * (size_t)dtype_size(a.dtype);  // one load: as many elements as a 16-byte sample vector
     flat_ok = a.col_stride == 1 && a.row_stride == n_cols && a.inner_rows == 0 && ((uintptr_t)a.data & (vec_bytes - 1)) == 0;
   }
-  const bool use_flat = flat_ok && !prefer && p->flat_rows >= 0 && n_rows >= 4096 && n_cols <= (p->flat_rows > 0 ? 65535 : kFlatMaxCols) &&
+  const bool use_flat = flat_ok && !prefer && kn.flat_rows >= 0 && n_rows >= 4096 && n_cols <= (kn.flat_rows > 0 ? 65535 : kFlatMaxCols) &&
                         !(all_natural && samples[0].row_stride == 1);
   // (hist_lanes: a counter column per lane, or — shared by a row's lane groups — per row, for as few as 16 rows per workgroup)
   const size_t lds_least = table_bytes + (size_t)p->n_bins * (weighted ? 17 * 8 : 9 * 4);
@@ -731,7 +737,7 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
       const int direct = accumulate ? 0 : 1;
       const uint64_t magic = (((uint64_t)1 << 40) / (uint64_t)n_cols) + 1u;
       LaunchRecord rec(p, stream);
-      if (int rrc = rec.begin(profile)) return rrc;
+      if (int rrc = rec.begin(kn.profile)) return rrc;
       if (lds_flat > 48 * 1024) HIPC(hipFuncSetAttribute((const void*)ff, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_flat));
       XH_LAUNCH_PICKED(ff, dim3((unsigned)row_blocks), dim3(kLaneBlock), lds_flat, stream, kp, (int32_t)direct, (int32_t)R, (int32_t)flat_k_log2,
                          magic, (int64_t)(n_rows * n_cols));
@@ -776,7 +782,7 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
       if (row_blocks > 2147483647LL) return XHIST_ERR_UNSUPPORTED;
       const int direct = accumulate ? 0 : 1;
       LaunchRecord rec(p, stream);
-      if (int rrc = rec.begin(profile)) return rrc;
+      if (int rrc = rec.begin(kn.profile)) return rrc;
       if (lds_f > 48 * 1024) HIPC(hipFuncSetAttribute((const void*)f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
       XH_LAUNCH_PICKED(f1, dim3((unsigned)row_blocks), dim3(kLaneBlock), lds_f, stream, kp, (int32_t)direct);
       HIPC(hipGetLastError());
@@ -804,10 +810,9 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
   memset(&kp, 0, sizeof kp);
   const DimTable* dims = tset.dim;
   LaunchRecord rec(p, stream);
-  if (int rrc = rec.begin(profile)) return release(rrc);
-  for (int d = 0; d <= D; ++d) {
-    if (d == D && !weighted) break;
-    const xhist_array& a = d < D ? samples[d] : *weights;
+  if (int rrc = rec.begin(kn.profile)) return release(rrc);
+  for (int d = 0; d < n_arrays(D, weights); ++d) {
+    const xhist_array& a = array_at(samples, weights, D, d);
     const void* ptr = a.data;
     int64_t rs = a.row_stride, cs = a.col_stride, ir = a.inner_rows, os = a.outer_stride;
     if (transpose && rs != 0 && cs != 0) {
@@ -864,8 +869,7 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
   int lane_pitch = 0;
   auto lds_shared = [&](int rows, bool u16) { return table_bytes + (size_t)p->n_bins * (u16 ? (size_t)(rows / 2 + 1) * 4 : (size_t)(rows + 1) * (weighted ? 8 : 4)); };
   const bool u16_ok = !weighted && n_cols <= 65535;  // (one workgroup per row block then sees every column: see segs16 below)
-  static const size_t share_above = [] { const char* e = getenv("XHIST_AMD_LANES_SHARE_ABOVE_KB"); return (size_t)(e && *e ? atoi(e) : 64) * 1024; }();  // A/B runs
-  static const size_t share_target = [] { const char* e = getenv("XHIST_AMD_LANES_SHARE_TARGET_KB"); return (size_t)(e && *e ? atoi(e) : 40) * 1024; }();
+  constexpr size_t share_above = 64 * 1024, share_target = 40 * 1024;
   if ((u16_ok ? table_bytes + (size_t)p->n_bins * (kLaneBlock / 2 + 1) * 4 : lds_bytes) > std::min(p->lds_max, share_above)) {
     lane_rows = std::min(lane_rows, 128);
     while (lane_rows > 16 && lds_shared(lane_rows, u16_ok) > share_target) lane_rows /= 2;
@@ -919,132 +923,173 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
   return release(XHIST_OK);
 }
 
-// weights2 / out2 (optional): a second weight array binned in the same pass (hist_fast<..., W2>).
-// Only the vector family with LDS histograms does that; anything else returns
-// XHIST_ERR_UNSUPPORTED before touching the outputs, and the caller runs two passes.
-static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_rows,
-                          int64_t n_cols, void* out, int accumulate, hipStream_t stream,
-                          const xhist_array* weights2 = nullptr, void* out2 = nullptr) {
-  const int D = p->n_dims;
-  const bool weighted = weights != nullptr;
-  const bool two = weights2 != nullptr;
-  const int64_t out_elems = n_rows * p->n_bins;
-  if (out_elems == 0) return XHIST_OK;
-  if (n_cols == 0) {
-    if (!accumulate) {
-      if (int zrc = zero_output(out, out_elems, stream)) return zrc;
-      if (two)
-        if (int zrc = zero_output(out2, out_elems, stream)) return zrc;
+// ------------------------------------------------------------------------------------------
+// the streaming kernels: execute_device and its steps
+// ------------------------------------------------------------------------------------------
+static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_rows, int64_t n_cols,
+                          void* out, int accumulate, hipStream_t stream, const xhist_array* weights2 = nullptr, void* out2 = nullptr);
+
+// One execute's arrays and shape, as the steps below see them.
+struct Inputs {
+  const xhist_array* samples;
+  const xhist_array* weights;   // nullptr: counts
+  const xhist_array* weights2;  // a second weight array binned in the same pass, or nullptr
+  int64_t n_rows, n_cols;
+  int D, sdt, wdt;  // wdt: -1 without weights
+  bool weighted, two, float_samples;
+  int n_arrays() const { return ::n_arrays(D, weights); }
+  const xhist_array& array(int d) const { return array_at(samples, weights, D, d); }
+};
+
+// ---- a few rows that are the contiguous direction, too many bins for the row-per-lane kernels ----------------
+// (the columns of an (n, K) table histogrammed over its leading axis with thousands of bins): every other kernel
+// would walk them with a column stride of K elements — the generic family at ~1 TB/s, memory-side atomics at 0.1
+// beyond LDS.  Gather the rows into dense scratch first (one pass, read + write) and run the vector kernels on that:
+// 25 x 10^6 x 4 float32, 5000 bins 0.44 -> see profiles/r02_j_table_columns*.jsonl.
+// Returns XHIST_ERR_UNSUPPORTED (nothing touched) for every other shape.
+static int execute_table_columns(xhist_plan* p, const PlanKnobs& kn, const Inputs& in, void* out, int accumulate, hipStream_t stream) {
+  const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  if (kn.force_generic || in.two || n_rows < 1 || n_rows > 64 || n_cols < 4096) return XHIST_ERR_UNSUPPORTED;
+  bool table = true;
+  for (int d = 0; d < in.n_arrays() && table; ++d) {
+    const xhist_array& a = in.array(d);
+    table = a.inner_rows == 0 && a.row_stride == 1 && a.col_stride >= n_rows && a.col_stride > 1 &&
+            ((uintptr_t)a.data % (size_t)dtype_size(a.dtype)) == 0;
+  }
+  // (up to four 8-byte columns with a histogram that fits LDS: the strided walk of the generic family is as fast — 25 x 10^6 x 4
+  //  float64 + weights, 5000 bins: 0.50 ms against 0.87 with the gather; every other measured shape gains 1.3-9 x)
+  if (table && n_rows <= 4 && dtype_size(in.samples[0].dtype) == 8 && p->n_bins * (in.weighted ? 8 : 4) <= (int64_t)96 * 1024) table = false;
+  if (!table) return XHIST_ERR_UNSUPPORTED;
+  void* scratch[kMaxDims + 1] = {nullptr};
+  xhist_array dense[kMaxDims + 1];  // the samples, then the weights
+  int rc = XHIST_OK;
+  for (int d = 0; d < in.n_arrays() && rc == XHIST_OK; ++d) {
+    const xhist_array& a = in.array(d);
+    const int es = dtype_size(a.dtype);
+    if (scratch_malloc(&scratch[d], (size_t)n_rows * n_cols * es, stream) != hipSuccess) {
+      (void)hipGetLastError();
+      rc = fail(XHIST_ERR_NOMEM, "allocation of %lld bytes of gather scratch failed", (long long)n_rows * n_cols * es);
+      break;
     }
-    return XHIST_OK;
-  }
-
-  int block_threads, grid_blocks, force_global, force_generic, lds_copies, profile, partition, lanes, arith_pref, slices_pref, fused_pref, pack_pref, arith32_pref;
-  {
-    std::lock_guard<std::mutex> lk(p->mu);
-    block_threads = p->block_threads; grid_blocks = p->grid_blocks; force_global = p->force_global;
-    force_generic = p->force_generic; lds_copies = p->lds_copies; profile = p->profile; partition = p->partition;
-    lanes = p->lanes; arith_pref = p->arith_pref; slices_pref = p->slices_pref; fused_pref = p->fused_pref;
-    pack_pref = p->pack_pref;
-    arith32_pref = p->arith32_pref;
-  }
-
-  // ---- many short rows / leading-axis reductions: one row per lane (xhist_lanes.hip.h) --------
-  if (lanes >= 0 && !force_generic && !force_global && !two) {
-    const int rc = execute_lanes(p, samples, weights, n_rows, n_cols, out, accumulate, stream, lanes > 0, profile);
-    if (rc != XHIST_ERR_UNSUPPORTED) return rc;  // UNSUPPORTED = not this shape, fall through
-  }
-  // (the output is zeroed further down, once the launch geometry says whether it has to be at all)
-
-  // ---- a few rows that are the contiguous direction, too many bins for the row-per-lane kernels ----------------
-  // (the columns of an (n, K) table histogrammed over its leading axis with thousands of bins): every other kernel
-  // would walk them with a column stride of K elements — the generic family at ~1 TB/s, memory-side atomics at 0.1
-  // beyond LDS.  Gather the rows into dense scratch first (one pass, read + write) and run the vector kernels on that:
-  // 25 x 10^6 x 4 float32, 5000 bins 0.44 -> see profiles/r02_j_table_columns*.jsonl.
-  if (!force_generic && !two && n_rows >= 1 && n_rows <= 64 && n_cols >= 4096) {
-    bool table = true;
-    for (int d = 0; d <= D && table; ++d) {
-      if (d == D && !weighted) break;
-      const xhist_array& a = d < D ? samples[d] : *weights;
-      table = a.inner_rows == 0 && a.row_stride == 1 && a.col_stride >= n_rows && a.col_stride > 1 &&
-              ((uintptr_t)a.data % (size_t)dtype_size(a.dtype)) == 0;
+    const int grid = (int)std::min<int64_t>((n_cols + 255) / 256, (int64_t)p->cus * 16);
+    // whole tables with rows of whole 16-byte units: tiled through LDS (256 rows x (k + 1) elements)
+    const size_t tile_lds = (size_t)256 * (n_rows + 1) * es;
+    if (a.col_stride == n_rows && ((int64_t)n_rows * es) % 16 == 0 && ((uintptr_t)a.data % 16) == 0 && es >= 4 && tile_lds <= 64 * 1024) {
+      const int tgrid = (int)std::min<int64_t>((n_cols + 255) / 256, (int64_t)p->cus * (int64_t)std::max<size_t>(1, (160 * 1024) / tile_lds));
+      if (es == 8) hipLaunchKernelGGL(gather_rows_tiled<uint64_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint64_t*)a.data, (int)n_rows, n_cols, (uint64_t*)scratch[d]);
+      else hipLaunchKernelGGL(gather_rows_tiled<uint32_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint32_t*)a.data, (int)n_rows, n_cols, (uint32_t*)scratch[d]);
+    } else
+    switch (es) {
+      case 8: hipLaunchKernelGGL(gather_rows<uint64_t>, dim3(grid), dim3(256), 0, stream, (const uint64_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint64_t*)scratch[d]); break;
+      case 4: hipLaunchKernelGGL(gather_rows<uint32_t>, dim3(grid), dim3(256), 0, stream, (const uint32_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint32_t*)scratch[d]); break;
+      case 2: hipLaunchKernelGGL(gather_rows<uint16_t>, dim3(grid), dim3(256), 0, stream, (const uint16_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint16_t*)scratch[d]); break;
+      default: hipLaunchKernelGGL(gather_rows<uint8_t>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint8_t*)scratch[d]); break;
     }
-    // (up to four 8-byte columns with a histogram that fits LDS: the strided walk of the generic family is as fast — 25 x 10^6 x 4
-    //  float64 + weights, 5000 bins: 0.50 ms against 0.87 with the gather; every other measured shape gains 1.3-9 x)
-    if (table && n_rows <= 4 && dtype_size(samples[0].dtype) == 8 && p->n_bins * (weighted ? 8 : 4) <= (int64_t)96 * 1024) table = false;
-    if (table) {
-      void* scratch[kMaxDims + 1] = {nullptr};
-      xhist_array dense[kMaxDims], dense_w;
-      int rc = XHIST_OK;
-      for (int d = 0; d <= D && rc == XHIST_OK; ++d) {
-        if (d == D && !weighted) break;
-        const xhist_array& a = d < D ? samples[d] : *weights;
-        const int es = dtype_size(a.dtype);
-        if (scratch_malloc(&scratch[d], (size_t)n_rows * n_cols * es, stream) != hipSuccess) {
-          (void)hipGetLastError();
-          rc = fail(XHIST_ERR_NOMEM, "allocation of %lld bytes of gather scratch failed", (long long)n_rows * n_cols * es);
-          break;
-        }
-        const int grid = (int)std::min<int64_t>((n_cols + 255) / 256, (int64_t)p->cus * 16);
-        // whole tables with rows of whole 16-byte units: tiled through LDS (256 rows x (k + 1) elements)
-        const size_t tile_lds = (size_t)256 * (n_rows + 1) * es;
-        if (a.col_stride == n_rows && ((int64_t)n_rows * es) % 16 == 0 && ((uintptr_t)a.data % 16) == 0 && es >= 4 && tile_lds <= 64 * 1024) {
-          const int tgrid = (int)std::min<int64_t>((n_cols + 255) / 256, (int64_t)p->cus * (int64_t)std::max<size_t>(1, (160 * 1024) / tile_lds));
-          if (es == 8) hipLaunchKernelGGL(gather_rows_tiled<uint64_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint64_t*)a.data, (int)n_rows, n_cols, (uint64_t*)scratch[d]);
-          else hipLaunchKernelGGL(gather_rows_tiled<uint32_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint32_t*)a.data, (int)n_rows, n_cols, (uint32_t*)scratch[d]);
-        } else
-        switch (es) {
-          case 8: hipLaunchKernelGGL(gather_rows<uint64_t>, dim3(grid), dim3(256), 0, stream, (const uint64_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint64_t*)scratch[d]); break;
-          case 4: hipLaunchKernelGGL(gather_rows<uint32_t>, dim3(grid), dim3(256), 0, stream, (const uint32_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint32_t*)scratch[d]); break;
-          case 2: hipLaunchKernelGGL(gather_rows<uint16_t>, dim3(grid), dim3(256), 0, stream, (const uint16_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint16_t*)scratch[d]); break;
-          default: hipLaunchKernelGGL(gather_rows<uint8_t>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint8_t*)scratch[d]); break;
-        }
-        if (hipGetLastError() != hipSuccess) rc = fail(XHIST_ERR_HIP, "gather_rows launch failed");
-        xhist_array v = a;
-        v.data = scratch[d];
-        v.row_stride = n_cols;
-        v.col_stride = 1;
-        if (d < D) dense[d] = v; else dense_w = v;
-      }
-      if (rc == XHIST_OK) rc = execute_device(p, dense, weighted ? &dense_w : nullptr, n_rows, n_cols, out, accumulate, stream);
-      for (auto* sc : scratch)
-        if (sc) (void)scratch_free(sc, stream);
-      return rc;
-    }
+    if (hipGetLastError() != hipSuccess) rc = fail(XHIST_ERR_HIP, "gather_rows launch failed");
+    dense[d] = a;
+    dense[d].data = scratch[d];
+    dense[d].row_stride = n_cols;
+    dense[d].col_stride = 1;
   }
+  if (rc == XHIST_OK) rc = execute_device(p, dense, in.weighted ? &dense[in.D] : nullptr, n_rows, n_cols, out, accumulate, stream);
+  for (auto* sc : scratch)
+    if (sc) (void)scratch_free(sc, stream);
+  return rc;
+}
 
-  // ---- family: fast (vector loads, homogeneous f64/f32) or generic --------------------------
+// Where the histogram lives for a table footprint of `tbytes`:
+//   lds:    replicated sub-histograms in LDS (one copy per lane bank), uint32 / float64
+//   packed: unweighted vector family only, uint16 counters packed two per word (exact, see kernel)
+//   global: device-scope atomics straight into the output
+// padded_bins: hist_fast's PADDED layout (the float32 arithmetic digitize of one input).
+struct Placement {
+  int hist = kHistGlobal;
+  int cl2 = 0;  // log2 of the LDS copies
+  size_t hist_bytes = 0;
+};
+static Placement place_histogram(const xhist_plan* p, const PlanKnobs& kn, const Inputs& in, size_t tbytes, bool vector_family,
+                                 bool padded_bins) {
+  Placement pl;
   const size_t lds_cap = p->lds_max;
-  const int sdt = samples[0].dtype;
-  const int wdt = weighted ? weights->dtype : -1;
-  int vec = 1;
-  const bool float_samples = sdt == XHIST_F64 || sdt == XHIST_F32;
+  if (kn.force_global || tbytes + 1024 > lds_cap || p->n_bins >= ((int64_t)1 << 24)) return pl;
+  const bool weighted = in.weighted;
+  const int acc_size = (weighted ? 8 : 4) * (in.two ? 2 : 1);  // two weights: two replicated histograms side by side
+  const int max_cl2 = weighted ? 4 : 5;
+  // replication is only worth LDS that small workgroups can share; unweighted 4-byte samples
+  // issue twice the LDS atomics per byte streamed and gain 5 % from more copies (1-D, 500-2000 bins)
+  const size_t soft = (!weighted && in.D == 1 && dtype_size(in.samples[0].dtype) <= 4 ? 64 : 24) * 1024;
+  int cl2 = max_cl2;
+  if (kn.lds_copies) { cl2 = 0; while ((1 << cl2) < kn.lds_copies) ++cl2; cl2 = std::min(cl2, max_cl2); }
+  // + 32 trash slots; the padded layout of the float32 arithmetic digitize (one input): a bin in front and one behind instead
+  // (2 x max(1, 32 >> c) bins of 2^c copies: 64 slots for every c <= 5)
+  auto bytes_at = [&](int c) { return (((size_t)p->n_bins << c) + (padded_bins ? (size_t)std::max(64, 2 << c) : 32)) * (size_t)acc_size; };
+  if (!kn.lds_copies) while (cl2 > 0 && bytes_at(cl2) > soft) --cl2;
+  // short rows: a workgroup zeroes and reads back every copy, which must stay small next to the
+  // samples it bins (10^5 rows x 1000 f32, 50 bins: 32 copies 0.162 ms, 4 copies 0.096 ms)
+  if (!kn.lds_copies) {
+    int64_t sb = 0;
+    for (int d = 0; d < in.D; ++d) sb += dtype_size(in.samples[d].dtype);
+    if (weighted) sb += dtype_size(in.weights->dtype);
+    const double wgs = (double)std::max<int64_t>(in.n_rows, (int64_t)p->cus * 8);
+    const double per_wg_bytes = (double)in.n_rows * (double)in.n_cols * (double)sb / wgs;
+    while (cl2 > 0 && (double)bytes_at(cl2) > per_wg_bytes / 4) --cl2;
+  }
+  while (cl2 > 0 && tbytes + bytes_at(cl2) > lds_cap) --cl2;
+  if (tbytes + bytes_at(cl2) <= lds_cap) {
+    pl.hist = kHistLds;
+    pl.cl2 = cl2;
+    pl.hist_bytes = bytes_at(cl2);
+  } else if (vector_family && in.float_samples && !weighted && tbytes + (((size_t)p->n_bins + 1) / 2 + 32) * 4 <= lds_cap) {
+    pl.hist = kHistPacked;
+    pl.hist_bytes = (((size_t)p->n_bins + 1) / 2 + 32) * 4;
+  }
+  return pl;
+}
+
+// What the streaming launch runs: the kernel, its family and digitize, and where the histogram lives.
+struct StreamChoice {
+  kernel_fn fn = nullptr;
+  bool fast = false;   // the vector family (else the generic one)
+  bool mixed = false;  // ... in its mixed-dtype variant
+  bool use_f32 = false;  // float32-threshold tables
+  bool tables_in_lds = false;
+  bool long_tiles = false;
+  int vec = 1, scan = 0;
+  int hist = kHistGlobal, cl2 = 0;
+  const TableSet* tset = nullptr;
+  size_t table_bytes = 0, hist_bytes = 0, lds_bytes = 0;
+  int n_slices = 1;  // bin slices (choose_slices): launches, and the bins of each
+  int64_t slice_bins = 0;
+};
+
+// ---- family: fast (vector loads, homogeneous f64/f32) or generic --------------------------
+// Two weights: XHIST_ERR_UNSUPPORTED before anything is touched when the vector family with an LDS histogram cannot take them.
+static int choose_streaming(const xhist_plan* p, const PlanKnobs& kn, const Inputs& in, StreamChoice& sc) {
+  const int D = in.D, sdt = in.sdt, wdt = in.wdt;
+  const bool weighted = in.weighted, two = in.two, float_samples = in.float_samples;
+  const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  const size_t lds_cap = p->lds_max;
   const bool small_samples = sdt == XHIST_I32 || sdt == XHIST_I64 || sdt == XHIST_I16 || sdt == XHIST_U8 || sdt == XHIST_F16;
   // the exact int64 domain has vector kernels for one int64 / datetime64 input
   const bool i64dom = p->cmp == XHIST_CMP_I64 && !p->uns && sdt == XHIST_I64 && D == 1 && (wdt == -1 || wdt == XHIST_F64);
-  bool fast_ok = !force_generic && (p->cmp == XHIST_CMP_F64 || i64dom) && p->n_bins < ((int64_t)1 << 31) &&
+  bool fast_ok = !kn.force_generic && (p->cmp == XHIST_CMP_F64 || i64dom) && p->n_bins < ((int64_t)1 << 31) &&
                  ((float_samples && D <= 3 && (wdt == -1 || wdt == XHIST_F64 || wdt == XHIST_F32)) ||
                   (small_samples && D == 1 && (wdt == -1 || wdt == XHIST_F64)));
   if (fast_ok) {
     // unit column stride is all the vector family needs: gfx950 vector loads take any
     // element-aligned address (rows of 365 or 3650 samples stay on 16-byte loads)
     for (int d = 0; d < D && fast_ok; ++d) {
-      const xhist_array& a = samples[d];
+      const xhist_array& a = in.samples[d];
       fast_ok = a.dtype == sdt && a.col_stride == 1 && ((uintptr_t)a.data % (size_t)dtype_size(sdt) == 0);
     }
-    if (fast_ok && weighted) fast_ok = weights->col_stride == 1 && ((uintptr_t)weights->data % (size_t)dtype_size(wdt) == 0);
-  }
-
-  if (fast_ok && !i64dom) {  // development switch: send homogeneous float inputs through the mixed-dtype kernels (A/B of the load path)
-    static const bool force_mixed = [] { const char* e = getenv("XHIST_AMD_FORCE_MIXED"); return e && e[0] == '1'; }();
-    if (force_mixed) fast_ok = false;
+    if (fast_ok && weighted) fast_ok = in.weights->col_stride == 1 && ((uintptr_t)in.weights->data % (size_t)dtype_size(wdt) == 0);
   }
   // Mixtures the homogeneous vector kernels do not take — float32 next to float64, integers in a joint histogram,
   // integer / bool / half weights — with unit column strides and the float64 compare domain: the MIXED variant of the
   // vector kernels (four elements per load in each array's own dtype, consumed as float64).  LDS histograms only;
   // beyond LDS the Python layer converts such inputs to float64 first (core._promote_for_big_histograms).
   bool mixed_ok = false;
-  if (!fast_ok && !force_generic && !two && p->cmp == XHIST_CMP_F64 && D <= 3 && p->n_bins < ((int64_t)1 << 24) && !p->huge) {
+  if (!fast_ok && !kn.force_generic && !two && p->cmp == XHIST_CMP_F64 && D <= 3 && p->n_bins < ((int64_t)1 << 24) && !p->huge) {
     // element-aligned, and for 1- / 2-byte elements every row dword-aligned (their four-element loads are one dword / two)
     auto vector_loadable = [&](const xhist_array& a) {
       const size_t es = (size_t)dtype_size(a.dtype), al = es < 4 ? 4 : es;
@@ -1053,67 +1098,23 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
       return (a.row_stride * es) % 4 == 0 && (a.outer_stride * es) % 4 == 0;
     };
     mixed_ok = true;
-    for (int d = 0; d < D && mixed_ok; ++d) mixed_ok = vector_loadable(samples[d]);
-    if (mixed_ok && weighted) mixed_ok = vector_loadable(*weights);
+    for (int d = 0; d < in.n_arrays() && mixed_ok; ++d) mixed_ok = vector_loadable(in.array(d));
     // measured (tools/mixtures.py, 2 x 10^8 samples, against the generic family): float32 + int32 weights 1.06 -> 0.30 ms,
     // int32 x int32 1.17 -> 0.40, uint8 x float32 1.15 -> 0.37, float32 x float64 0.91 -> 0.46
   }
 
   // Two attempts: the vector family with its tables, then (if it has no kernel for this
   // combination, or its tables do not fit LDS) the generic family with the native tables.
-  bool fast = false, use_f32 = false, tables_fit = false, lds_hist = false, tables_in_lds = false;
-  int scan = 0, hist = kHistGlobal, cl2 = 0;
+  // Every alternative digitize below asks place_histogram where the histogram would live with it, and takes it or leaves it.
+  bool fast = false, mixed = false, use_f32 = false, tables_fit = false, tables_in_lds = false;
+  int scan = 0, vec = 1;
   const TableSet* tset = nullptr;
-  size_t table_bytes = 0, hist_bytes = 0, lds_bytes = 0;
+  size_t table_bytes = 0;
+  Placement pl;
   kernel_fn fn = nullptr;
-  const int acc_size = (weighted ? 8 : 4) * (two ? 2 : 1);  // two weights: two replicated histograms side by side
-  const int max_cl2 = weighted ? 4 : 5;
-  // histogram placement for a given table footprint:
-  //   lds:    replicated sub-histograms in LDS (one copy per lane bank), uint32 / float64
-  //   packed: unweighted vector family only, uint16 counters packed two per word (exact, see kernel)
-  //   global: device-scope atomics straight into the output
-  bool padded_bins = false;  // (hist_fast's PADDED layout; set before place() is asked about it)
-  auto place = [&](size_t tbytes, bool vector_family) {
-    hist = kHistGlobal;
-    cl2 = 0;
-    hist_bytes = 0;
-    if (!force_global && tbytes + 1024 <= lds_cap && p->n_bins < ((int64_t)1 << 24)) {
-      // replication is only worth LDS that small workgroups can share; unweighted 4-byte samples
-      // issue twice the LDS atomics per byte streamed and gain 5 % from more copies (1-D, 500-2000 bins)
-      const size_t soft = (!weighted && D == 1 && dtype_size(samples[0].dtype) <= 4 ? 64 : 24) * 1024;
-      cl2 = max_cl2;
-      if (lds_copies) { cl2 = 0; while ((1 << cl2) < lds_copies) ++cl2; cl2 = std::min(cl2, max_cl2); }
-      // + 32 trash slots; the padded layout of the float32 arithmetic digitize (one input): a bin in front and one behind instead
-      // (2 x max(1, 32 >> c) bins of 2^c copies: 64 slots for every c <= 5)
-      auto bytes_at = [&](int c) { return (((size_t)p->n_bins << c) + (padded_bins ? (size_t)std::max(64, 2 << c) : 32)) * (size_t)acc_size; };
-      if (!lds_copies) while (cl2 > 0 && bytes_at(cl2) > soft) --cl2;
-      // short rows: a workgroup zeroes and reads back every copy, which must stay small next to the
-      // samples it bins (10^5 rows x 1000 f32, 50 bins: 32 copies 0.162 ms, 4 copies 0.096 ms)
-      if (!lds_copies) {
-        int64_t sb = 0;
-        for (int d = 0; d < D; ++d) sb += dtype_size(samples[d].dtype);
-        if (weighted) sb += dtype_size(weights->dtype);
-        const double wgs = (double)std::max<int64_t>(n_rows, (int64_t)p->cus * 8);
-        const double per_wg_bytes = (double)n_rows * (double)n_cols * (double)sb / wgs;
-        while (cl2 > 0 && (double)bytes_at(cl2) > per_wg_bytes / 4) --cl2;
-      }
-      while (cl2 > 0 && tbytes + bytes_at(cl2) > lds_cap) --cl2;
-      if (tbytes + bytes_at(cl2) <= lds_cap) {
-        hist = kHistLds;
-        hist_bytes = bytes_at(cl2);
-      } else if (vector_family && float_samples && !weighted && tbytes + (((size_t)p->n_bins + 1) / 2 + 32) * 4 <= lds_cap) {
-        hist = kHistPacked;
-        cl2 = 0;
-        hist_bytes = (((size_t)p->n_bins + 1) / 2 + 32) * 4;
-      }
-    }
-    if (hist == kHistGlobal) { cl2 = 0; hist_bytes = 0; }
-  };
-  bool mixed = false;
   for (int attempt = (fast_ok || mixed_ok) ? 0 : 1; attempt < 2 && !fn; ++attempt) {
     fast = attempt == 0;
     mixed = fast && !fast_ok;
-    padded_bins = false;
     // float32 samples are digitized against the float32-threshold tables (exact, see Dom<2>)
     use_f32 = fast && !mixed && sdt == XHIST_F32 && p->ts[1][0].blob != nullptr;  // (mixed dtypes are consumed as float64)
     scan = 0;
@@ -1125,7 +1126,7 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
     }
     table_bytes = (size_t)tset->words * 8;
     tables_fit = table_bytes + 1024 <= lds_cap && !(fast && p->huge);  // no bucket tables: not for the vector family
-    if (tables_fit || !fast) place(table_bytes, fast);
+    if (tables_fit || !fast) pl = place_histogram(p, kn, in, table_bytes, fast, false);
     // Arithmetic edges (bins=int, np.linspace): when the edge tables are what keeps the histogram
     // out of LDS — or do not fit LDS at all — digitize without tables (count_le_arith): 30000
     // uniform bins stay on the streaming kernels instead of 43 ms/10^9 samples of global atomics.
@@ -1135,75 +1136,64 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
     // every table-free launch — and on one box it beat the one-edge-per-bucket tables for float64 samples too, 1.33 -> 1.22 ms
     // for the unweighted headline; on another the two were level (1.19 / 1.21), 10^6 samples went 8.8 -> 12.7 us and a 20^3
     // float64 histogram 1.97 -> 2.06 ms: the rule stays as it was.  profiles/r03_ar_arith_ab.txt)
-    if (fast && (float_samples || mixed) && p->arith && arith_pref >= 0 &&
-        (!tables_fit || hist == kHistGlobal || scan == 0 || scan >= 3 || arith_pref > 0)) {
-      const int h0 = hist, c0 = cl2;
-      const size_t b0 = hist_bytes;
-      place(0, true);
-      if (hist != kHistGlobal || !tables_fit || arith_pref > 0) {
+    if (fast && (float_samples || mixed) && p->arith && kn.arith_pref >= 0 &&
+        (!tables_fit || pl.hist == kHistGlobal || scan == 0 || scan >= 3 || kn.arith_pref > 0)) {
+      const Placement alt = place_histogram(p, kn, in, 0, true, false);
+      if (alt.hist != kHistGlobal || !tables_fit || kn.arith_pref > 0) {
+        pl = alt;
         scan = kScanArith;
         use_f32 = false;
         tset = &p->ts[0][0];  // float64-domain DimTable (e_0, e_last, step); its tables are not read
         table_bytes = 0;
         tables_fit = true;
-      } else {
-        hist = h0; cl2 = c0; hist_bytes = b0;
       }
     }
     // float32 samples on arithmetic edges with an LDS histogram: the bin from float32 arithmetic, no table at all
     // (bin_arith32_fast: 7-9 vector instructions and one LDS operation per sample against 12 and three for the threshold
     // tables — BASELINE C4, whose dask-chunk-sized calls run while the clock of a just-woken GPU dips)
     // ("arith" = 1 asks for the float64 arithmetic by name and keeps it; "arith" = -1 rules out both)
-    if (fast && !mixed && !two && !i64dom && sdt == XHIST_F32 && p->arith32 && arith32_pref >= 0 && arith_pref >= 0 &&
-        (arith32_pref > 0 || (arith_pref == 0 && (scan == 1 || scan == 2 || scan == kScanArith)))) {
-      const int h0 = hist, c0 = cl2;
-      const size_t b0 = hist_bytes;
-      padded_bins = D == 1;
-      place(0, true);
+    if (fast && !mixed && !two && !i64dom && sdt == XHIST_F32 && p->arith32 && kn.arith32_pref >= 0 && kn.arith_pref >= 0 &&
+        (kn.arith32_pref > 0 || (kn.arith_pref == 0 && (scan == 1 || scan == 2 || scan == kScanArith)))) {
+      const Placement alt = place_histogram(p, kn, in, 0, true, /*padded_bins=*/D == 1);
       // (no second try without the padding: the kernel's PADDED layout is a compile-time property of <kScanArith32, D == 1, LDS>,
       //  so a one-input histogram that fits LDS only unpadded — n_bins within 64 of the cap — keeps the digitize it had)
-      if (hist == kHistLds) {
+      if (alt.hist == kHistLds) {
+        pl = alt;
         scan = kScanArith32;
         use_f32 = false;
         tset = &p->ts[0][0];  // float64-domain DimTable (e_0, e_last, step, a32_*); its tables are not read
         table_bytes = 0;
         tables_fit = true;
-      } else {
-        padded_bins = false;
-        hist = h0; cl2 = c0; hist_bytes = b0;
       }
     }
     // Non-uniform edges, float64 samples: packed 16-byte bucket entries (count_le_pack) — one LDS read per sample and
     // dimension instead of two dependent ones — where the histogram stays in LDS with them.  Measured for joint histograms
     // (C3: see DESIGN 4); 1-D histograms keep the two-level tables unless "pack" = 1.
     const int pk_np = sdt == XHIST_F64 ? p->pk_np : (sdt == XHIST_F32 && use_f32 ? p->pk32_np : 0);
-    if (fast && !mixed && !two && !i64dom && pk_np && pack_pref >= 0 && scan != kScanArith && scan != kScanArith32 && tables_fit &&
-        (scan == 0 || scan >= 2 || pack_pref > 0) && (D >= 2 || scan == 0 || (sdt == XHIST_F32 && !weighted) || pack_pref > 0)) {
+    if (fast && !mixed && !two && !i64dom && pk_np && kn.pack_pref >= 0 && scan != kScanArith && scan != kScanArith32 && tables_fit &&
+        (scan == 0 || scan >= 2 || kn.pack_pref > 0) && (D >= 2 || scan == 0 || (sdt == XHIST_F32 && !weighted) || kn.pack_pref > 0)) {
       // (scan 0: the alternative is a binary search; 1-D: measured level for float64 samples and for weighted float32 ones,
       //  0.74 -> 0.85 of 8 TB/s for float32 counts — twice the table reads per byte streamed: profiles/r04_h_*)
       const TableSet& pk = sdt == XHIST_F64 ? p->ts_pk : p->ts_pk32;
-      const int h0 = hist, c0 = cl2;
-      const size_t b0 = hist_bytes, tb = (size_t)pk.words * 8;
+      const size_t tb = (size_t)pk.words * 8;
       if (tb + 1024 <= lds_cap) {
-        place(tb, true);
-        if ((hist == kHistLds || hist == kHistPacked) && (hist == h0 || pack_pref > 0)) {
+        const Placement alt = place_histogram(p, kn, in, tb, true, false);
+        if ((alt.hist == kHistLds || alt.hist == kHistPacked) && (alt.hist == pl.hist || kn.pack_pref > 0)) {
+          pl = alt;
           scan = pk_np == 2 ? kScanPack2 : (pk_np == 3 ? kScanPack3 : kScanPackG);
           tset = &pk;
           table_bytes = tb;
-        } else {
-          hist = h0; cl2 = c0; hist_bytes = b0;
         }
       }
     }
     if (fast && !tables_fit) continue;  // the vector family keeps its tables in LDS
-    if (mixed && hist != kHistLds) continue;  // (packed / memory-side histograms: the generic family)
-    lds_hist = hist == kHistLds;
+    if (mixed && pl.hist != kHistLds) continue;  // (packed / memory-side histograms: the generic family)
     tables_in_lds = tables_fit;
-    lds_bytes = (tables_in_lds ? table_bytes : 0) + hist_bytes;
     // (scan 1..4: linear in-bucket count, no bucket holds more than 4 edges — always for uniform bins)
     if (two) {  // one attempt only: the vector family, LDS histograms, table digitize with <= 2 edges per bucket
-      if (!fast || hist != kHistLds || (scan != 1 && scan != 2) || !float_samples || weights2->dtype != wdt ||
-          weights2->col_stride != 1 || ((uintptr_t)weights2->data % (size_t)dtype_size(wdt)) != 0)
+      const xhist_array* w2 = in.weights2;
+      if (!fast || pl.hist != kHistLds || (scan != 1 && scan != 2) || !float_samples || w2->dtype != wdt ||
+          w2->col_stride != 1 || ((uintptr_t)w2->data % (size_t)dtype_size(wdt)) != 0)
         return XHIST_ERR_UNSUPPORTED;
       fn = fast_kernel_two_weights(sdt, wdt, D, scan, &vec);
       if (!fn) return XHIST_ERR_UNSUPPORTED;
@@ -1214,16 +1204,18 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
       vec = 4;
       continue;  // (no kernel: the loop goes on to the generic family)
     }
-    fn = fast ? (i64dom ? int64_domain_kernel(wdt, D, scan, hist, &vec) : fast_kernel(sdt, wdt, D, scan, hist, &vec))
-              : generic_kernel(p->cmp, weighted, lds_hist, tables_in_lds);
+    fn = fast ? (i64dom ? int64_domain_kernel(wdt, D, scan, pl.hist, &vec) : fast_kernel(sdt, wdt, D, scan, pl.hist, &vec))
+              : generic_kernel(p->cmp, weighted, pl.hist == kHistLds, tables_in_lds);
   }
+  if (!fn) return fail(XHIST_ERR_HIP, "internal: no kernel for this combination");
   // One input without weights, long rows: twice the samples per lane and tile — the 128 bytes per lane in flight that the
   // weighted kernel has with its two streams.  float64, one row of 10^9 samples, 100 bins (the headline's 8 B/sample variant):
   // 1.20-1.24 -> 1.14-1.16 ms (0.83 -> 0.86-0.88 of 8 TB/s); float32, BASELINE C4 (456 / 3650 rows of 1 036 800): 0.2872 ->
   // 0.2838 ms (0.823 -> 0.833) and 2.228 -> 2.208 ms (0.849 -> 0.857), profiles/r03_u8_unroll8.txt.  Short rows keep their tiles
   // (the geometry rules further down were fitted to them); float64 with many rows was not measured and stays as it was.
   bool long_tiles = false;
-  if (fn && fast && !mixed && !two && !i64dom && !weighted && D == 1 && hist == kHistLds && (scan == 1 || scan == 2 || scan == kScanArith32) && !block_threads && !grid_blocks) {
+  if (fast && !mixed && !two && !i64dom && !weighted && D == 1 && pl.hist == kHistLds && (scan == 1 || scan == 2 || scan == kScanArith32) &&
+      !kn.block_threads && !kn.grid_blocks) {
     kernel_fn lf = nullptr;
     // (exactly the two shape classes that were measured: one float32 row of 3*10^7 ... 10^9 samples came out 4-10 % SLOWER
     // with the long tiles in tools/size_ramp.py — its one-workgroup-per-CU geometry already has 64 KiB per CU in flight)
@@ -1234,238 +1226,277 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
       long_tiles = true;
     }
   }
-  if (two && !accumulate) {
-    if (int zrc = zero_output(out, out_elems, stream)) return zrc;
-    if (int zrc = zero_output(out2, out_elems, stream)) return zrc;
+  sc.fn = fn;
+  sc.fast = fast;
+  sc.mixed = mixed;
+  sc.use_f32 = use_f32;
+  sc.tables_in_lds = tables_in_lds;
+  sc.long_tiles = long_tiles;
+  sc.vec = fast ? vec : 1;
+  sc.scan = scan;
+  sc.hist = pl.hist;
+  sc.cl2 = pl.cl2;
+  sc.tset = tset;
+  sc.table_bytes = table_bytes;
+  sc.hist_bytes = pl.hist_bytes;
+  sc.lds_bytes = (tables_in_lds ? table_bytes : 0) + pl.hist_bytes;
+  sc.n_slices = 1;
+  sc.slice_bins = p->n_bins;
+  return XHIST_OK;
+}
+
+// ---- partitions of the partitioned mode (execute_partitioned_rows; choose_slices prices it) ---------------------------
+// 2^14 float64 or 2^15 uint32 bins = 128 KiB of LDS per partition, unless that leaves only a handful:
+// A handful of partitions is slower than a few dozen: the routing pass ranks a tile's records with ONE returning LDS
+// counter per partition, and a tile's 8192 adds on two or three addresses serialise (a tile lies in one row, so rows
+// that share a pass do not help).  5*10^8 samples, ms: float32 pairs + weights 160 x 160 bins, 2 partitions -> 13:
+// 3.04 -> 2.32; 200 x 200, 3 -> 20: 2.82 -> 2.35; float32 pair counts 300 x 300, 3 -> 22: 2.75 -> 1.58; 400 x 400,
+// 5 -> 20: 2.33 -> 1.60; float64 pair counts 300 x 300 2.78 -> 2.36; 10^5 bins 1-D, 4 -> 25: 2.65 -> 1.53; 12 rows x
+// 200 x 200 float32 weighted, 3 -> 10 per row: 2.89 -> 2.43 (profiles/r03_t_few_partitions.txt).  So the bins are cut
+// finer — down to 2^11 per partition — until a row has 16 partitions ("min_parts" overrides).  float64 samples with
+// float64 weights, whose tiles are half as long, gain nothing (4.10 -> 4.06, 12 rows 4.09 -> 4.34) and keep the big ones.
+struct PartGeom {
+  int shift;        // bins per partition = 1 << shift
+  int64_t n_parts;  // partitions per row
+};
+static PartGeom part_geometry(const xhist_plan* p, const PlanKnobs& kn, const Inputs& in) {
+  PartGeom g;
+  g.shift = in.weighted ? 14 : 15;
+  g.n_parts = (p->n_bins + ((int64_t)1 << g.shift) - 1) >> g.shift;
+  if (in.weighted && in.sdt == XHIST_F64 && in.wdt == XHIST_F64 && !kn.min_parts) return g;
+  const bool rows_share = in.n_rows > 1 && in.n_cols < ((int64_t)1 << 27);  // (uniform_rows in execute_partitioned_rows: several rows per pass)
+  const int64_t want_parts = kn.min_parts ? kn.min_parts : 16;
+  while (g.shift > 11 && g.n_parts < want_parts) {
+    const int64_t finer = (p->n_bins + ((int64_t)1 << (g.shift - 1)) - 1) >> (g.shift - 1);
+    // rows that fit ONE pass with 8+ partitions each stay in one pass (a pass costs ~0.1 ms beyond its traffic)
+    if (rows_share && g.n_parts >= 8 && in.n_rows * g.n_parts <= 128 && in.n_rows * finer > 128) break;
+    --g.shift;
+    g.n_parts = finer;
   }
-  if (!fn) return fail(XHIST_ERR_HIP, "internal: no kernel for this combination");
-  if (!fast) vec = 1;
-  const DimTable* dims = tset->dim;
+  return g;
+}
 
-  // ---- partitions of the partitioned mode (below; the slice rule prices it) ---------------------------
-  // 2^14 float64 or 2^15 uint32 bins = 128 KiB of LDS per partition, unless that leaves only a handful:
-  // A handful of partitions is slower than a few dozen: the routing pass ranks a tile's records with ONE returning LDS
-  // counter per partition, and a tile's 8192 adds on two or three addresses serialise (a tile lies in one row, so rows
-  // that share a pass do not help).  5*10^8 samples, ms: float32 pairs + weights 160 x 160 bins, 2 partitions -> 13:
-  // 3.04 -> 2.32; 200 x 200, 3 -> 20: 2.82 -> 2.35; float32 pair counts 300 x 300, 3 -> 22: 2.75 -> 1.58; 400 x 400,
-  // 5 -> 20: 2.33 -> 1.60; float64 pair counts 300 x 300 2.78 -> 2.36; 10^5 bins 1-D, 4 -> 25: 2.65 -> 1.53; 12 rows x
-  // 200 x 200 float32 weighted, 3 -> 10 per row: 2.89 -> 2.43 (profiles/r03_t_few_partitions.txt).  So the bins are cut
-  // finer — down to 2^11 per partition — until a row has 16 partitions ("min_parts" overrides).  float64 samples with
-  // float64 weights, whose tiles are half as long, gain nothing (4.10 -> 4.06, 12 rows 4.09 -> 4.34) and keep the big ones.
-  auto part_geometry = [&](int& shift, int64_t& n_parts) {
-    shift = weighted ? 14 : 15;
-    n_parts = (p->n_bins + ((int64_t)1 << shift) - 1) >> shift;
-    if (weighted && sdt == XHIST_F64 && wdt == XHIST_F64 && !p->min_parts) return;
-    const bool rows_share = n_rows > 1 && n_cols < ((int64_t)1 << 27);  // (uniform_rows below: several rows per pass)
-    const int64_t want_parts = p->min_parts ? p->min_parts : 16;
-    while (shift > 11 && n_parts < want_parts) {
-      const int64_t finer = (p->n_bins + ((int64_t)1 << (shift - 1)) - 1) >> (shift - 1);
-      // rows that fit ONE pass with 8+ partitions each stay in one pass (a pass costs ~0.1 ms beyond its traffic)
-      if (rows_share && n_parts >= 8 && n_rows * n_parts <= 128 && n_rows * finer > 128) break;
-      --shift;
-      n_parts = finer;
-    }
-  };
-
-  // ---- a few times the LDS capacity: bin slices ---------------------------------------------------
-  // S launches, each streaming all samples and keeping 1/S of the bins in LDS (hist_fast<SLICED>),
-  // cost S x the streaming time; the partitioned mode below moves B + 2 x record bytes per sample once and needs a few
-  // long rows.  Round 3, 5*10^8 samples, slices | partitioned ms (profiles/r03_t_few_partitions.txt): float32 pairs +
-  // float32 weights S = 2: 1.80 | 2.32, S = 3: 2.67 | 2.35, S = 4: 3.53 | 2.21; float64 pairs + float64 weights S = 2:
-  // 3.47 | 4.03, S = 3: 5.21 | 4.06; float32 pair counts (packed uint16 slices) S = 2: 1.73 | 1.58, S = 3: 2.62 | 1.60;
-  // float64 pair counts S = 2: 2.43 | 2.36, S = 3: 3.69 | 2.38.  (Round 1's rule — written when the partitioned mode took
-  // three passes, 9.3 ms for 200 x 200 weighted bins — kept slices up to S = 3-4.)
-  int n_slices = 1;
-  int64_t slice_bins = p->n_bins;
-  if (fast && float_samples && hist == kHistGlobal && !force_global && !two && slices_pref >= 0 && p->n_bins < ((int64_t)1 << 24) &&
-      (scan == 1 || scan == 2 || scan == kScanArith) && table_bytes + 4096 < lds_cap) {
-    const size_t budget = lds_cap - table_bytes - 2048;
-    const int64_t cap = weighted ? (int64_t)(budget / 8) - 32 : (((int64_t)(budget / 2) - 66) & ~(int64_t)1);
-    const int64_t S = (p->n_bins + cap - 1) / cap;
-    int64_t B = 0;
-    for (int d = 0; d < D; ++d) B += dtype_size(samples[d].dtype);
-    if (weighted) B += dtype_size(weights->dtype);
-    const int64_t rec = 2 + (weighted ? (wdt == XHIST_F32 ? 4 : 8) : 0);  // a record: uint16 code + the weight in its own precision
-    int part_shift = 0;
-    int64_t parts_per_row = 0;
-    part_geometry(part_shift, parts_per_row);
-    const bool part_ok = partition >= 0 && n_rows <= 64 && n_cols >= ((int64_t)1 << 22) && parts_per_row <= kPartMaxParts;
-    // per sample: a slice pass streams B bytes at ~6.5 TB/s (packed uint16 counters: no faster than 5.7 x 10^11 samples
-    // a second); the partitioned mode moves B + 2 x record bytes at ~4.7 TB/s and no faster than 3.3 x 10^11 samples a second
-    const double per_slice = std::max((double)B / 6.5e12, weighted ? 0.0 : 1.0 / 5.7e11);
-    const double per_part = std::max(((double)B + 2.0 * (double)(weighted ? std::min<int64_t>(rec, 8) : rec)) / 4.7e12, 1.0 / 3.3e11);
-    // (+ ~0.1 ms per routing / adding-up pass: rows share a pass while rows x partitions <= 128)
-    const double n_all = (double)n_rows * (double)n_cols;
-    const int64_t rows_per_pass = (n_rows > 1 && n_cols < ((int64_t)1 << 27) && parts_per_row * 2 <= 128) ? std::max<int64_t>(1, 128 / parts_per_row) : 1;
-    const double t_part = n_all * per_part + (double)((n_rows + rows_per_pass - 1) / rows_per_pass) * 1.0e-4;
-    // every slice pass ends with one global atomic per non-empty bin and workgroup (~2 x 10^11 a second for the chip) and costs
-    // ~13 us to launch: 10^7 float64 pairs into 512 x 512 counts, 5 slices 0.377 ms against 0.112 partitioned
-    const double slice_wgs = (double)std::max<int64_t>(p->cus, n_rows);
-    const double slice_bins_each = (double)((p->n_bins + S - 1) / S);
-    const double t_slice_fixed = 13e-6 + slice_wgs * std::min(slice_bins_each, n_all / slice_wgs) / 2.0e11;
-    bool choose = slices_pref > 0 ? S <= 64 : (partition > 0 ? false : (part_ok ? (double)S * (n_all * per_slice + t_slice_fixed) <= t_part : S <= 16));
-    if (choose && slices_pref == 0) {
-      // few samples: S launches cost S x ~13 us before they stream anything, memory-side atomics 2.4-2.7 x 10^10
-      // per second (10^5 samples, 256 x 256 weighted bins: 4 slices 54 us, global atomics 13 us)
-      const double n_tot = (double)n_rows * (double)n_cols;
-      const double t_global = 8e-6 + n_tot / (weighted ? 2.4e10 : 2.7e10);
-      const double t_slices = (double)S * (13e-6 + n_tot * (double)B / 4.0e12);
-      choose = t_slices <= t_global;
-    }
-    if (choose && S >= 1) {
-      const int shist = weighted ? kHistLds : kHistPacked;
-      kernel_fn sfn = fast_kernel_sliced(sdt, wdt, D, scan, shist, &vec);
-      if (sfn) {
-        fn = sfn;
-        hist = shist;
-        cl2 = 0;
-        n_slices = (int)S;
-        slice_bins = ((p->n_bins + S - 1) / S + 1) & ~(int64_t)1;  // even: packed counters pair up inside a slice
-        hist_bytes = weighted ? ((size_t)slice_bins + 32) * 8 : (((size_t)slice_bins + 1) / 2 + 32) * 4;
-        lds_hist = hist == kHistLds;
-        tables_in_lds = true;
-        lds_bytes = table_bytes + hist_bytes;
-      }
-    }
+// ---- a few times the LDS capacity: bin slices ---------------------------------------------------
+// S launches, each streaming all samples and keeping 1/S of the bins in LDS (hist_fast<SLICED>),
+// cost S x the streaming time; the partitioned mode moves B + 2 x record bytes per sample once and needs a few
+// long rows.  Round 3, 5*10^8 samples, slices | partitioned ms (profiles/r03_t_few_partitions.txt): float32 pairs +
+// float32 weights S = 2: 1.80 | 2.32, S = 3: 2.67 | 2.35, S = 4: 3.53 | 2.21; float64 pairs + float64 weights S = 2:
+// 3.47 | 4.03, S = 3: 5.21 | 4.06; float32 pair counts (packed uint16 slices) S = 2: 1.73 | 1.58, S = 3: 2.62 | 1.60;
+// float64 pair counts S = 2: 2.43 | 2.36, S = 3: 3.69 | 2.38.  (Round 1's rule — written when the partitioned mode took
+// three passes, 9.3 ms for 200 x 200 weighted bins — kept slices up to S = 3-4.)
+static void choose_slices(const xhist_plan* p, const PlanKnobs& kn, const Inputs& in, StreamChoice& sc) {
+  const size_t lds_cap = p->lds_max;
+  if (!(sc.fast && in.float_samples && sc.hist == kHistGlobal && !kn.force_global && !in.two && kn.slices_pref >= 0 &&
+        p->n_bins < ((int64_t)1 << 24) && (sc.scan == 1 || sc.scan == 2 || sc.scan == kScanArith) && sc.table_bytes + 4096 < lds_cap))
+    return;
+  const bool weighted = in.weighted;
+  const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  const size_t budget = lds_cap - sc.table_bytes - 2048;
+  const int64_t cap = weighted ? (int64_t)(budget / 8) - 32 : (((int64_t)(budget / 2) - 66) & ~(int64_t)1);
+  const int64_t S = (p->n_bins + cap - 1) / cap;
+  int64_t B = 0;
+  for (int d = 0; d < in.n_arrays(); ++d) B += dtype_size(in.array(d).dtype);
+  const int64_t rec = 2 + (weighted ? (in.wdt == XHIST_F32 ? 4 : 8) : 0);  // a record: uint16 code + the weight in its own precision
+  const PartGeom pg = part_geometry(p, kn, in);
+  const int64_t parts_per_row = pg.n_parts;
+  const bool part_ok = kn.partition >= 0 && n_rows <= 64 && n_cols >= ((int64_t)1 << 22) && parts_per_row <= kPartMaxParts;
+  // per sample: a slice pass streams B bytes at ~6.5 TB/s (packed uint16 counters: no faster than 5.7 x 10^11 samples
+  // a second); the partitioned mode moves B + 2 x record bytes at ~4.7 TB/s and no faster than 3.3 x 10^11 samples a second
+  const double per_slice = std::max((double)B / 6.5e12, weighted ? 0.0 : 1.0 / 5.7e11);
+  const double per_part = std::max(((double)B + 2.0 * (double)(weighted ? std::min<int64_t>(rec, 8) : rec)) / 4.7e12, 1.0 / 3.3e11);
+  // (+ ~0.1 ms per routing / adding-up pass: rows share a pass while rows x partitions <= 128)
+  const double n_all = (double)n_rows * (double)n_cols;
+  const int64_t rows_per_pass = (n_rows > 1 && n_cols < ((int64_t)1 << 27) && parts_per_row * 2 <= 128) ? std::max<int64_t>(1, 128 / parts_per_row) : 1;
+  const double t_part = n_all * per_part + (double)((n_rows + rows_per_pass - 1) / rows_per_pass) * 1.0e-4;
+  // every slice pass ends with one global atomic per non-empty bin and workgroup (~2 x 10^11 a second for the chip) and costs
+  // ~13 us to launch: 10^7 float64 pairs into 512 x 512 counts, 5 slices 0.377 ms against 0.112 partitioned
+  const double slice_wgs = (double)std::max<int64_t>(p->cus, n_rows);
+  const double slice_bins_each = (double)((p->n_bins + S - 1) / S);
+  const double t_slice_fixed = 13e-6 + slice_wgs * std::min(slice_bins_each, n_all / slice_wgs) / 2.0e11;
+  bool choose = kn.slices_pref > 0 ? S <= 64 : (kn.partition > 0 ? false : (part_ok ? (double)S * (n_all * per_slice + t_slice_fixed) <= t_part : S <= 16));
+  if (choose && kn.slices_pref == 0) {
+    // few samples: S launches cost S x ~13 us before they stream anything, memory-side atomics 2.4-2.7 x 10^10
+    // per second (10^5 samples, 256 x 256 weighted bins: 4 slices 54 us, global atomics 13 us)
+    const double t_global = 8e-6 + n_all / (weighted ? 2.4e10 : 2.7e10);
+    const double t_slices = (double)S * (13e-6 + n_all * (double)B / 4.0e12);
+    choose = t_slices <= t_global;
   }
+  if (!choose || S < 1) return;
+  const int shist = weighted ? kHistLds : kHistPacked;
+  kernel_fn sfn = fast_kernel_sliced(in.sdt, in.wdt, in.D, sc.scan, shist, &sc.vec);
+  if (!sfn) return;
+  sc.fn = sfn;
+  sc.hist = shist;
+  sc.cl2 = 0;
+  sc.n_slices = (int)S;
+  sc.slice_bins = ((p->n_bins + S - 1) / S + 1) & ~(int64_t)1;  // even: packed counters pair up inside a slice
+  sc.hist_bytes = weighted ? ((size_t)sc.slice_bins + 32) * 8 : (((size_t)sc.slice_bins + 1) / 2 + 32) * 4;
+  sc.tables_in_lds = true;
+  sc.lds_bytes = sc.table_bytes + sc.hist_bytes;
+}
 
-  // ---- histograms beyond LDS: partitioned multi-pass instead of memory-side atomics ----------
-  // (a few long rows — e.g. one joint histogram per time step — run it row by row)
-  if (fast && float_samples && hist == kHistGlobal && !force_global && partition >= 0 && n_rows <= 64 && !two && n_slices == 1) {
-    int shift = 0;
-    int64_t n_parts = 0;
-    part_geometry(shift, n_parts);
-    const bool big_enough = n_cols >= ((int64_t)1 << 22) || (partition > 0 && n_cols >= 4);  // part_scatter reads whole weight quads
-    if (n_parts <= kPartMaxParts && big_enough && (size_t)(1u << shift) * (weighted ? 8 : 4) + 1024 <= lds_cap) {
-      if (!accumulate)
-        if (int zrc = zero_output(out, out_elems, stream)) return zrc;
-      LaunchRecord rec(p, stream);
-      int rc = XHIST_OK;
-      // the routing pass keeps the digitize tables in LDS next to its sort buffers; where they do not fit (or cost a
-      // workgroup per CU) and the edges are arithmetic (C5: 2 x 1025 np.linspace edges, 32 KiB of tables) it
-      // digitizes table-free
-      int r_scan = scan;
-      const TableSet* r_tset = tset;
-      bool r_f32 = use_f32;
-      const bool can_arith = p->arith && arith_pref >= 0 && n_parts <= 128;
-      const int w_tag = weighted ? wdt : -1;
-      // geometry first: the long tile with the arithmetic digitize where the edges allow it, else with the tables if both
-      // fit the LDS, else the short tile
-      RouteGeom geom = route_geom_for(p, sdt, w_tag, D, can_arith ? kScanArith : scan);
-      if (geom.spl == 8 && (can_arith || scan == kScanArith)) {
-        if (scan != kScanArith) {
-          r_scan = kScanArith;
-          r_tset = &p->ts[0][0];
-          r_f32 = false;
-        }
-      } else {
-        if (geom.spl == 8 && !p->route_spl &&
-            part_route_lds((size_t)tset->words * 8, (int)n_parts, weighted, route_tile(geom.block, 8), geom.block) > p->lds_max)
-          geom.spl = 4;
-        if (can_arith && scan != kScanArith) {
-          const int t4 = route_tile(geom.block, geom.spl);
-          const size_t lds_tab = part_route_lds((size_t)tset->words * 8, (int)n_parts, weighted, t4, geom.block),
-                       lds_notab = part_route_lds(0, (int)n_parts, weighted, t4, geom.block);
-          if (lds_tab > p->lds_max || (size_t)160 * 1024 / lds_notab > (size_t)160 * 1024 / lds_tab) {
-            r_scan = kScanArith;
-            r_tset = &p->ts[0][0];
-            r_f32 = false;
-          }
-        }
+// Row r of every array of a call: the samples into row_s, the weights into row_w.
+static void row_views(const Inputs& in, int64_t r, xhist_array* row_s, xhist_array& row_w) {
+  for (int d = 0; d < in.n_arrays(); ++d) {
+    const xhist_array& a = in.array(d);
+    xhist_array& v = d < in.D ? row_s[d] : row_w;
+    v = a;
+    v.data = const_cast<void*>(advance(a.data, a.dtype, row_offset(r, a.row_stride, a.inner_rows, a.outer_stride)));
+  }
+}
+
+// ---- histograms beyond LDS: partitioned multi-pass instead of memory-side atomics ----------
+// (a few long rows — e.g. one joint histogram per time step — run it row by row)
+// XHIST_ERR_UNSUPPORTED: nothing was launched.  The output may have been zeroed by then; `accumulate` is 1 if so.
+static int execute_partitioned_rows(xhist_plan* p, const PlanKnobs& kn, const Inputs& in, const StreamChoice& sc, void* out,
+                                    int& accumulate, hipStream_t stream) {
+  const int D = in.D, sdt = in.sdt, wdt = in.wdt;
+  const bool weighted = in.weighted;
+  const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  if (!(sc.fast && in.float_samples && sc.hist == kHistGlobal && !kn.force_global && kn.partition >= 0 && n_rows <= 64 && !in.two &&
+        sc.n_slices == 1))
+    return XHIST_ERR_UNSUPPORTED;
+  const PartGeom pg = part_geometry(p, kn, in);
+  const int shift = pg.shift;
+  const int64_t n_parts = pg.n_parts;
+  const bool big_enough = n_cols >= ((int64_t)1 << 22) || (kn.partition > 0 && n_cols >= 4);  // part_scatter reads whole weight quads
+  if (n_parts > kPartMaxParts || !big_enough || (size_t)(1u << shift) * (weighted ? 8 : 4) + 1024 > p->lds_max) return XHIST_ERR_UNSUPPORTED;
+  if (!accumulate) {
+    if (int zrc = zero_output(out, n_rows * p->n_bins, stream)) return zrc;
+    accumulate = 1;  // (for the streaming kernels, should nothing below launch)
+  }
+  LaunchRecord rec(p, stream);
+  int rc = XHIST_OK;
+  // the routing pass keeps the digitize tables in LDS next to its sort buffers; where they do not fit (or cost a
+  // workgroup per CU) and the edges are arithmetic (C5: 2 x 1025 np.linspace edges, 32 KiB of tables) it
+  // digitizes table-free
+  const int scan = sc.scan;
+  const TableSet* tset = sc.tset;
+  int r_scan = scan;
+  const TableSet* r_tset = tset;
+  bool r_f32 = sc.use_f32;
+  const bool can_arith = p->arith && kn.arith_pref >= 0 && n_parts <= 128;
+  const int w_tag = weighted ? wdt : -1;
+  // geometry first: the long tile with the arithmetic digitize where the edges allow it, else with the tables if both
+  // fit the LDS, else the short tile
+  RouteGeom geom = route_geom_for(kn, sdt, w_tag, D, can_arith ? kScanArith : scan);
+  if (geom.spl == 8 && (can_arith || scan == kScanArith)) {
+    if (scan != kScanArith) {
+      r_scan = kScanArith;
+      r_tset = &p->ts[0][0];
+      r_f32 = false;
+    }
+  } else {
+    if (geom.spl == 8 && !kn.route_spl &&
+        part_route_lds((size_t)tset->words * 8, (int)n_parts, weighted, route_tile(geom.block, 8), geom.block) > p->lds_max)
+      geom.spl = 4;
+    if (can_arith && scan != kScanArith) {
+      const int t4 = route_tile(geom.block, geom.spl);
+      const size_t lds_tab = part_route_lds((size_t)tset->words * 8, (int)n_parts, weighted, t4, geom.block),
+                   lds_notab = part_route_lds(0, (int)n_parts, weighted, t4, geom.block);
+      if (lds_tab > p->lds_max || (size_t)160 * 1024 / lds_notab > (size_t)160 * 1024 / lds_tab) {
+        r_scan = kScanArith;
+        r_tset = &p->ts[0][0];
+        r_f32 = false;
       }
-      // non-uniform edges: the packed entries (general variant) instead of a binary search or a 2-4-edge scan per sample and
-      // dimension — the routing pass feels its digitize (5*10^8 float64 pairs into 512 x 512 counts: linspace 2.07 ms, random
-      // edges 2.48, geometric 3.42; profiles/r04_l_*) — where entries and sort buffers fit the LDS together
-      {
-        const int pk_np = sdt == XHIST_F64 ? p->pk_np : (sdt == XHIST_F32 && use_f32 ? p->pk32_np : 0);
-        if (pk_np && pack_pref >= 0 && r_scan != kScanArith && (r_scan == 0 || r_scan >= 2 || pack_pref > 0) && n_parts <= 128) {
-          const TableSet& pk = sdt == XHIST_F64 ? p->ts_pk : p->ts_pk32;
-          int spl = geom.spl;
-          if (spl == 8 && part_route_lds((size_t)pk.words * 8, (int)n_parts, weighted, route_tile(geom.block, 8), geom.block) > p->lds_max) spl = 4;
-          if (part_route_lds((size_t)pk.words * 8, (int)n_parts, weighted, route_tile(geom.block, spl), geom.block) <= p->lds_max &&
-              route_kernel(sdt, w_tag, D, kScanPackG, false, geom.block, spl)) {
-            r_scan = kScanPackG;
-            r_tset = &pk;
-            geom.spl = spl;
-          }
-        }
-      }
-      const int r_block = geom.block, r_tile = route_tile(r_block, geom.spl);
-      // rows that follow each other at one stride go through the routing pass several at a time
-      // (32 x 3*10^7 float32 pairs + weights, 300 x 300 bins: 8.05 -> 6.02 ms; 8 x 6*10^7 float64, 512 x 512: 5.17 -> 4.18;
-      // rows of 5*10^8 samples gain nothing — 8.63 -> 8.95 ms with 128 partitions in flight — and stay one per pass)
-      // a single row of float64 samples with float64 weights below ~1.5 x 10^7 samples: the routing pass's fixed costs (chunk
-      // pool, lists, one partial chunk per workgroup and partition) show, and count + prefix + scatter is 9-15 % faster
-      // (5*10^6: 0.155 | 0.132 ms, 10^7: 0.191 | 0.174, 2*10^7: 0.273 | 0.269: profiles/r03_h_fused_vs_three_pass_mid_sizes.txt);
-      // every other dtype combination is ahead with one pass from 5*10^6 samples on
-      const bool three_pass = fused_pref == 0 && partition == 0 && n_rows == 1 && weighted && sdt == XHIST_F64 && wdt == XHIST_F64 && n_cols < 15000000;
-      const int fused_use = three_pass ? -1 : fused_pref;
-      bool uniform_rows = fused_use >= 0 && n_rows > 1 && n_parts * 2 <= 128 && n_cols < ((int64_t)1 << 27) && (!weighted || weights->inner_rows == 0);
-      for (int d = 0; d < D; ++d) uniform_rows &= samples[d].inner_rows == 0;
-      static const bool batch_off = [] { const char* e = getenv("XHIST_AMD_ROW_BATCH"); return e && *e == '0'; }();
-      if (batch_off) uniform_rows = false;
-      int64_t r = 0;
-      while (uniform_rows && r < n_rows && rc == XHIST_OK) {
-        int rows = (int)std::min<int64_t>(n_rows - r, 128 / n_parts);
-        const size_t tab_bytes = r_scan == kScanArith ? 0 : (size_t)r_tset->words * 8;
-        while (rows > 1 && part_route_lds(tab_bytes, rows * (int)n_parts, weighted, r_tile, r_block) > p->lds_max) --rows;
-        if (rows < 2) break;  // (one row at a time below)
-        xhist_array row_s[XHIST_MAX_DIMS], row_w;
-        for (int d = 0; d < D; ++d) {
-          row_s[d] = samples[d];
-          row_s[d].data = const_cast<void*>(advance(samples[d].data, samples[d].dtype, r * samples[d].row_stride));
-        }
-        if (weighted) {
-          row_w = *weights;
-          row_w.data = const_cast<void*>(advance(weights->data, weights->dtype, r * weights->row_stride));
-        }
-        void* row_out = static_cast<char*>(out) + (size_t)r * p->n_bins * 8;
-        rc = execute_partitioned_fused(p, row_s, weighted ? &row_w : nullptr, n_cols, row_out, stream, sdt, wdt, r_scan, r_f32, *r_tset, shift,
-                                       (int)n_parts, profile, rec, r == 0, r + rows == n_rows, geom, rows);
-        if (rc == XHIST_ERR_UNSUPPORTED) {
-          if (r > 0) rc = fail(XHIST_ERR_HIP, "internal: partitioned mode refused rows from %lld after accepting row 0", (long long)r);
-          else rc = XHIST_OK;  // nothing launched: row by row below
-          break;
-        }
-        r += rows;
-      }
-      for (; r < n_rows && rc == XHIST_OK; ++r) {
-        xhist_array row_s[XHIST_MAX_DIMS], row_w;
-        for (int d = 0; d < D; ++d) {
-          row_s[d] = samples[d];
-          row_s[d].data = const_cast<void*>(advance(samples[d].data, samples[d].dtype,
-                                                    row_offset(r, samples[d].row_stride, samples[d].inner_rows, samples[d].outer_stride)));
-        }
-        if (weighted) {
-          row_w = *weights;
-          row_w.data = const_cast<void*>(advance(weights->data, weights->dtype,
-                                                 row_offset(r, weights->row_stride, weights->inner_rows, weights->outer_stride)));
-        }
-        void* row_out = static_cast<char*>(out) + (size_t)r * p->n_bins * 8;
-        // one routing pass (44 B per C5 sample) where it applies, else count + prefix + scatter (52.5 B); the
-        // choice depends on the plan and the dtypes only, so every row of a call takes the same route
-        rc = fused_use >= 0 ? execute_partitioned_fused(p, row_s, weighted ? &row_w : nullptr, n_cols, row_out, stream, sdt, wdt, r_scan,
-                                                         r_f32, *r_tset, shift, (int)n_parts, profile, rec, r == 0, r == n_rows - 1, geom)
-                             : XHIST_ERR_UNSUPPORTED;
-        if (rc == XHIST_ERR_UNSUPPORTED)
-          rc = execute_partitioned(p, row_s, weighted ? &row_w : nullptr, n_cols, row_out, stream,
-                                   sdt, wdt, scan, use_f32, *tset, shift, (int)n_parts, profile, rec, r == 0, r == n_rows - 1);
-        if (rc == XHIST_ERR_UNSUPPORTED && r > 0) rc = fail(XHIST_ERR_HIP, "internal: partitioned mode refused row %lld after accepting row 0", (long long)r);
-      }
-      if (rc != XHIST_ERR_UNSUPPORTED) return rc;  // UNSUPPORTED (from row 0, nothing launched) = fall through to global atomics
-      accumulate = 1;  // the output has just been zeroed
     }
   }
-  const int kUnroll = long_tiles ? 8 : (mixed ? mixed_unroll(D) : (fast ? unroll_for(D, vec, scan) : 1));
+  // non-uniform edges: the packed entries (general variant) instead of a binary search or a 2-4-edge scan per sample and
+  // dimension — the routing pass feels its digitize (5*10^8 float64 pairs into 512 x 512 counts: linspace 2.07 ms, random
+  // edges 2.48, geometric 3.42; profiles/r04_l_*) — where entries and sort buffers fit the LDS together
+  {
+    const int pk_np = sdt == XHIST_F64 ? p->pk_np : (sdt == XHIST_F32 && sc.use_f32 ? p->pk32_np : 0);
+    if (pk_np && kn.pack_pref >= 0 && r_scan != kScanArith && (r_scan == 0 || r_scan >= 2 || kn.pack_pref > 0) && n_parts <= 128) {
+      const TableSet& pk = sdt == XHIST_F64 ? p->ts_pk : p->ts_pk32;
+      int spl = geom.spl;
+      if (spl == 8 && part_route_lds((size_t)pk.words * 8, (int)n_parts, weighted, route_tile(geom.block, 8), geom.block) > p->lds_max) spl = 4;
+      if (part_route_lds((size_t)pk.words * 8, (int)n_parts, weighted, route_tile(geom.block, spl), geom.block) <= p->lds_max &&
+          route_kernel(sdt, w_tag, D, kScanPackG, false, geom.block, spl)) {
+        r_scan = kScanPackG;
+        r_tset = &pk;
+        geom.spl = spl;
+      }
+    }
+  }
+  const int r_block = geom.block, r_tile = route_tile(r_block, geom.spl);
+  // rows that follow each other at one stride go through the routing pass several at a time
+  // (32 x 3*10^7 float32 pairs + weights, 300 x 300 bins: 8.05 -> 6.02 ms; 8 x 6*10^7 float64, 512 x 512: 5.17 -> 4.18;
+  // rows of 5*10^8 samples gain nothing — 8.63 -> 8.95 ms with 128 partitions in flight — and stay one per pass)
+  // a single row of float64 samples with float64 weights below ~1.5 x 10^7 samples: the routing pass's fixed costs (chunk
+  // pool, lists, one partial chunk per workgroup and partition) show, and count + prefix + scatter is 9-15 % faster
+  // (5*10^6: 0.155 | 0.132 ms, 10^7: 0.191 | 0.174, 2*10^7: 0.273 | 0.269: profiles/r03_h_fused_vs_three_pass_mid_sizes.txt);
+  // every other dtype combination is ahead with one pass from 5*10^6 samples on
+  const bool three_pass = kn.fused_pref == 0 && kn.partition == 0 && n_rows == 1 && weighted && sdt == XHIST_F64 && wdt == XHIST_F64 && n_cols < 15000000;
+  const int fused_use = three_pass ? -1 : kn.fused_pref;
+  bool uniform_rows = fused_use >= 0 && n_rows > 1 && n_parts * 2 <= 128 && n_cols < ((int64_t)1 << 27);
+  for (int d = 0; d < in.n_arrays(); ++d) uniform_rows &= in.array(d).inner_rows == 0;
+  xhist_array row_s[XHIST_MAX_DIMS], row_w;
+  const xhist_array* row_wp = weighted ? &row_w : nullptr;
+  int64_t r = 0;
+  while (uniform_rows && r < n_rows && rc == XHIST_OK) {
+    int rows = (int)std::min<int64_t>(n_rows - r, 128 / n_parts);
+    const size_t tab_bytes = r_scan == kScanArith ? 0 : (size_t)r_tset->words * 8;
+    while (rows > 1 && part_route_lds(tab_bytes, rows * (int)n_parts, weighted, r_tile, r_block) > p->lds_max) --rows;
+    if (rows < 2) break;  // (one row at a time below)
+    row_views(in, r, row_s, row_w);
+    void* row_out = static_cast<char*>(out) + (size_t)r * p->n_bins * 8;
+    rc = execute_partitioned_fused(p, row_s, row_wp, n_cols, row_out, stream, sdt, wdt, r_scan, r_f32, *r_tset, shift,
+                                   (int)n_parts, kn, rec, r == 0, r + rows == n_rows, geom, rows);
+    if (rc == XHIST_ERR_UNSUPPORTED) {
+      if (r > 0) rc = fail(XHIST_ERR_HIP, "internal: partitioned mode refused rows from %lld after accepting row 0", (long long)r);
+      else rc = XHIST_OK;  // nothing launched: row by row below
+      break;
+    }
+    r += rows;
+  }
+  for (; r < n_rows && rc == XHIST_OK; ++r) {
+    row_views(in, r, row_s, row_w);
+    void* row_out = static_cast<char*>(out) + (size_t)r * p->n_bins * 8;
+    // one routing pass (44 B per C5 sample) where it applies, else count + prefix + scatter (52.5 B); the
+    // choice depends on the plan and the dtypes only, so every row of a call takes the same route
+    rc = fused_use >= 0 ? execute_partitioned_fused(p, row_s, row_wp, n_cols, row_out, stream, sdt, wdt, r_scan,
+                                                     r_f32, *r_tset, shift, (int)n_parts, kn, rec, r == 0, r == n_rows - 1, geom)
+                         : XHIST_ERR_UNSUPPORTED;
+    if (rc == XHIST_ERR_UNSUPPORTED)
+      rc = execute_partitioned(p, row_s, row_wp, n_cols, row_out, stream,
+                               sdt, wdt, scan, sc.use_f32, *tset, shift, (int)n_parts, kn, rec, r == 0, r == n_rows - 1);
+    if (rc == XHIST_ERR_UNSUPPORTED && r > 0) rc = fail(XHIST_ERR_HIP, "internal: partitioned mode refused row %lld after accepting row 0", (long long)r);
+  }
+  return rc;  // UNSUPPORTED (from row 0, nothing launched): the caller goes on to global atomics
+}
 
-  // ---- geometry -----------------------------------------------------------------------------
-  // Workgroups per CU are sized by bytes in flight, not by occupancy: measured on MI355X
-  // (profiles/r01_a_sweep.jsonl) the streaming rate peaks at ~64 KiB of outstanding loads per CU
-  // (f64+weights: 2 x 256 threads x 128 B; f64: 4 x 256 x 64 B) and falls by 5-10% with more.
+// rows per launch are bounded by the grid limit
+static constexpr int64_t kMaxGrid = ((int64_t)1 << 31) - 1;
+
+// Launch geometry of the streaming kernels.
+struct StreamGeom {
+  int unroll;
+  int block, bpc;     // threads per workgroup, workgroups per CU
+  int over;           // oversubscription of the chip (many rows)
+  bool exact;         // exactly the workgroups that are resident at once, a whole number per row
+  int64_t target;     // workgroups over all rows
+  int64_t tile;       // samples a workgroup takes per step
+  int64_t col_chunk;  // columns per launch
+  int64_t segs0;      // workgroups per row of the first launch
+  bool direct;        // plain stores of the LDS histogram, no zeroing pass
+};
+
+// ---- geometry -----------------------------------------------------------------------------
+// Workgroups per CU are sized by bytes in flight, not by occupancy: measured on MI355X
+// (profiles/r01_a_sweep.jsonl) the streaming rate peaks at ~64 KiB of outstanding loads per CU
+// (f64+weights: 2 x 256 threads x 128 B; f64: 4 x 256 x 64 B) and falls by 5-10% with more.
+static StreamGeom streaming_geometry(const xhist_plan* p, const PlanKnobs& kn, const Inputs& in, const StreamChoice& sc, int accumulate) {
+  const int D = in.D;
+  const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  const bool fast = sc.fast, mixed = sc.mixed;
+  const int vec = sc.vec, scan = sc.scan, hist = sc.hist;
+  const size_t lds_bytes = sc.lds_bytes;
+  const int block_threads = kn.block_threads, grid_blocks = kn.grid_blocks;
+  StreamGeom g;
+  const int kUnroll = sc.long_tiles ? 8 : (mixed ? mixed_unroll(D) : (fast ? unroll_for(D, vec, scan) : 1));
   int64_t lane_bytes = 0;
-  for (int d = 0; d < D; ++d) lane_bytes += dtype_size(samples[d].dtype);
-  if (weighted) lane_bytes += dtype_size(weights->dtype);
-  if (two) lane_bytes += dtype_size(weights->dtype);
+  for (int d = 0; d < in.n_arrays(); ++d) lane_bytes += dtype_size(in.array(d).dtype);
+  if (in.two) lane_bytes += dtype_size(in.weights->dtype);
   lane_bytes *= fast ? (int64_t)vec * kUnroll : 4;
   int block = block_threads ? block_threads : 256;
   if (!block_threads && lds_bytes > 40 * 1024) {
@@ -1503,8 +1534,7 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
   // even neighbours: 17 / 19 / 21 / 23 / 27 / 31 per row 0.2946 / 0.2942 / 0.2980 / 0.2965 / 0.3067 / 0.3013 ms against
   // 0.2854-0.2876 for 16 ... 28, profiles/r03_n_c4_segs_per_row.txt: the workgroups of a row walk its 16 KiB tiles interleaved,
   // and an odd stride between a workgroup's tiles lands on the memory channels worse.  Hence 16 x, and an even count below.)
-  static const bool segs_legacy = [] { const char* e = getenv("XHIST_AMD_SEGS_LEGACY"); return e && *e == '1'; }();  // A/B switch
-  int over = n_rows <= 16 ? 1 : (segs_legacy ? 8 : 16);
+  int over = n_rows <= 16 ? 1 : 16;
   if (!grid_blocks && over > 1) {
     const double t_stream = total_samples * (double)sample_bytes / 6.0e12;
     while (over > 1) {
@@ -1526,11 +1556,11 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
     // 256-thread workgroups per CU are 15-20 % ahead.  The block shrinks until there is a tile for half
     // the CUs, and to whatever size lets a whole number of workgroups per row fill the chip best.
     int64_t ssz = 0;
-    for (int d = 0; d < D; ++d) ssz = std::max<int64_t>(ssz, dtype_size(samples[d].dtype));
+    for (int d = 0; d < D; ++d) ssz = std::max<int64_t>(ssz, dtype_size(in.samples[d].dtype));
     int64_t threads_per_cu = (int64_t)bpc * 256;  // (block is 64..256 here, bpc was sized for 256)
     block = 256;
     if (mixed || !(lane_bytes >= 128 && ssz >= 8 && total_samples * (double)sample_bytes > (double)((int64_t)256 << 20))) {
-      int64_t per_cu = (ssz >= 8 && scan == 1 && float_samples ? 32 : 64) * 1024 / std::max<int64_t>(lane_bytes, 1);
+      int64_t per_cu = (ssz >= 8 && scan == 1 && in.float_samples ? 32 : 64) * 1024 / std::max<int64_t>(lane_bytes, 1);
       // the mixed-dtype kernels convert after loading and want the whole CU: float32 x float64, 2 x 10^8 samples:
       // 256 threads per CU 0.88 ms, 512 0.52, 1024 0.44 (tools/mixtures.py)
       if (mixed) per_cu = 1024;
@@ -1566,18 +1596,14 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
     const double rate = 25e9 * block / 256;
     const int64_t cap = std::max<int64_t>(1, target / n_rows);
     int64_t per_row = std::max<int64_t>(1, std::min<int64_t>(cap, (int64_t)std::sqrt(bytes / (rate * 12e-9))));
-    const double flushed = std::min<double>((double)(n_slices > 1 ? slice_bins : p->n_bins), (double)n_cols / (double)per_row);
+    const double flushed = std::min<double>((double)(sc.n_slices > 1 ? sc.slice_bins : p->n_bins), (double)n_cols / (double)per_row);
     const double per_wg = std::max(12e-9, flushed / 2.0e11);
     per_row = std::max<int64_t>(1, std::min<int64_t>(cap, (int64_t)std::sqrt(bytes / (rate * per_wg))));
     target = per_row * n_rows;  // a whole number per row, never more than are resident at once
   }
   const int64_t tile = fast ? (int64_t)block * vec * kUnroll : (int64_t)block * 4;
   const int64_t tiles_per_row = (n_cols + tile - 1) / tile;
-  if (lds_bytes > 48 * 1024) HIPC(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-
-  // rows per launch bounded by the grid limit; columns per launch bounded so that no workgroup
-  // can overflow a uint32 LDS counter (< 2^31 samples per workgroup per launch)
-  const int64_t kMaxGrid = ((int64_t)1 << 31) - 1;
+  // columns per launch bounded so that no workgroup can overflow a uint32 LDS counter (< 2^31 samples per workgroup per launch)
   int64_t col_chunk = n_cols;
   {
     int64_t segs_full = std::max<int64_t>(1, std::min<int64_t>(tiles_per_row, (target + n_rows - 1) / n_rows));
@@ -1588,20 +1614,39 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
   // with plain writes — no zeroing pass over the output, no global atomics (10^5 rows x 1000 f32,
   // 50 bins: the 5 x 10^6 flush atomics alone took the whole 0.18 ms).
   int64_t segs0 = std::max<int64_t>(1, std::min<int64_t>((std::min(col_chunk, n_cols) + tile - 1) / tile, (target + n_rows - 1) / n_rows));
-  if (!segs_legacy && !exact && !grid_blocks && segs0 > 1 && (segs0 & 1) && segs0 + 1 <= (std::min(col_chunk, n_cols) + tile - 1) / tile) ++segs0;
-  const bool direct = !accumulate && !two && fast && hist == kHistLds && n_slices == 1 && col_chunk >= n_cols && segs0 == 1 &&
-                      n_rows <= kMaxGrid;
-  if (!accumulate && !direct && !two)
-    if (int zrc = zero_output(out, out_elems, stream)) return zrc;
+  if (!exact && !grid_blocks && segs0 > 1 && (segs0 & 1) && segs0 + 1 <= (std::min(col_chunk, n_cols) + tile - 1) / tile) ++segs0;
+  g.unroll = kUnroll;
+  g.block = block;
+  g.bpc = bpc;
+  g.over = over;
+  g.exact = exact;
+  g.target = target;
+  g.tile = tile;
+  g.col_chunk = col_chunk;
+  g.segs0 = segs0;
+  g.direct = !accumulate && !in.two && fast && hist == kHistLds && sc.n_slices == 1 && col_chunk >= n_cols && segs0 == 1 && n_rows <= kMaxGrid;
+  return g;
+}
+
+// ---- the streaming launches: column chunks x row ranges x bin slices ----------------------------------
+static int launch_streaming(xhist_plan* p, const PlanKnobs& kn, const Inputs& in, const StreamChoice& sc, const StreamGeom& g, void* out,
+                            void* out2, int accumulate, hipStream_t stream) {
+  const int D = in.D;
+  const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  const xhist_array *samples = in.samples, *weights = in.weights, *weights2 = in.weights2;
+  const DimTable* dims = sc.tset->dim;
+  if (sc.lds_bytes > 48 * 1024) HIPC(hipFuncSetAttribute((const void*)sc.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sc.lds_bytes));
+  if (!accumulate && !g.direct && !in.two)
+    if (int zrc = zero_output(out, n_rows * p->n_bins, stream)) return zrc;
   bool first_launch = true;
   LaunchRecord rec(p, stream);
   char desc[384];
-  for (int64_t c0 = 0; c0 < n_cols; c0 += col_chunk) {
-    const int64_t nc = std::min(col_chunk, n_cols - c0);
-    const int64_t tpr = (nc + tile - 1) / tile;
+  for (int64_t c0 = 0; c0 < n_cols; c0 += g.col_chunk) {
+    const int64_t nc = std::min(g.col_chunk, n_cols - c0);
+    const int64_t tpr = (nc + g.tile - 1) / g.tile;
     for (int64_t r0 = 0; r0 < n_rows;) {
-      int64_t segs = std::max<int64_t>(1, std::min<int64_t>(tpr, (target + (n_rows - r0) - 1) / (n_rows - r0)));
-      if (!segs_legacy && !exact && !grid_blocks && segs > 1 && (segs & 1) && segs + 1 <= tpr) ++segs;  // oversubscribed rows: an even number each
+      int64_t segs = std::max<int64_t>(1, std::min<int64_t>(tpr, (g.target + (n_rows - r0) - 1) / (n_rows - r0)));
+      if (!g.exact && !kn.grid_blocks && segs > 1 && (segs & 1) && segs + 1 <= tpr) ++segs;  // oversubscribed rows: an even number each
       const int64_t nr = std::min<int64_t>(n_rows - r0, kMaxGrid / segs);
       Params kp;
       memset(&kp, 0, sizeof kp);
@@ -1615,7 +1660,7 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
         kp.s_dt[d] = a.dtype;
         kp.dim[d] = dims[d];
       }
-      if (weighted) {
+      if (in.weighted) {
         kp.w_ptr = advance(weights->data, weights->dtype, c0 * weights->col_stride);
         kp.w_rs = weights->row_stride;
         kp.w_cs = weights->col_stride;
@@ -1623,7 +1668,7 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
         kp.w_os = weights->outer_stride;
         kp.w_dt = weights->dtype;
       }
-      if (two) {
+      if (in.two) {
         kp.w2_ptr = advance(weights2->data, weights2->dtype, c0);
         kp.w2_rs = weights2->row_stride;
         kp.w2_ir = weights2->inner_rows;
@@ -1632,38 +1677,97 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
       }
       kp.row0 = r0;
       kp.n_dims = D;
-      kp.tables = tset->blob;
-      kp.table_words = (scan == kScanArith || scan == kScanArith32) ? 0 : tset->words;  // arithmetic edges: nothing to stage
-      kp.tables_in_lds = tables_in_lds ? 1 : 0;
+      kp.tables = sc.tset->blob;
+      kp.table_words = (sc.scan == kScanArith || sc.scan == kScanArith32) ? 0 : sc.tset->words;  // arithmetic edges: nothing to stage
+      kp.tables_in_lds = sc.tables_in_lds ? 1 : 0;
       kp.n_rows = nr;
       kp.n_cols = nc;
       kp.n_bins = p->n_bins;
       kp.out = static_cast<char*>(out) + (size_t)r0 * p->n_bins * 8;
-      kp.copies_log2 = cl2;
-      kp.direct_store = direct ? 1 : 0;
+      kp.copies_log2 = sc.cl2;
+      kp.direct_store = g.direct ? 1 : 0;
       kp.segs = (int32_t)segs;
       const dim3 grid((unsigned)(nr * segs));
       if (first_launch)
-        if (int rrc = rec.begin(profile)) return rrc;
-      for (int sl = 0; sl < n_slices; ++sl) {  // (one launch unless the histogram is built in bin slices)
-        kp.slice_lo = (int64_t)sl * slice_bins;
-        kp.slice_n = (int32_t)std::min<int64_t>(slice_bins, p->n_bins - kp.slice_lo);
-        XH_LAUNCH_PICKED(fn, grid, dim3(block), lds_bytes, stream, kp);
+        if (int rrc = rec.begin(kn.profile)) return rrc;
+      for (int sl = 0; sl < sc.n_slices; ++sl) {  // (one launch unless the histogram is built in bin slices)
+        kp.slice_lo = (int64_t)sl * sc.slice_bins;
+        kp.slice_n = (int32_t)std::min<int64_t>(sc.slice_bins, p->n_bins - kp.slice_lo);
+        XH_LAUNCH_PICKED(sc.fn, grid, dim3(g.block), sc.lds_bytes, stream, kp);
         HIPC(hipGetLastError());
       }
       if (first_launch) {
         snprintf(desc, sizeof desc,
                  "family=%s hist=%s vec=%d unroll=%d block=%d grid=%lld segs=%lld lds_bytes=%zu copies=%d table_bytes=%zu "
                  "lut_k0=%d steps0=%d scan=%d weighted=%d D=%d cmp=%s lds_cap=%zu%s slices=%d direct_store=%d",
-                 mixed ? "fast mixed-dtypes" : (fast ? "fast" : "generic"), hist == kHistLds ? "lds" : (hist == kHistPacked ? "packed16" : "global"),
-                 fast ? vec : 1, fast ? kUnroll : 1, block, (long long)(nr * segs), (long long)segs, lds_bytes, 1 << cl2,
-                 table_bytes, dims[0].lut_k, dims[0].steps, scan, (int)weighted, D,
-                 use_f32 ? "f32thr" : (p->cmp == XHIST_CMP_I64 ? "i64" : (p->cmp == XHIST_CMP_F64 ? "f64" : "per-input")), lds_cap,
-                 two ? " weights=2" : "", n_slices, (int)direct);
+                 sc.mixed ? "fast mixed-dtypes" : (sc.fast ? "fast" : "generic"), sc.hist == kHistLds ? "lds" : (sc.hist == kHistPacked ? "packed16" : "global"),
+                 sc.fast ? sc.vec : 1, sc.fast ? g.unroll : 1, g.block, (long long)(nr * segs), (long long)segs, sc.lds_bytes, 1 << sc.cl2,
+                 sc.table_bytes, dims[0].lut_k, dims[0].steps, sc.scan, (int)in.weighted, D,
+                 sc.use_f32 ? "f32thr" : (p->cmp == XHIST_CMP_I64 ? "i64" : (p->cmp == XHIST_CMP_F64 ? "f64" : "per-input")), p->lds_max,
+                 in.two ? " weights=2" : "", sc.n_slices, (int)g.direct);
       }
       first_launch = false;
       r0 += nr;
     }
   }
   return rec.end(desc);
+}
+
+// weights2 / out2 (optional): a second weight array binned in the same pass (hist_fast<..., W2>).
+// Only the vector family with LDS histograms does that; anything else returns
+// XHIST_ERR_UNSUPPORTED before touching the outputs, and the caller runs two passes.
+static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_rows, int64_t n_cols,
+                          void* out, int accumulate, hipStream_t stream, const xhist_array* weights2, void* out2) {
+  const bool two = weights2 != nullptr;
+  const int64_t out_elems = n_rows * p->n_bins;
+  if (out_elems == 0) return XHIST_OK;
+  if (n_cols == 0) {
+    if (!accumulate) {
+      if (int zrc = zero_output(out, out_elems, stream)) return zrc;
+      if (two)
+        if (int zrc = zero_output(out2, out_elems, stream)) return zrc;
+    }
+    return XHIST_OK;
+  }
+  PlanKnobs kn;
+  {
+    std::lock_guard<std::mutex> lk(p->mu);
+    kn = p->knobs;
+  }
+  Inputs in;
+  in.samples = samples;
+  in.weights = weights;
+  in.weights2 = weights2;
+  in.n_rows = n_rows;
+  in.n_cols = n_cols;
+  in.D = p->n_dims;
+  in.sdt = samples[0].dtype;
+  in.wdt = weights ? weights->dtype : -1;
+  in.weighted = weights != nullptr;
+  in.two = two;
+  in.float_samples = in.sdt == XHIST_F64 || in.sdt == XHIST_F32;
+
+  // ---- many short rows / leading-axis reductions: one row per lane (xhist_lanes.hip.h) --------
+  if (kn.lanes >= 0 && !kn.force_generic && !kn.force_global && !two) {
+    const int rc = execute_lanes(p, samples, weights, n_rows, n_cols, out, accumulate, stream, kn);
+    if (rc != XHIST_ERR_UNSUPPORTED) return rc;  // UNSUPPORTED = not this shape, fall through
+  }
+  // (the output is zeroed further down, once the launch geometry says whether it has to be at all)
+  {
+    const int rc = execute_table_columns(p, kn, in, out, accumulate, stream);
+    if (rc != XHIST_ERR_UNSUPPORTED) return rc;
+  }
+  StreamChoice sc;
+  if (int rc = choose_streaming(p, kn, in, sc)) return rc;
+  if (two && !accumulate) {
+    if (int zrc = zero_output(out, out_elems, stream)) return zrc;
+    if (int zrc = zero_output(out2, out_elems, stream)) return zrc;
+  }
+  choose_slices(p, kn, in, sc);
+  {
+    const int rc = execute_partitioned_rows(p, kn, in, sc, out, accumulate, stream);
+    if (rc != XHIST_ERR_UNSUPPORTED) return rc;
+  }
+  const StreamGeom g = streaming_geometry(p, kn, in, sc, accumulate);
+  return launch_streaming(p, kn, in, sc, g, out, out2, accumulate, stream);
 }

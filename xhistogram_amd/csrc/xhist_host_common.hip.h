@@ -259,24 +259,7 @@ static void scratch_evict(int device, uint64_t keep, bool sync) {
 }
 
 // same shape as hipMallocAsync / hipFreeAsync; the device the caller made current is the block's device
-static bool scratch_use_hip_pool() {  // A/B switch for measurements only (the HIP pool is the unsafe one, see above)
-  static const bool on = [] { const char* e = getenv("XHIST_AMD_SCRATCH"); return e && !strcmp(e, "hip-pool"); }();
-  return on;
-}
-
 static hipError_t scratch_malloc(void** out, size_t bytes, hipStream_t stream) {
-  if (scratch_use_hip_pool()) {
-    static thread_local int warmed = -1;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (warmed != dev) {  // (the A/B needs the pool to keep its memory, as the round-2 code before the switch did)
-      hipMemPool_t pool;
-      uint64_t keep = ~(uint64_t)0;
-      if (hipDeviceGetDefaultMemPool(&pool, dev) == hipSuccess) (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
-      warmed = dev;
-    }
-    return hipMallocAsync(out, bytes, stream);
-  }
   int device = 0;
   if (hipGetDevice(&device) != hipSuccess) return hipErrorInvalidDevice;
   const size_t want = scratch_round(bytes);
@@ -330,7 +313,6 @@ static hipError_t scratch_malloc(void** out, size_t bytes, hipStream_t stream) {
 // synced: the caller has synchronised `stream` since the block's last use (no event needed)
 static hipError_t scratch_free(void* p, hipStream_t stream, bool synced = false) {
   if (!p) return hipSuccess;
-  if (scratch_use_hip_pool()) return hipFreeAsync(p, stream);
   std::lock_guard<std::mutex> lk(g_sc_mu);
   auto it = g_sc_live.find(p);
   if (it == g_sc_live.end()) return hipErrorInvalidValue;
@@ -425,6 +407,44 @@ struct TableSet {
   int max_cnt = 0;           // most edges sharing one bucket
 };
 
+// The user-set tuning keys of a plan (xhist_plan_set_param).  Every execute copies them once, under the plan's lock, and
+// decides with that copy alone.
+struct PlanKnobs {
+  int block_threads = 0;
+  int grid_blocks = 0;
+  int force_global = 0;
+  int force_generic = 0;
+  int partition = 0;  // 0 auto, 1 prefer the partitioned mode whenever it is legal, -1 never
+  int fused_pref = 0;  // partitioned mode: 0 one routing pass where it applies, -1 always count + prefix + scatter
+  int records48_pref = 0;  // routing pass, float64 weights: 0 packed 8-byte records while the weights have one sign, -1 never
+  int route_spl = 0;       // routing pass: samples per lane and tile (0 auto; 4; 8 = auto: the long tile exists only where auto picks it)
+  int flat_rows = 0;       // dense short rows streamed flat (hist_flat_rows): -1 off, 0 auto, 1 for any row length below 65536
+  int min_parts = 0;       // partitioned mode: bins are cut finer until a pass has this many partitions (0 auto = 16; 1 = never)
+  int route_grid = 0, acc_grid = 0;  // workgroups of the routing / adding-up pass of execute_partitioned_fused (0 auto) — scaling runs
+  int exchange_pref = 0;   // exchange mode of the partitioned path (xhist_exchange.hip.h): -1 never, 0 where eligible and the probe's window holds enough samples, 1 whenever the kernel can run (tests)
+  int exchange_min_pct = 0;    // window coverage (per cent of the probe's samples) from which the mode takes a call; 0 = kExchMinPpm
+  int exchange_arrive_us = 0;  // how long its workgroups wait for one another to start; 0 = 200 us
+  int exchange_budget_ms = 0;  // deadline of a workgroup's waits in that mode: 0 = 500 ms; -1: every wait gives up at once (tests of the fallback)
+  int route_pool_pct = 0;  // routing pass: chunk pool cut to this percentage of its worst-case size (tests of the pool-dry path; 0 = full)
+  int slices_pref = 0;  // 0 auto, 1 prefer bin slices for histograms beyond LDS, -1 never
+  int arith_pref = 0;  // 0 auto, 1 table-free digitize whenever the edges are arithmetic, -1 never
+  int arith32_pref = 0;  // 0 auto, 1 float32 arithmetic digitize for float32 samples wherever the plan offers it, -1 never
+  int lanes = 0;      // 0 auto, 1 prefer the row-per-lane kernels whenever they are legal, -1 never
+  int lds_copies = 0;
+  int pack_pref = 0;   // 0 auto, 1 packed entries whenever the plan has them, -1 never
+  int profile = 0;
+};
+
+// What the exchange mode remembers between the calls of a plan (execute_partitioned_fused); read and written under the plan's lock.
+struct ExchangeState {
+  int skip = 0;       // an exchange kernel gave up in flight (deadline, placement): eligible calls that still stay on the classic passes
+  int backoff = 16;   // ... and how many that will be after the next abort (doubles per abort, back to 16 after a clean call)
+  bool ran_last = false;  // the last eligible call launched the exchange kernel
+  uint32_t aborts_seen = 0;
+  size_t occ_lds = 0;  // the LDS size the occupancy question was asked for, and its answer
+  bool occ_ok = false;
+};
+
 struct xhist_plan {
   int device = 0;
   int n_dims = 0;
@@ -439,7 +459,6 @@ struct xhist_plan {
   int pk_np = 0;
   TableSet ts_pk32;    // the same for float32 SAMPLES: entries only (exact float32 thresholds, no redo path, no edges in LDS)
   int pk32_np = 0;
-  int pack_pref = 0;   // 0 auto, 1 packed entries whenever the plan has them, -1 never
   bool uns = false;    // the int64-domain inputs hold unsigned 64-bit values (XHIST_CMP_UNSIGNED)
   bool huge = false;   // some dimension has more than 65535 edges: no bucket tables (lut_k = 0)
   bool arith = false;  // every dimension has arithmetic (numpy.linspace) edges: table-free digitize available
@@ -447,39 +466,12 @@ struct xhist_plan {
   int64_t n_bins = 0;
   int cus = 256;
   size_t lds_max = 64 * 1024;
-  // tuning / diagnostics
-  int block_threads = 0;
-  int grid_blocks = 0;
-  int force_global = 0;
-  int force_generic = 0;
-  int partition = 0;  // 0 auto, 1 prefer the partitioned mode whenever it is legal, -1 never
-  int fused_pref = 0;  // partitioned mode: 0 one routing pass where it applies, -1 always count + prefix + scatter
-  int records48_pref = 0;  // routing pass, float64 weights: 0 packed 8-byte records while the weights have one sign, -1 never
+  PlanKnobs knobs;  // tuning / diagnostics (xhist_plan_set_param); an execute copies them once, under mu
   uint32_t* mixed_hint = nullptr;  // pinned host words the GPU sets: [0] a call met weights of both signs, [1] a chunk pool ran dry (see execute_partitioned_fused)
-  int route_spl = 0;       // routing pass: samples per lane and tile (0 auto; 4; 8 = auto: the long tile exists only where auto picks it)
-  int flat_rows = 0;       // dense short rows streamed flat (hist_flat_rows): -1 off, 0 auto, 1 for any row length below 65536
-  int min_parts = 0;       // partitioned mode: bins are cut finer until a pass has this many partitions (0 auto = 16; 1 = never)
-  int route_grid = 0, acc_grid = 0;  // workgroups of the routing / adding-up pass of execute_partitioned_fused (0 auto) — scaling runs
-  int exchange_pref = 0;   // exchange mode of the partitioned path (xhist_exchange.hip.h): -1 never, 0 where eligible and the probe's window holds enough samples, 1 whenever the kernel can run (tests)
-  int exchange_skip = 0;       // an exchange kernel gave up in flight (deadline, placement): eligible calls that still stay on the classic passes
-  int exchange_backoff = 16;   // ... and how many that will be after the next abort (doubles per abort, back to 16 after a clean call)
-  bool exchange_ran_last = false;  // the last eligible call launched the exchange kernel
-  int exchange_min_pct = 0;    // window coverage (per cent of the probe's samples) from which the mode takes a call; 0 = kExchMinPpm
-  int exchange_arrive_us = 0;  // how long its workgroups wait for one another to start; 0 = 200 us
-  uint32_t exchange_aborts_seen = 0;
-  size_t exchange_occ_lds = 0;  // the LDS size the occupancy question below was asked for, and its answer
-  bool exchange_occ_ok = false;
-  int exchange_budget_ms = 0;  // deadline of a workgroup's waits in that mode: 0 = 500 ms; -1: every wait gives up at once (tests of the fallback)
-  int route_pool_pct = 0;  // routing pass: chunk pool cut to this percentage of its worst-case size (tests of the pool-dry path; 0 = full)
-  int slices_pref = 0;  // 0 auto, 1 prefer bin slices for histograms beyond LDS, -1 never
-  int arith_pref = 0;  // 0 auto, 1 table-free digitize whenever the edges are arithmetic, -1 never
-  int arith32_pref = 0;  // 0 auto, 1 float32 arithmetic digitize for float32 samples wherever the plan offers it, -1 never
-  int lanes = 0;      // 0 auto, 1 prefer the row-per-lane kernels whenever they are legal, -1 never
-  int lds_copies = 0;
-  int profile = 0;
+  ExchangeState exch;  // under mu
   int profile_stride = 1;  // record the event pair of every stride-th execute only (microsecond kernels: two event records cost as much as the launch)
   int64_t n_seen = 0;
-  std::mutex mu;  // guards events + desc
+  std::mutex mu;  // guards knobs, exch, events + desc
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ring;  // profile > 0: event pairs around the main kernel
   int64_t n_recorded = 0;                                // executes recorded since the last read
   std::string desc;

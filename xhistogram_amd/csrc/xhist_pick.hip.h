@@ -53,7 +53,7 @@ constexpr int unroll_for(int D, int vec, int scan) {
 //    thresholds of a weighted histogram fit (<= 16384 bins, SCAN 0 or 2, the short tile); everything else with one input digitizes
 //    arithmetically or takes the three-pass route.
 //  * Bin slices keep float64 sums in LDS and counts as packed uint16 pairs: there is no sliced uint32 home.
-//  * The generic family keeps its histogram in LDS only when its tables are there too (place() in execute_device).
+//  * The generic family keeps its histogram in LDS only when its tables are there too (place_histogram() in xhist_exec_device.hip.h).
 constexpr bool one_input_home_exists(bool is_f64, bool unweighted, int scan, int hist_home /* 0 global, 1 lds, 2 packed */) {
   (void)unweighted;
   if (hist_home == 2) return scan == 0 || scan == 3 || scan == 4 || scan == kScanArith || (scan == 2 && is_f64);

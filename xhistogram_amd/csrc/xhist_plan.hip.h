@@ -234,8 +234,6 @@ static int build_pack_domain(xhist_plan* p, bool f32dom, int n_inputs, const int
       return k;
     };
     const uint32_t k0 = key_of(thr[0]), k1 = key_of(thr[(size_t)E - 1]);
-    // buckets per edge the search stops at (development override: XHIST_AMD_KEY_K_PER_EDGE)
-    static const double key_k_per_edge = [] { const char* e = getenv("XHIST_AMD_KEY_K_PER_EDGE"); return e && *e ? atof(e) : 0.0; }();
     int best_shift = -1;
     best_k = 0;
     for (int shift = 0; shift < 32; ++shift) {
@@ -255,7 +253,6 @@ static int build_pack_domain(xhist_plan* p, bool f32dom, int n_inputs, const int
       if (mx > 3) break;
       best_shift = shift;
       best_k = K;
-      if ((double)K <= key_k_per_edge * (double)E) break;  // coarse enough (see key_k_per_edge)
     }
     if (best_shift < 0) return XHIST_OK;
     t.lut_k = best_k;
@@ -614,69 +611,69 @@ extern "C" int xhist_plan_set_param(xhist_plan* p, const char* key, int64_t valu
   std::lock_guard<std::mutex> lk(p->mu);
   if (!strcmp(key, "block_threads")) {
     if (value != 0 && (value < 64 || value > 1024 || value % 64)) return fail(XHIST_ERR_INVALID, "block_threads must be a multiple of 64 in [64, 1024]");
-    p->block_threads = (int)value;
+    p->knobs.block_threads = (int)value;
   } else if (!strcmp(key, "grid_blocks")) {
     if (value < 0) return fail(XHIST_ERR_INVALID, "grid_blocks must be >= 0");
-    p->grid_blocks = (int)std::min<int64_t>(value, 1 << 30);
+    p->knobs.grid_blocks = (int)std::min<int64_t>(value, 1 << 30);
   } else if (!strcmp(key, "force_global")) {
-    p->force_global = value != 0;
+    p->knobs.force_global = value != 0;
   } else if (!strcmp(key, "force_generic")) {
-    p->force_generic = value != 0;
+    p->knobs.force_generic = value != 0;
   } else if (!strcmp(key, "profile_stride")) {
     p->profile_stride = (int)std::max<int64_t>(1, std::min<int64_t>(value, 1 << 20));
     p->n_seen = 0;
   } else if (!strcmp(key, "fused")) {
-    p->fused_pref = value < 0 ? -1 : (value > 0 ? 1 : 0);
+    p->knobs.fused_pref = value < 0 ? -1 : (value > 0 ? 1 : 0);
   } else if (!strcmp(key, "records48")) {
-    p->records48_pref = value < 0 ? -1 : 0;
+    p->knobs.records48_pref = value < 0 ? -1 : 0;
     if (p->mixed_hint) *p->mixed_hint = 0u;  // (setting the knob also forgets what earlier calls saw)
   } else if (!strcmp(key, "exchange")) {
-    p->exchange_pref = value < 0 ? -1 : (value > 0 ? 1 : 0);
-    p->exchange_skip = 0;
-    p->exchange_backoff = 16;
+    p->knobs.exchange_pref = value < 0 ? -1 : (value > 0 ? 1 : 0);
+    p->exch.skip = 0;
+    p->exch.backoff = 16;
   } else if (!strcmp(key, "exchange_min_pct")) {
     if (value < 0 || value > 100) return fail(XHIST_ERR_INVALID, "exchange_min_pct must be in [0, 100]");
-    p->exchange_min_pct = (int)value;
+    p->knobs.exchange_min_pct = (int)value;
   } else if (!strcmp(key, "exchange_arrive_us")) {
     if (value < 0 || value > 1000000) return fail(XHIST_ERR_INVALID, "exchange_arrive_us must be in [0, 1000000]");
-    p->exchange_arrive_us = (int)value;
+    p->knobs.exchange_arrive_us = (int)value;
   } else if (!strcmp(key, "exchange_budget_ms")) {
     if (value < -1 || value > 600000) return fail(XHIST_ERR_INVALID, "exchange_budget_ms must be in [-1, 600000]");
-    p->exchange_budget_ms = (int)value;
+    p->knobs.exchange_budget_ms = (int)value;
   } else if (!strcmp(key, "route_spl")) {
     if (value != 0 && value != 4 && value != 8) return fail(XHIST_ERR_INVALID, "route_spl must be 0 (auto), 4 or 8");
-    p->route_spl = (int)value;
+    p->knobs.route_spl = (int)value;
   } else if (!strcmp(key, "flat_rows")) {
     if (value < -1 || value > 1) return fail(XHIST_ERR_INVALID, "flat_rows must be -1 (off), 0 (auto) or 1 (any row length below 65536)");
-    p->flat_rows = (int)value;
+    p->knobs.flat_rows = (int)value;
   } else if (!strcmp(key, "min_parts")) {
     if (value < 0 || value > 128) return fail(XHIST_ERR_INVALID, "min_parts must be in [0, 128]");
-    p->min_parts = (int)value;
+    p->knobs.min_parts = (int)value;
   } else if (!strcmp(key, "route_pool_pct")) {
     if (value < 0 || value > 100) return fail(XHIST_ERR_INVALID, "route_pool_pct must be in [0, 100]");
-    p->route_pool_pct = (int)value;
+    p->knobs.route_pool_pct = (int)value;
     if (value != 0 && p->mixed_hint) p->mixed_hint[1] = 0u;  // (a new setting forgets what earlier calls ran into; 0 keeps the note readable)
   } else if (!strcmp(key, "partition")) {
-    p->partition = value > 0 ? 1 : (value < 0 ? -1 : 0);
+    p->knobs.partition = value > 0 ? 1 : (value < 0 ? -1 : 0);
   } else if (!strcmp(key, "lanes")) {
-    p->lanes = value > 0 ? 1 : (value < 0 ? -1 : 0);
+    p->knobs.lanes = value > 0 ? 1 : (value < 0 ? -1 : 0);
   } else if (!strcmp(key, "slices")) {
-    p->slices_pref = value > 0 ? 1 : (value < 0 ? -1 : 0);
+    p->knobs.slices_pref = value > 0 ? 1 : (value < 0 ? -1 : 0);
   } else if (!strcmp(key, "route_grid")) {
     if (value < 0 || value > 4096) return fail(XHIST_ERR_INVALID, "route_grid must be in [0, 4096]");
-    p->route_grid = (int)value;
+    p->knobs.route_grid = (int)value;
   } else if (!strcmp(key, "acc_grid")) {
     if (value < 0 || value > 4096) return fail(XHIST_ERR_INVALID, "acc_grid must be in [0, 4096]");
-    p->acc_grid = (int)value;
+    p->knobs.acc_grid = (int)value;
   } else if (!strcmp(key, "pack")) {
-    p->pack_pref = value > 0 ? 1 : (value < 0 ? -1 : 0);
+    p->knobs.pack_pref = value > 0 ? 1 : (value < 0 ? -1 : 0);
   } else if (!strcmp(key, "arith")) {
-    p->arith_pref = value > 0 ? 1 : (value < 0 ? -1 : 0);
+    p->knobs.arith_pref = value > 0 ? 1 : (value < 0 ? -1 : 0);
   } else if (!strcmp(key, "arith32")) {
-    p->arith32_pref = value > 0 ? 1 : (value < 0 ? -1 : 0);
+    p->knobs.arith32_pref = value > 0 ? 1 : (value < 0 ? -1 : 0);
   } else if (!strcmp(key, "lds_copies")) {
     if (value != 0 && (value < 1 || value > 32 || (value & (value - 1)))) return fail(XHIST_ERR_INVALID, "lds_copies must be a power of two in [1, 32]");
-    p->lds_copies = (int)value;
+    p->knobs.lds_copies = (int)value;
   } else if (!strcmp(key, "profile")) {
     // value = number of most recent executes whose main-kernel duration is kept (0 = off)
     if (value < 0 || value > 4096) return fail(XHIST_ERR_INVALID, "profile must be in [0, 4096]");
@@ -688,7 +685,7 @@ extern "C" int xhist_plan_set_param(xhist_plan* p, const char* key, int64_t valu
       HIPC(hipEventCreate(&b));
       p->ring.emplace_back(a, b);
     }
-    p->profile = (int)value;
+    p->knobs.profile = (int)value;
     p->n_recorded = 0;
   } else {
     return fail(XHIST_ERR_INVALID, "unknown parameter '%s'", key);
@@ -710,12 +707,12 @@ extern "C" int xhist_plan_profile_read(xhist_plan* p, float* ms, int cap, int* n
   if (!p || !ms || !n_out || cap < 0) return fail(XHIST_ERR_INVALID, "plan / ms / n_out is NULL");
   std::lock_guard<std::mutex> lk(p->mu);
   *n_out = 0;
-  if (!p->profile || p->n_recorded == 0) return XHIST_OK;
+  if (!p->knobs.profile || p->n_recorded == 0) return XHIST_OK;
   DeviceGuard g;
   if (int rc = g.set(p->device)) return rc;
-  const int64_t kept = std::min<int64_t>(p->n_recorded, p->profile);
+  const int64_t kept = std::min<int64_t>(p->n_recorded, p->knobs.profile);
   for (int64_t k = p->n_recorded - kept; k < p->n_recorded && *n_out < cap; ++k) {
-    auto& e = p->ring[(size_t)(k % p->profile)];
+    auto& e = p->ring[(size_t)(k % p->knobs.profile)];
     HIPC(hipEventSynchronize(e.second));
     HIPC(hipEventElapsedTime(&ms[*n_out], e.first, e.second));
     ++*n_out;

@@ -184,7 +184,7 @@ static kernel_fn generic_kernel_t(int cmp, bool weighted, bool lds) {
   return lds ? (kernel_fn)hist_generic<3, false, true, TLDS> : (kernel_fn)hist_generic<3, false, false, TLDS>;
 }
 
-// tables outside LDS: the histogram is never in LDS then (place() in execute_device puts it there only next to its tables), so
+// tables outside LDS: the histogram is never in LDS then (place_histogram() puts it there only next to its tables), so
 // those three-times-two kernels are not instantiated (census of round 6)
 static kernel_fn generic_kernel_no_lds(int cmp, bool weighted) {
   if (cmp == XHIST_CMP_F64) return weighted ? (kernel_fn)hist_generic<0, true, false, false> : (kernel_fn)hist_generic<0, false, false, false>;
