@@ -21,6 +21,7 @@ import os
 import numpy as np
 import pytest
 
+import exact_weights as ew
 from conftest import assert_hist_equal
 from oracle import oracle_np as onp
 from test_gpu_parity import _dev, xh  # noqa: F401  (xh: the module fixture)
@@ -202,14 +203,28 @@ def _dev_lead(a):
     return torch.as_tensor(np.ascontiguousarray(a.T)).cuda().T
 
 
-def _run_case(core, st, wt, D, case, seed):
+def _bound_check(xs, edges, w, got, want, desc):
+    """beside assert_hist_equal for full-mantissa weights: the float64 bound of tests/exact_weights.py (the oracle's |w| histogram
+    and counts over the samples `xs` as the oracle takes them; 2^-37 per weight more where the description shows packed records)"""
+    ew.assert_within_f64_bound(got, want, onp.bincount_rows(xs, edges, np.abs(w.astype(F64))), onp.bincount_rows(xs, edges, None),
+                               ew.records_rounding(desc), desc)
+
+
+def _run_case(core, st, wt, D, case, seed, make_w=None):
+    """make_w: None (weights U[0.25, 2), compared within 1e-6 and the float64 bound) or a factory (rng, shape) -> weights of
+    exactly summable values (tests/exact_weights.py), compared bit for bit"""
     import torch
 
     edges = [edges_of(case["kind"], nb, seed=seed + d) for d, nb in enumerate(case["nbs"])]
     n_rows, n_cols = case["shape"]
     xs = samples_for(edges, n_rows, n_cols, st, seed)
     rng = np.random.default_rng(seed + 99)
-    w = None if wt is None else rng.uniform(0.25, 2.0, (n_rows, n_cols)).astype(wt)
+    if wt is None or make_w is None:
+        w = None if wt is None else rng.uniform(0.25, 2.0, (n_rows, n_cols)).astype(wt)
+    else:
+        w = make_w(rng, (n_rows, n_cols))
+        assert w.dtype == wt
+        ew.assert_summable(n_cols, wt)
     # the oracle compares in float64 against float64 edges (numpy's promotion); float32 weights are added as float64
     want = onp.bincount_rows([x.astype(F64) for x in xs], edges, None if w is None else w.astype(F64))
     put = _dev_lead if case.get("lead") else _dev
@@ -227,7 +242,13 @@ def _run_case(core, st, wt, D, case, seed):
     finally:
         for k in case["params"]:
             plan.set_param(k, 0)
-    assert_hist_equal(got.cpu().numpy(), want, weighted=wt is not None), (case, desc)
+    got = got.cpu().numpy()
+    if make_w is not None and wt is not None:
+        ew.assert_bits_equal(got, want, desc)
+        return desc
+    assert_hist_equal(got, want, weighted=wt is not None), (case, desc)
+    if wt is not None:
+        _bound_check([x.astype(F64) for x in xs], edges, w, got, want, desc)
     return desc
 
 
@@ -288,8 +309,9 @@ def test_dispatch_surface_float_samples(xh, st, wt, D):
 # ---------------------------------------------------------------------------------------------------------------------
 # the other kernel families: small integer / half samples, the exact int64 domain, dtype mixtures, two weights, generic
 # ---------------------------------------------------------------------------------------------------------------------
-def _run_general(core, samples, edges, w, params, weighted, lead=False):
-    """samples: list of [rows, cols] numpy arrays (any dtype); compares with the oracle in float64 / exact int64"""
+def _run_general(core, samples, edges, w, params, weighted, lead=False, exact=False):
+    """samples: list of [rows, cols] numpy arrays (any dtype); compares with the oracle in float64 / exact int64 — weighted results
+    also within the float64 bound, or (exact=True: `w` exactly summable, tests/exact_weights.py) bit for bit"""
     import torch
 
     put = _dev_lead if lead else _dev
@@ -303,17 +325,35 @@ def _run_general(core, samples, edges, w, params, weighted, lead=False):
     try:
         got = core._bincount_2d_vectorized(*xd, bins=edges, weights=wd)
         torch.cuda.synchronize()
+        desc = plan.describe()
     finally:
         for k in params:
             plan.set_param(k, 0)
     want = onp.bincount_rows(samples, edges, w)
-    assert_hist_equal(got.cpu().numpy(), want, weighted)
+    got = got.cpu().numpy()
+    if exact and w is not None:
+        ew.assert_summable(samples[0].shape[1], w.dtype)
+        ew.assert_bits_equal(got, want, desc)
+        return
+    assert_hist_equal(got, want, weighted)
+    if w is not None:
+        _bound_check(samples, edges, w, got, want, desc)
 
 
 @pytest.mark.parametrize("dtype", ["int32", "int64", "int16", "uint8", "float16"])
 def test_dispatch_surface_small_samples(xh, dtype):
     """one input of a small integer / half dtype (compared in float64 like numpy does): counts or float64 weights, histogram in
     LDS or behind memory-side atomics, one edge per bucket or a binary search; rows streamed or one row per lane"""
+    _small_samples(xh, dtype)
+
+
+def _uniform(lo, hi):
+    return lambda rng, shape: rng.uniform(lo, hi, shape)
+
+
+# The bodies of the families below take an optional weights factory (rng, shape) -> weights: None draws today's full-mantissa
+# weights; an exactly summable one (tests/exact_weights.py, from test_gpu_weighted_exact.py) makes every weighted result bitwise.
+def _small_samples(xh, dtype, make_w=None):
     rng = np.random.default_rng(7)
     dt = np.dtype(dtype)
     for kind in ("k1", "crowd", "lin"):
@@ -327,25 +367,33 @@ def test_dispatch_surface_small_samples(xh, dtype):
                 else:
                     x = rng.uniform(-110, 110, shape).astype(dt)
                     x.reshape(-1)[::97] = np.nan
-                w = rng.uniform(0.5, 1.5, shape) if weighted else None
-                _run_general(xh, [x], [e], w, params, weighted, lead=home.startswith("lanes_lead"))
+                w = (make_w or _uniform(0.5, 1.5))(rng, shape) if weighted else None
+                _run_general(xh, [x], [e], w, params, weighted, lead=home.startswith("lanes_lead"), exact=make_w is not None)
 
 
 def test_dispatch_surface_int64_domain(xh):
     """int64 samples against INTEGER edges: compared exactly in int64 (values beyond 2^53 included)"""
+    _int64_domain(xh)
+
+
+def _int64_domain(xh, make_w=None):
     rng = np.random.default_rng(8)
     for home, shape, params in (("lds", (3, 20_011), {}), ("global", (2, 10_007), {"force_global": 1})):
         for weighted in (False, True):
             base = (1 << 60)
             e = base + np.sort(rng.choice(100_000, 65, replace=False)).astype(np.int64)
             x = base + rng.integers(-1000, 101_000, shape).astype(np.int64)
-            w = rng.uniform(0.5, 1.5, shape) if weighted else None
-            _run_general(xh, [x], [e], w, params, weighted)
+            w = (make_w or _uniform(0.5, 1.5))(rng, shape) if weighted else None
+            _run_general(xh, [x], [e], w, params, weighted, exact=make_w is not None)
 
 
 def test_dispatch_surface_generic_integer_domains(xh):
     """the generic family's exact-integer variants: TWO int64 inputs against integer edges (compared in int64), an int64 input
     next to a float64 one (a compare domain per input), edge arrays too long for LDS; histogram in LDS or behind memory-side atomics"""
+    _generic_integer_domains(xh)
+
+
+def _generic_integer_domains(xh, make_w=None):
     rng = np.random.default_rng(10)
     base = 1 << 58
     shape = (3, 20_011)
@@ -358,21 +406,26 @@ def test_dispatch_surface_generic_integer_domains(xh):
     big = base + np.sort(rng.choice(4_000_000, 30_001, replace=False)).astype(np.int64)  # 30001 int64 edges: 240 KB, beyond LDS
     xb = base + rng.integers(-5_000, 4_005_000, shape).astype(np.int64)
     bigf = np.sort(rng.uniform(-3, 3, 30_001))
+    ex = make_w is not None
     for weighted in (False, True):
-        w = rng.uniform(0.5, 1.5, shape) if weighted else None
+        w = (make_w or _uniform(0.5, 1.5))(rng, shape) if weighted else None
         for params in ({}, {"force_global": 1}):
-            _run_general(xh, [xi, xj], [ei, ej], w, params, weighted)        # int64 domain, two inputs
-            _run_general(xh, [xi, xf], [ei, ef], w, params, weighted)        # per-input domains
-            _run_general(xh, [xf, xj], [ef, ej], w, params, weighted)
-        _run_general(xh, [xb], [big], w, {}, weighted)                       # tables that do not fit LDS: int64 domain
-        _run_general(xh, [xb, xf], [big, ef], w, {}, weighted)               # ... per-input domains
-        _run_general(xh, [xf * 1.0], [bigf], w, {"force_generic": 1}, weighted)  # ... float64 domain
+            _run_general(xh, [xi, xj], [ei, ej], w, params, weighted, exact=ex)        # int64 domain, two inputs
+            _run_general(xh, [xi, xf], [ei, ef], w, params, weighted, exact=ex)        # per-input domains
+            _run_general(xh, [xf, xj], [ef, ej], w, params, weighted, exact=ex)
+        _run_general(xh, [xb], [big], w, {}, weighted, exact=ex)                       # tables that do not fit LDS: int64 domain
+        _run_general(xh, [xb, xf], [big, ef], w, {}, weighted, exact=ex)               # ... per-input domains
+        _run_general(xh, [xf * 1.0], [bigf], w, {"force_generic": 1}, weighted, exact=ex)  # ... float64 domain
 
 
 @pytest.mark.parametrize("D", [1, 2, 3])
 def test_dispatch_surface_mixed_dtypes(xh, D):
     """inputs of different dtypes / integer weights (consumed as float64 by the MIXED vector kernels; the generic family where
     those have no variant): every digitize form they take, weighted and not"""
+    _mixed_dtypes(xh, D)
+
+
+def _mixed_dtypes(xh, D, make_w=None):
     rng = np.random.default_rng(9 + D)
     dts = [np.float32, np.int32, np.float64][:D] if D > 1 else [np.float32]
     for kind in ("lin", "k1", "k2", "k3", "crowd"):
@@ -387,10 +440,10 @@ def test_dispatch_surface_mixed_dtypes(xh, D):
                 for d in range(D):
                     v = rng.uniform(-55, 55, shape)
                     xs.append(np.rint(v).astype(dts[d]) if np.dtype(dts[d]).kind == "i" else v.astype(dts[d]))
-                w = None if wkind is None else (rng.integers(1, 5, shape).astype(wkind) if np.dtype(wkind).kind == "i" else rng.uniform(0.5, 2, shape))
+                w = None if wkind is None else (rng.integers(1, 5, shape).astype(wkind) if np.dtype(wkind).kind == "i" else (make_w or _uniform(0.5, 2))(rng, shape))
                 if D == 1 and wkind is None:
                     continue  # (homogeneous: the float product above)
-                _run_general(xh, xs, edges, w, params, w is not None)
+                _run_general(xh, xs, edges, w, params, w is not None, exact=make_w is not None)
 
 
 def test_dispatch_surface_odds_and_ends(xh):
@@ -495,6 +548,10 @@ def test_dispatch_surface_one_long_float64_row(xh):
 def test_dispatch_surface_two_weights(xh, st, wt, D):
     """two weight arrays in one pass (histogram_two_weights: the TODO at /root/reference/xhistogram/xarray.py:106): each of the
     pair equals the oracle's single-weight histogram, for one and two edges per bucket"""
+    _two_weights(xh, st, wt, D)
+
+
+def _two_weights(xh, st, wt, D, make_w=None):
     import torch
 
     rng = np.random.default_rng(11 * D)
@@ -503,7 +560,7 @@ def test_dispatch_surface_two_weights(xh, st, wt, D):
         edges = [edges_of(kind, nb, seed=d) for d, nb in enumerate(nbs)]
         shape = (2, 20_011)
         xs = samples_for(edges, shape[0], shape[1], _ST[st], 5)
-        wa, wb = (rng.uniform(0.5, 2.0, shape).astype(_WT[wt]) for _ in range(2))
+        wa, wb = ((make_w or _uniform(0.5, 2.0))(rng, shape).astype(_WT[wt]) for _ in range(2))
         for params in ({}, {"arith": -1}):
             xd = [_dev(x) for x in xs]
             dts = [xh._np_dtype_of(t) for t in xd]
@@ -518,5 +575,9 @@ def test_dispatch_surface_two_weights(xh, st, wt, D):
                 for k in params:
                     plan.set_param(k, 0)
             x64 = [x.astype(F64) for x in xs]
-            assert_hist_equal(ha.cpu().numpy(), onp.bincount_rows(x64, edges, wa.astype(F64)), True)
-            assert_hist_equal(hb.cpu().numpy(), onp.bincount_rows(x64, edges, wb.astype(F64)), True)
+            for h, wx in ((ha, wa), (hb, wb)):
+                want = onp.bincount_rows(x64, edges, wx.astype(F64))
+                if make_w is not None:
+                    ew.assert_bits_equal(h.cpu().numpy(), want, "histogram_two_weights")
+                else:
+                    assert_hist_equal(h.cpu().numpy(), want, True)

@@ -10,6 +10,7 @@ any size, any window coverage) so that sizes the oracle finishes in seconds reac
 import numpy as np
 import pytest
 
+import exact_weights as ew
 from conftest import assert_hist_equal
 from oracle import oracle_np as onp
 from test_gpu_parity import _dev, _plan_for, _run, xh  # noqa: F401  (xh: the module fixture)
@@ -32,11 +33,19 @@ def test_exchange_mode_c5_shape_against_the_oracle(xh, n):
     x, y = rng.standard_normal((1, n)), rng.standard_normal((1, n))
     w = rng.uniform(0, 1, (1, n))
     want = onp.bincount_rows([x, y], edges, w)
-    got, _ = _exchange(xh, [x, y], edges, w)
+    got, xdesc = _exchange(xh, [x, y], edges, w)
     assert_hist_equal(got, want, True)
     classic, desc = _run(xh, [x, y], edges, w, True, partition=1, exchange=-1)
     assert "exchange=no" in desc, desc
     np.testing.assert_allclose(got, classic, rtol=2.0 ** -34, atol=0)  # (both round the weights to 36 mantissa bits, then add in float64)
+    _bound(got, want, [x, y], edges, w, xdesc)
+    _bound(classic, want, [x, y], edges, w, desc)
+
+
+def _bound(got, want, samples, edges, w, desc):
+    """the float64 bound of tests/exact_weights.py: 2 gamma(n) |w|-sums per bin, plus 2^-37 of them where records are packed"""
+    ew.assert_within_f64_bound(got, want, onp.bincount_rows(samples, edges, np.abs(w)), onp.bincount_rows(samples, edges, None),
+                               ew.records_rounding(desc), desc)
 
 
 def test_exchange_mode_specials_and_edges(xh):
@@ -427,11 +436,13 @@ def test_exchange_mode_exact_records_c5_shape(xh, n, signs):
     x, y = rng.standard_normal((1, n)), rng.standard_normal((1, n))
     w = rng.uniform(0, 1, (1, n)) if signs == "one" else rng.standard_normal((1, n))
     want = onp.bincount_rows([x, y], edges, w)
-    got, _ = _exchange_exact(xh, [x, y], edges, w)
+    got, xdesc = _exchange_exact(xh, [x, y], edges, w)
     classic, desc = _run(xh, [x, y], edges, w, True, partition=1, exchange=-1, records48=-1)
     assert "exchange=no" in desc, desc
     np.testing.assert_allclose(got, classic, rtol=1e-12, atol=1e-12 * np.abs(w).max())
     np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-9 * np.abs(w).max())
+    _bound(got, want, [x, y], edges, w, xdesc)
+    _bound(classic, want, [x, y], edges, w, desc)
 
 
 def test_exchange_mode_exact_records_keep_every_bit_of_a_weight(xh):
@@ -478,5 +489,6 @@ def test_exchange_mode_exact_records_other_shapes(xh, case):
         samples = [rng.uniform(0, 1, (1, n)), rng.uniform(0, 1, (1, n))]
     w = rng.standard_normal((1, n))
     want = onp.bincount_rows(samples, edges, w)
-    got, _ = _exchange_exact(xh, samples, edges, w)
+    got, desc = _exchange_exact(xh, samples, edges, w)
     np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-9 * np.abs(w).max())
+    _bound(got, want, samples, edges, w, desc)

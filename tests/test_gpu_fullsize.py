@@ -161,8 +161,26 @@ def test_c5_full_size_4e9_samples_weighted_density(xh):
         plan.set_param("partition", 0)
     want = onp.histogram(x[:m].cpu().numpy(), y[:m].cpu().numpy(), bins=[e, e], weights=w[:m].cpu().numpy())[0]
     assert_hist_equal(hp.cpu().numpy(), want, weighted=True)
+    # exactly summable weights (2^24 + k) * 2^-25 (tests/exact_weights.py), made in place: every order of float64 additions gives
+    # the same bits — the exchange mode and the classic passes against the torch restatement, bit for bit (one weighted sample lost
+    # or counted twice among 4 * 10^9 shows; packed records carry these 25 bits exactly)
+    del ha, hb, dens
+    w.mul_(2**24).floor_().add_(2**24).mul_(2**-25)
+    ref = bench.torch_reference(torch, [x, y], w, [e, e], 1, n, True).reshape(1024, 1024)
+    assert float(ref.max()) < 2**27  # (every weight >= 0.5: no bin holds 2^28 samples)
+    exact, _ = xh.histogram(x, y, bins=[e, e], weights=w)
+    assert "exchange=if the probe" in plan.describe(), plan.describe()
+    assert torch.equal(exact, ref)
+    plan.set_param("exchange", -1)
+    try:
+        exact, _ = xh.histogram(x, y, bins=[e, e], weights=w)
+        assert "exchange=no" in plan.describe(), plan.describe()
+    finally:
+        plan.set_param("exchange", 0)
+    assert torch.equal(exact, ref)
+    del exact, ref
     # unweighted counts at full size: exact, run-to-run identical, total = samples in range
-    del w, ha, hb, dens
+    del w
     torch.cuda.empty_cache()
     c1, _ = xh.histogram(x, y, bins=[e, e])
     c2, _ = xh.histogram(x, y, bins=[e, e])

@@ -385,6 +385,13 @@ def test_full_size_c2_properties(xh, big):
     ref_w = torch.bincount(idx, weights=w, minlength=102)[1:101]
     torch.testing.assert_close(hw, ref_w, rtol=1e-6, atol=0)
     assert n == 1_000_000_000
+    # exactly summable weights (2^24 + k) * 2^-25 (tests/exact_weights.py): every order of float64 additions gives the same bits,
+    # so one weighted sample lost or counted twice among 10^9 shows (a copy: the module's `big` stays as C3 uses it)
+    assert int(h.max().item()) < 2**28
+    we = w.mul(2**24).floor_().add_(2**24).mul_(2**-25)
+    hwe, _ = xh.histogram(x, bins=edges, weights=we)
+    assert torch.equal(hwe, torch.bincount(idx, weights=we, minlength=102)[1:101])
+    del we, idx
 
 
 def test_full_size_c3_properties(xh, big):

@@ -6,6 +6,7 @@ import threading
 import numpy as np
 import pytest
 
+import exact_weights as ew
 from conftest import assert_hist_equal
 from oracle import oracle_np as onp
 
@@ -104,6 +105,10 @@ def test_random_cases_match_oracle(xh, case):
             plan.set_param(override, 0)
     got = got.cpu().numpy() if resident else got
     assert_hist_equal(got, want, weighted=(w is not None) or density)
+    if w is not None and not density:  # (float64 sums of the same terms in another order: the bound of tests/exact_weights.py)
+        a, _ = onp.histogram(*args, weights=np.abs(w), **kw)
+        cnt, _ = onp.histogram(*args, **kw)
+        ew.assert_within_f64_bound(got, want, a, cnt)
 
 
 def test_one_plan_many_threads(xh):
