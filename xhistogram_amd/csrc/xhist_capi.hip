@@ -566,12 +566,9 @@ extern "C" int xhist_moments(int device, const xhist_array* a, int64_t n_rows, i
   if (int rc = g.set(device)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int grid = 1024;
+  ScratchScope scratch(s);
   double* d_part = nullptr;
-  auto done = [&](int code) {
-    if (d_part) (void)scratch_free(d_part, s);
-    return code;
-  };
-  if (scratch_malloc((void**)&d_part, sizeof(double) * 5 * grid, s) != hipSuccess) return done(fail(XHIST_ERR_NOMEM, "device allocation failed"));
+  if (scratch.alloc((void**)&d_part, sizeof(double) * 5 * grid) != hipSuccess) return fail(XHIST_ERR_NOMEM, "device allocation failed");
   std::vector<double> part(5 * grid);
   auto pass = [&](int which, double mean) -> int {
     hipLaunchKernelGGL(moments_kernel, dim3(grid), dim3(256), 0, s, a->data, a->dtype, a->row_stride, a->col_stride, a->inner_rows, a->outer_stride,
@@ -581,7 +578,7 @@ extern "C" int xhist_moments(int device, const xhist_array* a, int64_t n_rows, i
       return fail(XHIST_ERR_HIP, "moments kernel failed: %s", hipGetErrorString(hipGetLastError()));
     return XHIST_OK;
   };
-  if (int rc = pass(0, 0.0)) return done(rc);
+  if (int rc = pass(0, 0.0)) return rc;
   double cnt = 0.0, mn = HUGE_VAL, mx = -HUGE_VAL, sum = 0.0;
   bool nan = false;
   for (int b = 0; b < grid; ++b) {
@@ -597,12 +594,12 @@ extern "C" int xhist_moments(int device, const xhist_array* a, int64_t n_rows, i
   result[3] = cnt > 0.0 ? sum / cnt : NAN;
   result[4] = NAN;
   if (want_m2 && cnt > 0.0 && !nan) {
-    if (int rc = pass(1, result[3])) return done(rc);
+    if (int rc = pass(1, result[3])) return rc;
     double m2 = 0.0;
     for (int b = 0; b < grid; ++b) m2 += part[5 * b];
     result[4] = m2;
   }
-  return done(XHIST_OK);
+  return XHIST_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -624,26 +621,29 @@ extern "C" int xhist_minmax(int device, const xhist_array* a, int64_t n_rows, in
     if (int rc = stage_chunk(*a, 0, n_rows, 0, n_cols, st, &view, s)) { stage_free(st, s); return rc; }
   }
   const int grid = 1024;
+  ScratchScope scratch(s);
   double* d_part = nullptr;
-  auto done = [&](int code) {
-    if (d_part) (void)scratch_free(d_part, s);
+  if (scratch.alloc((void**)&d_part, sizeof(double) * 3 * grid) != hipSuccess) {
     stage_free(st, s);
-    return code;
-  };
-  if (scratch_malloc((void**)&d_part, sizeof(double) * 3 * grid, s) != hipSuccess) return done(fail(XHIST_ERR_NOMEM, "device allocation failed"));
+    return fail(XHIST_ERR_NOMEM, "device allocation failed");
+  }
   // contiguous float data (the usual `bins=int` on a whole array): the vectorised kernel
   const bool flat = (view.dtype == XHIST_F64 || view.dtype == XHIST_F32) && view.inner_rows == 0 && (n_cols == 1 || view.col_stride == 1) &&
                     (n_rows == 1 || view.row_stride == n_cols) && ((uintptr_t)view.data % (size_t)dtype_size(view.dtype)) == 0;
-  if (flat)  // (`bins=int` on a whole float array is a first call's shape too: these two live in the hot code object)
-    (void)xhist_hot_minmax_flat(view.dtype == XHIST_F64, view.data, n_rows * n_cols, d_part, grid, s);
-  else
+  hipError_t launched;
+  if (flat) {  // (`bins=int` on a whole float array is a first call's shape too: these two live in the hot code object)
+    launched = (hipError_t)xhist_hot_minmax_flat(view.dtype == XHIST_F64, view.data, n_rows * n_cols, d_part, grid, s);
+  } else {
     hipLaunchKernelGGL(minmax_kernel, dim3(grid), dim3(256), 0, s, view.data, view.dtype, view.row_stride, view.col_stride, view.inner_rows,
                        view.outer_stride, n_rows, n_cols, d_part);
+    launched = hipGetLastError();
+  }
+  stage_free(st, s);  // (stream-ordered: nothing reuses the staged copy before the kernel above has read it)
+  if (launched != hipSuccess) return fail(XHIST_ERR_HIP, "min/max kernel failed: %s", hipGetErrorString(launched));
   std::vector<double> part(3 * grid);
-  if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(part.data(), d_part, sizeof(double) * 3 * grid, hipMemcpyDeviceToHost, s) != hipSuccess ||
+  if (hipMemcpyAsync(part.data(), d_part, sizeof(double) * 3 * grid, hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return done(fail(XHIST_ERR_HIP, "min/max kernel failed: %s", hipGetErrorString(hipGetLastError())));
+    return fail(XHIST_ERR_HIP, "min/max kernel failed: %s", hipGetErrorString(hipGetLastError()));
   double mn = HUGE_VAL, mx = -HUGE_VAL;
   bool nan = false;
   for (int b = 0; b < grid; ++b) {
@@ -653,5 +653,5 @@ extern "C" int xhist_minmax(int device, const xhist_array* a, int64_t n_rows, in
   }
   result[0] = nan ? NAN : mn;
   result[1] = nan ? NAN : mx;
-  return done(XHIST_OK);
+  return XHIST_OK;
 }

@@ -55,6 +55,37 @@ static const xhist_array& array_at(const xhist_array* samples, const xhist_array
   return d < D ? samples[d] : *weights;
 }
 
+// The Params fields both forms of the partitioned mode share: rows of unit column stride, the tables, the histogram and its
+// partitions.  Each caller adds its own: segs, n_rows, and the record streams or parts_per_row.
+static Params partitioned_params(const xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_cols,
+                                 void* out, const TableSet& tset, int32_t table_words, int shift, int n_parts) {
+  Params kp;
+  memset(&kp, 0, sizeof kp);
+  for (int d = 0; d < p->n_dims; ++d) {
+    kp.s_ptr[d] = samples[d].data;
+    kp.s_rs[d] = samples[d].row_stride;
+    kp.s_cs[d] = 1;
+    kp.s_dt[d] = samples[d].dtype;
+    kp.dim[d] = tset.dim[d];
+  }
+  if (weights) {
+    kp.w_ptr = weights->data;
+    kp.w_rs = weights->row_stride;
+    kp.w_cs = 1;
+    kp.w_dt = weights->dtype;
+  }
+  kp.n_dims = p->n_dims;
+  kp.tables = tset.blob;
+  kp.table_words = table_words;
+  kp.tables_in_lds = 1;
+  kp.n_cols = n_cols;
+  kp.n_bins = p->n_bins;
+  kp.out = out;
+  kp.part_shift = shift;
+  kp.n_parts = n_parts;
+  return kp;
+}
+
 // Partitioned mode (xhist_partition.hip.h): count -> prefix -> scatter -> accumulate, all on
 // `stream`, scratch from the stream-ordered allocator (so concurrent callers never share it).
 static int execute_partitioned(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_cols, void* out,
@@ -87,107 +118,62 @@ static int execute_partitioned(xhist_plan* p, const xhist_array* samples, const 
   const int G = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)p->cus * per_cu, n_tiles));
   const int Gb = (int)std::max<int64_t>(1, std::min<int64_t>(p->cus, (n_cols + 65535) / 65536));
 
+  ScratchScope scratch(stream);
   uint32_t* d_counts = nullptr;
   uint64_t *d_base = nullptr, *d_offsets = nullptr;
   uint16_t* d_codes = nullptr;
   void* d_w = nullptr;  // record weights: float64, or float32 when the caller's weights are
   uint32_t* d_flat = nullptr;
-  auto release = [&](int rc) {
-    if (d_flat) (void)scratch_free(d_flat, stream);
-    if (d_counts) (void)scratch_free(d_counts, stream);
-    if (d_base) (void)scratch_free(d_base, stream);
-    if (d_offsets) (void)scratch_free(d_offsets, stream);
-    if (d_codes) (void)scratch_free(d_codes, stream);
-    if (d_w) (void)scratch_free(d_w, stream);
-    return rc;
-  };
-#define HIPR(expr)                                                                                     \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return release(fail(XHIST_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); \
-  } while (0)
-  HIPR(scratch_malloc((void**)&d_counts, (size_t)G * n_parts * 4, stream));
-  HIPR(scratch_malloc((void**)&d_base, (size_t)G * n_parts * 8, stream));
-  HIPR(scratch_malloc((void**)&d_offsets, (size_t)(n_parts + 1) * 8, stream));
-  HIPR(scratch_malloc((void**)&d_flat, (size_t)n_tiles * kPartTile * 4, stream));
+  HIPC(scratch.alloc((void**)&d_counts, (size_t)G * n_parts * 4));
+  HIPC(scratch.alloc((void**)&d_base, (size_t)G * n_parts * 8));
+  HIPC(scratch.alloc((void**)&d_offsets, (size_t)(n_parts + 1) * 8));
+  HIPC(scratch.alloc((void**)&d_flat, (size_t)n_tiles * kPartTile * 4));
   const size_t n_rec = (size_t)n_cols + (size_t)G * n_parts * grp;  // every slice rounded up to whole groups
-  HIPR(scratch_malloc((void**)&d_codes, n_rec * 2 + 16, stream));
+  HIPC(scratch.alloc((void**)&d_codes, n_rec * 2 + 16));
   const bool rec_f32 = wdt == XHIST_F32;
-  if (weighted) HIPR(scratch_malloc(&d_w, n_rec * (rec_f32 ? 4 : 8) + 16, stream));
+  if (weighted) HIPC(scratch.alloc(&d_w, n_rec * (rec_f32 ? 4 : 8) + 16));
 
-  Params kp;
-  memset(&kp, 0, sizeof kp);
-  const DimTable* dims = tset.dim;
-  for (int d = 0; d < D; ++d) {
-    kp.s_ptr[d] = samples[d].data;
-    kp.s_rs[d] = samples[d].row_stride;
-    kp.s_cs[d] = 1;
-    kp.s_dt[d] = samples[d].dtype;
-    kp.dim[d] = dims[d];
-  }
-  if (weighted) {
-    kp.w_ptr = weights->data;
-    kp.w_rs = weights->row_stride;
-    kp.w_cs = 1;
-    kp.w_dt = weights->dtype;
-  }
-  kp.n_dims = D;
-  kp.tables = tset.blob;
-  kp.table_words = table_words;
-  kp.tables_in_lds = 1;
+  Params kp = partitioned_params(p, samples, weights, n_cols, out, tset, table_words, shift, n_parts);
   kp.n_rows = 1;
-  kp.n_cols = n_cols;
-  kp.n_bins = p->n_bins;
-  kp.out = out;
   kp.segs = G;
   kp.part_counts = d_counts;
   kp.part_base = d_base;
   kp.part_codes = d_codes;
   kp.part_w = static_cast<double*>(d_w);
-  kp.part_shift = shift;
-  kp.n_parts = n_parts;
 
-  if (lds_count > 48 * 1024) HIPR(hipFuncSetAttribute((const void*)k_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_count));
-  if (lds_scatter > 48 * 1024) HIPR(hipFuncSetAttribute((const void*)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_scatter));
+  HIPC(set_dynamic_lds((const void*)k_count, lds_count));
+  HIPC(set_dynamic_lds((const void*)k_scatter, lds_scatter));
   kernel_fn_acc k_acc = weighted ? (rec_f32 ? (kernel_fn_acc)part_accumulate<true, float> : (kernel_fn_acc)part_accumulate<true, double>)
                                  : (kernel_fn_acc)part_accumulate<false, double>;
-  if (lds_acc > 48 * 1024) HIPR(hipFuncSetAttribute((const void*)k_acc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_acc));
+  HIPC(set_dynamic_lds((const void*)k_acc, lds_acc));
 
   if (first)  // one timing record per execute: opened before the first row's kernels, closed after the last row's
-    if (int rrc = rec.begin(kn.profile)) return release(rrc);
+    if (int rrc = rec.begin(kn.profile)) return rrc;
   XH_LAUNCH_PICKED(k_count, dim3(G), dim3(kPartBlock), lds_count, stream, kp, d_flat);
-  HIPR(hipGetLastError());
+  HIPC(hipGetLastError());
   hipLaunchKernelGGL(part_prefix, dim3(1), dim3(1024), 0, stream, (const uint32_t*)d_counts, G, n_parts, grp, d_offsets, d_base);
-  HIPR(hipGetLastError());
+  HIPC(hipGetLastError());
   XH_LAUNCH_PICKED(k_scatter, dim3(G), dim3(kPartBlock), lds_scatter, stream, (const uint32_t*)d_flat,
                      weighted ? weights->data : nullptr, n_cols, (const uint64_t*)d_base, d_codes, d_w, shift, n_parts);
-  HIPR(hipGetLastError());
+  HIPC(hipGetLastError());
   XH_LAUNCH_PICKED(k_acc, dim3(Gb), dim3(1024), lds_acc, stream, (const uint16_t*)d_codes, (const void*)d_w,
                      (const uint64_t*)d_offsets, out, p->n_bins, shift, n_parts);
-  HIPR(hipGetLastError());
-  {
-    char desc[384];
-    snprintf(desc, sizeof desc,
-             "family=fast hist=partitioned parts=%d bins_per_part=%d group=%d vec=%d tile=%d block=%d grid=%d acc_grid=%d "
-             "lds_count=%zu lds_scatter=%zu lds_acc=%zu scan=%d weighted=%d D=%d cmp=%s",
-             n_parts, 1 << shift, grp, vec, kPartTile, kPartBlock, G, Gb, lds_count, lds_scatter, lds_acc, scan, (int)weighted, D,
-             use_f32 ? "f32thr" : "f64");
-    if (last)
-      if (int rrc = rec.end(desc)) return release(rrc);
-  }
-#undef HIPR
-  return release(XHIST_OK);
+  HIPC(hipGetLastError());
+  if (!last) return XHIST_OK;
+  char desc[384];
+  snprintf(desc, sizeof desc,
+           "family=fast hist=partitioned parts=%d bins_per_part=%d group=%d vec=%d tile=%d block=%d grid=%d acc_grid=%d "
+           "lds_count=%zu lds_scatter=%zu lds_acc=%zu scan=%d weighted=%d D=%d cmp=%s",
+           n_parts, 1 << shift, grp, vec, kPartTile, kPartBlock, G, Gb, lds_count, lds_scatter, lds_acc, scan, (int)weighted, D,
+           use_f32 ? "f32thr" : "f64");
+  return rec.end(desc);
 }
 
-// Partitioned mode in one routing pass (xhist_route.hip.h): zero the chunk counters -> part_route ->
-// part_accumulate_chunks, all on `stream`.  Returns XHIST_ERR_UNSUPPORTED (nothing launched) for what only
-// the multi-pass form takes: more than 128 partitions, tables that do not fit LDS next to the sort buffers,
-// in-bucket scans of 3 or 4 edges, integer samples.
 // The exchange mode's kernel wants every compute unit for itself (256 persistent workgroups that wait for one another): two
 // of them running on two streams of one GPU would each hold part of the chip and wait for the rest until their deadlines.
 // So a call whose stream is not the one the last exchange kernel of this device went to looks at that kernel's event first
 // and takes the classic passes when it has not finished.  (Other people's kernels on other streams can still hold compute
-// units back; that costs the deadline once and takes the plan off the mode — execute_partitioned_fused.)
+// units back; that costs the deadline once and takes the plan off the mode — exchange_bookkeeping.)
 struct ExchInFlight {
   std::mutex mu;
   hipEvent_t ev = nullptr;
@@ -197,6 +183,12 @@ struct ExchInFlight {
 static ExchInFlight& exch_in_flight(int device) {
   static ExchInFlight slots[64];
   return slots[device & 63];
+}
+// fl.mu held: the last exchange kernel of this device went to another stream and may still be running
+static bool exchange_running_elsewhere(ExchInFlight& fl, hipStream_t stream) {
+  const bool busy = fl.armed && fl.stream != stream && hipEventQuery(fl.ev) == hipErrorNotReady;
+  (void)hipGetLastError();
+  return busy;
 }
 
 static bool exact_records_env() {
@@ -244,6 +236,321 @@ static RouteGeom route_geom_for(const PlanKnobs& kn, int sdt, int wdt /* -1: cou
   return g;
 }
 
+// ---- execute_partitioned_fused and its steps ----------------------------------------------------------------------------
+
+// The pinned host words the GPU writes for a plan: [0] a call met weights of both signs, [1] a chunk pool ran dry, [2..5] the
+// exchange mode's notes (ExchArgs::note).
+static void ensure_mixed_hint(xhist_plan* p) {
+  if (p->mixed_hint) return;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->mixed_hint) return;
+  uint32_t* h = nullptr;
+  if (hipHostMalloc((void**)&h, 64, hipHostMallocDefault) == hipSuccess) { memset(h, 0, 64); p->mixed_hint = h; }
+  else (void)hipGetLastError();
+}
+
+// An exchange kernel of an earlier call gave up IN FLIGHT (a wait that outlived its deadline, a placement other than 32
+// workgroups per XCD) and the classic passes took that call: the plan stays away from the mode for its next 16 eligible
+// calls, twice as many after every further abort (a second hang would cost its deadline again), and is admitted again after
+// that; a clean call resets the count.  (Workgroups that were not all resident at the START cost arrive_ticks, not the
+// deadline, and do not count: note[5].)  "exchange" set again forgets all of it.  Returns the calls still to skip.
+static int exchange_bookkeeping(xhist_plan* p) {
+  std::lock_guard<std::mutex> lk(p->mu);
+  ExchangeState& xs = p->exch;
+  if (p->mixed_hint) {
+    if (p->mixed_hint[2] != xs.aborts_seen) {
+      xs.aborts_seen = p->mixed_hint[2];
+      xs.skip = xs.backoff;
+      xs.backoff = std::min(xs.backoff * 2, 4096);
+    } else if (xs.skip > 0) {
+      xs.skip -= 1;
+    } else if (xs.ran_last) {
+      xs.backoff = 16;
+    }
+    xs.ran_last = false;
+  }
+  return xs.skip;
+}
+
+// The routing and adding-up passes of one call: kernels, records, LDS, grids and the chunk pool.
+struct RoutePlan {
+  kernel_fn_route k_route = nullptr, k_route48 = nullptr;  // (k_route48: packed records only)
+  kernel_fn_acc_chunks k_acc = nullptr, k_acc48 = nullptr;
+  bool pack = false;  // packed 8-byte records first (float64 weights), exact ones only if both signs turn up
+  int block = 0, tile = 0;
+  int32_t table_words = 0;
+  size_t lds_route = 0, lds_acc = 0;
+  int G = 0, Gb = 0;  // workgroups of the routing / adding-up pass
+  int lg = 0;         // log2 of the records per chunk
+  int64_t pool_chunks = 0, ctr_words = 0;
+};
+
+// Decided before anything is allocated or launched: XHIST_ERR_UNSUPPORTED where the LDS or the chunk pool does not fit.
+static int plan_route(const xhist_plan* p, const PlanKnobs& kn, kernel_fn_route k_route, int sdt, int wdt, bool weighted, int scan,
+                      const TableSet& tset, int shift, int n_parts, int rows, int64_t n_cols, RouteGeom geom, RoutePlan& rp) {
+  const int D = p->n_dims;
+  const int block = geom.block, spl = geom.spl;
+  rp.k_route = k_route;
+  rp.block = block;
+  rp.pack = weighted && wdt == XHIST_F64 && kn.records48_pref >= 0 && !exact_records_env();
+  if (rp.pack && (!p->mixed_hint || *p->mixed_hint != 0u)) rp.pack = false;  // (earlier calls met both signs: straight to exact records)
+  rp.k_route48 = rp.pack ? route_kernel(sdt, kWdtPacked48, D, scan, rows > 1, block, spl) : nullptr;
+  if (rp.pack && !rp.k_route48) rp.pack = false;
+  const bool rec_f32 = wdt == XHIST_F32;
+  rp.k_acc = weighted ? (rec_f32 ? (kernel_fn_acc_chunks)part_accumulate_chunks<true, float>
+                                 : (kernel_fn_acc_chunks)part_accumulate_chunks<true, double>)
+                      : (kernel_fn_acc_chunks)part_accumulate_chunks<false, double>;
+  rp.k_acc48 = (kernel_fn_acc_chunks)part_accumulate_chunks<true, double, true>;
+  rp.table_words = scan == kScanArith ? 0 : tset.words;  // arithmetic edges: no tables
+  const int tile = rp.tile = route_tile(block, spl);
+  rp.lds_route = part_route_lds((size_t)rp.table_words * 8, n_parts, weighted, tile, block);
+  const size_t hist_bytes = (size_t)((1u << shift) + 1) * (weighted ? 8 : 4);
+  rp.lds_acc = ((hist_bytes + 15) & ~(size_t)15) + (size_t)kAccBatch * 8 + (size_t)(n_parts + 1) * 4 + 16;
+  if (rp.lds_route > p->lds_max || rp.lds_acc > p->lds_max) return XHIST_ERR_UNSUPPORTED;
+  // (Round 4 also ran the adding-up pass of sample sub-batch k on a second stream under the routing pass of sub-batch k + 1:
+  // 25-60 % slower, both passes scale with the compute units they get — DESIGN_HISTORY 4.2b, profiles/r04_b_*; removed in
+  // round 5.)
+  const int64_t n_piece = n_cols * rows;  // samples one routing pass sees
+  const int64_t n_tiles = ((n_cols + tile - 1) / tile) * rows;
+  // workgroups resident per CU: by LDS — and by registers: the routing pass is held to 128 per lane (waves_per_eu 4), so a
+  // CU holds 1024 of its threads.  (Sized by LDS alone, a 77 KB workgroup of 1024 threads got a grid of 2 per CU, ran it
+  // in two rounds, and 10^7 float64 pairs + weights into 512 x 512 bins took 0.233 ms against 0.170 for the three-pass route.)
+  const int per_cu = std::max<int>(1, std::min<int>(std::min<int>(4, 1024 / block), (int)((size_t)160 * 1024 / rp.lds_route)));
+  rp.G = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)p->cus * per_cu, n_tiles));
+  rp.Gb = (int)std::max<int64_t>(1, std::min<int64_t>(p->cus, (n_piece + 65535) / 65536));
+  if (kn.route_grid) rp.G = (int)std::min<int64_t>(kn.route_grid, n_tiles);
+  if (kn.acc_grid) rp.Gb = kn.acc_grid;
+  // chunk size: a workgroup files at most kRouteListCap chunks (its list lives in LDS), 2^10 .. 2^14 records each
+  int lg = 10;
+  while (lg < 14 && (((n_piece / rp.G) + tile) >> lg) + n_parts + 16 > route_list_cap(block)) ++lg;
+  rp.lg = lg;
+  const int64_t GP = (int64_t)rp.G * n_parts;
+  // Chunks that hold records: every chunk but the one in use by its (workgroup, partition) owner is full, and at most 7
+  // padding records are added per owner.  Ids taken from the pool but never used: a workgroup's stock drops fewer ids than
+  // its largest request whenever a range of `batch` ids runs out (batch >= 8 x that request: < 1/7 of the ids it served),
+  // and ends with at most two ranges in hand.
+  const int64_t used = ((n_piece + 7 * GP) >> lg) + GP;
+  rp.pool_chunks = used + used / 6 + (int64_t)rp.G * (2 * route_batch(n_parts, lg, tile) + 2 * route_max_need(lg, tile)) + 64;
+  // "route_pool_pct" < 100 (tests): a pool too small on purpose — what finds no chunk goes straight into the output
+  if (kn.route_pool_pct > 0 && kn.route_pool_pct < 100) rp.pool_chunks = std::max<int64_t>(1, rp.pool_chunks * kn.route_pool_pct / 100);
+  if (rp.pool_chunks >= ((int64_t)1 << 31) || (rp.pool_chunks << lg) >= ((int64_t)1 << 44)) return XHIST_ERR_UNSUPPORTED;
+  rp.ctr_words = (2 + n_parts + 1) / 2 + 1;  // [0] pool, [1] signs seen, [2 .. 2 + P) chunks filed per partition; two sets (packed + exact)
+  return XHIST_OK;
+}
+
+// The exchange mode (xhist_exchange.hip.h): packed records that never go through HBM — one persistent workgroup per compute
+// unit keeps rows of a WINDOW of the histogram in LDS, records travel through rings inside each XCD.  Offered for float64
+// samples + float64 weights on arithmetic edges, one row, on the 8 x 32-CU chip; whether a call takes it is decided on the
+// GPU by the probe (the window must hold >= 88 % of the samples) — the classic packed kernels are queued all the same
+// and return at once when it does.  "exchange" = -1 / 1: never / whenever it can run (any size, any coverage: tests).
+struct ExchPlan {
+  bool on = false;     // eligible: the exchange kernels are launched unless their occupancy or another stream's exchange kernel says no
+  bool exact = false;  // full float64 records: 12 bytes through two rings
+  kernel_fn_exch k_xch = nullptr, k_xprobe = nullptr;
+  size_t lds = 0;
+  // one block for everything that is zeroed per call (one launch): control words | window, cold arguments, probe counts | side copy | rings
+  size_t ctl_bytes = 0, words_bytes = 0, side_bytes = 0, rings_bytes = 0;
+  ExchArgs xa;  // everything but the scratch pointers and the sign word
+};
+
+static ExchPlan plan_exchange(const xhist_plan* p, const PlanKnobs& kn, const xhist_array* samples, const xhist_array* weights,
+                              int64_t n_cols, int rows, int sdt, int wdt, bool pack, int exch_skip) {
+  const int D = p->n_dims;
+  ExchPlan xp;
+  memset(&xp.xa, 0, sizeof xp.xa);
+  // float64 weights that travel as FULL float64 records ("records48" = -1, XHIST_AMD_EXACT_RECORDS, or a plan that has met weights of
+  // both signs): the exchange mode takes these too, with 12-byte records through two rings (part_exchange<D, true>, round 6)
+  // (by default for joint histograms only: measured over the shape matrix of tools/exchange_cliffs.py with exact records,
+  //  3*10^8 samples, 2-3 inputs read 0.93-1.03 of the classic exact passes — whose own time moves by 10 % from process to process
+  //  and size to size with the placement of their five streams, while this form does not: C5 4.14-4.18 ms in every process against
+  //  4.09 | 4.50-4.53 — and ONE input reads 1.08-1.11: profiles/r06_e_*)
+  const bool xexact = weights && wdt == XHIST_F64 && !pack && rows == 1 && (D >= 2 || kn.exchange_pref > 0);
+  if (!((pack || xexact) && rows == 1 && kn.exchange_pref >= 0 && (exch_skip == 0 || kn.exchange_pref > 0) && sdt == XHIST_F64 && p->arith &&
+        kn.arith_pref >= 0 && D <= 3 && p->cus == kExchXcds * kExchRings &&
+        p->n_bins <= ((int64_t)1 << 23) /* (the side copy is zeroed per call) */ && (kn.exchange_pref > 0 || n_cols >= ((int64_t)1 << 25))))
+    return xp;
+  const int64_t L = D >= 2 ? (int64_t)p->ts[0][0].dim[D - 1].nb : 256;
+  const int64_t hist_rows = D >= 2 ? p->n_bins / L : (p->n_bins + 255) / 256;
+  const int64_t units = (hist_rows + kExchUnitRows - 1) / kExchUnitRows;
+  const int64_t max_local = xexact ? kExchMaxLocalExact : kExchMaxLocal;
+  const int64_t rows_per = L <= max_local ? std::min<int64_t>(max_local / L, units) : 0;
+  xp.k_xch = xhist_pick_exchange(D, xexact);
+  xp.k_xprobe = xhist_pick_exchange_probe(D);
+  xp.lds = rows_per >= 1 ? exchange_lds((int)(rows_per * L), xexact) : 0;
+  if (!(rows_per >= 1 && units <= 4096 && xp.k_xch && xp.k_xprobe && xp.lds <= p->lds_max)) return xp;
+  xp.on = true;
+  xp.exact = xexact;
+  ExchArgs& xa = xp.xa;
+  xa.row_len = L;
+  xa.n_hist_rows = hist_rows;
+  xa.rows_per = (int32_t)rows_per;
+  xa.local_bins = (int32_t)(rows_per * L);
+  xa.n_units = (int32_t)units;
+  xa.force = kn.exchange_pref > 0 ? 1 : 0;
+  { int64_t p2 = 1; while (p2 * 2 <= L) p2 *= 2; xa.side_rot_mask = (int32_t)(p2 - 1); }
+  xa.min_ppm = kn.exchange_min_pct > 0 ? kn.exchange_min_pct * 10000 : kExchMinPpm;
+  xa.max_uneven_ppm = 1250000;
+  xa.budget_ticks = kn.exchange_budget_ms < 0 ? 0 : (long long)(kn.exchange_budget_ms ? kn.exchange_budget_ms : 500) * 100000;
+  xa.arrive_ticks = (long long)(kn.exchange_arrive_us > 0 ? kn.exchange_arrive_us : 200) * 100;  // 200 us: the launch of 256 workgroups on a free chip takes a few
+  for (int d = 0; d < D; ++d) {  // (the arithmetic-edge constants of the float64 table set, whatever the classic routing pass digitizes with)
+    const DimTable& t = p->ts[0][0].dim[d];
+    xa.s_ptr[d] = static_cast<const double*>(samples[d].data);
+    xa.dim[d].e0 = t.e0_f;
+    xa.dim[d].eL = t.eL_f;
+    xa.dim[d].step = t.step;
+    xa.dim[d].inv_step = t.inv_step;
+    xa.dim[d].arith_h = t.arith_h;
+    xa.dim[d].nb = t.nb;
+  }
+  xa.w_ptr = static_cast<const double*>(weights->data);
+  xa.n = n_cols;
+  xa.note = p->mixed_hint;
+  xp.words_bytes = ((size_t)(units + kExchRings + 8 + 32) * 4 + 7) & ~(size_t)7;  // win[8], the cold arguments (32 words), the probe's counts (units, then owners)
+  xp.ctl_bytes = sizeof(ExchCtl) * kExchXcds;
+  xp.side_bytes = (size_t)(hist_rows * L) * 8;  // (whole rows: exch_side_index rotates inside a row)
+  xp.rings_bytes = (size_t)kExchXcds * kExchRings * kExchRings * kExchCap * (xexact ? 12 : 8);  // (exact records: the ring of low bits behind the ring of packed words)
+  static_assert(sizeof(ExchCtl) % 8 == 0, "the block's parts stay 8-byte aligned");
+  return xp;
+}
+
+// Every workgroup of the exchange kernel must be resident (they wait for one another): one per compute unit is what its LDS
+// and registers must allow.  Asked once per plan, kernel and LDS size (a kernel of the host's that holds compute units at run
+// time is the deadline's business).
+static bool exchange_fits(xhist_plan* p, kernel_fn_exch k, size_t lds) {
+  {
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (p->exch.occ_fn == (const void*)k && p->exch.occ_lds == lds) return p->exch.occ_ok;
+  }
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k, kExchBlock, lds) != hipSuccess) { per_cu = 0; (void)hipGetLastError(); }
+  std::lock_guard<std::mutex> lk(p->mu);
+  p->exch.occ_fn = (const void*)k;
+  p->exch.occ_lds = lds;
+  p->exch.occ_ok = per_cu >= 1;
+  return p->exch.occ_ok;
+}
+
+// The call's scratch: the chunk pool and its counters (returned as the RouteArgs of the first counter set), and the exchange
+// mode's blocks when it is on.  Ends with the kernels' LDS limits raised; clears xp.on when the exchange kernel cannot be resident.
+static int alloc_fused(ScratchScope& scratch, xhist_plan* p, const RoutePlan& rp, int n_parts, bool weighted, bool rec_f32,
+                       ExchPlan& xp, RouteArgs& ra) {
+  const size_t plist_elems = (size_t)n_parts * rp.pool_chunks, pool_recs = ((size_t)rp.pool_chunks << rp.lg);
+  memset(&ra, 0, sizeof ra);
+  HIPC(scratch.alloc((void**)&ra.pool, (size_t)rp.ctr_words * 8 * 2));  // (two counter sets of ctr_words 8-byte words each)
+  HIPC(scratch.alloc((void**)&ra.plist, plist_elems * 4));
+  HIPC(scratch.alloc((void**)&ra.cmeta, (size_t)rp.pool_chunks * 4));
+  HIPC(scratch.alloc((void**)&ra.codes, pool_recs * 2));
+  if (weighted) HIPC(scratch.alloc(&ra.wrec, pool_recs * (rec_f32 ? 4 : 8)));
+  ra.pcount = ra.pool + 2;
+  ra.list_cap = (uint32_t)rp.pool_chunks;
+  ra.chunk_log2 = rp.lg;
+  ra.flags = ra.pool + 1;
+  ra.dry = p->mixed_hint ? p->mixed_hint + 1 : nullptr;
+
+  if (xp.on) {
+    void *x_ctl = nullptr, *x_part = nullptr;
+    ExchArgs& xa = xp.xa;
+    HIPC(scratch.alloc(&x_ctl, xp.ctl_bytes + xp.words_bytes + xp.side_bytes + xp.rings_bytes));
+    HIPC(scratch.alloc(&x_part, (size_t)kExchXcds * kExchRings * (size_t)xa.local_bins * 8));
+    char* const base = static_cast<char*>(x_ctl);
+    xa.ctl = static_cast<ExchCtl*>(x_ctl);
+    xa.win = reinterpret_cast<uint32_t*>(base + xp.ctl_bytes);
+    xa.side = reinterpret_cast<double*>(base + xp.ctl_bytes + xp.words_bytes);
+    xa.rings = reinterpret_cast<uint64_t*>(base + xp.ctl_bytes + xp.words_bytes + xp.side_bytes);
+    xa.rings_lo = xp.exact ? reinterpret_cast<uint32_t*>(xa.rings + (size_t)kExchXcds * kExchRings * kExchRings * kExchCap) : nullptr;
+    xa.part = static_cast<double*>(x_part);
+    xa.cold = reinterpret_cast<ExchCold*>(xa.win + 8);
+    static_assert(sizeof(ExchCold) <= 32 * 4, "the cold arguments fit their 32 words");
+    xa.counts = xa.win + 8 + 32;
+    xa.flags = ra.pool + 1;
+    HIPC(set_dynamic_lds((const void*)xp.k_xch, xp.lds));
+    if (!exchange_fits(p, xp.k_xch, xp.lds)) xp.on = false;
+  }
+
+  HIPC(set_dynamic_lds((const void*)rp.k_route, rp.lds_route));
+  HIPC(set_dynamic_lds((const void*)rp.k_acc, rp.lds_acc));
+  if (rp.pack) {
+    HIPC(set_dynamic_lds((const void*)rp.k_route48, rp.lds_route));
+    HIPC(set_dynamic_lds((const void*)rp.k_acc48, rp.lds_acc));
+  }
+  return XHIST_OK;
+}
+
+// The exchange kernels of one call: zero their block, probe, pick, exchange.  Clears xp.on (and launches nothing) while an
+// exchange kernel of another stream may still be running on this device.
+static int launch_exchange(xhist_plan* p, hipStream_t stream, ExchPlan& xp) {
+  // Invariant: at most one exchange kernel per device is in flight at a time, so two of them never each hold part of the chip
+  // and wait for the rest.  The lock is held from the look at the last exchange kernel's event to the record of this call's, so
+  // two host threads that both see "idle" can never both launch one.
+  ExchInFlight& fl = exch_in_flight(p->device);
+  std::lock_guard<std::mutex> lk(fl.mu);
+  if (exchange_running_elsewhere(fl, stream)) {
+    xp.on = false;
+    return XHIST_OK;
+  }
+  const ExchArgs& xa = xp.xa;
+  if (int zrc = zero_output(xa.ctl, (int64_t)((xp.ctl_bytes + xp.words_bytes + xp.side_bytes + xp.rings_bytes) / 8), stream)) return zrc;
+  // (the probe always runs: a histogram that fits the window has nothing outside it, but its owners' loads must be even too)
+  XH_LAUNCH_PICKED(xp.k_xprobe, dim3(256), dim3(256), 0, stream, xa);
+  HIPC(hipGetLastError());
+  XH_LAUNCH_PICKED(xhist_pick_exchange_pick(), dim3(1), dim3(64), 0, stream, xa);
+  HIPC(hipGetLastError());
+  XH_LAUNCH_PICKED(xp.k_xch, dim3(kExchXcds * kExchRings), dim3(kExchBlock), xp.lds, stream, xa);
+  HIPC(hipGetLastError());
+  if (!fl.ev && hipEventCreateWithFlags(&fl.ev, hipEventDisableTiming) != hipSuccess) { fl.ev = nullptr; (void)hipGetLastError(); }
+  if (fl.ev && hipEventRecord(fl.ev, stream) == hipSuccess) { fl.stream = stream; fl.armed = true; }
+  else { fl.armed = false; (void)hipGetLastError(); }
+  return XHIST_OK;
+}
+
+// Zero the counters, the exchange kernels when the mode is on, then the routing and adding-up passes (packed, then exact, when
+// packing) and the exchange mode's merge.  `ra`: the first counter set (alloc_fused); kp's part fields describe the pass.
+static int launch_fused(xhist_plan* p, hipStream_t stream, const Params& kp, const RoutePlan& rp, RouteArgs ra, ExchPlan& xp) {
+  uint32_t* const ctr = ra.pool;
+  void* const out = kp.out;
+  const int shift = kp.part_shift, n_parts = kp.n_parts, rows = (int)kp.n_rows, parts_per_row = kp.parts_per_row;
+  if (int zrc = zero_output(ctr, rp.ctr_words * 2, stream)) return zrc;
+  if (xp.on)
+    if (int xrc = launch_exchange(p, stream, xp)) return xrc;
+  if (xp.on) {
+    std::lock_guard<std::mutex> lk(p->mu);
+    p->exch.ran_last = true;
+    ra.xgate = xp.xa.win + 1;  // the classic packed kernels below return at once when the mode took the call
+  }
+  RouteArgs ra48 = ra;
+  if (rp.pack) {
+    XH_LAUNCH_PICKED(rp.k_route48, dim3(rp.G), dim3(rp.block), rp.lds_route, stream, kp, ra);  // packed records, notes the signs
+    HIPC(hipGetLastError());
+    ra48.gate = ctr + 1;
+    ra48.gate_mode = 1;  // one sign: add the packed records up
+    // both signs: the exact pass below runs (its own counters: the second set), otherwise its kernels return at once
+    ra.pool = ctr + 2 * rp.ctr_words;
+    ra.pcount = ra.pool + 2;
+    ra.flags = ra.pool + 1;
+    ra.gate = ctr + 1;
+    ra.gate_mode = 2;
+    ra.hint = p->mixed_hint;
+    ra.xgate = nullptr;  // (the exact passes redo the call whenever the sign word says so, exchange mode or not)
+  }
+  XH_LAUNCH_PICKED(rp.k_route, dim3(rp.G), dim3(rp.block), rp.lds_route, stream, kp, ra);
+  HIPC(hipGetLastError());
+  if (rp.pack) {
+    XH_LAUNCH_PICKED(rp.k_acc48, dim3(rp.Gb), dim3(1024), rp.lds_acc, stream, ra48, out, p->n_bins, shift, n_parts, rows > 1 ? parts_per_row : 0);
+    HIPC(hipGetLastError());
+  }
+  XH_LAUNCH_PICKED(rp.k_acc, dim3(rp.Gb), dim3(1024), rp.lds_acc, stream, ra, out, p->n_bins, shift, n_parts, rows > 1 ? parts_per_row : 0);
+  HIPC(hipGetLastError());
+  if (xp.on) {  // (runs when the mode was on and the weights had one sign: exactly when none of the four kernels above did)
+    XH_LAUNCH_PICKED(xhist_pick_exchange_merge(), dim3((unsigned)((p->n_bins + 255) / 256)), dim3(256), 0, stream, xp.xa, static_cast<double*>(out), p->n_bins);
+    HIPC(hipGetLastError());
+  }
+  return XHIST_OK;
+}
+
+// Partitioned mode in one routing pass (xhist_route.hip.h): zero the chunk counters -> part_route ->
+// part_accumulate_chunks, all on `stream`.  Returns XHIST_ERR_UNSUPPORTED (nothing launched) for what only
+// the multi-pass form takes: more than 128 partitions, tables that do not fit LDS next to the sort buffers,
+// in-bucket scans of 3 or 4 edges, integer samples.
 //
 // Packed records (float64 weights).  A record is normally a 16-bit bin code plus the float64 weight: 10 bytes in two streams.
 // Rounding the weight to 36 mantissa bits makes room for the code in its low 16 bits: ONE 8-byte record, 40 instead of 44
@@ -261,346 +568,46 @@ static RouteGeom route_geom_for(const PlanKnobs& kn, int sdt, int wdt /* -1: cou
 static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_cols, void* out,
                                      hipStream_t stream, int sdt, int wdt, int scan, bool use_f32, const TableSet& tset, int shift,
                                      int parts_per_row, const PlanKnobs& kn, LaunchRecord& rec, bool first, bool last, RouteGeom geom, int rows = 1) {
-  const int D = p->n_dims;
   const bool weighted = weights != nullptr;
   const int n_parts = parts_per_row * rows;
-  const int64_t n_total = n_cols * rows;
-  if (n_total >= ((int64_t)1 << 40) || n_cols < 4 || n_parts > 128) return XHIST_ERR_UNSUPPORTED;
-  const int block = geom.block, spl = geom.spl;
-  kernel_fn_route k_route = route_kernel(sdt, wdt, D, scan, rows > 1, block, spl);
+  if (n_cols * rows >= ((int64_t)1 << 40) || n_cols < 4 || n_parts > 128) return XHIST_ERR_UNSUPPORTED;
+  kernel_fn_route k_route = route_kernel(sdt, wdt, p->n_dims, scan, rows > 1, geom.block, geom.spl);
   if (!k_route) return XHIST_ERR_UNSUPPORTED;
-  bool pack = weighted && wdt == XHIST_F64 && kn.records48_pref >= 0 && !exact_records_env();
-  if (!p->mixed_hint) {  // pinned host words the GPU writes: [0] a call met weights of both signs, [1] a chunk pool ran dry
-    std::lock_guard<std::mutex> lk(p->mu);
-    if (!p->mixed_hint) {
-      uint32_t* h = nullptr;
-      if (hipHostMalloc((void**)&h, 64, hipHostMallocDefault) == hipSuccess) { memset(h, 0, 64); p->mixed_hint = h; }
-      else (void)hipGetLastError();
-    }
-  }
-  int exch_skip;
-  {
-    // An exchange kernel of an earlier call gave up IN FLIGHT (a wait that outlived its deadline, a placement other than 32
-    // workgroups per XCD) and the classic passes took that call: the plan stays away from the mode for its next 16 eligible
-    // calls, twice as many after every further abort (a second hang would cost its deadline again), and is admitted again after
-    // that; a clean call resets the count.  (Workgroups that were not all resident at the START cost arrive_ticks, not the
-    // deadline, and do not count: note[5].)  "exchange" set again forgets all of it.
-    std::lock_guard<std::mutex> lk(p->mu);
-    ExchangeState& xs = p->exch;
-    if (p->mixed_hint) {
-      if (p->mixed_hint[2] != xs.aborts_seen) {
-        xs.aborts_seen = p->mixed_hint[2];
-        xs.skip = xs.backoff;
-        xs.backoff = std::min(xs.backoff * 2, 4096);
-      } else if (xs.skip > 0) {
-        xs.skip -= 1;
-      } else if (xs.ran_last) {
-        xs.backoff = 16;
-      }
-      xs.ran_last = false;
-    }
-    exch_skip = xs.skip;
-  }
-  if (pack && (!p->mixed_hint || *p->mixed_hint != 0u)) pack = false;  // (earlier calls met both signs: straight to exact records)
-  kernel_fn_route k_route48 = pack ? route_kernel(sdt, kWdtPacked48, D, scan, rows > 1, block, spl) : nullptr;
-  if (pack && !k_route48) pack = false;
-  // float64 weights that travel as FULL float64 records ("records48" = -1, XHIST_AMD_EXACT_RECORDS, or a plan that has met weights of
-  // both signs): the exchange mode takes these too, with 12-byte records through two rings (part_exchange<D, true>, round 6)
-  // (by default for joint histograms only: measured over the shape matrix of tools/exchange_cliffs.py with exact records,
-  //  3*10^8 samples, 2-3 inputs read 0.93-1.03 of the classic exact passes — whose own time moves by 10 % from process to process
-  //  and size to size with the placement of their five streams, while this form does not: C5 4.14-4.18 ms in every process against
-  //  4.09 | 4.50-4.53 — and ONE input reads 1.08-1.11: profiles/r06_e_*)
-  const bool xexact = weighted && wdt == XHIST_F64 && !pack && rows == 1 && (D >= 2 || kn.exchange_pref > 0);
-  // an exchange kernel of ANOTHER stream may still hold the GPU: looked at before the scratch allocations below, and the lock is
-  // kept until this call's own exchange kernel has been launched and its event recorded (two host threads that both saw "idle"
-  // would otherwise both launch one)
-  bool other_stream_busy = false;
-  std::unique_lock<std::mutex> xfl_lock;
-  if ((pack || xexact) && kn.exchange_pref >= 0) {
+  ensure_mixed_hint(p);
+  const int exch_skip = exchange_bookkeeping(p);
+  RoutePlan rp;
+  if (int rc = plan_route(p, kn, k_route, sdt, wdt, weighted, scan, tset, shift, n_parts, rows, n_cols, geom, rp)) return rc;
+  ExchPlan xp = plan_exchange(p, kn, samples, weights, n_cols, rows, sdt, wdt, rp.pack, exch_skip);
+  if (xp.on) {  // a first look, before the mode's scratch is allocated (launch_exchange looks again, and decides)
     ExchInFlight& fl = exch_in_flight(p->device);
-    xfl_lock = std::unique_lock<std::mutex>(fl.mu);
-    if (fl.armed && fl.stream != stream && hipEventQuery(fl.ev) == hipErrorNotReady) other_stream_busy = true;
-    (void)hipGetLastError();
-    if (other_stream_busy) xfl_lock.unlock();
-  }
-  const int32_t table_words = scan == kScanArith ? 0 : tset.words;  // arithmetic edges: no tables
-  const int tile = route_tile(block, spl);
-  const size_t lds_route = part_route_lds((size_t)table_words * 8, n_parts, weighted, tile, block);
-  const bool rec_f32 = wdt == XHIST_F32;
-  const size_t hist_bytes = (size_t)((1u << shift) + 1) * (weighted ? 8 : 4);
-  const size_t lds_acc = ((hist_bytes + 15) & ~(size_t)15) + (size_t)kAccBatch * 8 + (size_t)(n_parts + 1) * 4 + 16;
-  if (lds_route > p->lds_max || lds_acc > p->lds_max) return XHIST_ERR_UNSUPPORTED;
-  // (Round 4 also ran the adding-up pass of sample sub-batch k on a second stream under the routing pass of sub-batch k + 1:
-  // 25-60 % slower, both passes scale with the compute units they get — DESIGN_HISTORY 4.2b, profiles/r04_b_*; removed in
-  // round 5.)
-  const int64_t n_piece = n_total;  // samples one routing pass sees
-  const int64_t n_tiles = ((n_cols + tile - 1) / tile) * rows;
-  // workgroups resident per CU: by LDS — and by registers: the routing pass is held to 128 per lane (waves_per_eu 4), so a
-  // CU holds 1024 of its threads.  (Sized by LDS alone, a 77 KB workgroup of 1024 threads got a grid of 2 per CU, ran it
-  // in two rounds, and 10^7 float64 pairs + weights into 512 x 512 bins took 0.233 ms against 0.170 for the three-pass route.)
-  const int per_cu = std::max<int>(1, std::min<int>(std::min<int>(4, 1024 / block), (int)((size_t)160 * 1024 / lds_route)));
-  int G = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)p->cus * per_cu, n_tiles));
-  int Gb = (int)std::max<int64_t>(1, std::min<int64_t>(p->cus, (n_piece + 65535) / 65536));
-  if (kn.route_grid) G = (int)std::min<int64_t>(kn.route_grid, n_tiles);
-  if (kn.acc_grid) Gb = kn.acc_grid;
-  // chunk size: a workgroup files at most kRouteListCap chunks (its list lives in LDS), 2^10 .. 2^14 records each
-  int lg = 10;
-  while (lg < 14 && (((n_piece / G) + tile) >> lg) + n_parts + 16 > route_list_cap(block)) ++lg;
-  const int64_t GP = (int64_t)G * n_parts;
-  // Chunks that hold records: every chunk but the one in use by its (workgroup, partition) owner is full, and at most 7
-  // padding records are added per owner.  Ids taken from the pool but never used: a workgroup's stock drops fewer ids than
-  // its largest request whenever a range of `batch` ids runs out (batch >= 8 x that request: < 1/7 of the ids it served),
-  // and ends with at most two ranges in hand.
-  const int64_t used = ((n_piece + 7 * GP) >> lg) + GP;
-  int64_t pool_chunks = used + used / 6 + (int64_t)G * (2 * route_batch(n_parts, lg, tile) + 2 * route_max_need(lg, tile)) + 64;
-  // "route_pool_pct" < 100 (tests): a pool too small on purpose — what finds no chunk goes straight into the output
-  if (kn.route_pool_pct > 0 && kn.route_pool_pct < 100) pool_chunks = std::max<int64_t>(1, pool_chunks * kn.route_pool_pct / 100);
-  if (pool_chunks >= ((int64_t)1 << 31) || (pool_chunks << lg) >= ((int64_t)1 << 44)) return XHIST_ERR_UNSUPPORTED;
-
-  uint32_t *d_ctr = nullptr, *d_plist = nullptr, *d_cmeta = nullptr;
-  uint16_t* d_codes = nullptr;
-  void* d_w = nullptr;
-  void *x_ctl = nullptr, *x_part = nullptr;  // the exchange mode's scratch: what is zeroed per call (one block), and the XCD partials
-  int64_t x_zero_words = 0;
-  auto release = [&](int rc) {
-    for (void* q : {x_ctl, x_part})
-      if (q) (void)scratch_free(q, stream);
-    if (d_ctr) (void)scratch_free(d_ctr, stream);
-    if (d_plist) (void)scratch_free(d_plist, stream);
-    if (d_cmeta) (void)scratch_free(d_cmeta, stream);
-    if (d_codes) (void)scratch_free(d_codes, stream);
-    if (d_w) (void)scratch_free(d_w, stream);
-    return rc;
-  };
-#define HIPR(expr)                                                                                     \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return release(fail(XHIST_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); \
-  } while (0)
-  const int64_t ctr_words = (2 + n_parts + 1) / 2 + 1;  // [0] pool, [1] signs seen, [2 .. 2 + P) chunks filed per partition; two sets (packed + exact)
-  const size_t rec_bytes = rec_f32 ? 4 : 8;
-  const size_t plist_elems = (size_t)n_parts * pool_chunks, pool_recs = ((size_t)pool_chunks << lg);
-  HIPR(scratch_malloc((void**)&d_ctr, (size_t)ctr_words * 8 * 2, stream));
-  HIPR(scratch_malloc((void**)&d_plist, plist_elems * 4, stream));
-  HIPR(scratch_malloc((void**)&d_cmeta, (size_t)pool_chunks * 4, stream));
-  HIPR(scratch_malloc((void**)&d_codes, pool_recs * 2, stream));
-  if (weighted) HIPR(scratch_malloc(&d_w, pool_recs * rec_bytes, stream));
-
-  // The exchange mode (xhist_exchange.hip.h): packed records that never go through HBM — one persistent workgroup per compute
-  // unit keeps rows of a WINDOW of the histogram in LDS, records travel through rings inside each XCD.  Offered for float64
-  // samples + float64 weights on arithmetic edges, one row, on the 8 x 32-CU chip; whether a call takes it is decided on the
-  // GPU by the probe (the window must hold >= 88 % of the samples) — the classic packed kernels below are queued all the same
-  // and return at once when it does.  "exchange" = -1 / 1: never / whenever it can run (any size, any coverage: tests).
-  ExchArgs xa;
-  memset(&xa, 0, sizeof xa);
-  bool xch = false, xch_probe = false;
-  kernel_fn_exch k_xch = nullptr, k_xprobe = nullptr;
-  size_t lds_xch = 0;
-  if ((pack || xexact) && rows == 1 && kn.exchange_pref >= 0 && (exch_skip == 0 || kn.exchange_pref > 0) && sdt == XHIST_F64 && p->arith && kn.arith_pref >= 0 && D <= 3 && p->cus == kExchXcds * kExchRings &&
-      p->n_bins <= ((int64_t)1 << 23) /* (the side copy is zeroed per call) */ && (kn.exchange_pref > 0 || n_cols >= ((int64_t)1 << 25))) {
-    const int64_t L = D >= 2 ? (int64_t)p->ts[0][0].dim[D - 1].nb : 256;
-    const int64_t hist_rows = D >= 2 ? p->n_bins / L : (p->n_bins + 255) / 256;
-    const int64_t units = (hist_rows + kExchUnitRows - 1) / kExchUnitRows;
-    const int64_t max_local = xexact ? kExchMaxLocalExact : kExchMaxLocal;
-    const int64_t rows_per = L <= max_local ? std::min<int64_t>(max_local / L, units) : 0;
-    k_xch = xhist_pick_exchange(D, xexact);
-    k_xprobe = xhist_pick_exchange_probe(D);
-    lds_xch = rows_per >= 1 ? exchange_lds((int)(rows_per * L), xexact) : 0;
-    if (rows_per >= 1 && units <= 4096 && k_xch && k_xprobe && lds_xch <= p->lds_max && !other_stream_busy) {
-      xch = true;
-      xch_probe = true;  // (always: a histogram that fits the window has nothing outside it, but its owners' loads must be even too)
-      xa.row_len = L;
-      xa.n_hist_rows = hist_rows;
-      xa.rows_per = (int32_t)rows_per;
-      xa.local_bins = (int32_t)(rows_per * L);
-      xa.n_units = (int32_t)units;
-      xa.force = kn.exchange_pref > 0 ? 1 : 0;
-      { int64_t p2 = 1; while (p2 * 2 <= L) p2 *= 2; xa.side_rot_mask = (int32_t)(p2 - 1); }
-      xa.min_ppm = kn.exchange_min_pct > 0 ? kn.exchange_min_pct * 10000 : kExchMinPpm;
-      xa.max_uneven_ppm = 1250000;
-      xa.budget_ticks = kn.exchange_budget_ms < 0 ? 0 : (long long)(kn.exchange_budget_ms ? kn.exchange_budget_ms : 500) * 100000;
-      xa.arrive_ticks = (long long)(kn.exchange_arrive_us > 0 ? kn.exchange_arrive_us : 200) * 100;  // 200 us: the launch of 256 workgroups on a free chip takes a few
-      const size_t words_bytes = ((size_t)(units + kExchRings + 8 + 32) * 4 + 7) & ~(size_t)7;  // win[8], the cold arguments (32 words), the probe's counts (units, then owners)
-      // one block for everything that is zeroed per call (one launch): control words | window, cold arguments, probe counts | side copy | rings
-      const size_t ctl_bytes = sizeof(ExchCtl) * kExchXcds, side_bytes = (size_t)(hist_rows * L) * 8;  // (whole rows: exch_side_index rotates inside a row)
-      const size_t rings_bytes = (size_t)kExchXcds * kExchRings * kExchRings * kExchCap * (xexact ? 12 : 8);  // (exact records: the ring of low bits behind the ring of packed words)
-      static_assert(sizeof(ExchCtl) % 8 == 0, "the block's parts stay 8-byte aligned");
-      x_zero_words = (int64_t)((ctl_bytes + words_bytes + side_bytes + rings_bytes) / 8);
-      HIPR(scratch_malloc(&x_ctl, ctl_bytes + words_bytes + side_bytes + rings_bytes, stream));
-      HIPR(scratch_malloc(&x_part, (size_t)kExchXcds * kExchRings * (size_t)xa.local_bins * 8, stream));
-      xa.ctl = static_cast<ExchCtl*>(x_ctl);
-      xa.win = reinterpret_cast<uint32_t*>(static_cast<char*>(x_ctl) + ctl_bytes);
-      xa.side = reinterpret_cast<double*>(static_cast<char*>(x_ctl) + ctl_bytes + words_bytes);
-      xa.rings = reinterpret_cast<uint64_t*>(static_cast<char*>(x_ctl) + ctl_bytes + words_bytes + side_bytes);
-      xa.rings_lo = xexact ? reinterpret_cast<uint32_t*>(xa.rings + (size_t)kExchXcds * kExchRings * kExchRings * kExchCap) : nullptr;
-      xa.part = static_cast<double*>(x_part);
-      xa.cold = reinterpret_cast<ExchCold*>(xa.win + 8);
-      static_assert(sizeof(ExchCold) <= 32 * 4, "the cold arguments fit their 32 words");
-      xa.counts = xa.win + 8 + 32;
-      xa.note = p->mixed_hint;
-      if (lds_xch > 48 * 1024) HIPR(hipFuncSetAttribute((const void*)k_xch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_xch));
-      // every workgroup of the kernel must be resident (they wait for one another): one per compute unit is what its LDS and
-      // registers must allow; asked once per plan and LDS size (a kernel of the host's that holds compute units at run time is
-      // the deadline's business)
-      bool occ_known, occ_ok;
-      {
-        std::lock_guard<std::mutex> lk(p->mu);
-        occ_known = p->exch.occ_lds == lds_xch;
-        occ_ok = p->exch.occ_ok;
-      }
-      if (!occ_known) {
-        int per_cu_x = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_x, (const void*)k_xch, kExchBlock, lds_xch) != hipSuccess) { per_cu_x = 0; (void)hipGetLastError(); }
-        occ_ok = per_cu_x >= 1;
-        std::lock_guard<std::mutex> lk(p->mu);
-        p->exch.occ_lds = lds_xch;
-        p->exch.occ_ok = occ_ok;
-      }
-      if (!occ_ok) xch = false;
-    }
+    std::lock_guard<std::mutex> lk(fl.mu);
+    if (exchange_running_elsewhere(fl, stream)) xp.on = false;
   }
 
-  if (lds_route > 48 * 1024) HIPR(hipFuncSetAttribute((const void*)k_route, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_route));
-  kernel_fn_acc_chunks k_acc = weighted ? (rec_f32 ? (kernel_fn_acc_chunks)part_accumulate_chunks<true, float>
-                                                   : (kernel_fn_acc_chunks)part_accumulate_chunks<true, double>)
-                                        : (kernel_fn_acc_chunks)part_accumulate_chunks<false, double>;
-  if (lds_acc > 48 * 1024) HIPR(hipFuncSetAttribute((const void*)k_acc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_acc));
-  kernel_fn_acc_chunks k_acc48 = (kernel_fn_acc_chunks)part_accumulate_chunks<true, double, true>;
-  if (pack) {
-    if (lds_route > 48 * 1024) HIPR(hipFuncSetAttribute((const void*)k_route48, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_route));
-    if (lds_acc > 48 * 1024) HIPR(hipFuncSetAttribute((const void*)k_acc48, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_acc));
-  }
-
+  ScratchScope scratch(stream);
+  RouteArgs ra;
+  if (int rc = alloc_fused(scratch, p, rp, n_parts, weighted, wdt == XHIST_F32, xp, ra)) return rc;
   if (first)  // one timing record per execute: opened before the first row's kernels, closed after the last row's
-    if (int rrc = rec.begin(kn.profile)) return release(rrc);
-  const DimTable* dims = tset.dim;
-  {
-    Params kp;
-    memset(&kp, 0, sizeof kp);
-    for (int d = 0; d < D; ++d) {
-      kp.s_ptr[d] = samples[d].data;
-      kp.s_rs[d] = samples[d].row_stride;
-      kp.s_cs[d] = 1;
-      kp.s_dt[d] = samples[d].dtype;
-      kp.dim[d] = dims[d];
-    }
-    if (weighted) {
-      kp.w_ptr = weights->data;
-      kp.w_rs = weights->row_stride;
-      kp.w_cs = 1;
-      kp.w_dt = weights->dtype;
-    }
-    kp.n_dims = D;
-    kp.tables = tset.blob;
-    kp.table_words = table_words;
-    kp.tables_in_lds = 1;
-    kp.n_rows = rows;
-    kp.n_cols = n_cols;
-    kp.n_bins = p->n_bins;
-    kp.out = out;
-    kp.part_shift = shift;
-    kp.n_parts = n_parts;
-    kp.parts_per_row = parts_per_row;
-    const int Gk = G;
-    kp.segs = Gk;
-    uint32_t* ctr = d_ctr;  // (two counter sets of ctr_words 8-byte words each)
-    RouteArgs ra;
-    ra.pool = ctr;
-    ra.pcount = ctr + 2;
-    ra.plist = d_plist;
-    ra.cmeta = d_cmeta;
-    ra.codes = d_codes;
-    ra.wrec = weighted ? d_w : nullptr;
-    ra.list_cap = (uint32_t)pool_chunks;
-    ra.chunk_log2 = lg;
-    ra.flags = ctr + 1;
-    ra.gate = nullptr;
-    ra.hint = nullptr;
-    ra.gate_mode = 0;
-    ra.dry = p->mixed_hint ? p->mixed_hint + 1 : nullptr;
-
-    if (int zrc = zero_output(ctr, ctr_words * 2, stream)) return release(zrc);
-    ra.xgate = nullptr;
-    if (xch) {
-      xa.flags = ctr + 1;
-      if (int zrc = zero_output(x_ctl, x_zero_words, stream)) return release(zrc);
-      for (int d = 0; d < D; ++d) {  // (the arithmetic-edge constants of the float64 table set, whatever the classic routing pass digitizes with)
-        const DimTable& t = p->ts[0][0].dim[d];
-        xa.s_ptr[d] = static_cast<const double*>(samples[d].data);
-        xa.dim[d].e0 = t.e0_f;
-        xa.dim[d].eL = t.eL_f;
-        xa.dim[d].step = t.step;
-        xa.dim[d].inv_step = t.inv_step;
-        xa.dim[d].arith_h = t.arith_h;
-        xa.dim[d].nb = t.nb;
-      }
-      xa.w_ptr = static_cast<const double*>(weights->data);
-      xa.n = n_cols;
-      if (xch_probe) {
-        XH_LAUNCH_PICKED(k_xprobe, dim3(256), dim3(256), 0, stream, xa);
-        HIPR(hipGetLastError());
-      }
-      XH_LAUNCH_PICKED(xhist_pick_exchange_pick(), dim3(1), dim3(64), 0, stream, xa);
-      HIPR(hipGetLastError());
-      XH_LAUNCH_PICKED(k_xch, dim3(kExchXcds * kExchRings), dim3(kExchBlock), lds_xch, stream, xa);
-      HIPR(hipGetLastError());
-      {
-        ExchInFlight& fl = exch_in_flight(p->device);  // (xfl_lock holds fl.mu since the look at the last kernel's event)
-        if (!fl.ev && hipEventCreateWithFlags(&fl.ev, hipEventDisableTiming) != hipSuccess) { fl.ev = nullptr; (void)hipGetLastError(); }
-        if (fl.ev && hipEventRecord(fl.ev, stream) == hipSuccess) { fl.stream = stream; fl.armed = true; }
-        else { fl.armed = false; (void)hipGetLastError(); }
-      }
-      {
-        std::lock_guard<std::mutex> lk(p->mu);
-        p->exch.ran_last = true;
-      }
-      ra.xgate = xa.win + 1;  // the classic packed kernels below return at once when the mode took the call
-    }
-    if (xfl_lock.owns_lock()) xfl_lock.unlock();
-    RouteArgs ra48 = ra;
-    if (pack) {
-      XH_LAUNCH_PICKED(k_route48, dim3(Gk), dim3(block), lds_route, stream, kp, ra);  // packed records, notes the signs
-      HIPR(hipGetLastError());
-      ra48.gate = ctr + 1;
-      ra48.gate_mode = 1;  // one sign: add the packed records up
-      // both signs: the exact pass below runs (its own counters: the second set), otherwise its kernels return at once
-      ra.pool = ctr + 2 * ctr_words;
-      ra.pcount = ra.pool + 2;
-      ra.flags = ra.pool + 1;
-      ra.gate = ctr + 1;
-      ra.gate_mode = 2;
-      ra.hint = p->mixed_hint;
-      ra.xgate = nullptr;  // (the exact passes redo the call whenever the sign word says so, exchange mode or not)
-    }
-    XH_LAUNCH_PICKED(k_route, dim3(Gk), dim3(block), lds_route, stream, kp, ra);
-    HIPR(hipGetLastError());
-    if (pack) {
-      XH_LAUNCH_PICKED(k_acc48, dim3(Gb), dim3(1024), lds_acc, stream, ra48, out, p->n_bins, shift, n_parts, rows > 1 ? parts_per_row : 0);
-      HIPR(hipGetLastError());
-    }
-    XH_LAUNCH_PICKED(k_acc, dim3(Gb), dim3(1024), lds_acc, stream, ra, out, p->n_bins, shift, n_parts, rows > 1 ? parts_per_row : 0);
-    HIPR(hipGetLastError());
-    if (xch) {  // (runs when the mode was on and the weights had one sign: exactly when none of the four kernels above did)
-      XH_LAUNCH_PICKED(xhist_pick_exchange_merge(), dim3((unsigned)((p->n_bins + 255) / 256)), dim3(256), 0, stream, xa, static_cast<double*>(out), p->n_bins);
-      HIPR(hipGetLastError());
-    }
-  }
-  {
-    char desc[768];
-    snprintf(desc, sizeof desc,
-             "family=fast hist=partitioned route=fused rows_per_pass=%d parts=%d bins_per_part=%d group=%d chunk=%d chunks<=%lld tile=%d block=%d grid=%d "
-             "acc_grid=%d lds_route=%zu lds_acc=%zu scan=%d weighted=%d D=%d cmp=%s records=%s exchange=%s exchange_window_ppm_before=%u exchange_aborts=%u exchange_busiest_owner_ppm_before=%u exchange_arrival_misses=%u exchange_records=%s",
-             rows, n_parts, 1 << shift, kRouteGrp, 1 << lg, (long long)pool_chunks, tile, block, G, Gb, lds_route, lds_acc, scan,
-             (int)weighted, D, use_f32 ? "f32thr" : "f64",
-             !weighted ? "u16" : pack ? "packed48(+exact if both signs)" : wdt == XHIST_F32 ? "u16+f32" : "u16+f64",
-             !xch ? "no" : xa.force ? "forced" : xa.n_units > xa.rows_per ? "if the probe's window holds enough of the samples" : "whole histogram in the window",
-             p->mixed_hint ? p->mixed_hint[3] : 0u, p->mixed_hint ? p->mixed_hint[2] : 0u, p->mixed_hint ? p->mixed_hint[4] : 0u, p->mixed_hint ? p->mixed_hint[5] : 0u,  // (what the GPU has reported so far: the calls before this one)
-             !xch ? "-" : xexact ? "exact12(two_rings)" : "packed8");
-    if (last)
-      if (int rrc = rec.end(desc)) return release(rrc);
-  }
-#undef HIPR
-  return release(XHIST_OK);
+    if (int rrc = rec.begin(kn.profile)) return rrc;
+  Params kp = partitioned_params(p, samples, weights, n_cols, out, tset, rp.table_words, shift, n_parts);
+  kp.n_rows = rows;
+  kp.parts_per_row = parts_per_row;
+  kp.segs = rp.G;
+  if (int rc = launch_fused(p, stream, kp, rp, ra, xp)) return rc;
+  if (!last) return XHIST_OK;
+  const ExchArgs& xa = xp.xa;
+  const uint32_t* note = p->mixed_hint;  // (what the GPU has reported so far: the calls before this one)
+  char desc[768];
+  snprintf(desc, sizeof desc,
+           "family=fast hist=partitioned route=fused rows_per_pass=%d parts=%d bins_per_part=%d group=%d chunk=%d chunks<=%lld tile=%d block=%d grid=%d "
+           "acc_grid=%d lds_route=%zu lds_acc=%zu scan=%d weighted=%d D=%d cmp=%s records=%s exchange=%s exchange_window_ppm_before=%u exchange_aborts=%u exchange_busiest_owner_ppm_before=%u exchange_arrival_misses=%u exchange_records=%s",
+           rows, n_parts, 1 << shift, kRouteGrp, 1 << rp.lg, (long long)rp.pool_chunks, rp.tile, rp.block, rp.G, rp.Gb, rp.lds_route, rp.lds_acc, scan,
+           (int)weighted, p->n_dims, use_f32 ? "f32thr" : "f64",
+           !weighted ? "u16" : rp.pack ? "packed48(+exact if both signs)" : wdt == XHIST_F32 ? "u16+f32" : "u16+f64",
+           !xp.on ? "no" : xa.force ? "forced" : xa.n_units > xa.rows_per ? "if the probe's window holds enough of the samples" : "whole histogram in the window",
+           note ? note[3] : 0u, note ? note[2] : 0u, note ? note[4] : 0u, note ? note[5] : 0u,
+           !xp.on ? "-" : xp.exact ? "exact12(two_rings)" : "packed8");
+  return rec.end(desc);
 }
 
 // Row-per-lane mode (xhist_lanes.hip.h).  Takes (a) views whose ROWS are the contiguous direction
@@ -738,7 +745,7 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
       const uint64_t magic = (((uint64_t)1 << 40) / (uint64_t)n_cols) + 1u;
       LaunchRecord rec(p, stream);
       if (int rrc = rec.begin(kn.profile)) return rrc;
-      if (lds_flat > 48 * 1024) HIPC(hipFuncSetAttribute((const void*)ff, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_flat));
+      HIPC(set_dynamic_lds((const void*)ff, lds_flat));
       XH_LAUNCH_PICKED(ff, dim3((unsigned)row_blocks), dim3(kLaneBlock), lds_flat, stream, kp, (int32_t)direct, (int32_t)R, (int32_t)flat_k_log2,
                          magic, (int64_t)(n_rows * n_cols));
       HIPC(hipGetLastError());
@@ -783,7 +790,7 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
       const int direct = accumulate ? 0 : 1;
       LaunchRecord rec(p, stream);
       if (int rrc = rec.begin(kn.profile)) return rrc;
-      if (lds_f > 48 * 1024) HIPC(hipFuncSetAttribute((const void*)f1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
+      HIPC(set_dynamic_lds((const void*)f1, lds_f));
       XH_LAUNCH_PICKED(f1, dim3((unsigned)row_blocks), dim3(kLaneBlock), lds_f, stream, kp, (int32_t)direct);
       HIPC(hipGetLastError());
       char desc[384];
@@ -794,23 +801,12 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
     }
   }
 
-  void* scratch[kMaxDims + 1] = {nullptr};
-  auto release = [&](int rc) {
-    for (auto s : scratch)
-      if (s) (void)scratch_free(s, stream);
-    return rc;
-  };
-#define HIPL(expr)                                                                                     \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return release(fail(XHIST_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); \
-  } while (0)
-
+  ScratchScope scratch(stream);
   Params kp;
   memset(&kp, 0, sizeof kp);
   const DimTable* dims = tset.dim;
   LaunchRecord rec(p, stream);
-  if (int rrc = rec.begin(kn.profile)) return release(rrc);
+  if (int rrc = rec.begin(kn.profile)) return rrc;
   for (int d = 0; d < n_arrays(D, weights); ++d) {
     const xhist_array& a = array_at(samples, weights, D, d);
     const void* ptr = a.data;
@@ -818,14 +814,15 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
     if (transpose && rs != 0 && cs != 0) {
       ir = os = 0;
       const int es = dtype_size(a.dtype);
-      HIPL(scratch_malloc(&scratch[d], (size_t)n_rows * n_cols * es, stream));
+      void* dense = nullptr;
+      HIPC(scratch.alloc(&dense, (size_t)n_rows * n_cols * es));
       const dim3 grid((unsigned)((n_rows + 63) / 64), (unsigned)((n_cols + 63) / 64));
       if (es == 8)
-        hipLaunchKernelGGL(transpose_2d<double>, grid, dim3(256), 0, stream, (const double*)a.data, rs, n_rows, n_cols, (double*)scratch[d]);
+        hipLaunchKernelGGL(transpose_2d<double>, grid, dim3(256), 0, stream, (const double*)a.data, rs, n_rows, n_cols, (double*)dense);
       else
-        hipLaunchKernelGGL(transpose_2d<float>, grid, dim3(256), 0, stream, (const float*)a.data, rs, n_rows, n_cols, (float*)scratch[d]);
-      HIPL(hipGetLastError());
-      ptr = scratch[d];
+        hipLaunchKernelGGL(transpose_2d<float>, grid, dim3(256), 0, stream, (const float*)a.data, rs, n_rows, n_cols, (float*)dense);
+      HIPC(hipGetLastError());
+      ptr = dense;
       rs = 1;
       cs = n_rows;
     }
@@ -873,7 +870,7 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
   if ((u16_ok ? table_bytes + (size_t)p->n_bins * (kLaneBlock / 2 + 1) * 4 : lds_bytes) > std::min(p->lds_max, share_above)) {
     lane_rows = std::min(lane_rows, 128);
     while (lane_rows > 16 && lds_shared(lane_rows, u16_ok) > share_target) lane_rows /= 2;
-    if (lds_shared(lane_rows, u16_ok) > p->lds_max) return release(XHIST_ERR_UNSUPPORTED);
+    if (lds_shared(lane_rows, u16_ok) > p->lds_max) return XHIST_ERR_UNSUPPORTED;
     lane_pitch = 1;  // (the number of words is set below, once the counter width is known)
   }
   kp.lane_rows = lane_rows;
@@ -889,13 +886,13 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
     // (a segment of more than 65535 columns: only with so many row blocks that there is one segment each — beyond 10^10
     //  samples; the row-streaming kernels take that call.  The uint32-column kernels this used to fall back to were never
     //  selected by anything — census of round 6 — and are gone)
-    if ((n_cols + segs16 - 1) / segs16 > 65535) return release(XHIST_ERR_UNSUPPORTED);
+    if ((n_cols + segs16 - 1) / segs16 > 65535) return XHIST_ERR_UNSUPPORTED;
     packed16 = true;
     lds_use = lds16;
   }
   if (lane_pitch) lane_pitch = packed16 ? lane_rows / 2 + 1 : lane_rows + 1;
   kp.lane_pitch = lane_pitch;
-  if (lds_use > p->lds_max) return release(XHIST_ERR_UNSUPPORTED);
+  if (lds_use > p->lds_max) return XHIST_ERR_UNSUPPORTED;
   const int bpc = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)160 * 1024 / lds_use));
   int64_t col_segs = std::max<int64_t>(1, ((int64_t)p->cus * bpc * 2 + row_blocks - 1) / row_blocks);
   col_segs = std::min<int64_t>(col_segs, std::max<int64_t>(1, n_cols / 64));
@@ -904,23 +901,19 @@ static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_
   col_segs = (n_cols + cols_per_seg - 1) / cols_per_seg;
   const int direct = (col_segs == 1 && !accumulate) ? 1 : 0;
   if (!direct && !accumulate)
-    if (int zrc = zero_output(out, n_rows * p->n_bins, stream)) return release(zrc);
-  if (row_blocks > 2147483647LL) return release(XHIST_ERR_UNSUPPORTED);
-  if (lds_use > 48 * 1024) HIPL(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_use));
+    if (int zrc = zero_output(out, n_rows * p->n_bins, stream)) return zrc;
+  if (row_blocks > 2147483647LL) return XHIST_ERR_UNSUPPORTED;
+  HIPC(set_dynamic_lds((const void*)fn, lds_use));
   XH_LAUNCH_PICKED(fn, dim3((unsigned)row_blocks, (unsigned)col_segs), dim3(kLaneBlock), lds_use, stream, kp, (int32_t)direct,
                      cols_per_seg);
-  HIPL(hipGetLastError());
-  {
-    char desc[384];
-    snprintf(desc, sizeof desc,
-             "family=lanes hist=%s%s rows_per_wg=%d transpose=%d direct_store=%d block=%d grid=%lldx%lld lds_bytes=%zu scan=%d weighted=%d D=%d cmp=%s",
-             packed16 ? "lds16" : "lds", lane_pitch ? "(shared)" : "", lane_rows, (int)transpose, direct, kLaneBlock, (long long)row_blocks, (long long)col_segs, lds_use, scan,
-             (int)weighted, D,
-             use_f32 ? "f32thr" : "f64");
-    if (int rrc = rec.end(desc)) return release(rrc);
-  }
-#undef HIPL
-  return release(XHIST_OK);
+  HIPC(hipGetLastError());
+  char desc[384];
+  snprintf(desc, sizeof desc,
+           "family=lanes hist=%s%s rows_per_wg=%d transpose=%d direct_store=%d block=%d grid=%lldx%lld lds_bytes=%zu scan=%d weighted=%d D=%d cmp=%s",
+           packed16 ? "lds16" : "lds", lane_pitch ? "(shared)" : "", lane_rows, (int)transpose, direct, kLaneBlock, (long long)row_blocks, (long long)col_segs, lds_use, scan,
+           (int)weighted, D,
+           use_f32 ? "f32thr" : "f64");
+  return rec.end(desc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -960,41 +953,37 @@ static int execute_table_columns(xhist_plan* p, const PlanKnobs& kn, const Input
   //  float64 + weights, 5000 bins: 0.50 ms against 0.87 with the gather; every other measured shape gains 1.3-9 x)
   if (table && n_rows <= 4 && dtype_size(in.samples[0].dtype) == 8 && p->n_bins * (in.weighted ? 8 : 4) <= (int64_t)96 * 1024) table = false;
   if (!table) return XHIST_ERR_UNSUPPORTED;
-  void* scratch[kMaxDims + 1] = {nullptr};
+  ScratchScope scratch(stream);
   xhist_array dense[kMaxDims + 1];  // the samples, then the weights
-  int rc = XHIST_OK;
-  for (int d = 0; d < in.n_arrays() && rc == XHIST_OK; ++d) {
+  for (int d = 0; d < in.n_arrays(); ++d) {
     const xhist_array& a = in.array(d);
     const int es = dtype_size(a.dtype);
-    if (scratch_malloc(&scratch[d], (size_t)n_rows * n_cols * es, stream) != hipSuccess) {
+    void* buf = nullptr;
+    if (scratch.alloc(&buf, (size_t)n_rows * n_cols * es) != hipSuccess) {
       (void)hipGetLastError();
-      rc = fail(XHIST_ERR_NOMEM, "allocation of %lld bytes of gather scratch failed", (long long)n_rows * n_cols * es);
-      break;
+      return fail(XHIST_ERR_NOMEM, "allocation of %lld bytes of gather scratch failed", (long long)n_rows * n_cols * es);
     }
     const int grid = (int)std::min<int64_t>((n_cols + 255) / 256, (int64_t)p->cus * 16);
     // whole tables with rows of whole 16-byte units: tiled through LDS (256 rows x (k + 1) elements)
     const size_t tile_lds = (size_t)256 * (n_rows + 1) * es;
     if (a.col_stride == n_rows && ((int64_t)n_rows * es) % 16 == 0 && ((uintptr_t)a.data % 16) == 0 && es >= 4 && tile_lds <= 64 * 1024) {
       const int tgrid = (int)std::min<int64_t>((n_cols + 255) / 256, (int64_t)p->cus * (int64_t)std::max<size_t>(1, (160 * 1024) / tile_lds));
-      if (es == 8) hipLaunchKernelGGL(gather_rows_tiled<uint64_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint64_t*)a.data, (int)n_rows, n_cols, (uint64_t*)scratch[d]);
-      else hipLaunchKernelGGL(gather_rows_tiled<uint32_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint32_t*)a.data, (int)n_rows, n_cols, (uint32_t*)scratch[d]);
+      if (es == 8) hipLaunchKernelGGL(gather_rows_tiled<uint64_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint64_t*)a.data, (int)n_rows, n_cols, (uint64_t*)buf);
+      else hipLaunchKernelGGL(gather_rows_tiled<uint32_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint32_t*)a.data, (int)n_rows, n_cols, (uint32_t*)buf);
     } else
     switch (es) {
-      case 8: hipLaunchKernelGGL(gather_rows<uint64_t>, dim3(grid), dim3(256), 0, stream, (const uint64_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint64_t*)scratch[d]); break;
-      case 4: hipLaunchKernelGGL(gather_rows<uint32_t>, dim3(grid), dim3(256), 0, stream, (const uint32_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint32_t*)scratch[d]); break;
-      case 2: hipLaunchKernelGGL(gather_rows<uint16_t>, dim3(grid), dim3(256), 0, stream, (const uint16_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint16_t*)scratch[d]); break;
-      default: hipLaunchKernelGGL(gather_rows<uint8_t>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint8_t*)scratch[d]); break;
+      case 8: hipLaunchKernelGGL(gather_rows<uint64_t>, dim3(grid), dim3(256), 0, stream, (const uint64_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint64_t*)buf); break;
+      case 4: hipLaunchKernelGGL(gather_rows<uint32_t>, dim3(grid), dim3(256), 0, stream, (const uint32_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint32_t*)buf); break;
+      case 2: hipLaunchKernelGGL(gather_rows<uint16_t>, dim3(grid), dim3(256), 0, stream, (const uint16_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint16_t*)buf); break;
+      default: hipLaunchKernelGGL(gather_rows<uint8_t>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint8_t*)buf); break;
     }
-    if (hipGetLastError() != hipSuccess) rc = fail(XHIST_ERR_HIP, "gather_rows launch failed");
+    if (hipGetLastError() != hipSuccess) return fail(XHIST_ERR_HIP, "gather_rows launch failed");
     dense[d] = a;
-    dense[d].data = scratch[d];
+    dense[d].data = buf;
     dense[d].row_stride = n_cols;
     dense[d].col_stride = 1;
   }
-  if (rc == XHIST_OK) rc = execute_device(p, dense, in.weighted ? &dense[in.D] : nullptr, n_rows, n_cols, out, accumulate, stream);
-  for (auto* sc : scratch)
-    if (sc) (void)scratch_free(sc, stream);
-  return rc;
+  return execute_device(p, dense, in.weighted ? &dense[in.D] : nullptr, n_rows, n_cols, out, accumulate, stream);
 }
 
 // Where the histogram lives for a table footprint of `tbytes`:
@@ -1635,7 +1624,7 @@ static int launch_streaming(xhist_plan* p, const PlanKnobs& kn, const Inputs& in
   const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
   const xhist_array *samples = in.samples, *weights = in.weights, *weights2 = in.weights2;
   const DimTable* dims = sc.tset->dim;
-  if (sc.lds_bytes > 48 * 1024) HIPC(hipFuncSetAttribute((const void*)sc.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sc.lds_bytes));
+  HIPC(set_dynamic_lds((const void*)sc.fn, sc.lds_bytes));
   if (!accumulate && !g.direct && !in.two)
     if (int zrc = zero_output(out, n_rows * p->n_bins, stream)) return zrc;
   bool first_launch = true;

@@ -339,6 +339,36 @@ static hipError_t scratch_free(void* p, hipStream_t stream, bool synced = false)
   return hipSuccess;
 }
 
+// The scratch blocks of one call on one stream: whatever alloc() handed out goes back through scratch_free on that stream, in
+// the order it was allocated, when the scope ends.
+class ScratchScope {
+ public:
+  explicit ScratchScope(hipStream_t stream) : stream_(stream) {}
+  ScratchScope(const ScratchScope&) = delete;
+  ScratchScope& operator=(const ScratchScope&) = delete;
+  ~ScratchScope() {
+    for (int i = 0; i < n_; ++i) (void)scratch_free(blocks_[i], stream_);
+  }
+  hipError_t alloc(void** p, size_t bytes) {
+    if (n_ == kCap) return hipErrorInvalidValue;
+    if (hipError_t e = scratch_malloc(p, bytes, stream_)) return e;
+    blocks_[n_++] = *p;
+    return hipSuccess;
+  }
+
+ private:
+  static constexpr int kCap = kMaxDims + 1;  // the most one call holds: a transpose or gather of every sample array and the weights
+  hipStream_t stream_;
+  void* blocks_[kCap] = {};
+  int n_ = 0;
+};
+
+// Dynamic LDS beyond the default 48 KiB must be allowed per kernel first.
+static hipError_t set_dynamic_lds(const void* fn, size_t bytes) {
+  if (bytes <= 48 * 1024) return hipSuccess;
+  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
 extern "C" int xhist_scratch_stats(int device, uint64_t* stats, int n) {
   if (!stats || n < 4) return fail(XHIST_ERR_INVALID, "stats is NULL / shorter than 4");
   if (device < 0 || device >= n_devices()) return fail(XHIST_ERR_NO_DEVICE, "device %d not available", device);
@@ -367,7 +397,7 @@ extern "C" int xhist_debug_hold_cus(int device, int workgroups, int lds_bytes, i
   if (device < 0 || device >= n_devices()) return fail(XHIST_ERR_NO_DEVICE, "device %d not available", device);
   DeviceGuard g;
   if (int rc = g.set(device)) return rc;
-  if (lds_bytes > 48 * 1024 && hipFuncSetAttribute((const void*)debug_hold_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
+  if (set_dynamic_lds((const void*)debug_hold_kernel, (size_t)lds_bytes) != hipSuccess)
     return fail(XHIST_ERR_HIP, "hold_cus: %s", hipGetErrorString(hipGetLastError()));
   hipLaunchKernelGGL(debug_hold_kernel, dim3((unsigned)workgroups), dim3(64), (size_t)lds_bytes, static_cast<hipStream_t>(stream), (long long)microseconds * 100);
   if (hipError_t e = hipGetLastError()) return fail(XHIST_ERR_HIP, "hold_cus launch: %s", hipGetErrorString(e));
@@ -441,7 +471,8 @@ struct ExchangeState {
   int backoff = 16;   // ... and how many that will be after the next abort (doubles per abort, back to 16 after a clean call)
   bool ran_last = false;  // the last eligible call launched the exchange kernel
   uint32_t aborts_seen = 0;
-  size_t occ_lds = 0;  // the LDS size the occupancy question was asked for, and its answer
+  const void* occ_fn = nullptr;  // the exchange kernel and LDS size the occupancy question was asked for, and its answer
+  size_t occ_lds = 0;
   bool occ_ok = false;
 };
 
