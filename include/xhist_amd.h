@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define XHIST_ABI_VERSION 9
+#define XHIST_ABI_VERSION 10
 #define XHIST_MAX_DIMS 8 /* max number of sample arrays (histogram dimensionality) */
 
 typedef enum {
@@ -131,6 +131,19 @@ int xhist_plan_execute(xhist_plan* plan, const xhist_array* samples, const xhist
 int xhist_plan_execute_two_weights(xhist_plan* plan, const xhist_array* samples, const xhist_array* weights_a,
                                    const xhist_array* weights_b, int64_t n_rows, int64_t n_cols, void* out_a,
                                    void* out_b, int mem_kind, int accumulate, void* stream);
+
+/* Per-bin minimum and maximum of `values` (ABI v10): which samples count is exactly what xhist_plan_execute counts (same
+ * digitize, last bin closed, NaN / out-of-range samples dropped); each counted sample contributes its value converted to
+ * float64.  NaN values are ignored (np.fmin / np.fmax), values are ordered totally with -0.0 < +0.0, and a bin that received
+ * no value is NaN in both outputs.  Results are exact.
+ *   values: an xhist_array of any real dtype, same logical [n_rows, n_cols] shape as the samples (strides 0 broadcast).
+ *   out_min, out_max: contiguous float64 [n_rows, prod(nb_d)], DEVICE buffers; they double as the kernels' working space.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   accumulate != 0: combine into the existing outputs (NaN there = empty) instead of overwriting them — chunked inputs.
+ *   Asynchronous on `stream`. */
+int xhist_plan_execute_extrema(xhist_plan* plan, const xhist_array* samples, const xhist_array* values,
+                               int64_t n_rows, int64_t n_cols, double* out_min, double* out_max,
+                               int mem_kind, int accumulate, void* stream);
 
 /* One-shot form of the two calls above with an internal plan cache keyed on (device, edges). */
 int xhist_bincount_rows(int device, int n_inputs, const xhist_array* samples,

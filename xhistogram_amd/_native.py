@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # $XHIST_AMD_LIB points development builds (A/B kernel variants) at another shared object
 LIB_PATH = os.environ.get("XHIST_AMD_LIB") or os.path.join(_HERE, "libxhist_amd.so")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 MAX_DIMS = 8
 
 # status codes (xhist_status)
@@ -68,7 +68,8 @@ _lock = threading.Lock()
 
 EXPORTS = (
     "xhist_abi_version", "xhist_last_error", "xhist_device_count", "xhist_device_info",
-    "xhist_plan_create", "xhist_plan_destroy", "xhist_plan_execute", "xhist_plan_execute_two_weights", "xhist_bincount_rows",
+    "xhist_plan_create", "xhist_plan_destroy", "xhist_plan_execute", "xhist_plan_execute_two_weights", "xhist_plan_execute_extrema",
+    "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
     "xhist_comm_wait", "xhist_comm_destroy", "xhist_buffer_alloc", "xhist_buffer_free", "xhist_buffer_copy", "xhist_buffer_add", "xhist_buffer_copy_nd",
@@ -129,6 +130,10 @@ def load():
         lib.xhist_plan_execute_two_weights.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
             C.c_int, C.c_int, C.c_void_p,
+        ]
+        lib.xhist_plan_execute_extrema.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+            C.c_void_p,
         ]
         lib.xhist_bincount_rows.argtypes = [
             C.c_int, C.c_int, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_void_p),
@@ -326,6 +331,20 @@ class Plan:
             load().xhist_plan_execute_two_weights(
                 self._h, arr, C.byref(wa_view), C.byref(wb_view), int(n_rows), int(n_cols), C.c_void_p(out_a_ptr),
                 C.c_void_p(out_b_ptr), int(mem_kind), 1 if accumulate else 0, C.c_void_p(stream or 0),
+            )
+        )
+
+    def execute_extrema(self, sample_views, value_view, n_rows, n_cols, out_min_ptr, out_max_ptr, accumulate=False, stream=0):
+        """per-bin minimum and maximum of the values (float64 [n_rows, bins] each, NaN where no value arrived) of
+        device-resident views into device buffers, asynchronous on `stream` (xhist_plan_execute_extrema)"""
+        d = self.n_dims
+        if len(sample_views) != d:
+            raise ValueError("plan was built for %d inputs, got %d" % (d, len(sample_views)))
+        arr = (XhistArray * d)(*sample_views)
+        check(
+            load().xhist_plan_execute_extrema(
+                self._h, arr, C.byref(value_view), int(n_rows), int(n_cols), C.c_void_p(out_min_ptr), C.c_void_p(out_max_ptr),
+                MEM_DEVICE, 1 if accumulate else 0, C.c_void_p(stream or 0),
             )
         )
 

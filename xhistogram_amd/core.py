@@ -32,7 +32,7 @@ from .devicearray import DeviceArray, _nocopy_reshape_strides
 # range is a keyword of histogram(), like in the reference
 _range = range
 
-__all__ = ["histogram", "histogram_two_weights"]
+__all__ = ["histogram", "histogram_two_weights", "histogram_extrema"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1729,3 +1729,214 @@ def _histogram(args, bins, range, axis, weights, density, block_size, _second_we
 
     h = _density(bin_counts, bins, n_inputs) if density else bin_counts
     return h, bins
+
+
+# ---------------------------------------------------------------------------------------------
+# per-bin minimum and maximum of a value array
+# ---------------------------------------------------------------------------------------------
+_ALL_ONES = np.uint64(0xFFFFFFFFFFFFFFFF)
+_SIGN = np.uint64(1 << 63)
+
+
+def extrema_keys(a):
+    """order-preserving uint64 keys of float64 values, as the GPU kernels make them: unsigned order is the total order of the
+    values with -0.0 < +0.0.  NaN has no key of its own (callers map it to an empty marker)."""
+    b = np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+    return b ^ np.where(b >> np.uint64(63) != 0, _ALL_ONES, _SIGN)
+
+
+def _extrema_values(k):
+    """inverse of extrema_keys"""
+    k = np.ascontiguousarray(k, dtype=np.uint64)
+    return (k ^ np.where(k >> np.uint64(63) != 0, _SIGN, _ALL_ONES)).view(np.float64)
+
+
+def combine_extrema(vmin, vmax, axis):
+    """Per-bin minimum and maximum over `axis` (kept as axes of extent 1) of partial results, NaN meaning "no value", in the
+    order of the GPU's keys: -0.0 < +0.0, and a bin is NaN only where every partial is.  The reduction of dask's partials."""
+    vmin, vmax = np.asarray(vmin, np.float64), np.asarray(vmax, np.float64)
+    kmin = np.where(np.isnan(vmin), _ALL_ONES, extrema_keys(vmin)).min(axis=axis, keepdims=True)
+    kmax = np.where(np.isnan(vmax), np.uint64(0), extrema_keys(vmax)).max(axis=axis, keepdims=True)
+    lo = np.where(kmin == _ALL_ONES, np.nan, _extrema_values(kmin))
+    hi = np.where(kmax == np.uint64(0), np.nan, _extrema_values(kmax))
+    return lo, hi
+
+
+def _extrema_pair_reduce(x, axis=None, keepdims=True, **_):
+    """dask.array.reduction step over [2, ...] blocks of (min, max) partials"""
+    ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
+    lo, hi = combine_extrema(x[0], x[1], tuple(a - 1 for a in ax))
+    out = np.stack([lo, hi])
+    return out if keepdims else out.squeeze(ax)
+
+
+def _check_values_dtype(values):
+    """TypeError, before any device work, for values that have no order or no float64 image"""
+    if _is_torch(values):
+        if values.dtype.is_complex:
+            raise TypeError("complex values have no order: histogram_extrema takes real values")
+        _torch_tag(values.dtype)
+        return
+    dt = np.dtype(values.dtype) if hasattr(values, "dtype") else np.asarray(values).dtype
+    if dt.kind == "c":
+        raise TypeError("complex values have no order: histogram_extrema takes real values")
+    if dt.kind not in "fiub":
+        raise TypeError("histogram_extrema takes real values, got dtype %s" % dt)
+
+
+def _upload_host(args, values, bins):
+    """host (numpy) samples and values as DeviceArrays on the calling thread's GPU, broadcast there (stride 0, not copied)"""
+    args = [np.asarray(a) for a in args]
+    args, _ = _prepare_dtypes(args, None, [a.dtype for a in args], bins, "numpy")
+    dev = _host_device()
+    _native.require_device(dev)
+    arrays = [DeviceArray.from_numpy(a, dev) for a in args + [np.asarray(values)]]
+    shape = np.broadcast_shapes(*[a.shape for a in arrays])
+    return [a.broadcast_to(shape) for a in arrays]
+
+
+def _extrema_block(*all_arrays, axis=None, bins=None):
+    """one dask block: its (min, max) pair as a [2, block axes (reduced ones of extent 1), bins...] numpy array"""
+    arrays = _upload_host(all_arrays[:-1], all_arrays[-1], bins)
+    vmin, vmax = _extrema_rows(arrays[:-1], arrays[-1], axis, bins, "device")
+    return np.stack([vmin, vmax])
+
+
+def _extrema_rows(args, values, axis, bins, backend):
+    """(vmin, vmax) of broadcast torch tensors or DeviceArrays: kept axes in place, reduced axes of extent 1, then the bin
+    axes.  The [rows, cols] views of _bincount's block adapter; layouts no three strides describe are copied."""
+    a0 = args[0]
+    ndim = a0.ndim
+    do_full_array = (axis is None) or (set(axis) == set(_range(ndim)))
+    kept_axes_shape = (1,) * ndim if do_full_array else tuple(int(a0.shape[i]) if i not in axis else 1 for i in _range(ndim))
+    dtypes = [_np_dtype_of(a) for a in args]
+    cmp_domain, edges, common = _compare_domain(dtypes, bins)
+    if backend == "device" and any(c is not None and a.dtype != c for a, c in zip(args, common)):
+        raise TypeError("datetime64 DeviceArrays must already have the unit they share with their bin edges")
+    arrays = list(args) + [values]
+    order = _reduced_order(arrays[0], list(_range(ndim)) if do_full_array else axis)
+    descs = [_collapse(a, axis, do_full_array, order) for a in arrays]
+    views = None
+    if all(d is not None for d in descs) and len({d[:2] for d in descs}) == 1:
+        views = [_view_of(a, d, backend) for a, d in zip(arrays, descs)]
+        m, c = (int(n) for n in descs[0][:2])
+        if any(v is None for v in views):
+            views = None
+    if views is None:
+        blocks = [_rows_cols(a, axis, do_full_array) for a in arrays]
+        m, c = (int(n) for n in blocks[0].shape)
+        views = [_strided_view(b, backend) for b in blocks]
+    if backend == "device":
+        device, stream = a0.device, 0
+    else:
+        torch = _torch()
+        if a0.device.type != "cuda":
+            raise RuntimeError("torch inputs must live on an MI355X (device='cuda'); got %s" % a0.device)
+        device = _torch_device_index(a0.device)
+        stream = torch.cuda.current_stream(a0.device).cuda_stream
+    _native.require_device(device)
+    plan = _get_plan(edges, cmp_domain, device)
+    n = m * plan.n_bins
+    if backend == "torch":
+        out = torch.empty((2, n), dtype=torch.float64, device=a0.device)
+        ptr = out.data_ptr()
+    else:
+        buf = _native.DeviceBuffer(device, max(2 * n, 1) * 8)
+        ptr = buf.ptr
+    if n > 0:
+        nv = [_native.make_view(*v[:6]) for v in views]
+        plan.execute_extrema(nv[:-1], nv[-1], m, c, ptr, ptr + n * 8, accumulate=False, stream=stream)
+    if backend != "torch":
+        out = np.empty((2, n), np.float64)
+        if n > 0:
+            buf.download(out)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+    out = out.reshape((2,) + kept_axes_shape + plan.bins_shape)
+    return out[0], out[1]
+
+
+def histogram_extrema(*args, values, bins=None, range=None, axis=None, block_size="auto"):
+    """Per-bin minimum and maximum of ``values``, computed on an MI355X: the extreme value in each bin, as
+    ``scipy.stats.binned_statistic`` gives it with ``statistic="min"`` / ``"max"``.
+
+    ``args``, ``bins``, ``range`` and ``axis`` are those of :func:`histogram`, and the samples that count are exactly the ones
+    ``histogram`` counts (same digitize, last bin closed on the right, NaN and out-of-range samples dropped, the same
+    broadcasting).  The edges are those the unweighted ``histogram`` call gives: estimator names are allowed.  ``values``
+    (any real dtype, converted like ``astype(np.float64)``; broadcast like weights) is what each counted sample contributes.
+    NaN values are ignored (``np.fmin`` / ``np.fmax``), values are ordered totally with ``-0.0 < +0.0``, and a bin that got no
+    value is NaN in both outputs.  The results are exact.  ``block_size`` is accepted and changes nothing.
+
+    Returns ``(vmin, vmax, bin_edges)``: float64, with the shape ``histogram`` gives (kept axes, then bin axes).  numpy in ->
+    numpy out, torch in -> torch out on the same device, DeviceArray in -> numpy out, dask in -> lazy dask arrays."""
+    if values is None:
+        raise TypeError("histogram_extrema needs values")
+    if not args:
+        raise TypeError("histogram_extrema needs at least one array of samples")
+    _check_values_dtype(values)
+    n_inputs = len(args)
+    axis = _normalise_axis(axis, args[0].ndim if hasattr(args[0], "ndim") else np.ndim(args[0]))
+    all_arrays = list(args) + [values]
+    raw = None
+    if any(_is_dask(a) for a in all_arrays):
+        import dask.array as dsa
+
+        backend = "dask"
+        all_arrays = list(dsa.broadcast_arrays(*[a if _is_dask(a) else dsa.asarray(np.asarray(a)) for a in all_arrays]))
+    elif any(_is_torch(a) for a in all_arrays):
+        torch = _torch()
+        backend = "torch"
+        dev = next((a.device for a in all_arrays if _is_torch(a) and a.device.type == "cuda"), None)
+        if dev is None:
+            raise RuntimeError("torch inputs must live on an MI355X (device='cuda'); every tensor given is on the CPU")
+        all_arrays = [a.to(dev) if _is_torch(a) else torch.as_tensor(np.asarray(a)).to(dev) for a in all_arrays]
+        all_arrays = list(torch.broadcast_tensors(*all_arrays))
+    elif any(_is_devarr(a) for a in all_arrays):
+        backend = "device"
+        dev = next(a.device for a in all_arrays if _is_devarr(a))
+        all_arrays = [a.to(dev) if _is_devarr(a) else DeviceArray.from_numpy(np.asarray(a), dev) for a in all_arrays]
+        shape = np.broadcast_shapes(*[a.shape for a in all_arrays])
+        all_arrays = [a.broadcast_to(shape) for a in all_arrays]
+    else:
+        backend = "numpy"
+        raw = [np.asarray(a) for a in all_arrays]
+        all_arrays = list(np.broadcast_arrays(*raw))
+    drop_axes = tuple(axis) if axis is not None else tuple(_range(all_arrays[0].ndim))
+
+    # ---- bin edges: those of the unweighted histogram ------------------------------------------
+    bins = _ensure_correctly_formatted_bins(bins, n_inputs)
+    range = _ensure_correctly_formatted_range(range, n_inputs)
+    if backend == "dask":
+        if not all(isinstance(b, np.ndarray) for b in bins):
+            raise TypeError("When using dask arrays, bins must be provided as numpy array(s) of edges")
+    elif backend in ("torch", "device"):
+        bins = [_device_bin_edges(a, b, r, False) for a, b, r in zip(all_arrays[:n_inputs], bins, range)]
+    else:
+        bins = [np.histogram_bin_edges(a, bins=b, range=r) for a, b, r in zip(all_arrays[:n_inputs], bins, range)]
+
+    if backend == "dask":
+        import dask.array as dsa
+
+        ndim = all_arrays[0].ndim
+        data_index = tuple(_range(1, ndim + 1))
+        bin_index = tuple(_range(ndim + 1, ndim + 1 + n_inputs))
+        operands = [item for arr in all_arrays for item in (arr, data_index)]
+        # one task per block with its (min, max) pair on a leading axis; the pairs of the blocks that share output rows meet
+        # in the key-ordered combine on the host (also under XHIST_AMD_DASK_EXCHANGE=rccl: the exchange adds only)
+        partials = dsa.blockwise(
+            _extrema_block, (0,) + data_index + bin_index, *operands,
+            new_axes=dict([(0, 2)] + [(ax, len(b) - 1) for ax, b in zip(bin_index, bins)]),
+            adjust_chunks={ax + 1: (lambda extent: 1) for ax in drop_axes},
+            meta=np.array((), np.float64), axis=axis, bins=bins,
+        )
+        pair = dsa.reduction(partials, _extrema_pair_reduce, _extrema_pair_reduce, combine=_extrema_pair_reduce,
+                             axis=tuple(ax + 1 for ax in drop_axes), keepdims=False, dtype=np.float64, concatenate=True,
+                             meta=np.array((), np.float64))
+        return pair[0], pair[1], bins
+    if backend == "numpy":
+        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins)
+        vmin, vmax = _extrema_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, "device")
+    else:
+        vmin, vmax = _extrema_rows(all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend)
+    if backend == "torch":
+        keep = [s for i, s in enumerate(vmin.shape) if i not in drop_axes]
+        return vmin.reshape(keep), vmax.reshape(keep), bins
+    return vmin.squeeze(drop_axes), vmax.squeeze(drop_axes), bins

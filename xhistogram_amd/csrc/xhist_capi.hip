@@ -3,6 +3,7 @@
 // No CPU compute path exists here on purpose: without a HIP device every compute entry point
 // fails with XHIST_ERR_NO_DEVICE.
 #include "xhist_pick.hip.h"
+#include "xhist_extrema.hip.h"
 
 #include <dlfcn.h>
 
@@ -245,6 +246,44 @@ extern "C" int xhist_plan_execute_two_weights(xhist_plan* p, const xhist_array* 
   }
   if (int rc = xhist_plan_execute(p, samples, weights_a, n_rows, n_cols, out_a, XHIST_F64, mem_kind, accumulate, stream)) return rc;
   return xhist_plan_execute(p, samples, weights_b, n_rows, n_cols, out_b, XHIST_F64, mem_kind, accumulate, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// per-bin minimum and maximum of a value array (the kernels and their selection: xhist_extrema.hip)
+// ------------------------------------------------------------------------------------------
+void xhist_log_picked_kernel(const void* fn) { log_picked_kernel(fn); }
+
+extern "C" int xhist_plan_execute_extrema(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                                          int64_t n_cols, double* out_min, double* out_max, int mem_kind, int accumulate, void* stream) {
+  if (!values) return fail(XHIST_ERR_INVALID, "values are required");
+  if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out_min, XHIST_F64)) return rc;
+  if (!out_max && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "out_max is NULL");
+  if (mem_kind != XHIST_MEM_DEVICE)
+    return fail(XHIST_ERR_INVALID, "xhist_plan_execute_extrema takes DEVICE arrays (mem_kind XHIST_MEM_DEVICE); upload host data first");
+  if (n_rows * p->n_bins == 0) return XHIST_OK;
+  DeviceGuard g;
+  if (int rc = g.set(p->device)) return rc;
+  ExtremaPlan pl;
+  pl.n_dims = p->n_dims;
+  pl.cmp = p->cmp;
+  pl.n_bins = p->n_bins;
+  pl.cus = p->cus;
+  pl.lds_max = p->lds_max;
+  pl.arith = p->arith;
+  auto tables = [](const TableSet& t) { return ExtremaTables{t.dim, t.blob, t.words, t.max_cnt}; };
+  pl.native = tables(p->ts[0][0]);
+  pl.fine64 = tables(p->ts[0][1]);
+  pl.fine32 = tables(p->ts[1][1]);
+  Range r("xhist_plan_execute_extrema");
+  char err[256] = {0}, desc[256] = {0};
+  const int rc = xhist_extrema_run(pl, samples, values, n_rows, n_cols, out_min, out_max, accumulate, static_cast<hipStream_t>(stream),
+                                   err, sizeof err, desc, sizeof desc);
+  if (rc != XHIST_OK) return fail(rc, "%s", err);
+  if (desc[0]) {
+    std::lock_guard<std::mutex> lk(p->mu);
+    p->desc = desc;
+  }
+  return XHIST_OK;
 }
 
 // ------------------------------------------------------------------------------------------

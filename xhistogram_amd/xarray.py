@@ -11,7 +11,7 @@ from __future__ import annotations
 from .core import histogram as _core_histogram
 from .core import histogram_two_weights as _core_histogram_two_weights
 
-__all__ = ["histogram"]
+__all__ = ["histogram", "histogram_extrema"]
 
 
 def _xr():
@@ -123,3 +123,64 @@ def histogram(*args, bins=None, range=None, dim=None, weights=None, density=Fals
     out_name = "_".join(["histogram"] + [a.name for a in operands[:n_data]])
     out = tuple(xr.DataArray(h, dims=out_dims, coords=coords, name=out_name) for h in h_all)
     return out if pair else out[0]
+
+
+def histogram_extrema(*args, values, bins=None, range=None, dim=None, block_size="auto", keep_coords=False, bin_dim_suffix="_bin"):
+    """Per-bin minimum and maximum of the DataArray ``values`` over the bins of ``args``
+    (:func:`xhistogram_amd.core.histogram_extrema` with the labels of :func:`histogram`).
+
+    ``args``, ``bins``, ``range``, ``dim``, ``keep_coords`` and ``bin_dim_suffix`` are those of :func:`histogram`; ``values``
+    takes the place of its weights (dims a subset of the data's).  Returns ``(vmin, vmax)``: two DataArrays with the dims and
+    coords ``histogram`` gives for the same ``args``, ``bins`` and ``dim``, named ``<values name>_min`` / ``_max`` (``values``
+    when the DataArray has no name)."""
+    from .core import histogram_extrema as _core_histogram_extrema
+
+    xr = _xr()
+    data_args = list(args)
+    n_data = len(data_args)
+    for a in data_args + [values]:
+        if not isinstance(a, xr.DataArray):
+            raise TypeError(
+                "xhistogram.xarray.histogram_extrema accepts only xarray.DataArray objects but a %s was provided" % type(a).__name__
+            )
+    for a in data_args:
+        assert a.name is not None, "all arrays must have a name"
+    operands = list(data_args) if keep_coords else [a.reset_coords(drop=True) for a in data_args]
+    operands.append(values.reset_coords(drop=True))
+    operands = list(xr.align(*operands, join="exact"))
+    first = operands[0]
+    first_coords = first.coords
+    dims_order = []
+    for a in operands:
+        for d in a.dims:
+            if d not in dims_order:
+                dims_order.append(d)
+    lined_up = []
+    for a in operands:
+        missing = [d for d in dims_order if d not in a.dims]
+        if missing:
+            a = a.expand_dims({d: 1 for d in missing})
+        if tuple(a.dims) != tuple(dims_order):
+            a = a.transpose(*dims_order)
+        lined_up.append(a)
+    arrays = [a.data for a in lined_up]
+    v_data = arrays.pop()
+    if dim is not None:
+        kept_dims = [d for d in dims_order if d not in dim]
+        axis = [lined_up[0].get_axis_num(d) for d in dim]
+    else:
+        kept_dims = []
+        axis = None
+    vmin, vmax, edges = _core_histogram_extrema(*arrays, values=v_data, bins=bins, range=range, axis=axis, block_size=block_size)
+    bin_dims = [a.name + bin_dim_suffix for a in operands[:n_data]]
+    out_dims = kept_dims + bin_dims
+    coords = {name: first[name] for name in kept_dims if name in first_coords}
+    for name, e, a in zip(bin_dims, edges, operands):
+        coords[name] = ((name,), 0.5 * (e[:-1] + e[1:]), a.attrs)
+    if keep_coords:
+        for c in first_coords:
+            if c not in coords and set(first[c].dims).issubset(out_dims):
+                coords[c] = first[c]
+    base = values.name or "values"
+    return (xr.DataArray(vmin, dims=out_dims, coords=coords, name="%s_min" % base),
+            xr.DataArray(vmax, dims=out_dims, coords=coords, name="%s_max" % base))
