@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define XHIST_ABI_VERSION 10
+#define XHIST_ABI_VERSION 11
 #define XHIST_MAX_DIMS 8 /* max number of sample arrays (histogram dimensionality) */
 
 typedef enum {
@@ -144,6 +144,21 @@ int xhist_plan_execute_two_weights(xhist_plan* plan, const xhist_array* samples,
 int xhist_plan_execute_extrema(xhist_plan* plan, const xhist_array* samples, const xhist_array* values,
                                int64_t n_rows, int64_t n_cols, double* out_min, double* out_max,
                                int mem_kind, int accumulate, void* stream);
+
+/* Per-bin count, mean and sum of squared deviations of `values` (ABI v11): which samples count is exactly what
+ * xhist_plan_execute counts (same digitize, last bin closed, NaN / out-of-range samples dropped); each counted sample whose
+ * value is not NaN contributes that value converted to float64.  Two passes (Chan, Golub & LeVeque): n and S = sum(v), then
+ * d = v - S/n in float64 and M2 = max(0, sum(d*d) - sum(d)^2 / n).  mean = S/n and M2 are NaN where n == 0; the variance is
+ * M2 / (n - ddof), left to the caller.  Float64 atomics add in arbitrary order: the last bits can differ between runs, except
+ * for data whose sums are exact in every order.
+ *   values: an xhist_array of any real dtype, same logical [n_rows, n_cols] shape as the samples (strides 0 broadcast).
+ *   out_count (int64), out_mean, out_m2 (float64): contiguous [n_rows, prod(nb_d)] DEVICE buffers, overwritten (no
+ *   accumulate mode); one float64 scratch block of that size is taken for the call.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Asynchronous on `stream`.  xhist_plan_describe then names the kernel family of each pass and where its slots live. */
+int xhist_plan_execute_mean_var(xhist_plan* plan, const xhist_array* samples, const xhist_array* values,
+                                int64_t n_rows, int64_t n_cols, int64_t* out_count, double* out_mean, double* out_m2,
+                                int mem_kind, void* stream);
 
 /* One-shot form of the two calls above with an internal plan cache keyed on (device, edges). */
 int xhist_bincount_rows(int device, int n_inputs, const xhist_array* samples,

@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # $XHIST_AMD_LIB points development builds (A/B kernel variants) at another shared object
 LIB_PATH = os.environ.get("XHIST_AMD_LIB") or os.path.join(_HERE, "libxhist_amd.so")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_DIMS = 8
 
 # status codes (xhist_status)
@@ -69,6 +69,7 @@ _lock = threading.Lock()
 EXPORTS = (
     "xhist_abi_version", "xhist_last_error", "xhist_device_count", "xhist_device_info",
     "xhist_plan_create", "xhist_plan_destroy", "xhist_plan_execute", "xhist_plan_execute_two_weights", "xhist_plan_execute_extrema",
+    "xhist_plan_execute_mean_var",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -134,6 +135,10 @@ def load():
         lib.xhist_plan_execute_extrema.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
             C.c_void_p,
+        ]
+        lib.xhist_plan_execute_mean_var.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_int, C.c_void_p,
         ]
         lib.xhist_bincount_rows.argtypes = [
             C.c_int, C.c_int, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_void_p),
@@ -345,6 +350,21 @@ class Plan:
             load().xhist_plan_execute_extrema(
                 self._h, arr, C.byref(value_view), int(n_rows), int(n_cols), C.c_void_p(out_min_ptr), C.c_void_p(out_max_ptr),
                 MEM_DEVICE, 1 if accumulate else 0, C.c_void_p(stream or 0),
+            )
+        )
+
+    def execute_mean_var(self, sample_views, value_view, n_rows, n_cols, out_count_ptr, out_mean_ptr, out_m2_ptr, stream=0):
+        """per-bin count (int64), mean and sum of squared deviations M2 (float64; NaN where no value arrived) of the values of
+        device-resident views, into device buffers of [n_rows, bins] each, asynchronous on `stream`
+        (xhist_plan_execute_mean_var)"""
+        d = self.n_dims
+        if len(sample_views) != d:
+            raise ValueError("plan was built for %d inputs, got %d" % (d, len(sample_views)))
+        arr = (XhistArray * d)(*sample_views)
+        check(
+            load().xhist_plan_execute_mean_var(
+                self._h, arr, C.byref(value_view), int(n_rows), int(n_cols), C.c_void_p(out_count_ptr), C.c_void_p(out_mean_ptr),
+                C.c_void_p(out_m2_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
             )
         )
 

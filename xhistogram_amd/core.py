@@ -21,6 +21,7 @@ import re
 import threading
 from collections import OrderedDict
 from collections.abc import Iterable
+from functools import partial
 
 import warnings
 
@@ -32,7 +33,7 @@ from .devicearray import DeviceArray, _nocopy_reshape_strides
 # range is a keyword of histogram(), like in the reference
 _range = range
 
-__all__ = ["histogram", "histogram_two_weights", "histogram_extrema"]
+__all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1770,18 +1771,18 @@ def _extrema_pair_reduce(x, axis=None, keepdims=True, **_):
     return out if keepdims else out.squeeze(ax)
 
 
-def _check_values_dtype(values):
+def _check_values_dtype(values, name="histogram_extrema"):
     """TypeError, before any device work, for values that have no order or no float64 image"""
     if _is_torch(values):
         if values.dtype.is_complex:
-            raise TypeError("complex values have no order: histogram_extrema takes real values")
+            raise TypeError("complex values have no order: %s takes real values" % name)
         _torch_tag(values.dtype)
         return
     dt = np.dtype(values.dtype) if hasattr(values, "dtype") else np.asarray(values).dtype
     if dt.kind == "c":
-        raise TypeError("complex values have no order: histogram_extrema takes real values")
+        raise TypeError("complex values have no order: %s takes real values" % name)
     if dt.kind not in "fiub":
-        raise TypeError("histogram_extrema takes real values, got dtype %s" % dt)
+        raise TypeError("%s takes real values, got dtype %s" % (name, dt))
 
 
 def _upload_host(args, values, bins):
@@ -1802,9 +1803,12 @@ def _extrema_block(*all_arrays, axis=None, bins=None):
     return np.stack([vmin, vmax])
 
 
-def _extrema_rows(args, values, axis, bins, backend):
-    """(vmin, vmax) of broadcast torch tensors or DeviceArrays: kept axes in place, reduced axes of extent 1, then the bin
-    axes.  The [rows, cols] views of _bincount's block adapter; layouts no three strides describe are copied."""
+def _value_views(args, values, axis, bins, backend):
+    """the [rows, cols] views of broadcast torch tensors or DeviceArrays and of their values, for a per-bin statistic of the
+    values: (plan, native views (samples..., values), the views they were made of (their copies, if any, must outlive the
+    kernels: callers hold them until the download), rows, cols, kept axes shape, device, stream).  The kept axes stay in
+    place and the reduced ones have extent 1 (then come the bin axes).  The views are those of _bincount's block adapter;
+    layouts no three strides describe are copied."""
     a0 = args[0]
     ndim = a0.ndim
     do_full_array = (axis is None) or (set(axis) == set(_range(ndim)))
@@ -1836,15 +1840,23 @@ def _extrema_rows(args, values, axis, bins, backend):
         stream = torch.cuda.current_stream(a0.device).cuda_stream
     _native.require_device(device)
     plan = _get_plan(edges, cmp_domain, device)
+    nv = [_native.make_view(*v[:6]) for v in views]
+    return plan, nv, views, m, c, kept_axes_shape, device, stream
+
+
+def _extrema_rows(args, values, axis, bins, backend):
+    """(vmin, vmax) of broadcast torch tensors or DeviceArrays: kept axes in place, reduced axes of extent 1, then the bin
+    axes."""
+    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend)
     n = m * plan.n_bins
     if backend == "torch":
-        out = torch.empty((2, n), dtype=torch.float64, device=a0.device)
+        torch = _torch()
+        out = torch.empty((2, n), dtype=torch.float64, device=args[0].device)
         ptr = out.data_ptr()
     else:
         buf = _native.DeviceBuffer(device, max(2 * n, 1) * 8)
         ptr = buf.ptr
     if n > 0:
-        nv = [_native.make_view(*v[:6]) for v in views]
         plan.execute_extrema(nv[:-1], nv[-1], m, c, ptr, ptr + n * 8, accumulate=False, stream=stream)
     if backend != "torch":
         out = np.empty((2, n), np.float64)
@@ -1867,11 +1879,38 @@ def histogram_extrema(*args, values, bins=None, range=None, axis=None, block_siz
 
     Returns ``(vmin, vmax, bin_edges)``: float64, with the shape ``histogram`` gives (kept axes, then bin axes).  numpy in ->
     numpy out, torch in -> torch out on the same device, DeviceArray in -> numpy out, dask in -> lazy dask arrays."""
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_extrema")
+    n_inputs = len(args)
+    if backend == "dask":
+        import dask.array as dsa
+
+        # one task per block with its (min, max) pair on a leading axis; the pairs of the blocks that share output rows meet
+        # in the key-ordered combine on the host (also under XHIST_AMD_DASK_EXCHANGE=rccl: the exchange adds only)
+        partials = _values_blockwise(_extrema_block, 2, all_arrays, bins, axis, drop_axes)
+        pair = dsa.reduction(partials, _extrema_pair_reduce, _extrema_pair_reduce, combine=_extrema_pair_reduce,
+                             axis=tuple(ax + 1 for ax in drop_axes), keepdims=False, dtype=np.float64, concatenate=True,
+                             meta=np.array((), np.float64))
+        return pair[0], pair[1], bins
+    if backend == "numpy":
+        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins)
+        vmin, vmax = _extrema_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, "device")
+    else:
+        vmin, vmax = _extrema_rows(all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend)
+    if backend == "torch":
+        keep = [s for i, s in enumerate(vmin.shape) if i not in drop_axes]
+        return vmin.reshape(keep), vmax.reshape(keep), bins
+    return vmin.squeeze(drop_axes), vmax.squeeze(drop_axes), bins
+
+
+def _values_call(args, values, bins, range, axis, name):
+    """the front of a per-bin statistic of values: argument checks before any device work, the backend, the broadcast
+    arrays (samples..., values), the numpy originals (numpy backend), the edges of the unweighted histogram, the normalised
+    axis and the reduced axes"""
     if values is None:
-        raise TypeError("histogram_extrema needs values")
+        raise TypeError("%s needs values" % name)
     if not args:
-        raise TypeError("histogram_extrema needs at least one array of samples")
-    _check_values_dtype(values)
+        raise TypeError("%s needs at least one array of samples" % name)
+    _check_values_dtype(values, name)
     n_inputs = len(args)
     axis = _normalise_axis(axis, args[0].ndim if hasattr(args[0], "ndim") else np.ndim(args[0]))
     all_arrays = list(args) + [values]
@@ -1911,32 +1950,160 @@ def histogram_extrema(*args, values, bins=None, range=None, axis=None, block_siz
         bins = [_device_bin_edges(a, b, r, False) for a, b, r in zip(all_arrays[:n_inputs], bins, range)]
     else:
         bins = [np.histogram_bin_edges(a, bins=b, range=r) for a, b, r in zip(all_arrays[:n_inputs], bins, range)]
+    return backend, all_arrays, raw, bins, axis, drop_axes
 
+
+def _values_blockwise(block_fn, k, all_arrays, bins, axis, drop_axes):
+    """dask: one task per block of the broadcast (samples..., values), each giving k statistics on a leading axis —
+    [k, block axes (reduced ones of extent 1), bins...]"""
+    import dask.array as dsa
+
+    n_inputs = len(all_arrays) - 1
+    ndim = all_arrays[0].ndim
+    data_index = tuple(_range(1, ndim + 1))
+    bin_index = tuple(_range(ndim + 1, ndim + 1 + n_inputs))
+    operands = [item for arr in all_arrays for item in (arr, data_index)]
+    return dsa.blockwise(
+        block_fn, (0,) + data_index + bin_index, *operands,
+        new_axes=dict([(0, k)] + [(ax, len(b) - 1) for ax, b in zip(bin_index, bins)]),
+        adjust_chunks={ax + 1: (lambda extent: 1) for ax in drop_axes},
+        meta=np.array((), np.float64), axis=axis, bins=bins,
+    )
+
+
+# ---------------------------------------------------------------------------------------------
+# per-bin count, mean and variance of a value array
+# ---------------------------------------------------------------------------------------------
+def _check_ddof(ddof):
+    if isinstance(ddof, (bool, np.bool_)) or not isinstance(ddof, (int, np.integer)) or ddof < 0:
+        raise ValueError("ddof must be an integer >= 0, got %r" % (ddof,))
+    return int(ddof)
+
+
+def combine_mean_var(n, mean, m2, axis):
+    """Merge partial (count, mean, M2) results over `axis` (kept as axes of extent 1) with Chan's pairwise formula, one
+    partial after another in index order (C order over several axes):
+        n = na + nb,  d = mb - ma,  mean = ma + d * nb / n,  M2 = M2a + M2b + d^2 * na * nb / n.
+    Partials with n == 0 are skipped; where every partial is empty, mean and M2 are NaN and n is 0.  The reduction of dask's
+    partials.  Returns float64 (n, mean, M2)."""
+    n, mean, m2 = (np.asarray(a, np.float64) for a in (n, mean, m2))
+    ax = tuple(sorted(int(a) % n.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
+    rest = [i for i in _range(n.ndim) if i not in ax]
+    keep_shape = tuple(1 if i in ax else n.shape[i] for i in _range(n.ndim))
+
+    def lead(a):
+        a = np.transpose(a, ax + tuple(rest))
+        return a.reshape((-1,) + a.shape[len(ax):])
+
+    n, mean, m2 = lead(n), lead(mean), lead(m2)
+    cn = np.zeros(n.shape[1:])
+    cm = np.full(n.shape[1:], np.nan)
+    cq = np.full(n.shape[1:], np.nan)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for k in _range(n.shape[0]):
+            nb, mb, qb = n[k], mean[k], m2[k]
+            take = nb > 0
+            first = take & (cn == 0)
+            both = take & (cn > 0)
+            tot = cn + nb
+            d = mb - cm
+            m_new = cm + d * nb / tot
+            q_new = cq + qb + d * d * cn * nb / tot
+            cm = np.where(first, mb, np.where(both, m_new, cm))
+            cq = np.where(first, qb, np.where(both, q_new, cq))
+            cn = np.where(take, tot, cn)
+    return cn.reshape(keep_shape), cm.reshape(keep_shape), cq.reshape(keep_shape)
+
+
+def _mean_var_reduce(x, axis=None, keepdims=True, **_):
+    """dask.array.reduction step over [3, ...] blocks of (n, mean, M2) partials"""
+    ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
+    out = np.stack(combine_mean_var(x[0], x[1], x[2], tuple(a - 1 for a in ax)))
+    return out if keepdims else out.squeeze(ax)
+
+
+def _mean_var_aggregate(x, axis=None, keepdims=True, ddof=0, **_):
+    """the last step: (n, mean, var), the division by n - ddof done here only"""
+    out = _mean_var_reduce(x, axis=axis, keepdims=keepdims)
+    n = out[0]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out[2] = np.where(n > ddof, out[2] / (n - ddof), np.nan)
+    return out
+
+
+def _mean_var_block(*all_arrays, axis=None, bins=None):
+    """one dask block: its (n, mean, M2) as a [3, block axes (reduced ones of extent 1), bins...] float64 numpy array"""
+    arrays = _upload_host(all_arrays[:-1], all_arrays[-1], bins)
+    n, mean, m2 = _mean_var_rows(arrays[:-1], arrays[-1], axis, bins, "device")
+    return np.stack([n.astype(np.float64), mean, m2])
+
+
+def _mean_var_rows(args, values, axis, bins, backend):
+    """(count, mean, M2) of broadcast torch tensors or DeviceArrays: kept axes in place, reduced axes of extent 1, then the
+    bin axes.  count is int64, mean and M2 float64 (NaN where the count is 0)."""
+    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend)
+    n = m * plan.n_bins
+    shape = kept_axes_shape + plan.bins_shape
+    if backend == "torch":
+        torch = _torch()
+        cnt = torch.empty(n, dtype=torch.int64, device=args[0].device)
+        out = torch.empty((2, n), dtype=torch.float64, device=args[0].device)
+        ptrs = (cnt.data_ptr(), out.data_ptr(), out.data_ptr() + n * 8)
+    else:
+        buf = _native.DeviceBuffer(device, max(3 * n, 1) * 8)
+        ptrs = (buf.ptr, buf.ptr + n * 8, buf.ptr + 2 * n * 8)
+    if n > 0:
+        plan.execute_mean_var(nv[:-1], nv[-1], m, c, ptrs[0], ptrs[1], ptrs[2], stream=stream)
+    if backend != "torch":
+        host = np.empty((3, n), np.float64)
+        if n > 0:
+            buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+        cnt, out = host[0].view(np.int64), host[1:]
+    return cnt.reshape(shape), out[0].reshape(shape), out[1].reshape(shape)
+
+
+def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, block_size="auto"):
+    """Per-bin count, mean and variance of ``values``, computed on an MI355X: ``scipy.stats.binned_statistic`` with
+    ``statistic="count"``, ``"mean"`` and ``"std"`` (squared), NaN-ignoring like ``np.nanmean`` / ``np.nanvar``.
+
+    ``args``, ``bins``, ``range`` and ``axis`` are those of :func:`histogram`, and a sample counts when ``histogram`` counts it
+    (same digitize, last bin closed on the right, NaN and out-of-range samples dropped, the same broadcasting) and its value is
+    not NaN.  The edges are those the unweighted ``histogram`` call gives: estimator names are allowed.  ``values`` (any real
+    dtype, converted like ``astype(np.float64)``; broadcast like weights) is what each counted sample contributes.
+    ``block_size`` is accepted and changes nothing.
+
+    Two passes over the data: ``n`` and the float64 sum ``S`` of each bin, ``mean = S / n``; then ``d = v - mean`` in float64
+    and the corrected two-pass sum of squared deviations (Chan, Golub & LeVeque) ``M2 = max(0, sum(d**2) - sum(d)**2 / n)``,
+    ``var = M2 / (n - ddof)``.  The mean is NaN where ``n == 0``, the variance where ``n <= ddof``; infinite values give what
+    ``np.nanmean`` / ``np.nanvar`` give.  Float64 atomics add in arbitrary order, so the last bits of the mean and the
+    variance can differ from run to run; data whose sums are exact in any order give the same bits every time.
+
+    Returns ``(count, mean, var, bin_edges)``: count int64, mean and var float64, with the shape ``histogram`` gives (kept
+    axes, then bin axes).  numpy in -> numpy out, torch in -> torch out on the same device, DeviceArray in -> numpy out, dask
+    in -> lazy dask arrays."""
+    ddof = _check_ddof(ddof)
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_mean_var")
+    n_inputs = len(args)
     if backend == "dask":
         import dask.array as dsa
 
-        ndim = all_arrays[0].ndim
-        data_index = tuple(_range(1, ndim + 1))
-        bin_index = tuple(_range(ndim + 1, ndim + 1 + n_inputs))
-        operands = [item for arr in all_arrays for item in (arr, data_index)]
-        # one task per block with its (min, max) pair on a leading axis; the pairs of the blocks that share output rows meet
-        # in the key-ordered combine on the host (also under XHIST_AMD_DASK_EXCHANGE=rccl: the exchange adds only)
-        partials = dsa.blockwise(
-            _extrema_block, (0,) + data_index + bin_index, *operands,
-            new_axes=dict([(0, 2)] + [(ax, len(b) - 1) for ax, b in zip(bin_index, bins)]),
-            adjust_chunks={ax + 1: (lambda extent: 1) for ax in drop_axes},
-            meta=np.array((), np.float64), axis=axis, bins=bins,
-        )
-        pair = dsa.reduction(partials, _extrema_pair_reduce, _extrema_pair_reduce, combine=_extrema_pair_reduce,
-                             axis=tuple(ax + 1 for ax in drop_axes), keepdims=False, dtype=np.float64, concatenate=True,
-                             meta=np.array((), np.float64))
-        return pair[0], pair[1], bins
+        # one task per block with its (n, mean, M2) on a leading axis; the partials of the blocks that share output rows are
+        # merged on the host in block order (Chan), and the last step divides by n - ddof
+        partials = _values_blockwise(_mean_var_block, 3, all_arrays, bins, axis, drop_axes)
+        res = dsa.reduction(partials, _mean_var_reduce, partial(_mean_var_aggregate, ddof=ddof), combine=_mean_var_reduce,
+                            axis=tuple(ax + 1 for ax in drop_axes), keepdims=False, dtype=np.float64, concatenate=True,
+                            meta=np.array((), np.float64))
+        return res[0].astype(np.int64), res[1], res[2], bins
     if backend == "numpy":
         arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins)
-        vmin, vmax = _extrema_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, "device")
+        cnt, mean, m2 = _mean_var_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, "device")
     else:
-        vmin, vmax = _extrema_rows(all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend)
+        cnt, mean, m2 = _mean_var_rows(all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend)
     if backend == "torch":
-        keep = [s for i, s in enumerate(vmin.shape) if i not in drop_axes]
-        return vmin.reshape(keep), vmax.reshape(keep), bins
-    return vmin.squeeze(drop_axes), vmax.squeeze(drop_axes), bins
+        torch = _torch()
+        var = torch.where(cnt > ddof, m2 / (cnt - ddof).to(torch.float64), torch.full_like(m2, float("nan")))
+        keep = [s for i, s in enumerate(cnt.shape) if i not in drop_axes]
+        return cnt.reshape(keep), mean.reshape(keep), var.reshape(keep), bins
+    with np.errstate(invalid="ignore", divide="ignore"):
+        var = np.where(cnt > ddof, m2 / (cnt - ddof), np.nan)
+    return cnt.squeeze(drop_axes), mean.squeeze(drop_axes), var.squeeze(drop_axes), bins

@@ -4,6 +4,7 @@
 // fails with XHIST_ERR_NO_DEVICE.
 #include "xhist_pick.hip.h"
 #include "xhist_extrema.hip.h"
+#include "xhist_meanvar.hip.h"
 
 #include <dlfcn.h>
 
@@ -253,16 +254,8 @@ extern "C" int xhist_plan_execute_two_weights(xhist_plan* p, const xhist_array* 
 // ------------------------------------------------------------------------------------------
 void xhist_log_picked_kernel(const void* fn) { log_picked_kernel(fn); }
 
-extern "C" int xhist_plan_execute_extrema(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
-                                          int64_t n_cols, double* out_min, double* out_max, int mem_kind, int accumulate, void* stream) {
-  if (!values) return fail(XHIST_ERR_INVALID, "values are required");
-  if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out_min, XHIST_F64)) return rc;
-  if (!out_max && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "out_max is NULL");
-  if (mem_kind != XHIST_MEM_DEVICE)
-    return fail(XHIST_ERR_INVALID, "xhist_plan_execute_extrema takes DEVICE arrays (mem_kind XHIST_MEM_DEVICE); upload host data first");
-  if (n_rows * p->n_bins == 0) return XHIST_OK;
-  DeviceGuard g;
-  if (int rc = g.set(p->device)) return rc;
+// what the extrema and mean_var units need of a plan
+static ExtremaPlan extrema_plan(const xhist_plan* p) {
   ExtremaPlan pl;
   pl.n_dims = p->n_dims;
   pl.cmp = p->cmp;
@@ -274,10 +267,54 @@ extern "C" int xhist_plan_execute_extrema(xhist_plan* p, const xhist_array* samp
   pl.native = tables(p->ts[0][0]);
   pl.fine64 = tables(p->ts[0][1]);
   pl.fine32 = tables(p->ts[1][1]);
+  return pl;
+}
+
+extern "C" int xhist_plan_execute_extrema(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                                          int64_t n_cols, double* out_min, double* out_max, int mem_kind, int accumulate, void* stream) {
+  if (!values) return fail(XHIST_ERR_INVALID, "values are required");
+  if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out_min, XHIST_F64)) return rc;
+  if (!out_max && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "out_max is NULL");
+  if (mem_kind != XHIST_MEM_DEVICE)
+    return fail(XHIST_ERR_INVALID, "xhist_plan_execute_extrema takes DEVICE arrays (mem_kind XHIST_MEM_DEVICE); upload host data first");
+  if (n_rows * p->n_bins == 0) return XHIST_OK;
+  DeviceGuard g;
+  if (int rc = g.set(p->device)) return rc;
+  const ExtremaPlan pl = extrema_plan(p);
   Range r("xhist_plan_execute_extrema");
   char err[256] = {0}, desc[256] = {0};
   const int rc = xhist_extrema_run(pl, samples, values, n_rows, n_cols, out_min, out_max, accumulate, static_cast<hipStream_t>(stream),
                                    err, sizeof err, desc, sizeof desc);
+  if (rc != XHIST_OK) return fail(rc, "%s", err);
+  if (desc[0]) {
+    std::lock_guard<std::mutex> lk(p->mu);
+    p->desc = desc;
+  }
+  return XHIST_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// per-bin count, mean and sum of squared deviations of a value array (the kernels and their selection: xhist_meanvar.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" int xhist_plan_execute_mean_var(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                                           int64_t n_cols, int64_t* out_count, double* out_mean, double* out_m2, int mem_kind, void* stream) {
+  if (!values) return fail(XHIST_ERR_INVALID, "values are required");
+  if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out_mean, XHIST_F64)) return rc;
+  if ((!out_count || !out_m2) && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "out_count / out_m2 is NULL");
+  if (mem_kind != XHIST_MEM_DEVICE)
+    return fail(XHIST_ERR_INVALID, "xhist_plan_execute_mean_var takes DEVICE arrays (mem_kind XHIST_MEM_DEVICE); upload host data first");
+  if (n_rows * p->n_bins == 0) return XHIST_OK;
+  DeviceGuard g;
+  if (int rc = g.set(p->device)) return rc;
+  const ExtremaPlan pl = extrema_plan(p);
+  Range r("xhist_plan_execute_mean_var");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ScratchScope scratch(s);
+  double* sd = nullptr;
+  if (scratch.alloc((void**)&sd, (size_t)(n_rows * p->n_bins) * sizeof(double)) != hipSuccess)
+    return fail(XHIST_ERR_NOMEM, "allocation of the mean_var scratch block failed");
+  char err[256] = {0}, desc[256] = {0};
+  const int rc = xhist_meanvar_run(pl, samples, values, n_rows, n_cols, out_count, out_mean, out_m2, sd, s, err, sizeof err, desc, sizeof desc);
   if (rc != XHIST_OK) return fail(rc, "%s", err);
   if (desc[0]) {
     std::lock_guard<std::mutex> lk(p->mu);

@@ -11,7 +11,7 @@ from __future__ import annotations
 from .core import histogram as _core_histogram
 from .core import histogram_two_weights as _core_histogram_two_weights
 
-__all__ = ["histogram", "histogram_extrema"]
+__all__ = ["histogram", "histogram_extrema", "histogram_mean_var"]
 
 
 def _xr():
@@ -135,13 +135,42 @@ def histogram_extrema(*args, values, bins=None, range=None, dim=None, block_size
     when the DataArray has no name)."""
     from .core import histogram_extrema as _core_histogram_extrema
 
+    (vmin, vmax), out_dims, coords, base = _values_statistic(
+        "histogram_extrema", _core_histogram_extrema, args, values, bins, range, dim, keep_coords, bin_dim_suffix, block_size=block_size)
+    xr = _xr()
+    return (xr.DataArray(vmin, dims=out_dims, coords=coords, name="%s_min" % base),
+            xr.DataArray(vmax, dims=out_dims, coords=coords, name="%s_max" % base))
+
+
+def histogram_mean_var(*args, values, bins=None, range=None, dim=None, ddof=0, block_size="auto", keep_coords=False,
+                       bin_dim_suffix="_bin"):
+    """Per-bin count, mean and variance of the DataArray ``values`` over the bins of ``args``
+    (:func:`xhistogram_amd.core.histogram_mean_var` with the labels of :func:`histogram`).
+
+    ``args``, ``bins``, ``range``, ``dim``, ``keep_coords`` and ``bin_dim_suffix`` are those of :func:`histogram`; ``values``
+    takes the place of its weights (dims a subset of the data's).  Returns ``(count, mean, var)``: three DataArrays with the
+    dims and coords ``histogram`` gives for the same ``args``, ``bins`` and ``dim``, named ``<values name>_count`` / ``_mean``
+    / ``_var`` (``values`` when the DataArray has no name)."""
+    from .core import histogram_mean_var as _core_histogram_mean_var
+
+    (cnt, mean, var), out_dims, coords, base = _values_statistic(
+        "histogram_mean_var", _core_histogram_mean_var, args, values, bins, range, dim, keep_coords, bin_dim_suffix, ddof=ddof,
+        block_size=block_size)
+    xr = _xr()
+    return tuple(xr.DataArray(a, dims=out_dims, coords=coords, name="%s_%s" % (base, suffix))
+                 for a, suffix in ((cnt, "count"), (mean, "mean"), (var, "var")))
+
+
+def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords, bin_dim_suffix, **kw):
+    """a per-bin statistic of ``values`` with the labels of :func:`histogram`: (core_fn's arrays, dims, coords, the values'
+    name or "values")"""
     xr = _xr()
     data_args = list(args)
     n_data = len(data_args)
     for a in data_args + [values]:
         if not isinstance(a, xr.DataArray):
             raise TypeError(
-                "xhistogram.xarray.histogram_extrema accepts only xarray.DataArray objects but a %s was provided" % type(a).__name__
+                "xhistogram.xarray.%s accepts only xarray.DataArray objects but a %s was provided" % (name, type(a).__name__)
             )
     for a in data_args:
         assert a.name is not None, "all arrays must have a name"
@@ -171,7 +200,7 @@ def histogram_extrema(*args, values, bins=None, range=None, dim=None, block_size
     else:
         kept_dims = []
         axis = None
-    vmin, vmax, edges = _core_histogram_extrema(*arrays, values=v_data, bins=bins, range=range, axis=axis, block_size=block_size)
+    *results, edges = core_fn(*arrays, values=v_data, bins=bins, range=range, axis=axis, **kw)
     bin_dims = [a.name + bin_dim_suffix for a in operands[:n_data]]
     out_dims = kept_dims + bin_dims
     coords = {name: first[name] for name in kept_dims if name in first_coords}
@@ -181,6 +210,4 @@ def histogram_extrema(*args, values, bins=None, range=None, dim=None, block_size
         for c in first_coords:
             if c not in coords and set(first[c].dims).issubset(out_dims):
                 coords[c] = first[c]
-    base = values.name or "values"
-    return (xr.DataArray(vmin, dims=out_dims, coords=coords, name="%s_min" % base),
-            xr.DataArray(vmax, dims=out_dims, coords=coords, name="%s_max" % base))
+    return results, out_dims, coords, values.name or "values"
