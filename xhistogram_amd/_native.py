@@ -339,13 +339,17 @@ class Plan:
             )
         )
 
-    def execute_extrema(self, sample_views, value_view, n_rows, n_cols, out_min_ptr, out_max_ptr, accumulate=False, stream=0):
-        """per-bin minimum and maximum of the values (float64 [n_rows, bins] each, NaN where no value arrived) of
-        device-resident views into device buffers, asynchronous on `stream` (xhist_plan_execute_extrema)"""
+    def _sample_array(self, sample_views):
+        """the C array of one view per input the plan was built for"""
         d = self.n_dims
         if len(sample_views) != d:
             raise ValueError("plan was built for %d inputs, got %d" % (d, len(sample_views)))
-        arr = (XhistArray * d)(*sample_views)
+        return (XhistArray * d)(*sample_views)
+
+    def execute_extrema(self, sample_views, value_view, n_rows, n_cols, out_min_ptr, out_max_ptr, accumulate=False, stream=0):
+        """per-bin minimum and maximum of the values (float64 [n_rows, bins] each, NaN where no value arrived) of
+        device-resident views into device buffers, asynchronous on `stream` (xhist_plan_execute_extrema)"""
+        arr = self._sample_array(sample_views)
         check(
             load().xhist_plan_execute_extrema(
                 self._h, arr, C.byref(value_view), int(n_rows), int(n_cols), C.c_void_p(out_min_ptr), C.c_void_p(out_max_ptr),
@@ -357,10 +361,7 @@ class Plan:
         """per-bin count (int64), mean and sum of squared deviations M2 (float64; NaN where no value arrived) of the values of
         device-resident views, into device buffers of [n_rows, bins] each, asynchronous on `stream`
         (xhist_plan_execute_mean_var)"""
-        d = self.n_dims
-        if len(sample_views) != d:
-            raise ValueError("plan was built for %d inputs, got %d" % (d, len(sample_views)))
-        arr = (XhistArray * d)(*sample_views)
+        arr = self._sample_array(sample_views)
         check(
             load().xhist_plan_execute_mean_var(
                 self._h, arr, C.byref(value_view), int(n_rows), int(n_cols), C.c_void_p(out_count_ptr), C.c_void_p(out_mean_ptr),

@@ -19,7 +19,7 @@ from __future__ import annotations
 import os
 import re
 import threading
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from collections.abc import Iterable
 from functools import partial
 
@@ -1796,13 +1796,6 @@ def _upload_host(args, values, bins):
     return [a.broadcast_to(shape) for a in arrays]
 
 
-def _extrema_block(*all_arrays, axis=None, bins=None):
-    """one dask block: its (min, max) pair as a [2, block axes (reduced ones of extent 1), bins...] numpy array"""
-    arrays = _upload_host(all_arrays[:-1], all_arrays[-1], bins)
-    vmin, vmax = _extrema_rows(arrays[:-1], arrays[-1], axis, bins, "device")
-    return np.stack([vmin, vmax])
-
-
 def _value_views(args, values, axis, bins, backend):
     """the [rows, cols] views of broadcast torch tensors or DeviceArrays and of their values, for a per-bin statistic of the
     values: (plan, native views (samples..., values), the views they were made of (their copies, if any, must outlive the
@@ -1844,26 +1837,66 @@ def _value_views(args, values, axis, bins, backend):
     return plan, nv, views, m, c, kept_axes_shape, device, stream
 
 
-def _extrema_rows(args, values, axis, bins, backend):
-    """(vmin, vmax) of broadcast torch tensors or DeviceArrays: kept axes in place, reduced axes of extent 1, then the bin
-    axes."""
+# What the shared paths need of a per-bin statistic of values: its number of outputs (the first an int64 count when
+# `counted`, all others float64), the Plan method that fills them from output pointers, and the dask step that merges the
+# partials of blocks that share output rows.
+_ValueStat = namedtuple("_ValueStat", "k counted method reduce")
+
+
+def _value_stat_rows(stat, args, values, axis, bins, backend):
+    """the statistic's outputs of broadcast torch tensors or DeviceArrays: kept axes in place, reduced axes of extent 1, then
+    the bin axes"""
     plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend)
     n = m * plan.n_bins
+    k, counted = stat.k, int(stat.counted)
     if backend == "torch":
         torch = _torch()
-        out = torch.empty((2, n), dtype=torch.float64, device=args[0].device)
-        ptr = out.data_ptr()
+        cnt = [torch.empty(n, dtype=torch.int64, device=args[0].device)] if counted else []
+        out = torch.empty((k - counted, n), dtype=torch.float64, device=args[0].device)
+        ptrs = [t.data_ptr() for t in cnt] + [out.data_ptr() + i * n * 8 for i in _range(k - counted)]
     else:
-        buf = _native.DeviceBuffer(device, max(2 * n, 1) * 8)
-        ptr = buf.ptr
+        buf = _native.DeviceBuffer(device, max(k * n, 1) * 8)
+        ptrs = [buf.ptr + i * n * 8 for i in _range(k)]
     if n > 0:
-        plan.execute_extrema(nv[:-1], nv[-1], m, c, ptr, ptr + n * 8, accumulate=False, stream=stream)
+        getattr(plan, stat.method)(nv[:-1], nv[-1], m, c, *ptrs, stream=stream)
     if backend != "torch":
-        out = np.empty((2, n), np.float64)
+        host = np.empty((k, n), np.float64)
         if n > 0:
-            buf.download(out)  # (waits for the kernels: the views' keepalive copies are not needed after this)
-    out = out.reshape((2,) + kept_axes_shape + plan.bins_shape)
-    return out[0], out[1]
+            buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+        cnt, out = [host[0].view(np.int64)] if counted else [], host[counted:]
+    shape = kept_axes_shape + plan.bins_shape
+    return [a.reshape(shape) for a in cnt + list(out)]
+
+
+def _value_stat_block(*all_arrays, stat=None, axis=None, bins=None):
+    """one dask block: its statistic as a [k, block axes (reduced ones of extent 1), bins...] float64 numpy array"""
+    arrays = _upload_host(all_arrays[:-1], all_arrays[-1], bins)
+    outs = _value_stat_rows(_VALUE_STATS[stat], arrays[:-1], arrays[-1], axis, bins, "device")
+    return np.stack([a.astype(np.float64, copy=False) for a in outs])
+
+
+def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None):
+    """the backends of a per-bin statistic of values: (backend, the outputs with the shape ``histogram`` gives, bin edges,
+    reduced axes).  dask: lazy float64 arrays, the partials merged by stat.reduce and the last step by `aggregate`."""
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name)
+    n_inputs = len(args)
+    st = _VALUE_STATS[stat]
+    if backend == "dask":
+        import dask.array as dsa
+
+        partials = _values_blockwise(partial(_value_stat_block, stat=stat), st.k, all_arrays, bins, axis, drop_axes)
+        res = dsa.reduction(partials, st.reduce, aggregate or st.reduce, combine=st.reduce, axis=tuple(ax + 1 for ax in drop_axes),
+                            keepdims=False, dtype=np.float64, concatenate=True, meta=np.array((), np.float64))
+        return backend, [res[i] for i in _range(st.k)], bins, drop_axes
+    if backend == "numpy":
+        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins)
+        outs = _value_stat_rows(st, arrays[:n_inputs], arrays[n_inputs], axis, bins, "device")
+    else:
+        outs = _value_stat_rows(st, all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend)
+    if backend == "torch":
+        keep = [s for i, s in enumerate(outs[0].shape) if i not in drop_axes]
+        return backend, [a.reshape(keep) for a in outs], bins, drop_axes
+    return backend, [a.squeeze(drop_axes) for a in outs], bins, drop_axes
 
 
 def histogram_extrema(*args, values, bins=None, range=None, axis=None, block_size="auto"):
@@ -1879,27 +1912,10 @@ def histogram_extrema(*args, values, bins=None, range=None, axis=None, block_siz
 
     Returns ``(vmin, vmax, bin_edges)``: float64, with the shape ``histogram`` gives (kept axes, then bin axes).  numpy in ->
     numpy out, torch in -> torch out on the same device, DeviceArray in -> numpy out, dask in -> lazy dask arrays."""
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_extrema")
-    n_inputs = len(args)
-    if backend == "dask":
-        import dask.array as dsa
-
-        # one task per block with its (min, max) pair on a leading axis; the pairs of the blocks that share output rows meet
-        # in the key-ordered combine on the host (also under XHIST_AMD_DASK_EXCHANGE=rccl: the exchange adds only)
-        partials = _values_blockwise(_extrema_block, 2, all_arrays, bins, axis, drop_axes)
-        pair = dsa.reduction(partials, _extrema_pair_reduce, _extrema_pair_reduce, combine=_extrema_pair_reduce,
-                             axis=tuple(ax + 1 for ax in drop_axes), keepdims=False, dtype=np.float64, concatenate=True,
-                             meta=np.array((), np.float64))
-        return pair[0], pair[1], bins
-    if backend == "numpy":
-        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins)
-        vmin, vmax = _extrema_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, "device")
-    else:
-        vmin, vmax = _extrema_rows(all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend)
-    if backend == "torch":
-        keep = [s for i, s in enumerate(vmin.shape) if i not in drop_axes]
-        return vmin.reshape(keep), vmax.reshape(keep), bins
-    return vmin.squeeze(drop_axes), vmax.squeeze(drop_axes), bins
+    # dask: one task per block with its (min, max) pair on a leading axis; the pairs of the blocks that share output rows meet
+    # in the key-ordered combine on the host (also under XHIST_AMD_DASK_EXCHANGE=rccl: the exchange adds only)
+    _, (vmin, vmax), bins, _ = _value_stat("extrema", args, values, bins, range, axis, "histogram_extrema")
+    return vmin, vmax, bins
 
 
 def _values_call(args, values, bins, range, axis, name):
@@ -2031,37 +2047,6 @@ def _mean_var_aggregate(x, axis=None, keepdims=True, ddof=0, **_):
     return out
 
 
-def _mean_var_block(*all_arrays, axis=None, bins=None):
-    """one dask block: its (n, mean, M2) as a [3, block axes (reduced ones of extent 1), bins...] float64 numpy array"""
-    arrays = _upload_host(all_arrays[:-1], all_arrays[-1], bins)
-    n, mean, m2 = _mean_var_rows(arrays[:-1], arrays[-1], axis, bins, "device")
-    return np.stack([n.astype(np.float64), mean, m2])
-
-
-def _mean_var_rows(args, values, axis, bins, backend):
-    """(count, mean, M2) of broadcast torch tensors or DeviceArrays: kept axes in place, reduced axes of extent 1, then the
-    bin axes.  count is int64, mean and M2 float64 (NaN where the count is 0)."""
-    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend)
-    n = m * plan.n_bins
-    shape = kept_axes_shape + plan.bins_shape
-    if backend == "torch":
-        torch = _torch()
-        cnt = torch.empty(n, dtype=torch.int64, device=args[0].device)
-        out = torch.empty((2, n), dtype=torch.float64, device=args[0].device)
-        ptrs = (cnt.data_ptr(), out.data_ptr(), out.data_ptr() + n * 8)
-    else:
-        buf = _native.DeviceBuffer(device, max(3 * n, 1) * 8)
-        ptrs = (buf.ptr, buf.ptr + n * 8, buf.ptr + 2 * n * 8)
-    if n > 0:
-        plan.execute_mean_var(nv[:-1], nv[-1], m, c, ptrs[0], ptrs[1], ptrs[2], stream=stream)
-    if backend != "torch":
-        host = np.empty((3, n), np.float64)
-        if n > 0:
-            buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
-        cnt, out = host[0].view(np.int64), host[1:]
-    return cnt.reshape(shape), out[0].reshape(shape), out[1].reshape(shape)
-
-
 def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, block_size="auto"):
     """Per-bin count, mean and variance of ``values``, computed on an MI355X: ``scipy.stats.binned_statistic`` with
     ``statistic="count"``, ``"mean"`` and ``"std"`` (squared), NaN-ignoring like ``np.nanmean`` / ``np.nanvar``.
@@ -2082,28 +2067,22 @@ def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, 
     axes, then bin axes).  numpy in -> numpy out, torch in -> torch out on the same device, DeviceArray in -> numpy out, dask
     in -> lazy dask arrays."""
     ddof = _check_ddof(ddof)
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_mean_var")
-    n_inputs = len(args)
+    # dask: one task per block with its (n, mean, M2) on a leading axis; the partials of the blocks that share output rows are
+    # merged on the host in block order (Chan), and the last step divides by n - ddof
+    backend, (cnt, mean, m2), bins, _ = _value_stat("mean_var", args, values, bins, range, axis, "histogram_mean_var",
+                                                   partial(_mean_var_aggregate, ddof=ddof))
     if backend == "dask":
-        import dask.array as dsa
-
-        # one task per block with its (n, mean, M2) on a leading axis; the partials of the blocks that share output rows are
-        # merged on the host in block order (Chan), and the last step divides by n - ddof
-        partials = _values_blockwise(_mean_var_block, 3, all_arrays, bins, axis, drop_axes)
-        res = dsa.reduction(partials, _mean_var_reduce, partial(_mean_var_aggregate, ddof=ddof), combine=_mean_var_reduce,
-                            axis=tuple(ax + 1 for ax in drop_axes), keepdims=False, dtype=np.float64, concatenate=True,
-                            meta=np.array((), np.float64))
-        return res[0].astype(np.int64), res[1], res[2], bins
-    if backend == "numpy":
-        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins)
-        cnt, mean, m2 = _mean_var_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, "device")
-    else:
-        cnt, mean, m2 = _mean_var_rows(all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend)
+        return cnt.astype(np.int64), mean, m2, bins
     if backend == "torch":
         torch = _torch()
         var = torch.where(cnt > ddof, m2 / (cnt - ddof).to(torch.float64), torch.full_like(m2, float("nan")))
-        keep = [s for i, s in enumerate(cnt.shape) if i not in drop_axes]
-        return cnt.reshape(keep), mean.reshape(keep), var.reshape(keep), bins
+        return cnt, mean, var, bins
     with np.errstate(invalid="ignore", divide="ignore"):
         var = np.where(cnt > ddof, m2 / (cnt - ddof), np.nan)
-    return cnt.squeeze(drop_axes), mean.squeeze(drop_axes), var.squeeze(drop_axes), bins
+    return cnt, mean, var, bins
+
+
+_VALUE_STATS = {
+    "extrema": _ValueStat(2, False, "execute_extrema", _extrema_pair_reduce),
+    "mean_var": _ValueStat(3, True, "execute_mean_var", _mean_var_reduce),
+}

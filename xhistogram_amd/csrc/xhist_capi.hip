@@ -250,41 +250,45 @@ extern "C" int xhist_plan_execute_two_weights(xhist_plan* p, const xhist_array* 
 }
 
 // ------------------------------------------------------------------------------------------
-// per-bin minimum and maximum of a value array (the kernels and their selection: xhist_extrema.hip)
+// per-bin statistics of a value array: minimum and maximum (xhist_extrema.hip), count, mean and sum of squared deviations
+// (xhist_meanvar.hip); the choice and the launches they share: xhist_values.hip.h
 // ------------------------------------------------------------------------------------------
 void xhist_log_picked_kernel(const void* fn) { log_picked_kernel(fn); }
 
-// what the extrema and mean_var units need of a plan
-static ExtremaPlan extrema_plan(const xhist_plan* p) {
-  ExtremaPlan pl;
+// what the statistics' units need of a plan
+static ValuesPlan values_plan(const xhist_plan* p) {
+  ValuesPlan pl;
   pl.n_dims = p->n_dims;
   pl.cmp = p->cmp;
   pl.n_bins = p->n_bins;
   pl.cus = p->cus;
   pl.lds_max = p->lds_max;
   pl.arith = p->arith;
-  auto tables = [](const TableSet& t) { return ExtremaTables{t.dim, t.blob, t.words, t.max_cnt}; };
+  auto tables = [](const TableSet& t) { return ValuesTables{t.dim, t.blob, t.words, t.max_cnt}; };
   pl.native = tables(p->ts[0][0]);
   pl.fine64 = tables(p->ts[0][1]);
   pl.fine32 = tables(p->ts[1][1]);
   return pl;
 }
 
-extern "C" int xhist_plan_execute_extrema(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
-                                          int64_t n_cols, double* out_min, double* out_max, int mem_kind, int accumulate, void* stream) {
+// The checks and the tail both entry points share: `out` is the statistic's float64 output validate_arrays checks,
+// `outs_ok` whether the others are given (`outs_missing` the message if not).  run(plan, err, err_cap, desc, desc_cap) launches
+// on the plan's device; the line it writes to `desc` becomes the plan's describe().
+template <class Run>
+static int execute_values(xhist_plan* p, const char* name, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                          int64_t n_cols, double* out, bool outs_ok, const char* outs_missing, int mem_kind, Run run) {
   if (!values) return fail(XHIST_ERR_INVALID, "values are required");
-  if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out_min, XHIST_F64)) return rc;
-  if (!out_max && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "out_max is NULL");
+  if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out, XHIST_F64)) return rc;
+  if (!outs_ok && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "%s", outs_missing);
   if (mem_kind != XHIST_MEM_DEVICE)
-    return fail(XHIST_ERR_INVALID, "xhist_plan_execute_extrema takes DEVICE arrays (mem_kind XHIST_MEM_DEVICE); upload host data first");
+    return fail(XHIST_ERR_INVALID, "%s takes DEVICE arrays (mem_kind XHIST_MEM_DEVICE); upload host data first", name);
   if (n_rows * p->n_bins == 0) return XHIST_OK;
   DeviceGuard g;
   if (int rc = g.set(p->device)) return rc;
-  const ExtremaPlan pl = extrema_plan(p);
-  Range r("xhist_plan_execute_extrema");
+  const ValuesPlan pl = values_plan(p);
+  Range r(name);
   char err[256] = {0}, desc[256] = {0};
-  const int rc = xhist_extrema_run(pl, samples, values, n_rows, n_cols, out_min, out_max, accumulate, static_cast<hipStream_t>(stream),
-                                   err, sizeof err, desc, sizeof desc);
+  const int rc = run(pl, err, sizeof err, desc, sizeof desc);
   if (rc != XHIST_OK) return fail(rc, "%s", err);
   if (desc[0]) {
     std::lock_guard<std::mutex> lk(p->mu);
@@ -293,34 +297,29 @@ extern "C" int xhist_plan_execute_extrema(xhist_plan* p, const xhist_array* samp
   return XHIST_OK;
 }
 
-// ------------------------------------------------------------------------------------------
-// per-bin count, mean and sum of squared deviations of a value array (the kernels and their selection: xhist_meanvar.hip)
-// ------------------------------------------------------------------------------------------
+extern "C" int xhist_plan_execute_extrema(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                                          int64_t n_cols, double* out_min, double* out_max, int mem_kind, int accumulate, void* stream) {
+  return execute_values(p, "xhist_plan_execute_extrema", samples, values, n_rows, n_cols, out_min, out_max != nullptr,
+                        "out_max is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
+                          return xhist_extrema_run(pl, samples, values, n_rows, n_cols, out_min, out_max, accumulate,
+                                                   static_cast<hipStream_t>(stream), err, err_cap, desc, desc_cap);
+                        });
+}
+
 extern "C" int xhist_plan_execute_mean_var(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
                                            int64_t n_cols, int64_t* out_count, double* out_mean, double* out_m2, int mem_kind, void* stream) {
-  if (!values) return fail(XHIST_ERR_INVALID, "values are required");
-  if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out_mean, XHIST_F64)) return rc;
-  if ((!out_count || !out_m2) && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "out_count / out_m2 is NULL");
-  if (mem_kind != XHIST_MEM_DEVICE)
-    return fail(XHIST_ERR_INVALID, "xhist_plan_execute_mean_var takes DEVICE arrays (mem_kind XHIST_MEM_DEVICE); upload host data first");
-  if (n_rows * p->n_bins == 0) return XHIST_OK;
-  DeviceGuard g;
-  if (int rc = g.set(p->device)) return rc;
-  const ExtremaPlan pl = extrema_plan(p);
-  Range r("xhist_plan_execute_mean_var");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ScratchScope scratch(s);
-  double* sd = nullptr;
-  if (scratch.alloc((void**)&sd, (size_t)(n_rows * p->n_bins) * sizeof(double)) != hipSuccess)
-    return fail(XHIST_ERR_NOMEM, "allocation of the mean_var scratch block failed");
-  char err[256] = {0}, desc[256] = {0};
-  const int rc = xhist_meanvar_run(pl, samples, values, n_rows, n_cols, out_count, out_mean, out_m2, sd, s, err, sizeof err, desc, sizeof desc);
-  if (rc != XHIST_OK) return fail(rc, "%s", err);
-  if (desc[0]) {
-    std::lock_guard<std::mutex> lk(p->mu);
-    p->desc = desc;
-  }
-  return XHIST_OK;
+  return execute_values(p, "xhist_plan_execute_mean_var", samples, values, n_rows, n_cols, out_mean, out_count && out_m2,
+                        "out_count / out_m2 is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
+                          hipStream_t s = static_cast<hipStream_t>(stream);
+                          ScratchScope scratch(s);
+                          double* sd = nullptr;  // the sums of d
+                          if (scratch.alloc((void**)&sd, (size_t)(n_rows * p->n_bins) * sizeof(double)) != hipSuccess) {
+                            snprintf(err, err_cap, "allocation of the mean_var scratch block failed");
+                            return (int)XHIST_ERR_NOMEM;
+                          }
+                          return xhist_meanvar_run(pl, samples, values, n_rows, n_cols, out_count, out_mean, out_m2, sd, s, err, err_cap,
+                                                   desc, desc_cap);
+                        });
 }
 
 // ------------------------------------------------------------------------------------------

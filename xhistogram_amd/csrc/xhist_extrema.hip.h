@@ -1,5 +1,5 @@
-// xhist_extrema.hip.h — per-bin minimum and maximum of a value array (histogram_extrema): the kernels, and what the C ABI
-// (xhist_capi.hip) hands the selection function of the translation unit xhist_extrema.hip.
+// xhist_extrema.hip.h — per-bin minimum and maximum of a value array (histogram_extrema): the keys, the statistic's policy
+// for the shared kernel skeletons of xhist_values.hip.h, its binning kernels, and the driver of xhist_extrema.hip.
 //
 // Which samples count is decided exactly as for the histogram: the same digitize, the same tables.  What a counted sample
 // contributes is its value, converted to float64 (numpy's astype) and mapped to an order-preserving unsigned key
@@ -20,9 +20,7 @@
 // the current one.  The flush into the output and the kernels that work straight in global memory filter the same way.
 #pragma once
 
-#include "xhist_kernels.hip.h"
-
-#include "../../include/xhist_amd.h"
+#include "xhist_values.hip.h"
 
 namespace xhist {
 
@@ -66,64 +64,68 @@ struct ExtKeys<uint32_t> {
   static __device__ __forceinline__ uint64_t wide(uint32_t k) { return extrema_key64((double)extrema_value32(k)); }
 };
 
-// one key into a bin's LDS slot, atomics only where it improves on what the slot holds
+// The statistic of the shared skeletons (xhist_values.hip.h): a bin's [min, max] keys, KT 64-bit (float64 values, and every
+// value of the generic family) or 32-bit (float32 values of the fast family).  One copy of the slots.
 template <typename KT>
-__device__ __forceinline__ void ext_lds_update(typename ExtKeys<KT>::slot_t* slots, uint32_t bin, KT k) {
-  typename ExtKeys<KT>::slot_t* s = slots + bin;
-  const typename ExtKeys<KT>::slot_t cur = *s;
-  KT* keys = reinterpret_cast<KT*>(s);
-  if (k < cur[0]) atomicMin(keys, k);
-  if (k > cur[1]) atomicMax(keys + 1, k);
-}
-
-// ... and into the output's two key arrays (global memory): the same filter on a relaxed read of each
-__device__ __forceinline__ void ext_global_update(uint64_t* kmin, uint64_t* kmax, int64_t bin, uint64_t k) {
-  if (k < __hip_atomic_load(kmin + bin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-    atomicMin(reinterpret_cast<unsigned long long*>(kmin + bin), (unsigned long long)k);
-  if (k > __hip_atomic_load(kmax + bin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-    atomicMax(reinterpret_cast<unsigned long long*>(kmax + bin), (unsigned long long)k);
-}
-
-// the slots sit behind the staged tables, 16-byte aligned
-__host__ __device__ __forceinline__ size_t ext_slots_offset(const Params& p) { return (size_t)((p.table_words + 1) & ~1) * 8; }
-
-template <typename KT>
-__device__ __forceinline__ void ext_init(typename ExtKeys<KT>::slot_t* slots, uint32_t n_bins) {
-  typename ExtKeys<KT>::slot_t e;
-  e[0] = ExtKeys<KT>::kMin;
-  e[1] = ExtKeys<KT>::kMax;
-  for (uint32_t b = threadIdx.x; b < n_bins; b += blockDim.x) slots[b] = e;
-}
-
-// a workgroup's LDS slots into the output rows `kmin` / `kmax`; bins nothing reached are skipped
-template <typename KT>
-__device__ __forceinline__ void ext_flush(const typename ExtKeys<KT>::slot_t* slots, uint32_t n_bins, uint64_t* kmin, uint64_t* kmax) {
-  for (uint32_t b = threadIdx.x; b < n_bins; b += blockDim.x) {
-    const typename ExtKeys<KT>::slot_t s = slots[b];
-    if (s[0] == ExtKeys<KT>::kMin) continue;  // (the min and the max of a bin are set together)
-    const uint64_t lo = ExtKeys<KT>::wide(s[0]), hi = ExtKeys<KT>::wide(s[1]);
-    if (lo < __hip_atomic_load(kmin + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      atomicMin(reinterpret_cast<unsigned long long*>(kmin + b), (unsigned long long)lo);
-    if (hi > __hip_atomic_load(kmax + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      atomicMax(reinterpret_cast<unsigned long long*>(kmax + b), (unsigned long long)hi);
+struct ExtAcc {
+  using K = ExtKeys<KT>;
+  using slot_t = typename K::slot_t;
+  static constexpr bool kCopies = false;
+  static __device__ __forceinline__ void init(slot_t* slots, const Params& p, int64_t) {
+    slot_t e;
+    e[0] = K::kMin;
+    e[1] = K::kMax;
+    for (uint32_t b = threadIdx.x; b < (uint32_t)p.n_bins; b += blockDim.x) slots[b] = e;
   }
-}
+  // one value into a bin's LDS slot, atomics only where its key improves on what the slot holds
+  template <typename V>
+  static __device__ __forceinline__ void lds_add(slot_t* slots, uint32_t bin, V v) {
+    const KT k = K::key(v);
+    slot_t* s = slots + bin;
+    const slot_t cur = *s;
+    KT* keys = reinterpret_cast<KT*>(s);
+    if (k < cur[0]) atomicMin(keys, k);
+    if (k > cur[1]) atomicMax(keys + 1, k);
+  }
+  // ... and into the output's two key arrays (global memory): the same filter on a relaxed read of each
+  static __device__ __forceinline__ void global_update(uint64_t* kmin, uint64_t* kmax, int64_t bin, uint64_t lo, uint64_t hi) {
+    if (lo < __hip_atomic_load(kmin + bin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+      atomicMin(reinterpret_cast<unsigned long long*>(kmin + bin), (unsigned long long)lo);
+    if (hi > __hip_atomic_load(kmax + bin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+      atomicMax(reinterpret_cast<unsigned long long*>(kmax + bin), (unsigned long long)hi);
+  }
+  static __device__ __forceinline__ void global_add(const Params& p, int64_t row, int64_t bin, double v) {
+    const uint64_t k = extrema_key64(v);
+    global_update(reinterpret_cast<uint64_t*>(p.out) + row * p.n_bins, reinterpret_cast<uint64_t*>(p.out2) + row * p.n_bins, bin, k, k);
+  }
+  // the workgroup's slots into its output rows of minimum keys (out) and maximum keys (out2); bins nothing reached are skipped
+  static __device__ __forceinline__ void flush(const slot_t* slots, const Params& p, int64_t row) {
+    uint64_t* kmin = reinterpret_cast<uint64_t*>(p.out) + row * p.n_bins;
+    uint64_t* kmax = reinterpret_cast<uint64_t*>(p.out2) + row * p.n_bins;
+    for (uint32_t b = threadIdx.x; b < (uint32_t)p.n_bins; b += blockDim.x) {
+      const slot_t s = slots[b];
+      if (s[0] == K::kMin) continue;  // (the min and the max of a bin are set together)
+      global_update(kmin, kmax, b, K::wide(s[0]), K::wide(s[1]));
+    }
+  }
+};
 
-// ---------------------------------------------------------------------------------------------
-// GENERIC family: any dtype per input and for the values, any element strides (broadcast and grouped rows), 1..8 inputs,
-// compare domains 0 (float64), 1 (int64) and 3 (per input).  Params as for hist_generic, with the values in the w_* fields,
-// the minimum keys at `out` and the maximum keys at `out2` ([n_rows, n_bins] each, pre-advanced to row p.row0).
-//   LDS: the slots of every bin in LDS behind the tables (which are then in LDS too).  Else every update goes to global
-//   memory, and the tables are read from LDS when they fit there (p.tables_in_lds) and through L2 otherwise.
-// ---------------------------------------------------------------------------------------------
+// The binning kernels: extrema_generic<CMP, LDS> (block 512) and extrema_fast<ST, D, SCAN> (block 256), the families of
+// xhist_values.hip.h with the minimum keys at `out` and the maximum keys at `out2`.  Keys are 32-bit for float32 values.
+//
+// extrema_generic keeps the strided loop of values_generic_body written out in the kernel.  Through the shared body the
+// LDS instances (<*, true>) hoist the per-input Params fields out of the loop and spill twice as many SGPRs (138 -> 266 for
+// <0, true>), which costs up to 3.5% on int64 / mixed-domain inputs; written in the kernel they reload them from the
+// kernel arguments.  The mean_var generic kernels use the shared body, as they always did.
 template <int CMP, bool LDS>
 __global__ void __launch_bounds__(512) extrema_generic(const Params p) {
   using CT = typename Dom<CMP>::T;
+  using A = ExtAcc<uint64_t>;
   const int64_t row = blockIdx.x / p.segs;
   const int seg = blockIdx.x % p.segs;
   const uint64_t* tab = p.tables_in_lds ? stage_tables(p) : p.tables;
-  ext_slot64* slots = reinterpret_cast<ext_slot64*>(xhist_smem + ext_slots_offset(p));
-  if (LDS) ext_init<uint64_t>(slots, (uint32_t)p.n_bins);
+  A::slot_t* slots = reinterpret_cast<A::slot_t*>(xhist_smem + ext_slots_offset(p));
+  if (LDS) A::init(slots, p, row);
   __syncthreads();
 
   uint64_t* kmin = reinterpret_cast<uint64_t*>(p.out) + row * p.n_bins;
@@ -137,7 +139,7 @@ __global__ void __launch_bounds__(512) extrema_generic(const Params p) {
   const int64_t stride = (int64_t)p.segs * blockDim.x;
   for (int64_t i = (int64_t)seg * blockDim.x + threadIdx.x; i < p.n_cols; i += stride) {
     const double v = load_as<double>(p.w_ptr, p.w_dt, voff + i * p.w_cs);
-    bool ok = v == v;  // NaN values are ignored (np.fmin / np.fmax)
+    bool ok = v == v;
     int64_t flat = 0;
 #pragma unroll
     for (int d = 0; d < kMaxDims; ++d) {
@@ -150,120 +152,24 @@ __global__ void __launch_bounds__(512) extrema_generic(const Params p) {
     }
     if (!ok) continue;
     const uint64_t k = extrema_key64(v);
-    if (LDS) ext_lds_update<uint64_t>(slots, (uint32_t)flat, k);
-    else ext_global_update(kmin, kmax, flat, k);
+    if (LDS) A::lds_add(slots, (uint32_t)flat, v);
+    else A::global_update(kmin, kmax, flat, k, k);
   }
   if (LDS) {
     __syncthreads();
-    ext_flush<uint64_t>(slots, (uint32_t)p.n_bins, kmin, kmax);
+    A::flush(slots, p, row);
   }
 }
-
-// ---------------------------------------------------------------------------------------------
-// VECTOR fast path: float32 or float64 samples with values of the same type, unit column stride, one or two inputs, bins in
-// LDS; digitize by the tables with at most two edges per bucket (SCAN 1 / 2: float64 edges for float64 samples, float32
-// thresholds for float32 ones) or by arithmetic (kScanArith).  Tiles as in hist_fast: VEC elements per 16-byte load, UNROLL
-// loads in flight per array and lane; the workgroups of a row walk its tiles interleaved.  Keys are 32-bit for float32 values.
-// ---------------------------------------------------------------------------------------------
 template <typename ST, int D, int SCAN>
 __global__ void __launch_bounds__(256) extrema_fast(const Params p) {
-  static_assert(__is_same(ST, double) || __is_same(ST, float), "float32 / float64 samples and values");
-  static_assert(SCAN == 1 || SCAN == 2 || SCAN == kScanArith, "tables with <= 2 edges per bucket, or arithmetic edges");
-  constexpr int CMP = (__is_same(ST, float) && SCAN != kScanArith) ? 2 : 0;
-  constexpr int VEC = 16 / (int)sizeof(ST);
-  constexpr int UNROLL = D == 1 ? 4 : 8 / VEC;  // 128 bytes of samples and values per lane in flight (192 for two inputs)
-  using KT = typename std::conditional<__is_same(ST, float), uint32_t, uint64_t>::type;
-  using K = ExtKeys<KT>;
-  using slot_t = typename K::slot_t;
-  using svec = typename VecOf<ST, VEC>::type;
-
-  const int tid = threadIdx.x;
-  const int64_t row = blockIdx.x / p.segs;
-  const int seg = blockIdx.x % p.segs;
-  const uint64_t* tab = stage_tables(p);
-  slot_t* slots = reinterpret_cast<slot_t*>(xhist_smem + ext_slots_offset(p));
-  ext_init<KT>(slots, (uint32_t)p.n_bins);
-  __syncthreads();
-
-  const ST* sp[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) sp[d] = reinterpret_cast<const ST*>(p.s_ptr[d]) + row_offset(p.row0 + row, p.s_rs[d], p.s_ir[d], p.s_os[d]);
-  const ST* vp = reinterpret_cast<const ST*>(p.w_ptr) + row_offset(p.row0 + row, p.w_rs, p.w_ir, p.w_os);
-  const uint32_t nb1 = D == 2 ? (uint32_t)p.dim[1].nb : 1u;
-
-  const int64_t tile_elems = (int64_t)blockDim.x * VEC * UNROLL;
-  const int64_t n_tiles = (p.n_cols + tile_elems - 1) / tile_elems;
-  for (int64_t t = seg; t < n_tiles; t += p.segs) {
-    const int64_t base = t * tile_elems;
-    svec xv[D][UNROLL], vv[UNROLL];
-    if (base + tile_elems <= p.n_cols) {
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t i = base + ((int64_t)u * blockDim.x + tid) * VEC;
-#pragma unroll
-        for (int d = 0; d < D; ++d) xv[d][u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(sp[d] + i));
-        vv[u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(vp + i));
-      }
-    } else {  // the ragged last tile: positions past the end become NaN samples, which digitize drops
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t i = base + ((int64_t)u * blockDim.x + tid) * VEC;
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-          const bool in = i + v < p.n_cols;
-#pragma unroll
-          for (int d = 0; d < D; ++d) xv[d][u][v] = in ? sp[d][i + v] : (ST)__builtin_nanf("");
-          vv[u][v] = in ? vp[i + v] : (ST)__builtin_nanf("");
-        }
-      }
-    }
-    uint32_t cnt[D][UNROLL][VEC];
-    count_le_tile<CMP, SCAN, D, UNROLL, VEC>(xv, p, tab, 1, cnt);
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) {
-        const ST val = vv[u][v];
-        bool ok = val == val;
-        uint32_t flat = 0;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-          const int b = bin_from_tile_count<CMP, SCAN>((typename Dom<CMP>::T)xv[d][u][v], p.dim[d], cnt[d][u][v]);
-          ok &= b >= 0;
-          flat = d == 0 ? (uint32_t)b : flat * nb1 + (uint32_t)b;
-        }
-        if (ok) ext_lds_update<KT>(slots, flat, K::key(val));
-      }
-  }
-  __syncthreads();
-  ext_flush<KT>(slots, (uint32_t)p.n_bins, reinterpret_cast<uint64_t*>(p.out) + row * p.n_bins,
-                reinterpret_cast<uint64_t*>(p.out2) + row * p.n_bins);
+  values_fast_body<ExtAcc<typename std::conditional<__is_same(ST, float), uint32_t, uint64_t>::type>, ST, D, SCAN>(p);
 }
 
 }  // namespace xhist
 
-// ---- the selection function of xhist_extrema.hip, called by xhist_plan_execute_extrema (xhist_capi.hip) --------------------
-// What it needs of a plan: the compare domain, the native (start, cnt) tables, the uint16 tables of the linear scan in the
-// float64 and the float32-threshold domain (blob == nullptr: not built), and whether every dimension has arithmetic edges.
-struct ExtremaTables {
-  const xhist::DimTable* dim;
-  const uint64_t* blob;
-  int32_t words;
-  int max_cnt;
-};
-struct ExtremaPlan {
-  int n_dims, cmp;
-  int64_t n_bins;
-  int cus;
-  size_t lds_max;
-  bool arith;
-  ExtremaTables native, fine64, fine32;
-};
 // The three launches on `stream` (prepare, binning, finalize) for DEVICE arrays the caller has validated, n_rows and n_cols
 // > 0, the plan's device current.  Returns XHIST_OK, or an error status with a message in `err`; `desc` receives a line
-// about the launch.
-int xhist_extrema_run(const ExtremaPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+// about the launch.  (Called by xhist_plan_execute_extrema, xhist_capi.hip.)
+int xhist_extrema_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
                       double* out_min, double* out_max, int accumulate, hipStream_t stream, char* err, size_t err_cap, char* desc,
                       size_t desc_cap);
-// the census log of launched kernels (xhist_host_common.hip.h: log_picked_kernel), for the launches of xhist_extrema.hip
-void xhist_log_picked_kernel(const void* fn);

@@ -1,5 +1,5 @@
-// xhist_meanvar.hip.h — per-bin count, mean and sum of squared deviations of a value array (histogram_mean_var): the kernels,
-// and what the C ABI (xhist_capi.hip) hands the selection function of the translation unit xhist_meanvar.hip.
+// xhist_meanvar.hip.h — per-bin count, mean and sum of squared deviations of a value array (histogram_mean_var): the slots
+// and the two passes' policies for the shared kernel skeletons of xhist_values.hip.h, the binning kernels, and the driver.
 //
 // Which samples count is decided exactly as for the histogram: the same digitize, the same tables.  A counted sample whose
 // value (converted to float64, numpy's astype) is not NaN contributes that value.  Two passes over the data, the corrected
@@ -22,7 +22,7 @@
 // generic family adds straight into the global arrays, and pass 2 reads the means through L2.
 #pragma once
 
-#include "xhist_extrema.hip.h"
+#include "xhist_values.hip.h"
 
 namespace xhist {
 
@@ -36,18 +36,17 @@ struct MvDevSlot {
   double mean, sd, s2;
 };
 
-// Params of both passes: samples and values (w_*) as for extrema_generic / extrema_fast; [n_rows, n_bins] arrays pre-advanced
-// to row p.row0 —
+// The statistic of the shared skeletons (xhist_values.hip.h), one policy per pass, with copies of the slots.  [n_rows, n_bins]
+// arrays pre-advanced to row p.row0 —
 //   pass 1: out = the uint64 counts, out2 = the float64 sums;
 //   pass 2: w2_ptr = the float64 means (read only), out = the float64 sums of d, out2 = the float64 sums of d*d.
-// The slots sit behind the staged tables, 16-byte aligned, as in the extrema kernels; bin b's copy c is slot
-// (b << p.copies_log2) + c (the generic family: one copy).
 template <int PASS>
 struct MvAcc;
 
 template <>
 struct MvAcc<1> {
   using slot_t = MvSumSlot;
+  static constexpr bool kCopies = true;
   static __device__ __forceinline__ void init(slot_t* s, const Params& p, int64_t) {
     const uint32_t n = (uint32_t)p.n_bins << p.copies_log2;
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
@@ -55,9 +54,10 @@ struct MvAcc<1> {
       s[i].s = 0.0;
     }
   }
-  static __device__ __forceinline__ void lds_add(slot_t* s, uint32_t i, double v) {
+  template <typename V>  // (values are accumulated in float64 whatever their type)
+  static __device__ __forceinline__ void lds_add(slot_t* s, uint32_t i, V v) {
     atomicAdd(&s[i].n, 1u);
-    unsafeAtomicAdd(&s[i].s, v);
+    unsafeAtomicAdd(&s[i].s, (double)v);
   }
   static __device__ __forceinline__ void global_add(const Params& p, int64_t row, int64_t b, double v) {
     const int64_t i = row * p.n_bins + b;
@@ -87,6 +87,7 @@ struct MvAcc<1> {
 template <>
 struct MvAcc<2> {
   using slot_t = MvDevSlot;
+  static constexpr bool kCopies = true;
   static __device__ __forceinline__ void init(slot_t* s, const Params& p, int64_t row) {
     const double* mean = reinterpret_cast<const double*>(p.w2_ptr) + row * p.n_bins;
     const uint32_t n = (uint32_t)p.n_bins << p.copies_log2;
@@ -96,8 +97,9 @@ struct MvAcc<2> {
       s[i].s2 = 0.0;
     }
   }
-  static __device__ __forceinline__ void lds_add(slot_t* s, uint32_t i, double v) {
-    const double d = v - s[i].mean;
+  template <typename V>
+  static __device__ __forceinline__ void lds_add(slot_t* s, uint32_t i, V v) {
+    const double d = (double)v - s[i].mean;
     unsafeAtomicAdd(&s[i].sd, d);
     unsafeAtomicAdd(&s[i].s2, d * d);
   }
@@ -124,157 +126,31 @@ struct MvAcc<2> {
   }
 };
 
-// ---------------------------------------------------------------------------------------------
-// GENERIC family body: any dtype per input and for the values, any element strides (broadcast and grouped rows), 1..8 inputs,
-// compare domains 0 (float64), 1 (int64) and 3 (per input).  LDS: the slots of every bin in LDS behind the tables (which are
-// then in LDS too).  Else every sample adds into the global arrays, and the tables are read from LDS when they fit there
-// (p.tables_in_lds) and through L2 otherwise.
-// ---------------------------------------------------------------------------------------------
-template <int PASS, int CMP, bool LDS>
-__device__ __forceinline__ void mv_generic_body(const Params& p) {
-  using CT = typename Dom<CMP>::T;
-  using A = MvAcc<PASS>;
-  const int64_t row = blockIdx.x / p.segs;
-  const int seg = blockIdx.x % p.segs;
-  const uint64_t* tab = p.tables_in_lds ? stage_tables(p) : p.tables;
-  typename A::slot_t* slots = reinterpret_cast<typename A::slot_t*>(xhist_smem + ext_slots_offset(p));
-  if (LDS) A::init(slots, p, row);
-  __syncthreads();
-
-  const int nd = p.n_dims;
-  int64_t roff[kMaxDims];
-#pragma unroll
-  for (int d = 0; d < kMaxDims; ++d) roff[d] = d < nd ? row_offset(p.row0 + row, p.s_rs[d], p.s_ir[d], p.s_os[d]) : 0;
-  const int64_t voff = row_offset(p.row0 + row, p.w_rs, p.w_ir, p.w_os);
-
-  const int64_t stride = (int64_t)p.segs * blockDim.x;
-  for (int64_t i = (int64_t)seg * blockDim.x + threadIdx.x; i < p.n_cols; i += stride) {
-    const double v = load_as<double>(p.w_ptr, p.w_dt, voff + i * p.w_cs);
-    bool ok = v == v;  // NaN values are ignored (np.nanmean / np.nanvar)
-    int64_t flat = 0;
-#pragma unroll
-    for (int d = 0; d < kMaxDims; ++d) {
-      if (d < nd) {
-        const CT x = load_dom<CMP>(p.s_ptr[d], p.s_dt[d], roff[d] + i * p.s_cs[d], p.dim[d]);
-        const int b = digitize<CMP>(x, p.dim[d], tab);
-        ok &= (b >= 0);
-        flat += (int64_t)b * p.dim[d].out_stride;
-      }
-    }
-    if (!ok) continue;
-    if (LDS) A::lds_add(slots, (uint32_t)flat, v);  // (one copy of the slots: p.copies_log2 == 0)
-    else A::global_add(p, row, flat, v);
-  }
-  if (LDS) {
-    __syncthreads();
-    A::flush(slots, p, row);
-  }
-}
-
+// The binning kernels of the two passes: mv_sum_generic / mv_dev_generic<CMP, LDS> (block 512) and mv_sum_fast /
+// mv_dev_fast<ST, D, SCAN> (block 256), the families of xhist_values.hip.h.
 template <int CMP, bool LDS>
 __global__ void __launch_bounds__(512) mv_sum_generic(const Params p) {
-  mv_generic_body<1, CMP, LDS>(p);
+  values_generic_body<MvAcc<1>, CMP, LDS>(p);
 }
 template <int CMP, bool LDS>
 __global__ void __launch_bounds__(512) mv_dev_generic(const Params p) {
-  mv_generic_body<2, CMP, LDS>(p);
+  values_generic_body<MvAcc<2>, CMP, LDS>(p);
 }
-
-// ---------------------------------------------------------------------------------------------
-// VECTOR fast path body: float32 or float64 samples with values of the same type, unit column stride, one or two inputs, slots
-// in LDS; digitize by the tables with at most two edges per bucket (SCAN 1 / 2) or by arithmetic (kScanArith).  Tiles as in
-// extrema_fast: VEC elements per 16-byte non-temporal load, UNROLL loads in flight per array and lane; the workgroups of a row
-// walk its tiles interleaved.  Values are accumulated in float64 whatever their type.
-// ---------------------------------------------------------------------------------------------
-template <int PASS, typename ST, int D, int SCAN>
-__device__ __forceinline__ void mv_fast_body(const Params& p) {
-  static_assert(__is_same(ST, double) || __is_same(ST, float), "float32 / float64 samples and values");
-  static_assert(SCAN == 1 || SCAN == 2 || SCAN == kScanArith, "tables with <= 2 edges per bucket, or arithmetic edges");
-  constexpr int CMP = (__is_same(ST, float) && SCAN != kScanArith) ? 2 : 0;
-  constexpr int VEC = 16 / (int)sizeof(ST);
-  constexpr int UNROLL = D == 1 ? 4 : 8 / VEC;
-  using A = MvAcc<PASS>;
-  using svec = typename VecOf<ST, VEC>::type;
-
-  const int tid = threadIdx.x;
-  const int64_t row = blockIdx.x / p.segs;
-  const int seg = blockIdx.x % p.segs;
-  const uint64_t* tab = stage_tables(p);
-  typename A::slot_t* slots = reinterpret_cast<typename A::slot_t*>(xhist_smem + ext_slots_offset(p));
-  A::init(slots, p, row);
-  __syncthreads();
-
-  const ST* sp[D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) sp[d] = reinterpret_cast<const ST*>(p.s_ptr[d]) + row_offset(p.row0 + row, p.s_rs[d], p.s_ir[d], p.s_os[d]);
-  const ST* vp = reinterpret_cast<const ST*>(p.w_ptr) + row_offset(p.row0 + row, p.w_rs, p.w_ir, p.w_os);
-  const uint32_t nb1 = D == 2 ? (uint32_t)p.dim[1].nb : 1u;
-  const uint32_t mycopy = (uint32_t)tid & ((1u << p.copies_log2) - 1u);
-
-  const int64_t tile_elems = (int64_t)blockDim.x * VEC * UNROLL;
-  const int64_t n_tiles = (p.n_cols + tile_elems - 1) / tile_elems;
-  for (int64_t t = seg; t < n_tiles; t += p.segs) {
-    const int64_t base = t * tile_elems;
-    svec xv[D][UNROLL], vv[UNROLL];
-    if (base + tile_elems <= p.n_cols) {
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t i = base + ((int64_t)u * blockDim.x + tid) * VEC;
-#pragma unroll
-        for (int d = 0; d < D; ++d) xv[d][u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(sp[d] + i));
-        vv[u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(vp + i));
-      }
-    } else {  // the ragged last tile: positions past the end become NaN samples, which digitize drops
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t i = base + ((int64_t)u * blockDim.x + tid) * VEC;
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-          const bool in = i + v < p.n_cols;
-#pragma unroll
-          for (int d = 0; d < D; ++d) xv[d][u][v] = in ? sp[d][i + v] : (ST)__builtin_nanf("");
-          vv[u][v] = in ? vp[i + v] : (ST)__builtin_nanf("");
-        }
-      }
-    }
-    uint32_t cnt[D][UNROLL][VEC];
-    count_le_tile<CMP, SCAN, D, UNROLL, VEC>(xv, p, tab, 1, cnt);
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) {
-        const ST val = vv[u][v];
-        bool ok = val == val;
-        uint32_t flat = 0;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-          const int b = bin_from_tile_count<CMP, SCAN>((typename Dom<CMP>::T)xv[d][u][v], p.dim[d], cnt[d][u][v]);
-          ok &= b >= 0;
-          flat = d == 0 ? (uint32_t)b : flat * nb1 + (uint32_t)b;
-        }
-        if (ok) A::lds_add(slots, (flat << p.copies_log2) + mycopy, (double)val);
-      }
-  }
-  __syncthreads();
-  A::flush(slots, p, row);
-}
-
 template <typename ST, int D, int SCAN>
 __global__ void __launch_bounds__(256) mv_sum_fast(const Params p) {
-  mv_fast_body<1, ST, D, SCAN>(p);
+  values_fast_body<MvAcc<1>, ST, D, SCAN>(p);
 }
 template <typename ST, int D, int SCAN>
 __global__ void __launch_bounds__(256) mv_dev_fast(const Params p) {
-  mv_fast_body<2, ST, D, SCAN>(p);
+  values_fast_body<MvAcc<2>, ST, D, SCAN>(p);
 }
 
 }  // namespace xhist
 
-// ---- the selection function of xhist_meanvar.hip, called by xhist_plan_execute_mean_var (xhist_capi.hip) --------------------
-// What it needs of a plan is what the extrema unit needs (ExtremaPlan, xhist_extrema.hip.h).
 // The zeroing and the five launches on `stream` (pass 1, mean, pass 2, finalize) for DEVICE arrays the caller has validated,
 // n_rows * n_bins > 0, the plan's device current.  `sd` is a float64 [n_rows, n_bins] block of the caller's for the sums of d.
-// Returns XHIST_OK, or an error status with a message in `err`; `desc` receives a line about the launches.
-int xhist_meanvar_run(const ExtremaPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+// Returns XHIST_OK, or an error status with a message in `err`; `desc` receives a line about the launches.  (Called by
+// xhist_plan_execute_mean_var, xhist_capi.hip.)
+int xhist_meanvar_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
                       int64_t* out_count, double* out_mean, double* out_m2, double* sd, hipStream_t stream, char* err, size_t err_cap,
                       char* desc, size_t desc_cap);

@@ -1,0 +1,385 @@
+// xhist_values.hip.h — what the per-bin statistics of a value array share: histogram_extrema (xhist_extrema.hip.h) and
+// histogram_mean_var (xhist_meanvar.hip.h).  The one kernel skeleton per family, into which a statistic plugs an
+// accumulator policy, and the one host-side launcher: the family and LDS rule, the launch geometry, the Params of a launch.
+//
+// Which samples count is decided exactly as for the histogram: the same digitize, the same tables.  A counted sample whose
+// value is not NaN hands that value to the policy.  The slots of a workgroup sit in LDS behind the staged tables; the generic
+// family without LDS room hands every value straight to global memory.
+//
+// Nothing here instantiates a kernel: the skeletons are templates, and the kernels are instantiated in the statistic's own
+// translation unit only (xhist_capi.hip includes this header for ValuesPlan and must not gain device code).
+#pragma once
+
+#include "xhist_kernels.hip.h"
+
+#include "../../include/xhist_amd.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+namespace xhist {
+
+// the slots sit behind the staged tables, 16-byte aligned
+__host__ __device__ __forceinline__ size_t ext_slots_offset(const Params& p) { return (size_t)((p.table_words + 1) & ~1) * 8; }
+
+// An accumulator policy `Acc` is one statistic's (one pass's) use of the slots:
+//   slot_t                    one bin's LDS slot
+//   kCopies                   the fast family keeps 2^p.copies_log2 copies of every slot, lane i adding into copy
+//                             i mod 2^copies_log2: bin b's copy c is slot (b << p.copies_log2) + c (the generic family: one)
+//   init(slots, p, row)       the workgroup's slots, before the first sample
+//   lds_add(slots, i, v)      one value into slot i: v in the sample type (fast family) or float64 (generic family)
+//   global_add(p, row, b, v)  one float64 value straight into bin b of the output row (generic family without LDS)
+//   flush(slots, p, row)      the workgroup's slots into its output row
+// Outputs are [n_rows, n_bins] arrays at p.out / p.out2, pre-advanced to row p.row0; the values are p.w_*.
+//
+// The bodies take the kernel's Params as `const Params& __restrict__`.  A body is optimised on its own before it is inlined
+// into its kernel, and without __restrict__ that step must assume the LDS and global atomics may write the Params: the
+// fast arithmetic-edge kernels then held up to 23 more VGPRs, and the generic ones spilled SGPRs to scratch.  With it the
+// body compiles as if written in the kernel, where Params is a private copy nothing else writes.
+
+// ---------------------------------------------------------------------------------------------
+// GENERIC family: any dtype per input and for the values, any element strides (broadcast and grouped rows), 1..8 inputs,
+// compare domains 0 (float64), 1 (int64) and 3 (per input).  LDS: the slots of every bin in LDS behind the tables (which are
+// then in LDS too).  Else every value goes to global memory, and the tables are read from LDS when they fit there
+// (p.tables_in_lds) and through L2 otherwise.
+// ---------------------------------------------------------------------------------------------
+template <class Acc, int CMP, bool LDS>
+__device__ __forceinline__ void values_generic_body(const Params& __restrict__ p) {
+  using CT = typename Dom<CMP>::T;
+  const int64_t row = blockIdx.x / p.segs;
+  const int seg = blockIdx.x % p.segs;
+  const uint64_t* tab = p.tables_in_lds ? stage_tables(p) : p.tables;
+  typename Acc::slot_t* slots = reinterpret_cast<typename Acc::slot_t*>(xhist_smem + ext_slots_offset(p));
+  if (LDS) Acc::init(slots, p, row);
+  __syncthreads();
+
+  const int nd = p.n_dims;
+  int64_t roff[kMaxDims];
+#pragma unroll
+  for (int d = 0; d < kMaxDims; ++d) roff[d] = d < nd ? row_offset(p.row0 + row, p.s_rs[d], p.s_ir[d], p.s_os[d]) : 0;
+  const int64_t voff = row_offset(p.row0 + row, p.w_rs, p.w_ir, p.w_os);
+
+  const int64_t stride = (int64_t)p.segs * blockDim.x;
+  for (int64_t i = (int64_t)seg * blockDim.x + threadIdx.x; i < p.n_cols; i += stride) {
+    const double v = load_as<double>(p.w_ptr, p.w_dt, voff + i * p.w_cs);
+    bool ok = v == v;  // NaN values are ignored (np.fmin / np.fmax, np.nanmean / np.nanvar)
+    int64_t flat = 0;
+#pragma unroll
+    for (int d = 0; d < kMaxDims; ++d) {
+      if (d < nd) {
+        const CT x = load_dom<CMP>(p.s_ptr[d], p.s_dt[d], roff[d] + i * p.s_cs[d], p.dim[d]);
+        const int b = digitize<CMP>(x, p.dim[d], tab);
+        ok &= (b >= 0);
+        flat += (int64_t)b * p.dim[d].out_stride;
+      }
+    }
+    if (!ok) continue;
+    if (LDS) Acc::lds_add(slots, (uint32_t)flat, v);  // (one copy of the slots: p.copies_log2 == 0)
+    else Acc::global_add(p, row, flat, v);
+  }
+  if (LDS) {
+    __syncthreads();
+    Acc::flush(slots, p, row);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// VECTOR fast path: float32 or float64 samples with values of the same type, unit column stride, one or two inputs, slots
+// in LDS; digitize by the tables with at most two edges per bucket (SCAN 1 / 2: float64 edges for float64 samples, float32
+// thresholds for float32 ones) or by arithmetic (kScanArith).  Tiles as in hist_fast: VEC elements per 16-byte
+// non-temporal load, UNROLL loads in flight per array and lane; the workgroups of a row walk its tiles interleaved.
+// ---------------------------------------------------------------------------------------------
+template <class Acc, typename ST, int D, int SCAN>
+__device__ __forceinline__ void values_fast_body(const Params& __restrict__ p) {
+  static_assert(__is_same(ST, double) || __is_same(ST, float), "float32 / float64 samples and values");
+  static_assert(SCAN == 1 || SCAN == 2 || SCAN == kScanArith, "tables with <= 2 edges per bucket, or arithmetic edges");
+  constexpr int CMP = (__is_same(ST, float) && SCAN != kScanArith) ? 2 : 0;
+  constexpr int VEC = 16 / (int)sizeof(ST);
+  constexpr int UNROLL = D == 1 ? 4 : 8 / VEC;  // 128 bytes of samples and values per lane in flight (192 for two inputs)
+  using svec = typename VecOf<ST, VEC>::type;
+
+  const int tid = threadIdx.x;
+  const int64_t row = blockIdx.x / p.segs;
+  const int seg = blockIdx.x % p.segs;
+  const uint64_t* tab = stage_tables(p);
+  typename Acc::slot_t* slots = reinterpret_cast<typename Acc::slot_t*>(xhist_smem + ext_slots_offset(p));
+  Acc::init(slots, p, row);
+  __syncthreads();
+
+  const ST* sp[D];
+#pragma unroll
+  for (int d = 0; d < D; ++d) sp[d] = reinterpret_cast<const ST*>(p.s_ptr[d]) + row_offset(p.row0 + row, p.s_rs[d], p.s_ir[d], p.s_os[d]);
+  const ST* vp = reinterpret_cast<const ST*>(p.w_ptr) + row_offset(p.row0 + row, p.w_rs, p.w_ir, p.w_os);
+  const uint32_t nb1 = D == 2 ? (uint32_t)p.dim[1].nb : 1u;
+  const uint32_t mycopy = Acc::kCopies ? (uint32_t)tid & ((1u << p.copies_log2) - 1u) : 0u;
+
+  const int64_t tile_elems = (int64_t)blockDim.x * VEC * UNROLL;
+  const int64_t n_tiles = (p.n_cols + tile_elems - 1) / tile_elems;
+  for (int64_t t = seg; t < n_tiles; t += p.segs) {
+    const int64_t base = t * tile_elems;
+    svec xv[D][UNROLL], vv[UNROLL];
+    if (base + tile_elems <= p.n_cols) {
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const int64_t i = base + ((int64_t)u * blockDim.x + tid) * VEC;
+#pragma unroll
+        for (int d = 0; d < D; ++d) xv[d][u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(sp[d] + i));
+        vv[u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(vp + i));
+      }
+    } else {  // the ragged last tile: positions past the end become NaN samples, which digitize drops
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const int64_t i = base + ((int64_t)u * blockDim.x + tid) * VEC;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          const bool in = i + v < p.n_cols;
+#pragma unroll
+          for (int d = 0; d < D; ++d) xv[d][u][v] = in ? sp[d][i + v] : (ST)__builtin_nanf("");
+          vv[u][v] = in ? vp[i + v] : (ST)__builtin_nanf("");
+        }
+      }
+    }
+    uint32_t cnt[D][UNROLL][VEC];
+    count_le_tile<CMP, SCAN, D, UNROLL, VEC>(xv, p, tab, 1, cnt);
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        const ST val = vv[u][v];
+        bool ok = val == val;
+        uint32_t flat = 0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+          const int b = bin_from_tile_count<CMP, SCAN>((typename Dom<CMP>::T)xv[d][u][v], p.dim[d], cnt[d][u][v]);
+          ok &= b >= 0;
+          flat = d == 0 ? (uint32_t)b : flat * nb1 + (uint32_t)b;
+        }
+        if (ok) Acc::lds_add(slots, Acc::kCopies ? (flat << p.copies_log2) + mycopy : flat, val);
+      }
+  }
+  __syncthreads();
+  Acc::flush(slots, p, row);
+}
+
+}  // namespace xhist
+
+// ---- host side -------------------------------------------------------------------------------------------------------------
+// What the units need of a plan (filled by xhist_capi.hip's values_plan()): the compare domain, the native (start, cnt)
+// tables, the uint16 tables of the linear scan in the float64 and the float32-threshold domain (blob == nullptr: not built),
+// and whether every dimension has arithmetic edges.
+struct ValuesTables {
+  const xhist::DimTable* dim;
+  const uint64_t* blob;
+  int32_t words;
+  int max_cnt;
+};
+struct ValuesPlan {
+  int n_dims, cmp;
+  int64_t n_bins;
+  int cus;
+  size_t lds_max;
+  bool arith;
+  ValuesTables native, fine64, fine32;
+};
+// the census log of launched kernels (xhist_host_common.hip.h: log_picked_kernel), for the launches of the statistics' units
+void xhist_log_picked_kernel(const void* fn);
+
+namespace xhist {
+
+typedef void (*values_fn)(const Params);
+
+// every kernel of a statistic goes through the census log of the dispatch surface (XH_LAUNCH_PICKED of
+// xhist_host_common.hip.h, whose logger lives in xhist_capi.hip)
+#define XH_VALUES_LAUNCH(fn, ...)                               \
+  do {                                                          \
+    xhist_log_picked_kernel(reinterpret_cast<const void*>(fn)); \
+    hipLaunchKernelGGL(fn, __VA_ARGS__);                        \
+  } while (0)
+
+static inline int values_error(char* err, size_t cap, int code, const char* what, hipError_t e) {
+  snprintf(err, cap, "%s: %s", what, hipGetErrorString(e));
+  return code;
+}
+
+#define XH_VALUES_LAUNCH_CHECK(what)                                                \
+  do {                                                                              \
+    hipError_t e_ = hipGetLastError();                                              \
+    if (e_ != hipSuccess) return values_error(err, err_cap, XHIST_ERR_HIP, what, e_); \
+  } while (0)
+
+static inline int elem_bytes(int dt) {
+  return (dt == XHIST_F64 || dt == XHIST_I64 || dt == XHIST_U64) ? 8 : (dt == XHIST_F32 || dt == XHIST_I32 || dt == XHIST_U32) ? 4
+       : (dt == XHIST_F16 || dt == XHIST_I16 || dt == XHIST_U16) ? 2 : 1;
+}
+
+// A statistic's LDS slots, for the family rule: the bytes of a bin's slot in each of its passes (0: no second pass), the
+// same for the fast family on float32 values, and whether the fast family keeps copies of its slots.
+struct ValuesSlots {
+  size_t bytes[2], fast32[2];
+  bool copies;
+};
+
+// What the binning launches run and where their slots live.
+struct ValuesChoice {
+  bool fast = false, lds = false, tables_in_lds = false, f32 = false;
+  int scan = 0, copies_log2 = 0;
+  const ValuesTables* tab = nullptr;
+  int32_t table_words = 0;
+  size_t lds_bytes[2] = {0, 0};  // per pass
+};
+
+// Copies of the fast family's slots: the most (up to 16) whose largest slots stay within 24 KiB, so that a CU still holds
+// several workgroups.  mean_var: C2's 100 bins get 8, C4's 50 get 16; above 1024 bins there is one.
+static inline int fast_copies_log2(int64_t n_bins, size_t slot, size_t tbytes, size_t lds_max) {
+  int cl = 0;
+  while (cl < 4 && ((size_t)n_bins * slot << (cl + 1)) <= 24 * 1024 && tbytes + ((size_t)n_bins * slot << (cl + 1)) <= lds_max) ++cl;
+  return cl;
+}
+
+// fast if eligible, else generic with its slots in LDS, else generic straight into global memory.  The largest slot of the
+// passes decides; every pass takes the family, the home and the copies chosen for it.
+static inline ValuesChoice choose_values(const ValuesPlan& pl, const ValuesSlots& sl, const xhist_array* samples,
+                                         const xhist_array* values, int64_t n_cols) {
+  ValuesChoice c;
+  const int D = pl.n_dims;
+  const int sdt = samples[0].dtype;
+  c.f32 = sdt == XHIST_F32;
+  bool fast_ok = pl.cmp == XHIST_CMP_F64 && D <= 2 && (sdt == XHIST_F64 || sdt == XHIST_F32) && values->dtype == sdt &&
+                 pl.n_bins < ((int64_t)1 << 24);
+  for (int d = 0; d < D && fast_ok; ++d)
+    fast_ok = samples[d].dtype == sdt && (samples[d].col_stride == 1 || n_cols == 1) && (uintptr_t)samples[d].data % (size_t)elem_bytes(sdt) == 0;
+  if (fast_ok) fast_ok = (values->col_stride == 1 || n_cols == 1) && (uintptr_t)values->data % (size_t)elem_bytes(sdt) == 0;
+  if (fast_ok) {
+    const size_t* bytes = c.f32 ? sl.fast32 : sl.bytes;
+    const size_t slot = std::max(bytes[0], bytes[1]);
+    const size_t slots = (size_t)pl.n_bins * slot;
+    const ValuesTables& fine = c.f32 ? pl.fine32 : pl.fine64;
+    const size_t fine_tbytes = ((size_t)fine.words + 1) / 2 * 16;
+    size_t tbytes = 0;
+    if (fine.blob && fine.max_cnt >= 1 && fine.max_cnt <= 2 && fine_tbytes + slots <= pl.lds_max) {
+      c.scan = fine.max_cnt;
+      c.tab = &fine;
+      c.table_words = fine.words;
+      tbytes = fine_tbytes;
+    } else if (pl.arith && slots <= pl.lds_max) {
+      c.scan = kScanArith;
+      c.tab = &pl.native;  // (the float64-domain DimTable carries e_0, e_last and the step; no table is read)
+      c.table_words = 0;
+    }
+    if (c.tab) {
+      c.copies_log2 = sl.copies ? fast_copies_log2(pl.n_bins, slot, tbytes, pl.lds_max) : 0;
+      for (int k = 0; k < 2; ++k) c.lds_bytes[k] = bytes[k] ? tbytes + ((size_t)pl.n_bins * bytes[k] << c.copies_log2) : 0;
+      c.fast = c.lds = c.tables_in_lds = true;
+      return c;
+    }
+  }
+  c.tab = &pl.native;
+  const size_t tbytes = ((size_t)pl.native.words + 1) / 2 * 16;
+  c.tables_in_lds = tbytes + 1024 <= pl.lds_max;
+  c.table_words = c.tables_in_lds ? pl.native.words : 0;
+  c.lds = c.tables_in_lds && pl.n_bins < ((int64_t)1 << 24) &&
+          tbytes + (size_t)pl.n_bins * std::max(sl.bytes[0], sl.bytes[1]) <= pl.lds_max;
+  for (int k = 0; k < 2; ++k)
+    c.lds_bytes[k] = c.tables_in_lds && sl.bytes[k] ? tbytes + (c.lds ? (size_t)pl.n_bins * sl.bytes[k] : 0) : 0;
+  return c;
+}
+
+// The kernel a choice runs, from a statistic's kernel set K: K::fast<ST, D, SCAN>() and K::generic<CMP, LDS>() name its
+// instantiations.  nullptr: none for this combination.
+template <class K, typename ST, int D>
+static values_fn fast_scan(int scan) {
+  if (scan == 1) return K::template fast<ST, D, 1>();
+  if (scan == 2) return K::template fast<ST, D, 2>();
+  if (scan == kScanArith) return K::template fast<ST, D, kScanArith>();
+  return nullptr;
+}
+template <class K>
+static values_fn pick_values_kernel(const ValuesChoice& c, const ValuesPlan& pl) {
+  if (c.fast) {
+    if (c.f32) return pl.n_dims == 1 ? fast_scan<K, float, 1>(c.scan) : fast_scan<K, float, 2>(c.scan);
+    return pl.n_dims == 1 ? fast_scan<K, double, 1>(c.scan) : fast_scan<K, double, 2>(c.scan);
+  }
+  // (the domain as the histogram's generic family reads it: exactly float64, exactly int64, else per input)
+  if (pl.cmp == XHIST_CMP_F64) return c.lds ? K::template generic<0, true>() : K::template generic<0, false>();
+  if (pl.cmp == XHIST_CMP_I64) return c.lds ? K::template generic<1, true>() : K::template generic<1, false>();
+  return c.lds ? K::template generic<3, true>() : K::template generic<3, false>();
+}
+
+// Launch geometry, the same for every pass: every resident workgroup at once, the workgroups of a row walking its tiles
+// interleaved; the largest pass's LDS footprint sets the residency.
+struct ValuesGeometry {
+  int block = 0;
+  int64_t segs = 0, max_rows = 0;
+};
+static inline ValuesGeometry values_geometry(const ValuesPlan& pl, const ValuesChoice& c, int64_t n_rows, int64_t n_cols) {
+  ValuesGeometry g;
+  g.block = c.fast ? 256 : 512;
+  const int vec = c.f32 ? 4 : 2;
+  const int64_t per_tile = c.fast ? (int64_t)g.block * (pl.n_dims == 1 ? 4 * vec : 8) : g.block;  // (fast body: VEC x UNROLL per lane)
+  const size_t lds = std::max(c.lds_bytes[0], c.lds_bytes[1]);
+  int bpc = 2048 / g.block;
+  if (lds) bpc = (int)std::max<size_t>(1, std::min<size_t>((size_t)bpc, 160 * 1024 / lds));
+  const int64_t target = (int64_t)pl.cus * bpc;
+  const int64_t tiles = (n_cols + per_tile - 1) / per_tile;
+  g.segs = std::max<int64_t>(1, std::min<int64_t>(tiles, (target + n_rows - 1) / n_rows));
+  // A workgroup sees fewer than 2^31 samples, so uint32 counts in its slots cannot wrap.  Only mean_var counts; for extrema the
+  // guard changes only the grid (and describe()'s segs), never the result.  It moves segs for rows longer than 2^31 samples
+  // once the rows alone fill the device (n_rows >= cus * bpc, segs 1), e.g. rows broadcast at row stride 0.
+  g.segs = std::max<int64_t>(g.segs, (tiles * per_tile + ((int64_t)1 << 31) - 1) >> 31);
+  g.max_rows = (((int64_t)1 << 31) - 1) / g.segs;
+  return g;
+}
+
+// A kernel's dynamic LDS beyond 48 KiB must be allowed before its first launch; drivers do it for every pass up front.
+static int allow_values_lds(values_fn fn, size_t lds, const char* what, char* err, size_t err_cap) {
+  if (lds <= 48 * 1024) return XHIST_OK;
+  const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  return e == hipSuccess ? XHIST_OK : values_error(err, err_cap, XHIST_ERR_HIP, what, e);
+}
+
+// One binning pass: the launches of row chunks of at most g.max_rows (the grid stays below 2^31 workgroups).  out / out2 / in2 are [n_rows, n_bins] arrays of 8-byte elements,
+// advanced to each chunk's first row (Params::out, out2 and w2_ptr); `what` names the pass in error messages.
+static int launch_values_pass(values_fn fn, size_t lds, const char* what, const ValuesPlan& pl,
+                              const ValuesChoice& c, const ValuesGeometry& g, const xhist_array* samples, const xhist_array* values,
+                              int64_t n_rows, int64_t n_cols, void* out, void* out2, const void* in2, hipStream_t stream, char* err,
+                              size_t err_cap) {
+  for (int64_t r0 = 0; r0 < n_rows; r0 += g.max_rows) {
+    const int64_t nr = std::min(g.max_rows, n_rows - r0);
+    Params kp;
+    memset(&kp, 0, sizeof kp);
+    for (int d = 0; d < pl.n_dims; ++d) {
+      kp.s_ptr[d] = samples[d].data;
+      kp.s_rs[d] = samples[d].row_stride;
+      kp.s_cs[d] = samples[d].col_stride;
+      kp.s_ir[d] = samples[d].inner_rows;
+      kp.s_os[d] = samples[d].outer_stride;
+      kp.s_dt[d] = samples[d].dtype;
+      kp.dim[d] = c.tab->dim[d];
+    }
+    kp.w_ptr = values->data;
+    kp.w_rs = values->row_stride;
+    kp.w_cs = values->col_stride;
+    kp.w_ir = values->inner_rows;
+    kp.w_os = values->outer_stride;
+    kp.w_dt = values->dtype;
+    kp.w2_ptr = in2 ? static_cast<const uint64_t*>(in2) + r0 * pl.n_bins : nullptr;
+    kp.row0 = r0;
+    kp.n_dims = pl.n_dims;
+    kp.tables = c.tab->blob;
+    kp.table_words = c.table_words;
+    kp.tables_in_lds = c.tables_in_lds ? 1 : 0;
+    kp.n_rows = nr;
+    kp.n_cols = n_cols;
+    kp.n_bins = pl.n_bins;
+    kp.out = static_cast<uint64_t*>(out) + r0 * pl.n_bins;
+    kp.out2 = static_cast<uint64_t*>(out2) + r0 * pl.n_bins;
+    kp.segs = (int32_t)g.segs;
+    kp.copies_log2 = c.copies_log2;
+    XH_VALUES_LAUNCH(fn, dim3((unsigned)(nr * g.segs)), dim3(g.block), lds, stream, kp);
+    XH_VALUES_LAUNCH_CHECK(what);
+  }
+  return XHIST_OK;
+}
+
+}  // namespace xhist
