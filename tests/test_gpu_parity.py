@@ -1795,6 +1795,21 @@ def test_lanes_many_short_rows(xh, shape):
     np.testing.assert_array_equal(xh.histogram(x, bins=edges, axis=1)[0], onp.histogram(x, bins=edges, axis=1)[0])
 
 
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("groups", [50, 64])  # 4000 | 5120 rows: either side of the 4096 rows of the scratch-transpose route
+def test_lanes_grouped_rows_too_many_bins_for_rows1(xh, dtype, groups):
+    """grouped rows (kept axes on both sides of the reduced one: (groups, 100, 80)[:, :80, :] over its last axis is `groups` x 80
+    rows of 80 columns, row stride 80, group stride 8000) with 300 bins, too many for the fused turn-around kernel's LDS:
+    transpose_2d takes plain row strides only, so the call must not reach hist_lanes on transposed scratch"""
+    gen = torch.Generator(device="cuda").manual_seed(54)
+    x = torch.randn(groups, 100, 80, dtype=dtype, device="cuda", generator=gen)[:, :80, :]
+    edges = np.linspace(-4, 4, 301)
+    got, _ = xh.histogram(x, bins=edges, axis=2)
+    desc = _describe_last(xh, [x], [edges])
+    np.testing.assert_array_equal(got.cpu().numpy(), onp.histogram(x.cpu().numpy(), bins=edges, axis=2)[0], err_msg=desc)
+    assert "transpose=1" not in desc, desc
+
+
 def test_lanes_2d_joint_nonuniform_and_binary_search_tables(xh):
     rng = np.random.default_rng(53)
     a = rng.standard_normal((6000, 33)).astype(np.float32)

@@ -55,118 +55,39 @@ static const xhist_array& array_at(const xhist_array* samples, const xhist_array
   return d < D ? samples[d] : *weights;
 }
 
-// The Params fields both forms of the partitioned mode share: rows of unit column stride, the tables, the histogram and its
-// partitions.  Each caller adds its own: segs, n_rows, and the record streams or parts_per_row.
-static Params partitioned_params(const xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_cols,
-                                 void* out, const TableSet& tset, int32_t table_words, int shift, int n_parts) {
+// A Params with the arrays of a call (samples[0 .. D), then the weights when there are any) as they are, their tables and
+// shape, and the histogram; every other field zero.  Each launch adds its own.
+static Params fill_params(const xhist_array* samples, const xhist_array* weights, int D, const TableSet& tset, int32_t table_words,
+                          int64_t n_rows, int64_t n_cols, int64_t n_bins, void* out) {
   Params kp;
   memset(&kp, 0, sizeof kp);
-  for (int d = 0; d < p->n_dims; ++d) {
-    kp.s_ptr[d] = samples[d].data;
-    kp.s_rs[d] = samples[d].row_stride;
-    kp.s_cs[d] = 1;
-    kp.s_dt[d] = samples[d].dtype;
+  for (int d = 0; d < D; ++d) {
+    const xhist_array& a = samples[d];
+    kp.s_ptr[d] = a.data;
+    kp.s_rs[d] = a.row_stride;
+    kp.s_cs[d] = a.col_stride;
+    kp.s_ir[d] = a.inner_rows;
+    kp.s_os[d] = a.outer_stride;
+    kp.s_dt[d] = a.dtype;
     kp.dim[d] = tset.dim[d];
   }
   if (weights) {
     kp.w_ptr = weights->data;
     kp.w_rs = weights->row_stride;
-    kp.w_cs = 1;
+    kp.w_cs = weights->col_stride;
+    kp.w_ir = weights->inner_rows;
+    kp.w_os = weights->outer_stride;
     kp.w_dt = weights->dtype;
   }
-  kp.n_dims = p->n_dims;
+  kp.n_dims = D;
   kp.tables = tset.blob;
   kp.table_words = table_words;
   kp.tables_in_lds = 1;
+  kp.n_rows = n_rows;
   kp.n_cols = n_cols;
-  kp.n_bins = p->n_bins;
+  kp.n_bins = n_bins;
   kp.out = out;
-  kp.part_shift = shift;
-  kp.n_parts = n_parts;
   return kp;
-}
-
-// Partitioned mode (xhist_partition.hip.h): count -> prefix -> scatter -> accumulate, all on
-// `stream`, scratch from the stream-ordered allocator (so concurrent callers never share it).
-static int execute_partitioned(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_cols, void* out,
-                               hipStream_t stream, int sdt, int wdt, int scan, bool use_f32, const TableSet& tset, int shift,
-                               int n_parts, const PlanKnobs& kn, LaunchRecord& rec, bool first, bool last) {
-  const int D = p->n_dims;
-  const bool weighted = weights != nullptr;
-  if (n_cols >= ((int64_t)1 << 40)) return XHIST_ERR_UNSUPPORTED;
-  int vec = 1;
-  kernel_fn_count k_count = (kernel_fn_count)fast_kernel(sdt, wdt, D, scan, kHistPartCount, &vec);
-  if (!k_count) return XHIST_ERR_UNSUPPORTED;
-  // records leave part_scatter in aligned groups: 8 (one 16-byte code store) while the carried
-  // records of all partitions fit LDS next to the tile, else 4
-  const int grp = n_parts <= 128 ? 8 : 4;
-  kernel_fn_scatter k_scatter;
-  if (grp == 8)
-    k_scatter = wdt < 0 ? (kernel_fn_scatter)part_scatter<NoWeight, 8>
-                        : (wdt == XHIST_F64 ? (kernel_fn_scatter)part_scatter<double, 8> : (kernel_fn_scatter)part_scatter<float, 8>);
-  else
-    k_scatter = wdt < 0 ? (kernel_fn_scatter)part_scatter<NoWeight, 4>
-                        : (wdt == XHIST_F64 ? (kernel_fn_scatter)part_scatter<double, 4> : (kernel_fn_scatter)part_scatter<float, 4>);
-  const int32_t table_words = scan == kScanArith ? 0 : tset.words;  // arithmetic edges: no tables
-  const size_t table_bytes = (size_t)table_words * 8;
-  const size_t lds_count = table_bytes + (size_t)(n_parts + 1) * 32 * 4;
-  const size_t lds_scatter = part_scatter_lds(n_parts, grp, weighted);
-  const size_t lds_acc = (size_t)((1u << shift) + 1) * (weighted ? 8 : 4);  // + the trash slot of padding records
-  if (lds_count > p->lds_max || lds_scatter > p->lds_max || lds_acc > p->lds_max) return XHIST_ERR_UNSUPPORTED;
-  const int per_cu = std::max<int>(1, std::min<int>(4, (int)(160 * 1024 / std::max(lds_count, lds_scatter))));
-  const int64_t n_tiles = (n_cols + kPartTile - 1) / kPartTile;
-  const int G = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)p->cus * per_cu, n_tiles));
-  const int Gb = (int)std::max<int64_t>(1, std::min<int64_t>(p->cus, (n_cols + 65535) / 65536));
-
-  ScratchScope scratch(stream);
-  uint32_t* d_counts = nullptr;
-  uint64_t *d_base = nullptr, *d_offsets = nullptr;
-  uint16_t* d_codes = nullptr;
-  void* d_w = nullptr;  // record weights: float64, or float32 when the caller's weights are
-  uint32_t* d_flat = nullptr;
-  HIPC(scratch.alloc((void**)&d_counts, (size_t)G * n_parts * 4));
-  HIPC(scratch.alloc((void**)&d_base, (size_t)G * n_parts * 8));
-  HIPC(scratch.alloc((void**)&d_offsets, (size_t)(n_parts + 1) * 8));
-  HIPC(scratch.alloc((void**)&d_flat, (size_t)n_tiles * kPartTile * 4));
-  const size_t n_rec = (size_t)n_cols + (size_t)G * n_parts * grp;  // every slice rounded up to whole groups
-  HIPC(scratch.alloc((void**)&d_codes, n_rec * 2 + 16));
-  const bool rec_f32 = wdt == XHIST_F32;
-  if (weighted) HIPC(scratch.alloc(&d_w, n_rec * (rec_f32 ? 4 : 8) + 16));
-
-  Params kp = partitioned_params(p, samples, weights, n_cols, out, tset, table_words, shift, n_parts);
-  kp.n_rows = 1;
-  kp.segs = G;
-  kp.part_counts = d_counts;
-  kp.part_base = d_base;
-  kp.part_codes = d_codes;
-  kp.part_w = static_cast<double*>(d_w);
-
-  HIPC(set_dynamic_lds((const void*)k_count, lds_count));
-  HIPC(set_dynamic_lds((const void*)k_scatter, lds_scatter));
-  kernel_fn_acc k_acc = weighted ? (rec_f32 ? (kernel_fn_acc)part_accumulate<true, float> : (kernel_fn_acc)part_accumulate<true, double>)
-                                 : (kernel_fn_acc)part_accumulate<false, double>;
-  HIPC(set_dynamic_lds((const void*)k_acc, lds_acc));
-
-  if (first)  // one timing record per execute: opened before the first row's kernels, closed after the last row's
-    if (int rrc = rec.begin(kn.profile)) return rrc;
-  XH_LAUNCH_PICKED(k_count, dim3(G), dim3(kPartBlock), lds_count, stream, kp, d_flat);
-  HIPC(hipGetLastError());
-  hipLaunchKernelGGL(part_prefix, dim3(1), dim3(1024), 0, stream, (const uint32_t*)d_counts, G, n_parts, grp, d_offsets, d_base);
-  HIPC(hipGetLastError());
-  XH_LAUNCH_PICKED(k_scatter, dim3(G), dim3(kPartBlock), lds_scatter, stream, (const uint32_t*)d_flat,
-                     weighted ? weights->data : nullptr, n_cols, (const uint64_t*)d_base, d_codes, d_w, shift, n_parts);
-  HIPC(hipGetLastError());
-  XH_LAUNCH_PICKED(k_acc, dim3(Gb), dim3(1024), lds_acc, stream, (const uint16_t*)d_codes, (const void*)d_w,
-                     (const uint64_t*)d_offsets, out, p->n_bins, shift, n_parts);
-  HIPC(hipGetLastError());
-  if (!last) return XHIST_OK;
-  char desc[384];
-  snprintf(desc, sizeof desc,
-           "family=fast hist=partitioned parts=%d bins_per_part=%d group=%d vec=%d tile=%d block=%d grid=%d acc_grid=%d "
-           "lds_count=%zu lds_scatter=%zu lds_acc=%zu scan=%d weighted=%d D=%d cmp=%s",
-           n_parts, 1 << shift, grp, vec, kPartTile, kPartBlock, G, Gb, lds_count, lds_scatter, lds_acc, scan, (int)weighted, D,
-           use_f32 ? "f32thr" : "f64");
-  return rec.end(desc);
 }
 
 // The exchange mode's kernel wants every compute unit for itself (256 persistent workgroups that wait for one another): two
@@ -234,6 +155,120 @@ static RouteGeom route_geom_for(const PlanKnobs& kn, int sdt, int wdt /* -1: cou
   const bool long_ok = route_long_tile_ok(sdt == XHIST_F64 ? 8 : 4, wdt == XHIST_F64 ? 8 : wdt == XHIST_F32 ? 4 : 0, D, scan == kScanArith);
   g.spl = kn.route_spl == 4 ? 4 : (long_ok ? 8 : 4);
   return g;
+}
+
+// The digitize and geometry of the partitioned mode's one routing pass (route_digitize).
+struct RouteDigitize {
+  int scan;
+  const TableSet* tset;
+  bool f32;
+  RouteGeom geom;
+};
+
+// What execute_partitioned_rows hands, unchanged, to every execute_partitioned and execute_partitioned_fused call of an execute.
+struct PartCall {
+  int sdt, wdt;  // wdt: -1 without weights
+  int64_t n_cols;
+  int shift, parts_per_row;
+  int scan;  // count + prefix + scatter: the streaming choice's digitize
+  bool use_f32;
+  const TableSet* tset;
+  RouteDigitize route;  // the one routing pass: its own digitize
+  LaunchRecord* rec;    // one timing record per execute: opened before the first row's kernels, closed after the last row's
+};
+
+// The Params fields both forms of the partitioned mode share: the row views (unit column stride: the vector family, see
+// execute_partitioned_rows; one row or rows at one stride, no groups: row_views), the tables, the histogram and its
+// partitions.  Each caller adds its own: segs, and the record streams or parts_per_row.
+static Params partitioned_params(const xhist_plan* p, const PartCall& pc, const xhist_array* samples, const xhist_array* weights,
+                                 void* out, const TableSet& tset, int32_t table_words, int64_t rows, int n_parts) {
+  Params kp = fill_params(samples, weights, p->n_dims, tset, table_words, rows, pc.n_cols, p->n_bins, out);
+  kp.part_shift = pc.shift;
+  kp.n_parts = n_parts;
+  return kp;
+}
+
+// Partitioned mode (xhist_partition.hip.h): count -> prefix -> scatter -> accumulate, all on
+// `stream`, scratch from the stream-ordered allocator (so concurrent callers never share it).
+static int execute_partitioned(xhist_plan* p, const PlanKnobs& kn, const PartCall& pc, const xhist_array* samples,
+                               const xhist_array* weights, void* out, hipStream_t stream, bool first, bool last) {
+  const int D = p->n_dims;
+  const bool weighted = weights != nullptr;
+  const int64_t n_cols = pc.n_cols;
+  const int sdt = pc.sdt, wdt = pc.wdt, scan = pc.scan, shift = pc.shift, n_parts = pc.parts_per_row;
+  if (n_cols >= ((int64_t)1 << 40)) return XHIST_ERR_UNSUPPORTED;
+  int vec = 1;
+  kernel_fn_count k_count = (kernel_fn_count)fast_kernel(sdt, wdt, D, scan, kHistPartCount, &vec);
+  if (!k_count) return XHIST_ERR_UNSUPPORTED;
+  // records leave part_scatter in aligned groups: 8 (one 16-byte code store) while the carried
+  // records of all partitions fit LDS next to the tile, else 4
+  const int grp = n_parts <= 128 ? 8 : 4;
+  kernel_fn_scatter k_scatter;
+  if (grp == 8)
+    k_scatter = wdt < 0 ? (kernel_fn_scatter)part_scatter<NoWeight, 8>
+                        : (wdt == XHIST_F64 ? (kernel_fn_scatter)part_scatter<double, 8> : (kernel_fn_scatter)part_scatter<float, 8>);
+  else
+    k_scatter = wdt < 0 ? (kernel_fn_scatter)part_scatter<NoWeight, 4>
+                        : (wdt == XHIST_F64 ? (kernel_fn_scatter)part_scatter<double, 4> : (kernel_fn_scatter)part_scatter<float, 4>);
+  const int32_t table_words = scan == kScanArith ? 0 : pc.tset->words;  // arithmetic edges: no tables
+  const size_t table_bytes = (size_t)table_words * 8;
+  const size_t lds_count = table_bytes + (size_t)(n_parts + 1) * 32 * 4;
+  const size_t lds_scatter = part_scatter_lds(n_parts, grp, weighted);
+  const size_t lds_acc = (size_t)((1u << shift) + 1) * (weighted ? 8 : 4);  // + the trash slot of padding records
+  if (lds_count > p->lds_max || lds_scatter > p->lds_max || lds_acc > p->lds_max) return XHIST_ERR_UNSUPPORTED;
+  const int per_cu = std::max<int>(1, std::min<int>(4, (int)(160 * 1024 / std::max(lds_count, lds_scatter))));
+  const int64_t n_tiles = (n_cols + kPartTile - 1) / kPartTile;
+  const int G = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)p->cus * per_cu, n_tiles));
+  const int Gb = (int)std::max<int64_t>(1, std::min<int64_t>(p->cus, (n_cols + 65535) / 65536));
+
+  ScratchScope scratch(stream);
+  uint32_t* d_counts = nullptr;
+  uint64_t *d_base = nullptr, *d_offsets = nullptr;
+  uint16_t* d_codes = nullptr;
+  void* d_w = nullptr;  // record weights: float64, or float32 when the caller's weights are
+  uint32_t* d_flat = nullptr;
+  HIPC(scratch.alloc((void**)&d_counts, (size_t)G * n_parts * 4));
+  HIPC(scratch.alloc((void**)&d_base, (size_t)G * n_parts * 8));
+  HIPC(scratch.alloc((void**)&d_offsets, (size_t)(n_parts + 1) * 8));
+  HIPC(scratch.alloc((void**)&d_flat, (size_t)n_tiles * kPartTile * 4));
+  const size_t n_rec = (size_t)n_cols + (size_t)G * n_parts * grp;  // every slice rounded up to whole groups
+  HIPC(scratch.alloc((void**)&d_codes, n_rec * 2 + 16));
+  const bool rec_f32 = wdt == XHIST_F32;
+  if (weighted) HIPC(scratch.alloc(&d_w, n_rec * (rec_f32 ? 4 : 8) + 16));
+
+  Params kp = partitioned_params(p, pc, samples, weights, out, *pc.tset, table_words, 1, n_parts);
+  kp.segs = G;
+  kp.part_counts = d_counts;
+  kp.part_base = d_base;
+  kp.part_codes = d_codes;
+  kp.part_w = static_cast<double*>(d_w);
+
+  HIPC(set_dynamic_lds((const void*)k_count, lds_count));
+  HIPC(set_dynamic_lds((const void*)k_scatter, lds_scatter));
+  kernel_fn_acc k_acc = weighted ? (rec_f32 ? (kernel_fn_acc)part_accumulate<true, float> : (kernel_fn_acc)part_accumulate<true, double>)
+                                 : (kernel_fn_acc)part_accumulate<false, double>;
+  HIPC(set_dynamic_lds((const void*)k_acc, lds_acc));
+
+  if (first)
+    if (int rrc = pc.rec->begin(kn.profile)) return rrc;
+  XH_LAUNCH_PICKED(k_count, dim3(G), dim3(kPartBlock), lds_count, stream, kp, d_flat);
+  HIPC(hipGetLastError());
+  hipLaunchKernelGGL(part_prefix, dim3(1), dim3(1024), 0, stream, (const uint32_t*)d_counts, G, n_parts, grp, d_offsets, d_base);
+  HIPC(hipGetLastError());
+  XH_LAUNCH_PICKED(k_scatter, dim3(G), dim3(kPartBlock), lds_scatter, stream, (const uint32_t*)d_flat,
+                     weighted ? weights->data : nullptr, n_cols, (const uint64_t*)d_base, d_codes, d_w, shift, n_parts);
+  HIPC(hipGetLastError());
+  XH_LAUNCH_PICKED(k_acc, dim3(Gb), dim3(1024), lds_acc, stream, (const uint16_t*)d_codes, (const void*)d_w,
+                     (const uint64_t*)d_offsets, out, p->n_bins, shift, n_parts);
+  HIPC(hipGetLastError());
+  if (!last) return XHIST_OK;
+  char desc[384];
+  snprintf(desc, sizeof desc,
+           "family=fast hist=partitioned parts=%d bins_per_part=%d group=%d vec=%d tile=%d block=%d grid=%d acc_grid=%d "
+           "lds_count=%zu lds_scatter=%zu lds_acc=%zu scan=%d weighted=%d D=%d cmp=%s",
+           n_parts, 1 << shift, grp, vec, kPartTile, kPartBlock, G, Gb, lds_count, lds_scatter, lds_acc, scan, (int)weighted, D,
+           pc.use_f32 ? "f32thr" : "f64");
+  return pc.rec->end(desc);
 }
 
 // ---- execute_partitioned_fused and its steps ----------------------------------------------------------------------------
@@ -565,10 +600,12 @@ static int launch_fused(xhist_plan* p, hipStream_t stream, const Params& kp, con
 //
 // `rows` > 1: that many rows (uniform row strides) in ONE pass — the routing pass treats (row, partition) as the partition, so
 // a few time steps of a big joint histogram cost one launch pair instead of one per row; rows * parts_per_row <= 128.
-static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_cols, void* out,
-                                     hipStream_t stream, int sdt, int wdt, int scan, bool use_f32, const TableSet& tset, int shift,
-                                     int parts_per_row, const PlanKnobs& kn, LaunchRecord& rec, bool first, bool last, RouteGeom geom, int rows = 1) {
+static int execute_partitioned_fused(xhist_plan* p, const PlanKnobs& kn, const PartCall& pc, const xhist_array* samples,
+                                     const xhist_array* weights, void* out, hipStream_t stream, bool first, bool last, int rows = 1) {
   const bool weighted = weights != nullptr;
+  const int64_t n_cols = pc.n_cols;
+  const int sdt = pc.sdt, wdt = pc.wdt, scan = pc.route.scan, shift = pc.shift, parts_per_row = pc.parts_per_row;
+  const RouteGeom geom = pc.route.geom;
   const int n_parts = parts_per_row * rows;
   if (n_cols * rows >= ((int64_t)1 << 40) || n_cols < 4 || n_parts > 128) return XHIST_ERR_UNSUPPORTED;
   kernel_fn_route k_route = route_kernel(sdt, wdt, p->n_dims, scan, rows > 1, geom.block, geom.spl);
@@ -576,7 +613,7 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
   ensure_mixed_hint(p);
   const int exch_skip = exchange_bookkeeping(p);
   RoutePlan rp;
-  if (int rc = plan_route(p, kn, k_route, sdt, wdt, weighted, scan, tset, shift, n_parts, rows, n_cols, geom, rp)) return rc;
+  if (int rc = plan_route(p, kn, k_route, sdt, wdt, weighted, scan, *pc.route.tset, shift, n_parts, rows, n_cols, geom, rp)) return rc;
   ExchPlan xp = plan_exchange(p, kn, samples, weights, n_cols, rows, sdt, wdt, rp.pack, exch_skip);
   if (xp.on) {  // a first look, before the mode's scratch is allocated (launch_exchange looks again, and decides)
     ExchInFlight& fl = exch_in_flight(p->device);
@@ -587,10 +624,9 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
   ScratchScope scratch(stream);
   RouteArgs ra;
   if (int rc = alloc_fused(scratch, p, rp, n_parts, weighted, wdt == XHIST_F32, xp, ra)) return rc;
-  if (first)  // one timing record per execute: opened before the first row's kernels, closed after the last row's
-    if (int rrc = rec.begin(kn.profile)) return rrc;
-  Params kp = partitioned_params(p, samples, weights, n_cols, out, tset, rp.table_words, shift, n_parts);
-  kp.n_rows = rows;
+  if (first)
+    if (int rrc = pc.rec->begin(kn.profile)) return rrc;
+  Params kp = partitioned_params(p, pc, samples, weights, out, *pc.route.tset, rp.table_words, rows, n_parts);
   kp.parts_per_row = parts_per_row;
   kp.segs = rp.G;
   if (int rc = launch_fused(p, stream, kp, rp, ra, xp)) return rc;
@@ -602,325 +638,13 @@ static int execute_partitioned_fused(xhist_plan* p, const xhist_array* samples, 
            "family=fast hist=partitioned route=fused rows_per_pass=%d parts=%d bins_per_part=%d group=%d chunk=%d chunks<=%lld tile=%d block=%d grid=%d "
            "acc_grid=%d lds_route=%zu lds_acc=%zu scan=%d weighted=%d D=%d cmp=%s records=%s exchange=%s exchange_window_ppm_before=%u exchange_aborts=%u exchange_busiest_owner_ppm_before=%u exchange_arrival_misses=%u exchange_records=%s",
            rows, n_parts, 1 << shift, kRouteGrp, 1 << rp.lg, (long long)rp.pool_chunks, rp.tile, rp.block, rp.G, rp.Gb, rp.lds_route, rp.lds_acc, scan,
-           (int)weighted, p->n_dims, use_f32 ? "f32thr" : "f64",
+           (int)weighted, p->n_dims, pc.route.f32 ? "f32thr" : "f64",
            !weighted ? "u16" : rp.pack ? "packed48(+exact if both signs)" : wdt == XHIST_F32 ? "u16+f32" : "u16+f64",
            !xp.on ? "no" : xa.force ? "forced" : xa.n_units > xa.rows_per ? "if the probe's window holds enough of the samples" : "whole histogram in the window",
            note ? note[3] : 0u, note ? note[2] : 0u, note ? note[4] : 0u, note ? note[5] : 0u,
            !xp.on ? "-" : xp.exact ? "exact12(two_rings)" : "packed8");
-  return rec.end(desc);
+  return pc.rec->end(desc);
 }
-
-// Row-per-lane mode (xhist_lanes.hip.h).  Takes (a) views whose ROWS are the contiguous direction
-// (row stride 1: reductions over leading axes) as they are, and (b) many short contiguous rows
-// after transposing them into a [cols, rows] scratch.  Returns XHIST_ERR_UNSUPPORTED when the
-// shape is better served by the row-streaming kernels.
-static int execute_lanes(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_rows, int64_t n_cols,
-                         void* out, int accumulate, hipStream_t stream, const PlanKnobs& kn) {
-  const int D = p->n_dims;
-  const bool prefer = kn.lanes > 0;
-  const bool weighted = weights != nullptr;
-  if (p->cmp != XHIST_CMP_F64 || D > 3 || n_cols >= ((int64_t)1 << 31) || p->n_bins >= (1 << 16) || p->huge) return XHIST_ERR_UNSUPPORTED;
-  const int sdt = samples[0].dtype, wdt = weighted ? weights->dtype : -1;
-  // integer / half-precision samples: one input, unweighted or float64 weights, and only as views whose rows
-  // are the contiguous direction (10^6 x 100 int32 over the leading axis: generic family 1.70 ms)
-  const bool small = sdt == XHIST_I32 || sdt == XHIST_I64 || sdt == XHIST_I16 || sdt == XHIST_U8 || sdt == XHIST_F16;
-  if (small ? !(D == 1 && (wdt == -1 || wdt == XHIST_F64))
-            : ((sdt != XHIST_F64 && sdt != XHIST_F32) || (wdt != -1 && wdt != XHIST_F64 && wdt != XHIST_F32)))
-    return XHIST_ERR_UNSUPPORTED;
-  // shape class of every array: natural (row stride 0/1, any column stride) or needs a transpose
-  // (unit column stride, dense-ish rows)
-  bool all_natural = true, all_rowmajor = true, grouped_any = false;
-  for (int d = 0; d < n_arrays(D, weights); ++d) {
-    const xhist_array& a = array_at(samples, weights, D, d);
-    if (d < D && a.dtype != sdt) return XHIST_ERR_UNSUPPORTED;
-    const bool bcast = a.row_stride == 0 || a.col_stride == 0;
-    const bool natural = bcast || (a.row_stride == 1 && (a.inner_rows ? a.col_stride >= 1 : a.col_stride >= n_rows));
-    const bool rowmajor = bcast || (a.col_stride == 1 && a.row_stride >= n_cols);
-    grouped_any |= a.inner_rows != 0 && !bcast;
-    all_natural &= natural;
-    all_rowmajor &= rowmajor;
-  }
-  const bool use_f32 = sdt == XHIST_F32 && p->ts[1][0].blob != nullptr;
-  int scan = 0;
-  const TableSet* picked = &pick_tables(p, use_f32, &scan);
-  if (small && scan > 1) {  // their kernels exist for the one-compare scan and the binary search only
-    picked = &p->ts[0][0];
-    scan = 0;
-  }
-  // crowded buckets (geometric edges: a binary search in the two-level tables): the packed entries, general variant — the
-  // row-per-lane and flat-rows kernels digitize sample by sample and feel every table read ((1825, 360, 720) float32 over
-  // time, 50 geometric bins: 0.97 -> see profiles/r04_j_*)
-  {
-    const int pk_np = small ? 0 : (sdt == XHIST_F64 ? p->pk_np : (use_f32 ? p->pk32_np : 0));
-    // (only against the binary search: with 3-4 edges per bucket the two-level tables are AHEAD in these LDS-hungry kernels —
-    //  400 random edges, float32: row-per-lane 0.62 against 0.89 ms, flat rows 0.95 against 1.60)
-    if (pk_np && kn.pack_pref >= 0 && (scan == 0 || kn.pack_pref > 0)) {
-      picked = sdt == XHIST_F64 ? &p->ts_pk : &p->ts_pk32;
-      scan = kScanPackG;
-    }
-  }
-  const TableSet& tset = *picked;
-  const size_t table_bytes = (size_t)tset.words * 8;
-  const size_t lds_bytes = table_bytes + (size_t)p->n_bins * kLanePitch * (weighted ? 8 : 4);
-  bool transpose = false;
-  if (small && !(all_natural && samples[0].row_stride == 1)) return XHIST_ERR_UNSUPPORTED;
-  // dense short rows of one or two float inputs, with or without float weights: streamed flat (hist_flat_rows)
-  // (3.65 x 10^8 float32 samples, 50 bins, ms per call, fused turn-around kernel / row streaming | flat: rows of 20 2.25 | 1.83;
-  // 64 1.00 | 0.72; 100 1.07 | 0.66; 200 0.84 | 0.46; 365 0.79 | 0.41; 512 0.59 | 0.42; 720 0.46 | 0.43; 1024 0.33 | 0.38;
-  // 2048 0.28 | 0.37: profiles/r03_f_flat_rows.txt)
-  constexpr int64_t kFlatMaxCols = 800;
-  const uint32_t flat_nbp = weighted ? (uint32_t)p->n_bins : (((uint32_t)p->n_bins + 1u) & ~1u);
-  // (copies of a row's counters for the lanes of a wavefront to spread over — they read neighbouring samples, one or two
-  // rows at a time — were measured and bought nothing: 10^6 rows of 365 float32, 1 / 2 / 4 / 8 copies 0.403 / 0.411 / 0.422 /
-  // 0.497 ms; rows of 200: 0.463 / 0.468 / 0.520 / 0.684; the kernel keeps the parameter, at one copy here)
-  constexpr int flat_k_log2 = 0;
-  const size_t flat_row_bytes = ((size_t)flat_nbp << flat_k_log2) * (weighted ? 8 : 2);  // LDS per row of a workgroup
-  bool flat_ok = (D == 1 || D == 2) && !small && n_cols >= 1 && n_cols < 65536 && (sdt != XHIST_F32 || use_f32) && flat_row_bytes <= 4096 &&
-                 (!weighted || wdt == XHIST_F32 || wdt == XHIST_F64);
-  for (int d = 0; d < n_arrays(D, weights) && flat_ok; ++d) {
-    const xhist_array& a = array_at(samples, weights, D, d);
-    const size_t vec_bytes = (size_t)(16 / dtype_size(sdt)) * (size_t)dtype_size(a.dtype);  // one load: as many elements as a 16-byte sample vector
-    flat_ok = a.col_stride == 1 && a.row_stride == n_cols && a.inner_rows == 0 && ((uintptr_t)a.data & (vec_bytes - 1)) == 0;
-  }
-  const bool use_flat = flat_ok && !prefer && kn.flat_rows >= 0 && n_rows >= 4096 && n_cols <= (kn.flat_rows > 0 ? 65535 : kFlatMaxCols) &&
-                        !(all_natural && samples[0].row_stride == 1);
-  // (hist_lanes: a counter column per lane, or — shared by a row's lane groups — per row, for as few as 16 rows per workgroup)
-  const size_t lds_least = table_bytes + (size_t)p->n_bins * (weighted ? 17 * 8 : 9 * 4);
-  if (lds_least > p->lds_max && !use_flat) return XHIST_ERR_UNSUPPORTED;
-  if (all_natural && (samples[0].row_stride == 1 || prefer)) {
-    // rows are the contiguous direction: the row-streaming kernels cannot coalesce this at all
-  } else if (use_flat) {
-    transpose = true;  // (dense short rows: hist_flat_rows below)
-  } else if (all_rowmajor && (prefer || (n_rows >= 4096 && n_cols <= ((D == 1 && !weighted) ? 400 : 80)))) {
-    // many short rows.  Measured crossovers with the row-streaming kernels (64-thread workgroups,
-    // few LDS copies, plain-store flush; 3.65 x 10^8 f32 samples): ~400 columns for the fused kernel
-    // (one unweighted input: 384 columns 0.64 against 0.67 ms, 512 columns 0.62 against 0.50), below
-    // ~90 for scratch-transpose + lanes (weighted, 96 columns: 3.6 against 3.3 ms)
-    transpose = true;
-  } else {
-    return XHIST_ERR_UNSUPPORTED;
-  }
-
-  int vec = 1;
-  // (counts: uint16 counter columns, two per word — the only unweighted form: a column segment longer than 65535 samples
-  //  would need 2^24 rows to be asked for, see the packed16 rule below; sums: float64 columns)
-  kernel_fn_lanes fn = (kernel_fn_lanes)fast_kernel(sdt, wdt, D, scan, weighted ? kHistLanes : kHistLanes16, &vec);
-  if (!fn) return XHIST_ERR_UNSUPPORTED;
-
-  const bool fused_ok = D == 1 && !weighted && n_cols < 65536 && samples[0].col_stride == 1 && samples[0].row_stride != 0;
-  if (transpose && grouped_any && !fused_ok) return XHIST_ERR_UNSUPPORTED;  // transpose_2d takes plain row strides only
-  if (use_flat) {
-    kernel_fn_flat ff = xhist_pick_flat_rows(sdt, weighted ? wdt : -1, D, scan);
-    // R rows per workgroup: ~16 Ki samples, at most 24 KiB of counters, and enough workgroups for every CU
-    int64_t R = std::min<int64_t>(16384 / n_cols, (int64_t)(24576 / flat_row_bytes));
-    R = std::min<int64_t>(R, std::max<int64_t>((2048 + n_cols - 1) / n_cols, n_rows / ((int64_t)p->cus * 8)));  // (2048+ samples a workgroup)
-    R = std::max<int64_t>(1, std::min<int64_t>(R, 1024));
-    const size_t lds_flat = ((table_bytes + 15) & ~(size_t)15) + (size_t)R * flat_row_bytes + 32 * (weighted ? 8 : 4);
-    const int64_t row_blocks = (n_rows + R - 1) / R;
-    if (ff && lds_flat <= p->lds_max && row_blocks <= 2147483647LL) {
-      Params kp;
-      memset(&kp, 0, sizeof kp);
-      for (int d = 0; d < D; ++d) {
-        kp.s_ptr[d] = samples[d].data;
-        kp.s_rs[d] = samples[d].row_stride;
-        kp.s_cs[d] = 1;
-        kp.s_dt[d] = sdt;
-        kp.dim[d] = tset.dim[d];
-      }
-      if (weighted) {
-        kp.w_ptr = weights->data;
-        kp.w_rs = weights->row_stride;
-        kp.w_cs = 1;
-        kp.w_dt = weights->dtype;
-      }
-      kp.n_dims = D;
-      kp.tables = tset.blob;
-      kp.table_words = tset.words;
-      kp.tables_in_lds = 1;
-      kp.n_rows = n_rows;
-      kp.n_cols = n_cols;
-      kp.n_bins = p->n_bins;
-      kp.out = out;
-      const int direct = accumulate ? 0 : 1;
-      const uint64_t magic = (((uint64_t)1 << 40) / (uint64_t)n_cols) + 1u;
-      LaunchRecord rec(p, stream);
-      if (int rrc = rec.begin(kn.profile)) return rrc;
-      HIPC(set_dynamic_lds((const void*)ff, lds_flat));
-      XH_LAUNCH_PICKED(ff, dim3((unsigned)row_blocks), dim3(kLaneBlock), lds_flat, stream, kp, (int32_t)direct, (int32_t)R, (int32_t)flat_k_log2,
-                         magic, (int64_t)(n_rows * n_cols));
-      HIPC(hipGetLastError());
-      char desc[320];
-      snprintf(desc, sizeof desc,
-               "family=flat_rows hist=%s rows_per_wg=%lld copies=%d direct_store=%d block=%d grid=%lld lds_bytes=%zu scan=%d weighted=%d D=%d cmp=%s",
-               weighted ? "lds" : "lds16", (long long)R, 1 << flat_k_log2, direct, kLaneBlock, (long long)row_blocks, lds_flat, scan, (int)weighted, D,
-               use_f32 ? "f32thr" : "f64");
-      return rec.end(desc);
-    }
-  }
-  // the flat kernel was the only reason to be here and was not launched (no such variant, or its LDS does not fit): beyond
-  // the column limits of the scratch-transpose route the row-streaming kernels are the faster answer (ADVICE r3)
-  if (use_flat && !(all_rowmajor && n_cols <= ((D == 1 && !weighted) ? 400 : 80))) return XHIST_ERR_UNSUPPORTED;
-  if (lds_least > p->lds_max) return XHIST_ERR_UNSUPPORTED;
-  // one contiguous-row input, unweighted, < 65536 columns: fused load-transpose-count kernel
-  if (transpose && D == 1 && !weighted && n_cols < 65536 && samples[0].col_stride == 1 && samples[0].row_stride != 0) {
-    const int es = dtype_size(sdt);
-    const size_t hist_bytes = (size_t)p->n_bins * (kLaneBlock / 2 + 1) * 4;
-    const size_t lds_f = ((table_bytes + hist_bytes + 15) & ~(size_t)15) + (size_t)kLaneBlock * (128 / es + 1) * es;
-    kernel_fn_rows1 f1 = rows1_kernel(sdt, scan);
-    if (f1 && lds_f <= p->lds_max) {
-      Params kp;
-      memset(&kp, 0, sizeof kp);
-      kp.s_ptr[0] = samples[0].data;
-      kp.s_rs[0] = samples[0].row_stride;
-      kp.s_cs[0] = 1;
-      kp.s_ir[0] = samples[0].inner_rows;
-      kp.s_os[0] = samples[0].outer_stride;
-      kp.s_dt[0] = sdt;
-      kp.dim[0] = tset.dim[0];
-      kp.n_dims = 1;
-      kp.tables = tset.blob;
-      kp.table_words = tset.words;
-      kp.tables_in_lds = 1;
-      kp.n_rows = n_rows;
-      kp.n_cols = n_cols;
-      kp.n_bins = p->n_bins;
-      kp.out = out;
-      const int64_t row_blocks = (n_rows + kLaneBlock - 1) / kLaneBlock;
-      if (row_blocks > 2147483647LL) return XHIST_ERR_UNSUPPORTED;
-      const int direct = accumulate ? 0 : 1;
-      LaunchRecord rec(p, stream);
-      if (int rrc = rec.begin(kn.profile)) return rrc;
-      HIPC(set_dynamic_lds((const void*)f1, lds_f));
-      XH_LAUNCH_PICKED(f1, dim3((unsigned)row_blocks), dim3(kLaneBlock), lds_f, stream, kp, (int32_t)direct);
-      HIPC(hipGetLastError());
-      char desc[384];
-      snprintf(desc, sizeof desc,
-               "family=lanes hist=lds16 transpose=fused direct_store=%d block=%d grid=%lld lds_bytes=%zu scan=%d weighted=0 D=1 cmp=%s",
-               direct, kLaneBlock, (long long)row_blocks, lds_f, scan, use_f32 ? "f32thr" : "f64");
-      return rec.end(desc);
-    }
-  }
-
-  ScratchScope scratch(stream);
-  Params kp;
-  memset(&kp, 0, sizeof kp);
-  const DimTable* dims = tset.dim;
-  LaunchRecord rec(p, stream);
-  if (int rrc = rec.begin(kn.profile)) return rrc;
-  for (int d = 0; d < n_arrays(D, weights); ++d) {
-    const xhist_array& a = array_at(samples, weights, D, d);
-    const void* ptr = a.data;
-    int64_t rs = a.row_stride, cs = a.col_stride, ir = a.inner_rows, os = a.outer_stride;
-    if (transpose && rs != 0 && cs != 0) {
-      ir = os = 0;
-      const int es = dtype_size(a.dtype);
-      void* dense = nullptr;
-      HIPC(scratch.alloc(&dense, (size_t)n_rows * n_cols * es));
-      const dim3 grid((unsigned)((n_rows + 63) / 64), (unsigned)((n_cols + 63) / 64));
-      if (es == 8)
-        hipLaunchKernelGGL(transpose_2d<double>, grid, dim3(256), 0, stream, (const double*)a.data, rs, n_rows, n_cols, (double*)dense);
-      else
-        hipLaunchKernelGGL(transpose_2d<float>, grid, dim3(256), 0, stream, (const float*)a.data, rs, n_rows, n_cols, (float*)dense);
-      HIPC(hipGetLastError());
-      ptr = dense;
-      rs = 1;
-      cs = n_rows;
-    }
-    if (d < D) {
-      kp.s_ptr[d] = ptr;
-      kp.s_rs[d] = rs;
-      kp.s_cs[d] = cs;
-      kp.s_ir[d] = ir;
-      kp.s_os[d] = os;
-      kp.s_dt[d] = a.dtype;
-      kp.dim[d] = dims[d];
-    } else {
-      kp.w_ptr = ptr;
-      kp.w_rs = rs;
-      kp.w_cs = cs;
-      kp.w_ir = ir;
-      kp.w_os = os;
-      kp.w_dt = a.dtype;
-    }
-  }
-  kp.n_dims = D;
-  kp.tables = tset.blob;
-  kp.table_words = tset.words;
-  kp.tables_in_lds = 1;
-  kp.n_rows = n_rows;
-  kp.n_cols = n_cols;
-  kp.n_bins = p->n_bins;
-  kp.out = out;
-
-  int lane_rows = kLaneBlock;  // the smallest power of two that holds the rows when there are fewer than 256
-  while (lane_rows > 1 && lane_rows / 2 >= n_rows) lane_rows /= 2;
-  // more rows than that, long reductions: 64-row workgroups with four column streams keep 4x the loads in
-  // flight per row (10^5 x 1000 f32 over the leading axis: 0.25 -> 0.14 ms); short reductions pay for the
-  // smaller blocks' zeroing and write-out instead (10^6 rows of 100: 0.17 -> 0.19 ms) and keep 256
-  if (n_rows > 128 && n_cols >= 512) lane_rows = 64;
-  // Counter columns per lane need n_bins x 257 words.  Where that does not fit (joint histograms over a leading axis:
-  // 20 x 20 bins, (1825, 360, 720) float32 pairs over `time`: the generic family took 7.8 ms, now 1.0) or leaves one
-  // workgroup per CU (float64 sums of 50 bins: 103 KB; the same array with weights 1.49 -> 0.78 ms), the lane groups of a
-  // row share one column per row and the workgroup shrinks to as many rows as fit 40 KiB, 16 at least (joint counts: 64
-  // rows / 54 KB 1.36 ms, 32 rows / 28 KB 1.02, 16 rows 1.80; weighted 50 bins: 128 rows / 53 KB 0.96-1.05, 64 rows 0.78-1.09).
-  int lane_pitch = 0;
-  auto lds_shared = [&](int rows, bool u16) { return table_bytes + (size_t)p->n_bins * (u16 ? (size_t)(rows / 2 + 1) * 4 : (size_t)(rows + 1) * (weighted ? 8 : 4)); };
-  const bool u16_ok = !weighted && n_cols <= 65535;  // (one workgroup per row block then sees every column: see segs16 below)
-  constexpr size_t share_above = 64 * 1024, share_target = 40 * 1024;
-  if ((u16_ok ? table_bytes + (size_t)p->n_bins * (kLaneBlock / 2 + 1) * 4 : lds_bytes) > std::min(p->lds_max, share_above)) {
-    lane_rows = std::min(lane_rows, 128);
-    while (lane_rows > 16 && lds_shared(lane_rows, u16_ok) > share_target) lane_rows /= 2;
-    if (lds_shared(lane_rows, u16_ok) > p->lds_max) return XHIST_ERR_UNSUPPORTED;
-    lane_pitch = 1;  // (the number of words is set below, once the counter width is known)
-  }
-  kp.lane_rows = lane_rows;
-  const int64_t row_blocks = (n_rows + lane_rows - 1) / lane_rows;
-  // unweighted and few enough columns per workgroup: uint16 counters, half the LDS
-  size_t lds_use = lane_pitch ? lds_shared(lane_rows, false) : lds_bytes;
-  bool packed16 = false;
-  if (!weighted) {
-    const size_t lds16 = lane_pitch ? lds_shared(lane_rows, true) : table_bytes + (size_t)p->n_bins * (kLaneBlock / 2 + 1) * 4;
-    const int bpc16 = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)160 * 1024 / lds16));
-    int64_t segs16 = std::max<int64_t>(1, ((int64_t)p->cus * bpc16 * 2 + row_blocks - 1) / row_blocks);
-    segs16 = std::min<int64_t>(std::min<int64_t>(segs16, std::max<int64_t>(1, n_cols / 64)), 65535);
-    // (a segment of more than 65535 columns: only with so many row blocks that there is one segment each — beyond 10^10
-    //  samples; the row-streaming kernels take that call.  The uint32-column kernels this used to fall back to were never
-    //  selected by anything — census of round 6 — and are gone)
-    if ((n_cols + segs16 - 1) / segs16 > 65535) return XHIST_ERR_UNSUPPORTED;
-    packed16 = true;
-    lds_use = lds16;
-  }
-  if (lane_pitch) lane_pitch = packed16 ? lane_rows / 2 + 1 : lane_rows + 1;
-  kp.lane_pitch = lane_pitch;
-  if (lds_use > p->lds_max) return XHIST_ERR_UNSUPPORTED;
-  const int bpc = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)160 * 1024 / lds_use));
-  int64_t col_segs = std::max<int64_t>(1, ((int64_t)p->cus * bpc * 2 + row_blocks - 1) / row_blocks);
-  col_segs = std::min<int64_t>(col_segs, std::max<int64_t>(1, n_cols / 64));
-  col_segs = std::min<int64_t>(col_segs, 65535);
-  const int64_t cols_per_seg = (n_cols + col_segs - 1) / col_segs;
-  col_segs = (n_cols + cols_per_seg - 1) / cols_per_seg;
-  const int direct = (col_segs == 1 && !accumulate) ? 1 : 0;
-  if (!direct && !accumulate)
-    if (int zrc = zero_output(out, n_rows * p->n_bins, stream)) return zrc;
-  if (row_blocks > 2147483647LL) return XHIST_ERR_UNSUPPORTED;
-  HIPC(set_dynamic_lds((const void*)fn, lds_use));
-  XH_LAUNCH_PICKED(fn, dim3((unsigned)row_blocks, (unsigned)col_segs), dim3(kLaneBlock), lds_use, stream, kp, (int32_t)direct,
-                     cols_per_seg);
-  HIPC(hipGetLastError());
-  char desc[384];
-  snprintf(desc, sizeof desc,
-           "family=lanes hist=%s%s rows_per_wg=%d transpose=%d direct_store=%d block=%d grid=%lldx%lld lds_bytes=%zu scan=%d weighted=%d D=%d cmp=%s",
-           packed16 ? "lds16" : "lds", lane_pitch ? "(shared)" : "", lane_rows, (int)transpose, direct, kLaneBlock, (long long)row_blocks, (long long)col_segs, lds_use, scan,
-           (int)weighted, D,
-           use_f32 ? "f32thr" : "f64");
-  return rec.end(desc);
-}
-
-// ------------------------------------------------------------------------------------------
-// the streaming kernels: execute_device and its steps
-// ------------------------------------------------------------------------------------------
-static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_rows, int64_t n_cols,
-                          void* out, int accumulate, hipStream_t stream, const xhist_array* weights2 = nullptr, void* out2 = nullptr);
 
 // One execute's arrays and shape, as the steps below see them.
 struct Inputs {
@@ -933,6 +657,326 @@ struct Inputs {
   int n_arrays() const { return ::n_arrays(D, weights); }
   const xhist_array& array(int d) const { return array_at(samples, weights, D, d); }
 };
+
+// ---- row-per-lane mode: execute_lanes and its steps (xhist_lanes.hip.h) -------------------------------------------------
+// Takes (a) views whose ROWS are the contiguous direction (row stride 1: reductions over leading axes) as they are, and (b) many
+// short contiguous rows: streamed flat (hist_flat_rows), or turned around in one pass (hist_lanes_rows1), or transposed into a
+// [cols, rows] scratch first (hist_lanes).  Returns XHIST_ERR_UNSUPPORTED, before anything is recorded or launched, when the
+// shape is better served by the row-streaming kernels.
+enum LaneFamily { kLaneFlatRows, kLaneRows1, kLaneColumns };
+
+// What execute_lanes launches, decided by choose_lanes.
+struct LaneChoice {
+  int family = kLaneColumns;
+  bool transpose = false;  // row-major arrays: flat rows, rows1, or hist_lanes on transposed scratch
+  bool use_f32 = false;
+  int scan = 0;
+  const TableSet* tset = nullptr;
+  size_t table_bytes = 0;
+  int64_t row_blocks = 0;
+  size_t lds = 0;  // dynamic LDS of the launch
+  int direct = 0;
+  kernel_fn_flat ff = nullptr;  // flat rows: R rows per workgroup
+  int64_t R = 0;
+  kernel_fn_rows1 f1 = nullptr;
+  kernel_fn_lanes fn = nullptr;  // hist_lanes: lane_rows rows per workgroup, col_segs segments of cols_per_seg columns
+  int lane_rows = 0, lane_pitch = 0;
+  bool packed16 = false;
+  int64_t col_segs = 0, cols_per_seg = 0;
+};
+
+// hist_flat_rows' LDS per row of a workgroup: uint16 counters (an even number) or float64 sums.
+// (copies of a row's counters for the lanes of a wavefront to spread over — they read neighbouring samples, one or two
+// rows at a time — were measured and bought nothing: 10^6 rows of 365 float32, 1 / 2 / 4 / 8 copies 0.403 / 0.411 / 0.422 /
+// 0.497 ms; rows of 200: 0.463 / 0.468 / 0.520 / 0.684; the kernel keeps the parameter, at one copy here)
+static constexpr int kFlatCopiesLog2 = 0;
+static size_t flat_row_bytes(int64_t n_bins, bool weighted) {
+  const uint32_t nbp = weighted ? (uint32_t)n_bins : (((uint32_t)n_bins + 1u) & ~1u);
+  return ((size_t)nbp << kFlatCopiesLog2) * (weighted ? 8 : 2);
+}
+
+// hist_lanes with the lane groups of a row sharing one counter column per row: `rows` rows, uint16 or 4- / 8-byte counters
+static size_t lanes_shared_lds(size_t table_bytes, int64_t n_bins, int rows, bool u16, bool weighted) {
+  return table_bytes + (size_t)n_bins * (u16 ? (size_t)(rows / 2 + 1) * 4 : (size_t)(rows + 1) * (weighted ? 8 : 4));
+}
+
+// The digitize of the row-per-lane kernels: the plan's pick, with the overrides of small dtypes and of crowded buckets.
+static void lane_tables(const xhist_plan* p, const PlanKnobs& kn, int sdt, bool small, LaneChoice& lc) {
+  lc.use_f32 = sdt == XHIST_F32 && p->ts[1][0].blob != nullptr;
+  lc.tset = &pick_tables(p, lc.use_f32, &lc.scan);
+  if (small && lc.scan > 1) {  // their kernels exist for the one-compare scan and the binary search only
+    lc.tset = &p->ts[0][0];
+    lc.scan = 0;
+  }
+  // crowded buckets (geometric edges: a binary search in the two-level tables): the packed entries, general variant — the
+  // row-per-lane and flat-rows kernels digitize sample by sample and feel every table read ((1825, 360, 720) float32 over
+  // time, 50 geometric bins: 0.97 -> see profiles/r04_j_*)
+  const int pk_np = small ? 0 : (sdt == XHIST_F64 ? p->pk_np : (lc.use_f32 ? p->pk32_np : 0));
+  // (only against the binary search: with 3-4 edges per bucket the two-level tables are AHEAD in these LDS-hungry kernels —
+  //  400 random edges, float32: row-per-lane 0.62 against 0.89 ms, flat rows 0.95 against 1.60)
+  if (pk_np && kn.pack_pref >= 0 && (lc.scan == 0 || kn.pack_pref > 0)) {
+    lc.tset = sdt == XHIST_F64 ? &p->ts_pk : &p->ts_pk32;
+    lc.scan = kScanPackG;
+  }
+  lc.table_bytes = (size_t)lc.tset->words * 8;
+}
+
+// hist_flat_rows: R rows per workgroup.  False when there is no such variant or its LDS does not fit.
+static bool plan_flat_rows(const xhist_plan* p, const Inputs& in, int accumulate, LaneChoice& lc) {
+  const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  const size_t row_bytes = flat_row_bytes(p->n_bins, in.weighted);
+  kernel_fn_flat ff = xhist_pick_flat_rows(in.sdt, in.wdt, in.D, lc.scan);
+  // R rows per workgroup: ~16 Ki samples, at most 24 KiB of counters, and enough workgroups for every CU
+  int64_t R = std::min<int64_t>(16384 / n_cols, (int64_t)(24576 / row_bytes));
+  R = std::min<int64_t>(R, std::max<int64_t>((2048 + n_cols - 1) / n_cols, n_rows / ((int64_t)p->cus * 8)));  // (2048+ samples a workgroup)
+  R = std::max<int64_t>(1, std::min<int64_t>(R, 1024));
+  const size_t lds = ((lc.table_bytes + 15) & ~(size_t)15) + (size_t)R * row_bytes + 32 * (in.weighted ? 8 : 4);
+  const int64_t row_blocks = (n_rows + R - 1) / R;
+  if (!ff || lds > p->lds_max || row_blocks > 2147483647LL) return false;
+  lc.family = kLaneFlatRows;
+  lc.ff = ff;
+  lc.R = R;
+  lc.lds = lds;
+  lc.row_blocks = row_blocks;
+  lc.direct = accumulate ? 0 : 1;
+  return true;
+}
+
+// hist_lanes_rows1, the fused load-transpose-count kernel.  False when there is no such variant or its LDS does not fit.
+static bool plan_rows1(const xhist_plan* p, const Inputs& in, int accumulate, LaneChoice& lc) {
+  const int es = dtype_size(in.sdt);
+  const size_t hist_bytes = (size_t)p->n_bins * (kLaneBlock / 2 + 1) * 4;
+  const size_t lds = ((lc.table_bytes + hist_bytes + 15) & ~(size_t)15) + (size_t)kLaneBlock * (128 / es + 1) * es;
+  kernel_fn_rows1 f1 = rows1_kernel(in.sdt, lc.scan);
+  if (!f1 || lds > p->lds_max) return false;
+  lc.family = kLaneRows1;
+  lc.f1 = f1;
+  lc.lds = lds;
+  lc.row_blocks = (in.n_rows + kLaneBlock - 1) / kLaneBlock;
+  lc.direct = accumulate ? 0 : 1;
+  return true;
+}
+
+// hist_lanes: rows per workgroup, counter layout and column segments.
+static int plan_lane_columns(const xhist_plan* p, const Inputs& in, int accumulate, LaneChoice& lc) {
+  const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  const bool weighted = in.weighted;
+  const size_t table_bytes = lc.table_bytes;
+  const size_t lds_lane = table_bytes + (size_t)p->n_bins * kLanePitch * (weighted ? 8 : 4);
+  const size_t lds_lane16 = table_bytes + (size_t)p->n_bins * (kLaneBlock / 2 + 1) * 4;
+  int lane_rows = kLaneBlock;  // the smallest power of two that holds the rows when there are fewer than 256
+  while (lane_rows > 1 && lane_rows / 2 >= n_rows) lane_rows /= 2;
+  // more rows than that, long reductions: 64-row workgroups with four column streams keep 4x the loads in
+  // flight per row (10^5 x 1000 f32 over the leading axis: 0.25 -> 0.14 ms); short reductions pay for the
+  // smaller blocks' zeroing and write-out instead (10^6 rows of 100: 0.17 -> 0.19 ms) and keep 256
+  if (n_rows > 128 && n_cols >= 512) lane_rows = 64;
+  // Counter columns per lane need n_bins x 257 words.  Where that does not fit (joint histograms over a leading axis:
+  // 20 x 20 bins, (1825, 360, 720) float32 pairs over `time`: the generic family took 7.8 ms, now 1.0) or leaves one
+  // workgroup per CU (float64 sums of 50 bins: 103 KB; the same array with weights 1.49 -> 0.78 ms), the lane groups of a
+  // row share one column per row and the workgroup shrinks to as many rows as fit 40 KiB, 16 at least (joint counts: 64
+  // rows / 54 KB 1.36 ms, 32 rows / 28 KB 1.02, 16 rows 1.80; weighted 50 bins: 128 rows / 53 KB 0.96-1.05, 64 rows 0.78-1.09).
+  const bool u16_ok = !weighted && n_cols <= 65535;  // (one workgroup per row block then sees every column: see cols_per_seg below)
+  constexpr size_t share_above = 64 * 1024, share_target = 40 * 1024;
+  bool shared = false;
+  if ((u16_ok ? lds_lane16 : lds_lane) > std::min(p->lds_max, share_above)) {
+    lane_rows = std::min(lane_rows, 128);
+    while (lane_rows > 16 && lanes_shared_lds(table_bytes, p->n_bins, lane_rows, u16_ok, weighted) > share_target) lane_rows /= 2;
+    if (lanes_shared_lds(table_bytes, p->n_bins, lane_rows, u16_ok, weighted) > p->lds_max) return XHIST_ERR_UNSUPPORTED;
+    shared = true;
+  }
+  // (counts: uint16 counter columns, two per word — the only unweighted form: a column segment longer than 65535 samples
+  //  would need 2^24 rows to be asked for, see the check on cols_per_seg below; sums: float64 columns)
+  const bool packed16 = !weighted;
+  const size_t lds = shared ? lanes_shared_lds(table_bytes, p->n_bins, lane_rows, packed16, weighted) : (packed16 ? lds_lane16 : lds_lane);
+  if (lds > p->lds_max) return XHIST_ERR_UNSUPPORTED;
+  const int64_t row_blocks = (n_rows + lane_rows - 1) / lane_rows;
+  const int bpc = (int)std::max<size_t>(1, std::min<size_t>(8, (size_t)160 * 1024 / lds));
+  int64_t col_segs = std::max<int64_t>(1, ((int64_t)p->cus * bpc * 2 + row_blocks - 1) / row_blocks);
+  col_segs = std::min<int64_t>(col_segs, std::max<int64_t>(1, n_cols / 64));
+  col_segs = std::min<int64_t>(col_segs, 65535);
+  const int64_t cols_per_seg = (n_cols + col_segs - 1) / col_segs;
+  // (uint16 counters and a segment of more than 65535 columns: only with so many row blocks that there is one segment each —
+  //  beyond 10^10 samples; the row-streaming kernels take that call.  The uint32-column kernels this used to fall back to were
+  //  never selected by anything — census of round 6 — and are gone)
+  if (packed16 && cols_per_seg > 65535) return XHIST_ERR_UNSUPPORTED;
+  if (row_blocks > 2147483647LL) return XHIST_ERR_UNSUPPORTED;
+  lc.family = kLaneColumns;
+  lc.lane_rows = lane_rows;
+  lc.lane_pitch = !shared ? 0 : packed16 ? lane_rows / 2 + 1 : lane_rows + 1;
+  lc.packed16 = packed16;
+  lc.lds = lds;
+  lc.row_blocks = row_blocks;
+  lc.col_segs = (n_cols + cols_per_seg - 1) / cols_per_seg;
+  lc.cols_per_seg = cols_per_seg;
+  lc.direct = (lc.col_segs == 1 && !accumulate) ? 1 : 0;
+  return XHIST_OK;
+}
+
+// Every decision of execute_lanes, and every XHIST_ERR_UNSUPPORTED it returns: nothing is recorded, allocated or launched here.
+static int choose_lanes(const xhist_plan* p, const PlanKnobs& kn, const Inputs& in, int accumulate, LaneChoice& lc) {
+  const int D = in.D, sdt = in.sdt, wdt = in.wdt;
+  const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  const bool prefer = kn.lanes > 0;
+  const bool weighted = in.weighted;
+  if (p->cmp != XHIST_CMP_F64 || D > 3 || n_cols >= ((int64_t)1 << 31) || p->n_bins >= (1 << 16) || p->huge) return XHIST_ERR_UNSUPPORTED;
+  // integer / half-precision samples: one input, unweighted or float64 weights, and only as views whose rows
+  // are the contiguous direction (10^6 x 100 int32 over the leading axis: generic family 1.70 ms)
+  const bool small = sdt == XHIST_I32 || sdt == XHIST_I64 || sdt == XHIST_I16 || sdt == XHIST_U8 || sdt == XHIST_F16;
+  if (small ? !(D == 1 && (wdt == -1 || wdt == XHIST_F64))
+            : ((sdt != XHIST_F64 && sdt != XHIST_F32) || (wdt != -1 && wdt != XHIST_F64 && wdt != XHIST_F32)))
+    return XHIST_ERR_UNSUPPORTED;
+  // shape class of every array: natural (row stride 0/1, any column stride) or needs a transpose
+  // (unit column stride, dense-ish rows)
+  // (and dense rows of aligned vectors: what the flat-rows kernel streams)
+  bool all_natural = true, all_rowmajor = true, grouped_any = false, all_dense = true;
+  for (int d = 0; d < in.n_arrays(); ++d) {
+    const xhist_array& a = in.array(d);
+    if (d < D && a.dtype != sdt) return XHIST_ERR_UNSUPPORTED;
+    const bool bcast = a.row_stride == 0 || a.col_stride == 0;
+    const bool natural = bcast || (a.row_stride == 1 && (a.inner_rows ? a.col_stride >= 1 : a.col_stride >= n_rows));
+    const bool rowmajor = bcast || (a.col_stride == 1 && a.row_stride >= n_cols);
+    const size_t vec_bytes = (size_t)(16 / dtype_size(sdt)) * (size_t)dtype_size(a.dtype);  // one load: as many elements as a 16-byte sample vector
+    grouped_any |= a.inner_rows != 0 && !bcast;
+    all_natural &= natural;
+    all_rowmajor &= rowmajor;
+    all_dense &= a.col_stride == 1 && a.row_stride == n_cols && a.inner_rows == 0 && ((uintptr_t)a.data & (vec_bytes - 1)) == 0;
+  }
+  const bool rows_natural = all_natural && in.samples[0].row_stride == 1;
+  if (small && !rows_natural) return XHIST_ERR_UNSUPPORTED;
+  lane_tables(p, kn, sdt, small, lc);
+  // dense short rows of one or two float inputs, with or without float weights: streamed flat (hist_flat_rows)
+  // (3.65 x 10^8 float32 samples, 50 bins, ms per call, fused turn-around kernel / row streaming | flat: rows of 20 2.25 | 1.83;
+  // 64 1.00 | 0.72; 100 1.07 | 0.66; 200 0.84 | 0.46; 365 0.79 | 0.41; 512 0.59 | 0.42; 720 0.46 | 0.43; 1024 0.33 | 0.38;
+  // 2048 0.28 | 0.37: profiles/r03_f_flat_rows.txt)
+  constexpr int64_t kFlatMaxCols = 800;
+  const bool flat_ok = (D == 1 || D == 2) && !small && n_cols >= 1 && n_cols < 65536 && (sdt != XHIST_F32 || lc.use_f32) &&
+                       flat_row_bytes(p->n_bins, weighted) <= 4096 && (!weighted || wdt == XHIST_F32 || wdt == XHIST_F64) && all_dense;
+  const bool use_flat = flat_ok && !prefer && kn.flat_rows >= 0 && n_rows >= 4096 && n_cols <= (kn.flat_rows > 0 ? 65535 : kFlatMaxCols) &&
+                        !rows_natural;
+  // many short rows.  Measured crossovers with the row-streaming kernels (64-thread workgroups, few LDS copies, plain-store
+  // flush; 3.65 x 10^8 f32 samples): ~400 columns for the fused kernel (one unweighted input: 384 columns 0.64 against
+  // 0.67 ms, 512 columns 0.62 against 0.50), below ~90 for scratch-transpose + lanes (weighted, 96 columns: 3.6 against 3.3 ms)
+  const bool short_rows = all_rowmajor && n_cols <= ((D == 1 && !weighted) ? 400 : 80);
+  if (all_natural && (in.samples[0].row_stride == 1 || prefer)) {
+    // rows are the contiguous direction: the row-streaming kernels cannot coalesce this at all
+  } else if (use_flat || (all_rowmajor && prefer) || (n_rows >= 4096 && short_rows)) {
+    lc.transpose = true;
+  } else {
+    return XHIST_ERR_UNSUPPORTED;
+  }
+  int vec = 1;
+  lc.fn = (kernel_fn_lanes)fast_kernel(sdt, wdt, D, lc.scan, weighted ? kHistLanes : kHistLanes16, &vec);
+  if (!lc.fn) return XHIST_ERR_UNSUPPORTED;
+  if (use_flat && plan_flat_rows(p, in, accumulate, lc)) return XHIST_OK;
+  // the flat kernel was the only reason to be here and was not launched (no such variant, or its LDS does not fit): beyond
+  // the column limits of the scratch-transpose route the row-streaming kernels are the faster answer (ADVICE r3)
+  if (use_flat && !short_rows) return XHIST_ERR_UNSUPPORTED;
+  // (hist_lanes: a counter column per lane, or — shared by a row's lane groups — per row, for as few as 16 rows per workgroup)
+  const size_t lds_least = lc.table_bytes + (size_t)p->n_bins * (weighted ? 17 * 8 : 9 * 4);
+  if (lds_least > p->lds_max) return XHIST_ERR_UNSUPPORTED;
+  // one contiguous-row input, unweighted, < 65536 columns: the fused load-transpose-count kernel, which takes grouped rows too
+  const bool rows1_ok = D == 1 && !weighted && n_cols < 65536 && in.samples[0].col_stride == 1 && in.samples[0].row_stride != 0;
+  if (lc.transpose && rows1_ok && plan_rows1(p, in, accumulate, lc))
+    return lc.row_blocks > 2147483647LL ? XHIST_ERR_UNSUPPORTED : XHIST_OK;
+  if (lc.transpose && grouped_any) return XHIST_ERR_UNSUPPORTED;  // transpose_2d takes plain row strides only
+  return plan_lane_columns(p, in, accumulate, lc);
+}
+
+static int launch_flat_rows(xhist_plan* p, const PlanKnobs& kn, const Inputs& in, const LaneChoice& lc, void* out, hipStream_t stream) {
+  const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  // (flat rows: unit column stride and no groups, choose_lanes; what the kernel is handed of the groups stays zero)
+  Params kp = fill_params(in.samples, in.weights, in.D, *lc.tset, lc.tset->words, n_rows, n_cols, p->n_bins, out);
+  for (int d = 0; d < in.D; ++d) kp.s_os[d] = 0;
+  kp.w_os = 0;
+  const uint64_t magic = (((uint64_t)1 << 40) / (uint64_t)n_cols) + 1u;
+  LaunchRecord rec(p, stream);
+  if (int rrc = rec.begin(kn.profile)) return rrc;
+  HIPC(set_dynamic_lds((const void*)lc.ff, lc.lds));
+  XH_LAUNCH_PICKED(lc.ff, dim3((unsigned)lc.row_blocks), dim3(kLaneBlock), lc.lds, stream, kp, (int32_t)lc.direct, (int32_t)lc.R,
+                   (int32_t)kFlatCopiesLog2, magic, (int64_t)(n_rows * n_cols));
+  HIPC(hipGetLastError());
+  char desc[320];
+  snprintf(desc, sizeof desc,
+           "family=flat_rows hist=%s rows_per_wg=%lld copies=%d direct_store=%d block=%d grid=%lld lds_bytes=%zu scan=%d weighted=%d D=%d cmp=%s",
+           in.weighted ? "lds" : "lds16", (long long)lc.R, 1 << kFlatCopiesLog2, lc.direct, kLaneBlock, (long long)lc.row_blocks, lc.lds, lc.scan,
+           (int)in.weighted, in.D, lc.use_f32 ? "f32thr" : "f64");
+  return rec.end(desc);
+}
+
+static int launch_rows1(xhist_plan* p, const PlanKnobs& kn, const Inputs& in, const LaneChoice& lc, void* out, hipStream_t stream) {
+  // (one unweighted input of unit column stride, choose_lanes)
+  const Params kp = fill_params(in.samples, nullptr, 1, *lc.tset, lc.tset->words, in.n_rows, in.n_cols, p->n_bins, out);
+  LaunchRecord rec(p, stream);
+  if (int rrc = rec.begin(kn.profile)) return rrc;
+  HIPC(set_dynamic_lds((const void*)lc.f1, lc.lds));
+  XH_LAUNCH_PICKED(lc.f1, dim3((unsigned)lc.row_blocks), dim3(kLaneBlock), lc.lds, stream, kp, (int32_t)lc.direct);
+  HIPC(hipGetLastError());
+  char desc[384];
+  snprintf(desc, sizeof desc,
+           "family=lanes hist=lds16 transpose=fused direct_store=%d block=%d grid=%lld lds_bytes=%zu scan=%d weighted=0 D=1 cmp=%s",
+           lc.direct, kLaneBlock, (long long)lc.row_blocks, lc.lds, lc.scan, lc.use_f32 ? "f32thr" : "f64");
+  return rec.end(desc);
+}
+
+// hist_lanes, on the arrays as they are or on [cols, rows] scratch copies of the row-major ones (broadcast arrays stay as they are).
+static int launch_lane_columns(xhist_plan* p, const PlanKnobs& kn, const Inputs& in, const LaneChoice& lc, void* out, int accumulate,
+                               hipStream_t stream) {
+  const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  ScratchScope scratch(stream);
+  LaunchRecord rec(p, stream);
+  if (int rrc = rec.begin(kn.profile)) return rrc;
+  xhist_array views[kMaxDims + 1];  // the samples, then the weights
+  for (int d = 0; d < in.n_arrays(); ++d) {
+    const xhist_array& a = in.array(d);
+    views[d] = a;
+    if (!lc.transpose || a.row_stride == 0 || a.col_stride == 0) continue;
+    const int es = dtype_size(a.dtype);
+    void* dense = nullptr;
+    HIPC(scratch.alloc(&dense, (size_t)n_rows * n_cols * es));
+    const dim3 grid((unsigned)((n_rows + 63) / 64), (unsigned)((n_cols + 63) / 64));
+    if (es == 8)
+      hipLaunchKernelGGL(transpose_2d<double>, grid, dim3(256), 0, stream, (const double*)a.data, a.row_stride, n_rows, n_cols, (double*)dense);
+    else
+      hipLaunchKernelGGL(transpose_2d<float>, grid, dim3(256), 0, stream, (const float*)a.data, a.row_stride, n_rows, n_cols, (float*)dense);
+    HIPC(hipGetLastError());
+    views[d].data = dense;
+    views[d].row_stride = 1;
+    views[d].col_stride = n_rows;
+    views[d].inner_rows = 0;
+    views[d].outer_stride = 0;
+  }
+  Params kp = fill_params(views, in.weighted ? &views[in.D] : nullptr, in.D, *lc.tset, lc.tset->words, n_rows, n_cols, p->n_bins, out);
+  kp.lane_rows = lc.lane_rows;
+  kp.lane_pitch = lc.lane_pitch;
+  if (!lc.direct && !accumulate)
+    if (int zrc = zero_output(out, n_rows * p->n_bins, stream)) return zrc;
+  HIPC(set_dynamic_lds((const void*)lc.fn, lc.lds));
+  XH_LAUNCH_PICKED(lc.fn, dim3((unsigned)lc.row_blocks, (unsigned)lc.col_segs), dim3(kLaneBlock), lc.lds, stream, kp, (int32_t)lc.direct,
+                   lc.cols_per_seg);
+  HIPC(hipGetLastError());
+  char desc[384];
+  snprintf(desc, sizeof desc,
+           "family=lanes hist=%s%s rows_per_wg=%d transpose=%d direct_store=%d block=%d grid=%lldx%lld lds_bytes=%zu scan=%d weighted=%d D=%d cmp=%s",
+           lc.packed16 ? "lds16" : "lds", lc.lane_pitch ? "(shared)" : "", lc.lane_rows, (int)lc.transpose, lc.direct, kLaneBlock,
+           (long long)lc.row_blocks, (long long)lc.col_segs, lc.lds, lc.scan, (int)in.weighted, in.D, lc.use_f32 ? "f32thr" : "f64");
+  return rec.end(desc);
+}
+
+static int execute_lanes(xhist_plan* p, const PlanKnobs& kn, const Inputs& in, void* out, int accumulate, hipStream_t stream) {
+  LaneChoice lc;
+  if (int rc = choose_lanes(p, kn, in, accumulate, lc)) return rc;
+  switch (lc.family) {
+    case kLaneFlatRows: return launch_flat_rows(p, kn, in, lc, out, stream);
+    case kLaneRows1: return launch_rows1(p, kn, in, lc, out, stream);
+    default: return launch_lane_columns(p, kn, in, lc, out, accumulate, stream);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// the streaming kernels: execute_device and its steps
+// ------------------------------------------------------------------------------------------
+static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_rows, int64_t n_cols,
+                          void* out, int accumulate, hipStream_t stream, const xhist_array* weights2 = nullptr, void* out2 = nullptr);
 
 // ---- a few rows that are the contiguous direction, too many bins for the row-per-lane kernels ----------------
 // (the columns of an (n, K) table histogrammed over its leading axis with thousands of bins): every other kernel
@@ -1324,14 +1368,71 @@ static void choose_slices(const xhist_plan* p, const PlanKnobs& kn, const Inputs
   sc.lds_bytes = sc.table_bytes + sc.hist_bytes;
 }
 
-// Row r of every array of a call: the samples into row_s, the weights into row_w.
+// Row r of every array of a call: the samples into row_s, the weights into row_w.  Plain rows, no groups: a view is one row, or
+// rows at one row stride when the arrays have no groups to begin with (the partitioned mode's several rows per pass).
 static void row_views(const Inputs& in, int64_t r, xhist_array* row_s, xhist_array& row_w) {
   for (int d = 0; d < in.n_arrays(); ++d) {
     const xhist_array& a = in.array(d);
     xhist_array& v = d < in.D ? row_s[d] : row_w;
     v = a;
     v.data = const_cast<void*>(advance(a.data, a.dtype, row_offset(r, a.row_stride, a.inner_rows, a.outer_stride)));
+    v.inner_rows = 0;
+    v.outer_stride = 0;
   }
+}
+
+// The digitize of the routing pass.  It keeps the digitize tables in LDS next to its sort buffers; where they do not fit (or
+// cost a workgroup per CU) and the edges are arithmetic (C5: 2 x 1025 np.linspace edges, 32 KiB of tables) it digitizes
+// table-free.
+static RouteDigitize route_digitize(const xhist_plan* p, const PlanKnobs& kn, const Inputs& in, const StreamChoice& sc, int64_t n_parts) {
+  const int D = in.D, sdt = in.sdt;
+  const bool weighted = in.weighted;
+  const int scan = sc.scan;
+  const TableSet* tset = sc.tset;
+  RouteDigitize r{scan, tset, sc.use_f32, RouteGeom{}};
+  const bool can_arith = p->arith && kn.arith_pref >= 0 && n_parts <= 128;
+  const int w_tag = weighted ? in.wdt : -1;
+  // geometry first: the long tile with the arithmetic digitize where the edges allow it, else with the tables if both
+  // fit the LDS, else the short tile
+  RouteGeom& geom = r.geom;
+  geom = route_geom_for(kn, sdt, w_tag, D, can_arith ? kScanArith : scan);
+  if (geom.spl == 8 && (can_arith || scan == kScanArith)) {
+    if (scan != kScanArith) {
+      r.scan = kScanArith;
+      r.tset = &p->ts[0][0];
+      r.f32 = false;
+    }
+  } else {
+    if (geom.spl == 8 && !kn.route_spl &&
+        part_route_lds((size_t)tset->words * 8, (int)n_parts, weighted, route_tile(geom.block, 8), geom.block) > p->lds_max)
+      geom.spl = 4;
+    if (can_arith && scan != kScanArith) {
+      const int t4 = route_tile(geom.block, geom.spl);
+      const size_t lds_tab = part_route_lds((size_t)tset->words * 8, (int)n_parts, weighted, t4, geom.block),
+                   lds_notab = part_route_lds(0, (int)n_parts, weighted, t4, geom.block);
+      if (lds_tab > p->lds_max || (size_t)160 * 1024 / lds_notab > (size_t)160 * 1024 / lds_tab) {
+        r.scan = kScanArith;
+        r.tset = &p->ts[0][0];
+        r.f32 = false;
+      }
+    }
+  }
+  // non-uniform edges: the packed entries (general variant) instead of a binary search or a 2-4-edge scan per sample and
+  // dimension — the routing pass feels its digitize (5*10^8 float64 pairs into 512 x 512 counts: linspace 2.07 ms, random
+  // edges 2.48, geometric 3.42; profiles/r04_l_*) — where entries and sort buffers fit the LDS together
+  const int pk_np = sdt == XHIST_F64 ? p->pk_np : (sdt == XHIST_F32 && sc.use_f32 ? p->pk32_np : 0);
+  if (pk_np && kn.pack_pref >= 0 && r.scan != kScanArith && (r.scan == 0 || r.scan >= 2 || kn.pack_pref > 0) && n_parts <= 128) {
+    const TableSet& pk = sdt == XHIST_F64 ? p->ts_pk : p->ts_pk32;
+    int spl = geom.spl;
+    if (spl == 8 && part_route_lds((size_t)pk.words * 8, (int)n_parts, weighted, route_tile(geom.block, 8), geom.block) > p->lds_max) spl = 4;
+    if (part_route_lds((size_t)pk.words * 8, (int)n_parts, weighted, route_tile(geom.block, spl), geom.block) <= p->lds_max &&
+        route_kernel(sdt, w_tag, D, kScanPackG, false, geom.block, spl)) {
+      r.scan = kScanPackG;
+      r.tset = &pk;
+      geom.spl = spl;
+    }
+  }
+  return r;
 }
 
 // ---- histograms beyond LDS: partitioned multi-pass instead of memory-side atomics ----------
@@ -1339,9 +1440,9 @@ static void row_views(const Inputs& in, int64_t r, xhist_array* row_s, xhist_arr
 // XHIST_ERR_UNSUPPORTED: nothing was launched.  The output may have been zeroed by then; `accumulate` is 1 if so.
 static int execute_partitioned_rows(xhist_plan* p, const PlanKnobs& kn, const Inputs& in, const StreamChoice& sc, void* out,
                                     int& accumulate, hipStream_t stream) {
-  const int D = in.D, sdt = in.sdt, wdt = in.wdt;
   const bool weighted = in.weighted;
   const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
+  // (sc.fast with float samples: the vector family, whose arrays all have unit column stride — choose_streaming)
   if (!(sc.fast && in.float_samples && sc.hist == kHistGlobal && !kn.force_global && kn.partition >= 0 && n_rows <= 64 && !in.two &&
         sc.n_slices == 1))
     return XHIST_ERR_UNSUPPORTED;
@@ -1355,59 +1456,8 @@ static int execute_partitioned_rows(xhist_plan* p, const PlanKnobs& kn, const In
     accumulate = 1;  // (for the streaming kernels, should nothing below launch)
   }
   LaunchRecord rec(p, stream);
-  int rc = XHIST_OK;
-  // the routing pass keeps the digitize tables in LDS next to its sort buffers; where they do not fit (or cost a
-  // workgroup per CU) and the edges are arithmetic (C5: 2 x 1025 np.linspace edges, 32 KiB of tables) it
-  // digitizes table-free
-  const int scan = sc.scan;
-  const TableSet* tset = sc.tset;
-  int r_scan = scan;
-  const TableSet* r_tset = tset;
-  bool r_f32 = sc.use_f32;
-  const bool can_arith = p->arith && kn.arith_pref >= 0 && n_parts <= 128;
-  const int w_tag = weighted ? wdt : -1;
-  // geometry first: the long tile with the arithmetic digitize where the edges allow it, else with the tables if both
-  // fit the LDS, else the short tile
-  RouteGeom geom = route_geom_for(kn, sdt, w_tag, D, can_arith ? kScanArith : scan);
-  if (geom.spl == 8 && (can_arith || scan == kScanArith)) {
-    if (scan != kScanArith) {
-      r_scan = kScanArith;
-      r_tset = &p->ts[0][0];
-      r_f32 = false;
-    }
-  } else {
-    if (geom.spl == 8 && !kn.route_spl &&
-        part_route_lds((size_t)tset->words * 8, (int)n_parts, weighted, route_tile(geom.block, 8), geom.block) > p->lds_max)
-      geom.spl = 4;
-    if (can_arith && scan != kScanArith) {
-      const int t4 = route_tile(geom.block, geom.spl);
-      const size_t lds_tab = part_route_lds((size_t)tset->words * 8, (int)n_parts, weighted, t4, geom.block),
-                   lds_notab = part_route_lds(0, (int)n_parts, weighted, t4, geom.block);
-      if (lds_tab > p->lds_max || (size_t)160 * 1024 / lds_notab > (size_t)160 * 1024 / lds_tab) {
-        r_scan = kScanArith;
-        r_tset = &p->ts[0][0];
-        r_f32 = false;
-      }
-    }
-  }
-  // non-uniform edges: the packed entries (general variant) instead of a binary search or a 2-4-edge scan per sample and
-  // dimension — the routing pass feels its digitize (5*10^8 float64 pairs into 512 x 512 counts: linspace 2.07 ms, random
-  // edges 2.48, geometric 3.42; profiles/r04_l_*) — where entries and sort buffers fit the LDS together
-  {
-    const int pk_np = sdt == XHIST_F64 ? p->pk_np : (sdt == XHIST_F32 && sc.use_f32 ? p->pk32_np : 0);
-    if (pk_np && kn.pack_pref >= 0 && r_scan != kScanArith && (r_scan == 0 || r_scan >= 2 || kn.pack_pref > 0) && n_parts <= 128) {
-      const TableSet& pk = sdt == XHIST_F64 ? p->ts_pk : p->ts_pk32;
-      int spl = geom.spl;
-      if (spl == 8 && part_route_lds((size_t)pk.words * 8, (int)n_parts, weighted, route_tile(geom.block, 8), geom.block) > p->lds_max) spl = 4;
-      if (part_route_lds((size_t)pk.words * 8, (int)n_parts, weighted, route_tile(geom.block, spl), geom.block) <= p->lds_max &&
-          route_kernel(sdt, w_tag, D, kScanPackG, false, geom.block, spl)) {
-        r_scan = kScanPackG;
-        r_tset = &pk;
-        geom.spl = spl;
-      }
-    }
-  }
-  const int r_block = geom.block, r_tile = route_tile(r_block, geom.spl);
+  const PartCall pc{in.sdt, in.wdt, n_cols, shift, (int)n_parts, sc.scan, sc.use_f32, sc.tset, route_digitize(p, kn, in, sc, n_parts), &rec};
+  const int r_block = pc.route.geom.block, r_tile = route_tile(r_block, pc.route.geom.spl);
   // rows that follow each other at one stride go through the routing pass several at a time
   // (32 x 3*10^7 float32 pairs + weights, 300 x 300 bins: 8.05 -> 6.02 ms; 8 x 6*10^7 float64, 512 x 512: 5.17 -> 4.18;
   // rows of 5*10^8 samples gain nothing — 8.63 -> 8.95 ms with 128 partitions in flight — and stay one per pass)
@@ -1415,22 +1465,22 @@ static int execute_partitioned_rows(xhist_plan* p, const PlanKnobs& kn, const In
   // pool, lists, one partial chunk per workgroup and partition) show, and count + prefix + scatter is 9-15 % faster
   // (5*10^6: 0.155 | 0.132 ms, 10^7: 0.191 | 0.174, 2*10^7: 0.273 | 0.269: profiles/r03_h_fused_vs_three_pass_mid_sizes.txt);
   // every other dtype combination is ahead with one pass from 5*10^6 samples on
-  const bool three_pass = kn.fused_pref == 0 && kn.partition == 0 && n_rows == 1 && weighted && sdt == XHIST_F64 && wdt == XHIST_F64 && n_cols < 15000000;
+  const bool three_pass = kn.fused_pref == 0 && kn.partition == 0 && n_rows == 1 && weighted && in.sdt == XHIST_F64 && in.wdt == XHIST_F64 && n_cols < 15000000;
   const int fused_use = three_pass ? -1 : kn.fused_pref;
   bool uniform_rows = fused_use >= 0 && n_rows > 1 && n_parts * 2 <= 128 && n_cols < ((int64_t)1 << 27);
   for (int d = 0; d < in.n_arrays(); ++d) uniform_rows &= in.array(d).inner_rows == 0;
   xhist_array row_s[XHIST_MAX_DIMS], row_w;
   const xhist_array* row_wp = weighted ? &row_w : nullptr;
+  int rc = XHIST_OK;
   int64_t r = 0;
   while (uniform_rows && r < n_rows && rc == XHIST_OK) {
     int rows = (int)std::min<int64_t>(n_rows - r, 128 / n_parts);
-    const size_t tab_bytes = r_scan == kScanArith ? 0 : (size_t)r_tset->words * 8;
+    const size_t tab_bytes = pc.route.scan == kScanArith ? 0 : (size_t)pc.route.tset->words * 8;
     while (rows > 1 && part_route_lds(tab_bytes, rows * (int)n_parts, weighted, r_tile, r_block) > p->lds_max) --rows;
     if (rows < 2) break;  // (one row at a time below)
     row_views(in, r, row_s, row_w);
     void* row_out = static_cast<char*>(out) + (size_t)r * p->n_bins * 8;
-    rc = execute_partitioned_fused(p, row_s, row_wp, n_cols, row_out, stream, sdt, wdt, r_scan, r_f32, *r_tset, shift,
-                                   (int)n_parts, kn, rec, r == 0, r + rows == n_rows, geom, rows);
+    rc = execute_partitioned_fused(p, kn, pc, row_s, row_wp, row_out, stream, r == 0, r + rows == n_rows, rows);
     if (rc == XHIST_ERR_UNSUPPORTED) {
       if (r > 0) rc = fail(XHIST_ERR_HIP, "internal: partitioned mode refused rows from %lld after accepting row 0", (long long)r);
       else rc = XHIST_OK;  // nothing launched: row by row below
@@ -1443,12 +1493,9 @@ static int execute_partitioned_rows(xhist_plan* p, const PlanKnobs& kn, const In
     void* row_out = static_cast<char*>(out) + (size_t)r * p->n_bins * 8;
     // one routing pass (44 B per C5 sample) where it applies, else count + prefix + scatter (52.5 B); the
     // choice depends on the plan and the dtypes only, so every row of a call takes the same route
-    rc = fused_use >= 0 ? execute_partitioned_fused(p, row_s, row_wp, n_cols, row_out, stream, sdt, wdt, r_scan,
-                                                     r_f32, *r_tset, shift, (int)n_parts, kn, rec, r == 0, r == n_rows - 1, geom)
+    rc = fused_use >= 0 ? execute_partitioned_fused(p, kn, pc, row_s, row_wp, row_out, stream, r == 0, r == n_rows - 1)
                          : XHIST_ERR_UNSUPPORTED;
-    if (rc == XHIST_ERR_UNSUPPORTED)
-      rc = execute_partitioned(p, row_s, row_wp, n_cols, row_out, stream,
-                               sdt, wdt, scan, sc.use_f32, *tset, shift, (int)n_parts, kn, rec, r == 0, r == n_rows - 1);
+    if (rc == XHIST_ERR_UNSUPPORTED) rc = execute_partitioned(p, kn, pc, row_s, row_wp, row_out, stream, r == 0, r == n_rows - 1);
     if (rc == XHIST_ERR_UNSUPPORTED && r > 0) rc = fail(XHIST_ERR_HIP, "internal: partitioned mode refused row %lld after accepting row 0", (long long)r);
   }
   return rc;  // UNSUPPORTED (from row 0, nothing launched): the caller goes on to global atomics
@@ -1624,6 +1671,16 @@ static int launch_streaming(xhist_plan* p, const PlanKnobs& kn, const Inputs& in
   const int64_t n_rows = in.n_rows, n_cols = in.n_cols;
   const xhist_array *samples = in.samples, *weights = in.weights, *weights2 = in.weights2;
   const DimTable* dims = sc.tset->dim;
+  const int32_t table_words = (sc.scan == kScanArith || sc.scan == kScanArith32) ? 0 : sc.tset->words;  // arithmetic edges: nothing to stage
+  Params base = fill_params(samples, weights, D, *sc.tset, table_words, n_rows, n_cols, p->n_bins, out);
+  base.tables_in_lds = sc.tables_in_lds ? 1 : 0;
+  base.copies_log2 = sc.cl2;
+  base.direct_store = g.direct ? 1 : 0;
+  if (in.two) {
+    base.w2_rs = weights2->row_stride;
+    base.w2_ir = weights2->inner_rows;
+    base.w2_os = weights2->outer_stride;
+  }
   HIPC(set_dynamic_lds((const void*)sc.fn, sc.lds_bytes));
   if (!accumulate && !g.direct && !in.two)
     if (int zrc = zero_output(out, n_rows * p->n_bins, stream)) return zrc;
@@ -1637,44 +1694,17 @@ static int launch_streaming(xhist_plan* p, const PlanKnobs& kn, const Inputs& in
       int64_t segs = std::max<int64_t>(1, std::min<int64_t>(tpr, (g.target + (n_rows - r0) - 1) / (n_rows - r0)));
       if (!g.exact && !kn.grid_blocks && segs > 1 && (segs & 1) && segs + 1 <= tpr) ++segs;  // oversubscribed rows: an even number each
       const int64_t nr = std::min<int64_t>(n_rows - r0, kMaxGrid / segs);
-      Params kp;
-      memset(&kp, 0, sizeof kp);
-      for (int d = 0; d < D; ++d) {
-        const xhist_array& a = samples[d];
-        kp.s_ptr[d] = advance(a.data, a.dtype, c0 * a.col_stride);
-        kp.s_rs[d] = a.row_stride;
-        kp.s_cs[d] = a.col_stride;
-        kp.s_ir[d] = a.inner_rows;
-        kp.s_os[d] = a.outer_stride;
-        kp.s_dt[d] = a.dtype;
-        kp.dim[d] = dims[d];
-      }
-      if (in.weighted) {
-        kp.w_ptr = advance(weights->data, weights->dtype, c0 * weights->col_stride);
-        kp.w_rs = weights->row_stride;
-        kp.w_cs = weights->col_stride;
-        kp.w_ir = weights->inner_rows;
-        kp.w_os = weights->outer_stride;
-        kp.w_dt = weights->dtype;
-      }
+      Params kp = base;
+      for (int d = 0; d < D; ++d) kp.s_ptr[d] = advance(samples[d].data, samples[d].dtype, c0 * samples[d].col_stride);
+      if (in.weighted) kp.w_ptr = advance(weights->data, weights->dtype, c0 * weights->col_stride);
       if (in.two) {
         kp.w2_ptr = advance(weights2->data, weights2->dtype, c0);
-        kp.w2_rs = weights2->row_stride;
-        kp.w2_ir = weights2->inner_rows;
-        kp.w2_os = weights2->outer_stride;
         kp.out2 = static_cast<char*>(out2) + (size_t)r0 * p->n_bins * 8;
       }
       kp.row0 = r0;
-      kp.n_dims = D;
-      kp.tables = sc.tset->blob;
-      kp.table_words = (sc.scan == kScanArith || sc.scan == kScanArith32) ? 0 : sc.tset->words;  // arithmetic edges: nothing to stage
-      kp.tables_in_lds = sc.tables_in_lds ? 1 : 0;
       kp.n_rows = nr;
       kp.n_cols = nc;
-      kp.n_bins = p->n_bins;
       kp.out = static_cast<char*>(out) + (size_t)r0 * p->n_bins * 8;
-      kp.copies_log2 = sc.cl2;
-      kp.direct_store = g.direct ? 1 : 0;
       kp.segs = (int32_t)segs;
       const dim3 grid((unsigned)(nr * segs));
       if (first_launch)
@@ -1738,7 +1768,7 @@ static int execute_device(xhist_plan* p, const xhist_array* samples, const xhist
 
   // ---- many short rows / leading-axis reductions: one row per lane (xhist_lanes.hip.h) --------
   if (kn.lanes >= 0 && !kn.force_generic && !kn.force_global && !two) {
-    const int rc = execute_lanes(p, samples, weights, n_rows, n_cols, out, accumulate, stream, kn);
+    const int rc = execute_lanes(p, kn, in, out, accumulate, stream);
     if (rc != XHIST_ERR_UNSUPPORTED) return rc;  // UNSUPPORTED = not this shape, fall through
   }
   // (the output is zeroed further down, once the launch geometry says whether it has to be at all)
