@@ -72,9 +72,9 @@ int xhist_extrema_run(const ValuesPlan& pl, const xhist_array* samples, const xh
                                     stream, err, err_cap))
       return rc;
     if (desc && desc_cap)
-      snprintf(desc, desc_cap, "extrema family=%s slots=%s scan=%d block=%d segs=%lld lds_bytes=%zu tables_in_lds=%d D=%d",
+      snprintf(desc, desc_cap, "extrema family=%s slots=%s scan=%d block=%d segs=%lld lds_bytes=%zu tables_in_lds=%d D=%d cmp=%d",
                c.fast ? "fast" : "generic", c.lds ? "lds" : "global", c.scan, g.block, (long long)g.segs, c.lds_bytes[0],
-               (int)c.tables_in_lds, pl.n_dims);
+               (int)c.tables_in_lds, pl.n_dims, values_cmp(pl));
   }
   XH_VALUES_LAUNCH(extrema_finalize, dim3(grid_io), dim3(256), 0, stream, kmin, kmax, n_out);
   XH_VALUES_LAUNCH_CHECK("extrema_finalize launch");

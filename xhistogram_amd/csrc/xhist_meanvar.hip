@@ -101,9 +101,9 @@ int xhist_meanvar_run(const ValuesPlan& pl, const xhist_array* samples, const xh
     const char* home = !sum ? "none" : c.lds ? "lds" : "global";
     snprintf(desc, desc_cap,
              "mean_var pass1=mv_sum_%s slots=%s pass2=mv_dev_%s slots=%s scan=%d copies=%d block=%d segs=%lld lds_bytes=%zu/%zu "
-             "tables_in_lds=%d D=%d",
+             "tables_in_lds=%d D=%d cmp=%d",
              fam, home, fam, home, c.scan, 1 << c.copies_log2, g.block, (long long)g.segs, c.lds_bytes[0], c.lds_bytes[1],
-             (int)c.tables_in_lds, pl.n_dims);
+             (int)c.tables_in_lds, pl.n_dims, values_cmp(pl));
   }
   return XHIST_OK;
 }

@@ -294,6 +294,9 @@ static values_fn fast_scan(int scan) {
   if (scan == kScanArith) return K::template fast<ST, D, kScanArith>();
   return nullptr;
 }
+// the compare domain of the generic family's kernels for a plan (0 float64, 1 int64, 3 per input), as describe() names it
+static inline int values_cmp(const ValuesPlan& pl) { return pl.cmp == XHIST_CMP_F64 ? 0 : pl.cmp == XHIST_CMP_I64 ? 1 : 3; }
+
 template <class K>
 static values_fn pick_values_kernel(const ValuesChoice& c, const ValuesPlan& pl) {
   if (c.fast) {
@@ -327,7 +330,9 @@ static inline ValuesGeometry values_geometry(const ValuesPlan& pl, const ValuesC
   // guard changes only the grid (and describe()'s segs), never the result.  It moves segs for rows longer than 2^31 samples
   // once the rows alone fill the device (n_rows >= cus * bpc, segs 1), e.g. rows broadcast at row stride 0.
   g.segs = std::max<int64_t>(g.segs, (tiles * per_tile + ((int64_t)1 << 31) - 1) >> 31);
-  g.max_rows = (((int64_t)1 << 31) - 1) / g.segs;
+  // A launch's grid counts its work-items in 32 bits: a grid of 2^31 - 1 workgroups of 256 lanes wraps to 2^24 - 1 of them, and
+  // the rows past those were never binned.  So a chunk of rows keeps both the workgroups below 2^31 and the lanes below 2^32.
+  g.max_rows = std::min<int64_t>(((int64_t)1 << 31) - 1, (((int64_t)1 << 32) - 1) / g.block) / g.segs;
   return g;
 }
 
@@ -338,7 +343,7 @@ static int allow_values_lds(values_fn fn, size_t lds, const char* what, char* er
   return e == hipSuccess ? XHIST_OK : values_error(err, err_cap, XHIST_ERR_HIP, what, e);
 }
 
-// One binning pass: the launches of row chunks of at most g.max_rows (the grid stays below 2^31 workgroups).  out / out2 / in2 are [n_rows, n_bins] arrays of 8-byte elements,
+// One binning pass: the launches of row chunks of at most g.max_rows (the grid stays below 2^31 workgroups and 2^32 lanes).  out / out2 / in2 are [n_rows, n_bins] arrays of 8-byte elements,
 // advanced to each chunk's first row (Params::out, out2 and w2_ptr); `what` names the pass in error messages.
 static int launch_values_pass(values_fn fn, size_t lds, const char* what, const ValuesPlan& pl,
                               const ValuesChoice& c, const ValuesGeometry& g, const xhist_array* samples, const xhist_array* values,
