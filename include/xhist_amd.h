@@ -160,6 +160,26 @@ int xhist_plan_execute_mean_var(xhist_plan* plan, const xhist_array* samples, co
                                 int64_t n_rows, int64_t n_cols, int64_t* out_count, double* out_mean, double* out_m2,
                                 int mem_kind, void* stream);
 
+/* Per-bin quantiles of `values`, exact: every output element is what np.nanquantile(values of that bin as float64, q[i],
+ * method=...) gives, bit for bit, NaN for a bin with no value.  Which samples count is exactly what xhist_plan_execute counts
+ * (same digitize, last bin closed, NaN / out-of-range samples dropped); NaN values are ignored.  Rows of at most 4096 values
+ * are sorted in LDS, a few whole rows per workgroup; longer rows take an exact radix select on order-preserving keys of the
+ * values, in a fixed number of streaming passes, its working state in row chunks of at most 256 MiB (one row at least).
+ *   values: an xhist_array of any real dtype, same logical [n_rows, n_cols] shape as the samples (strides 0 broadcast).
+ *   q: HOST array of n_q values in [0, 1] (not checked here); method: one of the XHIST_Q_* codes (numpy's method names).
+ *   out: contiguous float64 [n_q, n_rows, prod(nb_d)] DEVICE buffer, overwritten.  Scratch comes from the library's allocator.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Asynchronous on `stream`, no host synchronisation.  xhist_plan_describe then names the family, the kernel family and home
+ *   of the passes, the digit width d, the number of passes and the row chunks. */
+#define XHIST_Q_LINEAR 0
+#define XHIST_Q_LOWER 1
+#define XHIST_Q_HIGHER 2
+#define XHIST_Q_MIDPOINT 3
+#define XHIST_Q_NEAREST 4
+int xhist_plan_execute_quantile(xhist_plan* plan, const xhist_array* samples, const xhist_array* values,
+                                int64_t n_rows, int64_t n_cols, const double* q, int n_q, int method, double* out,
+                                int mem_kind, void* stream);
+
 /* One-shot form of the two calls above with an internal plan cache keyed on (device, edges). */
 int xhist_bincount_rows(int device, int n_inputs, const xhist_array* samples,
                         const xhist_array* weights, int64_t n_rows, int64_t n_cols,

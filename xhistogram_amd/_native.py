@@ -69,7 +69,7 @@ _lock = threading.Lock()
 EXPORTS = (
     "xhist_abi_version", "xhist_last_error", "xhist_device_count", "xhist_device_info",
     "xhist_plan_create", "xhist_plan_destroy", "xhist_plan_execute", "xhist_plan_execute_two_weights", "xhist_plan_execute_extrema",
-    "xhist_plan_execute_mean_var",
+    "xhist_plan_execute_mean_var", "xhist_plan_execute_quantile",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -139,6 +139,10 @@ def load():
         lib.xhist_plan_execute_mean_var.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_int, C.c_void_p,
+        ]
+        lib.xhist_plan_execute_quantile.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int,
+            C.c_void_p, C.c_int, C.c_void_p,
         ]
         lib.xhist_bincount_rows.argtypes = [
             C.c_int, C.c_int, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_void_p),
@@ -369,6 +373,23 @@ class Plan:
             )
         )
 
+
+    def execute_quantile(self, sample_views, value_view, n_rows, n_cols, out_ptr, q, method, stream=0):
+        """per-bin quantiles q (host float64 values in [0, 1]) of the values of device-resident views by numpy's `method` code
+        (QUANTILE_METHODS index; NaN where no value arrived), into a float64 device buffer [len(q), n_rows, bins], asynchronous
+        on `stream` (xhist_plan_execute_quantile)"""
+        arr = self._sample_array(sample_views)
+        qa = np.ascontiguousarray(q, dtype=np.float64).ravel()
+        check(
+            load().xhist_plan_execute_quantile(
+                self._h, arr, C.byref(value_view), int(n_rows), int(n_cols), qa.ctypes.data_as(C.POINTER(C.c_double)), int(qa.size),
+                int(method), C.c_void_p(out_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
+            )
+        )
+
+
+# numpy's classic quantile methods in the order of the XHIST_Q_* codes of include/xhist_amd.h
+QUANTILE_METHODS = ("linear", "lower", "higher", "midpoint", "nearest")
 
 def minmax(view, n_rows, n_cols, mem_kind, device=0, stream=0):
     out = (C.c_double * 2)()

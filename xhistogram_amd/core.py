@@ -33,7 +33,7 @@ from .devicearray import DeviceArray, _nocopy_reshape_strides
 # range is a keyword of histogram(), like in the reference
 _range = range
 
-__all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var"]
+__all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2086,3 +2086,94 @@ _VALUE_STATS = {
     "extrema": _ValueStat(2, False, "execute_extrema", _extrema_pair_reduce),
     "mean_var": _ValueStat(3, True, "execute_mean_var", _mean_var_reduce),
 }
+
+
+# ---------------------------------------------------------------------------------------------
+# per-bin quantiles of a value array
+# ---------------------------------------------------------------------------------------------
+def _check_quantile_args(q, method):
+    """(q as a 1-D float64 array, whether q was a scalar, the method's code), checked as np.nanquantile checks them"""
+    if method not in _native.QUANTILE_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (", ".join(repr(m) for m in _native.QUANTILE_METHODS), method))
+    qa = np.asanyarray(q)
+    if qa.dtype.kind == "c" or qa.dtype.kind not in "fiub":
+        raise TypeError("q must be a float or a 1-D array-like of floats, got dtype %s" % qa.dtype)
+    if qa.ndim > 1:
+        raise ValueError("q must be a float or a 1-D array-like, got %d dimensions" % qa.ndim)
+    qf = qa.astype(np.float64).ravel()
+    if not (np.all(qf >= 0) and np.all(qf <= 1)):  # (NaN fails both)
+        raise ValueError("Quantiles must be in the range [0, 1]")
+    return qf, qa.ndim == 0, _native.QUANTILE_METHODS.index(method)
+
+
+def _quantile_rows(args, values, axis, bins, backend, q, code):
+    """[len(q), kept axes (reduced ones of extent 1), bins...] float64 quantiles of broadcast torch tensors (torch out) or
+    DeviceArrays (numpy out)"""
+    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend)
+    n = m * plan.n_bins
+    shape = (len(q),) + kept_axes_shape + plan.bins_shape
+    if backend == "torch":
+        out = _torch().empty(shape, dtype=_torch().float64, device=args[0].device)
+        if n > 0 and len(q):
+            plan.execute_quantile(nv[:-1], nv[-1], m, c, out.data_ptr(), q, code, stream=stream)
+        return out
+    host = np.empty(shape, np.float64)
+    if n > 0 and len(q):
+        buf = _native.DeviceBuffer(device, len(q) * n * 8)
+        plan.execute_quantile(nv[:-1], nv[-1], m, c, buf.ptr, q, code, stream=stream)
+        buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+    return host
+
+
+def _quantile_block(*all_arrays, axis=None, bins=None, q=None, code=0):
+    """one dask block, complete along the reduced axes: its quantiles [len(q), block axes (reduced ones of extent 1), bins...]"""
+    arrays = _upload_host(all_arrays[:-1], all_arrays[-1], bins)
+    return _quantile_rows(arrays[:-1], arrays[-1], axis, bins, "device", q, code)
+
+
+def histogram_quantile(*args, values, q, bins=None, range=None, axis=None, method="linear", block_size="auto", weights=None,
+                       density=None):
+    """Per-bin quantiles of ``values``, computed exactly on an MI355X: every element is what
+    ``np.nanquantile(values_in_that_bin.astype(np.float64), q, method=method)`` gives, bit for bit (``method="linear"`` with
+    ``q=0.5`` is ``scipy.stats.binned_statistic``'s ``"median"``).  A bin with no non-NaN value gives NaN.
+
+    ``args``, ``bins``, ``range``, ``axis`` and ``values`` are those of :func:`histogram_mean_var`: a sample counts when
+    ``histogram`` counts it and its value is not NaN; the edges are those of the unweighted ``histogram``.  ``q`` is a float or a
+    1-D array-like in [0, 1] (taken as float64), ``method`` one of ``"linear"``, ``"lower"``, ``"higher"``, ``"midpoint"``,
+    ``"nearest"``.  ``weights`` and ``density`` are not supported.  ``block_size`` is accepted and changes nothing.
+
+    Rows of at most 4096 values are sorted in LDS; longer rows take an exact radix select over order-preserving keys of the
+    values in a fixed number of streaming passes (about 9 for float64 values).
+
+    Returns ``(quantiles, bin_edges)``: float64 with the shape ``histogram`` gives (kept axes, then bin axes), behind a leading
+    ``len(q)`` axis when ``q`` is 1-D (numpy's convention).  numpy in -> numpy out, torch in -> torch out on the same device
+    (asynchronous on the current stream), DeviceArray in -> numpy out, dask in -> a lazy dask array, one task per block: every
+    reduced axis must then be a single chunk."""
+    if weights is not None:
+        raise TypeError("histogram_quantile does not take weights: weighted quantiles are not supported")
+    if density is not None:
+        raise TypeError("histogram_quantile does not take density")
+    qf, scalar, code = _check_quantile_args(q, method)
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_quantile")
+    n_inputs = len(args)
+    lead = (0,) if scalar else ()
+    if backend == "dask":
+        for a in all_arrays:
+            if any(len(a.chunks[ax]) > 1 for ax in drop_axes):
+                raise ValueError("exact quantiles of several chunks cannot be merged: rechunk the reduced axes of every input into "
+                                 "one chunk (e.g. arr.rechunk({axis: -1}))")
+        res = _values_blockwise(partial(_quantile_block, q=qf, code=code), len(qf), all_arrays, bins, axis, drop_axes)
+        res = res[(slice(None),) + tuple(0 if i in drop_axes else slice(None) for i in _range(all_arrays[0].ndim))]
+        return (res[0] if scalar else res), bins
+    if backend == "numpy":
+        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins)
+        out = _quantile_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, "device", qf, code)
+    else:
+        out = _quantile_rows(all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend, qf, code)
+    squeeze = tuple(a + 1 for a in drop_axes)
+    if backend == "torch":
+        keep = [s for i, s in enumerate(out.shape) if i - 1 not in drop_axes]
+        out = out.reshape(keep)
+        return (out[0] if scalar else out), bins
+    out = out.squeeze(squeeze)
+    return (out[0] if scalar else out), bins

@@ -5,6 +5,7 @@
 #include "xhist_pick.hip.h"
 #include "xhist_extrema.hip.h"
 #include "xhist_meanvar.hip.h"
+#include "xhist_quantile.hip.h"
 
 #include <dlfcn.h>
 
@@ -251,7 +252,7 @@ extern "C" int xhist_plan_execute_two_weights(xhist_plan* p, const xhist_array* 
 
 // ------------------------------------------------------------------------------------------
 // per-bin statistics of a value array: minimum and maximum (xhist_extrema.hip), count, mean and sum of squared deviations
-// (xhist_meanvar.hip); the choice and the launches they share: xhist_values.hip.h
+// (xhist_meanvar.hip), quantiles (xhist_quantile.hip); the choice and the launches they share: xhist_values.hip.h
 // ------------------------------------------------------------------------------------------
 void xhist_log_picked_kernel(const void* fn) { log_picked_kernel(fn); }
 
@@ -319,6 +320,23 @@ extern "C" int xhist_plan_execute_mean_var(xhist_plan* p, const xhist_array* sam
                           }
                           return xhist_meanvar_run(pl, samples, values, n_rows, n_cols, out_count, out_mean, out_m2, sd, s, err, err_cap,
                                                    desc, desc_cap);
+                        });
+}
+
+extern "C" int xhist_plan_execute_quantile(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                                           int64_t n_cols, const double* q, int n_q, int method, double* out, int mem_kind, void* stream) {
+  if (n_q < 1 || !q) return fail(XHIST_ERR_INVALID, "q is NULL or n_q < 1");
+  if (method < XHIST_Q_LINEAR || method > XHIST_Q_NEAREST) return fail(XHIST_ERR_INVALID, "unknown quantile method %d", method);
+  return execute_values(p, "xhist_plan_execute_quantile", samples, values, n_rows, n_cols, out, true, "", mem_kind,
+                        [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
+                          hipStream_t s = static_cast<hipStream_t>(stream);
+                          ScratchScope scratch(s);
+                          auto alloc = [](void* ctx, size_t bytes) -> void* {
+                            void* d = nullptr;
+                            return static_cast<ScratchScope*>(ctx)->alloc(&d, bytes ? bytes : 8) == hipSuccess ? d : nullptr;
+                          };
+                          return xhist_quantile_run(pl, samples, values, n_rows, n_cols, q, n_q, method, out, alloc, &scratch, s, err,
+                                                    err_cap, desc, desc_cap);
                         });
 }
 

@@ -343,6 +343,40 @@ static int allow_values_lds(values_fn fn, size_t lds, const char* what, char* er
   return e == hipSuccess ? XHIST_OK : values_error(err, err_cap, XHIST_ERR_HIP, what, e);
 }
 
+// The Params of a launch over rows [r0, r0 + nr) of the inputs: samples, values, tables and geometry; the outputs (out, out2,
+// w2_ptr) are the caller's to set.
+static inline Params values_params(const ValuesPlan& pl, const ValuesChoice& c, int64_t segs, const xhist_array* samples,
+                                   const xhist_array* values, int64_t r0, int64_t nr, int64_t n_cols) {
+  Params kp;
+  memset(&kp, 0, sizeof kp);
+  for (int d = 0; d < pl.n_dims; ++d) {
+    kp.s_ptr[d] = samples[d].data;
+    kp.s_rs[d] = samples[d].row_stride;
+    kp.s_cs[d] = samples[d].col_stride;
+    kp.s_ir[d] = samples[d].inner_rows;
+    kp.s_os[d] = samples[d].outer_stride;
+    kp.s_dt[d] = samples[d].dtype;
+    kp.dim[d] = c.tab->dim[d];
+  }
+  kp.w_ptr = values->data;
+  kp.w_rs = values->row_stride;
+  kp.w_cs = values->col_stride;
+  kp.w_ir = values->inner_rows;
+  kp.w_os = values->outer_stride;
+  kp.w_dt = values->dtype;
+  kp.row0 = r0;
+  kp.n_dims = pl.n_dims;
+  kp.tables = c.tab->blob;
+  kp.table_words = c.table_words;
+  kp.tables_in_lds = c.tables_in_lds ? 1 : 0;
+  kp.n_rows = nr;
+  kp.n_cols = n_cols;
+  kp.n_bins = pl.n_bins;
+  kp.segs = (int32_t)segs;
+  kp.copies_log2 = c.copies_log2;
+  return kp;
+}
+
 // One binning pass: the launches of row chunks of at most g.max_rows (the grid stays below 2^31 workgroups and 2^32 lanes).  out / out2 / in2 are [n_rows, n_bins] arrays of 8-byte elements,
 // advanced to each chunk's first row (Params::out, out2 and w2_ptr); `what` names the pass in error messages.
 static int launch_values_pass(values_fn fn, size_t lds, const char* what, const ValuesPlan& pl,
@@ -351,36 +385,10 @@ static int launch_values_pass(values_fn fn, size_t lds, const char* what, const 
                               size_t err_cap) {
   for (int64_t r0 = 0; r0 < n_rows; r0 += g.max_rows) {
     const int64_t nr = std::min(g.max_rows, n_rows - r0);
-    Params kp;
-    memset(&kp, 0, sizeof kp);
-    for (int d = 0; d < pl.n_dims; ++d) {
-      kp.s_ptr[d] = samples[d].data;
-      kp.s_rs[d] = samples[d].row_stride;
-      kp.s_cs[d] = samples[d].col_stride;
-      kp.s_ir[d] = samples[d].inner_rows;
-      kp.s_os[d] = samples[d].outer_stride;
-      kp.s_dt[d] = samples[d].dtype;
-      kp.dim[d] = c.tab->dim[d];
-    }
-    kp.w_ptr = values->data;
-    kp.w_rs = values->row_stride;
-    kp.w_cs = values->col_stride;
-    kp.w_ir = values->inner_rows;
-    kp.w_os = values->outer_stride;
-    kp.w_dt = values->dtype;
+    Params kp = values_params(pl, c, g.segs, samples, values, r0, nr, n_cols);
     kp.w2_ptr = in2 ? static_cast<const uint64_t*>(in2) + r0 * pl.n_bins : nullptr;
-    kp.row0 = r0;
-    kp.n_dims = pl.n_dims;
-    kp.tables = c.tab->blob;
-    kp.table_words = c.table_words;
-    kp.tables_in_lds = c.tables_in_lds ? 1 : 0;
-    kp.n_rows = nr;
-    kp.n_cols = n_cols;
-    kp.n_bins = pl.n_bins;
     kp.out = static_cast<uint64_t*>(out) + r0 * pl.n_bins;
     kp.out2 = static_cast<uint64_t*>(out2) + r0 * pl.n_bins;
-    kp.segs = (int32_t)g.segs;
-    kp.copies_log2 = c.copies_log2;
     XH_VALUES_LAUNCH(fn, dim3((unsigned)(nr * g.segs)), dim3(g.block), lds, stream, kp);
     XH_VALUES_LAUNCH_CHECK(what);
   }
