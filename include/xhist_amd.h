@@ -160,6 +160,23 @@ int xhist_plan_execute_mean_var(xhist_plan* plan, const xhist_array* samples, co
                                 int64_t n_rows, int64_t n_cols, int64_t* out_count, double* out_mean, double* out_m2,
                                 int mem_kind, void* stream);
 
+/* Per-bin sum of weights, weighted mean and weighted sum of squared deviations of `values` (added within ABI v11): which
+ * samples count is exactly what xhist_plan_execute_mean_var counts; each counted sample whose value is not NaN contributes the
+ * pair (w, v), both converted to float64 (frequency weights).  Two passes: W = sum(w) and S = sum(w*v), then d = v - S/W in
+ * float64 and M2 = max(0, sum(w*d*d) - sum(w*d)^2 / W).  mean = S/W and M2 are NaN where W == 0 (empty bins, and bins whose
+ * weights sum to 0); a NaN weight makes its bin's W, mean and M2 NaN.  Negative weights are not checked: the formulas apply,
+ * the clamp of M2 at 0 included.  The variance is M2 / (W - ddof), left to the caller.  Float64 atomics add in arbitrary
+ * order: the last bits can differ between runs, except for data whose sums are exact in every order.
+ *   values, weights: xhist_arrays of any real dtype, same logical [n_rows, n_cols] shape as the samples (strides 0 broadcast).
+ *   out_wsum, out_mean, out_m2 (float64): contiguous [n_rows, prod(nb_d)] DEVICE buffers, overwritten (no accumulate mode);
+ *   one float64 scratch block of that size is taken for the call.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Asynchronous on `stream`.  xhist_plan_describe then names the kernel family of each pass and where its slots live
+ *   ("mean_var_w pass1=mvw_sum_..."). */
+int xhist_plan_execute_mean_var_weighted(xhist_plan* plan, const xhist_array* samples, const xhist_array* values,
+                                         const xhist_array* weights, int64_t n_rows, int64_t n_cols, double* out_wsum,
+                                         double* out_mean, double* out_m2, int mem_kind, void* stream);
+
 /* Per-bin quantiles of `values`, exact: every output element is what np.nanquantile(values of that bin as float64, q[i],
  * method=...) gives, bit for bit, NaN for a bin with no value.  Which samples count is exactly what xhist_plan_execute counts
  * (same digitize, last bin closed, NaN / out-of-range samples dropped); NaN values are ignored.  Rows of at most 4096 values

@@ -69,7 +69,7 @@ _lock = threading.Lock()
 EXPORTS = (
     "xhist_abi_version", "xhist_last_error", "xhist_device_count", "xhist_device_info",
     "xhist_plan_create", "xhist_plan_destroy", "xhist_plan_execute", "xhist_plan_execute_two_weights", "xhist_plan_execute_extrema",
-    "xhist_plan_execute_mean_var", "xhist_plan_execute_quantile",
+    "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -139,6 +139,10 @@ def load():
         lib.xhist_plan_execute_mean_var.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_int, C.c_void_p,
+        ]
+        lib.xhist_plan_execute_mean_var_weighted.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
         ]
         lib.xhist_plan_execute_quantile.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int,
@@ -370,6 +374,19 @@ class Plan:
             load().xhist_plan_execute_mean_var(
                 self._h, arr, C.byref(value_view), int(n_rows), int(n_cols), C.c_void_p(out_count_ptr), C.c_void_p(out_mean_ptr),
                 C.c_void_p(out_m2_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
+            )
+        )
+
+    def execute_mean_var_weighted(self, sample_views, value_view, weight_view, n_rows, n_cols, out_wsum_ptr, out_mean_ptr, out_m2_ptr,
+                                  stream=0):
+        """per-bin sum of weights W, weighted mean and weighted sum of squared deviations M2 (float64 each; mean and M2 NaN
+        where W == 0) of the values of device-resident views, into device buffers of [n_rows, bins] each, asynchronous on
+        `stream` (xhist_plan_execute_mean_var_weighted)"""
+        arr = self._sample_array(sample_views)
+        check(
+            load().xhist_plan_execute_mean_var_weighted(
+                self._h, arr, C.byref(value_view), C.byref(weight_view), int(n_rows), int(n_cols), C.c_void_p(out_wsum_ptr),
+                C.c_void_p(out_mean_ptr), C.c_void_p(out_m2_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
             )
         )
 

@@ -1785,20 +1785,21 @@ def _check_values_dtype(values, name="histogram_extrema"):
         raise TypeError("%s takes real values, got dtype %s" % (name, dt))
 
 
-def _upload_host(args, values, bins):
-    """host (numpy) samples and values as DeviceArrays on the calling thread's GPU, broadcast there (stride 0, not copied)"""
+def _upload_host(args, values, bins, weights=None):
+    """host (numpy) samples and values (and weights, if given) as DeviceArrays on the calling thread's GPU, broadcast there
+    (stride 0, not copied)"""
     args = [np.asarray(a) for a in args]
     args, _ = _prepare_dtypes(args, None, [a.dtype for a in args], bins, "numpy")
     dev = _host_device()
     _native.require_device(dev)
-    arrays = [DeviceArray.from_numpy(a, dev) for a in args + [np.asarray(values)]]
+    arrays = [DeviceArray.from_numpy(a, dev) for a in args + [np.asarray(values)] + ([] if weights is None else [np.asarray(weights)])]
     shape = np.broadcast_shapes(*[a.shape for a in arrays])
     return [a.broadcast_to(shape) for a in arrays]
 
 
-def _value_views(args, values, axis, bins, backend):
-    """the [rows, cols] views of broadcast torch tensors or DeviceArrays and of their values, for a per-bin statistic of the
-    values: (plan, native views (samples..., values), the views they were made of (their copies, if any, must outlive the
+def _value_views(args, values, axis, bins, backend, weights=None):
+    """the [rows, cols] views of broadcast torch tensors or DeviceArrays and of their values (and weights, if given), for a
+    per-bin statistic of the values: (plan, native views (samples..., values[, weights]), the views they were made of (their copies, if any, must outlive the
     kernels: callers hold them until the download), rows, cols, kept axes shape, device, stream).  The kept axes stay in
     place and the reduced ones have extent 1 (then come the bin axes).  The views are those of _bincount's block adapter;
     layouts no three strides describe are copied."""
@@ -1810,7 +1811,7 @@ def _value_views(args, values, axis, bins, backend):
     cmp_domain, edges, common = _compare_domain(dtypes, bins)
     if backend == "device" and any(c is not None and a.dtype != c for a, c in zip(args, common)):
         raise TypeError("datetime64 DeviceArrays must already have the unit they share with their bin edges")
-    arrays = list(args) + [values]
+    arrays = list(args) + [values] + ([] if weights is None else [weights])
     order = _reduced_order(arrays[0], list(_range(ndim)) if do_full_array else axis)
     descs = [_collapse(a, axis, do_full_array, order) for a in arrays]
     views = None
@@ -1838,15 +1839,15 @@ def _value_views(args, values, axis, bins, backend):
 
 
 # What the shared paths need of a per-bin statistic of values: its number of outputs (the first an int64 count when
-# `counted`, all others float64), the Plan method that fills them from output pointers, and the dask step that merges the
-# partials of blocks that share output rows.
-_ValueStat = namedtuple("_ValueStat", "k counted method reduce")
+# `counted`, all others float64), the Plan method that fills them from output pointers, the dask step that merges the
+# partials of blocks that share output rows, and whether it reads weights after the values.
+_ValueStat = namedtuple("_ValueStat", "k counted method reduce weighted", defaults=(False,))
 
 
-def _value_stat_rows(stat, args, values, axis, bins, backend):
+def _value_stat_rows(stat, args, values, axis, bins, backend, weights=None):
     """the statistic's outputs of broadcast torch tensors or DeviceArrays: kept axes in place, reduced axes of extent 1, then
     the bin axes"""
-    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend)
+    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, weights)
     n = m * plan.n_bins
     k, counted = stat.k, int(stat.counted)
     if backend == "torch":
@@ -1858,7 +1859,7 @@ def _value_stat_rows(stat, args, values, axis, bins, backend):
         buf = _native.DeviceBuffer(device, max(k * n, 1) * 8)
         ptrs = [buf.ptr + i * n * 8 for i in _range(k)]
     if n > 0:
-        getattr(plan, stat.method)(nv[:-1], nv[-1], m, c, *ptrs, stream=stream)
+        getattr(plan, stat.method)(nv[:len(args)], *nv[len(args):], m, c, *ptrs, stream=stream)
     if backend != "torch":
         host = np.empty((k, n), np.float64)
         if n > 0:
@@ -1870,15 +1871,17 @@ def _value_stat_rows(stat, args, values, axis, bins, backend):
 
 def _value_stat_block(*all_arrays, stat=None, axis=None, bins=None):
     """one dask block: its statistic as a [k, block axes (reduced ones of extent 1), bins...] float64 numpy array"""
-    arrays = _upload_host(all_arrays[:-1], all_arrays[-1], bins)
-    outs = _value_stat_rows(_VALUE_STATS[stat], arrays[:-1], arrays[-1], axis, bins, "device")
+    st = _VALUE_STATS[stat]
+    n = len(all_arrays) - 1 - int(st.weighted)  # (samples..., values[, weights])
+    arrays = _upload_host(all_arrays[:n], all_arrays[n], bins, *all_arrays[n + 1:])
+    outs = _value_stat_rows(st, arrays[:n], arrays[n], axis, bins, "device", *arrays[n + 1:])
     return np.stack([a.astype(np.float64, copy=False) for a in outs])
 
 
-def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None):
+def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, weights=None):
     """the backends of a per-bin statistic of values: (backend, the outputs with the shape ``histogram`` gives, bin edges,
     reduced axes).  dask: lazy float64 arrays, the partials merged by stat.reduce and the last step by `aggregate`."""
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name)
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, weights)
     n_inputs = len(args)
     st = _VALUE_STATS[stat]
     if backend == "dask":
@@ -1889,10 +1892,10 @@ def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None):
                             keepdims=False, dtype=np.float64, concatenate=True, meta=np.array((), np.float64))
         return backend, [res[i] for i in _range(st.k)], bins, drop_axes
     if backend == "numpy":
-        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins)
-        outs = _value_stat_rows(st, arrays[:n_inputs], arrays[n_inputs], axis, bins, "device")
+        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins, *raw[n_inputs + 1:])
+        outs = _value_stat_rows(st, arrays[:n_inputs], arrays[n_inputs], axis, bins, "device", *arrays[n_inputs + 1:])
     else:
-        outs = _value_stat_rows(st, all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend)
+        outs = _value_stat_rows(st, all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend, *all_arrays[n_inputs + 1:])
     if backend == "torch":
         keep = [s for i, s in enumerate(outs[0].shape) if i not in drop_axes]
         return backend, [a.reshape(keep) for a in outs], bins, drop_axes
@@ -1918,18 +1921,20 @@ def histogram_extrema(*args, values, bins=None, range=None, axis=None, block_siz
     return vmin, vmax, bins
 
 
-def _values_call(args, values, bins, range, axis, name):
+def _values_call(args, values, bins, range, axis, name, weights=None):
     """the front of a per-bin statistic of values: argument checks before any device work, the backend, the broadcast
-    arrays (samples..., values), the numpy originals (numpy backend), the edges of the unweighted histogram, the normalised
-    axis and the reduced axes"""
+    arrays (samples..., values[, weights]), the numpy originals (numpy backend), the edges of the unweighted histogram, the
+    normalised axis and the reduced axes"""
     if values is None:
         raise TypeError("%s needs values" % name)
     if not args:
         raise TypeError("%s needs at least one array of samples" % name)
     _check_values_dtype(values, name)
+    if weights is not None:
+        _check_values_dtype(weights, name)
     n_inputs = len(args)
     axis = _normalise_axis(axis, args[0].ndim if hasattr(args[0], "ndim") else np.ndim(args[0]))
-    all_arrays = list(args) + [values]
+    all_arrays = list(args) + [values] + ([] if weights is None else [weights])
     raw = None
     if any(_is_dask(a) for a in all_arrays):
         import dask.array as dsa
@@ -1970,11 +1975,11 @@ def _values_call(args, values, bins, range, axis, name):
 
 
 def _values_blockwise(block_fn, k, all_arrays, bins, axis, drop_axes):
-    """dask: one task per block of the broadcast (samples..., values), each giving k statistics on a leading axis —
+    """dask: one task per block of the broadcast (samples..., values[, weights]), each giving k statistics on a leading axis —
     [k, block axes (reduced ones of extent 1), bins...]"""
     import dask.array as dsa
 
-    n_inputs = len(all_arrays) - 1
+    n_inputs = len(bins)
     ndim = all_arrays[0].ndim
     data_index = tuple(_range(1, ndim + 1))
     bin_index = tuple(_range(ndim + 1, ndim + 1 + n_inputs))
@@ -2047,7 +2052,58 @@ def _mean_var_aggregate(x, axis=None, keepdims=True, ddof=0, **_):
     return out
 
 
-def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, block_size="auto"):
+def combine_weighted_mean_var(w, mean, m2, axis):
+    """Merge partial weighted (W, mean, M2) results over `axis` (kept as axes of extent 1) with the weighted form of Chan's
+    pairwise formula, one partial after another in index order (C order over several axes):
+        W = Wa + Wb,  d = mb - ma,  mean = ma + d * Wb / W,  M2 = M2a + M2b + d^2 * Wa * Wb / W.
+    Partials with W == 0 are skipped; a NaN partial (a NaN W among them) makes the bin NaN.  Where every partial has W == 0,
+    mean and M2 are NaN and W is 0.  The reduction of dask's weighted partials.  Returns float64 (W, mean, M2)."""
+    w, mean, m2 = (np.asarray(a, np.float64) for a in (w, mean, m2))
+    ax = tuple(sorted(int(a) % w.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
+    rest = [i for i in _range(w.ndim) if i not in ax]
+    keep_shape = tuple(1 if i in ax else w.shape[i] for i in _range(w.ndim))
+
+    def lead(a):
+        a = np.transpose(a, ax + tuple(rest))
+        return a.reshape((-1,) + a.shape[len(ax):])
+
+    w, mean, m2 = lead(w), lead(mean), lead(m2)
+    cw = np.zeros(w.shape[1:])
+    cm = np.full(w.shape[1:], np.nan)
+    cq = np.full(w.shape[1:], np.nan)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for k in _range(w.shape[0]):
+            wb, mb, qb = w[k], mean[k], m2[k]
+            take = wb != 0  # (NaN != 0: a NaN partial is taken, and its NaN spreads)
+            first = take & (cw == 0)
+            both = take & (cw != 0)
+            tot = cw + wb
+            d = mb - cm
+            m_new = cm + d * wb / tot
+            q_new = cq + qb + d * d * cw * wb / tot
+            cm = np.where(first, mb, np.where(both, m_new, cm))
+            cq = np.where(first, qb, np.where(both, q_new, cq))
+            cw = np.where(take, tot, cw)
+    return cw.reshape(keep_shape), cm.reshape(keep_shape), cq.reshape(keep_shape)
+
+
+def _mean_var_w_reduce(x, axis=None, keepdims=True, **_):
+    """dask.array.reduction step over [3, ...] blocks of weighted (W, mean, M2) partials"""
+    ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
+    out = np.stack(combine_weighted_mean_var(x[0], x[1], x[2], tuple(a - 1 for a in ax)))
+    return out if keepdims else out.squeeze(ax)
+
+
+def _mean_var_w_aggregate(x, axis=None, keepdims=True, ddof=0, **_):
+    """the last weighted step: (W, mean, var), the division by W - ddof done here only"""
+    out = _mean_var_w_reduce(x, axis=axis, keepdims=keepdims)
+    w = out[0]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out[2] = np.where(w > ddof, out[2] / (w - ddof), np.nan)
+    return out
+
+
+def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, weights=None, block_size="auto"):
     """Per-bin count, mean and variance of ``values``, computed on an MI355X: ``scipy.stats.binned_statistic`` with
     ``statistic="count"``, ``"mean"`` and ``"std"`` (squared), NaN-ignoring like ``np.nanmean`` / ``np.nanvar``.
 
@@ -2065,8 +2121,32 @@ def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, 
 
     Returns ``(count, mean, var, bin_edges)``: count int64, mean and var float64, with the shape ``histogram`` gives (kept
     axes, then bin axes).  numpy in -> numpy out, torch in -> torch out on the same device, DeviceArray in -> numpy out, dask
-    in -> lazy dask arrays."""
+    in -> lazy dask arrays.
+
+    ``weights`` (any real dtype, converted like ``astype(np.float64)``; broadcast like ``values``) makes them frequency
+    weights, the convention of statsmodels' ``DescrStatsW``: each counted sample contributes its pair ``(w, v)``, and
+    ``W = sum(w)``, ``mean = sum(w * v) / W``, ``d = v - mean``, ``M2 = max(0, sum(w * d**2) - sum(w * d)**2 / W)``,
+    ``var = M2 / (W - ddof)``, all in float64.  With ``ddof=0`` the mean is ``np.average(v, weights=w)`` and the variance
+    ``np.average((v - mean)**2, weights=w)``; with ``w == 1`` every output equals the unweighted call's.  The mean and M2 are
+    NaN where ``W == 0`` (empty bins and bins whose weights sum to 0), the variance where ``W <= ddof``.  A NaN weight makes
+    its bin's W, mean and variance NaN; zero weights contribute nothing (``0 * inf`` is NaN, as in ``np.average``); infinite
+    weights give what the formulas give.  Negative weights are not checked: the formulas apply, the clamp of M2 at 0
+    included, which is meaningful only for non-negative weights.  Returns ``(sum_of_weights, mean, var, bin_edges)``, all
+    three float64 (W, the census of the samples that carry a value, takes the place of the count), with the same shapes and
+    backends; dask merges the blocks' partials with :func:`combine_weighted_mean_var`."""
     ddof = _check_ddof(ddof)
+    if weights is not None:
+        backend, (wsum, mean, m2), bins, _ = _value_stat("mean_var_w", args, values, bins, range, axis, "histogram_mean_var",
+                                                        partial(_mean_var_w_aggregate, ddof=ddof), weights=weights)
+        if backend == "dask":
+            return wsum, mean, m2, bins
+        if backend == "torch":
+            torch = _torch()
+            var = torch.where(wsum > ddof, m2 / (wsum - ddof), torch.full_like(m2, float("nan")))
+            return wsum, mean, var, bins
+        with np.errstate(invalid="ignore", divide="ignore"):
+            var = np.where(wsum > ddof, m2 / (wsum - ddof), np.nan)
+        return wsum, mean, var, bins
     # dask: one task per block with its (n, mean, M2) on a leading axis; the partials of the blocks that share output rows are
     # merged on the host in block order (Chan), and the last step divides by n - ddof
     backend, (cnt, mean, m2), bins, _ = _value_stat("mean_var", args, values, bins, range, axis, "histogram_mean_var",
@@ -2085,6 +2165,7 @@ def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, 
 _VALUE_STATS = {
     "extrema": _ValueStat(2, False, "execute_extrema", _extrema_pair_reduce),
     "mean_var": _ValueStat(3, True, "execute_mean_var", _mean_var_reduce),
+    "mean_var_w": _ValueStat(3, False, "execute_mean_var_weighted", _mean_var_w_reduce, True),
 }
 
 

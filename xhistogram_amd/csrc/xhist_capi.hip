@@ -323,6 +323,25 @@ extern "C" int xhist_plan_execute_mean_var(xhist_plan* p, const xhist_array* sam
                         });
 }
 
+extern "C" int xhist_plan_execute_mean_var_weighted(xhist_plan* p, const xhist_array* samples, const xhist_array* values,
+                                                    const xhist_array* weights, int64_t n_rows, int64_t n_cols, double* out_wsum,
+                                                    double* out_mean, double* out_m2, int mem_kind, void* stream) {
+  if (!weights) return fail(XHIST_ERR_INVALID, "weights are required");
+  if (int rc = validate_arrays(p, samples, weights, n_rows, n_cols, out_wsum, XHIST_F64)) return rc;
+  return execute_values(p, "xhist_plan_execute_mean_var_weighted", samples, values, n_rows, n_cols, out_mean, out_m2 != nullptr,
+                        "out_m2 is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
+                          hipStream_t s = static_cast<hipStream_t>(stream);
+                          ScratchScope scratch(s);
+                          double* sd = nullptr;  // the sums of w*d
+                          if (scratch.alloc((void**)&sd, (size_t)(n_rows * p->n_bins) * sizeof(double)) != hipSuccess) {
+                            snprintf(err, err_cap, "allocation of the weighted mean_var scratch block failed");
+                            return (int)XHIST_ERR_NOMEM;
+                          }
+                          return xhist_meanvar_w_run(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_m2, sd, s, err,
+                                                     err_cap, desc, desc_cap);
+                        });
+}
+
 extern "C" int xhist_plan_execute_quantile(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
                                            int64_t n_cols, const double* q, int n_q, int method, double* out, int mem_kind, void* stream) {
   if (n_q < 1 || !q) return fail(XHIST_ERR_INVALID, "q is NULL or n_q < 1");

@@ -20,6 +20,15 @@
 // with 16 (the weighted histogram: 553); C2's 100 bins 2662 / 2612 us with one, 2489 / 2448 with 8 (histogram: 2274).
 // Each workgroup flushes the bins it reached with global atomics, the copies summed in copy order.  Without LDS room the
 // generic family adds straight into the global arrays, and pass 2 reads the means through L2.
+//
+// Weighted (frequency weights, xhist_meanvar_w.hip): the skeletons' third stream hands each pass the pair (v, w), both in
+// float64 (a float32 w*v is exact there), and the same two passes run on weighted sums:
+//   pass 1 (mvw_sum_*)  W = sum(w), S = sum(w*v)                      -> out_wsum, out_mean (float64 atomics)
+//   mvw_mean            mean = S / W (NaN where W == 0)
+//   pass 2 (mvw_dev_*)  d = v - mean[bin]; the sums of w*d and of w*d*d -> the scratch block and out_m2
+//   mvw_finalize        M2 = max(0, sum(w*d*d) - sum(w*d)^2 / W), NaN where W == 0
+// The slots keep today's sizes: pass 1 {W, S} in 16 bytes (two ds_add_f64), pass 2 the MvDevSlot of the unweighted pass, so
+// the choice, the copies and the geometry are those of the unweighted call.
 #pragma once
 
 #include "xhist_values.hip.h"
@@ -126,6 +135,76 @@ struct MvAcc<2> {
   }
 };
 
+// The weighted passes' policies (kWeighted: the skeletons hand them (v, w)).  [n_rows, n_bins] arrays pre-advanced to row
+// p.row0 —
+//   pass 1: out = the float64 sums of weights W, out2 = the float64 sums of w*v;
+//   pass 2: as MvAcc<2>, the sums of w*d and w*d*d.
+// A flush skips a bin whose two sums are 0 (nothing reached it, or it adds nothing); a NaN sum is not 0 and reaches global memory.
+struct __attribute__((aligned(16))) MvwSumSlot {
+  double w, s;
+};
+
+template <int PASS>
+struct MvwAcc;
+
+template <>
+struct MvwAcc<1> {
+  using slot_t = MvwSumSlot;
+  static constexpr bool kCopies = true, kWeighted = true;
+  static __device__ __forceinline__ void init(slot_t* s, const Params& p, int64_t) {
+    const uint32_t n = (uint32_t)p.n_bins << p.copies_log2;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+      s[i].w = 0.0;
+      s[i].s = 0.0;
+    }
+  }
+  template <typename V>
+  static __device__ __forceinline__ void lds_add(slot_t* s, uint32_t i, V v, V w) {
+    unsafeAtomicAdd(&s[i].w, (double)w);
+    unsafeAtomicAdd(&s[i].s, (double)w * (double)v);
+  }
+  static __device__ __forceinline__ void global_add(const Params& p, int64_t row, int64_t b, double v, double w) {
+    const int64_t i = row * p.n_bins + b;
+    unsafeAtomicAdd(reinterpret_cast<double*>(p.out) + i, w);
+    unsafeAtomicAdd(reinterpret_cast<double*>(p.out2) + i, w * v);
+  }
+  static __device__ __forceinline__ void flush(const slot_t* s, const Params& p, int64_t row) {
+    double* ws = reinterpret_cast<double*>(p.out) + row * p.n_bins;
+    double* sum = reinterpret_cast<double*>(p.out2) + row * p.n_bins;
+    const uint32_t copies = 1u << p.copies_log2;
+    for (uint32_t b = threadIdx.x; b < (uint32_t)p.n_bins; b += blockDim.x) {
+      double w = 0.0, a = 0.0;
+      for (uint32_t c = 0; c < copies; ++c) {
+        const slot_t x = s[(b << p.copies_log2) + c];
+        w += x.w;
+        a += x.s;
+      }
+      if (w == 0.0 && a == 0.0) continue;
+      unsafeAtomicAdd(ws + b, w);
+      unsafeAtomicAdd(sum + b, a);
+    }
+  }
+};
+
+template <>
+struct MvwAcc<2> : MvAcc<2> {
+  static constexpr bool kWeighted = true;
+  template <typename V>
+  static __device__ __forceinline__ void lds_add(slot_t* s, uint32_t i, V v, V w) {
+    const double d = (double)v - s[i].mean;
+    const double wd = (double)w * d;
+    unsafeAtomicAdd(&s[i].sd, wd);
+    unsafeAtomicAdd(&s[i].s2, wd * d);
+  }
+  static __device__ __forceinline__ void global_add(const Params& p, int64_t row, int64_t b, double v, double w) {
+    const int64_t i = row * p.n_bins + b;
+    const double d = v - reinterpret_cast<const double*>(p.w2_ptr)[i];
+    const double wd = w * d;
+    unsafeAtomicAdd(reinterpret_cast<double*>(p.out) + i, wd);
+    unsafeAtomicAdd(reinterpret_cast<double*>(p.out2) + i, wd * d);
+  }
+};
+
 // The binning kernels of the two passes: mv_sum_generic / mv_dev_generic<CMP, LDS> (block 512) and mv_sum_fast /
 // mv_dev_fast<ST, D, SCAN> (block 256), the families of xhist_values.hip.h.
 template <int CMP, bool LDS>
@@ -145,6 +224,25 @@ __global__ void __launch_bounds__(256) mv_dev_fast(const Params p) {
   values_fast_body<MvAcc<2>, ST, D, SCAN>(p);
 }
 
+// ... and of the weighted passes: mvw_sum_generic / mvw_dev_generic<CMP, LDS> (block 512), mvw_sum_fast / mvw_dev_fast<ST, D,
+// SCAN> (block 256), instantiated in xhist_meanvar_w.hip only.
+template <int CMP, bool LDS>
+__global__ void __launch_bounds__(512) mvw_sum_generic(const WParams p) {
+  values_generic_body<MvwAcc<1>, CMP, LDS>(p);
+}
+template <int CMP, bool LDS>
+__global__ void __launch_bounds__(512) mvw_dev_generic(const WParams p) {
+  values_generic_body<MvwAcc<2>, CMP, LDS>(p);
+}
+template <typename ST, int D, int SCAN>
+__global__ void __launch_bounds__(256) mvw_sum_fast(const WParams p) {
+  values_fast_body<MvwAcc<1>, ST, D, SCAN>(p);
+}
+template <typename ST, int D, int SCAN>
+__global__ void __launch_bounds__(256) mvw_dev_fast(const WParams p) {
+  values_fast_body<MvwAcc<2>, ST, D, SCAN>(p);
+}
+
 }  // namespace xhist
 
 // The zeroing and the five launches on `stream` (pass 1, mean, pass 2, finalize) for DEVICE arrays the caller has validated,
@@ -154,3 +252,9 @@ __global__ void __launch_bounds__(256) mv_dev_fast(const Params p) {
 int xhist_meanvar_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
                       int64_t* out_count, double* out_mean, double* out_m2, double* sd, hipStream_t stream, char* err, size_t err_cap,
                       char* desc, size_t desc_cap);
+
+// The same for the weighted form (xhist_meanvar_w.hip): `weights` a validated DEVICE array of the samples' logical shape, the
+// sums of weights into out_wsum (float64).  (Called by xhist_plan_execute_mean_var_weighted, xhist_capi.hip.)
+int xhist_meanvar_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
+                        int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_m2, double* sd, hipStream_t stream,
+                        char* err, size_t err_cap, char* desc, size_t desc_cap);

@@ -6,6 +6,9 @@
 // value is not NaN hands that value to the policy.  The slots of a workgroup sit in LDS behind the staged tables; the generic
 // family without LDS room hands every value straight to global memory.
 //
+// The weighted statistics (histogram_mean_var with weights, xhist_meanvar_w.hip) read a third stream, the weights, through the
+// same skeletons: a policy with kWeighted = true is handed (value, weight) pairs, and its kernels take WParams.
+//
 // Nothing here instantiates a kernel: the skeletons are templates, and the kernels are instantiated in the statistic's own
 // translation unit only (xhist_capi.hip includes this header for ValuesPlan and must not gain device code).
 #pragma once
@@ -17,11 +20,20 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 namespace xhist {
 
 // the slots sit behind the staged tables, 16-byte aligned
 __host__ __device__ __forceinline__ size_t ext_slots_offset(const Params& p) { return (size_t)((p.table_words + 1) & ~1) * 8; }
+
+// The Params of the weighted statistics' kernels: Params, whose fields do not move, and the weights, a third input stream laid
+// out as the values are (x_ptr[row_offset(r, x_rs, x_ir, x_os) + c * x_cs], dtype x_dt).  Only the weighted kernels take it.
+struct WParams : Params {
+  const void* x_ptr;
+  int64_t x_rs, x_cs, x_ir, x_os;
+  int32_t x_dt;
+};
 
 // An accumulator policy `Acc` is one statistic's (one pass's) use of the slots:
 //   slot_t                    one bin's LDS slot
@@ -32,6 +44,13 @@ __host__ __device__ __forceinline__ size_t ext_slots_offset(const Params& p) { r
 //   global_add(p, row, b, v)  one float64 value straight into bin b of the output row (generic family without LDS)
 //   flush(slots, p, row)      the workgroup's slots into its output row
 // Outputs are [n_rows, n_bins] arrays at p.out / p.out2, pre-advanced to row p.row0; the values are p.w_*.
+// A weighted policy (kWeighted = true; its kernels take WParams, the weights at p.x_*) takes the sample's weight as well:
+//   lds_add(slots, i, v, w)  global_add(p, row, b, v, w)   (w in the sample type or float64, as v)
+// The skeletons choose the stream at compile time (if constexpr); the unweighted policies have no kWeighted.
+template <class Acc, class = void>
+struct AccWeighted : std::false_type {};
+template <class Acc>
+struct AccWeighted<Acc, std::enable_if_t<Acc::kWeighted>> : std::true_type {};
 //
 // The bodies take the kernel's Params as `const Params& __restrict__`.  A body is optimised on its own before it is inlined
 // into its kernel, and without __restrict__ that step must assume the LDS and global atomics may write the Params: the
@@ -44,8 +63,10 @@ __host__ __device__ __forceinline__ size_t ext_slots_offset(const Params& p) { r
 // then in LDS too).  Else every value goes to global memory, and the tables are read from LDS when they fit there
 // (p.tables_in_lds) and through L2 otherwise.
 // ---------------------------------------------------------------------------------------------
-template <class Acc, int CMP, bool LDS>
-__device__ __forceinline__ void values_generic_body(const Params& __restrict__ p) {
+template <class Acc, int CMP, bool LDS, class P>
+__device__ __forceinline__ void values_generic_body(const P& __restrict__ p) {
+  constexpr bool W = AccWeighted<Acc>::value;
+  static_assert(!W || std::is_same<P, WParams>::value, "weighted policies read the weights of WParams");
   using CT = typename Dom<CMP>::T;
   const int64_t row = blockIdx.x / p.segs;
   const int seg = blockIdx.x % p.segs;
@@ -61,7 +82,14 @@ __device__ __forceinline__ void values_generic_body(const Params& __restrict__ p
   const int64_t voff = row_offset(p.row0 + row, p.w_rs, p.w_ir, p.w_os);
 
   const int64_t stride = (int64_t)p.segs * blockDim.x;
-  for (int64_t i = (int64_t)seg * blockDim.x + threadIdx.x; i < p.n_cols; i += stride) {
+  // The weight's element index walks with i, per lane: the weights then hold 5 SGPRs (pointer, dtype, step) instead of 7,
+  // and the weighted kernels keep clear of scratch (with a row offset and a column stride live, two of them reserved 36 bytes).
+  int64_t xi = 0, xstep = 0;
+  if constexpr (W) {
+    xi = row_offset(p.row0 + row, p.x_rs, p.x_ir, p.x_os) + ((int64_t)seg * blockDim.x + threadIdx.x) * p.x_cs;
+    xstep = stride * p.x_cs;
+  }
+  for (int64_t i = (int64_t)seg * blockDim.x + threadIdx.x; i < p.n_cols; i += stride, xi += xstep) {
     const double v = load_as<double>(p.w_ptr, p.w_dt, voff + i * p.w_cs);
     bool ok = v == v;  // NaN values are ignored (np.fmin / np.fmax, np.nanmean / np.nanvar)
     int64_t flat = 0;
@@ -75,8 +103,14 @@ __device__ __forceinline__ void values_generic_body(const Params& __restrict__ p
       }
     }
     if (!ok) continue;
-    if (LDS) Acc::lds_add(slots, (uint32_t)flat, v);  // (one copy of the slots: p.copies_log2 == 0)
-    else Acc::global_add(p, row, flat, v);
+    if constexpr (W) {
+      const double w = load_as<double>(p.x_ptr, p.x_dt, xi);  // (only for a sample that counts)
+      if (LDS) Acc::lds_add(slots, (uint32_t)flat, v, w);
+      else Acc::global_add(p, row, flat, v, w);
+    } else {
+      if (LDS) Acc::lds_add(slots, (uint32_t)flat, v);  // (one copy of the slots: p.copies_log2 == 0)
+      else Acc::global_add(p, row, flat, v);
+    }
   }
   if (LDS) {
     __syncthreads();
@@ -88,15 +122,22 @@ __device__ __forceinline__ void values_generic_body(const Params& __restrict__ p
 // VECTOR fast path: float32 or float64 samples with values of the same type, unit column stride, one or two inputs, slots
 // in LDS; digitize by the tables with at most two edges per bucket (SCAN 1 / 2: float64 edges for float64 samples, float32
 // thresholds for float32 ones) or by arithmetic (kScanArith).  Tiles as in hist_fast: VEC elements per 16-byte
-// non-temporal load, UNROLL loads in flight per array and lane; the workgroups of a row walk its tiles interleaved.
+// non-temporal load, UNROLL loads in flight per array and lane; the workgroups of a row walk its tiles interleaved.  A weighted
+// policy's weights have the sample type and unit column stride too, and are loaded the same way.
 // ---------------------------------------------------------------------------------------------
-template <class Acc, typename ST, int D, int SCAN>
-__device__ __forceinline__ void values_fast_body(const Params& __restrict__ p) {
+template <class Acc, typename ST, int D, int SCAN, class P>
+__device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
+  constexpr bool W = AccWeighted<Acc>::value;
+  static_assert(!W || std::is_same<P, WParams>::value, "weighted policies read the weights of WParams");
   static_assert(__is_same(ST, double) || __is_same(ST, float), "float32 / float64 samples and values");
   static_assert(SCAN == 1 || SCAN == 2 || SCAN == kScanArith, "tables with <= 2 edges per bucket, or arithmetic edges");
   constexpr int CMP = (__is_same(ST, float) && SCAN != kScanArith) ? 2 : 0;
   constexpr int VEC = 16 / (int)sizeof(ST);
   constexpr int UNROLL = D == 1 ? 4 : 8 / VEC;  // 128 bytes of samples and values per lane in flight (192 for two inputs)
+  // Weighted float64 pairs read a tile in two halves of UNROLL / 2 loads per array: four streams then keep 128 bytes per lane in
+  // flight, and the VGPRs, hence the waves per SIMD, of the unweighted form.  The tile, and with it the launch geometry, stays.
+  constexpr int HALVES = (W && D == 2 && __is_same(ST, double)) ? 2 : 1;
+  constexpr int UH = UNROLL / HALVES;
   using svec = typename VecOf<ST, VEC>::type;
 
   const int tid = threadIdx.x;
@@ -111,6 +152,8 @@ __device__ __forceinline__ void values_fast_body(const Params& __restrict__ p) {
 #pragma unroll
   for (int d = 0; d < D; ++d) sp[d] = reinterpret_cast<const ST*>(p.s_ptr[d]) + row_offset(p.row0 + row, p.s_rs[d], p.s_ir[d], p.s_os[d]);
   const ST* vp = reinterpret_cast<const ST*>(p.w_ptr) + row_offset(p.row0 + row, p.w_rs, p.w_ir, p.w_os);
+  const ST* xp = nullptr;
+  if constexpr (W) xp = reinterpret_cast<const ST*>(p.x_ptr) + row_offset(p.row0 + row, p.x_rs, p.x_ir, p.x_os);
   const uint32_t nb1 = D == 2 ? (uint32_t)p.dim[1].nb : 1u;
   const uint32_t mycopy = Acc::kCopies ? (uint32_t)tid & ((1u << p.copies_log2) - 1u) : 0u;
 
@@ -118,45 +161,55 @@ __device__ __forceinline__ void values_fast_body(const Params& __restrict__ p) {
   const int64_t n_tiles = (p.n_cols + tile_elems - 1) / tile_elems;
   for (int64_t t = seg; t < n_tiles; t += p.segs) {
     const int64_t base = t * tile_elems;
-    svec xv[D][UNROLL], vv[UNROLL];
-    if (base + tile_elems <= p.n_cols) {
+    const bool full = base + tile_elems <= p.n_cols;
 #pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t i = base + ((int64_t)u * blockDim.x + tid) * VEC;
+    for (int h = 0; h < HALVES; ++h) {
+      svec xv[D][UH], vv[UH], wv[W ? UH : 1];
+      if (full) {
 #pragma unroll
-        for (int d = 0; d < D; ++d) xv[d][u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(sp[d] + i));
-        vv[u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(vp + i));
+        for (int u = 0; u < UH; ++u) {
+          const int64_t i = base + ((int64_t)(h * UH + u) * blockDim.x + tid) * VEC;
+#pragma unroll
+          for (int d = 0; d < D; ++d) xv[d][u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(sp[d] + i));
+          vv[u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(vp + i));
+          if constexpr (W) wv[u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(xp + i));
+        }
+      } else {  // the ragged last tile: positions past the end become NaN samples, which digitize drops (their weights are 0)
+#pragma unroll
+        for (int u = 0; u < UH; ++u) {
+          const int64_t i = base + ((int64_t)(h * UH + u) * blockDim.x + tid) * VEC;
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) {
+            const bool in = i + v < p.n_cols;
+#pragma unroll
+            for (int d = 0; d < D; ++d) xv[d][u][v] = in ? sp[d][i + v] : (ST)__builtin_nanf("");
+            vv[u][v] = in ? vp[i + v] : (ST)__builtin_nanf("");
+            if constexpr (W) wv[u][v] = in ? xp[i + v] : (ST)0;
+          }
+        }
       }
-    } else {  // the ragged last tile: positions past the end become NaN samples, which digitize drops
+      uint32_t cnt[D][UH][VEC];
+      count_le_tile<CMP, SCAN, D, UH, VEC>(xv, p, tab, 1, cnt);
 #pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t i = base + ((int64_t)u * blockDim.x + tid) * VEC;
+      for (int u = 0; u < UH; ++u)
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
-          const bool in = i + v < p.n_cols;
+          const ST val = vv[u][v];
+          bool ok = val == val;
+          uint32_t flat = 0;
 #pragma unroll
-          for (int d = 0; d < D; ++d) xv[d][u][v] = in ? sp[d][i + v] : (ST)__builtin_nanf("");
-          vv[u][v] = in ? vp[i + v] : (ST)__builtin_nanf("");
+          for (int d = 0; d < D; ++d) {
+            const int b = bin_from_tile_count<CMP, SCAN>((typename Dom<CMP>::T)xv[d][u][v], p.dim[d], cnt[d][u][v]);
+            ok &= b >= 0;
+            flat = d == 0 ? (uint32_t)b : flat * nb1 + (uint32_t)b;
+          }
+          if constexpr (W) {
+            if (ok) Acc::lds_add(slots, Acc::kCopies ? (flat << p.copies_log2) + mycopy : flat, val, (ST)wv[u][v]);
+          } else {
+            if (ok) Acc::lds_add(slots, Acc::kCopies ? (flat << p.copies_log2) + mycopy : flat, val);
+          }
         }
-      }
     }
-    uint32_t cnt[D][UNROLL][VEC];
-    count_le_tile<CMP, SCAN, D, UNROLL, VEC>(xv, p, tab, 1, cnt);
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u)
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) {
-        const ST val = vv[u][v];
-        bool ok = val == val;
-        uint32_t flat = 0;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-          const int b = bin_from_tile_count<CMP, SCAN>((typename Dom<CMP>::T)xv[d][u][v], p.dim[d], cnt[d][u][v]);
-          ok &= b >= 0;
-          flat = d == 0 ? (uint32_t)b : flat * nb1 + (uint32_t)b;
-        }
-        if (ok) Acc::lds_add(slots, Acc::kCopies ? (flat << p.copies_log2) + mycopy : flat, val);
-      }
   }
   __syncthreads();
   Acc::flush(slots, p, row);
@@ -238,9 +291,10 @@ static inline int fast_copies_log2(int64_t n_bins, size_t slot, size_t tbytes, s
 }
 
 // fast if eligible, else generic with its slots in LDS, else generic straight into global memory.  The largest slot of the
-// passes decides; every pass takes the family, the home and the copies chosen for it.
+// passes decides; every pass takes the family, the home and the copies chosen for it.  `weights` (nullptr: unweighted) must
+// qualify for the fast family as the values do: the sample dtype, unit column stride (or one column), element-aligned.
 static inline ValuesChoice choose_values(const ValuesPlan& pl, const ValuesSlots& sl, const xhist_array* samples,
-                                         const xhist_array* values, int64_t n_cols) {
+                                         const xhist_array* values, int64_t n_cols, const xhist_array* weights = nullptr) {
   ValuesChoice c;
   const int D = pl.n_dims;
   const int sdt = samples[0].dtype;
@@ -250,6 +304,8 @@ static inline ValuesChoice choose_values(const ValuesPlan& pl, const ValuesSlots
   for (int d = 0; d < D && fast_ok; ++d)
     fast_ok = samples[d].dtype == sdt && (samples[d].col_stride == 1 || n_cols == 1) && (uintptr_t)samples[d].data % (size_t)elem_bytes(sdt) == 0;
   if (fast_ok) fast_ok = (values->col_stride == 1 || n_cols == 1) && (uintptr_t)values->data % (size_t)elem_bytes(sdt) == 0;
+  if (fast_ok && weights)
+    fast_ok = weights->dtype == sdt && (weights->col_stride == 1 || n_cols == 1) && (uintptr_t)weights->data % (size_t)elem_bytes(sdt) == 0;
   if (fast_ok) {
     const size_t* bytes = c.f32 ? sl.fast32 : sl.bytes;
     const size_t slot = std::max(bytes[0], bytes[1]);
@@ -286,9 +342,12 @@ static inline ValuesChoice choose_values(const ValuesPlan& pl, const ValuesSlots
 }
 
 // The kernel a choice runs, from a statistic's kernel set K: K::fast<ST, D, SCAN>() and K::generic<CMP, LDS>() name its
-// instantiations.  nullptr: none for this combination.
+// instantiations (values_fn, or the WParams form of the weighted kernels).  nullptr: none for this combination.
+template <class K>
+using values_fn_of = decltype(K::template generic<0, true>());
+
 template <class K, typename ST, int D>
-static values_fn fast_scan(int scan) {
+static values_fn_of<K> fast_scan(int scan) {
   if (scan == 1) return K::template fast<ST, D, 1>();
   if (scan == 2) return K::template fast<ST, D, 2>();
   if (scan == kScanArith) return K::template fast<ST, D, kScanArith>();
@@ -298,7 +357,7 @@ static values_fn fast_scan(int scan) {
 static inline int values_cmp(const ValuesPlan& pl) { return pl.cmp == XHIST_CMP_F64 ? 0 : pl.cmp == XHIST_CMP_I64 ? 1 : 3; }
 
 template <class K>
-static values_fn pick_values_kernel(const ValuesChoice& c, const ValuesPlan& pl) {
+static values_fn_of<K> pick_values_kernel(const ValuesChoice& c, const ValuesPlan& pl) {
   if (c.fast) {
     if (c.f32) return pl.n_dims == 1 ? fast_scan<K, float, 1>(c.scan) : fast_scan<K, float, 2>(c.scan);
     return pl.n_dims == 1 ? fast_scan<K, double, 1>(c.scan) : fast_scan<K, double, 2>(c.scan);
@@ -337,7 +396,8 @@ static inline ValuesGeometry values_geometry(const ValuesPlan& pl, const ValuesC
 }
 
 // A kernel's dynamic LDS beyond 48 KiB must be allowed before its first launch; drivers do it for every pass up front.
-static int allow_values_lds(values_fn fn, size_t lds, const char* what, char* err, size_t err_cap) {
+template <class F>
+static int allow_values_lds(F fn, size_t lds, const char* what, char* err, size_t err_cap) {
   if (lds <= 48 * 1024) return XHIST_OK;
   const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   return e == hipSuccess ? XHIST_OK : values_error(err, err_cap, XHIST_ERR_HIP, what, e);
@@ -377,15 +437,29 @@ static inline Params values_params(const ValuesPlan& pl, const ValuesChoice& c, 
   return kp;
 }
 
+// the weights of a WParams launch over rows from r0 on
+static inline void weights_params(WParams& kp, const xhist_array* weights) {
+  kp.x_ptr = weights->data;
+  kp.x_rs = weights->row_stride;
+  kp.x_cs = weights->col_stride;
+  kp.x_ir = weights->inner_rows;
+  kp.x_os = weights->outer_stride;
+  kp.x_dt = weights->dtype;
+}
+
 // One binning pass: the launches of row chunks of at most g.max_rows (the grid stays below 2^31 workgroups and 2^32 lanes).  out / out2 / in2 are [n_rows, n_bins] arrays of 8-byte elements,
-// advanced to each chunk's first row (Params::out, out2 and w2_ptr); `what` names the pass in error messages.
-static int launch_values_pass(values_fn fn, size_t lds, const char* what, const ValuesPlan& pl,
+// advanced to each chunk's first row (Params::out, out2 and w2_ptr); `what` names the pass in error messages.  A weighted
+// kernel (it takes WParams) reads `weights`.
+template <class P>
+static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what, const ValuesPlan& pl,
                               const ValuesChoice& c, const ValuesGeometry& g, const xhist_array* samples, const xhist_array* values,
                               int64_t n_rows, int64_t n_cols, void* out, void* out2, const void* in2, hipStream_t stream, char* err,
-                              size_t err_cap) {
+                              size_t err_cap, const xhist_array* weights = nullptr) {
   for (int64_t r0 = 0; r0 < n_rows; r0 += g.max_rows) {
     const int64_t nr = std::min(g.max_rows, n_rows - r0);
-    Params kp = values_params(pl, c, g.segs, samples, values, r0, nr, n_cols);
+    P kp;
+    static_cast<Params&>(kp) = values_params(pl, c, g.segs, samples, values, r0, nr, n_cols);
+    if constexpr (std::is_same<P, WParams>::value) weights_params(kp, weights);
     kp.w2_ptr = in2 ? static_cast<const uint64_t*>(in2) + r0 * pl.n_bins : nullptr;
     kp.out = static_cast<uint64_t*>(out) + r0 * pl.n_bins;
     kp.out2 = static_cast<uint64_t*>(out2) + r0 * pl.n_bins;

@@ -145,22 +145,26 @@ def histogram_extrema(*args, values, bins=None, range=None, dim=None, block_size
 
 
 def histogram_mean_var(*args, values, bins=None, range=None, dim=None, ddof=0, block_size="auto", keep_coords=False,
-                       bin_dim_suffix="_bin"):
+                       bin_dim_suffix="_bin", weights=None):
     """Per-bin count, mean and variance of the DataArray ``values`` over the bins of ``args``
     (:func:`xhistogram_amd.core.histogram_mean_var` with the labels of :func:`histogram`).
 
     ``args``, ``bins``, ``range``, ``dim``, ``keep_coords`` and ``bin_dim_suffix`` are those of :func:`histogram`; ``values``
     takes the place of its weights (dims a subset of the data's).  Returns ``(count, mean, var)``: three DataArrays with the
     dims and coords ``histogram`` gives for the same ``args``, ``bins`` and ``dim``, named ``<values name>_count`` / ``_mean``
-    / ``_var`` (``values`` when the DataArray has no name)."""
+    / ``_var`` (``values`` when the DataArray has no name).
+
+    ``weights`` (a DataArray whose dims are a subset of the data's, aligned and broadcast as ``values`` is) gives the
+    frequency-weighted form: ``(sum_of_weights, mean, var)``, the first named ``<values name>_sum_of_weights``."""
     from .core import histogram_mean_var as _core_histogram_mean_var
 
     (cnt, mean, var), out_dims, coords, base = _values_statistic(
         "histogram_mean_var", _core_histogram_mean_var, args, values, bins, range, dim, keep_coords, bin_dim_suffix, ddof=ddof,
-        block_size=block_size)
+        block_size=block_size, weights=weights)
     xr = _xr()
+    first = "count" if weights is None else "sum_of_weights"
     return tuple(xr.DataArray(a, dims=out_dims, coords=coords, name="%s_%s" % (base, suffix))
-                 for a, suffix in ((cnt, "count"), (mean, "mean"), (var, "var")))
+                 for a, suffix in ((cnt, first), (mean, "mean"), (var, "var")))
 
 
 def histogram_quantile(*args, values, q, bins=None, range=None, dim=None, method="linear", block_size="auto", keep_coords=False,
@@ -187,13 +191,14 @@ def histogram_quantile(*args, values, q, bins=None, range=None, dim=None, method
         coords = dict(coords, quantile=(("quantile",), qa))
     return xr.DataArray(res, dims=out_dims, coords=coords, name="%s_quantile" % base)
 
-def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords, bin_dim_suffix, **kw):
+def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords, bin_dim_suffix, weights=None, **kw):
     """a per-bin statistic of ``values`` with the labels of :func:`histogram`: (core_fn's arrays, dims, coords, the values'
-    name or "values")"""
+    name or "values").  ``weights`` (a DataArray or None) is lined up as ``values`` is and passed on as core_fn's weights."""
     xr = _xr()
     data_args = list(args)
     n_data = len(data_args)
-    for a in data_args + [values]:
+    extra = [values] + ([] if weights is None else [weights])
+    for a in data_args + extra:
         if not isinstance(a, xr.DataArray):
             raise TypeError(
                 "xhistogram.xarray.%s accepts only xarray.DataArray objects but a %s was provided" % (name, type(a).__name__)
@@ -201,7 +206,7 @@ def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords
     for a in data_args:
         assert a.name is not None, "all arrays must have a name"
     operands = list(data_args) if keep_coords else [a.reset_coords(drop=True) for a in data_args]
-    operands.append(values.reset_coords(drop=True))
+    operands += [a.reset_coords(drop=True) for a in extra]
     operands = list(xr.align(*operands, join="exact"))
     first = operands[0]
     first_coords = first.coords
@@ -219,6 +224,8 @@ def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords
             a = a.transpose(*dims_order)
         lined_up.append(a)
     arrays = [a.data for a in lined_up]
+    if weights is not None:
+        kw["weights"] = arrays.pop()
     v_data = arrays.pop()
     if dim is not None:
         kept_dims = [d for d in dims_order if d not in dim]
