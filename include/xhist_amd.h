@@ -197,6 +197,21 @@ int xhist_plan_execute_quantile(xhist_plan* plan, const xhist_array* samples, co
                                 int64_t n_rows, int64_t n_cols, const double* q, int n_q, int method, double* out,
                                 int mem_kind, void* stream);
 
+/* Weighted per-bin quantiles of `values` (added within ABI v11): numpy's method="inverted_cdf" with weights.  Samples and
+ * values count as for xhist_plan_execute_quantile; each brings its weight, converted to float64.  Per bin, with C(x) the sum
+ * of the weights of the values <= x and W the sum of all: the smallest value x with C(x) / W >= q[i] (one float64 division) and
+ * C(x) > 0, or the largest value of positive weight if rounding leaves none.  NaN where the bin has no value, W is not finite
+ * and positive, or a weight of the bin is NaN or negative.  On weights whose float64 sums are exact in any order every element
+ * equals np.nanquantile(values of the bin, q[i], weights=..., method="inverted_cdf") bit for bit (zeros by value); on other
+ * weights the order of the sums moves C and W in their last bits and the result may be a neighbouring value of the bin.
+ *   weights: an xhist_array of any real dtype, shaped like the values (strides 0 broadcast).  The fast kernels take weights of
+ *   the sample dtype with unit column stride; anything else runs the generic family.  Rows of at most 2048 values are sorted
+ *   in LDS.  q, out, mem_kind, stream and scratch are those of xhist_plan_execute_quantile.  xhist_plan_describe then starts
+ *   with "weighted_quantile family=...". */
+int xhist_plan_execute_quantile_weighted(xhist_plan* plan, const xhist_array* samples, const xhist_array* values,
+                                         const xhist_array* weights, int64_t n_rows, int64_t n_cols, const double* q, int n_q,
+                                         double* out, int mem_kind, void* stream);
+
 /* One-shot form of the two calls above with an internal plan cache keyed on (device, edges). */
 int xhist_bincount_rows(int device, int n_inputs, const xhist_array* samples,
                         const xhist_array* weights, int64_t n_rows, int64_t n_cols,

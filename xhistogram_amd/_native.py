@@ -70,6 +70,7 @@ EXPORTS = (
     "xhist_abi_version", "xhist_last_error", "xhist_device_count", "xhist_device_info",
     "xhist_plan_create", "xhist_plan_destroy", "xhist_plan_execute", "xhist_plan_execute_two_weights", "xhist_plan_execute_extrema",
     "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
+    "xhist_plan_execute_quantile_weighted",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -147,6 +148,10 @@ def load():
         lib.xhist_plan_execute_quantile.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int,
             C.c_void_p, C.c_int, C.c_void_p,
+        ]
+        lib.xhist_plan_execute_quantile_weighted.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64,
+            C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_int, C.c_void_p,
         ]
         lib.xhist_bincount_rows.argtypes = [
             C.c_int, C.c_int, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_void_p),
@@ -401,6 +406,20 @@ class Plan:
             load().xhist_plan_execute_quantile(
                 self._h, arr, C.byref(value_view), int(n_rows), int(n_cols), qa.ctypes.data_as(C.POINTER(C.c_double)), int(qa.size),
                 int(method), C.c_void_p(out_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
+            )
+        )
+
+    def execute_quantile_weighted(self, sample_views, value_view, weight_view, n_rows, n_cols, out_ptr, q, stream=0):
+        """weighted per-bin quantiles q (host float64 values in [0, 1]; numpy's method="inverted_cdf") of the values of
+        device-resident views, into a float64 device buffer [len(q), n_rows, bins] (NaN where the bin has no value, its weights
+        do not sum to a finite positive number, or one of them is NaN or negative), asynchronous on `stream`
+        (xhist_plan_execute_quantile_weighted)"""
+        arr = self._sample_array(sample_views)
+        qa = np.ascontiguousarray(q, dtype=np.float64).ravel()
+        check(
+            load().xhist_plan_execute_quantile_weighted(
+                self._h, arr, C.byref(value_view), C.byref(weight_view), int(n_rows), int(n_cols),
+                qa.ctypes.data_as(C.POINTER(C.c_double)), int(qa.size), C.c_void_p(out_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
             )
         )
 

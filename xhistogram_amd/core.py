@@ -33,7 +33,8 @@ from .devicearray import DeviceArray, _nocopy_reshape_strides
 # range is a keyword of histogram(), like in the reference
 _range = range
 
-__all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile"]
+__all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
+           "histogram_weighted_quantile"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2221,7 +2222,7 @@ def histogram_quantile(*args, values, q, bins=None, range=None, axis=None, metho
     ``args``, ``bins``, ``range``, ``axis`` and ``values`` are those of :func:`histogram_mean_var`: a sample counts when
     ``histogram`` counts it and its value is not NaN; the edges are those of the unweighted ``histogram``.  ``q`` is a float or a
     1-D array-like in [0, 1] (taken as float64), ``method`` one of ``"linear"``, ``"lower"``, ``"higher"``, ``"midpoint"``,
-    ``"nearest"``.  ``weights`` and ``density`` are not supported.  ``block_size`` is accepted and changes nothing.
+    ``"nearest"``.  ``weights`` (see :func:`histogram_weighted_quantile`) and ``density`` are not taken.  ``block_size`` is accepted and changes nothing.
 
     Rows of at most 4096 values are sorted in LDS; longer rows take an exact radix select over order-preserving keys of the
     values in a fixed number of streaming passes (about 9 for float64 values).
@@ -2231,7 +2232,7 @@ def histogram_quantile(*args, values, q, bins=None, range=None, axis=None, metho
     (asynchronous on the current stream), DeviceArray in -> numpy out, dask in -> a lazy dask array, one task per block: every
     reduced axis must then be a single chunk."""
     if weights is not None:
-        raise TypeError("histogram_quantile does not take weights: weighted quantiles are not supported")
+        raise TypeError("histogram_quantile does not take weights: weighted quantiles are histogram_weighted_quantile's")
     if density is not None:
         raise TypeError("histogram_quantile does not take density")
     qf, scalar, code = _check_quantile_args(q, method)
@@ -2257,4 +2258,94 @@ def histogram_quantile(*args, values, q, bins=None, range=None, axis=None, metho
         out = out.reshape(keep)
         return (out[0] if scalar else out), bins
     out = out.squeeze(squeeze)
+    return (out[0] if scalar else out), bins
+
+
+# ---------------------------------------------------------------------------------------------
+# weighted per-bin quantiles of a value array
+# ---------------------------------------------------------------------------------------------
+def _weighted_quantile_rows(args, values, weights, axis, bins, backend, q):
+    """[len(q), kept axes (reduced ones of extent 1), bins...] float64 weighted quantiles of broadcast torch tensors (torch out)
+    or DeviceArrays (numpy out)"""
+    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, weights)
+    n = m * plan.n_bins
+    shape = (len(q),) + kept_axes_shape + plan.bins_shape
+    if backend == "torch":
+        out = _torch().empty(shape, dtype=_torch().float64, device=args[0].device)
+        if n > 0 and len(q):
+            plan.execute_quantile_weighted(nv[:-2], nv[-2], nv[-1], m, c, out.data_ptr(), q, stream=stream)
+        return out
+    host = np.empty(shape, np.float64)
+    if n > 0 and len(q):
+        buf = _native.DeviceBuffer(device, len(q) * n * 8)
+        plan.execute_quantile_weighted(nv[:-2], nv[-2], nv[-1], m, c, buf.ptr, q, stream=stream)
+        buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+    return host
+
+
+def _weighted_quantile_block(*all_arrays, axis=None, bins=None, q=None):
+    """one dask block, complete along the reduced axes: its weighted quantiles [len(q), block axes (reduced ones of extent 1),
+    bins...]"""
+    arrays = _upload_host(all_arrays[:-2], all_arrays[-2], bins, all_arrays[-1])
+    return _weighted_quantile_rows(arrays[:-2], arrays[-2], arrays[-1], axis, bins, "device", q)
+
+
+def histogram_weighted_quantile(*args, values, weights, q, bins=None, range=None, axis=None, method="inverted_cdf",
+                                block_size="auto"):
+    """Weighted per-bin quantiles of ``values``, computed on an MI355X: what
+    ``np.nanquantile(values_in_that_bin.astype(np.float64), q, weights=weights_in_that_bin, method="inverted_cdf")`` gives.
+
+    ``args``, ``bins``, ``range``, ``axis``, ``values`` and ``q`` are those of :func:`histogram_quantile`: a sample counts when
+    ``histogram`` counts it and its value is not NaN; the edges are those of the unweighted ``histogram``.  ``weights`` (any real
+    dtype, taken as float64) broadcasts against the inputs as ``values`` does.  ``method`` accepts only ``"inverted_cdf"``, the
+    one method numpy defines with weights.  ``block_size`` is accepted and changes nothing.
+
+    Per (row, bin, q): with ``C(x)`` the float64 sum of the weights of the bin's values ``<= x`` (ordered as
+    ``histogram_quantile`` orders them, ``-0.0 < +0.0``) and ``W`` the sum of all of them, the result is the smallest value
+    ``x`` of the bin with ``C(x) / W >= q`` (one float64 division) and ``C(x) > 0`` — numpy's
+    ``cdf /= cdf[-1]; searchsorted(cdf, q, "left")``, which skips leading zero weights at ``q = 0`` — or the largest value of
+    positive weight if rounding leaves none.  The value returned always carries positive weight itself.  The result is NaN
+    where the bin has no value or ``W`` is not finite and positive, and a weight that is NaN or negative makes its own bin NaN
+    (numpy raises for negative weights and gives no meaningful answer for NaN weights or ``W = 0``; device data cannot be
+    checked without a synchronisation).  A NaN value contributes nothing, whatever its weight.
+
+    On weights whose float64 sums are exact in any order (fewer than 2^28 samples per bin) every element equals numpy's bit
+    for bit; zero results compare by value (numpy keeps the input order of ``-0.0`` and ``+0.0``).  On other weights the
+    float64 atomics add in arbitrary order, which moves ``C`` and ``W`` in their last bits: the result may then be a
+    neighbouring value of the bin, one whose cdf values bracket ``q`` within ``2 * gamma(n) + 2**-51`` (``gamma(n)`` the
+    any-order summation bound of the bin's ``n`` samples), and two runs may differ in the same way.
+
+    Rows of at most 2048 values are sorted in LDS with their weights; longer rows take a radix select over the values' keys
+    with per-digit sums of weights, in a fixed number of streaming passes.
+
+    Returns ``(quantiles, bin_edges)``: float64 with the shape ``histogram`` gives (kept axes, then bin axes), behind a leading
+    ``len(q)`` axis when ``q`` is 1-D.  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the
+    current stream), DeviceArray in -> numpy out, dask in -> a lazy dask array, one task per block: every reduced axis must
+    then be a single chunk."""
+    if method != "inverted_cdf":
+        raise ValueError("Only method 'inverted_cdf' supports weights. Got: %s." % (method,))
+    if weights is None:
+        raise TypeError("histogram_weighted_quantile needs weights")
+    qf, scalar, _ = _check_quantile_args(q, "linear")
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_weighted_quantile",
+                                                                   weights)
+    n_inputs = len(args)
+    if backend == "dask":
+        for a in all_arrays:
+            if any(len(a.chunks[ax]) > 1 for ax in drop_axes):
+                raise ValueError("exact quantiles of several chunks cannot be merged: rechunk the reduced axes of every input into "
+                                 "one chunk (e.g. arr.rechunk({axis: -1}))")
+        res = _values_blockwise(partial(_weighted_quantile_block, q=qf), len(qf), all_arrays, bins, axis, drop_axes)
+        res = res[(slice(None),) + tuple(0 if i in drop_axes else slice(None) for i in _range(all_arrays[0].ndim))]
+        return (res[0] if scalar else res), bins
+    if backend == "numpy":
+        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins, raw[n_inputs + 1])
+        out = _weighted_quantile_rows(arrays[:n_inputs], arrays[n_inputs], arrays[n_inputs + 1], axis, bins, "device", qf)
+    else:
+        out = _weighted_quantile_rows(all_arrays[:n_inputs], all_arrays[n_inputs], all_arrays[n_inputs + 1], axis, bins, backend, qf)
+    if backend == "torch":
+        keep = [s for i, s in enumerate(out.shape) if i - 1 not in drop_axes]
+        out = out.reshape(keep)
+        return (out[0] if scalar else out), bins
+    out = out.squeeze(tuple(a + 1 for a in drop_axes))
     return (out[0] if scalar else out), bins

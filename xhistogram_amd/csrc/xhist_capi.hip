@@ -6,6 +6,7 @@
 #include "xhist_extrema.hip.h"
 #include "xhist_meanvar.hip.h"
 #include "xhist_quantile.hip.h"
+#include "xhist_quantile_w.hip.h"
 
 #include <dlfcn.h>
 
@@ -356,6 +357,25 @@ extern "C" int xhist_plan_execute_quantile(xhist_plan* p, const xhist_array* sam
                           };
                           return xhist_quantile_run(pl, samples, values, n_rows, n_cols, q, n_q, method, out, alloc, &scratch, s, err,
                                                     err_cap, desc, desc_cap);
+                        });
+}
+
+extern "C" int xhist_plan_execute_quantile_weighted(xhist_plan* p, const xhist_array* samples, const xhist_array* values,
+                                                    const xhist_array* weights, int64_t n_rows, int64_t n_cols, const double* q, int n_q,
+                                                    double* out, int mem_kind, void* stream) {
+  if (n_q < 1 || !q) return fail(XHIST_ERR_INVALID, "q is NULL or n_q < 1");
+  if (!weights) return fail(XHIST_ERR_INVALID, "weights are required");
+  if (int rc = validate_arrays(p, samples, weights, n_rows, n_cols, out, XHIST_F64)) return rc;
+  return execute_values(p, "xhist_plan_execute_quantile_weighted", samples, values, n_rows, n_cols, out, true, "", mem_kind,
+                        [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
+                          hipStream_t s = static_cast<hipStream_t>(stream);
+                          ScratchScope scratch(s);
+                          auto alloc = [](void* ctx, size_t bytes) -> void* {
+                            void* d = nullptr;
+                            return static_cast<ScratchScope*>(ctx)->alloc(&d, bytes ? bytes : 8) == hipSuccess ? d : nullptr;
+                          };
+                          return xhist_quantile_w_run(pl, samples, values, weights, n_rows, n_cols, q, n_q, out, alloc, &scratch, s,
+                                                      err, err_cap, desc, desc_cap);
                         });
 }
 

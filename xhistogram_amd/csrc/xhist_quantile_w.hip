@@ -1,0 +1,296 @@
+// xhist_quantile_w.hip — exact weighted per-bin quantiles (histogram_weighted_quantile): the kernels of
+// xhist_quantile_w.hip.h, instantiated here and nowhere else, the steps between the binning passes, and the driver that orders
+// their launches (the choice and the binning geometry: xhist_values.hip.h).
+//
+// Instantiations (36 binning kernels + 3 short-row kernels + 4):
+//   qw_win_fast<ST, D, SCAN>, qw_digit_fast<ST, D, SCAN>    ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith      12 + 12
+//   qw_win_generic<CMP, LDS>, qw_digit_generic<CMP, LDS>    CMP 0 / 1 / 3, slots in LDS or sums in global memory       6 + 6
+//   qw_short<CMP>                                           CMP 0 / 1 / 3                                               3
+//   qw_window, qw_init, qw_select, qw_finalize                                                                          4
+// (and zero_words of xhist_kernels.hip.h, which is not dispatched)
+#include "xhist_quantile_w.hip.h"
+
+using namespace xhist;
+
+namespace xhist {
+
+// pass 0's records of one chunk, before the pass
+__global__ void __launch_bounds__(256) qw_window(const QWStep s) {
+  const int64_t n = s.rows * s.bins;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    s.win0[i] = QWWin{~0ull, 0ull, 0.0};
+  }
+}
+
+// pass 0 -> the targets of group s.qi0 .. s.qi0 + G - 1: settled at once where the result is NaN or the bin is constant
+__global__ void __launch_bounds__(256) qw_init(const QWStep s) {
+  const int64_t n = s.rows * s.bins * s.G;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const QWWin w = s.win0[i / s.G];
+    QWTgt x;
+    x.pre = w.mn;
+    x.below = 0.0;
+    x.w = w.w;
+    x.nfix = 64;
+    x.flags = 0;
+    if (!(w.mn <= w.mx && w.w > 0.0 && w.w < __builtin_inf())) {
+      x.flags = kQWNan;
+    } else if (w.mn != w.mx) {
+      x.nfix = (uint32_t)__builtin_clzll(w.mn ^ w.mx);
+      x.pre = w.mn & q_himask(x.nfix);
+      s.flags[1] = 1u;
+    }
+    s.tgt[i] = x;
+  }
+}
+
+// after digit pass s.pass: each active target takes the first bucket with a positive sum whose cdf value reaches q (the last
+// bucket with a positive sum if none does), and zeroes its sums
+__global__ void __launch_bounds__(256) qw_select(const QWStep s) {
+  if (!*reinterpret_cast<const volatile uint32_t*>(s.flags + 1 + s.pass)) return;
+  const int64_t n = s.rows * s.bins * s.G;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    QWTgt x = s.tgt[i];
+    if (x.nfix >= 64) continue;
+    const double q = s.q[i % s.G];
+    const uint32_t left = 64u - x.nfix, dd = left < (uint32_t)s.d ? left : (uint32_t)s.d;
+    double* c = s.sum + (i << s.d);
+    double cum = 0.0, under = 0.0;  // the running sum, and its value before the bucket taken
+    uint64_t dig = 0;
+    bool found = false;
+    for (uint32_t j = 0; j < (1u << dd); ++j) {
+      const double cj = c[j];
+      c[j] = 0.0;
+      if (found || !(cj > 0.0)) continue;
+      dig = j;
+      under = cum;
+      cum += cj;
+      found = qw_reached(x.below + cum, x.w, q);
+    }
+    x.below += under;
+    x.nfix += dd;
+    x.pre |= dig << (64u - x.nfix);
+    if (x.nfix < 64) s.flags[2 + s.pass] = 1u;
+    s.tgt[i] = x;
+  }
+}
+
+// the targets -> the value of each, into out[qi0 + t, row0 + row, bin]
+__global__ void __launch_bounds__(256) qw_finalize(const QWStep s) {
+  const int64_t n = s.rows * s.bins * s.G;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int t = (int)(i % s.G);
+    const int64_t rb = i / s.G, row = rb / s.bins, b = rb % s.bins;
+    const QWTgt x = s.tgt[i];
+    s.out[((int64_t)(s.qi0 + t) * s.n_rows_total + s.row0 + row) * s.bins + b] =
+        (x.flags & kQWNan) ? __builtin_nan("") : extrema_value64(x.pre);
+  }
+}
+
+}  // namespace xhist
+
+typedef void (*values_w_fn)(const WParams);
+
+// the binning kernels of each pass, for pick_values_kernel
+struct QWWinKernels {
+  template <typename ST, int D, int SCAN>
+  static values_w_fn fast() { return qw_win_fast<ST, D, SCAN>; }
+  template <int CMP, bool LDS>
+  static values_w_fn generic() { return qw_win_generic<CMP, LDS>; }
+};
+struct QWDigitKernels {
+  template <typename ST, int D, int SCAN>
+  static values_w_fn fast() { return qw_digit_fast<ST, D, SCAN>; }
+  template <int CMP, bool LDS>
+  static values_w_fn generic() { return qw_digit_generic<CMP, LDS>; }
+};
+
+namespace {
+
+// LDS bytes of a bin's slots: the window policy, and the digit policy with G targets of 2^d float64 sums
+constexpr size_t kWinBytes = 24;
+size_t digit_bytes(int G, int d) { return (size_t)G * (24 + ((size_t)8 << d)); }
+// the radix family's scratch per row of a chunk: pass 0's records, and per target its state and its sums
+size_t radix_row_bytes(int64_t bins, int G, int d) { return (size_t)bins * (sizeof(QWWin) + (size_t)G * (sizeof(QWTgt) + ((size_t)8 << d))); }
+
+struct Pass {
+  ValuesChoice c;
+  ValuesGeometry g;
+  values_w_fn fn = nullptr;
+};
+
+template <class K>
+int pick_pass(Pass& ps, const ValuesPlan& pl, size_t slot, const xhist_array* samples, const xhist_array* values,
+              const xhist_array* weights, int64_t rows, int64_t n_cols, const char* what, char* err, size_t err_cap) {
+  const ValuesSlots sl = {{slot, 0}, {slot, 0}, false};
+  ps.c = choose_values(pl, sl, samples, values, n_cols, weights);
+  ps.fn = pick_values_kernel<K>(ps.c, pl);
+  if (!ps.fn) {
+    snprintf(err, err_cap, "internal: no weighted quantile %s kernel for this combination", what);
+    return XHIST_ERR_HIP;
+  }
+  ps.g = values_geometry(pl, ps.c, rows, n_cols);
+  return allow_values_lds(ps.fn, ps.c.lds_bytes[0], "weighted quantile: setting the dynamic LDS size failed", err, err_cap);
+}
+
+// One binning pass over rows [r0, r0 + nr) of a chunk: `recs` the launch's records (Params::out), `tgt` the targets (w2_ptr),
+// `flag` its flag word, T targets per bin, digits of d bits.
+int launch_qw_pass(const Pass& ps, const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
+                   int64_t r0, int64_t nr, int64_t n_cols, void* recs, size_t rec_row_bytes, const QWTgt* tgt, uint32_t* flag, int T, int d,
+                   hipStream_t stream, const char* what, char* err, size_t err_cap) {
+  for (int64_t k = 0; k < nr; k += ps.g.max_rows) {
+    const int64_t n = std::min(ps.g.max_rows, nr - k);
+    WParams kp;
+    static_cast<Params&>(kp) = values_params(pl, ps.c, ps.g.segs, samples, values, r0 + k, n, n_cols);
+    weights_params(kp, weights);
+    kp.out = static_cast<char*>(recs) + k * rec_row_bytes;
+    kp.w2_ptr = reinterpret_cast<const uint64_t*>(tgt ? tgt + k * pl.n_bins * T : nullptr);
+    kp.part_counts = flag;
+    kp.n_parts = T;
+    kp.part_shift = d;
+    XH_VALUES_LAUNCH(ps.fn, dim3((unsigned)(n * ps.g.segs)), dim3(ps.g.block), ps.c.lds_bytes[0], stream, kp);
+    XH_VALUES_LAUNCH_CHECK(what);
+  }
+  return XHIST_OK;
+}
+
+}  // namespace
+
+int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
+                         int64_t n_rows, int64_t n_cols, const double* q, int n_q, double* out, xhist_quantile_alloc_fn alloc,
+                         void* alloc_ctx, hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap) {
+  ValuesPlan pl = pl_in;
+  pl.lds_max -= 64;  // (the launch header q_hdr() is static LDS next to the dynamic slots)
+  const int64_t bins = pl.n_bins;
+  const int cmp = values_cmp(pl);
+  QWStep st;
+  memset(&st, 0, sizeof st);
+  st.bins = bins;
+  st.n_rows_total = n_rows;
+  st.out = out;
+
+  // ---- short rows: one workgroup sorts whole rows in LDS -------------------------------------------------------------------
+  if (n_cols <= kQWShortCols) {
+    const int64_t R = std::max<int64_t>(1, std::min<int64_t>(kQWShortCols / std::max<int64_t>(n_cols, 1), (((int64_t)1 << 32) - 2) / bins));
+    uint32_t N = 2;
+    while (N < (uint32_t)(R * n_cols)) N <<= 1;
+    const size_t lds = (size_t)N * 20;
+    if (lds > 48 * 1024) return values_error(err, err_cap, XHIST_ERR_HIP, "internal: weighted short-row LDS", hipErrorInvalidValue);
+    const int64_t max_wg = ((int64_t)1 << 31) - 1;
+    for (int g0 = 0; g0 < n_q; g0 += kQGroup) {
+      st.qi0 = g0;
+      st.G = std::min(kQGroup, n_q - g0);
+      for (int t = 0; t < st.G; ++t) st.q[t] = q[g0 + t];
+      for (int64_t r0 = 0; r0 < n_rows; r0 += max_wg * R) {
+        const int64_t nr = std::min(max_wg * R, n_rows - r0);
+        ValuesChoice c;
+        c.tab = &pl.native;
+        WParams kp;
+        static_cast<Params&>(kp) = values_params(pl, c, 1, samples, values, r0, nr, n_cols);
+        weights_params(kp, weights);
+        kp.tables_in_lds = 0;  // (the tables are read through L2)
+        kp.lane_rows = (int32_t)R;
+        kp.slice_n = (int32_t)N;
+        const dim3 grid((unsigned)((nr + R - 1) / R));
+        if (cmp == 0) XH_VALUES_LAUNCH(qw_short<0>, grid, dim3(256), lds, stream, kp, st);
+        else if (cmp == 1) XH_VALUES_LAUNCH(qw_short<1>, grid, dim3(256), lds, stream, kp, st);
+        else XH_VALUES_LAUNCH(qw_short<3>, grid, dim3(256), lds, stream, kp, st);
+        XH_VALUES_LAUNCH_CHECK("qw_short launch");
+      }
+    }
+    if (desc && desc_cap)
+      snprintf(desc, desc_cap, "weighted_quantile family=short rows_per_wg=%lld triples=%u lds_bytes=%zu groups=%d block=256 D=%d cmp=%d",
+               (long long)R, N, lds, (n_q + kQGroup - 1) / kQGroup, pl.n_dims, cmp);
+    return XHIST_OK;
+  }
+
+  // ---- long rows: radix select -------------------------------------------------------------------------------------------
+  // The group size G and the digit width d, by the rule of the unweighted family over the 8-byte sums: the fewest streaming
+  // passes, groups x ceil(64 / d) (ties: the wider d), first over the (G, d) whose digit pass takes at most kQLdsBudget of
+  // LDS, then over those that fit LDS at all, both with d >= 4; if none does, sums in global memory, under the scratch cap.
+  int G = 0, d = 0;
+  int64_t best = INT64_MAX;
+  for (int tier = 0; tier < 3 && !G; ++tier) {
+    for (int g = std::min(kQGroup, n_q); g >= 1; --g)
+      for (int dd = 8; dd >= (tier < 2 ? 4 : 1); --dd) {
+        const int64_t cost = (int64_t)((n_q + g - 1) / g) * ((64 + dd - 1) / dd);
+        if (cost >= best) continue;
+        if (radix_row_bytes(bins, g, dd) > kQScratchCap && !(g == 1 && dd == 1)) continue;
+        const ValuesSlots sl = {{digit_bytes(g, dd), 0}, {digit_bytes(g, dd), 0}, false};
+        const ValuesChoice c = choose_values(pl, sl, samples, values, n_cols, weights);
+        if (c.lds != (tier < 2) || (tier == 0 && c.lds_bytes[0] > kQLdsBudget)) continue;
+        best = cost;
+        G = g;
+        d = dd;
+      }
+  }
+  Pass digit, win0;
+  const int passes = (64 + d - 1) / d;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_rows, (int64_t)(kQScratchCap / radix_row_bytes(bins, G, d))));
+  if ((uint64_t)chunk * (uint64_t)bins >> 32) {  // (the no-LDS window kernel indexes a launch's records in 32 bits)
+    snprintf(err, err_cap, "weighted quantiles of %lld bins are not supported (at most 2^32 - 1)", (long long)bins);
+    return XHIST_ERR_UNSUPPORTED;
+  }
+  if (int rc = pick_pass<QWDigitKernels>(digit, pl, digit_bytes(G, d), samples, values, weights, chunk, n_cols, "digit", err, err_cap)) return rc;
+  if (int rc = pick_pass<QWWinKernels>(win0, pl, kWinBytes, samples, values, weights, chunk, n_cols, "window", err, err_cap)) return rc;
+
+  const size_t n_rb = (size_t)chunk * bins;
+  QWWin* w0 = static_cast<QWWin*>(alloc(alloc_ctx, n_rb * sizeof(QWWin)));
+  QWTgt* tg = static_cast<QWTgt*>(alloc(alloc_ctx, n_rb * G * sizeof(QWTgt)));
+  double* sum = static_cast<double*>(alloc(alloc_ctx, (n_rb * G << d) * 8));
+  uint32_t* flags = static_cast<uint32_t*>(alloc(alloc_ctx, 8 * ((size_t)passes + 8)));
+  if (!w0 || !tg || !sum || !flags) {
+    snprintf(err, err_cap, "allocation of the weighted quantile scratch (%zu bytes per chunk) failed", radix_row_bytes(bins, G, d) * chunk);
+    return XHIST_ERR_NOMEM;
+  }
+  const int64_t n_flag_words = (2 + passes + 1) / 2;  // flags: [1 + j] digit pass j (and the word qw_select writes last)
+  hipLaunchKernelGGL(zero_words, dim3(2048), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(sum), (int64_t)(n_rb * G << d));
+  XH_VALUES_LAUNCH_CHECK("weighted quantile zeroing launch");
+  st.tgt = tg;
+  st.win0 = w0;
+  st.sum = sum;
+  st.flags = flags;
+  st.d = d;
+  for (int64_t r0 = 0; r0 < n_rows; r0 += chunk) {
+    const int64_t nr = std::min(chunk, n_rows - r0);
+    st.rows = nr;
+    st.row0 = r0;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (nr * bins * G + 255) / 256));
+    XH_VALUES_LAUNCH(qw_window, dim3(grid), dim3(256), 0, stream, st);
+    XH_VALUES_LAUNCH_CHECK("qw_window launch");
+    if (int rc = launch_qw_pass(win0, pl, samples, values, weights, r0, nr, n_cols, w0, bins * sizeof(QWWin), nullptr, flags, 1, d, stream,
+                                "weighted quantile window launch", err, err_cap))
+      return rc;
+    for (int g0 = 0; g0 < n_q; g0 += G) {
+      st.qi0 = g0;
+      st.G = std::min(G, n_q - g0);
+      for (int t = 0; t < st.G; ++t) st.q[t] = q[g0 + t];
+      // the flags of the digit passes start at zero for every group
+      hipLaunchKernelGGL(zero_words, dim3(1), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(flags), n_flag_words);
+      XH_VALUES_LAUNCH_CHECK("weighted quantile zeroing launch");
+      XH_VALUES_LAUNCH(qw_init, dim3(grid), dim3(256), 0, stream, st);
+      XH_VALUES_LAUNCH_CHECK("qw_init launch");
+      for (int j = 0; j < passes; ++j) {
+        st.pass = j;
+        if (int rc = launch_qw_pass(digit, pl, samples, values, weights, r0, nr, n_cols, sum, ((size_t)bins * st.G * 8) << d, tg,
+                                    flags + 1 + j, st.G, d, stream, "weighted quantile digit launch", err, err_cap))
+          return rc;
+        XH_VALUES_LAUNCH(qw_select, dim3(grid), dim3(256), 0, stream, st);
+        XH_VALUES_LAUNCH_CHECK("qw_select launch");
+      }
+      XH_VALUES_LAUNCH(qw_finalize, dim3(grid), dim3(256), 0, stream, st);
+      XH_VALUES_LAUNCH_CHECK("qw_finalize launch");
+    }
+  }
+  if (desc && desc_cap) {
+    auto fam = [](const Pass& p) { return p.c.fast ? "fast" : "generic"; };
+    auto home = [](const Pass& p) { return p.c.lds ? "lds" : "global"; };
+    snprintf(desc, desc_cap,
+             "weighted_quantile family=radix window=%s/%s digits=%s/%s scan=%d/%d d=%d group=%d groups=%d passes=%d chunks=%lld "
+             "rows_per_chunk=%lld block=%d segs=%lld lds_bytes=%zu/%zu D=%d cmp=%d",
+             fam(win0), home(win0), fam(digit), home(digit), win0.c.scan, digit.c.scan, d, G, (n_q + G - 1) / G, passes,
+             (long long)((n_rows + chunk - 1) / chunk), (long long)chunk, digit.g.block, (long long)digit.g.segs, win0.c.lds_bytes[0],
+             digit.c.lds_bytes[0], pl.n_dims, cmp);
+  }
+  return XHIST_OK;
+}

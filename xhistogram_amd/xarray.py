@@ -13,7 +13,7 @@ import numpy as np
 from .core import histogram as _core_histogram
 from .core import histogram_two_weights as _core_histogram_two_weights
 
-__all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile"]
+__all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile"]
 
 
 def _xr():
@@ -190,6 +190,29 @@ def histogram_quantile(*args, values, q, bins=None, range=None, dim=None, method
         out_dims = ["quantile"] + list(out_dims)
         coords = dict(coords, quantile=(("quantile",), qa))
     return xr.DataArray(res, dims=out_dims, coords=coords, name="%s_quantile" % base)
+
+
+def histogram_weighted_quantile(*args, values, weights, q, bins=None, range=None, dim=None, method="inverted_cdf", block_size="auto",
+                                keep_coords=False, bin_dim_suffix="_bin"):
+    """Weighted per-bin quantiles of the DataArray ``values`` over the bins of ``args``
+    (:func:`xhistogram_amd.core.histogram_weighted_quantile` with the labels of :func:`histogram_quantile`).
+
+    ``weights`` is a DataArray whose dims are a subset of the data's, aligned and broadcast as ``values`` is (cell areas or
+    volumes, ``cos(lat)``); ``method`` accepts only ``"inverted_cdf"``.  Returns one DataArray named
+    ``<values name>_weighted_quantile`` with the ``quantile`` dimension or scalar coordinate of :func:`histogram_quantile`."""
+    from .core import histogram_weighted_quantile as _core_histogram_weighted_quantile
+
+    (res,), out_dims, coords, base = _values_statistic(
+        "histogram_weighted_quantile", _core_histogram_weighted_quantile, args, values, bins, range, dim, keep_coords, bin_dim_suffix,
+        q=q, method=method, block_size=block_size, weights=weights)
+    xr = _xr()
+    qa = np.asarray(q, dtype=np.float64)
+    if qa.ndim == 0:
+        coords = dict(coords, quantile=((), qa))
+    else:
+        out_dims = ["quantile"] + list(out_dims)
+        coords = dict(coords, quantile=(("quantile",), qa))
+    return xr.DataArray(res, dims=out_dims, coords=coords, name="%s_weighted_quantile" % base)
 
 def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords, bin_dim_suffix, weights=None, **kw):
     """a per-bin statistic of ``values`` with the labels of :func:`histogram`: (core_fn's arrays, dims, coords, the values'
