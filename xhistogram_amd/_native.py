@@ -395,13 +395,15 @@ class Plan:
             )
         )
 
+    def _quantile_args(self, sample_views, q):
+        """the C array of the samples' views, and q as a contiguous 1-D float64 array"""
+        return self._sample_array(sample_views), np.ascontiguousarray(q, dtype=np.float64).ravel()
 
     def execute_quantile(self, sample_views, value_view, n_rows, n_cols, out_ptr, q, method, stream=0):
         """per-bin quantiles q (host float64 values in [0, 1]) of the values of device-resident views by numpy's `method` code
         (QUANTILE_METHODS index; NaN where no value arrived), into a float64 device buffer [len(q), n_rows, bins], asynchronous
         on `stream` (xhist_plan_execute_quantile)"""
-        arr = self._sample_array(sample_views)
-        qa = np.ascontiguousarray(q, dtype=np.float64).ravel()
+        arr, qa = self._quantile_args(sample_views, q)
         check(
             load().xhist_plan_execute_quantile(
                 self._h, arr, C.byref(value_view), int(n_rows), int(n_cols), qa.ctypes.data_as(C.POINTER(C.c_double)), int(qa.size),
@@ -414,8 +416,7 @@ class Plan:
         device-resident views, into a float64 device buffer [len(q), n_rows, bins] (NaN where the bin has no value, its weights
         do not sum to a finite positive number, or one of them is NaN or negative), asynchronous on `stream`
         (xhist_plan_execute_quantile_weighted)"""
-        arr = self._sample_array(sample_views)
-        qa = np.ascontiguousarray(q, dtype=np.float64).ravel()
+        arr, qa = self._quantile_args(sample_views, q)
         check(
             load().xhist_plan_execute_quantile_weighted(
                 self._h, arr, C.byref(value_view), C.byref(weight_view), int(n_rows), int(n_cols),

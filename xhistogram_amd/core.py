@@ -1879,6 +1879,21 @@ def _value_stat_block(*all_arrays, stat=None, axis=None, bins=None):
     return np.stack([a.astype(np.float64, copy=False) for a in outs])
 
 
+def _resident(backend, raw, all_arrays, n_inputs, bins):
+    """the arrays a rows function takes, and the backend it takes them as: numpy inputs (`raw`) uploaded to the calling thread's
+    GPU ("device"), torch tensors and DeviceArrays as they are"""
+    if backend == "numpy":
+        return _upload_host(raw[:n_inputs], raw[n_inputs], bins, *raw[n_inputs + 1:]), "device"
+    return all_arrays, backend
+
+
+def _drop_axes(a, axes, backend):
+    """a rows function's output without its reduced axes (of extent 1)"""
+    if backend == "torch":
+        return a.reshape([s for i, s in enumerate(a.shape) if i not in axes])
+    return a.squeeze(axes)
+
+
 def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, weights=None):
     """the backends of a per-bin statistic of values: (backend, the outputs with the shape ``histogram`` gives, bin edges,
     reduced axes).  dask: lazy float64 arrays, the partials merged by stat.reduce and the last step by `aggregate`."""
@@ -1892,15 +1907,9 @@ def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, wei
         res = dsa.reduction(partials, st.reduce, aggregate or st.reduce, combine=st.reduce, axis=tuple(ax + 1 for ax in drop_axes),
                             keepdims=False, dtype=np.float64, concatenate=True, meta=np.array((), np.float64))
         return backend, [res[i] for i in _range(st.k)], bins, drop_axes
-    if backend == "numpy":
-        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins, *raw[n_inputs + 1:])
-        outs = _value_stat_rows(st, arrays[:n_inputs], arrays[n_inputs], axis, bins, "device", *arrays[n_inputs + 1:])
-    else:
-        outs = _value_stat_rows(st, all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend, *all_arrays[n_inputs + 1:])
-    if backend == "torch":
-        keep = [s for i, s in enumerate(outs[0].shape) if i not in drop_axes]
-        return backend, [a.reshape(keep) for a in outs], bins, drop_axes
-    return backend, [a.squeeze(drop_axes) for a in outs], bins, drop_axes
+    arrays, on = _resident(backend, raw, all_arrays, n_inputs, bins)
+    outs = _value_stat_rows(st, arrays[:n_inputs], arrays[n_inputs], axis, bins, on, *arrays[n_inputs + 1:])
+    return backend, [_drop_axes(a, drop_axes, backend) for a in outs], bins, drop_axes
 
 
 def histogram_extrema(*args, values, bins=None, range=None, axis=None, block_size="auto"):
@@ -2002,55 +2011,46 @@ def _check_ddof(ddof):
     return int(ddof)
 
 
+def _chan_merge(x, mean, m2, axis, present):
+    """Chan's pairwise merge of partial (x, mean, M2) results over `axis` (kept as axes of extent 1), one partial after another
+    in index order (C order over several axes); x is the count or the sum of weights, and present(x) says where a partial (or
+    the running result) holds something.  Returns float64 (x, mean, M2)."""
+    x, mean, m2 = (np.asarray(a, np.float64) for a in (x, mean, m2))
+    ax = tuple(sorted(int(a) % x.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
+    rest = [i for i in _range(x.ndim) if i not in ax]
+    keep_shape = tuple(1 if i in ax else x.shape[i] for i in _range(x.ndim))
+
+    def lead(a):
+        a = np.transpose(a, ax + tuple(rest))
+        return a.reshape((-1,) + a.shape[len(ax):])
+
+    x, mean, m2 = lead(x), lead(mean), lead(m2)
+    cx = np.zeros(x.shape[1:])
+    cm = np.full(x.shape[1:], np.nan)
+    cq = np.full(x.shape[1:], np.nan)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for k in _range(x.shape[0]):
+            xb, mb, qb = x[k], mean[k], m2[k]
+            take = present(xb)
+            first = take & ~present(cx)
+            both = take & present(cx)
+            tot = cx + xb
+            d = mb - cm
+            m_new = cm + d * xb / tot
+            q_new = cq + qb + d * d * cx * xb / tot
+            cm = np.where(first, mb, np.where(both, m_new, cm))
+            cq = np.where(first, qb, np.where(both, q_new, cq))
+            cx = np.where(take, tot, cx)
+    return cx.reshape(keep_shape), cm.reshape(keep_shape), cq.reshape(keep_shape)
+
+
 def combine_mean_var(n, mean, m2, axis):
     """Merge partial (count, mean, M2) results over `axis` (kept as axes of extent 1) with Chan's pairwise formula, one
     partial after another in index order (C order over several axes):
         n = na + nb,  d = mb - ma,  mean = ma + d * nb / n,  M2 = M2a + M2b + d^2 * na * nb / n.
     Partials with n == 0 are skipped; where every partial is empty, mean and M2 are NaN and n is 0.  The reduction of dask's
     partials.  Returns float64 (n, mean, M2)."""
-    n, mean, m2 = (np.asarray(a, np.float64) for a in (n, mean, m2))
-    ax = tuple(sorted(int(a) % n.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
-    rest = [i for i in _range(n.ndim) if i not in ax]
-    keep_shape = tuple(1 if i in ax else n.shape[i] for i in _range(n.ndim))
-
-    def lead(a):
-        a = np.transpose(a, ax + tuple(rest))
-        return a.reshape((-1,) + a.shape[len(ax):])
-
-    n, mean, m2 = lead(n), lead(mean), lead(m2)
-    cn = np.zeros(n.shape[1:])
-    cm = np.full(n.shape[1:], np.nan)
-    cq = np.full(n.shape[1:], np.nan)
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        for k in _range(n.shape[0]):
-            nb, mb, qb = n[k], mean[k], m2[k]
-            take = nb > 0
-            first = take & (cn == 0)
-            both = take & (cn > 0)
-            tot = cn + nb
-            d = mb - cm
-            m_new = cm + d * nb / tot
-            q_new = cq + qb + d * d * cn * nb / tot
-            cm = np.where(first, mb, np.where(both, m_new, cm))
-            cq = np.where(first, qb, np.where(both, q_new, cq))
-            cn = np.where(take, tot, cn)
-    return cn.reshape(keep_shape), cm.reshape(keep_shape), cq.reshape(keep_shape)
-
-
-def _mean_var_reduce(x, axis=None, keepdims=True, **_):
-    """dask.array.reduction step over [3, ...] blocks of (n, mean, M2) partials"""
-    ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
-    out = np.stack(combine_mean_var(x[0], x[1], x[2], tuple(a - 1 for a in ax)))
-    return out if keepdims else out.squeeze(ax)
-
-
-def _mean_var_aggregate(x, axis=None, keepdims=True, ddof=0, **_):
-    """the last step: (n, mean, var), the division by n - ddof done here only"""
-    out = _mean_var_reduce(x, axis=axis, keepdims=keepdims)
-    n = out[0]
-    with np.errstate(invalid="ignore", divide="ignore"):
-        out[2] = np.where(n > ddof, out[2] / (n - ddof), np.nan)
-    return out
+    return _chan_merge(n, mean, m2, axis, lambda a: a > 0)
 
 
 def combine_weighted_mean_var(w, mean, m2, axis):
@@ -2059,49 +2059,47 @@ def combine_weighted_mean_var(w, mean, m2, axis):
         W = Wa + Wb,  d = mb - ma,  mean = ma + d * Wb / W,  M2 = M2a + M2b + d^2 * Wa * Wb / W.
     Partials with W == 0 are skipped; a NaN partial (a NaN W among them) makes the bin NaN.  Where every partial has W == 0,
     mean and M2 are NaN and W is 0.  The reduction of dask's weighted partials.  Returns float64 (W, mean, M2)."""
-    w, mean, m2 = (np.asarray(a, np.float64) for a in (w, mean, m2))
-    ax = tuple(sorted(int(a) % w.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
-    rest = [i for i in _range(w.ndim) if i not in ax]
-    keep_shape = tuple(1 if i in ax else w.shape[i] for i in _range(w.ndim))
+    return _chan_merge(w, mean, m2, axis, lambda a: a != 0)  # (NaN != 0: a NaN partial is taken, and its NaN spreads)
 
-    def lead(a):
-        a = np.transpose(a, ax + tuple(rest))
-        return a.reshape((-1,) + a.shape[len(ax):])
 
-    w, mean, m2 = lead(w), lead(mean), lead(m2)
-    cw = np.zeros(w.shape[1:])
-    cm = np.full(w.shape[1:], np.nan)
-    cq = np.full(w.shape[1:], np.nan)
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        for k in _range(w.shape[0]):
-            wb, mb, qb = w[k], mean[k], m2[k]
-            take = wb != 0  # (NaN != 0: a NaN partial is taken, and its NaN spreads)
-            first = take & (cw == 0)
-            both = take & (cw != 0)
-            tot = cw + wb
-            d = mb - cm
-            m_new = cm + d * wb / tot
-            q_new = cq + qb + d * d * cw * wb / tot
-            cm = np.where(first, mb, np.where(both, m_new, cm))
-            cq = np.where(first, qb, np.where(both, q_new, cq))
-            cw = np.where(take, tot, cw)
-    return cw.reshape(keep_shape), cm.reshape(keep_shape), cq.reshape(keep_shape)
+def _var_of(x, m2, ddof):
+    """the variance M2 / (x - ddof) of numpy arrays or torch tensors, x the count or the sum of weights: NaN where x <= ddof"""
+    if _is_torch(m2):
+        torch = _torch()
+        return torch.where(x > ddof, m2 / (x - ddof).to(torch.float64), torch.full_like(m2, float("nan")))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(x > ddof, m2 / (x - ddof), np.nan)
+
+
+def _chan_reduce(combine, x, axis, keepdims, ddof=None):
+    """dask.array.reduction step over [3, ...] blocks of (x, mean, M2) partials merged by `combine`; with ddof, the last step:
+    (x, mean, var), the division by x - ddof done here only"""
+    ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
+    out = np.stack(combine(x[0], x[1], x[2], tuple(a - 1 for a in ax)))
+    out = out if keepdims else out.squeeze(ax)
+    if ddof is not None:
+        out[2] = _var_of(out[0], out[2], ddof)
+    return out
+
+
+def _mean_var_reduce(x, axis=None, keepdims=True, **_):
+    """dask.array.reduction step over [3, ...] blocks of (n, mean, M2) partials"""
+    return _chan_reduce(combine_mean_var, x, axis, keepdims)
+
+
+def _mean_var_aggregate(x, axis=None, keepdims=True, ddof=0, **_):
+    """the last step: (n, mean, var), the division by n - ddof done here only"""
+    return _chan_reduce(combine_mean_var, x, axis, keepdims, ddof)
 
 
 def _mean_var_w_reduce(x, axis=None, keepdims=True, **_):
     """dask.array.reduction step over [3, ...] blocks of weighted (W, mean, M2) partials"""
-    ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
-    out = np.stack(combine_weighted_mean_var(x[0], x[1], x[2], tuple(a - 1 for a in ax)))
-    return out if keepdims else out.squeeze(ax)
+    return _chan_reduce(combine_weighted_mean_var, x, axis, keepdims)
 
 
 def _mean_var_w_aggregate(x, axis=None, keepdims=True, ddof=0, **_):
     """the last weighted step: (W, mean, var), the division by W - ddof done here only"""
-    out = _mean_var_w_reduce(x, axis=axis, keepdims=keepdims)
-    w = out[0]
-    with np.errstate(invalid="ignore", divide="ignore"):
-        out[2] = np.where(w > ddof, out[2] / (w - ddof), np.nan)
-    return out
+    return _chan_reduce(combine_weighted_mean_var, x, axis, keepdims, ddof)
 
 
 def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, weights=None, block_size="auto"):
@@ -2136,31 +2134,14 @@ def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, 
     three float64 (W, the census of the samples that carry a value, takes the place of the count), with the same shapes and
     backends; dask merges the blocks' partials with :func:`combine_weighted_mean_var`."""
     ddof = _check_ddof(ddof)
-    if weights is not None:
-        backend, (wsum, mean, m2), bins, _ = _value_stat("mean_var_w", args, values, bins, range, axis, "histogram_mean_var",
-                                                        partial(_mean_var_w_aggregate, ddof=ddof), weights=weights)
-        if backend == "dask":
-            return wsum, mean, m2, bins
-        if backend == "torch":
-            torch = _torch()
-            var = torch.where(wsum > ddof, m2 / (wsum - ddof), torch.full_like(m2, float("nan")))
-            return wsum, mean, var, bins
-        with np.errstate(invalid="ignore", divide="ignore"):
-            var = np.where(wsum > ddof, m2 / (wsum - ddof), np.nan)
-        return wsum, mean, var, bins
-    # dask: one task per block with its (n, mean, M2) on a leading axis; the partials of the blocks that share output rows are
-    # merged on the host in block order (Chan), and the last step divides by n - ddof
-    backend, (cnt, mean, m2), bins, _ = _value_stat("mean_var", args, values, bins, range, axis, "histogram_mean_var",
-                                                   partial(_mean_var_aggregate, ddof=ddof))
+    # dask: one task per block with its (n, mean, M2) or (W, mean, M2) on a leading axis; the partials of the blocks that share
+    # output rows are merged on the host in block order (Chan), and the last step divides by n - ddof (W - ddof)
+    stat, aggregate = ("mean_var", _mean_var_aggregate) if weights is None else ("mean_var_w", _mean_var_w_aggregate)
+    backend, (x, mean, m2), bins, _ = _value_stat(stat, args, values, bins, range, axis, "histogram_mean_var",
+                                                 partial(aggregate, ddof=ddof), weights=weights)
     if backend == "dask":
-        return cnt.astype(np.int64), mean, m2, bins
-    if backend == "torch":
-        torch = _torch()
-        var = torch.where(cnt > ddof, m2 / (cnt - ddof).to(torch.float64), torch.full_like(m2, float("nan")))
-        return cnt, mean, var, bins
-    with np.errstate(invalid="ignore", divide="ignore"):
-        var = np.where(cnt > ddof, m2 / (cnt - ddof), np.nan)
-    return cnt, mean, var, bins
+        return (x.astype(np.int64) if weights is None else x), mean, m2, bins
+    return x, mean, _var_of(x, m2, ddof), bins
 
 
 _VALUE_STATS = {
@@ -2188,29 +2169,58 @@ def _check_quantile_args(q, method):
     return qf, qa.ndim == 0, _native.QUANTILE_METHODS.index(method)
 
 
-def _quantile_rows(args, values, axis, bins, backend, q, code):
-    """[len(q), kept axes (reduced ones of extent 1), bins...] float64 quantiles of broadcast torch tensors (torch out) or
-    DeviceArrays (numpy out)"""
-    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend)
+def _quantile_rows(args, values, axis, bins, backend, q, code, weights=None):
+    """[len(q), kept axes (reduced ones of extent 1), bins...] float64 quantiles (weighted ones, if weights are given) of
+    broadcast torch tensors (torch out) or DeviceArrays (numpy out)"""
+    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, weights)
     n = m * plan.n_bins
     shape = (len(q),) + kept_axes_shape + plan.bins_shape
+
+    def execute(out_ptr):
+        if weights is None:
+            plan.execute_quantile(nv[:-1], nv[-1], m, c, out_ptr, q, code, stream=stream)
+        else:
+            plan.execute_quantile_weighted(nv[:-2], nv[-2], nv[-1], m, c, out_ptr, q, stream=stream)
+
     if backend == "torch":
         out = _torch().empty(shape, dtype=_torch().float64, device=args[0].device)
         if n > 0 and len(q):
-            plan.execute_quantile(nv[:-1], nv[-1], m, c, out.data_ptr(), q, code, stream=stream)
+            execute(out.data_ptr())
         return out
     host = np.empty(shape, np.float64)
     if n > 0 and len(q):
         buf = _native.DeviceBuffer(device, len(q) * n * 8)
-        plan.execute_quantile(nv[:-1], nv[-1], m, c, buf.ptr, q, code, stream=stream)
+        execute(buf.ptr)
         buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
     return host
 
 
-def _quantile_block(*all_arrays, axis=None, bins=None, q=None, code=0):
-    """one dask block, complete along the reduced axes: its quantiles [len(q), block axes (reduced ones of extent 1), bins...]"""
-    arrays = _upload_host(all_arrays[:-1], all_arrays[-1], bins)
-    return _quantile_rows(arrays[:-1], arrays[-1], axis, bins, "device", q, code)
+def _quantile_block(*all_arrays, axis=None, bins=None, q=None, code=0, weighted=False):
+    """one dask block (samples..., values[, weights]), complete along the reduced axes: its quantiles [len(q), block axes
+    (reduced ones of extent 1), bins...]"""
+    n = len(all_arrays) - 1 - int(weighted)
+    arrays = _upload_host(all_arrays[:n], all_arrays[n], bins, *all_arrays[n + 1:])
+    return _quantile_rows(arrays[:n], arrays[n], axis, bins, "device", q, code, *arrays[n + 1:])
+
+
+def _quantile_call(args, values, bins, range, axis, name, qf, scalar, code, weights=None):
+    """the backends of the per-bin quantiles qf (checked; `scalar`: q was one), after the function's own argument checks:
+    (quantiles with the shape ``histogram`` gives behind the q axis, bin edges)"""
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, weights)
+    n_inputs = len(args)
+    if backend == "dask":
+        for a in all_arrays:
+            if any(len(a.chunks[ax]) > 1 for ax in drop_axes):
+                raise ValueError("exact quantiles of several chunks cannot be merged: rechunk the reduced axes of every input into "
+                                 "one chunk (e.g. arr.rechunk({axis: -1}))")
+        res = _values_blockwise(partial(_quantile_block, q=qf, code=code, weighted=weights is not None), len(qf), all_arrays, bins,
+                                axis, drop_axes)
+        res = res[(slice(None),) + tuple(0 if i in drop_axes else slice(None) for i in _range(all_arrays[0].ndim))]
+    else:
+        arrays, on = _resident(backend, raw, all_arrays, n_inputs, bins)
+        res = _quantile_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, on, qf, code, *arrays[n_inputs + 1:])
+        res = _drop_axes(res, tuple(a + 1 for a in drop_axes), backend)
+    return (res[0] if scalar else res), bins
 
 
 def histogram_quantile(*args, values, q, bins=None, range=None, axis=None, method="linear", block_size="auto", weights=None,
@@ -2236,60 +2246,12 @@ def histogram_quantile(*args, values, q, bins=None, range=None, axis=None, metho
     if density is not None:
         raise TypeError("histogram_quantile does not take density")
     qf, scalar, code = _check_quantile_args(q, method)
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_quantile")
-    n_inputs = len(args)
-    lead = (0,) if scalar else ()
-    if backend == "dask":
-        for a in all_arrays:
-            if any(len(a.chunks[ax]) > 1 for ax in drop_axes):
-                raise ValueError("exact quantiles of several chunks cannot be merged: rechunk the reduced axes of every input into "
-                                 "one chunk (e.g. arr.rechunk({axis: -1}))")
-        res = _values_blockwise(partial(_quantile_block, q=qf, code=code), len(qf), all_arrays, bins, axis, drop_axes)
-        res = res[(slice(None),) + tuple(0 if i in drop_axes else slice(None) for i in _range(all_arrays[0].ndim))]
-        return (res[0] if scalar else res), bins
-    if backend == "numpy":
-        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins)
-        out = _quantile_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, "device", qf, code)
-    else:
-        out = _quantile_rows(all_arrays[:n_inputs], all_arrays[n_inputs], axis, bins, backend, qf, code)
-    squeeze = tuple(a + 1 for a in drop_axes)
-    if backend == "torch":
-        keep = [s for i, s in enumerate(out.shape) if i - 1 not in drop_axes]
-        out = out.reshape(keep)
-        return (out[0] if scalar else out), bins
-    out = out.squeeze(squeeze)
-    return (out[0] if scalar else out), bins
+    return _quantile_call(args, values, bins, range, axis, "histogram_quantile", qf, scalar, code)
 
 
 # ---------------------------------------------------------------------------------------------
 # weighted per-bin quantiles of a value array
 # ---------------------------------------------------------------------------------------------
-def _weighted_quantile_rows(args, values, weights, axis, bins, backend, q):
-    """[len(q), kept axes (reduced ones of extent 1), bins...] float64 weighted quantiles of broadcast torch tensors (torch out)
-    or DeviceArrays (numpy out)"""
-    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, weights)
-    n = m * plan.n_bins
-    shape = (len(q),) + kept_axes_shape + plan.bins_shape
-    if backend == "torch":
-        out = _torch().empty(shape, dtype=_torch().float64, device=args[0].device)
-        if n > 0 and len(q):
-            plan.execute_quantile_weighted(nv[:-2], nv[-2], nv[-1], m, c, out.data_ptr(), q, stream=stream)
-        return out
-    host = np.empty(shape, np.float64)
-    if n > 0 and len(q):
-        buf = _native.DeviceBuffer(device, len(q) * n * 8)
-        plan.execute_quantile_weighted(nv[:-2], nv[-2], nv[-1], m, c, buf.ptr, q, stream=stream)
-        buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
-    return host
-
-
-def _weighted_quantile_block(*all_arrays, axis=None, bins=None, q=None):
-    """one dask block, complete along the reduced axes: its weighted quantiles [len(q), block axes (reduced ones of extent 1),
-    bins...]"""
-    arrays = _upload_host(all_arrays[:-2], all_arrays[-2], bins, all_arrays[-1])
-    return _weighted_quantile_rows(arrays[:-2], arrays[-2], arrays[-1], axis, bins, "device", q)
-
-
 def histogram_weighted_quantile(*args, values, weights, q, bins=None, range=None, axis=None, method="inverted_cdf",
                                 block_size="auto"):
     """Weighted per-bin quantiles of ``values``, computed on an MI355X: what
@@ -2327,25 +2289,4 @@ def histogram_weighted_quantile(*args, values, weights, q, bins=None, range=None
     if weights is None:
         raise TypeError("histogram_weighted_quantile needs weights")
     qf, scalar, _ = _check_quantile_args(q, "linear")
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_weighted_quantile",
-                                                                   weights)
-    n_inputs = len(args)
-    if backend == "dask":
-        for a in all_arrays:
-            if any(len(a.chunks[ax]) > 1 for ax in drop_axes):
-                raise ValueError("exact quantiles of several chunks cannot be merged: rechunk the reduced axes of every input into "
-                                 "one chunk (e.g. arr.rechunk({axis: -1}))")
-        res = _values_blockwise(partial(_weighted_quantile_block, q=qf), len(qf), all_arrays, bins, axis, drop_axes)
-        res = res[(slice(None),) + tuple(0 if i in drop_axes else slice(None) for i in _range(all_arrays[0].ndim))]
-        return (res[0] if scalar else res), bins
-    if backend == "numpy":
-        arrays = _upload_host(raw[:n_inputs], raw[n_inputs], bins, raw[n_inputs + 1])
-        out = _weighted_quantile_rows(arrays[:n_inputs], arrays[n_inputs], arrays[n_inputs + 1], axis, bins, "device", qf)
-    else:
-        out = _weighted_quantile_rows(all_arrays[:n_inputs], all_arrays[n_inputs], all_arrays[n_inputs + 1], axis, bins, backend, qf)
-    if backend == "torch":
-        keep = [s for i, s in enumerate(out.shape) if i - 1 not in drop_axes]
-        out = out.reshape(keep)
-        return (out[0] if scalar else out), bins
-    out = out.squeeze(tuple(a + 1 for a in drop_axes))
-    return (out[0] if scalar else out), bins
+    return _quantile_call(args, values, bins, range, axis, "histogram_weighted_quantile", qf, scalar, 0, weights)

@@ -253,7 +253,8 @@ extern "C" int xhist_plan_execute_two_weights(xhist_plan* p, const xhist_array* 
 
 // ------------------------------------------------------------------------------------------
 // per-bin statistics of a value array: minimum and maximum (xhist_extrema.hip), count, mean and sum of squared deviations
-// (xhist_meanvar.hip), quantiles (xhist_quantile.hip); the choice and the launches they share: xhist_values.hip.h
+// (xhist_meanvar.hip, xhist_meanvar_w.hip), quantiles (xhist_quantile.hip, xhist_quantile_w.hip); the choice and the launches
+// they share: xhist_values.hip.h
 // ------------------------------------------------------------------------------------------
 void xhist_log_picked_kernel(const void* fn) { log_picked_kernel(fn); }
 
@@ -273,7 +274,7 @@ static ValuesPlan values_plan(const xhist_plan* p) {
   return pl;
 }
 
-// The checks and the tail both entry points share: `out` is the statistic's float64 output validate_arrays checks,
+// The checks and the tail the five entry points share: `out` is the statistic's float64 output validate_arrays checks,
 // `outs_ok` whether the others are given (`outs_missing` the message if not).  run(plan, err, err_cap, desc, desc_cap) launches
 // on the plan's device; the line it writes to `desc` becomes the plan's describe().
 template <class Run>
@@ -308,17 +309,23 @@ extern "C" int xhist_plan_execute_extrema(xhist_plan* p, const xhist_array* samp
                         });
 }
 
+// the float64 [n_rows, n_bins] block of a mean_var call for its sums of d (of w*d), freed with `scratch`; nullptr, with the
+// message in `err`, when the allocation fails
+static double* meanvar_scratch(ScratchScope& scratch, int64_t n_out, const char* form, char* err, size_t err_cap) {
+  double* sd = nullptr;
+  if (scratch.alloc((void**)&sd, (size_t)n_out * sizeof(double)) == hipSuccess) return sd;
+  snprintf(err, err_cap, "allocation of the %smean_var scratch block failed", form);
+  return nullptr;
+}
+
 extern "C" int xhist_plan_execute_mean_var(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
                                            int64_t n_cols, int64_t* out_count, double* out_mean, double* out_m2, int mem_kind, void* stream) {
   return execute_values(p, "xhist_plan_execute_mean_var", samples, values, n_rows, n_cols, out_mean, out_count && out_m2,
                         "out_count / out_m2 is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
                           hipStream_t s = static_cast<hipStream_t>(stream);
                           ScratchScope scratch(s);
-                          double* sd = nullptr;  // the sums of d
-                          if (scratch.alloc((void**)&sd, (size_t)(n_rows * p->n_bins) * sizeof(double)) != hipSuccess) {
-                            snprintf(err, err_cap, "allocation of the mean_var scratch block failed");
-                            return (int)XHIST_ERR_NOMEM;
-                          }
+                          double* sd = meanvar_scratch(scratch, n_rows * p->n_bins, "", err, err_cap);
+                          if (!sd) return (int)XHIST_ERR_NOMEM;
                           return xhist_meanvar_run(pl, samples, values, n_rows, n_cols, out_count, out_mean, out_m2, sd, s, err, err_cap,
                                                    desc, desc_cap);
                         });
@@ -333,14 +340,17 @@ extern "C" int xhist_plan_execute_mean_var_weighted(xhist_plan* p, const xhist_a
                         "out_m2 is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
                           hipStream_t s = static_cast<hipStream_t>(stream);
                           ScratchScope scratch(s);
-                          double* sd = nullptr;  // the sums of w*d
-                          if (scratch.alloc((void**)&sd, (size_t)(n_rows * p->n_bins) * sizeof(double)) != hipSuccess) {
-                            snprintf(err, err_cap, "allocation of the weighted mean_var scratch block failed");
-                            return (int)XHIST_ERR_NOMEM;
-                          }
+                          double* sd = meanvar_scratch(scratch, n_rows * p->n_bins, "weighted ", err, err_cap);
+                          if (!sd) return (int)XHIST_ERR_NOMEM;
                           return xhist_meanvar_w_run(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_m2, sd, s, err,
                                                      err_cap, desc, desc_cap);
                         });
+}
+
+// the scratch allocator of the quantile drivers (xhist_quantile_alloc_fn): ctx is the call's ScratchScope
+static void* quantile_scratch_alloc(void* ctx, size_t bytes) {
+  void* d = nullptr;
+  return static_cast<ScratchScope*>(ctx)->alloc(&d, bytes ? bytes : 8) == hipSuccess ? d : nullptr;
 }
 
 extern "C" int xhist_plan_execute_quantile(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
@@ -351,12 +361,8 @@ extern "C" int xhist_plan_execute_quantile(xhist_plan* p, const xhist_array* sam
                         [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
                           hipStream_t s = static_cast<hipStream_t>(stream);
                           ScratchScope scratch(s);
-                          auto alloc = [](void* ctx, size_t bytes) -> void* {
-                            void* d = nullptr;
-                            return static_cast<ScratchScope*>(ctx)->alloc(&d, bytes ? bytes : 8) == hipSuccess ? d : nullptr;
-                          };
-                          return xhist_quantile_run(pl, samples, values, n_rows, n_cols, q, n_q, method, out, alloc, &scratch, s, err,
-                                                    err_cap, desc, desc_cap);
+                          return xhist_quantile_run(pl, samples, values, n_rows, n_cols, q, n_q, method, out, quantile_scratch_alloc,
+                                                    &scratch, s, err, err_cap, desc, desc_cap);
                         });
 }
 
@@ -370,12 +376,8 @@ extern "C" int xhist_plan_execute_quantile_weighted(xhist_plan* p, const xhist_a
                         [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
                           hipStream_t s = static_cast<hipStream_t>(stream);
                           ScratchScope scratch(s);
-                          auto alloc = [](void* ctx, size_t bytes) -> void* {
-                            void* d = nullptr;
-                            return static_cast<ScratchScope*>(ctx)->alloc(&d, bytes ? bytes : 8) == hipSuccess ? d : nullptr;
-                          };
-                          return xhist_quantile_w_run(pl, samples, values, weights, n_rows, n_cols, q, n_q, out, alloc, &scratch, s,
-                                                      err, err_cap, desc, desc_cap);
+                          return xhist_quantile_w_run(pl, samples, values, weights, n_rows, n_cols, q, n_q, out, quantile_scratch_alloc,
+                                                      &scratch, s, err, err_cap, desc, desc_cap);
                         });
 }
 

@@ -1,6 +1,7 @@
 // xhist_meanvar_w.hip — per-bin sum of weights, weighted mean and variance (histogram_mean_var with weights): the weighted
-// kernels of xhist_meanvar.hip.h, instantiated here and nowhere else, the steps between and after the two passes, and the
-// driver that orders their launches (the choice and the binning launches themselves: xhist_values.hip.h).
+// kernels of xhist_meanvar.hip.h, instantiated here and nowhere else, the steps between and after the two passes, and what the
+// driver needs of this form: the driver itself is meanvar_run of xhist_meanvar.hip.h, shared with the unweighted form (the
+// choice and the binning launches themselves: xhist_values.hip.h).
 //
 // Instantiations (36 binning kernels + 2):
 //   mvw_sum_fast<ST, D, SCAN>, mvw_dev_fast<ST, D, SCAN>    ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith     12 + 12
@@ -55,58 +56,23 @@ struct MvwDevKernels {
   static values_w_fn generic() { return mvw_dev_generic<CMP, LDS>; }
 };
 
-// pass 1's sums of weights and of w*v, pass 2's mean and two sums: the slot sizes of the unweighted passes, so the same choice
-static constexpr ValuesSlots kMeanVarWSlots = {{sizeof(MvwSumSlot), sizeof(MvDevSlot)}, {sizeof(MvwSumSlot), sizeof(MvDevSlot)}, true};
+// what the shared driver (meanvar_run, xhist_meanvar.hip.h) needs of this form
+struct MeanVarW {
+  using Sum = MvwSumKernels;
+  using Dev = MvwDevKernels;
+  static constexpr auto mean = mvw_mean;
+  static constexpr auto finalize = mvw_finalize;
+  // pass 1's sums of weights and of w*v, pass 2's mean and two sums: the slot sizes of the unweighted passes, so the same choice
+  static constexpr ValuesSlots slots = {{sizeof(MvwSumSlot), sizeof(MvDevSlot)}, {sizeof(MvwSumSlot), sizeof(MvDevSlot)}, true};
+  static constexpr const char *name = "mean_var_w", *prefix = "mvw", *form = "weighted ";
+  static constexpr const char *lds_what = "mean_var_w: setting the dynamic LDS size failed";
+  static constexpr const char *sum_what = "mvw_sum launch", *dev_what = "mvw_dev launch";
+};
 static_assert(sizeof(MvwSumSlot) == sizeof(MvSumSlot), "the weighted pass 1 keeps the slot size of the unweighted one");
 
 int xhist_meanvar_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
                         int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_m2, double* sd, hipStream_t stream,
                         char* err, size_t err_cap, char* desc, size_t desc_cap) {
-  const int64_t n_out = n_rows * pl.n_bins;
-  const int grid_io = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_out + 255) / 256));
-  unsigned long long* zero[4] = {reinterpret_cast<unsigned long long*>(out_wsum), reinterpret_cast<unsigned long long*>(out_mean),
-                                 reinterpret_cast<unsigned long long*>(out_m2), reinterpret_cast<unsigned long long*>(sd)};
-  for (unsigned long long* z : zero) {
-    hipLaunchKernelGGL(zero_words, dim3(grid_io), dim3(256), 0, stream, z, n_out);
-    XH_VALUES_LAUNCH_CHECK("mean_var_w zeroing launch");
-  }
-
-  ValuesChoice c;
-  ValuesGeometry g;
-  values_w_fn sum = nullptr, dev = nullptr;
-  if (n_cols > 0) {
-    c = choose_values(pl, kMeanVarWSlots, samples, values, n_cols, weights);
-    sum = pick_values_kernel<MvwSumKernels>(c, pl);
-    dev = pick_values_kernel<MvwDevKernels>(c, pl);
-    if (!sum || !dev) {
-      snprintf(err, err_cap, "internal: no weighted mean_var kernel for this combination");
-      return XHIST_ERR_HIP;
-    }
-    for (int k = 0; k < 2; ++k)
-      if (int rc = allow_values_lds(k ? dev : sum, c.lds_bytes[k], "mean_var_w: setting the dynamic LDS size failed", err, err_cap))
-        return rc;
-    g = values_geometry(pl, c, n_rows, n_cols);
-    if (int rc = launch_values_pass(sum, c.lds_bytes[0], "mvw_sum launch", pl, c, g, samples, values, n_rows, n_cols, out_wsum, out_mean,
-                                    nullptr, stream, err, err_cap, weights))
-      return rc;
-  }
-  XH_VALUES_LAUNCH(mvw_mean, dim3(grid_io), dim3(256), 0, stream, out_wsum, out_mean, n_out);
-  XH_VALUES_LAUNCH_CHECK("mvw_mean launch");
-  if (n_cols > 0) {
-    if (int rc = launch_values_pass(dev, c.lds_bytes[1], "mvw_dev launch", pl, c, g, samples, values, n_rows, n_cols, sd, out_m2, out_mean,
-                                    stream, err, err_cap, weights))
-      return rc;
-  }
-  XH_VALUES_LAUNCH(mvw_finalize, dim3(grid_io), dim3(256), 0, stream, out_wsum, sd, out_m2, n_out);
-  XH_VALUES_LAUNCH_CHECK("mvw_finalize launch");
-  if (desc && desc_cap) {
-    const char* fam = !sum ? "none" : c.fast ? "fast" : "generic";
-    const char* home = !sum ? "none" : c.lds ? "lds" : "global";
-    snprintf(desc, desc_cap,
-             "mean_var_w pass1=mvw_sum_%s slots=%s pass2=mvw_dev_%s slots=%s scan=%d copies=%d block=%d segs=%lld lds_bytes=%zu/%zu "
-             "tables_in_lds=%d D=%d cmp=%d",
-             fam, home, fam, home, c.scan, 1 << c.copies_log2, g.block, (long long)g.segs, c.lds_bytes[0], c.lds_bytes[1],
-             (int)c.tables_in_lds, pl.n_dims, values_cmp(pl));
-  }
-  return XHIST_OK;
+  return meanvar_run<MeanVarW>(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_m2, sd, stream, err, err_cap, desc,
+                               desc_cap);
 }

@@ -1,6 +1,7 @@
 // xhist_quantile.hip.h — exact per-bin quantiles of a value array (histogram_quantile): the state of a selection, the two
-// policies it plugs into the shared kernel skeletons of xhist_values.hip.h, its binning kernels, the short-row kernel, and the
-// driver of xhist_quantile.hip.
+// policies it plugs into the shared kernel skeletons of xhist_values.hip.h, its binning kernels, the short-row kernel, the
+// host steps that the driver of xhist_quantile.hip shares with the weighted one of xhist_quantile_w.hip (templates over the
+// launch-parameter type, at the end), and the driver's declaration.
 //
 // Which samples count is decided exactly as for the histogram: the same digitize, the same tables.  A counted sample whose
 // value (converted to float64) is not NaN contributes the order-preserving key of that value (extrema_key64: unsigned order
@@ -351,6 +352,169 @@ __global__ void __launch_bounds__(256) q_short(const Params p, const QStep st) {
       st.out[((int64_t)(st.qi0 + t) * st.n_rows_total + p.row0 + row) * (int64_t)nb + (j % nb)] = r;
     }
   }
+}
+
+// ---- host side: the steps the driver shares with the weighted one (xhist_quantile_w.hip) ------------------------------------
+// Templates over the launch-parameter type P (Params, or WParams for the weighted kernels), as launch_values_pass<P> is.
+
+// what stays the same through one call: the plan (its lds_max less the launch header), the inputs (weights nullptr: the
+// unweighted statistic), the quantiles, the stream, and where an error message goes
+struct QCall {
+  const ValuesPlan& pl;
+  const xhist_array *samples, *values, *weights;
+  int64_t n_rows, n_cols;
+  const double* q;
+  int n_q;
+  hipStream_t stream;
+  char* err;
+  size_t err_cap;
+  // the statistic in error messages
+  const char* name() const { return weights ? "weighted quantile" : "quantile"; }
+  const char* lds_what() const {
+    return weights ? "weighted quantile: setting the dynamic LDS size failed" : "quantile: setting the dynamic LDS size failed";
+  }
+};
+
+// one binning pass of the radix family: the choice, the geometry and the kernel
+template <class P>
+struct Pass {
+  ValuesChoice c;
+  ValuesGeometry g;
+  void (*fn)(const P) = nullptr;
+};
+
+// the pass of kernel set K with `slot` bytes of LDS per bin, over chunks of `rows` rows
+template <class K, class P>
+static int pick_pass(Pass<P>& ps, const QCall& k, size_t slot, int64_t rows, const char* what) {
+  const ValuesSlots sl = {{slot, 0}, {slot, 0}, false};
+  ps.c = choose_values(k.pl, sl, k.samples, k.values, k.n_cols, k.weights);
+  ps.fn = pick_values_kernel<K>(ps.c, k.pl);
+  if (!ps.fn) {
+    snprintf(k.err, k.err_cap, "internal: no %s %s kernel for this combination", k.name(), what);
+    return XHIST_ERR_HIP;
+  }
+  ps.g = values_geometry(k.pl, ps.c, rows, k.n_cols);
+  return allow_values_lds(ps.fn, ps.c.lds_bytes[0], k.lds_what(), k.err, k.err_cap);
+}
+
+// One binning pass over rows [r0, r0 + nr) of a chunk: `recs` the launch's records (Params::out), `tgt` the targets of
+// `tgt_bytes` each (w2_ptr; nullptr: the pass reads none), `flag` its flag word, T records or targets per bin, digits of d bits.
+template <class P>
+static int launch_quantile_pass(const Pass<P>& ps, const QCall& k, int64_t r0, int64_t nr, void* recs, size_t rec_row_bytes,
+                                const void* tgt, size_t tgt_bytes, uint32_t* flag, int T, int d, const char* what) {
+  char* err = k.err;
+  const size_t err_cap = k.err_cap;
+  for (int64_t i = 0; i < nr; i += ps.g.max_rows) {
+    const int64_t n = std::min(ps.g.max_rows, nr - i);
+    P kp;
+    static_cast<Params&>(kp) = values_params(k.pl, ps.c, ps.g.segs, k.samples, k.values, r0 + i, n, k.n_cols);
+    if constexpr (std::is_same<P, WParams>::value) weights_params(kp, k.weights);
+    kp.out = static_cast<char*>(recs) + i * rec_row_bytes;
+    kp.w2_ptr = reinterpret_cast<const uint64_t*>(tgt ? static_cast<const char*>(tgt) + i * k.pl.n_bins * T * tgt_bytes : nullptr);
+    kp.part_counts = flag;
+    kp.n_parts = T;
+    kp.part_shift = d;
+    XH_VALUES_LAUNCH(ps.fn, dim3((unsigned)(n * ps.g.segs)), dim3(ps.g.block), ps.c.lds_bytes[0], k.stream, kp);
+    XH_VALUES_LAUNCH_CHECK(what);
+  }
+  return XHIST_OK;
+}
+
+// the targets of one group of a step struct (QStep, QWStep): q[g0 .. g0 + G), at most G of them
+template <class Step>
+static void quantile_group(Step& st, const QCall& k, int g0, int G) {
+  st.qi0 = g0;
+  st.G = std::min(G, k.n_q - g0);
+  for (int t = 0; t < st.G; ++t) st.q[t] = k.q[g0 + t];
+}
+
+// The radix family's group size G and digit width d, the digit passes of a group, and the rows of a chunk.  (G, d): the fewest
+// streaming passes, groups x ceil(64 / d) (ties: the wider d), first over the (G, d) whose digit pass takes at most
+// kQLdsBudget of LDS, then over those that fit LDS at all, both with d >= 4; if none does, counters (sums) in global memory,
+// under the scratch cap.  digit_bytes(G, d): a bin's LDS slots in a digit pass; radix_row_bytes(bins, G, d): the scratch of
+// one row of a chunk.
+struct QRadix {
+  int G = 0, d = 0, passes = 0;
+  int64_t chunk = 0;
+};
+static inline QRadix quantile_radix(const QCall& k, size_t (*digit_bytes)(int, int), size_t (*radix_row_bytes)(int64_t, int, int)) {
+  QRadix r;
+  int64_t best = INT64_MAX;
+  for (int tier = 0; tier < 3 && !r.G; ++tier) {
+    for (int g = std::min(kQGroup, k.n_q); g >= 1; --g)
+      for (int dd = 8; dd >= (tier < 2 ? 4 : 1); --dd) {
+        const int64_t cost = (int64_t)((k.n_q + g - 1) / g) * ((64 + dd - 1) / dd);
+        if (cost >= best) continue;
+        if (radix_row_bytes(k.pl.n_bins, g, dd) > kQScratchCap && !(g == 1 && dd == 1)) continue;
+        const ValuesSlots sl = {{digit_bytes(g, dd), 0}, {digit_bytes(g, dd), 0}, false};
+        const ValuesChoice c = choose_values(k.pl, sl, k.samples, k.values, k.n_cols, k.weights);
+        if (c.lds != (tier < 2) || (tier == 0 && c.lds_bytes[0] > kQLdsBudget)) continue;
+        best = cost;
+        r.G = g;
+        r.d = dd;
+      }
+  }
+  r.passes = (64 + r.d - 1) / r.d;
+  r.chunk = std::max<int64_t>(1, std::min<int64_t>(k.n_rows, (int64_t)(kQScratchCap / radix_row_bytes(k.pl.n_bins, r.G, r.d))));
+  return r;
+}
+
+// the radix family's describe() line (`name`: quantile / weighted_quantile)
+template <class P>
+static void describe_quantile_radix(char* desc, size_t desc_cap, const char* name, const QCall& k, const QRadix& r, const Pass<P>& win0,
+                                    const Pass<P>& digit) {
+  if (!desc || !desc_cap) return;
+  auto fam = [](const Pass<P>& p) { return p.c.fast ? "fast" : "generic"; };
+  auto home = [](const Pass<P>& p) { return p.c.lds ? "lds" : "global"; };
+  snprintf(desc, desc_cap,
+           "%s family=radix window=%s/%s digits=%s/%s scan=%d/%d d=%d group=%d groups=%d passes=%d chunks=%lld rows_per_chunk=%lld "
+           "block=%d segs=%lld lds_bytes=%zu/%zu D=%d cmp=%d",
+           name, fam(win0), home(win0), fam(digit), home(digit), win0.c.scan, digit.c.scan, r.d, r.G, (k.n_q + r.G - 1) / r.G, r.passes,
+           (long long)((k.n_rows + r.chunk - 1) / r.chunk), (long long)r.chunk, digit.g.block, (long long)digit.g.segs,
+           win0.c.lds_bytes[0], digit.c.lds_bytes[0], k.pl.n_dims, values_cmp(k.pl));
+}
+
+// The short-row family's launches: R whole rows per workgroup of 256 lanes (at most `short_cols` values in all, and R x bins
+// slots below 2^32), N the power of two above R x n_cols sorted elements of `elem_bytes` bytes of LDS each; per group of
+// targets, row chunks below 2^31 workgroups.  `fn`: the kernel for the compare domains 0, 1 and 3.
+struct QShort {
+  int64_t R = 0;
+  uint32_t N = 2;
+  size_t lds = 0;
+};
+template <class P, class Step>
+static int launch_quantile_short(const QCall& k, void (*const (&fn)[3])(const P, const Step), Step& st, int short_cols,
+                                 size_t elem_bytes, QShort& sh) {
+  char* err = k.err;
+  const size_t err_cap = k.err_cap;
+  const int64_t R = std::max<int64_t>(1, std::min<int64_t>(short_cols / std::max<int64_t>(k.n_cols, 1), (((int64_t)1 << 32) - 2) / k.pl.n_bins));
+  uint32_t N = 2;
+  while (N < (uint32_t)(R * k.n_cols)) N <<= 1;
+  const size_t lds = (size_t)N * elem_bytes;
+  sh = QShort{R, N, lds};
+  if (lds > 48 * 1024)
+    return values_error(err, err_cap, XHIST_ERR_HIP, k.weights ? "internal: weighted short-row LDS" : "internal: short-row LDS",
+                        hipErrorInvalidValue);
+  const int cmp = values_cmp(k.pl);
+  const auto short_fn = fn[cmp == 0 ? 0 : cmp == 1 ? 1 : 2];
+  const int64_t max_wg = ((int64_t)1 << 31) - 1;
+  for (int g0 = 0; g0 < k.n_q; g0 += kQGroup) {
+    quantile_group(st, k, g0, kQGroup);
+    for (int64_t r0 = 0; r0 < k.n_rows; r0 += max_wg * R) {
+      const int64_t nr = std::min(max_wg * R, k.n_rows - r0);
+      ValuesChoice c;
+      c.tab = &k.pl.native;
+      P kp;
+      static_cast<Params&>(kp) = values_params(k.pl, c, 1, k.samples, k.values, r0, nr, k.n_cols);
+      if constexpr (std::is_same<P, WParams>::value) weights_params(kp, k.weights);
+      kp.tables_in_lds = 0;  // (the tables are read through L2)
+      kp.lane_rows = (int32_t)R;
+      kp.slice_n = (int32_t)N;
+      XH_VALUES_LAUNCH(short_fn, dim3((unsigned)((nr + R - 1) / R)), dim3(256), lds, k.stream, kp, st);
+      XH_VALUES_LAUNCH_CHECK(k.weights ? "qw_short launch" : "q_short launch");
+    }
+  }
+  return XHIST_OK;
 }
 
 }  // namespace xhist

@@ -1,6 +1,7 @@
 // xhist_quantile_w.hip — exact weighted per-bin quantiles (histogram_weighted_quantile): the kernels of
-// xhist_quantile_w.hip.h, instantiated here and nowhere else, the steps between the binning passes, and the driver that orders
-// their launches (the choice and the binning geometry: xhist_values.hip.h).
+// xhist_quantile_w.hip.h, instantiated here and nowhere else, the steps between the binning passes, and the driver: the list of
+// its passes, with the 2^32 records check and no successor pass.  The host steps it shares with the unweighted driver are the
+// templates at the end of xhist_quantile.hip.h; the choice and the binning geometry: xhist_values.hip.h.
 //
 // Instantiations (36 binning kernels + 3 short-row kernels + 4):
 //   qw_win_fast<ST, D, SCAN>, qw_digit_fast<ST, D, SCAN>    ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith      12 + 12
@@ -113,46 +114,7 @@ size_t digit_bytes(int G, int d) { return (size_t)G * (24 + ((size_t)8 << d)); }
 // the radix family's scratch per row of a chunk: pass 0's records, and per target its state and its sums
 size_t radix_row_bytes(int64_t bins, int G, int d) { return (size_t)bins * (sizeof(QWWin) + (size_t)G * (sizeof(QWTgt) + ((size_t)8 << d))); }
 
-struct Pass {
-  ValuesChoice c;
-  ValuesGeometry g;
-  values_w_fn fn = nullptr;
-};
-
-template <class K>
-int pick_pass(Pass& ps, const ValuesPlan& pl, size_t slot, const xhist_array* samples, const xhist_array* values,
-              const xhist_array* weights, int64_t rows, int64_t n_cols, const char* what, char* err, size_t err_cap) {
-  const ValuesSlots sl = {{slot, 0}, {slot, 0}, false};
-  ps.c = choose_values(pl, sl, samples, values, n_cols, weights);
-  ps.fn = pick_values_kernel<K>(ps.c, pl);
-  if (!ps.fn) {
-    snprintf(err, err_cap, "internal: no weighted quantile %s kernel for this combination", what);
-    return XHIST_ERR_HIP;
-  }
-  ps.g = values_geometry(pl, ps.c, rows, n_cols);
-  return allow_values_lds(ps.fn, ps.c.lds_bytes[0], "weighted quantile: setting the dynamic LDS size failed", err, err_cap);
-}
-
-// One binning pass over rows [r0, r0 + nr) of a chunk: `recs` the launch's records (Params::out), `tgt` the targets (w2_ptr),
-// `flag` its flag word, T targets per bin, digits of d bits.
-int launch_qw_pass(const Pass& ps, const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
-                   int64_t r0, int64_t nr, int64_t n_cols, void* recs, size_t rec_row_bytes, const QWTgt* tgt, uint32_t* flag, int T, int d,
-                   hipStream_t stream, const char* what, char* err, size_t err_cap) {
-  for (int64_t k = 0; k < nr; k += ps.g.max_rows) {
-    const int64_t n = std::min(ps.g.max_rows, nr - k);
-    WParams kp;
-    static_cast<Params&>(kp) = values_params(pl, ps.c, ps.g.segs, samples, values, r0 + k, n, n_cols);
-    weights_params(kp, weights);
-    kp.out = static_cast<char*>(recs) + k * rec_row_bytes;
-    kp.w2_ptr = reinterpret_cast<const uint64_t*>(tgt ? tgt + k * pl.n_bins * T : nullptr);
-    kp.part_counts = flag;
-    kp.n_parts = T;
-    kp.part_shift = d;
-    XH_VALUES_LAUNCH(ps.fn, dim3((unsigned)(n * ps.g.segs)), dim3(ps.g.block), ps.c.lds_bytes[0], stream, kp);
-    XH_VALUES_LAUNCH_CHECK(what);
-  }
-  return XHIST_OK;
-}
+constexpr void (*kShortKernels[3])(const WParams, const QWStep) = {qw_short<0>, qw_short<1>, qw_short<3>};
 
 }  // namespace
 
@@ -161,8 +123,8 @@ int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, co
                          void* alloc_ctx, hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap) {
   ValuesPlan pl = pl_in;
   pl.lds_max -= 64;  // (the launch header q_hdr() is static LDS next to the dynamic slots)
+  const QCall k = {pl, samples, values, weights, n_rows, n_cols, q, n_q, stream, err, err_cap};
   const int64_t bins = pl.n_bins;
-  const int cmp = values_cmp(pl);
   QWStep st;
   memset(&st, 0, sizeof st);
   st.bins = bins;
@@ -171,76 +133,32 @@ int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, co
 
   // ---- short rows: one workgroup sorts whole rows in LDS -------------------------------------------------------------------
   if (n_cols <= kQWShortCols) {
-    const int64_t R = std::max<int64_t>(1, std::min<int64_t>(kQWShortCols / std::max<int64_t>(n_cols, 1), (((int64_t)1 << 32) - 2) / bins));
-    uint32_t N = 2;
-    while (N < (uint32_t)(R * n_cols)) N <<= 1;
-    const size_t lds = (size_t)N * 20;
-    if (lds > 48 * 1024) return values_error(err, err_cap, XHIST_ERR_HIP, "internal: weighted short-row LDS", hipErrorInvalidValue);
-    const int64_t max_wg = ((int64_t)1 << 31) - 1;
-    for (int g0 = 0; g0 < n_q; g0 += kQGroup) {
-      st.qi0 = g0;
-      st.G = std::min(kQGroup, n_q - g0);
-      for (int t = 0; t < st.G; ++t) st.q[t] = q[g0 + t];
-      for (int64_t r0 = 0; r0 < n_rows; r0 += max_wg * R) {
-        const int64_t nr = std::min(max_wg * R, n_rows - r0);
-        ValuesChoice c;
-        c.tab = &pl.native;
-        WParams kp;
-        static_cast<Params&>(kp) = values_params(pl, c, 1, samples, values, r0, nr, n_cols);
-        weights_params(kp, weights);
-        kp.tables_in_lds = 0;  // (the tables are read through L2)
-        kp.lane_rows = (int32_t)R;
-        kp.slice_n = (int32_t)N;
-        const dim3 grid((unsigned)((nr + R - 1) / R));
-        if (cmp == 0) XH_VALUES_LAUNCH(qw_short<0>, grid, dim3(256), lds, stream, kp, st);
-        else if (cmp == 1) XH_VALUES_LAUNCH(qw_short<1>, grid, dim3(256), lds, stream, kp, st);
-        else XH_VALUES_LAUNCH(qw_short<3>, grid, dim3(256), lds, stream, kp, st);
-        XH_VALUES_LAUNCH_CHECK("qw_short launch");
-      }
-    }
+    QShort sh;
+    if (int rc = launch_quantile_short(k, kShortKernels, st, kQWShortCols, 20, sh)) return rc;
     if (desc && desc_cap)
       snprintf(desc, desc_cap, "weighted_quantile family=short rows_per_wg=%lld triples=%u lds_bytes=%zu groups=%d block=256 D=%d cmp=%d",
-               (long long)R, N, lds, (n_q + kQGroup - 1) / kQGroup, pl.n_dims, cmp);
+               (long long)sh.R, sh.N, sh.lds, (n_q + kQGroup - 1) / kQGroup, pl.n_dims, values_cmp(pl));
     return XHIST_OK;
   }
 
-  // ---- long rows: radix select -------------------------------------------------------------------------------------------
-  // The group size G and the digit width d, by the rule of the unweighted family over the 8-byte sums: the fewest streaming
-  // passes, groups x ceil(64 / d) (ties: the wider d), first over the (G, d) whose digit pass takes at most kQLdsBudget of
-  // LDS, then over those that fit LDS at all, both with d >= 4; if none does, sums in global memory, under the scratch cap.
-  int G = 0, d = 0;
-  int64_t best = INT64_MAX;
-  for (int tier = 0; tier < 3 && !G; ++tier) {
-    for (int g = std::min(kQGroup, n_q); g >= 1; --g)
-      for (int dd = 8; dd >= (tier < 2 ? 4 : 1); --dd) {
-        const int64_t cost = (int64_t)((n_q + g - 1) / g) * ((64 + dd - 1) / dd);
-        if (cost >= best) continue;
-        if (radix_row_bytes(bins, g, dd) > kQScratchCap && !(g == 1 && dd == 1)) continue;
-        const ValuesSlots sl = {{digit_bytes(g, dd), 0}, {digit_bytes(g, dd), 0}, false};
-        const ValuesChoice c = choose_values(pl, sl, samples, values, n_cols, weights);
-        if (c.lds != (tier < 2) || (tier == 0 && c.lds_bytes[0] > kQLdsBudget)) continue;
-        best = cost;
-        G = g;
-        d = dd;
-      }
-  }
-  Pass digit, win0;
-  const int passes = (64 + d - 1) / d;
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_rows, (int64_t)(kQScratchCap / radix_row_bytes(bins, G, d))));
-  if ((uint64_t)chunk * (uint64_t)bins >> 32) {  // (the no-LDS window kernel indexes a launch's records in 32 bits)
+  // ---- long rows: radix select, by the rule of the unweighted family over the 8-byte sums ------------------------------------
+  const QRadix r = quantile_radix(k, digit_bytes, radix_row_bytes);
+  const int G = r.G, d = r.d, passes = r.passes;
+  if ((uint64_t)r.chunk * (uint64_t)bins >> 32) {  // (the no-LDS window kernel indexes a launch's records in 32 bits)
     snprintf(err, err_cap, "weighted quantiles of %lld bins are not supported (at most 2^32 - 1)", (long long)bins);
     return XHIST_ERR_UNSUPPORTED;
   }
-  if (int rc = pick_pass<QWDigitKernels>(digit, pl, digit_bytes(G, d), samples, values, weights, chunk, n_cols, "digit", err, err_cap)) return rc;
-  if (int rc = pick_pass<QWWinKernels>(win0, pl, kWinBytes, samples, values, weights, chunk, n_cols, "window", err, err_cap)) return rc;
+  Pass<WParams> digit, win0;
+  if (int rc = pick_pass<QWDigitKernels>(digit, k, digit_bytes(G, d), r.chunk, "digit")) return rc;
+  if (int rc = pick_pass<QWWinKernels>(win0, k, kWinBytes, r.chunk, "window")) return rc;
 
-  const size_t n_rb = (size_t)chunk * bins;
+  const size_t n_rb = (size_t)r.chunk * bins;
   QWWin* w0 = static_cast<QWWin*>(alloc(alloc_ctx, n_rb * sizeof(QWWin)));
   QWTgt* tg = static_cast<QWTgt*>(alloc(alloc_ctx, n_rb * G * sizeof(QWTgt)));
   double* sum = static_cast<double*>(alloc(alloc_ctx, (n_rb * G << d) * 8));
   uint32_t* flags = static_cast<uint32_t*>(alloc(alloc_ctx, 8 * ((size_t)passes + 8)));
   if (!w0 || !tg || !sum || !flags) {
-    snprintf(err, err_cap, "allocation of the weighted quantile scratch (%zu bytes per chunk) failed", radix_row_bytes(bins, G, d) * chunk);
+    snprintf(err, err_cap, "allocation of the weighted quantile scratch (%zu bytes per chunk) failed", radix_row_bytes(bins, G, d) * r.chunk);
     return XHIST_ERR_NOMEM;
   }
   const int64_t n_flag_words = (2 + passes + 1) / 2;  // flags: [1 + j] digit pass j (and the word qw_select writes last)
@@ -251,20 +169,18 @@ int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, co
   st.sum = sum;
   st.flags = flags;
   st.d = d;
-  for (int64_t r0 = 0; r0 < n_rows; r0 += chunk) {
-    const int64_t nr = std::min(chunk, n_rows - r0);
+  for (int64_t r0 = 0; r0 < n_rows; r0 += r.chunk) {
+    const int64_t nr = std::min(r.chunk, n_rows - r0);
     st.rows = nr;
     st.row0 = r0;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (nr * bins * G + 255) / 256));
     XH_VALUES_LAUNCH(qw_window, dim3(grid), dim3(256), 0, stream, st);
     XH_VALUES_LAUNCH_CHECK("qw_window launch");
-    if (int rc = launch_qw_pass(win0, pl, samples, values, weights, r0, nr, n_cols, w0, bins * sizeof(QWWin), nullptr, flags, 1, d, stream,
-                                "weighted quantile window launch", err, err_cap))
+    if (int rc = launch_quantile_pass(win0, k, r0, nr, w0, bins * sizeof(QWWin), nullptr, 0, flags, 1, d,
+                                      "weighted quantile window launch"))
       return rc;
     for (int g0 = 0; g0 < n_q; g0 += G) {
-      st.qi0 = g0;
-      st.G = std::min(G, n_q - g0);
-      for (int t = 0; t < st.G; ++t) st.q[t] = q[g0 + t];
+      quantile_group(st, k, g0, G);
       // the flags of the digit passes start at zero for every group
       hipLaunchKernelGGL(zero_words, dim3(1), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(flags), n_flag_words);
       XH_VALUES_LAUNCH_CHECK("weighted quantile zeroing launch");
@@ -272,8 +188,8 @@ int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, co
       XH_VALUES_LAUNCH_CHECK("qw_init launch");
       for (int j = 0; j < passes; ++j) {
         st.pass = j;
-        if (int rc = launch_qw_pass(digit, pl, samples, values, weights, r0, nr, n_cols, sum, ((size_t)bins * st.G * 8) << d, tg,
-                                    flags + 1 + j, st.G, d, stream, "weighted quantile digit launch", err, err_cap))
+        if (int rc = launch_quantile_pass(digit, k, r0, nr, sum, ((size_t)bins * st.G * 8) << d, tg, sizeof(QWTgt), flags + 1 + j, st.G, d,
+                                          "weighted quantile digit launch"))
           return rc;
         XH_VALUES_LAUNCH(qw_select, dim3(grid), dim3(256), 0, stream, st);
         XH_VALUES_LAUNCH_CHECK("qw_select launch");
@@ -282,15 +198,6 @@ int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, co
       XH_VALUES_LAUNCH_CHECK("qw_finalize launch");
     }
   }
-  if (desc && desc_cap) {
-    auto fam = [](const Pass& p) { return p.c.fast ? "fast" : "generic"; };
-    auto home = [](const Pass& p) { return p.c.lds ? "lds" : "global"; };
-    snprintf(desc, desc_cap,
-             "weighted_quantile family=radix window=%s/%s digits=%s/%s scan=%d/%d d=%d group=%d groups=%d passes=%d chunks=%lld "
-             "rows_per_chunk=%lld block=%d segs=%lld lds_bytes=%zu/%zu D=%d cmp=%d",
-             fam(win0), home(win0), fam(digit), home(digit), win0.c.scan, digit.c.scan, d, G, (n_q + G - 1) / G, passes,
-             (long long)((n_rows + chunk - 1) / chunk), (long long)chunk, digit.g.block, (long long)digit.g.segs, win0.c.lds_bytes[0],
-             digit.c.lds_bytes[0], pl.n_dims, cmp);
-  }
+  describe_quantile_radix(desc, desc_cap, "weighted_quantile", k, r, win0, digit);
   return XHIST_OK;
 }

@@ -1,6 +1,7 @@
 // xhist_quantile_w.hip.h — exact weighted per-bin quantiles of a value array (histogram_weighted_quantile, numpy's
 // method="inverted_cdf" with weights): the state of a weighted selection, the two weighted policies it plugs into the shared
-// kernel skeletons of xhist_values.hip.h, its binning kernels, the short-row kernel, and the driver of xhist_quantile_w.hip.
+// kernel skeletons of xhist_values.hip.h, its binning kernels, the short-row kernel, and the declaration of the driver of
+// xhist_quantile_w.hip (whose shared host steps are those of xhist_quantile.hip.h).
 //
 // Samples, values and keys are those of xhist_quantile.hip.h; every counted sample whose value is not NaN also brings its
 // weight (float64).  Per (row, bin): W = the sum of its weights, C(x) = the sum of the weights of its values <= x.  A target
