@@ -177,6 +177,25 @@ int xhist_plan_execute_mean_var_weighted(xhist_plan* plan, const xhist_array* sa
                                          const xhist_array* weights, int64_t n_rows, int64_t n_cols, double* out_wsum,
                                          double* out_mean, double* out_m2, int mem_kind, void* stream);
 
+/* Per-bin covariance of two value arrays (added within ABI v11): which samples count is exactly what
+ * xhist_plan_execute_mean_var counts, and a counted sample contributes its pair (a, b), both converted to float64, only if
+ * neither is NaN (pairwise-complete).  Two passes over the three streams, the corrected two-pass form of
+ * xhist_plan_execute_mean_var: n, Sa = sum(a), Sb = sum(b); then da = a - Sa/n, db = b - Sb/n in float64 and
+ *   M2_a = max(0, sum(da*da) - sum(da)^2 / n),  C_ab = sum(da*db) - sum(da) sum(db) / n,  M2_b = max(0, sum(db*db) - sum(db)^2 / n).
+ * C_ab is not clamped: a covariance may be negative.  The means and the three moments are NaN where n == 0; variances and
+ * covariance are M2 / (n - ddof) and C_ab / (n - ddof), left to the caller.  Float64 atomics add in arbitrary order: the last
+ * bits can differ between runs, except for data whose sums are exact in every order.
+ *   values_a, values_b: xhist_arrays of any real dtype, same logical [n_rows, n_cols] shape as the samples (strides 0 broadcast).
+ *   out_count (int64): contiguous [n_rows, prod(nb_d)]; out_mean (float64): contiguous [2, n_rows, prod(nb_d)], mean_a then
+ *   mean_b; out_comoment (float64): contiguous [3, n_rows, prod(nb_d)], M2_a, C_ab, M2_b.  DEVICE buffers, overwritten (no
+ *   accumulate mode); two float64 scratch blocks of [n_rows, prod(nb_d)] are taken from the library's allocator for the call.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Asynchronous on `stream`.  xhist_plan_describe then names the kernel family of each pass and where its slots live
+ *   ("cov pass1=cov_sum_..."). */
+int xhist_plan_execute_cov(xhist_plan* plan, const xhist_array* samples, const xhist_array* values_a,
+                           const xhist_array* values_b, int64_t n_rows, int64_t n_cols, int64_t* out_count,
+                           double* out_mean, double* out_comoment, int mem_kind, void* stream);
+
 /* Per-bin quantiles of `values`, exact: every output element is what np.nanquantile(values of that bin as float64, q[i],
  * method=...) gives, bit for bit, NaN for a bin with no value.  Which samples count is exactly what xhist_plan_execute counts
  * (same digitize, last bin closed, NaN / out-of-range samples dropped); NaN values are ignored.  Rows of at most 4096 values

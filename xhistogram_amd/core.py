@@ -34,7 +34,7 @@ from .devicearray import DeviceArray, _nocopy_reshape_strides
 _range = range
 
 __all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
-           "histogram_weighted_quantile"]
+           "histogram_weighted_quantile", "histogram_cov"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1841,8 +1841,9 @@ def _value_views(args, values, axis, bins, backend, weights=None):
 
 # What the shared paths need of a per-bin statistic of values: its number of outputs (the first an int64 count when
 # `counted`, all others float64), the Plan method that fills them from output pointers, the dask step that merges the
-# partials of blocks that share output rows, and whether it reads weights after the values.
-_ValueStat = namedtuple("_ValueStat", "k counted method reduce weighted", defaults=(False,))
+# partials of blocks that share output rows, whether it reads weights (histogram_cov: the second value array) after the
+# values, and, where the Plan method takes blocks of several outputs, the outputs whose pointers it is given.
+_ValueStat = namedtuple("_ValueStat", "k counted method reduce weighted ptrs", defaults=(False, None))
 
 
 def _value_stat_rows(stat, args, values, axis, bins, backend, weights=None):
@@ -1860,7 +1861,8 @@ def _value_stat_rows(stat, args, values, axis, bins, backend, weights=None):
         buf = _native.DeviceBuffer(device, max(k * n, 1) * 8)
         ptrs = [buf.ptr + i * n * 8 for i in _range(k)]
     if n > 0:
-        getattr(plan, stat.method)(nv[:len(args)], *nv[len(args):], m, c, *ptrs, stream=stream)
+        given = ptrs if stat.ptrs is None else [ptrs[i] for i in stat.ptrs]  # (the outputs are contiguous, in order)
+        getattr(plan, stat.method)(nv[:len(args)], *nv[len(args):], m, c, *given, stream=stream)
     if backend != "torch":
         host = np.empty((k, n), np.float64)
         if n > 0:
@@ -2144,10 +2146,106 @@ def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, 
     return x, mean, _var_of(x, m2, ddof), bins
 
 
+# ---------------------------------------------------------------------------------------------
+# per-bin covariance of two value arrays
+# ---------------------------------------------------------------------------------------------
+def combine_cov(n, mean_a, mean_b, m2_a, m2_b, c_ab, axis):
+    """Merge partial (count, mean_a, mean_b, M2_a, M2_b, C_ab) results over `axis` (kept as axes of extent 1) with Chan's
+    pairwise formula extended by the co-moment, one partial after another in index order (C order over several axes):
+        n = n1 + n2,  da = mean_a2 - mean_a1,  db = mean_b2 - mean_b1,  mean = mean1 + d * n2 / n,
+        M2 = M2_1 + M2_2 + d^2 * n1 * n2 / n,  C = C1 + C2 + da * db * n1 * n2 / n.
+    Partials with n == 0 are skipped; where every partial is empty, the means and moments are NaN and n is 0.  The reduction
+    of dask's partials.  Returns float64 (n, mean_a, mean_b, M2_a, M2_b, C_ab)."""
+    n, ma, mb, qa, qb, cc = (np.asarray(a, np.float64) for a in (n, mean_a, mean_b, m2_a, m2_b, c_ab))
+    ax = tuple(sorted(int(a) % n.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
+    rest = [i for i in _range(n.ndim) if i not in ax]
+    keep_shape = tuple(1 if i in ax else n.shape[i] for i in _range(n.ndim))
+
+    def lead(a):
+        a = np.transpose(a, ax + tuple(rest))
+        return a.reshape((-1,) + a.shape[len(ax):])
+
+    n, ma, mb, qa, qb, cc = (lead(a) for a in (n, ma, mb, qa, qb, cc))
+    cn = np.zeros(n.shape[1:])
+    cur = [np.full(n.shape[1:], np.nan) for _ in _range(5)]  # mean_a, mean_b, M2_a, M2_b, C_ab
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for k in _range(n.shape[0]):
+            nb = n[k]
+            take = nb > 0
+            first = take & ~(cn > 0)
+            both = take & (cn > 0)
+            tot = cn + nb
+            da, db = ma[k] - cur[0], mb[k] - cur[1]
+            f = cn * nb / tot
+            new = [cur[0] + da * nb / tot, cur[1] + db * nb / tot, cur[2] + qa[k] + da * da * f, cur[3] + qb[k] + db * db * f,
+                   cur[4] + cc[k] + da * db * f]
+            part = [ma[k], mb[k], qa[k], qb[k], cc[k]]
+            cur = [np.where(first, p, np.where(both, w, c)) for p, w, c in zip(part, new, cur)]
+            cn = np.where(take, tot, cn)
+    return tuple(a.reshape(keep_shape) for a in [cn] + cur)
+
+
+def _cov_reduce(x, axis=None, keepdims=True, ddof=None, **_):
+    """dask.array.reduction step over [6, ...] blocks of (n, mean_a, mean_b, M2_a, C_ab, M2_b) partials, the order of the
+    library's outputs; with ddof, the last step: the three moments divided by n - ddof, here only"""
+    ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
+    n, ma, mb, qa, qb, cc = combine_cov(x[0], x[1], x[2], x[3], x[5], x[4], tuple(a - 1 for a in ax))
+    out = np.stack([n, ma, mb, qa, cc, qb])
+    out = out if keepdims else out.squeeze(ax)
+    if ddof is not None:
+        for i in (3, 4, 5):
+            out[i] = _var_of(out[0], out[i], ddof)
+    return out
+
+
+def histogram_cov(*args, values, bins=None, range=None, axis=None, ddof=0, block_size="auto"):
+    """Per-bin count, means, variances and covariance of a pair of value arrays, computed on an MI355X: how two quantities move
+    together inside each class that :func:`histogram` counts.
+
+    ``args``, ``bins``, ``range`` and ``axis`` are those of :func:`histogram_mean_var`, and so are the counted samples and the
+    edges (those of the unweighted ``histogram`` call: estimator names are allowed; the same digitize; NaN and out-of-range
+    samples dropped).  ``values`` must be a pair ``(a, b)``; each broadcasts like ``values`` of ``histogram_mean_var``, may
+    have any real dtype and is taken as float64.  The statistics are pairwise-complete: a counted sample contributes only if
+    neither its ``a`` nor its ``b`` is NaN, so ``count`` plus the counted samples with a NaN in either value is ``histogram``'s
+    count.  ``block_size`` is accepted and changes nothing.
+
+    Two passes over the three arrays, the corrected two-pass form of ``histogram_mean_var``: ``n``, ``Sa = sum(a)`` and
+    ``Sb = sum(b)`` of each bin, ``mean_a = Sa / n``, ``mean_b = Sb / n``; then ``da = a - mean_a``, ``db = b - mean_b`` in
+    float64 and ``M2_a = max(0, sum(da**2) - sum(da)**2 / n)``, likewise ``M2_b``, and the co-moment
+    ``C_ab = sum(da * db) - sum(da) * sum(db) / n``, which is not clamped: a covariance may be negative.  ``var_a = M2_a / (n -
+    ddof)``, ``var_b = M2_b / (n - ddof)``, ``cov_ab = C_ab / (n - ddof)``.  The means are NaN where ``n == 0``, variances and
+    covariance where ``n <= ddof``.  The default ``ddof=0`` is that of ``histogram_mean_var``, not ``np.cov``'s 1, so that the
+    two calls agree: ``cov_ab`` with ``ddof=1`` is ``np.cov(a_bin, b_bin)[0, 1]``.  The correlation of a bin is ``cov_ab /
+    sqrt(var_a * var_b)`` and the slope of the regression of ``b`` on ``a`` is ``cov_ab / var_a``, whatever ``ddof``.  Float64
+    atomics add in arbitrary order, so the last bits can differ from run to run; data whose sums are exact in any order give
+    the same bits every time.
+
+    There is no ``weights`` parameter: a weighted covariance would read a fourth array and is not provided.
+
+    Returns ``(count, mean_a, mean_b, var_a, var_b, cov_ab, bin_edges)``: count int64, the others float64, with the shape
+    ``histogram`` gives (kept axes, then bin axes).  numpy in -> numpy out, torch in -> torch out on the same device
+    (asynchronous on the current stream), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block, the
+    partials merged by :func:`combine_cov`."""
+    if isinstance(values, (str, bytes)) or not isinstance(values, (tuple, list)) or len(values) != 2:
+        raise TypeError("histogram_cov needs values=(a, b), a pair of arrays")
+    a, b = values
+    if a is None or b is None:
+        raise TypeError("histogram_cov needs values=(a, b), a pair of arrays")
+    ddof = _check_ddof(ddof)
+    # the second value array travels where histogram_mean_var's weights travel
+    backend, (n, ma, mb, qa, cc, qb), bins, _ = _value_stat("cov", args, a, bins, range, axis, "histogram_cov",
+                                                           partial(_cov_reduce, ddof=ddof), weights=b)
+    if backend == "dask":
+        return n.astype(np.int64), ma, mb, qa, qb, cc, bins
+    return n, ma, mb, _var_of(n, qa, ddof), _var_of(n, qb, ddof), _var_of(n, cc, ddof), bins
+
+
 _VALUE_STATS = {
     "extrema": _ValueStat(2, False, "execute_extrema", _extrema_pair_reduce),
     "mean_var": _ValueStat(3, True, "execute_mean_var", _mean_var_reduce),
     "mean_var_w": _ValueStat(3, False, "execute_mean_var_weighted", _mean_var_w_reduce, True),
+    # (count, mean_a, mean_b, M2_a, C_ab, M2_b): the library takes the count, the block of means and the block of moments
+    "cov": _ValueStat(6, True, "execute_cov", _cov_reduce, True, (0, 1, 3)),
 }
 
 

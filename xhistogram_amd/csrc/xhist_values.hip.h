@@ -35,6 +35,13 @@ struct WParams : Params {
   int32_t x_dt;
 };
 
+// The Params of the statistics of two value arrays (histogram_cov, xhist_cov.hip.h): the second array travels as the weights
+// do, and a pass writes more arrays than out / out2 name, so each of out, out2 and w2_ptr is a block of [n_rows, n_bins] planes
+// `plane` 8-byte elements apart (launch_values_pass fills it).
+struct CovParams : WParams {
+  int64_t plane;
+};
+
 // An accumulator policy `Acc` is one statistic's (one pass's) use of the slots:
 //   slot_t                    one bin's LDS slot
 //   kCopies                   the fast family keeps 2^p.copies_log2 copies of every slot, lane i adding into copy
@@ -66,7 +73,7 @@ struct AccWeighted<Acc, std::enable_if_t<Acc::kWeighted>> : std::true_type {};
 template <class Acc, int CMP, bool LDS, class P>
 __device__ __forceinline__ void values_generic_body(const P& __restrict__ p) {
   constexpr bool W = AccWeighted<Acc>::value;
-  static_assert(!W || std::is_same<P, WParams>::value, "weighted policies read the weights of WParams");
+  static_assert(!W || std::is_base_of<WParams, P>::value, "weighted policies read the weights of WParams");
   using CT = typename Dom<CMP>::T;
   const int64_t row = blockIdx.x / p.segs;
   const int seg = blockIdx.x % p.segs;
@@ -128,7 +135,7 @@ __device__ __forceinline__ void values_generic_body(const P& __restrict__ p) {
 template <class Acc, typename ST, int D, int SCAN, class P>
 __device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
   constexpr bool W = AccWeighted<Acc>::value;
-  static_assert(!W || std::is_same<P, WParams>::value, "weighted policies read the weights of WParams");
+  static_assert(!W || std::is_base_of<WParams, P>::value, "weighted policies read the weights of WParams");
   static_assert(__is_same(ST, double) || __is_same(ST, float), "float32 / float64 samples and values");
   static_assert(SCAN == 1 || SCAN == 2 || SCAN == kScanArith, "tables with <= 2 edges per bucket, or arithmetic edges");
   constexpr int CMP = (__is_same(ST, float) && SCAN != kScanArith) ? 2 : 0;
@@ -449,7 +456,8 @@ static inline void weights_params(WParams& kp, const xhist_array* weights) {
 
 // One binning pass: the launches of row chunks of at most g.max_rows (the grid stays below 2^31 workgroups and 2^32 lanes).  out / out2 / in2 are [n_rows, n_bins] arrays of 8-byte elements,
 // advanced to each chunk's first row (Params::out, out2 and w2_ptr); `what` names the pass in error messages.  A weighted
-// kernel (it takes WParams) reads `weights`.
+// kernel (it takes WParams) reads `weights`; for a CovParams kernel each of the three is the first of several such arrays,
+// n_rows * n_bins elements apart.
 template <class P>
 static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what, const ValuesPlan& pl,
                               const ValuesChoice& c, const ValuesGeometry& g, const xhist_array* samples, const xhist_array* values,
@@ -459,7 +467,8 @@ static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what,
     const int64_t nr = std::min(g.max_rows, n_rows - r0);
     P kp;
     static_cast<Params&>(kp) = values_params(pl, c, g.segs, samples, values, r0, nr, n_cols);
-    if constexpr (std::is_same<P, WParams>::value) weights_params(kp, weights);
+    if constexpr (std::is_base_of<WParams, P>::value) weights_params(kp, weights);
+    if constexpr (std::is_same<P, CovParams>::value) kp.plane = n_rows * pl.n_bins;  // (the whole call's rows, whatever the chunk)
     kp.w2_ptr = in2 ? static_cast<const uint64_t*>(in2) + r0 * pl.n_bins : nullptr;
     kp.out = static_cast<uint64_t*>(out) + r0 * pl.n_bins;
     kp.out2 = static_cast<uint64_t*>(out2) + r0 * pl.n_bins;

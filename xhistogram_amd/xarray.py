@@ -13,7 +13,8 @@ import numpy as np
 from .core import histogram as _core_histogram
 from .core import histogram_two_weights as _core_histogram_two_weights
 
-__all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile"]
+__all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
+           "histogram_cov"]
 
 
 def _xr():
@@ -213,6 +214,32 @@ def histogram_weighted_quantile(*args, values, weights, q, bins=None, range=None
         out_dims = ["quantile"] + list(out_dims)
         coords = dict(coords, quantile=(("quantile",), qa))
     return xr.DataArray(res, dims=out_dims, coords=coords, name="%s_weighted_quantile" % base)
+
+def histogram_cov(*args, values, bins=None, range=None, dim=None, ddof=0, block_size="auto", keep_coords=False, bin_dim_suffix="_bin"):
+    """Per-bin count, means, variances and covariance of the pair of DataArrays ``values=(A, B)`` over the bins of ``args``
+    (:func:`xhistogram_amd.core.histogram_cov` with the labels of :func:`histogram`).
+
+    ``args``, ``bins``, ``range``, ``dim``, ``keep_coords`` and ``bin_dim_suffix`` are those of :func:`histogram`; ``A`` and
+    ``B`` are lined up as ``values`` of :func:`histogram_mean_var` (dims a subset of the data's).  Returns a dict of six
+    DataArrays with the dims and coords ``histogram`` gives, keyed by their names (``xarray.Dataset(result)`` makes a Dataset
+    of it): ``<a>_<b>_count``, ``<a>_mean``, ``<b>_mean``, ``<a>_var``, ``<b>_var``, ``<a>_<b>_cov``, with ``<a>`` / ``<b>``
+    the names of the DataArrays (``a`` / ``b`` for a nameless one).  There is no ``weights`` parameter."""
+    from .core import histogram_cov as _core_histogram_cov
+
+    if isinstance(values, (str, bytes)) or not isinstance(values, (tuple, list)) or len(values) != 2:
+        raise TypeError("histogram_cov needs values=(A, B), a pair of DataArrays")
+    A, B = values
+
+    def pair(*arrays, values, weights, **kw):  # (B is lined up where the weights of the other statistics are)
+        return _core_histogram_cov(*arrays, values=(values, weights), **kw)
+
+    results, out_dims, coords, _ = _values_statistic(
+        "histogram_cov", pair, args, A, bins, range, dim, keep_coords, bin_dim_suffix, ddof=ddof, block_size=block_size, weights=B)
+    xr = _xr()
+    a, b = A.name or "a", B.name or "b"
+    names = ("%s_%s_count" % (a, b), "%s_mean" % a, "%s_mean" % b, "%s_var" % a, "%s_var" % b, "%s_%s_cov" % (a, b))
+    return {n: xr.DataArray(r, dims=out_dims, coords=coords, name=n) for n, r in zip(names, results)}
+
 
 def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords, bin_dim_suffix, weights=None, **kw):
     """a per-bin statistic of ``values`` with the labels of :func:`histogram`: (core_fn's arrays, dims, coords, the values'
