@@ -6,7 +6,14 @@ of two up to 2^9 and within cov_exact's float64 bounds elsewhere.  Every census 
 against test_gpu_values_census.predict, a restatement of choose_values / values_geometry, with the slot sizes of the two cov
 passes (24 and 56 bytes, copies) registered in that module's tables from here.  Between them the fast-form and generic cases
 select all 36 binning kernels of xhist_cov.hip plus cov_mean and cov_finalize (tests/test_zz_gpu_census_total.py holds the
-session to that)."""
+session to that).
+
+What the launcher decides at run time inside one kernel symbol is not covered here: every census case of this file has one
+copy of its slots, one row chunk and dense arrays.  The copies of the 24 / 56-byte slots, the LDS borders, the tables read
+through L2, the datetime and uint64 domains, more than two sample arrays, segments and ragged tiles, a layout per stream through
+the C ABI and the row chunks (where the plane distance differs from the chunk's rows) are the cases of
+tests/test_gpu_values_census_streams.py, which borrows predict_cov, assert_cov_variant, check_exact, nan_grid and run_cov
+from here."""
 import os
 import subprocess
 import sys

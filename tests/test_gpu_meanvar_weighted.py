@@ -4,7 +4,12 @@ oracle (tests/meanvar_weighted_oracle.py).
 On exactly summable data (values on values_exact.grid, integer weights 0..7) W and the mean are checked bit for bit, and so is
 the variance where W is a power of two up to 2^8; elsewhere it stays within the oracle's float64 bound.  Every case also checks
 its describe() line against test_gpu_values_census.predict("mean_var", ...): the weighted slots have the unweighted sizes, so
-the choice is the same, with the fast family given up when the weights' dtype or layout disqualifies it."""
+the choice is the same, with the fast family given up when the weights' dtype or layout disqualifies it.
+
+The cases here have one copy of their slots or are checked against an rtol where they have more, one row chunk, and no case on
+an LDS border, with tables read through L2, in a datetime or uint64 domain, or with weights laid out otherwise than the values
+beyond test_fast_fallback_and_views.  Those launch variants, each held to the exact oracle, are the cases of
+tests/test_gpu_values_census_streams.py, which borrows check_exact, as_unweighted_line, int_weights and run_w from here."""
 import math
 import os
 import subprocess
