@@ -363,28 +363,28 @@ class Plan:
             raise ValueError("plan was built for %d inputs, got %d" % (d, len(sample_views)))
         return (XhistArray * d)(*sample_views)
 
+    def _execute_values(self, symbol, sample_views, views, n_rows, n_cols, out_ptrs, ints=(), stream=0):
+        """the xhist_plan_execute_* call `symbol` of a per-bin statistic of values: the samples, the value (and weight) views, the
+        rows and columns, the output pointers, MEM_DEVICE, any trailing integers, the stream"""
+        check(
+            getattr(load(), symbol)(
+                self._h, self._sample_array(sample_views), *[C.byref(v) for v in views], int(n_rows), int(n_cols),
+                *[C.c_void_p(p) for p in out_ptrs], MEM_DEVICE, *ints, C.c_void_p(stream or 0),
+            )
+        )
+
     def execute_extrema(self, sample_views, value_view, n_rows, n_cols, out_min_ptr, out_max_ptr, accumulate=False, stream=0):
         """per-bin minimum and maximum of the values (float64 [n_rows, bins] each, NaN where no value arrived) of
         device-resident views into device buffers, asynchronous on `stream` (xhist_plan_execute_extrema)"""
-        arr = self._sample_array(sample_views)
-        check(
-            load().xhist_plan_execute_extrema(
-                self._h, arr, C.byref(value_view), int(n_rows), int(n_cols), C.c_void_p(out_min_ptr), C.c_void_p(out_max_ptr),
-                MEM_DEVICE, 1 if accumulate else 0, C.c_void_p(stream or 0),
-            )
-        )
+        self._execute_values("xhist_plan_execute_extrema", sample_views, (value_view,), n_rows, n_cols, (out_min_ptr, out_max_ptr),
+                             (1 if accumulate else 0,), stream=stream)
 
     def execute_mean_var(self, sample_views, value_view, n_rows, n_cols, out_count_ptr, out_mean_ptr, out_m2_ptr, stream=0):
         """per-bin count (int64), mean and sum of squared deviations M2 (float64; NaN where no value arrived) of the values of
         device-resident views, into device buffers of [n_rows, bins] each, asynchronous on `stream`
         (xhist_plan_execute_mean_var)"""
-        arr = self._sample_array(sample_views)
-        check(
-            load().xhist_plan_execute_mean_var(
-                self._h, arr, C.byref(value_view), int(n_rows), int(n_cols), C.c_void_p(out_count_ptr), C.c_void_p(out_mean_ptr),
-                C.c_void_p(out_m2_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
-            )
-        )
+        self._execute_values("xhist_plan_execute_mean_var", sample_views, (value_view,), n_rows, n_cols,
+                             (out_count_ptr, out_mean_ptr, out_m2_ptr), stream=stream)
 
     def execute_cov(self, sample_views, value_a_view, value_b_view, n_rows, n_cols, out_count_ptr, out_mean_ptr, out_comoment_ptr,
                     stream=0):
@@ -392,26 +392,16 @@ class Plan:
         deviations with the co-moment between them (float64 [3, n_rows, bins]: M2_a, C_ab, M2_b; NaN where no pair arrived) of
         the pairwise-complete values of device-resident views, into device buffers, asynchronous on `stream`
         (xhist_plan_execute_cov)"""
-        arr = self._sample_array(sample_views)
-        check(
-            load().xhist_plan_execute_cov(
-                self._h, arr, C.byref(value_a_view), C.byref(value_b_view), int(n_rows), int(n_cols), C.c_void_p(out_count_ptr),
-                C.c_void_p(out_mean_ptr), C.c_void_p(out_comoment_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
-            )
-        )
+        self._execute_values("xhist_plan_execute_cov", sample_views, (value_a_view, value_b_view), n_rows, n_cols,
+                             (out_count_ptr, out_mean_ptr, out_comoment_ptr), stream=stream)
 
     def execute_mean_var_weighted(self, sample_views, value_view, weight_view, n_rows, n_cols, out_wsum_ptr, out_mean_ptr, out_m2_ptr,
                                   stream=0):
         """per-bin sum of weights W, weighted mean and weighted sum of squared deviations M2 (float64 each; mean and M2 NaN
         where W == 0) of the values of device-resident views, into device buffers of [n_rows, bins] each, asynchronous on
         `stream` (xhist_plan_execute_mean_var_weighted)"""
-        arr = self._sample_array(sample_views)
-        check(
-            load().xhist_plan_execute_mean_var_weighted(
-                self._h, arr, C.byref(value_view), C.byref(weight_view), int(n_rows), int(n_cols), C.c_void_p(out_wsum_ptr),
-                C.c_void_p(out_mean_ptr), C.c_void_p(out_m2_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
-            )
-        )
+        self._execute_values("xhist_plan_execute_mean_var_weighted", sample_views, (value_view, weight_view), n_rows, n_cols,
+                             (out_wsum_ptr, out_mean_ptr, out_m2_ptr), stream=stream)
 
     def _quantile_args(self, sample_views, q):
         """the C array of the samples' views, and q as a contiguous 1-D float64 array"""

@@ -2013,37 +2013,48 @@ def _check_ddof(ddof):
     return int(ddof)
 
 
-def _chan_merge(x, mean, m2, axis, present):
-    """Chan's pairwise merge of partial (x, mean, M2) results over `axis` (kept as axes of extent 1), one partial after another
-    in index order (C order over several axes); x is the count or the sum of weights, and present(x) says where a partial (or
-    the running result) holds something.  Returns float64 (x, mean, M2)."""
-    x, mean, m2 = (np.asarray(a, np.float64) for a in (x, mean, m2))
+def _chan_merge(x, means, moments, pairs, axis, present):
+    """Chan's pairwise merge of partial (x, means..., moments...) results over `axis` (kept as axes of extent 1), one partial
+    after another in index order (C order over several axes); x is the count or the sum of weights, present(x) says where a
+    partial (or the running result) holds something, and pairs[m] = (i, j) names the two means whose deviations multiply into
+    moment m's cross term ((0, 0): the M2 of mean 0).  Returns float64 (x, [means], [moments])."""
+    x, *rest = (np.asarray(a, np.float64) for a in [x] + list(means) + list(moments))
     ax = tuple(sorted(int(a) % x.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
-    rest = [i for i in _range(x.ndim) if i not in ax]
+    kept = [i for i in _range(x.ndim) if i not in ax]
     keep_shape = tuple(1 if i in ax else x.shape[i] for i in _range(x.ndim))
 
     def lead(a):
-        a = np.transpose(a, ax + tuple(rest))
+        a = np.transpose(a, ax + tuple(kept))
         return a.reshape((-1,) + a.shape[len(ax):])
 
-    x, mean, m2 = lead(x), lead(mean), lead(m2)
+    x, rest = lead(x), [lead(a) for a in rest]
+    means, moments = rest[:len(means)], rest[len(means):]
     cx = np.zeros(x.shape[1:])
-    cm = np.full(x.shape[1:], np.nan)
-    cq = np.full(x.shape[1:], np.nan)
+    cm = [np.full(x.shape[1:], np.nan) for _ in means]
+    cq = [np.full(x.shape[1:], np.nan) for _ in moments]
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         for k in _range(x.shape[0]):
-            xb, mb, qb = x[k], mean[k], m2[k]
+            xb = x[k]
             take = present(xb)
             first = take & ~present(cx)
             both = take & present(cx)
             tot = cx + xb
-            d = mb - cm
-            m_new = cm + d * xb / tot
-            q_new = cq + qb + d * d * cx * xb / tot
-            cm = np.where(first, mb, np.where(both, m_new, cm))
-            cq = np.where(first, qb, np.where(both, q_new, cq))
+            d = [m[k] - c for m, c in zip(means, cm)]
+            q_new = [c + q[k] + d[i] * d[j] * cx * xb / tot for c, q, (i, j) in zip(cq, moments, pairs)]
+            cm = [np.where(first, m[k], np.where(both, c + di * xb / tot, c)) for m, c, di in zip(means, cm, d)]
+            cq = [np.where(first, q[k], np.where(both, new, c)) for q, new, c in zip(moments, q_new, cq)]
             cx = np.where(take, tot, cx)
-    return cx.reshape(keep_shape), cm.reshape(keep_shape), cq.reshape(keep_shape)
+    return cx.reshape(keep_shape), [a.reshape(keep_shape) for a in cm], [a.reshape(keep_shape) for a in cq]
+
+
+def _counted(x):
+    """where a partial holds something: a count above 0"""
+    return x > 0
+
+
+def _weighed(x):
+    """where a weighted partial holds something: W != 0 (NaN != 0: a NaN partial is taken, and its NaN spreads)"""
+    return x != 0
 
 
 def combine_mean_var(n, mean, m2, axis):
@@ -2052,7 +2063,8 @@ def combine_mean_var(n, mean, m2, axis):
         n = na + nb,  d = mb - ma,  mean = ma + d * nb / n,  M2 = M2a + M2b + d^2 * na * nb / n.
     Partials with n == 0 are skipped; where every partial is empty, mean and M2 are NaN and n is 0.  The reduction of dask's
     partials.  Returns float64 (n, mean, M2)."""
-    return _chan_merge(n, mean, m2, axis, lambda a: a > 0)
+    n, (mean,), (m2,) = _chan_merge(n, [mean], [m2], [(0, 0)], axis, _counted)
+    return n, mean, m2
 
 
 def combine_weighted_mean_var(w, mean, m2, axis):
@@ -2061,7 +2073,8 @@ def combine_weighted_mean_var(w, mean, m2, axis):
         W = Wa + Wb,  d = mb - ma,  mean = ma + d * Wb / W,  M2 = M2a + M2b + d^2 * Wa * Wb / W.
     Partials with W == 0 are skipped; a NaN partial (a NaN W among them) makes the bin NaN.  Where every partial has W == 0,
     mean and M2 are NaN and W is 0.  The reduction of dask's weighted partials.  Returns float64 (W, mean, M2)."""
-    return _chan_merge(w, mean, m2, axis, lambda a: a != 0)  # (NaN != 0: a NaN partial is taken, and its NaN spreads)
+    w, (mean,), (m2,) = _chan_merge(w, [mean], [m2], [(0, 0)], axis, _weighed)
+    return w, mean, m2
 
 
 def _var_of(x, m2, ddof):
@@ -2073,35 +2086,27 @@ def _var_of(x, m2, ddof):
         return np.where(x > ddof, m2 / (x - ddof), np.nan)
 
 
-def _chan_reduce(combine, x, axis, keepdims, ddof=None):
-    """dask.array.reduction step over [3, ...] blocks of (x, mean, M2) partials merged by `combine`; with ddof, the last step:
-    (x, mean, var), the division by x - ddof done here only"""
+def _chan_reduce(x, axis=None, keepdims=True, ddof=None, present=_counted, pairs=((0, 0),), **_):
+    """dask.array.reduction step over stacked blocks of partials in the order the library emits them: x, the means, then the
+    moments, `pairs` naming each moment's means as _chan_merge reads them (so their number is that of the means, 1 + the
+    largest index).  With ddof, the last step: the moments divided by x - ddof, here only."""
     ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
-    out = np.stack(combine(x[0], x[1], x[2], tuple(a - 1 for a in ax)))
+    n_means = 1 + max(max(p) for p in pairs)
+    cx, cm, cq = _chan_merge(x[0], x[1:1 + n_means], x[1 + n_means:], pairs, tuple(a - 1 for a in ax), present)
+    out = np.stack([cx] + cm + cq)
     out = out if keepdims else out.squeeze(ax)
     if ddof is not None:
-        out[2] = _var_of(out[0], out[2], ddof)
+        for i in _range(1 + n_means, len(out)):
+            out[i] = _var_of(out[0], out[i], ddof)
     return out
 
 
-def _mean_var_reduce(x, axis=None, keepdims=True, **_):
-    """dask.array.reduction step over [3, ...] blocks of (n, mean, M2) partials"""
-    return _chan_reduce(combine_mean_var, x, axis, keepdims)
-
-
-def _mean_var_aggregate(x, axis=None, keepdims=True, ddof=0, **_):
-    """the last step: (n, mean, var), the division by n - ddof done here only"""
-    return _chan_reduce(combine_mean_var, x, axis, keepdims, ddof)
-
-
-def _mean_var_w_reduce(x, axis=None, keepdims=True, **_):
-    """dask.array.reduction step over [3, ...] blocks of weighted (W, mean, M2) partials"""
-    return _chan_reduce(combine_weighted_mean_var, x, axis, keepdims)
-
-
-def _mean_var_w_aggregate(x, axis=None, keepdims=True, ddof=0, **_):
-    """the last weighted step: (W, mean, var), the division by W - ddof done here only"""
-    return _chan_reduce(combine_weighted_mean_var, x, axis, keepdims, ddof)
+# the steps of (n, mean, M2) and of weighted (W, mean, M2) blocks; an aggregate is the last step, (x, mean, var).  Partials of a
+# module-level function, so that dask can pickle them.
+_mean_var_reduce = partial(_chan_reduce, present=_counted)
+_mean_var_aggregate = partial(_chan_reduce, present=_counted, ddof=0)
+_mean_var_w_reduce = partial(_chan_reduce, present=_weighed)
+_mean_var_w_aggregate = partial(_chan_reduce, present=_weighed, ddof=0)
 
 
 def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, weights=None, block_size="auto"):
@@ -2156,46 +2161,12 @@ def combine_cov(n, mean_a, mean_b, m2_a, m2_b, c_ab, axis):
         M2 = M2_1 + M2_2 + d^2 * n1 * n2 / n,  C = C1 + C2 + da * db * n1 * n2 / n.
     Partials with n == 0 are skipped; where every partial is empty, the means and moments are NaN and n is 0.  The reduction
     of dask's partials.  Returns float64 (n, mean_a, mean_b, M2_a, M2_b, C_ab)."""
-    n, ma, mb, qa, qb, cc = (np.asarray(a, np.float64) for a in (n, mean_a, mean_b, m2_a, m2_b, c_ab))
-    ax = tuple(sorted(int(a) % n.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
-    rest = [i for i in _range(n.ndim) if i not in ax]
-    keep_shape = tuple(1 if i in ax else n.shape[i] for i in _range(n.ndim))
-
-    def lead(a):
-        a = np.transpose(a, ax + tuple(rest))
-        return a.reshape((-1,) + a.shape[len(ax):])
-
-    n, ma, mb, qa, qb, cc = (lead(a) for a in (n, ma, mb, qa, qb, cc))
-    cn = np.zeros(n.shape[1:])
-    cur = [np.full(n.shape[1:], np.nan) for _ in _range(5)]  # mean_a, mean_b, M2_a, M2_b, C_ab
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        for k in _range(n.shape[0]):
-            nb = n[k]
-            take = nb > 0
-            first = take & ~(cn > 0)
-            both = take & (cn > 0)
-            tot = cn + nb
-            da, db = ma[k] - cur[0], mb[k] - cur[1]
-            f = cn * nb / tot
-            new = [cur[0] + da * nb / tot, cur[1] + db * nb / tot, cur[2] + qa[k] + da * da * f, cur[3] + qb[k] + db * db * f,
-                   cur[4] + cc[k] + da * db * f]
-            part = [ma[k], mb[k], qa[k], qb[k], cc[k]]
-            cur = [np.where(first, p, np.where(both, w, c)) for p, w, c in zip(part, new, cur)]
-            cn = np.where(take, tot, cn)
-    return tuple(a.reshape(keep_shape) for a in [cn] + cur)
+    n, (ma, mb), (qa, qb, cc) = _chan_merge(n, [mean_a, mean_b], [m2_a, m2_b, c_ab], [(0, 0), (1, 1), (0, 1)], axis, _counted)
+    return n, ma, mb, qa, qb, cc
 
 
-def _cov_reduce(x, axis=None, keepdims=True, ddof=None, **_):
-    """dask.array.reduction step over [6, ...] blocks of (n, mean_a, mean_b, M2_a, C_ab, M2_b) partials, the order of the
-    library's outputs; with ddof, the last step: the three moments divided by n - ddof, here only"""
-    ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
-    n, ma, mb, qa, qb, cc = combine_cov(x[0], x[1], x[2], x[3], x[5], x[4], tuple(a - 1 for a in ax))
-    out = np.stack([n, ma, mb, qa, cc, qb])
-    out = out if keepdims else out.squeeze(ax)
-    if ddof is not None:
-        for i in (3, 4, 5):
-            out[i] = _var_of(out[0], out[i], ddof)
-    return out
+# the step of (n, mean_a, mean_b, M2_a, C_ab, M2_b) blocks, the order of the library's outputs
+_cov_reduce = partial(_chan_reduce, present=_counted, pairs=((0, 0), (0, 1), (1, 1)))
 
 
 def histogram_cov(*args, values, bins=None, range=None, axis=None, ddof=0, block_size="auto"):

@@ -310,12 +310,12 @@ extern "C" int xhist_plan_execute_extrema(xhist_plan* p, const xhist_array* samp
                         });
 }
 
-// the float64 [n_rows, n_bins] block of a mean_var call for its sums of d (of w*d), freed with `scratch`; nullptr, with the
-// message in `err`, when the allocation fails
-static double* meanvar_scratch(ScratchScope& scratch, int64_t n_out, const char* form, char* err, size_t err_cap) {
+// the float64 block of `n` elements of a two-pass call for its sums of deviations ([n_rows, n_bins] of d or w*d; cov: two such
+// planes), freed with `scratch`; nullptr, with the message in `err` (`what` names the block there), when the allocation fails
+static double* two_pass_scratch(ScratchScope& scratch, int64_t n, const char* what, char* err, size_t err_cap) {
   double* sd = nullptr;
-  if (scratch.alloc((void**)&sd, (size_t)n_out * sizeof(double)) == hipSuccess) return sd;
-  snprintf(err, err_cap, "allocation of the %smean_var scratch block failed", form);
+  if (scratch.alloc((void**)&sd, (size_t)n * sizeof(double)) == hipSuccess) return sd;
+  snprintf(err, err_cap, "allocation of the %s failed", what);
   return nullptr;
 }
 
@@ -325,7 +325,7 @@ extern "C" int xhist_plan_execute_mean_var(xhist_plan* p, const xhist_array* sam
                         "out_count / out_m2 is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
                           hipStream_t s = static_cast<hipStream_t>(stream);
                           ScratchScope scratch(s);
-                          double* sd = meanvar_scratch(scratch, n_rows * p->n_bins, "", err, err_cap);
+                          double* sd = two_pass_scratch(scratch, n_rows * p->n_bins, "mean_var scratch block", err, err_cap);
                           if (!sd) return (int)XHIST_ERR_NOMEM;
                           return xhist_meanvar_run(pl, samples, values, n_rows, n_cols, out_count, out_mean, out_m2, sd, s, err, err_cap,
                                                    desc, desc_cap);
@@ -341,7 +341,7 @@ extern "C" int xhist_plan_execute_mean_var_weighted(xhist_plan* p, const xhist_a
                         "out_m2 is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
                           hipStream_t s = static_cast<hipStream_t>(stream);
                           ScratchScope scratch(s);
-                          double* sd = meanvar_scratch(scratch, n_rows * p->n_bins, "weighted ", err, err_cap);
+                          double* sd = two_pass_scratch(scratch, n_rows * p->n_bins, "weighted mean_var scratch block", err, err_cap);
                           if (!sd) return (int)XHIST_ERR_NOMEM;
                           return xhist_meanvar_w_run(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_m2, sd, s, err,
                                                      err_cap, desc, desc_cap);
@@ -357,11 +357,8 @@ extern "C" int xhist_plan_execute_cov(xhist_plan* p, const xhist_array* samples,
                         "out_count / out_comoment is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
                           hipStream_t s = static_cast<hipStream_t>(stream);
                           ScratchScope scratch(s);
-                          double* sd = nullptr;  // the sums of da and db, [2, n_rows, n_bins]
-                          if (scratch.alloc((void**)&sd, (size_t)(2 * n_rows * p->n_bins) * sizeof(double)) != hipSuccess) {
-                            snprintf(err, err_cap, "allocation of the cov scratch blocks failed");
-                            return (int)XHIST_ERR_NOMEM;
-                          }
+                          double* sd = two_pass_scratch(scratch, 2 * n_rows * p->n_bins, "cov scratch blocks", err, err_cap);
+                          if (!sd) return (int)XHIST_ERR_NOMEM;
                           return xhist_cov_run(pl, samples, values_a, values_b, n_rows, n_cols, out_count, out_mean, out_comoment, sd, s, err,
                                                err_cap, desc, desc_cap);
                         });

@@ -1,6 +1,7 @@
 // xhist_cov.hip — per-bin count, means, variances and covariance of two value arrays (histogram_cov): the kernels of
-// xhist_cov.hip.h, instantiated here and nowhere else, the steps between and after the two passes, and the driver (the choice
-// and the binning launches themselves: xhist_values.hip.h).
+// xhist_cov.hip.h, instantiated here and nowhere else, the steps between and after the two passes, and what the driver needs
+// of this statistic: the driver itself is two_pass_run of xhist_values.hip.h, shared with histogram_mean_var and its weighted
+// form (as are the choice and the binning launches themselves).
 //
 // Instantiations (36 binning kernels + 2):
 //   cov_sum_fast<ST, D, SCAN>, cov_dev_fast<ST, D, SCAN>    ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith     12 + 12
@@ -60,61 +61,24 @@ struct CovDevKernels {
   static cov_fn generic() { return cov_dev_generic<CMP, LDS>; }
 };
 
-// pass 1's count and two sums, pass 2's two means and five sums, whatever the type of the values; pass 2's slot decides for both
-static constexpr ValuesSlots kCovSlots = {{sizeof(CovSumSlot), sizeof(CovDevSlot)}, {sizeof(CovSumSlot), sizeof(CovDevSlot)}, true};
+// what the shared driver (two_pass_run, xhist_values.hip.h) needs of this statistic: the second value array travels in the
+// place of the weights, and the outputs are blocks of several planes
+struct Cov {
+  using Sum = CovSumKernels;
+  using Dev = CovDevKernels;
+  static constexpr auto mean = cov_mean;
+  static constexpr auto finalize = cov_finalize;
+  // pass 1's count and two sums, pass 2's two means and five sums, whatever the type of the values; pass 2's slot decides for both
+  static constexpr ValuesSlots slots = {{sizeof(CovSumSlot), sizeof(CovDevSlot)}, {sizeof(CovSumSlot), sizeof(CovDevSlot)}, true};
+  static constexpr int planes[4] = {1, 2, 3, 2};  // the count; mean_a, mean_b; M2_a, C_ab, M2_b; the sums of da and db
+  static constexpr const char *name = "cov", *prefix = "cov", *spelled = "cov";
+  static constexpr const char *lds_what = "cov: setting the dynamic LDS size failed";
+  static constexpr const char *sum_what = "cov_sum launch", *dev_what = "cov_dev launch";
+};
 
-// The zeroing and the five launches on `stream` (pass 1, means, pass 2, finalize), as meanvar_run (xhist_meanvar.hip.h) with
-// the second value array in the place of the weights and outputs of several planes.
 int xhist_cov_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values_a, const xhist_array* values_b,
                   int64_t n_rows, int64_t n_cols, int64_t* out_count, double* out_mean, double* out_comoment, double* sd,
                   hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-  const int64_t n_out = n_rows * pl.n_bins;
-  const int grid_io = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_out + 255) / 256));
-  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(out_count);
-  const struct {
-    void* p;
-    int planes;
-  } zero[4] = {{cnt, 1}, {out_mean, 2}, {out_comoment, 3}, {sd, 2}};
-  for (const auto& z : zero) {
-    hipLaunchKernelGGL(zero_words, dim3(grid_io), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(z.p), z.planes * n_out);
-    XH_VALUES_LAUNCH_CHECK("cov zeroing launch");
-  }
-
-  ValuesChoice c;
-  ValuesGeometry g;
-  cov_fn sum = nullptr, dev = nullptr;
-  if (n_cols > 0) {
-    c = choose_values(pl, kCovSlots, samples, values_a, n_cols, values_b);
-    sum = pick_values_kernel<CovSumKernels>(c, pl);
-    dev = pick_values_kernel<CovDevKernels>(c, pl);
-    if (!sum || !dev) {
-      snprintf(err, err_cap, "internal: no cov kernel for this combination");
-      return XHIST_ERR_HIP;
-    }
-    for (int k = 0; k < 2; ++k)
-      if (int rc = allow_values_lds(k ? dev : sum, c.lds_bytes[k], "cov: setting the dynamic LDS size failed", err, err_cap)) return rc;
-    g = values_geometry(pl, c, n_rows, n_cols);
-    if (int rc = launch_values_pass(sum, c.lds_bytes[0], "cov_sum launch", pl, c, g, samples, values_a, n_rows, n_cols, cnt, out_mean,
-                                    nullptr, stream, err, err_cap, values_b))
-      return rc;
-  }
-  XH_VALUES_LAUNCH(cov_mean, dim3(grid_io), dim3(256), 0, stream, cnt, out_mean, n_out);
-  XH_VALUES_LAUNCH_CHECK("cov_mean launch");
-  if (n_cols > 0) {
-    if (int rc = launch_values_pass(dev, c.lds_bytes[1], "cov_dev launch", pl, c, g, samples, values_a, n_rows, n_cols, sd, out_comoment,
-                                    out_mean, stream, err, err_cap, values_b))
-      return rc;
-  }
-  XH_VALUES_LAUNCH(cov_finalize, dim3(grid_io), dim3(256), 0, stream, cnt, sd, out_comoment, n_out);
-  XH_VALUES_LAUNCH_CHECK("cov_finalize launch");
-  if (desc && desc_cap) {
-    const char* fam = !sum ? "none" : c.fast ? "fast" : "generic";
-    const char* home = !sum ? "none" : c.lds ? "lds" : "global";
-    snprintf(desc, desc_cap,
-             "cov pass1=cov_sum_%s slots=%s pass2=cov_dev_%s slots=%s scan=%d copies=%d block=%d segs=%lld lds_bytes=%zu/%zu "
-             "tables_in_lds=%d D=%d cmp=%d",
-             fam, home, fam, home, c.scan, 1 << c.copies_log2, g.block, (long long)g.segs, c.lds_bytes[0], c.lds_bytes[1],
-             (int)c.tables_in_lds, pl.n_dims, values_cmp(pl));
-  }
-  return XHIST_OK;
+  return two_pass_run<Cov>(pl, samples, values_a, values_b, n_rows, n_cols, reinterpret_cast<unsigned long long*>(out_count), out_mean,
+                           out_comoment, sd, stream, err, err_cap, desc, desc_cap);
 }

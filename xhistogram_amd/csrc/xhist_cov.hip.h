@@ -1,5 +1,6 @@
 // xhist_cov.hip.h — per-bin count, means, sums of squared deviations and co-moment of TWO value arrays (histogram_cov): the
-// slots and the two passes' policies for the shared kernel skeletons of xhist_values.hip.h, and the binning kernels.
+// slots and the two passes' policies for the shared kernel skeletons of xhist_values.hip.h, and the binning kernels (their
+// driver: two_pass_run of xhist_values.hip.h).
 //
 // Which samples count is decided exactly as for the histogram: the same digitize, the same tables.  The second value array
 // travels where the weights of the weighted statistics travel (WParams::x_*), so the skeletons hand a policy the pair (a, b);
@@ -178,7 +179,7 @@ __global__ void __launch_bounds__(256) cov_dev_fast(const CovParams p) {
 }  // namespace xhist
 
 // The launches of histogram_cov for DEVICE arrays the caller has validated, n_rows * n_bins > 0, the plan's device current
-// (xhist_cov.hip).  out_mean is [2, n_rows, n_bins] (mean_a, mean_b), out_comoment [3, n_rows, n_bins] (M2_a, C_ab, M2_b), `sd`
+// (two_pass_run<Cov>, xhist_cov.hip).  out_mean is [2, n_rows, n_bins] (mean_a, mean_b), out_comoment [3, n_rows, n_bins] (M2_a, C_ab, M2_b), `sd`
 // a float64 [2, n_rows, n_bins] block of the caller's for the sums of da and db.  Returns XHIST_OK, or an error status with a
 // message in `err`; `desc` receives a line about the launches.  (Called by xhist_plan_execute_cov, xhist_capi.hip.)
 int xhist_cov_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values_a, const xhist_array* values_b,

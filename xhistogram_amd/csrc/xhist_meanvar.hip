@@ -1,7 +1,7 @@
 // xhist_meanvar.hip — per-bin count, mean and variance (histogram_mean_var): the kernels of xhist_meanvar.hip.h, instantiated
 // here and nowhere else, the steps between and after the two passes, and what the driver needs of this form: the driver itself
-// is meanvar_run of xhist_meanvar.hip.h, shared with the weighted form (the choice and the binning launches themselves:
-// xhist_values.hip.h).
+// is two_pass_run of xhist_values.hip.h, shared with the weighted form and the covariance (as are the choice and the binning
+// launches themselves).
 //
 // Instantiations (36 binning kernels + 2):
 //   mv_sum_fast<ST, D, SCAN>, mv_dev_fast<ST, D, SCAN>    ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith     12 + 12
@@ -54,7 +54,7 @@ struct MvDevKernels {
   static values_fn generic() { return mv_dev_generic<CMP, LDS>; }
 };
 
-// what the shared driver (meanvar_run, xhist_meanvar.hip.h) needs of this form
+// what the shared driver (two_pass_run, xhist_values.hip.h) needs of this form
 struct MeanVar {
   using Sum = MvSumKernels;
   using Dev = MvDevKernels;
@@ -62,7 +62,8 @@ struct MeanVar {
   static constexpr auto finalize = mv_finalize;
   // pass 1's count and sum, pass 2's mean and two sums, whatever the type of the values; pass 2's slot decides for both
   static constexpr ValuesSlots slots = {{sizeof(MvSumSlot), sizeof(MvDevSlot)}, {sizeof(MvSumSlot), sizeof(MvDevSlot)}, true};
-  static constexpr const char *name = "mean_var", *prefix = "mv", *form = "";
+  static constexpr int planes[4] = {1, 1, 1, 1};
+  static constexpr const char *name = "mean_var", *prefix = "mv", *spelled = "mean_var";
   static constexpr const char *lds_what = "mean_var: setting the dynamic LDS size failed";
   static constexpr const char *sum_what = "mv_sum launch", *dev_what = "mv_dev launch";
 };
@@ -70,6 +71,6 @@ struct MeanVar {
 int xhist_meanvar_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
                       int64_t* out_count, double* out_mean, double* out_m2, double* sd, hipStream_t stream, char* err, size_t err_cap,
                       char* desc, size_t desc_cap) {
-  return meanvar_run<MeanVar>(pl, samples, values, nullptr, n_rows, n_cols, reinterpret_cast<unsigned long long*>(out_count), out_mean,
-                              out_m2, sd, stream, err, err_cap, desc, desc_cap);
+  return two_pass_run<MeanVar>(pl, samples, values, nullptr, n_rows, n_cols, reinterpret_cast<unsigned long long*>(out_count), out_mean,
+                               out_m2, sd, stream, err, err_cap, desc, desc_cap);
 }

@@ -1,6 +1,6 @@
 // xhist_meanvar.hip.h — per-bin count, mean and sum of squared deviations of a value array (histogram_mean_var): the slots
-// and the two passes' policies for the shared kernel skeletons of xhist_values.hip.h, the binning kernels, and the one driver
-// of the unweighted and the weighted form (meanvar_run, at the end).
+// and the two passes' policies for the shared kernel skeletons of xhist_values.hip.h, and the binning kernels of the unweighted
+// and the weighted form (their driver: two_pass_run of xhist_values.hip.h).
 //
 // Which samples count is decided exactly as for the histogram: the same digitize, the same tables.  A counted sample whose
 // value (converted to float64, numpy's astype) is not NaN contributes that value.  Two passes over the data, the corrected
@@ -247,87 +247,15 @@ __global__ void __launch_bounds__(256) mvw_dev_fast(const WParams p) {
 }  // namespace xhist
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-// The driver of both forms: the zeroing and the five launches on `stream` (pass 1, mean, pass 2, finalize).  M names what a
-// form brings (xhist_meanvar.hip: MeanVar, xhist_meanvar_w.hip: MeanVarW):
-//   Sum, Dev          the kernel sets of the two passes, for pick_values_kernel
-//   mean, finalize    the kernels of the steps after them, over the first output (counts or sums of weights)
-//   slots             the ValuesSlots of the two passes
-//   name, prefix      the form in messages and in describe() (mean_var / mean_var_w), and its kernels' prefix (mv / mvw)
-//   form              "" or "weighted ", in front of "mean_var" where a message spells the form out
-//   lds_what, sum_what, dev_what   the messages handed to allow_values_lds and to the two launch_values_pass calls
-// `first` is out_count or out_wsum; `weights` nullptr for the unweighted form.
-namespace xhist {
-
-template <class M, class First>
-static int meanvar_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
-                       int64_t n_rows, int64_t n_cols, First* first, double* out_mean, double* out_m2, double* sd, hipStream_t stream,
-                       char* err, size_t err_cap, char* desc, size_t desc_cap) {
-  char buf[48];
-  auto what = [&](const char* a, const char* b) {  // "<a><b> launch": only XH_VALUES_LAUNCH_CHECK calls it, after a failed launch
-    snprintf(buf, sizeof buf, "%s%s launch", a, b);
-    return buf;
-  };
-  const auto mean = M::mean;
-  const auto finalize = M::finalize;
-  const int64_t n_out = n_rows * pl.n_bins;
-  const int grid_io = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_out + 255) / 256));
-  unsigned long long* zero[4] = {reinterpret_cast<unsigned long long*>(first), reinterpret_cast<unsigned long long*>(out_mean),
-                                 reinterpret_cast<unsigned long long*>(out_m2), reinterpret_cast<unsigned long long*>(sd)};
-  for (unsigned long long* z : zero) {
-    hipLaunchKernelGGL(zero_words, dim3(grid_io), dim3(256), 0, stream, z, n_out);
-    XH_VALUES_LAUNCH_CHECK(what(M::name, " zeroing"));
-  }
-
-  ValuesChoice c;
-  ValuesGeometry g;
-  values_fn_of<typename M::Sum> sum = nullptr, dev = nullptr;
-  if (n_cols > 0) {
-    c = choose_values(pl, M::slots, samples, values, n_cols, weights);
-    sum = pick_values_kernel<typename M::Sum>(c, pl);
-    dev = pick_values_kernel<typename M::Dev>(c, pl);
-    if (!sum || !dev) {
-      snprintf(err, err_cap, "internal: no %smean_var kernel for this combination", M::form);
-      return XHIST_ERR_HIP;
-    }
-    for (int k = 0; k < 2; ++k)
-      if (int rc = allow_values_lds(k ? dev : sum, c.lds_bytes[k], M::lds_what, err, err_cap)) return rc;
-    g = values_geometry(pl, c, n_rows, n_cols);
-    if (int rc = launch_values_pass(sum, c.lds_bytes[0], M::sum_what, pl, c, g, samples, values, n_rows, n_cols, first, out_mean,
-                                    nullptr, stream, err, err_cap, weights))
-      return rc;
-  }
-  XH_VALUES_LAUNCH(mean, dim3(grid_io), dim3(256), 0, stream, first, out_mean, n_out);
-  XH_VALUES_LAUNCH_CHECK(what(M::prefix, "_mean"));
-  if (n_cols > 0) {
-    if (int rc = launch_values_pass(dev, c.lds_bytes[1], M::dev_what, pl, c, g, samples, values, n_rows, n_cols, sd, out_m2,
-                                    out_mean, stream, err, err_cap, weights))
-      return rc;
-  }
-  XH_VALUES_LAUNCH(finalize, dim3(grid_io), dim3(256), 0, stream, first, sd, out_m2, n_out);
-  XH_VALUES_LAUNCH_CHECK(what(M::prefix, "_finalize"));
-  if (desc && desc_cap) {
-    const char* fam = !sum ? "none" : c.fast ? "fast" : "generic";
-    const char* home = !sum ? "none" : c.lds ? "lds" : "global";
-    snprintf(desc, desc_cap,
-             "%s pass1=%s_sum_%s slots=%s pass2=%s_dev_%s slots=%s scan=%d copies=%d block=%d segs=%lld lds_bytes=%zu/%zu "
-             "tables_in_lds=%d D=%d cmp=%d",
-             M::name, M::prefix, fam, home, M::prefix, fam, home, c.scan, 1 << c.copies_log2, g.block, (long long)g.segs, c.lds_bytes[0],
-             c.lds_bytes[1], (int)c.tables_in_lds, pl.n_dims, values_cmp(pl));
-  }
-  return XHIST_OK;
-}
-
-}  // namespace xhist
-
 // The launches of histogram_mean_var for DEVICE arrays the caller has validated, n_rows * n_bins > 0, the plan's device
-// current (meanvar_run<MeanVar>, xhist_meanvar.hip).  `sd` is a float64 [n_rows, n_bins] block of the caller's for the sums of
+// current (two_pass_run<MeanVar>, xhist_meanvar.hip).  `sd` is a float64 [n_rows, n_bins] block of the caller's for the sums of
 // d.  Returns XHIST_OK, or an error status with a message in `err`; `desc` receives a line about the launches.  (Called by
 // xhist_plan_execute_mean_var, xhist_capi.hip.)
 int xhist_meanvar_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
                       int64_t* out_count, double* out_mean, double* out_m2, double* sd, hipStream_t stream, char* err, size_t err_cap,
                       char* desc, size_t desc_cap);
 
-// The same for the weighted form (meanvar_run<MeanVarW>, xhist_meanvar_w.hip): `weights` a validated DEVICE array of the
+// The same for the weighted form (two_pass_run<MeanVarW>, xhist_meanvar_w.hip): `weights` a validated DEVICE array of the
 // samples' logical shape, the sums of weights into out_wsum (float64).  (Called by xhist_plan_execute_mean_var_weighted,
 // xhist_capi.hip.)
 int xhist_meanvar_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,

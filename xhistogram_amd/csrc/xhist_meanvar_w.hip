@@ -1,7 +1,7 @@
 // xhist_meanvar_w.hip — per-bin sum of weights, weighted mean and variance (histogram_mean_var with weights): the weighted
 // kernels of xhist_meanvar.hip.h, instantiated here and nowhere else, the steps between and after the two passes, and what the
-// driver needs of this form: the driver itself is meanvar_run of xhist_meanvar.hip.h, shared with the unweighted form (the
-// choice and the binning launches themselves: xhist_values.hip.h).
+// driver needs of this form: the driver itself is two_pass_run of xhist_values.hip.h, shared with the unweighted form and the
+// covariance (as are the choice and the binning launches themselves).
 //
 // Instantiations (36 binning kernels + 2):
 //   mvw_sum_fast<ST, D, SCAN>, mvw_dev_fast<ST, D, SCAN>    ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith     12 + 12
@@ -56,7 +56,7 @@ struct MvwDevKernels {
   static values_w_fn generic() { return mvw_dev_generic<CMP, LDS>; }
 };
 
-// what the shared driver (meanvar_run, xhist_meanvar.hip.h) needs of this form
+// what the shared driver (two_pass_run, xhist_values.hip.h) needs of this form
 struct MeanVarW {
   using Sum = MvwSumKernels;
   using Dev = MvwDevKernels;
@@ -64,7 +64,8 @@ struct MeanVarW {
   static constexpr auto finalize = mvw_finalize;
   // pass 1's sums of weights and of w*v, pass 2's mean and two sums: the slot sizes of the unweighted passes, so the same choice
   static constexpr ValuesSlots slots = {{sizeof(MvwSumSlot), sizeof(MvDevSlot)}, {sizeof(MvwSumSlot), sizeof(MvDevSlot)}, true};
-  static constexpr const char *name = "mean_var_w", *prefix = "mvw", *form = "weighted ";
+  static constexpr int planes[4] = {1, 1, 1, 1};
+  static constexpr const char *name = "mean_var_w", *prefix = "mvw", *spelled = "weighted mean_var";
   static constexpr const char *lds_what = "mean_var_w: setting the dynamic LDS size failed";
   static constexpr const char *sum_what = "mvw_sum launch", *dev_what = "mvw_dev launch";
 };
@@ -73,6 +74,6 @@ static_assert(sizeof(MvwSumSlot) == sizeof(MvSumSlot), "the weighted pass 1 keep
 int xhist_meanvar_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
                         int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_m2, double* sd, hipStream_t stream,
                         char* err, size_t err_cap, char* desc, size_t desc_cap) {
-  return meanvar_run<MeanVarW>(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_m2, sd, stream, err, err_cap, desc,
-                               desc_cap);
+  return two_pass_run<MeanVarW>(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_m2, sd, stream, err, err_cap, desc,
+                                desc_cap);
 }

@@ -1,6 +1,7 @@
-// xhist_values.hip.h — what the per-bin statistics of a value array share: histogram_extrema (xhist_extrema.hip.h) and
-// histogram_mean_var (xhist_meanvar.hip.h).  The one kernel skeleton per family, into which a statistic plugs an
-// accumulator policy, and the one host-side launcher: the family and LDS rule, the launch geometry, the Params of a launch.
+// xhist_values.hip.h — what the per-bin statistics of a value array share: histogram_extrema (xhist_extrema.hip.h),
+// histogram_mean_var (xhist_meanvar.hip.h) and histogram_cov (xhist_cov.hip.h).  The one kernel skeleton per family, into which
+// a statistic plugs an accumulator policy, and the one host-side launcher: the family and LDS rule, the launch geometry, the
+// Params of a launch, and the one driver of the two-pass statistics (two_pass_run, at the end: mean_var, its weighted form, cov).
 //
 // Which samples count is decided exactly as for the histogram: the same digitize, the same tables.  A counted sample whose
 // value is not NaN hands that value to the policy.  The slots of a workgroup sit in LDS behind the staged tables; the generic
@@ -474,6 +475,74 @@ static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what,
     kp.out2 = static_cast<uint64_t*>(out2) + r0 * pl.n_bins;
     XH_VALUES_LAUNCH(fn, dim3((unsigned)(nr * g.segs)), dim3(g.block), lds, stream, kp);
     XH_VALUES_LAUNCH_CHECK(what);
+  }
+  return XHIST_OK;
+}
+
+// The driver of the two-pass statistics: the zeroing and the five launches on `stream` (pass 1, means, pass 2, finalize).  M
+// names what a statistic brings (xhist_meanvar.hip: MeanVar, xhist_meanvar_w.hip: MeanVarW, xhist_cov.hip: Cov):
+//   Sum, Dev          the kernel sets of the two passes, for pick_values_kernel
+//   mean, finalize    the kernels of the steps after them, over the first output (counts or sums of weights)
+//   slots             the ValuesSlots of the two passes
+//   planes            the [n_rows, n_bins] planes behind first, out_mean, out_m2 and sd, in this order (cov: 1, 2, 3, 2)
+//   name, prefix      the statistic in messages and in describe() (mean_var / mean_var_w / cov), and its kernels' prefix
+//   spelled           the statistic where a message spells it out ("weighted mean_var")
+//   lds_what, sum_what, dev_what   the messages handed to allow_values_lds and to the two launch_values_pass calls
+// `first` is out_count or out_wsum; `third` the weights or the second value array, nullptr for a statistic of two streams.
+template <class M, class First>
+static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* third,
+                        int64_t n_rows, int64_t n_cols, First* first, double* out_mean, double* out_m2, double* sd, hipStream_t stream,
+                        char* err, size_t err_cap, char* desc, size_t desc_cap) {
+  char buf[48];
+  auto what = [&](const char* a, const char* b) {  // "<a><b> launch": only XH_VALUES_LAUNCH_CHECK calls it, after a failed launch
+    snprintf(buf, sizeof buf, "%s%s launch", a, b);
+    return buf;
+  };
+  const auto mean = M::mean;
+  const auto finalize = M::finalize;
+  const int64_t n_out = n_rows * pl.n_bins;
+  const int grid_io = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_out + 255) / 256));
+  void* const zero[4] = {first, out_mean, out_m2, sd};
+  for (int k = 0; k < 4; ++k) {
+    hipLaunchKernelGGL(zero_words, dim3(grid_io), dim3(256), 0, stream, static_cast<unsigned long long*>(zero[k]), M::planes[k] * n_out);
+    XH_VALUES_LAUNCH_CHECK(what(M::name, " zeroing"));
+  }
+
+  ValuesChoice c;
+  ValuesGeometry g;
+  values_fn_of<typename M::Sum> sum = nullptr, dev = nullptr;
+  if (n_cols > 0) {
+    c = choose_values(pl, M::slots, samples, values, n_cols, third);
+    sum = pick_values_kernel<typename M::Sum>(c, pl);
+    dev = pick_values_kernel<typename M::Dev>(c, pl);
+    if (!sum || !dev) {
+      snprintf(err, err_cap, "internal: no %s kernel for this combination", M::spelled);
+      return XHIST_ERR_HIP;
+    }
+    for (int k = 0; k < 2; ++k)
+      if (int rc = allow_values_lds(k ? dev : sum, c.lds_bytes[k], M::lds_what, err, err_cap)) return rc;
+    g = values_geometry(pl, c, n_rows, n_cols);
+    if (int rc = launch_values_pass(sum, c.lds_bytes[0], M::sum_what, pl, c, g, samples, values, n_rows, n_cols, first, out_mean,
+                                    nullptr, stream, err, err_cap, third))
+      return rc;
+  }
+  XH_VALUES_LAUNCH(mean, dim3(grid_io), dim3(256), 0, stream, first, out_mean, n_out);
+  XH_VALUES_LAUNCH_CHECK(what(M::prefix, "_mean"));
+  if (n_cols > 0) {
+    if (int rc = launch_values_pass(dev, c.lds_bytes[1], M::dev_what, pl, c, g, samples, values, n_rows, n_cols, sd, out_m2,
+                                    out_mean, stream, err, err_cap, third))
+      return rc;
+  }
+  XH_VALUES_LAUNCH(finalize, dim3(grid_io), dim3(256), 0, stream, first, sd, out_m2, n_out);
+  XH_VALUES_LAUNCH_CHECK(what(M::prefix, "_finalize"));
+  if (desc && desc_cap) {
+    const char* fam = !sum ? "none" : c.fast ? "fast" : "generic";
+    const char* home = !sum ? "none" : c.lds ? "lds" : "global";
+    snprintf(desc, desc_cap,
+             "%s pass1=%s_sum_%s slots=%s pass2=%s_dev_%s slots=%s scan=%d copies=%d block=%d segs=%lld lds_bytes=%zu/%zu "
+             "tables_in_lds=%d D=%d cmp=%d",
+             M::name, M::prefix, fam, home, M::prefix, fam, home, c.scan, 1 << c.copies_log2, g.block, (long long)g.segs, c.lds_bytes[0],
+             c.lds_bytes[1], (int)c.tables_in_lds, pl.n_dims, values_cmp(pl));
   }
   return XHIST_OK;
 }

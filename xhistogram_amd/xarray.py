@@ -168,6 +168,18 @@ def histogram_mean_var(*args, values, bins=None, range=None, dim=None, ddof=0, b
                  for a, suffix in ((cnt, first), (mean, "mean"), (var, "var")))
 
 
+def _with_quantile_coord(res, q, out_dims, coords, name):
+    """the DataArray of per-bin quantiles: a leading ``quantile`` dimension with coordinate ``q`` when ``q`` is 1-D, a scalar
+    ``quantile`` coordinate when it is a float (as ``DataArray.quantile`` does)"""
+    qa = np.asarray(q, dtype=np.float64)
+    if qa.ndim == 0:
+        coords = dict(coords, quantile=((), qa))
+    else:
+        out_dims = ["quantile"] + list(out_dims)
+        coords = dict(coords, quantile=(("quantile",), qa))
+    return _xr().DataArray(res, dims=out_dims, coords=coords, name=name)
+
+
 def histogram_quantile(*args, values, q, bins=None, range=None, dim=None, method="linear", block_size="auto", keep_coords=False,
                        bin_dim_suffix="_bin"):
     """Per-bin quantiles of the DataArray ``values`` over the bins of ``args``
@@ -183,14 +195,7 @@ def histogram_quantile(*args, values, q, bins=None, range=None, dim=None, method
     (res,), out_dims, coords, base = _values_statistic(
         "histogram_quantile", _core_histogram_quantile, args, values, bins, range, dim, keep_coords, bin_dim_suffix, q=q, method=method,
         block_size=block_size)
-    xr = _xr()
-    qa = np.asarray(q, dtype=np.float64)
-    if qa.ndim == 0:
-        coords = dict(coords, quantile=((), qa))
-    else:
-        out_dims = ["quantile"] + list(out_dims)
-        coords = dict(coords, quantile=(("quantile",), qa))
-    return xr.DataArray(res, dims=out_dims, coords=coords, name="%s_quantile" % base)
+    return _with_quantile_coord(res, q, out_dims, coords, "%s_quantile" % base)
 
 
 def histogram_weighted_quantile(*args, values, weights, q, bins=None, range=None, dim=None, method="inverted_cdf", block_size="auto",
@@ -206,14 +211,8 @@ def histogram_weighted_quantile(*args, values, weights, q, bins=None, range=None
     (res,), out_dims, coords, base = _values_statistic(
         "histogram_weighted_quantile", _core_histogram_weighted_quantile, args, values, bins, range, dim, keep_coords, bin_dim_suffix,
         q=q, method=method, block_size=block_size, weights=weights)
-    xr = _xr()
-    qa = np.asarray(q, dtype=np.float64)
-    if qa.ndim == 0:
-        coords = dict(coords, quantile=((), qa))
-    else:
-        out_dims = ["quantile"] + list(out_dims)
-        coords = dict(coords, quantile=(("quantile",), qa))
-    return xr.DataArray(res, dims=out_dims, coords=coords, name="%s_weighted_quantile" % base)
+    return _with_quantile_coord(res, q, out_dims, coords, "%s_weighted_quantile" % base)
+
 
 def histogram_cov(*args, values, bins=None, range=None, dim=None, ddof=0, block_size="auto", keep_coords=False, bin_dim_suffix="_bin"):
     """Per-bin count, means, variances and covariance of the pair of DataArrays ``values=(A, B)`` over the bins of ``args``
