@@ -196,6 +196,28 @@ int xhist_plan_execute_cov(xhist_plan* plan, const xhist_array* samples, const x
                            const xhist_array* values_b, int64_t n_rows, int64_t n_cols, int64_t* out_count,
                            double* out_mean, double* out_comoment, int mem_kind, void* stream);
 
+/* Weighted per-bin covariance of two value arrays (added within ABI v11): which samples count is exactly what
+ * xhist_plan_execute_cov counts, and a counted sample contributes its triple (w, a, b), all converted to float64, only if
+ * neither a nor b is NaN, whatever its weight (pairwise-complete; frequency weights, as xhist_plan_execute_mean_var_weighted's).
+ * Two passes over the four streams: W = sum(w), Swa = sum(w*a), Swb = sum(w*b); then da = a - Swa/W, db = b - Swb/W in
+ * float64, wda = w*da, wdb = w*db and
+ *   M2_a = max(0, sum(wda*da) - sum(wda)^2 / W),  C_ab = sum(wda*db) - sum(wda) sum(wdb) / W,  M2_b = max(0, sum(wdb*db) - sum(wdb)^2 / W).
+ * C_ab is not clamped.  The means and the three moments are NaN where W == 0 (empty bins, and bins whose weights sum to 0); a
+ * NaN weight on a complete pair makes its bin NaN.  Negative weights are not checked.  Variances and covariance are
+ * M2 / (W - ddof) and C_ab / (W - ddof), left to the caller.  Float64 atomics add in arbitrary order: the last bits can differ
+ * between runs, except for data whose sums are exact in every order.
+ *   values_a, values_b, weights: xhist_arrays of any real dtype, same logical [n_rows, n_cols] shape as the samples (strides 0
+ *   broadcast); all three are validated before any device work.
+ *   out_wsum (float64): contiguous [n_rows, prod(nb_d)]; out_mean (float64): contiguous [2, n_rows, prod(nb_d)], mean_a then
+ *   mean_b; out_comoment (float64): contiguous [3, n_rows, prod(nb_d)], M2_a, C_ab, M2_b.  DEVICE buffers, overwritten (no
+ *   accumulate mode); two float64 scratch blocks of [n_rows, prod(nb_d)] are taken from the library's allocator for the call.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Asynchronous on `stream`.  xhist_plan_describe then names the kernel family of each pass and where its slots live
+ *   ("cov_w pass1=covw_sum_..."). */
+int xhist_plan_execute_cov_weighted(xhist_plan* plan, const xhist_array* samples, const xhist_array* values_a,
+                                    const xhist_array* values_b, const xhist_array* weights, int64_t n_rows, int64_t n_cols,
+                                    double* out_wsum, double* out_mean, double* out_comoment, int mem_kind, void* stream);
+
 /* Per-bin quantiles of `values`, exact: every output element is what np.nanquantile(values of that bin as float64, q[i],
  * method=...) gives, bit for bit, NaN for a bin with no value.  Which samples count is exactly what xhist_plan_execute counts
  * (same digitize, last bin closed, NaN / out-of-range samples dropped); NaN values are ignored.  Rows of at most 4096 values

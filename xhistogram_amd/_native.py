@@ -70,7 +70,7 @@ EXPORTS = (
     "xhist_abi_version", "xhist_last_error", "xhist_device_count", "xhist_device_info",
     "xhist_plan_create", "xhist_plan_destroy", "xhist_plan_execute", "xhist_plan_execute_two_weights", "xhist_plan_execute_extrema",
     "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
-    "xhist_plan_execute_quantile_weighted", "xhist_plan_execute_cov",
+    "xhist_plan_execute_quantile_weighted", "xhist_plan_execute_cov", "xhist_plan_execute_cov_weighted",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -144,6 +144,10 @@ def load():
         lib.xhist_plan_execute_cov.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+        ]
+        lib.xhist_plan_execute_cov_weighted.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64,
+            C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
         ]
         lib.xhist_plan_execute_mean_var_weighted.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p,
@@ -394,6 +398,15 @@ class Plan:
         (xhist_plan_execute_cov)"""
         self._execute_values("xhist_plan_execute_cov", sample_views, (value_a_view, value_b_view), n_rows, n_cols,
                              (out_count_ptr, out_mean_ptr, out_comoment_ptr), stream=stream)
+
+    def execute_cov_weighted(self, sample_views, value_a_view, value_b_view, weight_view, n_rows, n_cols, out_wsum_ptr, out_mean_ptr,
+                             out_comoment_ptr, stream=0):
+        """per-bin sum of weights W (float64 [n_rows, bins]), weighted means (float64 [2, n_rows, bins]: mean_a, mean_b) and
+        weighted sums of squared deviations with the co-moment between them (float64 [3, n_rows, bins]: M2_a, C_ab, M2_b; NaN
+        where W == 0) of the pairwise-complete values of device-resident views, into device buffers, asynchronous on `stream`
+        (xhist_plan_execute_cov_weighted)"""
+        self._execute_values("xhist_plan_execute_cov_weighted", sample_views, (value_a_view, value_b_view, weight_view), n_rows,
+                             n_cols, (out_wsum_ptr, out_mean_ptr, out_comoment_ptr), stream=stream)
 
     def execute_mean_var_weighted(self, sample_views, value_view, weight_view, n_rows, n_cols, out_wsum_ptr, out_mean_ptr, out_m2_ptr,
                                   stream=0):

@@ -34,7 +34,7 @@ from .devicearray import DeviceArray, _nocopy_reshape_strides
 _range = range
 
 __all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
-           "histogram_weighted_quantile", "histogram_cov"]
+           "histogram_weighted_quantile", "histogram_cov", "histogram_weighted_cov", "combine_weighted_cov"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1786,21 +1786,22 @@ def _check_values_dtype(values, name="histogram_extrema"):
         raise TypeError("%s takes real values, got dtype %s" % (name, dt))
 
 
-def _upload_host(args, values, bins, weights=None):
-    """host (numpy) samples and values (and weights, if given) as DeviceArrays on the calling thread's GPU, broadcast there
-    (stride 0, not copied)"""
+def _upload_host(args, values, bins, *extras):
+    """host (numpy) samples and values (and the arrays after them: weights or a second value array, then the weights of a pair
+    of values; None: not given) as DeviceArrays on the calling thread's GPU, broadcast there (stride 0, not copied)"""
     args = [np.asarray(a) for a in args]
     args, _ = _prepare_dtypes(args, None, [a.dtype for a in args], bins, "numpy")
     dev = _host_device()
     _native.require_device(dev)
-    arrays = [DeviceArray.from_numpy(a, dev) for a in args + [np.asarray(values)] + ([] if weights is None else [np.asarray(weights)])]
+    arrays = [DeviceArray.from_numpy(a, dev) for a in args + [np.asarray(values)] + [np.asarray(e) for e in extras if e is not None]]
     shape = np.broadcast_shapes(*[a.shape for a in arrays])
     return [a.broadcast_to(shape) for a in arrays]
 
 
-def _value_views(args, values, axis, bins, backend, weights=None):
-    """the [rows, cols] views of broadcast torch tensors or DeviceArrays and of their values (and weights, if given), for a
-    per-bin statistic of the values: (plan, native views (samples..., values[, weights]), the views they were made of (their copies, if any, must outlive the
+def _value_views(args, values, axis, bins, backend, *extras):
+    """the [rows, cols] views of broadcast torch tensors or DeviceArrays and of their values (and of the arrays after them, as
+    _upload_host takes them), for a per-bin statistic of the values: (plan, native views (samples..., values[, weights or
+    second values[, weights]]), the views they were made of (their copies, if any, must outlive the
     kernels: callers hold them until the download), rows, cols, kept axes shape, device, stream).  The kept axes stay in
     place and the reduced ones have extent 1 (then come the bin axes).  The views are those of _bincount's block adapter;
     layouts no three strides describe are copied."""
@@ -1812,7 +1813,7 @@ def _value_views(args, values, axis, bins, backend, weights=None):
     cmp_domain, edges, common = _compare_domain(dtypes, bins)
     if backend == "device" and any(c is not None and a.dtype != c for a, c in zip(args, common)):
         raise TypeError("datetime64 DeviceArrays must already have the unit they share with their bin edges")
-    arrays = list(args) + [values] + ([] if weights is None else [weights])
+    arrays = list(args) + [values] + [e for e in extras if e is not None]
     order = _reduced_order(arrays[0], list(_range(ndim)) if do_full_array else axis)
     descs = [_collapse(a, axis, do_full_array, order) for a in arrays]
     views = None
@@ -1841,15 +1842,15 @@ def _value_views(args, values, axis, bins, backend, weights=None):
 
 # What the shared paths need of a per-bin statistic of values: its number of outputs (the first an int64 count when
 # `counted`, all others float64), the Plan method that fills them from output pointers, the dask step that merges the
-# partials of blocks that share output rows, whether it reads weights (histogram_cov: the second value array) after the
-# values, and, where the Plan method takes blocks of several outputs, the outputs whose pointers it is given.
+# partials of blocks that share output rows, how many arrays it reads after the values (1: weights, or histogram_cov's second
+# value array; 2: histogram_weighted_cov's second value array and weights), and, where the Plan method takes blocks of several outputs, the outputs whose pointers it is given.
 _ValueStat = namedtuple("_ValueStat", "k counted method reduce weighted ptrs", defaults=(False, None))
 
 
-def _value_stat_rows(stat, args, values, axis, bins, backend, weights=None):
+def _value_stat_rows(stat, args, values, axis, bins, backend, *extras):
     """the statistic's outputs of broadcast torch tensors or DeviceArrays: kept axes in place, reduced axes of extent 1, then
     the bin axes"""
-    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, weights)
+    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, *extras)
     n = m * plan.n_bins
     k, counted = stat.k, int(stat.counted)
     if backend == "torch":
@@ -1875,7 +1876,7 @@ def _value_stat_rows(stat, args, values, axis, bins, backend, weights=None):
 def _value_stat_block(*all_arrays, stat=None, axis=None, bins=None):
     """one dask block: its statistic as a [k, block axes (reduced ones of extent 1), bins...] float64 numpy array"""
     st = _VALUE_STATS[stat]
-    n = len(all_arrays) - 1 - int(st.weighted)  # (samples..., values[, weights])
+    n = len(all_arrays) - 1 - int(st.weighted)  # (samples..., values[, weights or second values[, weights]])
     arrays = _upload_host(all_arrays[:n], all_arrays[n], bins, *all_arrays[n + 1:])
     outs = _value_stat_rows(st, arrays[:n], arrays[n], axis, bins, "device", *arrays[n + 1:])
     return np.stack([a.astype(np.float64, copy=False) for a in outs])
@@ -1896,10 +1897,12 @@ def _drop_axes(a, axes, backend):
     return a.squeeze(axes)
 
 
-def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, weights=None):
+def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, weights=None, fourth=None):
     """the backends of a per-bin statistic of values: (backend, the outputs with the shape ``histogram`` gives, bin edges,
-    reduced axes).  dask: lazy float64 arrays, the partials merged by stat.reduce and the last step by `aggregate`."""
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, weights)
+    reduced axes).  dask: lazy float64 arrays, the partials merged by stat.reduce and the last step by `aggregate`.  `weights`
+    is the array behind the values, _values_call's `third` (the keyword is the one tests/test_chan_merge_cpu.py catches this
+    function with): the weights, or the second of a pair of values, whose weights are then `fourth`."""
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, weights, fourth)
     n_inputs = len(args)
     st = _VALUE_STATS[stat]
     if backend == "dask":
@@ -1933,20 +1936,22 @@ def histogram_extrema(*args, values, bins=None, range=None, axis=None, block_siz
     return vmin, vmax, bins
 
 
-def _values_call(args, values, bins, range, axis, name, weights=None):
+def _values_call(args, values, bins, range, axis, name, third=None, fourth=None):
     """the front of a per-bin statistic of values: argument checks before any device work, the backend, the broadcast
-    arrays (samples..., values[, weights]), the numpy originals (numpy backend), the edges of the unweighted histogram, the
+    arrays (samples..., values[, third[, fourth]]: `third` is the weights, or the second of a pair of values; `fourth`, the
+    weights of a pair of values, comes only with `third`), the numpy originals (numpy backend), the edges of the unweighted histogram, the
     normalised axis and the reduced axes"""
     if values is None:
         raise TypeError("%s needs values" % name)
     if not args:
         raise TypeError("%s needs at least one array of samples" % name)
     _check_values_dtype(values, name)
-    if weights is not None:
-        _check_values_dtype(weights, name)
+    extras = [x for x in (third, fourth) if x is not None]
+    for x in extras:
+        _check_values_dtype(x, name)
     n_inputs = len(args)
     axis = _normalise_axis(axis, args[0].ndim if hasattr(args[0], "ndim") else np.ndim(args[0]))
-    all_arrays = list(args) + [values] + ([] if weights is None else [weights])
+    all_arrays = list(args) + [values] + extras
     raw = None
     if any(_is_dask(a) for a in all_arrays):
         import dask.array as dsa
@@ -2191,7 +2196,7 @@ def histogram_cov(*args, values, bins=None, range=None, axis=None, ddof=0, block
     atomics add in arbitrary order, so the last bits can differ from run to run; data whose sums are exact in any order give
     the same bits every time.
 
-    There is no ``weights`` parameter: a weighted covariance would read a fourth array and is not provided.
+    There is no ``weights`` parameter here: the weighted covariance is :func:`histogram_weighted_cov`.
 
     Returns ``(count, mean_a, mean_b, var_a, var_b, cov_ab, bin_edges)``: count int64, the others float64, with the shape
     ``histogram`` gives (kept axes, then bin axes).  numpy in -> numpy out, torch in -> torch out on the same device
@@ -2211,12 +2216,74 @@ def histogram_cov(*args, values, bins=None, range=None, axis=None, ddof=0, block
     return n, ma, mb, _var_of(n, qa, ddof), _var_of(n, qb, ddof), _var_of(n, cc, ddof), bins
 
 
+def combine_weighted_cov(w, mean_a, mean_b, m2_a, m2_b, c_ab, axis):
+    """Merge partial weighted (W, mean_a, mean_b, M2_a, M2_b, C_ab) results over `axis` (kept as axes of extent 1) with the
+    weighted form of :func:`combine_cov`'s formula, one partial after another in index order (C order over several axes):
+        W = W1 + W2,  da = mean_a2 - mean_a1,  db = mean_b2 - mean_b1,  mean = mean1 + d * W2 / W,
+        M2 = M2_1 + M2_2 + d^2 * W1 * W2 / W,  C = C1 + C2 + da * db * W1 * W2 / W.
+    Partials with W == 0 are skipped; a NaN partial (a NaN W among them) makes the bin NaN.  Where every partial has W == 0,
+    the means and moments are NaN and W is 0.  The reduction of dask's weighted partials.  Returns float64 (W, mean_a, mean_b,
+    M2_a, M2_b, C_ab)."""
+    w, (ma, mb), (qa, qb, cc) = _chan_merge(w, [mean_a, mean_b], [m2_a, m2_b, c_ab], [(0, 0), (1, 1), (0, 1)], axis, _weighed)
+    return w, ma, mb, qa, qb, cc
+
+
+# the step of (W, mean_a, mean_b, M2_a, C_ab, M2_b) blocks, the order of the library's outputs
+_cov_w_reduce = partial(_chan_reduce, present=_weighed, pairs=((0, 0), (0, 1), (1, 1)))
+
+
+def histogram_weighted_cov(*args, values, weights, bins=None, range=None, axis=None, ddof=0, block_size="auto"):
+    """Weighted per-bin means, variances and covariance of a pair of value arrays, computed on an MI355X: :func:`histogram_cov`
+    with a weight per sample, e.g. the volume-weighted covariance of two tracers in each class, an area-weighted eddy flux, or
+    the weighted regression slope ``cov_ab / var_a`` of ``b`` on ``a``.
+
+    ``args``, ``bins``, ``range``, ``axis`` and ``values=(a, b)`` are those of :func:`histogram_cov`, and so are the counted
+    samples, the edges (those of the unweighted ``histogram`` call) and the broadcasting.  ``weights`` broadcasts like the
+    values, may have any real dtype and is taken as float64.  The statistics are pairwise-complete: a counted sample
+    contributes its triple ``(w, a, b)`` only if neither ``a`` nor ``b`` is NaN, whatever its weight.  ``block_size`` is accepted
+    and changes nothing.
+
+    The weights are frequency weights, as in the weighted :func:`histogram_mean_var`.  Two passes over the four arrays:
+    ``W = sum(w)``, ``mean_a = sum(w * a) / W``, ``mean_b = sum(w * b) / W``; then ``da = a - mean_a``, ``db = b - mean_b`` in
+    float64 and ``M2_a = max(0, sum(w * da**2) - sum(w * da)**2 / W)``, likewise ``M2_b``, and the co-moment
+    ``C_ab = sum(w * da * db) - sum(w * da) * sum(w * db) / W``, which is not clamped.  ``var_a = M2_a / (W - ddof)``,
+    ``var_b = M2_b / (W - ddof)``, ``cov_ab = C_ab / (W - ddof)``.  With integer weights and ``ddof=1``, ``cov_ab`` is
+    ``np.cov(a_bin, b_bin, fweights=w_bin)[0, 1]``; with any weights and ``ddof=0`` it is
+    ``np.cov(a_bin, b_bin, aweights=w_bin, ddof=0)[0, 1]``.  With ``w == 1``, ``W`` is ``histogram_cov``'s count and every
+    other output equals that call's.  The means and moments are NaN where ``W == 0`` (empty bins and bins whose weights sum to
+    0), variances and covariance where ``W <= ddof``.  A NaN weight on a complete pair makes its bin NaN; on an incomplete pair
+    it is dropped with the pair.  Zero weights contribute nothing (``0 * inf`` is NaN, as in ``np.average``).  Negative weights
+    are not checked: the formulas apply, the clamp of the M2 at 0 included.  Float64 atomics add in arbitrary order, so the last
+    bits can differ from run to run; data whose sums are exact in any order give the same bits every time.
+
+    Returns ``(sum_of_weights, mean_a, mean_b, var_a, var_b, cov_ab, bin_edges)``, all float64, with the shape ``histogram``
+    gives (kept axes, then bin axes).  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the
+    current stream), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block, the partials merged by
+    :func:`combine_weighted_cov`."""
+    if isinstance(values, (str, bytes)) or not isinstance(values, (tuple, list)) or len(values) != 2:
+        raise TypeError("histogram_weighted_cov needs values=(a, b), a pair of arrays")
+    a, b = values
+    if a is None or b is None:
+        raise TypeError("histogram_weighted_cov needs values=(a, b), a pair of arrays")
+    if weights is None:
+        raise TypeError("histogram_weighted_cov needs weights")
+    ddof = _check_ddof(ddof)
+    # the second value array travels where histogram_mean_var's weights travel, the weights behind it
+    backend, (w, ma, mb, qa, cc, qb), bins, _ = _value_stat("cov_w", args, a, bins, range, axis, "histogram_weighted_cov",
+                                                           partial(_cov_w_reduce, ddof=ddof), weights=b, fourth=weights)
+    if backend == "dask":
+        return w, ma, mb, qa, qb, cc, bins
+    return w, ma, mb, _var_of(w, qa, ddof), _var_of(w, qb, ddof), _var_of(w, cc, ddof), bins
+
+
 _VALUE_STATS = {
     "extrema": _ValueStat(2, False, "execute_extrema", _extrema_pair_reduce),
     "mean_var": _ValueStat(3, True, "execute_mean_var", _mean_var_reduce),
     "mean_var_w": _ValueStat(3, False, "execute_mean_var_weighted", _mean_var_w_reduce, True),
     # (count, mean_a, mean_b, M2_a, C_ab, M2_b): the library takes the count, the block of means and the block of moments
     "cov": _ValueStat(6, True, "execute_cov", _cov_reduce, True, (0, 1, 3)),
+    # (W, mean_a, mean_b, M2_a, C_ab, M2_b), all float64, in the same three blocks; two arrays after the first values
+    "cov_w": _ValueStat(6, False, "execute_cov_weighted", _cov_w_reduce, 2, (0, 1, 3)),
 }
 
 

@@ -6,6 +6,7 @@
 #include "xhist_extrema.hip.h"
 #include "xhist_meanvar.hip.h"
 #include "xhist_cov.hip.h"
+#include "xhist_cov_w.hip.h"
 #include "xhist_quantile.hip.h"
 #include "xhist_quantile_w.hip.h"
 
@@ -255,7 +256,7 @@ extern "C" int xhist_plan_execute_two_weights(xhist_plan* p, const xhist_array* 
 // ------------------------------------------------------------------------------------------
 // per-bin statistics of a value array: minimum and maximum (xhist_extrema.hip), count, mean and sum of squared deviations
 // (xhist_meanvar.hip, xhist_meanvar_w.hip), quantiles (xhist_quantile.hip, xhist_quantile_w.hip), the covariance of two value
-// arrays (xhist_cov.hip); the choice and the launches they share: xhist_values.hip.h
+// arrays (xhist_cov.hip) and its weighted form (xhist_cov_w.hip); the choice and the launches they share: xhist_values.hip.h
 // ------------------------------------------------------------------------------------------
 void xhist_log_picked_kernel(const void* fn) { log_picked_kernel(fn); }
 
@@ -275,7 +276,7 @@ static ValuesPlan values_plan(const xhist_plan* p) {
   return pl;
 }
 
-// The checks and the tail the six entry points share: `out` is the statistic's float64 output validate_arrays checks,
+// The checks and the tail the seven entry points share: `out` is the statistic's float64 output validate_arrays checks,
 // `outs_ok` whether the others are given (`outs_missing` the message if not).  run(plan, err, err_cap, desc, desc_cap) launches
 // on the plan's device; the line it writes to `desc` becomes the plan's describe().
 template <class Run>
@@ -361,6 +362,24 @@ extern "C" int xhist_plan_execute_cov(xhist_plan* p, const xhist_array* samples,
                           if (!sd) return (int)XHIST_ERR_NOMEM;
                           return xhist_cov_run(pl, samples, values_a, values_b, n_rows, n_cols, out_count, out_mean, out_comoment, sd, s, err,
                                                err_cap, desc, desc_cap);
+                        });
+}
+
+extern "C" int xhist_plan_execute_cov_weighted(xhist_plan* p, const xhist_array* samples, const xhist_array* values_a,
+                                               const xhist_array* values_b, const xhist_array* weights, int64_t n_rows, int64_t n_cols,
+                                               double* out_wsum, double* out_mean, double* out_comoment, int mem_kind, void* stream) {
+  if (!values_b) return fail(XHIST_ERR_INVALID, "values_b are required");
+  if (!weights) return fail(XHIST_ERR_INVALID, "weights are required");
+  if (int rc = validate_arrays(p, samples, values_b, n_rows, n_cols, out_mean, XHIST_F64)) return rc;
+  if (int rc = validate_arrays(p, samples, weights, n_rows, n_cols, out_wsum, XHIST_F64)) return rc;
+  return execute_values(p, "xhist_plan_execute_cov_weighted", samples, values_a, n_rows, n_cols, out_mean, out_comoment != nullptr,
+                        "out_comoment is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
+                          hipStream_t s = static_cast<hipStream_t>(stream);
+                          ScratchScope scratch(s);
+                          double* sd = two_pass_scratch(scratch, 2 * n_rows * p->n_bins, "weighted cov scratch blocks", err, err_cap);
+                          if (!sd) return (int)XHIST_ERR_NOMEM;
+                          return xhist_cov_w_run(pl, samples, values_a, values_b, weights, n_rows, n_cols, out_wsum, out_mean, out_comoment,
+                                                 sd, s, err, err_cap, desc, desc_cap);
                         });
 }
 

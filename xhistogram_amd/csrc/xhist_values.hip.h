@@ -10,6 +10,9 @@
 // The weighted statistics (histogram_mean_var with weights, xhist_meanvar_w.hip) read a third stream, the weights, through the
 // same skeletons: a policy with kWeighted = true is handed (value, weight) pairs, and its kernels take WParams.
 //
+// The weighted statistic of two value arrays (histogram_weighted_cov, xhist_cov_w.hip) reads a fourth stream the same way: a
+// policy with kSecond = true as well is handed (a, b, weight) triples, and its kernels take CovWParams.
+//
 // Nothing here instantiates a kernel: the skeletons are templates, and the kernels are instantiated in the statistic's own
 // translation unit only (xhist_capi.hip includes this header for ValuesPlan and must not gain device code).
 #pragma once
@@ -43,6 +46,14 @@ struct CovParams : WParams {
   int64_t plane;
 };
 
+// The Params of the weighted statistics of two value arrays (histogram_weighted_cov, xhist_cov_w.hip.h): CovParams, whose x_*
+// block is the second value array, and the weights, a fourth input stream laid out as the x_* block is.
+struct CovWParams : CovParams {
+  const void* y_ptr;
+  int64_t y_rs, y_cs, y_ir, y_os;
+  int32_t y_dt;
+};
+
 // An accumulator policy `Acc` is one statistic's (one pass's) use of the slots:
 //   slot_t                    one bin's LDS slot
 //   kCopies                   the fast family keeps 2^p.copies_log2 copies of every slot, lane i adding into copy
@@ -54,11 +65,19 @@ struct CovParams : WParams {
 // Outputs are [n_rows, n_bins] arrays at p.out / p.out2, pre-advanced to row p.row0; the values are p.w_*.
 // A weighted policy (kWeighted = true; its kernels take WParams, the weights at p.x_*) takes the sample's weight as well:
 //   lds_add(slots, i, v, w)  global_add(p, row, b, v, w)   (w in the sample type or float64, as v)
-// The skeletons choose the stream at compile time (if constexpr); the unweighted policies have no kWeighted.
+// A policy of two extra streams (kWeighted and kSecond = true; its kernels take CovWParams, the second value array at p.x_*
+// and the weights at p.y_*) takes both:
+//   lds_add(slots, i, a, b, w)  global_add(p, row, bin, a, b, w)
+// The skeletons choose the streams at compile time (if constexpr); the unweighted policies have no kWeighted, and only the
+// policies of xhist_cov_w.hip.h have kSecond.
 template <class Acc, class = void>
 struct AccWeighted : std::false_type {};
 template <class Acc>
 struct AccWeighted<Acc, std::enable_if_t<Acc::kWeighted>> : std::true_type {};
+template <class Acc, class = void>
+struct AccSecond : std::false_type {};
+template <class Acc>
+struct AccSecond<Acc, std::enable_if_t<Acc::kSecond>> : std::true_type {};
 //
 // The bodies take the kernel's Params as `const Params& __restrict__`.  A body is optimised on its own before it is inlined
 // into its kernel, and without __restrict__ that step must assume the LDS and global atomics may write the Params: the
@@ -74,7 +93,9 @@ struct AccWeighted<Acc, std::enable_if_t<Acc::kWeighted>> : std::true_type {};
 template <class Acc, int CMP, bool LDS, class P>
 __device__ __forceinline__ void values_generic_body(const P& __restrict__ p) {
   constexpr bool W = AccWeighted<Acc>::value;
+  constexpr bool W2 = AccSecond<Acc>::value;
   static_assert(!W || std::is_base_of<WParams, P>::value, "weighted policies read the weights of WParams");
+  static_assert(!W2 || (W && std::is_base_of<CovWParams, P>::value), "policies of two extra streams read both of CovWParams");
   using CT = typename Dom<CMP>::T;
   const int64_t row = blockIdx.x / p.segs;
   const int seg = blockIdx.x % p.segs;
@@ -97,7 +118,19 @@ __device__ __forceinline__ void values_generic_body(const P& __restrict__ p) {
     xi = row_offset(p.row0 + row, p.x_rs, p.x_ir, p.x_os) + ((int64_t)seg * blockDim.x + threadIdx.x) * p.x_cs;
     xstep = stride * p.x_cs;
   }
+  // The fourth stream walks as a per-lane address in bytes: it then holds 3 SGPRs (dtype, step), and the kernels of two extra
+  // streams keep clear of scratch too (walked by element index, covw_sum_generic<1, false> reserved 36 bytes).
+  const char* yp = nullptr;
+  int64_t ystep = 0;
+  if constexpr (W2) {
+    const int64_t eb = dt_size(p.y_dt);
+    yp = static_cast<const char*>(p.y_ptr) +
+         (row_offset(p.row0 + row, p.y_rs, p.y_ir, p.y_os) + ((int64_t)seg * blockDim.x + threadIdx.x) * p.y_cs) * eb;
+    ystep = stride * p.y_cs * eb;
+  }
   for (int64_t i = (int64_t)seg * blockDim.x + threadIdx.x; i < p.n_cols; i += stride, xi += xstep) {
+    const char* const ycur = yp;  // (this sample's weight; the address moves on here, ahead of the `continue` below)
+    if constexpr (W2) yp += ystep;
     const double v = load_as<double>(p.w_ptr, p.w_dt, voff + i * p.w_cs);
     bool ok = v == v;  // NaN values are ignored (np.fmin / np.fmax, np.nanmean / np.nanvar)
     int64_t flat = 0;
@@ -111,7 +144,12 @@ __device__ __forceinline__ void values_generic_body(const P& __restrict__ p) {
       }
     }
     if (!ok) continue;
-    if constexpr (W) {
+    if constexpr (W2) {
+      const double b = load_as<double>(p.x_ptr, p.x_dt, xi);  // (both only for a sample that counts)
+      const double w = load_as<double>(ycur, p.y_dt, 0);
+      if (LDS) Acc::lds_add(slots, (uint32_t)flat, v, b, w);
+      else Acc::global_add(p, row, flat, v, b, w);
+    } else if constexpr (W) {
       const double w = load_as<double>(p.x_ptr, p.x_dt, xi);  // (only for a sample that counts)
       if (LDS) Acc::lds_add(slots, (uint32_t)flat, v, w);
       else Acc::global_add(p, row, flat, v, w);
@@ -131,20 +169,48 @@ __device__ __forceinline__ void values_generic_body(const P& __restrict__ p) {
 // in LDS; digitize by the tables with at most two edges per bucket (SCAN 1 / 2: float64 edges for float64 samples, float32
 // thresholds for float32 ones) or by arithmetic (kScanArith).  Tiles as in hist_fast: VEC elements per 16-byte
 // non-temporal load, UNROLL loads in flight per array and lane; the workgroups of a row walk its tiles interleaved.  A weighted
-// policy's weights have the sample type and unit column stride too, and are loaded the same way.
+// policy's weights have the sample type and unit column stride too, and are loaded the same way; so is the fourth stream of a
+// policy with kSecond.
 // ---------------------------------------------------------------------------------------------
+// the parts a fast form reads its tile in: the fewest (a power of two, at most one load per array and part) that keep `limit`
+// bytes per lane in flight
+constexpr int fast_halves(int tile_bytes, int limit, int unroll) {
+  int h = 1;
+  while (tile_bytes / h > limit && h < unroll) h *= 2;
+  return h;
+}
+
 template <class Acc, typename ST, int D, int SCAN, class P>
 __device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
   constexpr bool W = AccWeighted<Acc>::value;
+  constexpr bool W2 = AccSecond<Acc>::value;
   static_assert(!W || std::is_base_of<WParams, P>::value, "weighted policies read the weights of WParams");
+  static_assert(!W2 || (W && std::is_base_of<CovWParams, P>::value), "policies of two extra streams read both of CovWParams");
   static_assert(__is_same(ST, double) || __is_same(ST, float), "float32 / float64 samples and values");
   static_assert(SCAN == 1 || SCAN == 2 || SCAN == kScanArith, "tables with <= 2 edges per bucket, or arithmetic edges");
   constexpr int CMP = (__is_same(ST, float) && SCAN != kScanArith) ? 2 : 0;
   constexpr int VEC = 16 / (int)sizeof(ST);
   constexpr int UNROLL = D == 1 ? 4 : 8 / VEC;  // 128 bytes of samples and values per lane in flight (192 for two inputs)
-  // Weighted float64 pairs read a tile in two halves of UNROLL / 2 loads per array: four streams then keep 128 bytes per lane in
-  // flight, and the VGPRs, hence the waves per SIMD, of the unweighted form.  The tile, and with it the launch geometry, stays.
-  constexpr int HALVES = (W && D == 2 && __is_same(ST, double)) ? 2 : 1;
+  // A form reads STREAMS arrays (D inputs, the values, the weights or second values, the fourth stream) of 16 * UNROLL bytes per
+  // lane and tile each, and reads its tile in HALVES parts of UNROLL / HALVES loads per array (fast_halves).  The tile, and with
+  // it the launch geometry, stays.  No form keeps more than 192 bytes per lane in flight, what three streams of 64 bytes hold:
+  // weighted float64 pairs would keep 256, and in two halves they keep the VGPRs, hence the waves per SIMD, of the unweighted
+  // form.  The same rule serves the forms with a fourth stream: their single inputs read two halves (128 bytes), float64 pairs
+  // two halves and float32 pairs the whole tile (160 bytes).  Six of the pair kernels then have three waves per SIMD where
+  // their histogram_cov twins have four; splitting further to keep the wave was measured and is slower.
+  //   streams   form                                    whole tile   HALVES   in flight per lane
+  //   2         single input                                  128        1         128
+  //   3         single input, weighted or two values          192        1         192
+  //   3         float64 pairs                                 192        1         192
+  //   3         float32 pairs                                  96        1          96
+  //   4         float64 pairs, weighted or two values         256        2         128
+  //   4         float32 pairs, weighted or two values         128        1         128
+  //   4         single input, two values and weights          256        2         128   (float64 and float32)
+  //   5         float64 pairs, two values and weights         320        2         160
+  //   5         float32 pairs, two values and weights         160        1         160
+  constexpr int STREAMS = D + 1 + (W ? 1 : 0) + (W2 ? 1 : 0);
+  constexpr int HALVES = fast_halves(STREAMS * 16 * UNROLL, 192, UNROLL);
+  static_assert(W2 || HALVES == ((W && D == 2 && __is_same(ST, double)) ? 2 : 1), "the forms of up to four streams keep their halves");
   constexpr int UH = UNROLL / HALVES;
   using svec = typename VecOf<ST, VEC>::type;
 
@@ -162,6 +228,8 @@ __device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
   const ST* vp = reinterpret_cast<const ST*>(p.w_ptr) + row_offset(p.row0 + row, p.w_rs, p.w_ir, p.w_os);
   const ST* xp = nullptr;
   if constexpr (W) xp = reinterpret_cast<const ST*>(p.x_ptr) + row_offset(p.row0 + row, p.x_rs, p.x_ir, p.x_os);
+  const ST* yp = nullptr;
+  if constexpr (W2) yp = reinterpret_cast<const ST*>(p.y_ptr) + row_offset(p.row0 + row, p.y_rs, p.y_ir, p.y_os);
   const uint32_t nb1 = D == 2 ? (uint32_t)p.dim[1].nb : 1u;
   const uint32_t mycopy = Acc::kCopies ? (uint32_t)tid & ((1u << p.copies_log2) - 1u) : 0u;
 
@@ -172,7 +240,7 @@ __device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
     const bool full = base + tile_elems <= p.n_cols;
 #pragma unroll
     for (int h = 0; h < HALVES; ++h) {
-      svec xv[D][UH], vv[UH], wv[W ? UH : 1];
+      svec xv[D][UH], vv[UH], wv[W ? UH : 1], yv[W2 ? UH : 1];
       if (full) {
 #pragma unroll
         for (int u = 0; u < UH; ++u) {
@@ -181,6 +249,7 @@ __device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
           for (int d = 0; d < D; ++d) xv[d][u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(sp[d] + i));
           vv[u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(vp + i));
           if constexpr (W) wv[u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(xp + i));
+          if constexpr (W2) yv[u] = __builtin_nontemporal_load(reinterpret_cast<const svec*>(yp + i));
         }
       } else {  // the ragged last tile: positions past the end become NaN samples, which digitize drops (their weights are 0)
 #pragma unroll
@@ -193,6 +262,7 @@ __device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
             for (int d = 0; d < D; ++d) xv[d][u][v] = in ? sp[d][i + v] : (ST)__builtin_nanf("");
             vv[u][v] = in ? vp[i + v] : (ST)__builtin_nanf("");
             if constexpr (W) wv[u][v] = in ? xp[i + v] : (ST)0;
+            if constexpr (W2) yv[u][v] = in ? yp[i + v] : (ST)0;
           }
         }
       }
@@ -211,7 +281,9 @@ __device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
             ok &= b >= 0;
             flat = d == 0 ? (uint32_t)b : flat * nb1 + (uint32_t)b;
           }
-          if constexpr (W) {
+          if constexpr (W2) {
+            if (ok) Acc::lds_add(slots, Acc::kCopies ? (flat << p.copies_log2) + mycopy : flat, val, (ST)wv[u][v], (ST)yv[u][v]);
+          } else if constexpr (W) {
             if (ok) Acc::lds_add(slots, Acc::kCopies ? (flat << p.copies_log2) + mycopy : flat, val, (ST)wv[u][v]);
           } else {
             if (ok) Acc::lds_add(slots, Acc::kCopies ? (flat << p.copies_log2) + mycopy : flat, val);
@@ -300,9 +372,11 @@ static inline int fast_copies_log2(int64_t n_bins, size_t slot, size_t tbytes, s
 
 // fast if eligible, else generic with its slots in LDS, else generic straight into global memory.  The largest slot of the
 // passes decides; every pass takes the family, the home and the copies chosen for it.  `weights` (nullptr: unweighted) must
-// qualify for the fast family as the values do: the sample dtype, unit column stride (or one column), element-aligned.
+// qualify for the fast family as the values do: the sample dtype, unit column stride (or one column), element-aligned; so must
+// `fourth` (nullptr: no fourth stream), and either alone sends the call to the generic family.
 static inline ValuesChoice choose_values(const ValuesPlan& pl, const ValuesSlots& sl, const xhist_array* samples,
-                                         const xhist_array* values, int64_t n_cols, const xhist_array* weights = nullptr) {
+                                         const xhist_array* values, int64_t n_cols, const xhist_array* weights = nullptr,
+                                         const xhist_array* fourth = nullptr) {
   ValuesChoice c;
   const int D = pl.n_dims;
   const int sdt = samples[0].dtype;
@@ -312,8 +386,8 @@ static inline ValuesChoice choose_values(const ValuesPlan& pl, const ValuesSlots
   for (int d = 0; d < D && fast_ok; ++d)
     fast_ok = samples[d].dtype == sdt && (samples[d].col_stride == 1 || n_cols == 1) && (uintptr_t)samples[d].data % (size_t)elem_bytes(sdt) == 0;
   if (fast_ok) fast_ok = (values->col_stride == 1 || n_cols == 1) && (uintptr_t)values->data % (size_t)elem_bytes(sdt) == 0;
-  if (fast_ok && weights)
-    fast_ok = weights->dtype == sdt && (weights->col_stride == 1 || n_cols == 1) && (uintptr_t)weights->data % (size_t)elem_bytes(sdt) == 0;
+  for (const xhist_array* x : {weights, fourth})
+    if (fast_ok && x) fast_ok = x->dtype == sdt && (x->col_stride == 1 || n_cols == 1) && (uintptr_t)x->data % (size_t)elem_bytes(sdt) == 0;
   if (fast_ok) {
     const size_t* bytes = c.f32 ? sl.fast32 : sl.bytes;
     const size_t slot = std::max(bytes[0], bytes[1]);
@@ -454,22 +528,33 @@ static inline void weights_params(WParams& kp, const xhist_array* weights) {
   kp.x_os = weights->outer_stride;
   kp.x_dt = weights->dtype;
 }
+// ... and the fourth stream of a CovWParams launch
+static inline void weights_params(CovWParams& kp, const xhist_array* third, const xhist_array* fourth) {
+  weights_params(kp, third);
+  kp.y_ptr = fourth->data;
+  kp.y_rs = fourth->row_stride;
+  kp.y_cs = fourth->col_stride;
+  kp.y_ir = fourth->inner_rows;
+  kp.y_os = fourth->outer_stride;
+  kp.y_dt = fourth->dtype;
+}
 
 // One binning pass: the launches of row chunks of at most g.max_rows (the grid stays below 2^31 workgroups and 2^32 lanes).  out / out2 / in2 are [n_rows, n_bins] arrays of 8-byte elements,
 // advanced to each chunk's first row (Params::out, out2 and w2_ptr); `what` names the pass in error messages.  A weighted
 // kernel (it takes WParams) reads `weights`; for a CovParams kernel each of the three is the first of several such arrays,
-// n_rows * n_bins elements apart.
+// n_rows * n_bins elements apart; a CovWParams kernel reads `fourth` as well.
 template <class P>
 static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what, const ValuesPlan& pl,
                               const ValuesChoice& c, const ValuesGeometry& g, const xhist_array* samples, const xhist_array* values,
                               int64_t n_rows, int64_t n_cols, void* out, void* out2, const void* in2, hipStream_t stream, char* err,
-                              size_t err_cap, const xhist_array* weights = nullptr) {
+                              size_t err_cap, const xhist_array* weights = nullptr, const xhist_array* fourth = nullptr) {
   for (int64_t r0 = 0; r0 < n_rows; r0 += g.max_rows) {
     const int64_t nr = std::min(g.max_rows, n_rows - r0);
     P kp;
     static_cast<Params&>(kp) = values_params(pl, c, g.segs, samples, values, r0, nr, n_cols);
-    if constexpr (std::is_base_of<WParams, P>::value) weights_params(kp, weights);
-    if constexpr (std::is_same<P, CovParams>::value) kp.plane = n_rows * pl.n_bins;  // (the whole call's rows, whatever the chunk)
+    if constexpr (std::is_base_of<CovWParams, P>::value) weights_params(kp, weights, fourth);
+    else if constexpr (std::is_base_of<WParams, P>::value) weights_params(kp, weights);
+    if constexpr (std::is_base_of<CovParams, P>::value) kp.plane = n_rows * pl.n_bins;  // (the whole call's rows, whatever the chunk)
     kp.w2_ptr = in2 ? static_cast<const uint64_t*>(in2) + r0 * pl.n_bins : nullptr;
     kp.out = static_cast<uint64_t*>(out) + r0 * pl.n_bins;
     kp.out2 = static_cast<uint64_t*>(out2) + r0 * pl.n_bins;
@@ -480,7 +565,8 @@ static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what,
 }
 
 // The driver of the two-pass statistics: the zeroing and the five launches on `stream` (pass 1, means, pass 2, finalize).  M
-// names what a statistic brings (xhist_meanvar.hip: MeanVar, xhist_meanvar_w.hip: MeanVarW, xhist_cov.hip: Cov):
+// names what a statistic brings (xhist_meanvar.hip: MeanVar, xhist_meanvar_w.hip: MeanVarW, xhist_cov.hip: Cov, xhist_cov_w.hip:
+// CovW):
 //   Sum, Dev          the kernel sets of the two passes, for pick_values_kernel
 //   mean, finalize    the kernels of the steps after them, over the first output (counts or sums of weights)
 //   slots             the ValuesSlots of the two passes
@@ -488,11 +574,12 @@ static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what,
 //   name, prefix      the statistic in messages and in describe() (mean_var / mean_var_w / cov), and its kernels' prefix
 //   spelled           the statistic where a message spells it out ("weighted mean_var")
 //   lds_what, sum_what, dev_what   the messages handed to allow_values_lds and to the two launch_values_pass calls
-// `first` is out_count or out_wsum; `third` the weights or the second value array, nullptr for a statistic of two streams.
+// `first` is out_count or out_wsum; `third` the weights or the second value array, nullptr for a statistic of two streams;
+// `fourth` the weights of a statistic of two value arrays, nullptr for every other.
 template <class M, class First>
 static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* third,
                         int64_t n_rows, int64_t n_cols, First* first, double* out_mean, double* out_m2, double* sd, hipStream_t stream,
-                        char* err, size_t err_cap, char* desc, size_t desc_cap) {
+                        char* err, size_t err_cap, char* desc, size_t desc_cap, const xhist_array* fourth = nullptr) {
   char buf[48];
   auto what = [&](const char* a, const char* b) {  // "<a><b> launch": only XH_VALUES_LAUNCH_CHECK calls it, after a failed launch
     snprintf(buf, sizeof buf, "%s%s launch", a, b);
@@ -512,7 +599,7 @@ static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const 
   ValuesGeometry g;
   values_fn_of<typename M::Sum> sum = nullptr, dev = nullptr;
   if (n_cols > 0) {
-    c = choose_values(pl, M::slots, samples, values, n_cols, third);
+    c = choose_values(pl, M::slots, samples, values, n_cols, third, fourth);
     sum = pick_values_kernel<typename M::Sum>(c, pl);
     dev = pick_values_kernel<typename M::Dev>(c, pl);
     if (!sum || !dev) {
@@ -523,14 +610,14 @@ static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const 
       if (int rc = allow_values_lds(k ? dev : sum, c.lds_bytes[k], M::lds_what, err, err_cap)) return rc;
     g = values_geometry(pl, c, n_rows, n_cols);
     if (int rc = launch_values_pass(sum, c.lds_bytes[0], M::sum_what, pl, c, g, samples, values, n_rows, n_cols, first, out_mean,
-                                    nullptr, stream, err, err_cap, third))
+                                    nullptr, stream, err, err_cap, third, fourth))
       return rc;
   }
   XH_VALUES_LAUNCH(mean, dim3(grid_io), dim3(256), 0, stream, first, out_mean, n_out);
   XH_VALUES_LAUNCH_CHECK(what(M::prefix, "_mean"));
   if (n_cols > 0) {
     if (int rc = launch_values_pass(dev, c.lds_bytes[1], M::dev_what, pl, c, g, samples, values, n_rows, n_cols, sd, out_m2,
-                                    out_mean, stream, err, err_cap, third))
+                                    out_mean, stream, err, err_cap, third, fourth))
       return rc;
   }
   XH_VALUES_LAUNCH(finalize, dim3(grid_io), dim3(256), 0, stream, first, sd, out_m2, n_out);

@@ -14,7 +14,7 @@ from .core import histogram as _core_histogram
 from .core import histogram_two_weights as _core_histogram_two_weights
 
 __all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
-           "histogram_cov"]
+           "histogram_cov", "histogram_weighted_cov"]
 
 
 def _xr():
@@ -222,7 +222,8 @@ def histogram_cov(*args, values, bins=None, range=None, dim=None, ddof=0, block_
     ``B`` are lined up as ``values`` of :func:`histogram_mean_var` (dims a subset of the data's).  Returns a dict of six
     DataArrays with the dims and coords ``histogram`` gives, keyed by their names (``xarray.Dataset(result)`` makes a Dataset
     of it): ``<a>_<b>_count``, ``<a>_mean``, ``<b>_mean``, ``<a>_var``, ``<b>_var``, ``<a>_<b>_cov``, with ``<a>`` / ``<b>``
-    the names of the DataArrays (``a`` / ``b`` for a nameless one).  There is no ``weights`` parameter."""
+    the names of the DataArrays (``a`` / ``b`` for a nameless one).  There is no ``weights`` parameter here: the weighted form
+    is :func:`histogram_weighted_cov`."""
     from .core import histogram_cov as _core_histogram_cov
 
     if isinstance(values, (str, bytes)) or not isinstance(values, (tuple, list)) or len(values) != 2:
@@ -240,13 +241,42 @@ def histogram_cov(*args, values, bins=None, range=None, dim=None, ddof=0, block_
     return {n: xr.DataArray(r, dims=out_dims, coords=coords, name=n) for n, r in zip(names, results)}
 
 
-def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords, bin_dim_suffix, weights=None, **kw):
+def histogram_weighted_cov(*args, values, weights, bins=None, range=None, dim=None, ddof=0, block_size="auto", keep_coords=False,
+                           bin_dim_suffix="_bin"):
+    """Weighted per-bin means, variances and covariance of the pair of DataArrays ``values=(A, B)`` over the bins of ``args``
+    (:func:`xhistogram_amd.core.histogram_weighted_cov` with the labels of :func:`histogram_cov`).
+
+    ``weights`` is a DataArray whose dims are a subset of the data's, aligned and broadcast as ``A`` and ``B`` are (cell areas
+    or volumes, ``cos(lat)``).  Returns a dict of six DataArrays named like :func:`histogram_cov`'s, with
+    ``<a>_<b>_sum_of_weights`` in place of ``<a>_<b>_count``."""
+    from .core import histogram_weighted_cov as _core_histogram_weighted_cov
+
+    if isinstance(values, (str, bytes)) or not isinstance(values, (tuple, list)) or len(values) != 2:
+        raise TypeError("histogram_weighted_cov needs values=(A, B), a pair of DataArrays")
+    if weights is None:
+        raise TypeError("histogram_weighted_cov needs weights")
+    A, B = values
+
+    def triple(*arrays, values, second, weights, **kw):
+        return _core_histogram_weighted_cov(*arrays, values=(values, second), weights=weights, **kw)
+
+    results, out_dims, coords, _ = _values_statistic(
+        "histogram_weighted_cov", triple, args, A, bins, range, dim, keep_coords, bin_dim_suffix, ddof=ddof, block_size=block_size,
+        weights=weights, second=B)
+    xr = _xr()
+    a, b = A.name or "a", B.name or "b"
+    names = ("%s_%s_sum_of_weights" % (a, b), "%s_mean" % a, "%s_mean" % b, "%s_var" % a, "%s_var" % b, "%s_%s_cov" % (a, b))
+    return {n: xr.DataArray(r, dims=out_dims, coords=coords, name=n) for n, r in zip(names, results)}
+
+
+def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords, bin_dim_suffix, weights=None, second=None, **kw):
     """a per-bin statistic of ``values`` with the labels of :func:`histogram`: (core_fn's arrays, dims, coords, the values'
-    name or "values").  ``weights`` (a DataArray or None) is lined up as ``values`` is and passed on as core_fn's weights."""
+    name or "values").  ``weights`` (a DataArray or None) is lined up as ``values`` is and passed on as core_fn's weights; so is
+    ``second``, the second of a pair of values that comes with weights of its own, as core_fn's ``second``."""
     xr = _xr()
     data_args = list(args)
     n_data = len(data_args)
-    extra = [values] + ([] if weights is None else [weights])
+    extra = [values] + ([] if second is None else [second]) + ([] if weights is None else [weights])
     for a in data_args + extra:
         if not isinstance(a, xr.DataArray):
             raise TypeError(
@@ -275,6 +305,8 @@ def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords
     arrays = [a.data for a in lined_up]
     if weights is not None:
         kw["weights"] = arrays.pop()
+    if second is not None:
+        kw["second"] = arrays.pop()
     v_data = arrays.pop()
     if dim is not None:
         kept_dims = [d for d in dims_order if d not in dim]
