@@ -5,8 +5,8 @@ against the oracle's and the histogram's, both means bit for bit, and M2_a, C_ab
 of two up to 2^9 and within cov_exact's float64 bounds elsewhere.  Every census case also checks its whole describe() line
 against test_gpu_values_census.predict, a restatement of choose_values / values_geometry, with the slot sizes of the two cov
 passes (24 and 56 bytes, copies) registered in that module's tables from here.  Between them the fast-form and generic cases
-select all 36 binning kernels of xhist_cov.hip plus cov_mean and cov_finalize (tests/test_zz_gpu_census_total.py holds the
-session to that).
+select all 36 binning kernels of xhist_cov.hip plus its moments_mean and moments_finalize (tests/test_zz_gpu_census_total.py
+holds the session to that).
 
 What the launcher decides at run time inside one kernel symbol is not covered here: every census case of this file has one
 copy of its slots, one row chunk and dense arrays.  The copies of the 24 / 56-byte slots, the LDS borders, the tables read
@@ -37,7 +37,7 @@ torch = pytest.importorskip("torch")
 F64, F32 = np.float64, np.float32
 PY39 = "/opt/conda/bin/python3.9"
 SCRIPT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cov_dask_script.py")
-SLOT1, SLOT2 = 24, 56  # a bin's LDS slot in the two passes (CovSumSlot, CovDevSlot of xhist_cov.hip.h)
+SLOT1, SLOT2 = 24, 56  # a bin's LDS slot in the two passes (MomentSumSlot<2, .>, MomentDevSlot<2> of xhist_moments.hip.h)
 tvc.SLOTS.setdefault("cov", ((SLOT1, SLOT2), (SLOT1, SLOT2)))
 tvc.COPIES.setdefault("cov", True)
 

@@ -10,8 +10,8 @@ copies): the weighted line is put into cov's words by `as_cov_line`, as test_gpu
 mean_var, and the fast family is given up when b or the weights alone disqualify it (`streams_fast`, restated from
 choose_values).
 
-The cases: every fast form, every generic kernel (between them all 36 binning kernels of xhist_cov_w.hip plus covw_mean and
-covw_finalize, which tests/test_zz_gpu_census_total.py holds the session to), ragged tiles around the tile's end and around the split point of every
+The cases: every fast form, every generic kernel (between them all 36 binning kernels of xhist_cov_w.hip plus its moments_mean and
+moments_finalize, which tests/test_zz_gpu_census_total.py holds the session to), ragged tiles around the tile's end and around the split point of every
 form that reads its tile in halves, each of the four streams misaligned on its own, b and the weights each alone
 at a column stride or of another dtype, row stride 0 for either, every number of copies, one LDS border from both sides, more
 than one row chunk through the C ABI, the NaN and zero rules, w == 1 and repeated samples against histogram_cov, b = a against

@@ -71,6 +71,7 @@ struct ExtAcc {
   using K = ExtKeys<KT>;
   using slot_t = typename K::slot_t;
   static constexpr bool kCopies = false;
+  static constexpr int kExtra = 0;
   static __device__ __forceinline__ void init(slot_t* slots, const Params& p, int64_t) {
     slot_t e;
     e[0] = K::kMin;

@@ -1,44 +1,16 @@
-// xhist_meanvar.hip — per-bin count, mean and variance (histogram_mean_var): the kernels of xhist_meanvar.hip.h, instantiated
-// here and nowhere else, the steps between and after the two passes, and what the driver needs of this form: the driver itself
-// is two_pass_run of xhist_values.hip.h, shared with the weighted form and the covariance (as are the choice and the binning
-// launches themselves).
+// xhist_meanvar.hip — per-bin count, mean and variance (histogram_mean_var): the kernels of xhist_meanvar.hip.h and the steps
+// between and after the two passes (xhist_moments.hip.h), instantiated here and nowhere else, and what the driver needs of this
+// form: the driver itself is two_pass_run of xhist_values.hip.h, shared with the weighted form and the covariance (as are the
+// choice and the binning launches themselves).
 //
 // Instantiations (36 binning kernels + 2):
 //   mv_sum_fast<ST, D, SCAN>, mv_dev_fast<ST, D, SCAN>    ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith     12 + 12
 //   mv_sum_generic<CMP, LDS>, mv_dev_generic<CMP, LDS>    CMP 0 / 1 / 3, slots in LDS or sums in global memory       6 + 6
-//   mv_mean, mv_finalize                                                                                              2
+//   moments_mean<1, unsigned long long>, moments_finalize<1, unsigned long long>                                      2
 // (and zero_words of xhist_kernels.hip.h, which is not dispatched)
 #include "xhist_meanvar.hip.h"
 
 using namespace xhist;
-
-namespace xhist {
-
-// the sums of pass 1 -> means, in place: S / n, NaN where no value arrived
-__global__ void __launch_bounds__(256) mv_mean(const unsigned long long* cnt, double* sum, int64_t n) {
-  const double nan = __builtin_nan("");
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const unsigned long long c = cnt[i];
-    sum[i] = c ? sum[i] / (double)c : nan;
-  }
-}
-
-// the sums of pass 2 -> M2 = max(0, sum(d*d) - sum(d)^2 / n), in place; NaN where no value arrived, and NaN stays NaN
-__global__ void __launch_bounds__(256) mv_finalize(const unsigned long long* cnt, const double* sd, double* m2, int64_t n) {
-  const double nan = __builtin_nan("");
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const unsigned long long c = cnt[i];
-    if (!c) {
-      m2[i] = nan;
-      continue;
-    }
-    const double s = sd[i];
-    const double r = m2[i] - s * s / (double)c;
-    m2[i] = r <= 0.0 ? 0.0 : r;
-  }
-}
-
-}  // namespace xhist
 
 // the binning kernels of each pass, for pick_values_kernel
 struct MvSumKernels {
@@ -58,14 +30,11 @@ struct MvDevKernels {
 struct MeanVar {
   using Sum = MvSumKernels;
   using Dev = MvDevKernels;
-  static constexpr auto mean = mv_mean;
-  static constexpr auto finalize = mv_finalize;
-  // pass 1's count and sum, pass 2's mean and two sums, whatever the type of the values; pass 2's slot decides for both
-  static constexpr ValuesSlots slots = {{sizeof(MvSumSlot), sizeof(MvDevSlot)}, {sizeof(MvSumSlot), sizeof(MvDevSlot)}, true};
+  static constexpr auto mean = moments_mean<1, unsigned long long>;
+  static constexpr auto finalize = moments_finalize<1, unsigned long long>;
+  static constexpr ValuesSlots slots = moment_slots<1, false>();
   static constexpr int planes[4] = {1, 1, 1, 1};
   static constexpr const char *name = "mean_var", *prefix = "mv", *spelled = "mean_var";
-  static constexpr const char *lds_what = "mean_var: setting the dynamic LDS size failed";
-  static constexpr const char *sum_what = "mv_sum launch", *dev_what = "mv_dev launch";
 };
 
 int xhist_meanvar_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,

@@ -122,6 +122,7 @@ __device__ __forceinline__ QHdr& q_hdr() {
 struct QWinAcc {
   using slot_t = uint64_t;
   static constexpr bool kCopies = false;
+  static constexpr int kExtra = 0;
   static __device__ __forceinline__ void init(slot_t* s, const Params& p, int64_t row) {
     const uint32_t n = (uint32_t)p.n_bins * (uint32_t)p.n_parts;
     if (threadIdx.x == 0) q_hdr() = QHdr{(uint32_t)p.n_parts, 0u, n * 4u};
@@ -178,6 +179,7 @@ struct QWinAcc {
 struct QDigitAcc {
   using slot_t = uint64_t;
   static constexpr bool kCopies = false;
+  static constexpr int kExtra = 0;
   // a target's prefix mask, digit shift and digit mask for digits of d bits
   static __device__ __forceinline__ void digit_of(const QTgt& t, uint32_t d, uint64_t& him, uint32_t& dshift, uint32_t& dmask) {
     him = q_himask(t.nfix);

@@ -78,7 +78,8 @@ __device__ __forceinline__ bool qw_reached(double c, double w, double q) { retur
 // LDS: per bin {mn, mx, W}.  Global records: p.out = QWWin [rows, bins].
 struct QWWinAcc {
   using slot_t = uint64_t;
-  static constexpr bool kCopies = false, kWeighted = true;
+  static constexpr bool kCopies = false;
+  static constexpr int kExtra = 1;
   static __device__ __forceinline__ void init(slot_t* s, const Params& p, int64_t) {
     const uint32_t n = (uint32_t)p.n_bins;
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
@@ -122,7 +123,8 @@ struct QWWinAcc {
 // Global: p.w2_ptr = QWTgt [rows, bins, T] (read only), p.out = float64 sums [rows, bins, T, 2^d].
 struct QWDigitAcc {
   using slot_t = uint64_t;
-  static constexpr bool kCopies = false, kWeighted = true;
+  static constexpr bool kCopies = false;
+  static constexpr int kExtra = 1;
   static __device__ __forceinline__ void digit_of(const QWTgt& t, uint32_t d, uint64_t& him, uint32_t& dshift, uint32_t& dmask) {
     him = q_himask(t.nfix);
     const uint32_t left = 64u - t.nfix, dd = left < d ? left : d;

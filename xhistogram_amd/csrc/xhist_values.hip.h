@@ -1,5 +1,6 @@
-// xhist_values.hip.h — what the per-bin statistics of a value array share: histogram_extrema (xhist_extrema.hip.h),
-// histogram_mean_var (xhist_meanvar.hip.h) and histogram_cov (xhist_cov.hip.h).  The one kernel skeleton per family, into which
+// xhist_values.hip.h — what the per-bin statistics of a value array share: histogram_extrema (xhist_extrema.hip.h), the
+// quantiles (xhist_quantile.hip.h) and the moments (xhist_moments.hip.h: histogram_mean_var, histogram_cov and their weighted
+// forms).  The one kernel skeleton per family, into which
 // a statistic plugs an accumulator policy, and the one host-side launcher: the family and LDS rule, the launch geometry, the
 // Params of a launch, and the one driver of the two-pass statistics (two_pass_run, at the end: mean_var, its weighted form, cov).
 //
@@ -8,10 +9,10 @@
 // family without LDS room hands every value straight to global memory.
 //
 // The weighted statistics (histogram_mean_var with weights, xhist_meanvar_w.hip) read a third stream, the weights, through the
-// same skeletons: a policy with kWeighted = true is handed (value, weight) pairs, and its kernels take WParams.
+// same skeletons: a policy with kExtra = 1 is handed (value, weight) pairs, and its kernels take WParams.
 //
 // The weighted statistic of two value arrays (histogram_weighted_cov, xhist_cov_w.hip) reads a fourth stream the same way: a
-// policy with kSecond = true as well is handed (a, b, weight) triples, and its kernels take CovWParams.
+// policy with kExtra = 2 is handed (a, b, weight) triples, and its kernels take CovWParams.
 //
 // Nothing here instantiates a kernel: the skeletons are templates, and the kernels are instantiated in the statistic's own
 // translation unit only (xhist_capi.hip includes this header for ValuesPlan and must not gain device code).
@@ -62,22 +63,15 @@ struct CovWParams : CovParams {
 //   lds_add(slots, i, v)      one value into slot i: v in the sample type (fast family) or float64 (generic family)
 //   global_add(p, row, b, v)  one float64 value straight into bin b of the output row (generic family without LDS)
 //   flush(slots, p, row)      the workgroup's slots into its output row
+//   kExtra                    the input streams it reads beyond the samples and the values: 0, 1 or 2
 // Outputs are [n_rows, n_bins] arrays at p.out / p.out2, pre-advanced to row p.row0; the values are p.w_*.
-// A weighted policy (kWeighted = true; its kernels take WParams, the weights at p.x_*) takes the sample's weight as well:
+// A policy of one extra stream (kExtra = 1; its kernels take WParams, the stream at p.x_*: the weights, or histogram_cov's
+// second value array) takes that stream's element as well:
 //   lds_add(slots, i, v, w)  global_add(p, row, b, v, w)   (w in the sample type or float64, as v)
-// A policy of two extra streams (kWeighted and kSecond = true; its kernels take CovWParams, the second value array at p.x_*
-// and the weights at p.y_*) takes both:
+// A policy of two extra streams (kExtra = 2; its kernels take CovWParams, the second value array at p.x_* and the weights at
+// p.y_*) takes both:
 //   lds_add(slots, i, a, b, w)  global_add(p, row, bin, a, b, w)
-// The skeletons choose the streams at compile time (if constexpr); the unweighted policies have no kWeighted, and only the
-// policies of xhist_cov_w.hip.h have kSecond.
-template <class Acc, class = void>
-struct AccWeighted : std::false_type {};
-template <class Acc>
-struct AccWeighted<Acc, std::enable_if_t<Acc::kWeighted>> : std::true_type {};
-template <class Acc, class = void>
-struct AccSecond : std::false_type {};
-template <class Acc>
-struct AccSecond<Acc, std::enable_if_t<Acc::kSecond>> : std::true_type {};
+// The skeletons choose the streams at compile time (if constexpr).
 //
 // The bodies take the kernel's Params as `const Params& __restrict__`.  A body is optimised on its own before it is inlined
 // into its kernel, and without __restrict__ that step must assume the LDS and global atomics may write the Params: the
@@ -92,10 +86,9 @@ struct AccSecond<Acc, std::enable_if_t<Acc::kSecond>> : std::true_type {};
 // ---------------------------------------------------------------------------------------------
 template <class Acc, int CMP, bool LDS, class P>
 __device__ __forceinline__ void values_generic_body(const P& __restrict__ p) {
-  constexpr bool W = AccWeighted<Acc>::value;
-  constexpr bool W2 = AccSecond<Acc>::value;
-  static_assert(!W || std::is_base_of<WParams, P>::value, "weighted policies read the weights of WParams");
-  static_assert(!W2 || (W && std::is_base_of<CovWParams, P>::value), "policies of two extra streams read both of CovWParams");
+  constexpr bool W = Acc::kExtra >= 1, W2 = Acc::kExtra == 2;
+  static_assert(!W || std::is_base_of<WParams, P>::value, "a policy of an extra stream reads the x_* block of WParams");
+  static_assert(!W2 || std::is_base_of<CovWParams, P>::value, "a policy of two extra streams reads the y_* block of CovWParams too");
   using CT = typename Dom<CMP>::T;
   const int64_t row = blockIdx.x / p.segs;
   const int seg = blockIdx.x % p.segs;
@@ -170,7 +163,7 @@ __device__ __forceinline__ void values_generic_body(const P& __restrict__ p) {
 // thresholds for float32 ones) or by arithmetic (kScanArith).  Tiles as in hist_fast: VEC elements per 16-byte
 // non-temporal load, UNROLL loads in flight per array and lane; the workgroups of a row walk its tiles interleaved.  A weighted
 // policy's weights have the sample type and unit column stride too, and are loaded the same way; so is the fourth stream of a
-// policy with kSecond.
+// policy of two extra streams.
 // ---------------------------------------------------------------------------------------------
 // the parts a fast form reads its tile in: the fewest (a power of two, at most one load per array and part) that keep `limit`
 // bytes per lane in flight
@@ -182,10 +175,9 @@ constexpr int fast_halves(int tile_bytes, int limit, int unroll) {
 
 template <class Acc, typename ST, int D, int SCAN, class P>
 __device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
-  constexpr bool W = AccWeighted<Acc>::value;
-  constexpr bool W2 = AccSecond<Acc>::value;
-  static_assert(!W || std::is_base_of<WParams, P>::value, "weighted policies read the weights of WParams");
-  static_assert(!W2 || (W && std::is_base_of<CovWParams, P>::value), "policies of two extra streams read both of CovWParams");
+  constexpr bool W = Acc::kExtra >= 1, W2 = Acc::kExtra == 2;
+  static_assert(!W || std::is_base_of<WParams, P>::value, "a policy of an extra stream reads the x_* block of WParams");
+  static_assert(!W2 || std::is_base_of<CovWParams, P>::value, "a policy of two extra streams reads the y_* block of CovWParams too");
   static_assert(__is_same(ST, double) || __is_same(ST, float), "float32 / float64 samples and values");
   static_assert(SCAN == 1 || SCAN == 2 || SCAN == kScanArith, "tables with <= 2 edges per bucket, or arithmetic edges");
   constexpr int CMP = (__is_same(ST, float) && SCAN != kScanArith) ? 2 : 0;
@@ -573,7 +565,6 @@ static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what,
 //   planes            the [n_rows, n_bins] planes behind first, out_mean, out_m2 and sd, in this order (cov: 1, 2, 3, 2)
 //   name, prefix      the statistic in messages and in describe() (mean_var / mean_var_w / cov), and its kernels' prefix
 //   spelled           the statistic where a message spells it out ("weighted mean_var")
-//   lds_what, sum_what, dev_what   the messages handed to allow_values_lds and to the two launch_values_pass calls
 // `first` is out_count or out_wsum; `third` the weights or the second value array, nullptr for a statistic of two streams;
 // `fourth` the weights of a statistic of two value arrays, nullptr for every other.
 template <class M, class First>
@@ -585,6 +576,10 @@ static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const 
     snprintf(buf, sizeof buf, "%s%s launch", a, b);
     return buf;
   };
+  char lds_what[64], sum_what[32], dev_what[32];  // (handed over before anything can fail, so made up front)
+  snprintf(lds_what, sizeof lds_what, "%s: setting the dynamic LDS size failed", M::name);
+  snprintf(sum_what, sizeof sum_what, "%s_sum launch", M::prefix);
+  snprintf(dev_what, sizeof dev_what, "%s_dev launch", M::prefix);
   const auto mean = M::mean;
   const auto finalize = M::finalize;
   const int64_t n_out = n_rows * pl.n_bins;
@@ -607,16 +602,16 @@ static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const 
       return XHIST_ERR_HIP;
     }
     for (int k = 0; k < 2; ++k)
-      if (int rc = allow_values_lds(k ? dev : sum, c.lds_bytes[k], M::lds_what, err, err_cap)) return rc;
+      if (int rc = allow_values_lds(k ? dev : sum, c.lds_bytes[k], lds_what, err, err_cap)) return rc;
     g = values_geometry(pl, c, n_rows, n_cols);
-    if (int rc = launch_values_pass(sum, c.lds_bytes[0], M::sum_what, pl, c, g, samples, values, n_rows, n_cols, first, out_mean,
+    if (int rc = launch_values_pass(sum, c.lds_bytes[0], sum_what, pl, c, g, samples, values, n_rows, n_cols, first, out_mean,
                                     nullptr, stream, err, err_cap, third, fourth))
       return rc;
   }
   XH_VALUES_LAUNCH(mean, dim3(grid_io), dim3(256), 0, stream, first, out_mean, n_out);
   XH_VALUES_LAUNCH_CHECK(what(M::prefix, "_mean"));
   if (n_cols > 0) {
-    if (int rc = launch_values_pass(dev, c.lds_bytes[1], M::dev_what, pl, c, g, samples, values, n_rows, n_cols, sd, out_m2,
+    if (int rc = launch_values_pass(dev, c.lds_bytes[1], dev_what, pl, c, g, samples, values, n_rows, n_cols, sd, out_m2,
                                     out_mean, stream, err, err_cap, third, fourth))
       return rc;
   }
