@@ -228,7 +228,9 @@ int xhist_plan_execute_cov_weighted(xhist_plan* plan, const xhist_array* samples
  *   out: contiguous float64 [n_q, n_rows, prod(nb_d)] DEVICE buffer, overwritten.  Scratch comes from the library's allocator.
  *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
  *   Asynchronous on `stream`, no host synchronisation.  xhist_plan_describe then names the family, the kernel family and home
- *   of the passes, the digit width d, the number of passes and the row chunks. */
+ *   of the passes, the digit width d, the number of passes and the row chunks; the radix line ends with the successor pass of
+ *   the interpolating methods, successor=<family>/<home>/<lds_bytes> (its home may differ from pass 0's: it keeps one window per
+ *   target of a group where pass 0 keeps one per bin). */
 #define XHIST_Q_LINEAR 0
 #define XHIST_Q_LOWER 1
 #define XHIST_Q_HIGHER 2

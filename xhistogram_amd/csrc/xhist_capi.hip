@@ -292,7 +292,7 @@ static int execute_values(xhist_plan* p, const char* name, const xhist_array* sa
   if (int rc = g.set(p->device)) return rc;
   const ValuesPlan pl = values_plan(p);
   Range r(name);
-  char err[256] = {0}, desc[256] = {0};
+  char err[256] = {0}, desc[384] = {0};  // (the radix quantile line with its successor field passes 256)
   const int rc = run(pl, err, sizeof err, desc, sizeof desc);
   if (rc != XHIST_OK) return fail(rc, "%s", err);
   if (desc[0]) {

@@ -227,6 +227,6 @@ int xhist_quantile_run(const ValuesPlan& pl_in, const xhist_array* samples, cons
       XH_VALUES_LAUNCH_CHECK("q_finalize launch");
     }
   }
-  describe_quantile_radix(desc, desc_cap, "quantile", k, r, win0, digit);
+  describe_quantile_radix(desc, desc_cap, "quantile", k, r, win0, digit, &winG);
   return XHIST_OK;
 }

@@ -461,19 +461,23 @@ static inline QRadix quantile_radix(const QCall& k, size_t (*digit_bytes)(int, i
   return r;
 }
 
-// the radix family's describe() line (`name`: quantile / weighted_quantile)
+// the radix family's describe() line (`name`: quantile / weighted_quantile); `succ`: the unweighted family's successor pass
+// (nullptr: the statistic has none), appended as successor=<family>/<home>/<lds_bytes>
 template <class P>
 static void describe_quantile_radix(char* desc, size_t desc_cap, const char* name, const QCall& k, const QRadix& r, const Pass<P>& win0,
-                                    const Pass<P>& digit) {
+                                    const Pass<P>& digit, const Pass<P>* succ = nullptr) {
   if (!desc || !desc_cap) return;
   auto fam = [](const Pass<P>& p) { return p.c.fast ? "fast" : "generic"; };
   auto home = [](const Pass<P>& p) { return p.c.lds ? "lds" : "global"; };
-  snprintf(desc, desc_cap,
-           "%s family=radix window=%s/%s digits=%s/%s scan=%d/%d d=%d group=%d groups=%d passes=%d chunks=%lld rows_per_chunk=%lld "
-           "block=%d segs=%lld lds_bytes=%zu/%zu D=%d cmp=%d",
-           name, fam(win0), home(win0), fam(digit), home(digit), win0.c.scan, digit.c.scan, r.d, r.G, (k.n_q + r.G - 1) / r.G, r.passes,
-           (long long)((k.n_rows + r.chunk - 1) / r.chunk), (long long)r.chunk, digit.g.block, (long long)digit.g.segs,
-           win0.c.lds_bytes[0], digit.c.lds_bytes[0], k.pl.n_dims, values_cmp(k.pl));
+  const int n = snprintf(desc, desc_cap,
+                         "%s family=radix window=%s/%s digits=%s/%s scan=%d/%d d=%d group=%d groups=%d passes=%d chunks=%lld "
+                         "rows_per_chunk=%lld block=%d segs=%lld lds_bytes=%zu/%zu D=%d cmp=%d",
+                         name, fam(win0), home(win0), fam(digit), home(digit), win0.c.scan, digit.c.scan, r.d, r.G,
+                         (k.n_q + r.G - 1) / r.G, r.passes, (long long)((k.n_rows + r.chunk - 1) / r.chunk), (long long)r.chunk,
+                         digit.g.block, (long long)digit.g.segs, win0.c.lds_bytes[0], digit.c.lds_bytes[0], k.pl.n_dims,
+                         values_cmp(k.pl));
+  if (succ && n > 0 && (size_t)n < desc_cap)
+    snprintf(desc + n, desc_cap - n, " successor=%s/%s/%zu", fam(*succ), home(*succ), succ->c.lds_bytes[0]);
 }
 
 // The short-row family's launches: R whole rows per workgroup of 256 lanes (at most `short_cols` values in all, and R x bins
