@@ -4,8 +4,9 @@
     XHIST_AMD_KERNEL_LOG=/path/log  <any workload: pytest -m gpu, tools/check_cliffs.py run, tools/soak.py ...>
     python tools/kernel_census.py xhistogram_amd/libxhist_amd.so /path/log [more logs] [--unused] [--json out.json]
 
-The library appends the name of every distinct kernel it launches through a dispatch table to $XHIST_AMD_KERNEL_LOG
-(csrc/xhist_host_common.hip.h::log_picked_kernel).  This tool lists the instantiations the shared object holds (the host
+The library appends the name of every distinct kernel it launches — picked through a dispatch table, or one of the helper kernels
+it launches directly — to $XHIST_AMD_KERNEL_LOG (csrc/xhist_host_common.hip.h::log_picked_kernel; debug_hold_kernel, test support,
+is the one kernel outside).  This tool lists the instantiations the shared object holds (the host
 stubs `__device_stub__<kernel>` of its symbol table), groups both by kernel template, and prints per template how many
 instantiations exist and how many were ever selected."""
 import collections
@@ -81,7 +82,7 @@ def main():
     for t, (a, b) in per.items():
         print("%-44s %8d %8d" % (t, a, b))
     unknown = sorted(used - have)
-    print("%-44s %8d %8d   (picked kernels; launched directly: the rest)" % ("total", len(have), len(used)))
+    print("%-44s %8d %8d   (every kernel but debug_hold_kernel is logged)" % ("total", len(have), len(used)))
     if unknown:
         print("selected but not found among the host stubs (name normalisation?):", len(unknown))
         for n in unknown[:10]:

@@ -259,6 +259,7 @@ extern "C" int xhist_plan_execute_two_weights(xhist_plan* p, const xhist_array* 
 // arrays (xhist_cov.hip) and its weighted form (xhist_cov_w.hip); the choice and the launches they share: xhist_values.hip.h
 // ------------------------------------------------------------------------------------------
 void xhist_log_picked_kernel(const void* fn) { log_picked_kernel(fn); }
+void xhist_log_local_kernel(const void* fn, const char* name) { log_picked_kernel(fn, name); }
 
 // what the statistics' units need of a plan
 static ValuesPlan values_plan(const xhist_plan* p) {
@@ -525,7 +526,7 @@ extern "C" int xhist_buffer_add(int device, void* dst, const void* src, int64_t 
   DeviceGuard g;
   if (int rc = g.set(device)) return rc;
   const int grid = (int)std::min<int64_t>((count + 255) / 256, 4096);
-  hipLaunchKernelGGL(buffer_add_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<uint64_t*>(dst),
+  XH_LAUNCH_PICKED(buffer_add_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<uint64_t*>(dst),
                      static_cast<const uint64_t*>(src), count, dtype == XHIST_F64 ? 1 : 0);
   HIPC(hipGetLastError());
   return XHIST_OK;
@@ -682,7 +683,7 @@ extern "C" int xhist_buffer_copy_nd(int device, int ndim, const int64_t* shape, 
       for (int k = 0; k < nd.ndim - 1; ++k)
         if (k != kd) n_tiles *= nd.shape[k];
       const int tgrid = (int)std::min<int64_t>(n_tiles, 256 * 16);
-#define XHIST_COPY_T(T) hipLaunchKernelGGL((copy_nd_transpose<T>), dim3(tgrid), dim3(256), 0, s, sp, dp, nd, kd, tiles_k, tiles_l, n_tiles)
+#define XHIST_COPY_T(T) XH_LAUNCH_PICKED((copy_nd_transpose<T>), dim3(tgrid), dim3(256), 0, s, sp, dp, nd, kd, tiles_k, tiles_l, n_tiles)
       if (item == 8) XHIST_COPY_T(uint64_t);
       else if (item == 4) XHIST_COPY_T(uint32_t);
       else if (item == 2) XHIST_COPY_T(uint16_t);
@@ -699,7 +700,7 @@ extern "C" int xhist_buffer_copy_nd(int device, int ndim, const int64_t* shape, 
   const int rows_per_wg = 256 >> wlog2;
   const int64_t tiles = ((rows + rows_per_wg - 1) / rows_per_wg) * col_tiles;
   const int grid = (int)std::min<int64_t>(tiles, 256 * 32);
-#define XHIST_COPY_ND(ITEM) hipLaunchKernelGGL((copy_nd_kernel<ITEM>), dim3(grid), dim3(256), 0, s, sp, dp, nd, wlog2, rows, col_tiles, (int32_t)src_dtype)
+#define XHIST_COPY_ND(ITEM) XH_LAUNCH_PICKED((copy_nd_kernel<ITEM>), dim3(grid), dim3(256), 0, s, sp, dp, nd, wlog2, rows, col_tiles, (int32_t)src_dtype)
   if (convert) XHIST_COPY_ND(0);
   else if (item_eff == 16) XHIST_COPY_ND(16);
   else if (item_eff == 8) XHIST_COPY_ND(8);
@@ -741,7 +742,7 @@ extern "C" int xhist_moments(int device, const xhist_array* a, int64_t n_rows, i
   if (scratch.alloc((void**)&d_part, sizeof(double) * 5 * grid) != hipSuccess) return fail(XHIST_ERR_NOMEM, "device allocation failed");
   std::vector<double> part(5 * grid);
   auto pass = [&](int which, double mean) -> int {
-    hipLaunchKernelGGL(moments_kernel, dim3(grid), dim3(256), 0, s, a->data, a->dtype, a->row_stride, a->col_stride, a->inner_rows, a->outer_stride,
+    XH_LAUNCH_PICKED_LOCAL(moments_kernel, dim3(grid), dim3(256), 0, s, a->data, a->dtype, a->row_stride, a->col_stride, a->inner_rows, a->outer_stride,
                        n_rows, n_cols, use_range, lo, hi, which, mean, d_part);
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(part.data(), d_part, sizeof(double) * 5 * grid, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
@@ -804,7 +805,7 @@ extern "C" int xhist_minmax(int device, const xhist_array* a, int64_t n_rows, in
   if (flat) {  // (`bins=int` on a whole float array is a first call's shape too: these two live in the hot code object)
     launched = (hipError_t)xhist_hot_minmax_flat(view.dtype == XHIST_F64, view.data, n_rows * n_cols, d_part, grid, s);
   } else {
-    hipLaunchKernelGGL(minmax_kernel, dim3(grid), dim3(256), 0, s, view.data, view.dtype, view.row_stride, view.col_stride, view.inner_rows,
+    XH_LAUNCH_PICKED_LOCAL(minmax_kernel, dim3(grid), dim3(256), 0, s, view.data, view.dtype, view.row_stride, view.col_stride, view.inner_rows,
                        view.outer_stride, n_rows, n_cols, d_part);
     launched = hipGetLastError();
   }

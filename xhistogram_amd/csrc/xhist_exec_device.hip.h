@@ -253,7 +253,7 @@ static int execute_partitioned(xhist_plan* p, const PlanKnobs& kn, const PartCal
     if (int rrc = pc.rec->begin(kn.profile)) return rrc;
   XH_LAUNCH_PICKED(k_count, dim3(G), dim3(kPartBlock), lds_count, stream, kp, d_flat);
   HIPC(hipGetLastError());
-  hipLaunchKernelGGL(part_prefix, dim3(1), dim3(1024), 0, stream, (const uint32_t*)d_counts, G, n_parts, grp, d_offsets, d_base);
+  XH_LAUNCH_PICKED_LOCAL(part_prefix, dim3(1), dim3(1024), 0, stream, (const uint32_t*)d_counts, G, n_parts, grp, d_offsets, d_base);
   HIPC(hipGetLastError());
   XH_LAUNCH_PICKED(k_scatter, dim3(G), dim3(kPartBlock), lds_scatter, stream, (const uint32_t*)d_flat,
                      weighted ? weights->data : nullptr, n_cols, (const uint64_t*)d_base, d_codes, d_w, shift, n_parts);
@@ -935,9 +935,9 @@ static int launch_lane_columns(xhist_plan* p, const PlanKnobs& kn, const Inputs&
     HIPC(scratch.alloc(&dense, (size_t)n_rows * n_cols * es));
     const dim3 grid((unsigned)((n_rows + 63) / 64), (unsigned)((n_cols + 63) / 64));
     if (es == 8)
-      hipLaunchKernelGGL(transpose_2d<double>, grid, dim3(256), 0, stream, (const double*)a.data, a.row_stride, n_rows, n_cols, (double*)dense);
+      XH_LAUNCH_PICKED(transpose_2d<double>, grid, dim3(256), 0, stream, (const double*)a.data, a.row_stride, n_rows, n_cols, (double*)dense);
     else
-      hipLaunchKernelGGL(transpose_2d<float>, grid, dim3(256), 0, stream, (const float*)a.data, a.row_stride, n_rows, n_cols, (float*)dense);
+      XH_LAUNCH_PICKED(transpose_2d<float>, grid, dim3(256), 0, stream, (const float*)a.data, a.row_stride, n_rows, n_cols, (float*)dense);
     HIPC(hipGetLastError());
     views[d].data = dense;
     views[d].row_stride = 1;
@@ -1012,14 +1012,14 @@ static int execute_table_columns(xhist_plan* p, const PlanKnobs& kn, const Input
     const size_t tile_lds = (size_t)256 * (n_rows + 1) * es;
     if (a.col_stride == n_rows && ((int64_t)n_rows * es) % 16 == 0 && ((uintptr_t)a.data % 16) == 0 && es >= 4 && tile_lds <= 64 * 1024) {
       const int tgrid = (int)std::min<int64_t>((n_cols + 255) / 256, (int64_t)p->cus * (int64_t)std::max<size_t>(1, (160 * 1024) / tile_lds));
-      if (es == 8) hipLaunchKernelGGL(gather_rows_tiled<uint64_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint64_t*)a.data, (int)n_rows, n_cols, (uint64_t*)buf);
-      else hipLaunchKernelGGL(gather_rows_tiled<uint32_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint32_t*)a.data, (int)n_rows, n_cols, (uint32_t*)buf);
+      if (es == 8) XH_LAUNCH_PICKED(gather_rows_tiled<uint64_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint64_t*)a.data, (int)n_rows, n_cols, (uint64_t*)buf);
+      else XH_LAUNCH_PICKED(gather_rows_tiled<uint32_t>, dim3(tgrid), dim3(256), tile_lds, stream, (const uint32_t*)a.data, (int)n_rows, n_cols, (uint32_t*)buf);
     } else
     switch (es) {
-      case 8: hipLaunchKernelGGL(gather_rows<uint64_t>, dim3(grid), dim3(256), 0, stream, (const uint64_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint64_t*)buf); break;
-      case 4: hipLaunchKernelGGL(gather_rows<uint32_t>, dim3(grid), dim3(256), 0, stream, (const uint32_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint32_t*)buf); break;
-      case 2: hipLaunchKernelGGL(gather_rows<uint16_t>, dim3(grid), dim3(256), 0, stream, (const uint16_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint16_t*)buf); break;
-      default: hipLaunchKernelGGL(gather_rows<uint8_t>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint8_t*)buf); break;
+      case 8: XH_LAUNCH_PICKED(gather_rows<uint64_t>, dim3(grid), dim3(256), 0, stream, (const uint64_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint64_t*)buf); break;
+      case 4: XH_LAUNCH_PICKED(gather_rows<uint32_t>, dim3(grid), dim3(256), 0, stream, (const uint32_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint32_t*)buf); break;
+      case 2: XH_LAUNCH_PICKED(gather_rows<uint16_t>, dim3(grid), dim3(256), 0, stream, (const uint16_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint16_t*)buf); break;
+      default: XH_LAUNCH_PICKED(gather_rows<uint8_t>, dim3(grid), dim3(256), 0, stream, (const uint8_t*)a.data, a.col_stride, (int)n_rows, n_cols, (uint8_t*)buf); break;
     }
     if (hipGetLastError() != hipSuccess) return fail(XHIST_ERR_HIP, "gather_rows launch failed");
     dense[d] = a;

@@ -25,8 +25,10 @@ static int fail(int code, const char* fmt, ...) {
 
 // Census of the dispatch surface (development): with XHIST_AMD_KERNEL_LOG=<file> the name of every distinct kernel
 // instantiation this process launches through a dispatch table is appended to <file> once (tools/kernel_census.py compares
-// the union over the tests, the cliff scanners and the soak with what the library holds; VERDICT r4 "next" #7).
-static void log_picked_kernel(const void* fn) {
+// the union over the tests, the cliff scanners and the soak with what the library holds; VERDICT r4 "next" #7).  The helper
+// kernels the library launches directly (zeroing, table builders, gathers, copies, reductions) are logged the same way.
+// local_name: the demangled name of a kernel with internal linkage, which the dynamic symbol table does not hold.
+static void log_picked_kernel(const void* fn, const char* local_name = nullptr) {
   static const char* const path = getenv("XHIST_AMD_KERNEL_LOG");
   if (!path || !*path) return;
   static const bool every_pick = [] { const char* e = getenv("XHIST_AMD_KERNEL_LOG_ALL"); return e && *e == '1'; }();  // (tests/test_gpu_census.py's discovery mode: which CASE picks what)
@@ -37,7 +39,7 @@ static void log_picked_kernel(const void* fn) {
   // the host stub's own symbol (`__device_stub__<kernel>`), from the dynamic symbol table: no call into the HIP runtime
   // (hipKernelNameRefByPtr hung a process that had loaded this library before torch's bundled runtime)
   Dl_info info;
-  const char* name = dladdr(fn, &info) && info.dli_sname ? info.dli_sname : "?";
+  const char* name = local_name ? local_name : dladdr(fn, &info) && info.dli_sname ? info.dli_sname : "?";
   if (FILE* f = fopen(path, "a")) {
     fprintf(f, "%s\n", name);
     fclose(f);
@@ -47,6 +49,11 @@ static void log_picked_kernel(const void* fn) {
   do {                                                           \
     log_picked_kernel(reinterpret_cast<const void*>(fn));        \
     hipLaunchKernelGGL(fn, __VA_ARGS__);                         \
+  } while (0)
+#define XH_LAUNCH_PICKED_LOCAL(fn, ...)                                      \
+  do {                                                                       \
+    log_picked_kernel(reinterpret_cast<const void*>(fn), "xhist::" #fn);     \
+    hipLaunchKernelGGL(fn, __VA_ARGS__);                                     \
   } while (0)
 
 // Logical -> physical devices (tests only): XHIST_AMD_DEVICE_ALIAS="0,0" makes the library show TWO devices that are both

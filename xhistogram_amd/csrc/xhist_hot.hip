@@ -54,26 +54,26 @@ kernel_fn xhist_pick_hot_long(int sdt, int scan) {
 }
 
 int xhist_hot_zero_words(unsigned long long* p, int64_t n, int grid, hipStream_t stream) {
-  hipLaunchKernelGGL(zero_words, dim3((unsigned)grid), dim3(256), 0, stream, p, n);
+  XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3((unsigned)grid), dim3(256), 0, stream, p, n);
   return (int)hipGetLastError();
 }
 
 int xhist_hot_build_tables(int dom, bool lut16, const DimTable& t, uint64_t* blob, int32_t* scratch) {
-  if (dom == 0 && !lut16) hipLaunchKernelGGL((build_tables<0, false>), dim3(1), dim3(256), 0, 0, t, blob, scratch);
-  else if (dom == 0) hipLaunchKernelGGL((build_tables<0, true>), dim3(1), dim3(256), 0, 0, t, blob, scratch);
-  else if (dom == 1) hipLaunchKernelGGL((build_tables<1, false>), dim3(1), dim3(256), 0, 0, t, blob, scratch);
-  else if (!lut16) hipLaunchKernelGGL((build_tables<2, false>), dim3(1), dim3(256), 0, 0, t, blob, scratch);
-  else hipLaunchKernelGGL((build_tables<2, true>), dim3(1), dim3(256), 0, 0, t, blob, scratch);
+  if (dom == 0 && !lut16) XH_LAUNCH_LOGGED((build_tables<0, false>), dim3(1), dim3(256), 0, 0, t, blob, scratch);
+  else if (dom == 0) XH_LAUNCH_LOGGED((build_tables<0, true>), dim3(1), dim3(256), 0, 0, t, blob, scratch);
+  else if (dom == 1) XH_LAUNCH_LOGGED((build_tables<1, false>), dim3(1), dim3(256), 0, 0, t, blob, scratch);
+  else if (!lut16) XH_LAUNCH_LOGGED((build_tables<2, false>), dim3(1), dim3(256), 0, 0, t, blob, scratch);
+  else XH_LAUNCH_LOGGED((build_tables<2, true>), dim3(1), dim3(256), 0, 0, t, blob, scratch);
   return (int)hipGetLastError();
 }
 
 int xhist_hot_build_pack_tables(const DimTable& t, uint64_t* blob, int32_t* scratch, const float* thr) {
-  hipLaunchKernelGGL(build_pack_tables, dim3(1), dim3(256), 0, 0, t, blob, scratch, thr);
+  XH_LAUNCH_LOGGED_LOCAL(build_pack_tables, dim3(1), dim3(256), 0, 0, t, blob, scratch, thr);
   return (int)hipGetLastError();
 }
 
 int xhist_hot_minmax_flat(bool f64, const void* x, int64_t n, double* partial, int grid, hipStream_t stream) {
-  if (f64) hipLaunchKernelGGL(minmax_flat<double>, dim3((unsigned)grid), dim3(256), 0, stream, static_cast<const double*>(x), n, partial);
-  else hipLaunchKernelGGL(minmax_flat<float>, dim3((unsigned)grid), dim3(256), 0, stream, static_cast<const float*>(x), n, partial);
+  if (f64) XH_LAUNCH_LOGGED(minmax_flat<double>, dim3((unsigned)grid), dim3(256), 0, stream, static_cast<const double*>(x), n, partial);
+  else XH_LAUNCH_LOGGED(minmax_flat<float>, dim3((unsigned)grid), dim3(256), 0, stream, static_cast<const float*>(x), n, partial);
   return (int)hipGetLastError();
 }

@@ -26,6 +26,22 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// The census log of launched kernels (xhist_host_common.hip.h: log_picked_kernel; both functions are defined in xhist_capi.hip), for
+// the launches of the other translation units.  A kernel with internal linkage (`static __global__` in a header that every unit
+// includes) has no dynamic symbol the logger could look up from the stub's address: its launch site names it.
+void xhist_log_picked_kernel(const void* fn);
+void xhist_log_local_kernel(const void* fn, const char* name);
+#define XH_LAUNCH_LOGGED(fn, ...)                               \
+  do {                                                          \
+    xhist_log_picked_kernel(reinterpret_cast<const void*>(fn)); \
+    hipLaunchKernelGGL(fn, __VA_ARGS__);                        \
+  } while (0)
+#define XH_LAUNCH_LOGGED_LOCAL(fn, ...)                                         \
+  do {                                                                          \
+    xhist_log_local_kernel(reinterpret_cast<const void*>(fn), "xhist::" #fn);   \
+    hipLaunchKernelGGL(fn, __VA_ARGS__);                                        \
+  } while (0)
+
 namespace xhist {
 
 constexpr int kMaxDims = 8;

@@ -185,7 +185,7 @@ int xhist_quantile_run(const ValuesPlan& pl_in, const xhist_array* samples, cons
     return XHIST_ERR_NOMEM;
   }
   const int64_t n_flag_words = (3 + passes + 1) / 2;  // flags: [0] pass 0, [1 + j] digit pass j, [2 + passes] the successor
-  hipLaunchKernelGGL(zero_words, dim3(2048), dim3(256), 0, stream, cnt, (int64_t)(n_rb * G << d));
+  XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3(2048), dim3(256), 0, stream, cnt, (int64_t)(n_rb * G << d));
   XH_VALUES_LAUNCH_CHECK("quantile zeroing launch");
   st.tgt = tg;
   st.win0 = w0;
@@ -205,7 +205,7 @@ int xhist_quantile_run(const ValuesPlan& pl_in, const xhist_array* samples, cons
     for (int g0 = 0; g0 < n_q; g0 += G) {
       quantile_group(st, k, g0, G);
       // the flags of the digit passes and of the successor start at zero for every group (pass 0 has run: its flag may go too)
-      hipLaunchKernelGGL(zero_words, dim3(1), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(flags), n_flag_words);
+      XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3(1), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(flags), n_flag_words);
       XH_VALUES_LAUNCH_CHECK("quantile zeroing launch");
       XH_VALUES_LAUNCH(q_init, dim3(grid), dim3(256), 0, stream, st);
       XH_VALUES_LAUNCH_CHECK("q_init launch");

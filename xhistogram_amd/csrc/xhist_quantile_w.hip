@@ -162,7 +162,7 @@ int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, co
     return XHIST_ERR_NOMEM;
   }
   const int64_t n_flag_words = (2 + passes + 1) / 2;  // flags: [1 + j] digit pass j (and the word qw_select writes last)
-  hipLaunchKernelGGL(zero_words, dim3(2048), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(sum), (int64_t)(n_rb * G << d));
+  XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3(2048), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(sum), (int64_t)(n_rb * G << d));
   XH_VALUES_LAUNCH_CHECK("weighted quantile zeroing launch");
   st.tgt = tg;
   st.win0 = w0;
@@ -182,7 +182,7 @@ int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, co
     for (int g0 = 0; g0 < n_q; g0 += G) {
       quantile_group(st, k, g0, G);
       // the flags of the digit passes start at zero for every group
-      hipLaunchKernelGGL(zero_words, dim3(1), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(flags), n_flag_words);
+      XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3(1), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(flags), n_flag_words);
       XH_VALUES_LAUNCH_CHECK("weighted quantile zeroing launch");
       XH_VALUES_LAUNCH(qw_init, dim3(grid), dim3(256), 0, stream, st);
       XH_VALUES_LAUNCH_CHECK("qw_init launch");

@@ -307,8 +307,6 @@ struct ValuesPlan {
   bool arith;
   ValuesTables native, fine64, fine32;
 };
-// the census log of launched kernels (xhist_host_common.hip.h: log_picked_kernel), for the launches of the statistics' units
-void xhist_log_picked_kernel(const void* fn);
 
 namespace xhist {
 
@@ -586,7 +584,7 @@ static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const 
   const int grid_io = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_out + 255) / 256));
   void* const zero[4] = {first, out_mean, out_m2, sd};
   for (int k = 0; k < 4; ++k) {
-    hipLaunchKernelGGL(zero_words, dim3(grid_io), dim3(256), 0, stream, static_cast<unsigned long long*>(zero[k]), M::planes[k] * n_out);
+    XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3(grid_io), dim3(256), 0, stream, static_cast<unsigned long long*>(zero[k]), M::planes[k] * n_out);
     XH_VALUES_LAUNCH_CHECK(what(M::name, " zeroing"));
   }
 
