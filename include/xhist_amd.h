@@ -177,6 +177,39 @@ int xhist_plan_execute_mean_var_weighted(xhist_plan* plan, const xhist_array* sa
                                          const xhist_array* weights, int64_t n_rows, int64_t n_cols, double* out_wsum,
                                          double* out_mean, double* out_m2, int mem_kind, void* stream);
 
+/* Per-bin count, mean and second, third and fourth central moments of `values` (added within ABI v11): the samples that count,
+ * pass 1 (n, S = sum(v)) and mean = S/n are exactly those of xhist_plan_execute_mean_var.  Pass 2 forms d = v - mean in float64,
+ * the terms t1 = d, t2 = t1*d, t3 = t2*d, t4 = t3*d in this order of products, and D = sum(t1), Q2 = sum(t2), Q3 = sum(t3),
+ * Q4 = sum(t4).  With delta = D/n, every product and sum rounded on its own:
+ *   M2 = max(0, Q2 - (D*D)/n)            (xhist_plan_execute_mean_var's expression: on equal sums, its bits)
+ *   d2 = delta*delta, d3 = d2*delta, d4 = d2*d2
+ *   M3 = (Q3 - (3*delta)*Q2) + (2*n)*d3  (not clamped)
+ *   M4 = max(0, ((Q4 - (4*delta)*Q3) + (6*d2)*Q2) - (3*n)*d4)
+ * The mean and the three moments are NaN where n == 0, and a NaN stays NaN.  Variance, skewness and kurtosis (M3/n / (M2/n)^1.5,
+ * M4/n / (M2/n)^2) are left to the caller.  Float64 atomics add in arbitrary order: the last bits can differ between runs,
+ * except for data whose sums are exact in every order.
+ *   values: an xhist_array of any real dtype, same logical [n_rows, n_cols] shape as the samples (strides 0 broadcast).
+ *   out_count (int64), out_mean (float64): contiguous [n_rows, prod(nb_d)]; out_moments (float64): contiguous [3, n_rows,
+ *   prod(nb_d)], M2, M3, M4.  DEVICE buffers, overwritten (no accumulate mode); one float64 scratch block of [n_rows, prod(nb_d)]
+ *   is taken for the call.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Asynchronous on `stream`.  xhist_plan_describe then names the kernel family of each pass and where its slots live
+ *   ("skew_kurt pass1=mv_sum_... pass2=sk_dev_..."). */
+int xhist_plan_execute_skew_kurt(xhist_plan* plan, const xhist_array* samples, const xhist_array* values,
+                                 int64_t n_rows, int64_t n_cols, int64_t* out_count, double* out_mean, double* out_moments,
+                                 int mem_kind, void* stream);
+
+/* The same with frequency weights (added within ABI v11): the samples that count, pass 1 (W = sum(w), S = sum(w*v)) and mean =
+ * S/W are exactly those of xhist_plan_execute_mean_var_weighted.  Pass 2 forms t1 = w*d and then t2, t3, t4 as above; the
+ * formulas above hold with W in the place of n.  The mean and the moments are NaN where W == 0; a NaN weight makes its bin NaN.
+ * Negative weights are not checked.
+ *   values, weights: xhist_arrays of any real dtype, same logical [n_rows, n_cols] shape as the samples (strides 0 broadcast).
+ *   out_wsum, out_mean (float64): contiguous [n_rows, prod(nb_d)]; out_moments (float64): contiguous [3, n_rows, prod(nb_d)].
+ *   Otherwise as above ("skew_kurt_w pass1=mvw_sum_... pass2=skw_dev_..."). */
+int xhist_plan_execute_skew_kurt_weighted(xhist_plan* plan, const xhist_array* samples, const xhist_array* values,
+                                          const xhist_array* weights, int64_t n_rows, int64_t n_cols, double* out_wsum,
+                                          double* out_mean, double* out_moments, int mem_kind, void* stream);
+
 /* Per-bin covariance of two value arrays (added within ABI v11): which samples count is exactly what
  * xhist_plan_execute_mean_var counts, and a counted sample contributes its pair (a, b), both converted to float64, only if
  * neither is NaN (pairwise-complete).  Two passes over the three streams, the corrected two-pass form of

@@ -2,7 +2,7 @@
 
 Each translation unit the base's build.sh lists is compiled, in the base (a `git archive` of --base) and in the working tree,
 with build.sh's flags.  The gfx950 code object of each object file is taken out of its .hip_fatbin bundle and disassembled
-with llvm-objdump -d; every symbol's instructions are compared with the addresses and encodings stripped.  Kernels only the
+with llvm-objdump -d; every symbol's instructions are compared with the addresses and encodings stripped (and the zero filler behind a symbol's last instruction dropped).  Kernels only the
 working tree has (new units, new instantiations) are counted, not compared.
 
     python tools/values_code_diff.py [--base HEAD] [--units xhist_extrema,xhist_meanvar,...] [--jobs 8]
@@ -49,7 +49,14 @@ def disassemble(tree, unit, work):
             continue
         ins = re.sub(r"\s*//.*$", "", line).strip()  # (the address and the encoding are in the trailing comment)
         if ins:
-            cur.append(re.sub(r"\s+", " ", ins))
+            enc = re.search(r"//\s*[0-9A-Fa-f]+:\s*([0-9A-Fa-f ]+)$", line)
+            cur.append((re.sub(r"\s+", " ", ins), ins == "..." or (bool(enc) and not enc.group(1).replace(" ", "").strip("0"))))  # ("...": objdump's run of zero words)
+    # Words of zeros behind a symbol's last instruction are the filler up to the next symbol's alignment (they disassemble as
+    # v_cndmask_b32 v0, s0, v0, vcc): how many there are depends on what follows the symbol, not on its code.
+    for name, body in syms.items():
+        while body and body[-1][1]:
+            body.pop()
+        syms[name] = [ins for ins, _ in body]
     return syms
 
 

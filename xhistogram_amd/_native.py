@@ -71,6 +71,7 @@ EXPORTS = (
     "xhist_plan_create", "xhist_plan_destroy", "xhist_plan_execute", "xhist_plan_execute_two_weights", "xhist_plan_execute_extrema",
     "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
     "xhist_plan_execute_quantile_weighted", "xhist_plan_execute_cov", "xhist_plan_execute_cov_weighted",
+    "xhist_plan_execute_skew_kurt", "xhist_plan_execute_skew_kurt_weighted",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -153,6 +154,8 @@ def load():
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p,
             C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
         ]
+        lib.xhist_plan_execute_skew_kurt.argtypes = lib.xhist_plan_execute_mean_var.argtypes
+        lib.xhist_plan_execute_skew_kurt_weighted.argtypes = lib.xhist_plan_execute_mean_var_weighted.argtypes
         lib.xhist_plan_execute_quantile.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int,
             C.c_void_p, C.c_int, C.c_void_p,
@@ -415,6 +418,21 @@ class Plan:
         `stream` (xhist_plan_execute_mean_var_weighted)"""
         self._execute_values("xhist_plan_execute_mean_var_weighted", sample_views, (value_view, weight_view), n_rows, n_cols,
                              (out_wsum_ptr, out_mean_ptr, out_m2_ptr), stream=stream)
+
+    def execute_skew_kurt(self, sample_views, value_view, n_rows, n_cols, out_count_ptr, out_mean_ptr, out_moments_ptr, stream=0):
+        """per-bin count (int64 [n_rows, bins]), mean (float64 [n_rows, bins]) and second, third and fourth central moments
+        (float64 [3, n_rows, bins]: M2, M3, M4; NaN where no value arrived) of the values of device-resident views, into device
+        buffers, asynchronous on `stream` (xhist_plan_execute_skew_kurt)"""
+        self._execute_values("xhist_plan_execute_skew_kurt", sample_views, (value_view,), n_rows, n_cols,
+                             (out_count_ptr, out_mean_ptr, out_moments_ptr), stream=stream)
+
+    def execute_skew_kurt_weighted(self, sample_views, value_view, weight_view, n_rows, n_cols, out_wsum_ptr, out_mean_ptr,
+                                   out_moments_ptr, stream=0):
+        """per-bin sum of weights W, weighted mean (float64 [n_rows, bins] each) and weighted second, third and fourth central
+        moments (float64 [3, n_rows, bins]: M2, M3, M4; NaN where W == 0) of the values of device-resident views, into device
+        buffers, asynchronous on `stream` (xhist_plan_execute_skew_kurt_weighted)"""
+        self._execute_values("xhist_plan_execute_skew_kurt_weighted", sample_views, (value_view, weight_view), n_rows, n_cols,
+                             (out_wsum_ptr, out_mean_ptr, out_moments_ptr), stream=stream)
 
     def _quantile_args(self, sample_views, q):
         """the C array of the samples' views, and q as a contiguous 1-D float64 array"""

@@ -34,7 +34,8 @@ from .devicearray import DeviceArray, _nocopy_reshape_strides
 _range = range
 
 __all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
-           "histogram_weighted_quantile", "histogram_cov", "histogram_weighted_cov", "combine_weighted_cov"]
+           "histogram_weighted_quantile", "histogram_cov", "histogram_weighted_cov", "combine_weighted_cov",
+           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1875,7 +1876,7 @@ def _value_stat_rows(stat, args, values, axis, bins, backend, *extras):
 
 def _value_stat_block(*all_arrays, stat=None, axis=None, bins=None):
     """one dask block: its statistic as a [k, block axes (reduced ones of extent 1), bins...] float64 numpy array"""
-    st = _VALUE_STATS[stat]
+    st = _stat_of(stat)
     n = len(all_arrays) - 1 - int(st.weighted)  # (samples..., values[, weights or second values[, weights]])
     arrays = _upload_host(all_arrays[:n], all_arrays[n], bins, *all_arrays[n + 1:])
     outs = _value_stat_rows(st, arrays[:n], arrays[n], axis, bins, "device", *arrays[n + 1:])
@@ -1904,7 +1905,7 @@ def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, wei
     function with): the weights, or the second of a pair of values, whose weights are then `fourth`."""
     backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, weights, fourth)
     n_inputs = len(args)
-    st = _VALUE_STATS[stat]
+    st = _stat_of(stat)
     if backend == "dask":
         import dask.array as dsa
 
@@ -2276,6 +2277,159 @@ def histogram_weighted_cov(*args, values, weights, bins=None, range=None, axis=N
     return w, ma, mb, _var_of(w, qa, ddof), _var_of(w, qb, ddof), _var_of(w, cc, ddof), bins
 
 
+# ---------------------------------------------------------------------------------------------
+# per-bin skewness and kurtosis of a value array
+# ---------------------------------------------------------------------------------------------
+def _check_flag(name, v):
+    if not isinstance(v, (bool, np.bool_)):
+        raise TypeError("%s must be a bool, got %r" % (name, v))
+    return bool(v)
+
+
+def _pebay_merge(x, mean, m2, m3, m4, axis, present):
+    """Pébay's pairwise merge of partial (x, mean, M2, M3, M4) results over `axis` (kept as axes of extent 1), one partial
+    after another in index order, exactly as _chan_merge walks them: x, mean and M2 by _chan_merge's very expressions (so they
+    have its bits), M3 and M4 by the update of :func:`combine_skew_kurt`.  Returns float64 (x, mean, M2, M3, M4)."""
+    x, mean, m2, m3, m4 = (np.asarray(a, np.float64) for a in (x, mean, m2, m3, m4))
+    ax = tuple(sorted(int(a) % x.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
+    kept = [i for i in _range(x.ndim) if i not in ax]
+    keep_shape = tuple(1 if i in ax else x.shape[i] for i in _range(x.ndim))
+
+    def lead(a):
+        a = np.transpose(a, ax + tuple(kept))
+        return a.reshape((-1,) + a.shape[len(ax):])
+
+    x, mean, m2, m3, m4 = (lead(a) for a in (x, mean, m2, m3, m4))
+    cx = np.zeros(x.shape[1:])
+    cm, c2, c3, c4 = (np.full(x.shape[1:], np.nan) for _ in _range(4))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for k in _range(x.shape[0]):
+            xb = x[k]
+            take = present(xb)
+            first = take & ~present(cx)
+            both = take & present(cx)
+            tot = cx + xb
+            d = mean[k] - cm
+            n2 = c2 + m2[k] + d * d * cx * xb / tot
+            n3 = (c3 + m3[k] + d * d * d * cx * xb * (cx - xb) / (tot * tot)
+                  + 3.0 * d * (cx * m2[k] - xb * c2) / tot)
+            n4 = (c4 + m4[k] + d * d * d * d * cx * xb * (cx * cx - cx * xb + xb * xb) / (tot * tot * tot)
+                  + 6.0 * d * d * (cx * cx * m2[k] + xb * xb * c2) / (tot * tot)
+                  + 4.0 * d * (cx * m3[k] - xb * c3) / tot)
+            cm = np.where(first, mean[k], np.where(both, cm + d * xb / tot, cm))
+            c2 = np.where(first, m2[k], np.where(both, n2, c2))
+            c3 = np.where(first, m3[k], np.where(both, n3, c3))
+            c4 = np.where(first, m4[k], np.where(both, n4, c4))
+            cx = np.where(take, tot, cx)
+    return tuple(a.reshape(keep_shape) for a in (cx, cm, c2, c3, c4))
+
+
+def combine_skew_kurt(n, mean, m2, m3, m4, axis):
+    """Merge partial (count, mean, M2, M3, M4) results over `axis` (kept as axes of extent 1) with Pébay's pairwise update, one
+    partial after another in index order (C order over several axes), as :func:`combine_mean_var` walks them.  With
+    ``d = mb - ma`` and ``n = na + nb``: ``mean`` and ``M2`` by :func:`combine_mean_var`'s expressions (bit for bit its
+    results), and
+        M3 = M3a + M3b + d^3 na nb (na - nb) / n^2 + 3 d (na M2b - nb M2a) / n,
+        M4 = M4a + M4b + d^4 na nb (na^2 - na nb + nb^2) / n^3 + 6 d^2 (na^2 M2b + nb^2 M2a) / n^2 + 4 d (na M3b - nb M3a) / n.
+    Partials with n == 0 are skipped; where every partial is empty, the mean and the moments are NaN and n is 0.  The reduction
+    of dask's partials.  Returns float64 (n, mean, M2, M3, M4)."""
+    return _pebay_merge(n, mean, m2, m3, m4, axis, _counted)
+
+
+def combine_weighted_skew_kurt(w, mean, m2, m3, m4, axis):
+    """:func:`combine_skew_kurt` for weighted partials (W, mean, M2, M3, M4), W in the place of n: partials with W == 0 are
+    skipped; a NaN partial (a NaN W among them) makes the bin NaN, as in :func:`combine_weighted_mean_var`, whose W, mean and M2
+    these are bit for bit.  Returns float64 (W, mean, M2, M3, M4)."""
+    return _pebay_merge(w, mean, m2, m3, m4, axis, _weighed)
+
+
+def _skew_kurt_of(x, m2, m3, m4, bias, fisher):
+    """(skew, kurt) of numpy arrays or torch tensors from the central moments' sums, x the count or the sum of weights:
+    g1 = (M3 / x) / (m2 sqrt(m2)), g2 = (M4 / x) / (m2 m2) with m2 = M2 / x, NaN where x == 0 or M2 == 0; bias=False applies
+    scipy's sample corrections with x for n, NaN where x <= 2 (skew) and x <= 3 (kurt)"""
+    if _is_torch(m2):
+        xp = _torch()
+        xf = x.to(xp.float64)
+    else:
+        xp = np
+        xf = np.asarray(x, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        nan = xp.full_like(m2, float("nan"))
+        v = m2 / xf
+        ok = (xf != 0) & (m2 != 0)
+        skew = xp.where(ok, (m3 / xf) / (v * xp.sqrt(v)), nan)
+        kurt = xp.where(ok, (m4 / xf) / (v * v), nan)
+        if not bias:
+            skew = xp.where(xf <= 2, nan, xp.sqrt(xf * (xf - 1.0)) / (xf - 2.0) * skew)
+            kurt = xp.where(xf <= 3, nan, (xf - 1.0) / ((xf - 2.0) * (xf - 3.0)) * ((xf + 1.0) * kurt - 3.0 * (xf - 1.0)) + 3.0)
+        if fisher:
+            kurt = kurt - 3.0
+    return skew, kurt
+
+
+def _pebay_reduce(x, axis=None, keepdims=True, final=None, present=_counted, **_):
+    """dask.array.reduction step over stacked blocks of (x, mean, M2, M3, M4) partials.  With final = (ddof, bias, fisher), the
+    last step: the moments turned into (var, skew, kurt), here only."""
+    ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
+    out = np.stack(_pebay_merge(x[0], x[1], x[2], x[3], x[4], tuple(a - 1 for a in ax), present))
+    out = out if keepdims else out.squeeze(ax)
+    if final is not None:
+        ddof, bias, fisher = final
+        skew, kurt = _skew_kurt_of(out[0], out[2], out[3], out[4], bias, fisher)
+        out[2] = _var_of(out[0], out[2], ddof)
+        out[3], out[4] = skew, kurt
+    return out
+
+
+_skew_kurt_reduce = partial(_pebay_reduce, present=_counted)
+_skew_kurt_w_reduce = partial(_pebay_reduce, present=_weighed)
+
+
+def histogram_skew_kurt(*args, values, bins=None, range=None, axis=None, weights=None, ddof=0, bias=True, fisher=True,
+                        block_size="auto"):
+    """Per-bin count, mean, variance, skewness and kurtosis of ``values``, computed on an MI355X: the shape of the distribution
+    inside each class :func:`histogram` counts, as ``scipy.stats.skew`` / ``scipy.stats.kurtosis`` give it for the values of a
+    bin (``nan_policy="omit"``).
+
+    The samples, the edges and the broadcasting, the NaN-value rule (a counted sample contributes when its value is not NaN),
+    the dtype rules (``values`` and ``weights`` of any real dtype, taken as float64), the backends (numpy in -> numpy out,
+    torch in -> torch out on the same device and asynchronous on the current stream, DeviceArray in -> numpy out, dask in ->
+    lazy dask arrays) and ``block_size`` (accepted, changes nothing) are those of :func:`histogram_mean_var`.
+
+    Write ``x`` for the count ``n``, or for ``W = sum(w)`` with ``weights`` (frequency weights, as in the weighted
+    ``histogram_mean_var``).  Two passes over the data: pass 1 is ``histogram_mean_var``'s (``x`` and ``mean``); pass 2 forms
+    ``d = v - mean`` in float64 and the terms ``t1 = d`` (weighted ``w * d``), ``t2 = t1 * d``, ``t3 = t2 * d``, ``t4 = t3 * d``
+    in this order of products, and adds ``D = sum(t1)``, ``Q2 = sum(t2)``, ``Q3 = sum(t3)``, ``Q4 = sum(t4)``.  With
+    ``delta = D / x`` the corrected two-pass formula carried to the fourth order gives
+        M2 = max(0, Q2 - D * D / x)                       (``histogram_mean_var``'s M2, bit for bit on equal sums)
+        M3 = Q3 - 3 delta Q2 + 2 x delta^3                (not clamped)
+        M4 = max(0, Q4 - 4 delta Q3 + 6 delta^2 Q2 - 3 x delta^4).
+    The sums keep the digits that the raw moments ``sum(v^k) / n`` cancel away when ``|mean| >> std``.
+
+    ``var = M2 / (x - ddof)``, NaN where ``x <= ddof``.  With ``m2 = M2 / x``: ``g1 = (M3 / x) / (m2 sqrt(m2))`` and
+    ``g2 = (M4 / x) / (m2 m2)``, both NaN where ``x == 0`` or ``M2 == 0`` (a constant bin is ``0 / 0``).  ``skew = g1`` and
+    ``kurt = g2 - 3`` (``fisher=False``: ``kurt = g2``).  ``bias=False`` applies scipy's sample corrections with ``x`` in the
+    place of ``n``: ``G1 = sqrt(x (x - 1)) / (x - 2) g1`` and ``G2 = (x - 1) / ((x - 2) (x - 3)) ((x + 1) g2 - 3 (x - 1)) + 3``
+    (minus 3 under ``fisher``).  scipy keeps the biased value where the count is too small for the correction; here ``G1`` is
+    NaN where ``x <= 2`` and ``G2`` where ``x <= 3``, as ``ddof`` gives NaN everywhere in this library.  A NaN weight makes its
+    bin NaN; zero weights contribute nothing; negative weights are not checked.  Float64 atomics add in arbitrary order, so the
+    last bits can differ from run to run; data whose sums are exact in any order give the same bits every time.
+
+    Returns ``(count, mean, var, skew, kurt, bin_edges)``: count int64, the others float64, with the shape ``histogram`` gives;
+    with ``weights`` the first output is the float64 ``sum_of_weights``.  dask merges the blocks' partials with
+    :func:`combine_skew_kurt` (:func:`combine_weighted_skew_kurt`)."""
+    ddof = _check_ddof(ddof)
+    bias = _check_flag("bias", bias)
+    fisher = _check_flag("fisher", fisher)
+    stat, reduce_ = ("skew_kurt", _skew_kurt_reduce) if weights is None else ("skew_kurt_w", _skew_kurt_w_reduce)
+    backend, (x, mean, m2, m3, m4), bins, _ = _value_stat(stat, args, values, bins, range, axis, "histogram_skew_kurt",
+                                                         partial(reduce_, final=(ddof, bias, fisher)), weights=weights)
+    if backend == "dask":  # (the aggregate step has turned the moments into var, skew and kurt)
+        return (x.astype(np.int64) if weights is None else x), mean, m2, m3, m4, bins
+    skew, kurt = _skew_kurt_of(x, m2, m3, m4, bias, fisher)
+    return x, mean, _var_of(x, m2, ddof), skew, kurt, bins
+
+
 _VALUE_STATS = {
     "extrema": _ValueStat(2, False, "execute_extrema", _extrema_pair_reduce),
     "mean_var": _ValueStat(3, True, "execute_mean_var", _mean_var_reduce),
@@ -2285,6 +2439,18 @@ _VALUE_STATS = {
     # (W, mean_a, mean_b, M2_a, C_ab, M2_b), all float64, in the same three blocks; two arrays after the first values
     "cov_w": _ValueStat(6, False, "execute_cov_weighted", _cov_w_reduce, 2, (0, 1, 3)),
 }
+# The statistics of the third and fourth moments, (x, mean, M2, M3, M4): the library takes the first, the mean and the block of
+# three moments.  A table of their own: what walks _VALUE_STATS takes a statistic's partials for extrema pairs or for the
+# (x, means, moments) blocks of Chan's merge, and these merge by Pébay's update (_pebay_reduce).
+_MOMENT4_STATS = {
+    "skew_kurt": _ValueStat(5, True, "execute_skew_kurt", _skew_kurt_reduce, False, (0, 1, 2)),
+    "skew_kurt_w": _ValueStat(5, False, "execute_skew_kurt_weighted", _skew_kurt_w_reduce, True, (0, 1, 2)),
+}
+
+
+def _stat_of(name):
+    """the _ValueStat of a per-bin statistic of values, by the name _value_stat takes"""
+    return _VALUE_STATS[name] if name in _VALUE_STATS else _MOMENT4_STATS[name]
 
 
 # ---------------------------------------------------------------------------------------------

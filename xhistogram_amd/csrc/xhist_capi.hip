@@ -350,6 +350,36 @@ extern "C" int xhist_plan_execute_mean_var_weighted(xhist_plan* p, const xhist_a
                         });
 }
 
+extern "C" int xhist_plan_execute_skew_kurt(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                                            int64_t n_cols, int64_t* out_count, double* out_mean, double* out_moments, int mem_kind,
+                                            void* stream) {
+  return execute_values(p, "xhist_plan_execute_skew_kurt", samples, values, n_rows, n_cols, out_mean, out_count && out_moments,
+                        "out_count / out_moments is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
+                          hipStream_t s = static_cast<hipStream_t>(stream);
+                          ScratchScope scratch(s);
+                          double* sd = two_pass_scratch(scratch, n_rows * p->n_bins, "skew_kurt scratch block", err, err_cap);
+                          if (!sd) return (int)XHIST_ERR_NOMEM;
+                          return xhist_skew_kurt_run(pl, samples, values, n_rows, n_cols, out_count, out_mean, out_moments, sd, s, err,
+                                                     err_cap, desc, desc_cap);
+                        });
+}
+
+extern "C" int xhist_plan_execute_skew_kurt_weighted(xhist_plan* p, const xhist_array* samples, const xhist_array* values,
+                                                     const xhist_array* weights, int64_t n_rows, int64_t n_cols, double* out_wsum,
+                                                     double* out_mean, double* out_moments, int mem_kind, void* stream) {
+  if (!weights) return fail(XHIST_ERR_INVALID, "weights are required");
+  if (int rc = validate_arrays(p, samples, weights, n_rows, n_cols, out_wsum, XHIST_F64)) return rc;
+  return execute_values(p, "xhist_plan_execute_skew_kurt_weighted", samples, values, n_rows, n_cols, out_mean, out_moments != nullptr,
+                        "out_moments is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
+                          hipStream_t s = static_cast<hipStream_t>(stream);
+                          ScratchScope scratch(s);
+                          double* sd = two_pass_scratch(scratch, n_rows * p->n_bins, "weighted skew_kurt scratch block", err, err_cap);
+                          if (!sd) return (int)XHIST_ERR_NOMEM;
+                          return xhist_skew_kurt_w_run(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_moments, sd, s,
+                                                       err, err_cap, desc, desc_cap);
+                        });
+}
+
 extern "C" int xhist_plan_execute_cov(xhist_plan* p, const xhist_array* samples, const xhist_array* values_a, const xhist_array* values_b,
                                       int64_t n_rows, int64_t n_cols, int64_t* out_count, double* out_mean, double* out_comoment,
                                       int mem_kind, void* stream) {

@@ -7,6 +7,10 @@
 //   mv_sum_fast<ST, D, SCAN>, mv_dev_fast<ST, D, SCAN>    ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith     12 + 12
 //   mv_sum_generic<CMP, LDS>, mv_dev_generic<CMP, LDS>    CMP 0 / 1 / 3, slots in LDS or sums in global memory       6 + 6
 //   moments_mean<1, unsigned long long>, moments_finalize<1, unsigned long long>                                      2
+// and, for histogram_skew_kurt, whose pass 1 and means are the ones above (18 binning kernels + 1):
+//   sk_dev_fast<ST, D, SCAN>                              ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith         12
+//   sk_dev_generic<CMP, LDS>                              CMP 0 / 1 / 3, slots in LDS or sums in global memory         6
+//   moments_finalize4<unsigned long long>                                                                             1
 // (and zero_words of xhist_kernels.hip.h, which is not dispatched)
 #include "xhist_meanvar.hip.h"
 
@@ -42,4 +46,31 @@ int xhist_meanvar_run(const ValuesPlan& pl, const xhist_array* samples, const xh
                       char* desc, size_t desc_cap) {
   return two_pass_run<MeanVar>(pl, samples, values, nullptr, n_rows, n_cols, reinterpret_cast<unsigned long long*>(out_count), out_mean,
                                out_m2, sd, stream, err, err_cap, desc, desc_cap);
+}
+
+// ---- histogram_skew_kurt: mean_var's pass 1, then the four sums of pass 2 ------------------------------------------------------
+typedef void (*sk_fn)(const CovParams);
+
+struct SkDevKernels {
+  template <typename ST, int D, int SCAN>
+  static sk_fn fast() { return sk_dev_fast<ST, D, SCAN>; }
+  template <int CMP, bool LDS>
+  static sk_fn generic() { return sk_dev_generic<CMP, LDS>; }
+};
+
+struct SkewKurt {
+  using Sum = MvSumKernels;
+  using Dev = SkDevKernels;
+  static constexpr auto mean = moments_mean<1, unsigned long long>;
+  static constexpr auto finalize = moments_finalize4<unsigned long long>;
+  static constexpr ValuesSlots slots = moment4_slots<false>();
+  static constexpr int planes[4] = {1, 1, 3, 1};  // n; mean; M2, M3, M4; D
+  static constexpr const char *name = "skew_kurt", *prefix = "sk", *sum_prefix = "mv", *spelled = "skew_kurt";
+};
+
+int xhist_skew_kurt_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+                        int64_t* out_count, double* out_mean, double* out_moments, double* sd, hipStream_t stream, char* err,
+                        size_t err_cap, char* desc, size_t desc_cap) {
+  return two_pass_run<SkewKurt>(pl, samples, values, nullptr, n_rows, n_cols, reinterpret_cast<unsigned long long*>(out_count), out_mean,
+                                out_moments, sd, stream, err, err_cap, desc, desc_cap);
 }

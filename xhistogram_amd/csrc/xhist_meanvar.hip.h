@@ -52,6 +52,27 @@ __global__ void __launch_bounds__(256) mvw_dev_fast(const WParams p) {
   values_fast_body<MomentAcc<1, true, 2>, ST, D, SCAN>(p);
 }
 
+// The binning kernels of pass 2 of the third and fourth moments (histogram_skew_kurt): sk_dev_generic<CMP, LDS> / sk_dev_fast<ST,
+// D, SCAN>, instantiated in xhist_meanvar.hip only beside the mv_sum_* they follow, and the weighted skw_dev_*, instantiated in
+// xhist_meanvar_w.hip only beside mvw_sum_*.  Pass 1 is mean_var's own.  They take CovParams: out2 is a block of three planes
+// (Q2, Q3, Q4); the unweighted ones read no x_* stream.
+template <int CMP, bool LDS>
+__global__ void __launch_bounds__(512) sk_dev_generic(const CovParams p) {
+  values_generic_body<Moment4Acc<false>, CMP, LDS>(p);
+}
+template <typename ST, int D, int SCAN>
+__global__ void __launch_bounds__(256) sk_dev_fast(const CovParams p) {
+  values_fast_body<Moment4Acc<false>, ST, D, SCAN>(p);
+}
+template <int CMP, bool LDS>
+__global__ void __launch_bounds__(512) skw_dev_generic(const CovParams p) {
+  values_generic_body<Moment4Acc<true>, CMP, LDS>(p);
+}
+template <typename ST, int D, int SCAN>
+__global__ void __launch_bounds__(256) skw_dev_fast(const CovParams p) {
+  values_fast_body<Moment4Acc<true>, ST, D, SCAN>(p);
+}
+
 }  // namespace xhist
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
@@ -69,3 +90,16 @@ int xhist_meanvar_run(const ValuesPlan& pl, const xhist_array* samples, const xh
 int xhist_meanvar_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
                         int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_m2, double* sd, hipStream_t stream,
                         char* err, size_t err_cap, char* desc, size_t desc_cap);
+
+// The launches of histogram_skew_kurt (two_pass_run<SkewKurt>, xhist_meanvar.hip): mean_var's pass 1 and means, then the four
+// sums of pass 2 and moments_finalize4.  out_moments is a float64 [3, n_rows, n_bins] block (M2, M3, M4), `sd` a float64
+// [n_rows, n_bins] block of the caller's for D.  (Called by xhist_plan_execute_skew_kurt, xhist_capi.hip.)
+int xhist_skew_kurt_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+                        int64_t* out_count, double* out_mean, double* out_moments, double* sd, hipStream_t stream, char* err,
+                        size_t err_cap, char* desc, size_t desc_cap);
+
+// The same for the weighted form (two_pass_run<SkewKurtW>, xhist_meanvar_w.hip).  (Called by
+// xhist_plan_execute_skew_kurt_weighted, xhist_capi.hip.)
+int xhist_skew_kurt_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
+                          int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_moments, double* sd,
+                          hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap);

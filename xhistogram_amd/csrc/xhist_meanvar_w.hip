@@ -7,6 +7,10 @@
 //   mvw_sum_fast<ST, D, SCAN>, mvw_dev_fast<ST, D, SCAN>    ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith     12 + 12
 //   mvw_sum_generic<CMP, LDS>, mvw_dev_generic<CMP, LDS>    CMP 0 / 1 / 3, slots in LDS or sums in global memory       6 + 6
 //   moments_mean<1, double>, moments_finalize<1, double>                                                                2
+// and, for the weighted histogram_skew_kurt, whose pass 1 and means are the ones above (18 binning kernels + 1):
+//   skw_dev_fast<ST, D, SCAN>                               ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith         12
+//   skw_dev_generic<CMP, LDS>                               CMP 0 / 1 / 3, slots in LDS or sums in global memory         6
+//   moments_finalize4<double>                                                                                           1
 // (and zero_words of xhist_kernels.hip.h, which is not dispatched)
 #include "xhist_meanvar.hip.h"
 
@@ -44,4 +48,31 @@ int xhist_meanvar_w_run(const ValuesPlan& pl, const xhist_array* samples, const 
                         char* err, size_t err_cap, char* desc, size_t desc_cap) {
   return two_pass_run<MeanVarW>(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_m2, sd, stream, err, err_cap, desc,
                                 desc_cap);
+}
+
+// ---- the weighted histogram_skew_kurt: the weighted mean_var's pass 1, then the four sums of pass 2 ----------------------------
+typedef void (*skw_fn)(const CovParams);
+
+struct SkwDevKernels {
+  template <typename ST, int D, int SCAN>
+  static skw_fn fast() { return skw_dev_fast<ST, D, SCAN>; }
+  template <int CMP, bool LDS>
+  static skw_fn generic() { return skw_dev_generic<CMP, LDS>; }
+};
+
+struct SkewKurtW {
+  using Sum = MvwSumKernels;
+  using Dev = SkwDevKernels;
+  static constexpr auto mean = moments_mean<1, double>;
+  static constexpr auto finalize = moments_finalize4<double>;
+  static constexpr ValuesSlots slots = moment4_slots<true>();
+  static constexpr int planes[4] = {1, 1, 3, 1};  // W; mean; M2, M3, M4; D
+  static constexpr const char *name = "skew_kurt_w", *prefix = "skw", *sum_prefix = "mvw", *spelled = "weighted skew_kurt";
+};
+
+int xhist_skew_kurt_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
+                          int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_moments, double* sd,
+                          hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap) {
+  return two_pass_run<SkewKurtW>(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_moments, sd, stream, err,
+                                 err_cap, desc, desc_cap);
 }

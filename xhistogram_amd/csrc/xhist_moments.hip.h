@@ -1,7 +1,8 @@
 // xhist_moments.hip.h — the per-bin first and second moments of NV value arrays, with frequency weights (WT) or without: the
 // slots, the one accumulator policy of the shared kernel skeletons (xhist_values.hip.h) and the steps between and after the two
 // passes, for histogram_mean_var (NV 1; xhist_meanvar.hip.h), its weighted form, histogram_cov (NV 2; xhist_cov.hip.h) and
-// histogram_weighted_cov (xhist_cov_w.hip.h).  Their driver is two_pass_run of xhist_values.hip.h.
+// histogram_weighted_cov (xhist_cov_w.hip.h).  Their driver is two_pass_run of xhist_values.hip.h.  histogram_skew_kurt runs
+// mean_var's pass 1 and a pass 2 of its own for the second, third and fourth moments (Moment4Acc, moments_finalize4, below).
 //
 // Which samples count is decided exactly as for the histogram: the same digitize, the same tables.  A counted sample hands the
 // policy its NV values v_k and, weighted, its weight w, all converted to float64 before any product (numpy's astype; a float32
@@ -243,6 +244,93 @@ struct MomentAcc<NV, WT, 2> : MomentTerms<NV, WT> {
   }
 };
 
+// ---- the third and fourth central moments of one value array (histogram_skew_kurt) ---------------------------------------------
+// Pass 1 and the means are those of mean_var (MomentAcc<1, WT, 1>, moments_mean<1, First>).  Pass 2 keeps, per bin, the mean and
+// four sums of the terms of a sample, formed in float64 in exactly this order of products:
+//   d = v - mean[bin];  t1 = d (weighted: w * d);  t2 = t1 * d;  t3 = t2 * d;  t4 = t3 * d
+//   D = sum(t1), Q2 = sum(t2), Q3 = sum(t3), Q4 = sum(t4)
+// moments_finalize4 then carries the corrected two-pass formula to the fourth order (see there).
+struct Moment4Slot {
+  double m, d, q2, q3, q4;
+};
+static_assert(sizeof(Moment4Slot) == 40 && offsetof(Moment4Slot, m) == 0 && offsetof(Moment4Slot, d) == 8 &&
+                  offsetof(Moment4Slot, q2) == 16 && offsetof(Moment4Slot, q4) == 32,
+              "pass 2's slot of the four moments: the mean, then D, Q2, Q3, Q4; the size the family rule and the tests restate");
+
+// the slots for the family rule: mean_var's pass 1 beside the 40-byte slot of pass 2, which decides (copies, geometry, borders)
+template <bool WT>
+constexpr ValuesSlots moment4_slots() {
+  return {{sizeof(MomentSumSlot<1, WT>), sizeof(Moment4Slot)}, {sizeof(MomentSumSlot<1, WT>), sizeof(Moment4Slot)}, true};
+}
+
+// The policy of pass 2, a sibling of MomentAcc<1, WT, 2>: w2_ptr = the means (read only), out = D [1 plane], out2 = Q2, Q3, Q4
+// [3 planes, CovParams::plane elements apart].  Four ds_add_f64 per sample; a flush sums the copies in copy order and skips a
+// bin whose four sums are all 0 (a NaN sum is not 0 and reaches global memory).  The skeletons hand it v, then w (WT).
+template <bool WT>
+struct Moment4Acc {
+  using params_t = CovParams;
+  using slot_t = Moment4Slot;
+  static constexpr bool kCopies = true;
+  static constexpr int kExtra = WT ? 1 : 0;
+  static __device__ __forceinline__ void init(slot_t* s, const params_t& p, int64_t row) {
+    const double* mean = reinterpret_cast<const double*>(p.w2_ptr) + row * p.n_bins;
+    const uint32_t n = (uint32_t)p.n_bins << p.copies_log2;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+      s[i].m = mean[i >> p.copies_log2];
+      s[i].d = 0.0;
+      s[i].q2 = 0.0;
+      s[i].q3 = 0.0;
+      s[i].q4 = 0.0;
+    }
+  }
+  template <typename V, typename... X>
+  static __device__ __forceinline__ void lds_add(slot_t* s, uint32_t i, V a, X... x) {
+    const V in[] = {a, x...};
+    const double d = (double)in[0] - s[i].m;
+    double t1 = d;
+    if constexpr (WT) t1 = (double)in[1] * d;
+    const double t2 = t1 * d, t3 = t2 * d, t4 = t3 * d;
+    unsafeAtomicAdd(&s[i].d, t1);
+    unsafeAtomicAdd(&s[i].q2, t2);
+    unsafeAtomicAdd(&s[i].q3, t3);
+    unsafeAtomicAdd(&s[i].q4, t4);
+  }
+  template <typename... X>
+  static __device__ __forceinline__ void global_add(const params_t& p, int64_t row, int64_t bin, double a, X... x) {
+    const double in[] = {a, x...};
+    const int64_t i = row * p.n_bins + bin;
+    const double d = in[0] - reinterpret_cast<const double*>(p.w2_ptr)[i];
+    double t1 = d;
+    if constexpr (WT) t1 = in[1] * d;
+    const double t2 = t1 * d, t3 = t2 * d, t4 = t3 * d;
+    double* q = reinterpret_cast<double*>(p.out2);
+    unsafeAtomicAdd(reinterpret_cast<double*>(p.out) + i, t1);
+    unsafeAtomicAdd(q + i, t2);
+    unsafeAtomicAdd(q + p.plane + i, t3);
+    unsafeAtomicAdd(q + 2 * p.plane + i, t4);
+  }
+  static __device__ __forceinline__ void flush(const slot_t* s, const params_t& p, int64_t row) {
+    double* sd = reinterpret_cast<double*>(p.out) + row * p.n_bins;
+    double* q = reinterpret_cast<double*>(p.out2) + row * p.n_bins;
+    const uint32_t copies = 1u << p.copies_log2;
+    for (uint32_t b = threadIdx.x; b < (uint32_t)p.n_bins; b += blockDim.x) {
+      double a = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
+      for (uint32_t c = 0; c < copies; ++c) {
+        const slot_t& x = s[(b << p.copies_log2) + c];
+        a += x.d;
+        q2 += x.q2;
+        q3 += x.q3;
+        q4 += x.q4;
+      }
+      if (a == 0.0 && q2 == 0.0 && q3 == 0.0 && q4 == 0.0) continue;
+      unsafeAtomicAdd(sd + b, a);
+      unsafeAtomicAdd(q + b, q2);
+      unsafeAtomicAdd(q + p.plane + b, q3);
+      unsafeAtomicAdd(q + 2 * p.plane + b, q4);
+    }
+  }
+};
+
 // The steps between and after the passes, over [n] arrays and [k, n] blocks; First is the type of pass 1's first output,
 // unsigned long long (the counts) or double (the sums of weights).
 // the sums of pass 1 -> the NV means, in place in `sum` [NV, n]: S / first, NaN where the first is 0 (a NaN W gives NaN)
@@ -278,6 +366,34 @@ __global__ void __launch_bounds__(256) moments_finalize(const First* first, cons
       co[n + i] = co[n + i] - s[0] * s[1] / (double)c;
       co[2 * n + i] = r[1] <= 0.0 ? 0.0 : r[1];
     }
+  }
+}
+
+// the sums of pass 2 of the four moments -> M2, M3, M4, in place in `q` [3, n] (Q2, Q3, Q4 on entry); `sd` is D [n].  With
+// x = first and delta = D / x, every product and sum rounded on its own (no contraction), evaluated in this order:
+//   M2 = max(0, Q2 - (D * D) / x)                                    (moments_finalize<1, First>'s very expression)
+//   d2 = delta * delta;  d3 = d2 * delta;  d4 = d2 * d2
+//   M3 = (Q3 - (3 * delta) * Q2) + (2 * x) * d3                      (not clamped)
+//   M4 = max(0, ((Q4 - (4 * delta) * Q3) + (6 * d2) * Q2) - (3 * x) * d4)
+// NaN where the first is 0, and NaN stays NaN.
+template <typename First>
+__global__ void __launch_bounds__(256) moments_finalize4(const First* first, const double* sd, double* q, int64_t n) {
+#pragma clang fp contract(off)
+  const double nan = __builtin_nan("");
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const First c = first[i];
+    if (c == 0) {
+      q[i] = q[n + i] = q[2 * n + i] = nan;
+      continue;
+    }
+    const double x = (double)c, s = sd[i], q2 = q[i], q3 = q[n + i], q4 = q[2 * n + i];
+    const double delta = s / x;
+    const double d2 = delta * delta, d3 = d2 * delta, d4 = d2 * d2;
+    const double r2 = q2 - s * s / x;
+    const double r4 = ((q4 - (4.0 * delta) * q3) + (6.0 * d2) * q2) - (3.0 * x) * d4;
+    q[i] = r2 <= 0.0 ? 0.0 : r2;
+    q[n + i] = (q3 - (3.0 * delta) * q2) + (2.0 * x) * d3;
+    q[2 * n + i] = r4 <= 0.0 ? 0.0 : r4;
   }
 }
 

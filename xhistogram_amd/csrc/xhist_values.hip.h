@@ -543,7 +543,10 @@ static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what,
     P kp;
     static_cast<Params&>(kp) = values_params(pl, c, g.segs, samples, values, r0, nr, n_cols);
     if constexpr (std::is_base_of<CovWParams, P>::value) weights_params(kp, weights, fourth);
-    else if constexpr (std::is_base_of<WParams, P>::value) weights_params(kp, weights);
+    else if constexpr (std::is_base_of<WParams, P>::value) {
+      static const xhist_array no_stream = {};  // (a CovParams kernel of one value array without weights reads no x_* stream)
+      weights_params(kp, weights ? weights : &no_stream);
+    }
     if constexpr (std::is_base_of<CovParams, P>::value) kp.plane = n_rows * pl.n_bins;  // (the whole call's rows, whatever the chunk)
     kp.w2_ptr = in2 ? static_cast<const uint64_t*>(in2) + r0 * pl.n_bins : nullptr;
     kp.out = static_cast<uint64_t*>(out) + r0 * pl.n_bins;
@@ -554,14 +557,26 @@ static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what,
   return XHIST_OK;
 }
 
+// the prefix of a two-pass statistic's pass-1 kernels: M::sum_prefix where it names one, else M::prefix (see two_pass_run)
+template <class M, class = void>
+struct sum_prefix_of {
+  static constexpr const char* value = M::prefix;
+};
+template <class M>
+struct sum_prefix_of<M, std::void_t<decltype(M::sum_prefix)>> {
+  static constexpr const char* value = M::sum_prefix;
+};
+
 // The driver of the two-pass statistics: the zeroing and the five launches on `stream` (pass 1, means, pass 2, finalize).  M
 // names what a statistic brings (xhist_meanvar.hip: MeanVar, xhist_meanvar_w.hip: MeanVarW, xhist_cov.hip: Cov, xhist_cov_w.hip:
-// CovW):
-//   Sum, Dev          the kernel sets of the two passes, for pick_values_kernel
+// CovW; SkewKurt and SkewKurtW, next to MeanVar and MeanVarW, whose pass 1 they run):
+//   Sum, Dev          the kernel sets of the two passes, for pick_values_kernel (each with the Params type of its own kernels)
 //   mean, finalize    the kernels of the steps after them, over the first output (counts or sums of weights)
 //   slots             the ValuesSlots of the two passes
 //   planes            the [n_rows, n_bins] planes behind first, out_mean, out_m2 and sd, in this order (cov: 1, 2, 3, 2)
 //   name, prefix      the statistic in messages and in describe() (mean_var / mean_var_w / cov), and its kernels' prefix
+//   sum_prefix        (optional) the prefix of pass 1's kernels and of the means' step where they are another statistic's:
+//                     skew_kurt runs mean_var's (mv_sum_*, then sk_dev_*), and the passes' kernels then take different Params
 //   spelled           the statistic where a message spells it out ("weighted mean_var")
 // `first` is out_count or out_wsum; `third` the weights or the second value array, nullptr for a statistic of two streams;
 // `fourth` the weights of a statistic of two value arrays, nullptr for every other.
@@ -576,7 +591,8 @@ static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const 
   };
   char lds_what[64], sum_what[32], dev_what[32];  // (handed over before anything can fail, so made up front)
   snprintf(lds_what, sizeof lds_what, "%s: setting the dynamic LDS size failed", M::name);
-  snprintf(sum_what, sizeof sum_what, "%s_sum launch", M::prefix);
+  const char* const prefix1 = sum_prefix_of<M>::value;
+  snprintf(sum_what, sizeof sum_what, "%s_sum launch", prefix1);
   snprintf(dev_what, sizeof dev_what, "%s_dev launch", M::prefix);
   const auto mean = M::mean;
   const auto finalize = M::finalize;
@@ -590,7 +606,8 @@ static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const 
 
   ValuesChoice c;
   ValuesGeometry g;
-  values_fn_of<typename M::Sum> sum = nullptr, dev = nullptr;
+  values_fn_of<typename M::Sum> sum = nullptr;
+  values_fn_of<typename M::Dev> dev = nullptr;
   if (n_cols > 0) {
     c = choose_values(pl, M::slots, samples, values, n_cols, third, fourth);
     sum = pick_values_kernel<typename M::Sum>(c, pl);
@@ -599,15 +616,15 @@ static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const 
       snprintf(err, err_cap, "internal: no %s kernel for this combination", M::spelled);
       return XHIST_ERR_HIP;
     }
-    for (int k = 0; k < 2; ++k)
-      if (int rc = allow_values_lds(k ? dev : sum, c.lds_bytes[k], lds_what, err, err_cap)) return rc;
+    if (int rc = allow_values_lds(sum, c.lds_bytes[0], lds_what, err, err_cap)) return rc;
+    if (int rc = allow_values_lds(dev, c.lds_bytes[1], lds_what, err, err_cap)) return rc;
     g = values_geometry(pl, c, n_rows, n_cols);
     if (int rc = launch_values_pass(sum, c.lds_bytes[0], sum_what, pl, c, g, samples, values, n_rows, n_cols, first, out_mean,
                                     nullptr, stream, err, err_cap, third, fourth))
       return rc;
   }
   XH_VALUES_LAUNCH(mean, dim3(grid_io), dim3(256), 0, stream, first, out_mean, n_out);
-  XH_VALUES_LAUNCH_CHECK(what(M::prefix, "_mean"));
+  XH_VALUES_LAUNCH_CHECK(what(prefix1, "_mean"));
   if (n_cols > 0) {
     if (int rc = launch_values_pass(dev, c.lds_bytes[1], dev_what, pl, c, g, samples, values, n_rows, n_cols, sd, out_m2,
                                     out_mean, stream, err, err_cap, third, fourth))
@@ -621,7 +638,7 @@ static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const 
     snprintf(desc, desc_cap,
              "%s pass1=%s_sum_%s slots=%s pass2=%s_dev_%s slots=%s scan=%d copies=%d block=%d segs=%lld lds_bytes=%zu/%zu "
              "tables_in_lds=%d D=%d cmp=%d",
-             M::name, M::prefix, fam, home, M::prefix, fam, home, c.scan, 1 << c.copies_log2, g.block, (long long)g.segs, c.lds_bytes[0],
+             M::name, prefix1, fam, home, M::prefix, fam, home, c.scan, 1 << c.copies_log2, g.block, (long long)g.segs, c.lds_bytes[0],
              c.lds_bytes[1], (int)c.tables_in_lds, pl.n_dims, values_cmp(pl));
   }
   return XHIST_OK;

@@ -14,7 +14,7 @@ from .core import histogram as _core_histogram
 from .core import histogram_two_weights as _core_histogram_two_weights
 
 __all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
-           "histogram_cov", "histogram_weighted_cov"]
+           "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt"]
 
 
 def _xr():
@@ -166,6 +166,27 @@ def histogram_mean_var(*args, values, bins=None, range=None, dim=None, ddof=0, b
     first = "count" if weights is None else "sum_of_weights"
     return tuple(xr.DataArray(a, dims=out_dims, coords=coords, name="%s_%s" % (base, suffix))
                  for a, suffix in ((cnt, first), (mean, "mean"), (var, "var")))
+
+
+def histogram_skew_kurt(*args, values, bins=None, range=None, dim=None, weights=None, ddof=0, bias=True, fisher=True,
+                        block_size="auto", keep_coords=False, bin_dim_suffix="_bin"):
+    """Per-bin count, mean, variance, skewness and kurtosis of the DataArray ``values`` over the bins of ``args``
+    (:func:`xhistogram_amd.core.histogram_skew_kurt` with the labels of :func:`histogram`).
+
+    ``args``, ``bins``, ``range``, ``dim``, ``keep_coords``, ``bin_dim_suffix``, ``values`` and ``weights`` are those of
+    :func:`histogram_mean_var`; ``ddof``, ``bias`` and ``fisher`` those of the core function.  Returns ``(count, mean, var,
+    skew, kurt)``: five DataArrays with the dims and coords ``histogram`` gives, named ``<values name>_count`` (with
+    ``weights``: ``<values name>_sum_of_weights``) / ``_mean`` / ``_var`` / ``_skew`` / ``_kurt`` (``values`` when the
+    DataArray has no name)."""
+    from .core import histogram_skew_kurt as _core_histogram_skew_kurt
+
+    results, out_dims, coords, base = _values_statistic(
+        "histogram_skew_kurt", _core_histogram_skew_kurt, args, values, bins, range, dim, keep_coords, bin_dim_suffix, ddof=ddof,
+        bias=bias, fisher=fisher, block_size=block_size, weights=weights)
+    xr = _xr()
+    first = "count" if weights is None else "sum_of_weights"
+    return tuple(xr.DataArray(a, dims=out_dims, coords=coords, name="%s_%s" % (base, suffix))
+                 for a, suffix in zip(results, (first, "mean", "var", "skew", "kurt")))
 
 
 def _with_quantile_coord(res, q, out_dims, coords, name):
