@@ -145,6 +145,19 @@ int xhist_plan_execute_extrema(xhist_plan* plan, const xhist_array* samples, con
                                int64_t n_rows, int64_t n_cols, double* out_min, double* out_max,
                                int mem_kind, int accumulate, void* stream);
 
+/* Where each bin's minimum and maximum of `values` lie (added within ABI v11): the samples that count, the conversion of the
+ * values, the NaN rule and the total order (-0.0 < +0.0) are xhist_plan_execute_extrema's, and out_values equals its two
+ * outputs bit for bit.  out_index holds, per bin, the column index (0 .. n_cols - 1 inside the bin's row) of the FIRST counted
+ * sample whose value is the bin's minimum (plane 0) or maximum (plane 1), and -1 where the bin received no value.  Exact and
+ * deterministic: pass 1 finds the extreme keys, pass 2 takes the smallest index among the samples whose key equals them.
+ *   out_values: contiguous float64 [2, n_rows, prod(nb_d)] (minimum, maximum), a DEVICE buffer; it doubles as working space.
+ *   out_index: contiguous int64 [2, n_rows, prod(nb_d)], a DEVICE buffer.  Both are overwritten (no accumulate mode).
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Asynchronous on `stream`.  xhist_plan_describe then names the kernel family of each pass and where its slots live. */
+int xhist_plan_execute_argextrema(xhist_plan* plan, const xhist_array* samples, const xhist_array* values,
+                                  int64_t n_rows, int64_t n_cols, double* out_values, int64_t* out_index,
+                                  int mem_kind, void* stream);
+
 /* Per-bin count, mean and sum of squared deviations of `values` (ABI v11): which samples count is exactly what
  * xhist_plan_execute counts (same digitize, last bin closed, NaN / out-of-range samples dropped); each counted sample whose
  * value is not NaN contributes that value converted to float64.  Two passes (Chan, Golub & LeVeque): n and S = sum(v), then

@@ -2,7 +2,7 @@
 
 Each translation unit the base's build.sh lists is compiled, in the base (a `git archive` of --base) and in the working tree,
 with build.sh's flags.  The gfx950 code object of each object file is taken out of its .hip_fatbin bundle and disassembled
-with llvm-objdump -d; every symbol's instructions are compared with the addresses and encodings stripped (and the zero filler behind a symbol's last instruction dropped).  Kernels only the
+with llvm-objdump -d; every symbol's instructions are compared with the addresses and encodings stripped (and the filler behind a symbol's last instruction dropped: zero words, and the s_nop run that pads the unit's last symbol).  Kernels only the
 working tree has (new units, new instantiations) are counted, not compared.
 
     python tools/values_code_diff.py [--base HEAD] [--units xhist_extrema,xhist_meanvar,...] [--jobs 8]
@@ -52,10 +52,21 @@ def disassemble(tree, unit, work):
             enc = re.search(r"//\s*[0-9A-Fa-f]+:\s*([0-9A-Fa-f ]+)$", line)
             cur.append((re.sub(r"\s+", " ", ins), ins == "..." or (bool(enc) and not enc.group(1).replace(" ", "").strip("0"))))  # ("...": objdump's run of zero words)
     # Words of zeros behind a symbol's last instruction are the filler up to the next symbol's alignment (they disassemble as
-    # v_cndmask_b32 v0, s0, v0, vcc): how many there are depends on what follows the symbol, not on its code.
+    # v_cndmask_b32 v0, s0, v0, vcc): how many there are depends on what follows the symbol, not on its code.  The same holds
+    # for the run of s_nop 0 behind the s_endpgm of the unit's last symbol (the padding of the code section's end): a symbol
+    # that another one now follows loses it.
     for name, body in syms.items():
-        while body and body[-1][1]:
-            body.pop()
+        while True:
+            n = len(body)
+            while body and body[-1][1]:
+                body.pop()
+            k = len(body)
+            while k and body[k - 1][0] == "s_nop 0":
+                k -= 1
+            if k and body[k - 1][0] == "s_endpgm":
+                del body[k:]
+            if len(body) == n:
+                break
         syms[name] = [ins for ins, _ in body]
     return syms
 

@@ -71,7 +71,7 @@ EXPORTS = (
     "xhist_plan_create", "xhist_plan_destroy", "xhist_plan_execute", "xhist_plan_execute_two_weights", "xhist_plan_execute_extrema",
     "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
     "xhist_plan_execute_quantile_weighted", "xhist_plan_execute_cov", "xhist_plan_execute_cov_weighted",
-    "xhist_plan_execute_skew_kurt", "xhist_plan_execute_skew_kurt_weighted",
+    "xhist_plan_execute_skew_kurt", "xhist_plan_execute_skew_kurt_weighted", "xhist_plan_execute_argextrema",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -137,6 +137,9 @@ def load():
         lib.xhist_plan_execute_extrema.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
             C.c_void_p,
+        ]
+        lib.xhist_plan_execute_argextrema.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
         ]
         lib.xhist_plan_execute_mean_var.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -385,6 +388,13 @@ class Plan:
         device-resident views into device buffers, asynchronous on `stream` (xhist_plan_execute_extrema)"""
         self._execute_values("xhist_plan_execute_extrema", sample_views, (value_view,), n_rows, n_cols, (out_min_ptr, out_max_ptr),
                              (1 if accumulate else 0,), stream=stream)
+
+    def execute_argextrema(self, sample_views, value_view, n_rows, n_cols, out_values_ptr, out_index_ptr, stream=0):
+        """per-bin minimum and maximum of the values (float64 [2, n_rows, bins]; NaN where no value arrived) and the column
+        index of the first sample that holds each (int64 [2, n_rows, bins]; -1 there) of device-resident views into device
+        buffers, asynchronous on `stream` (xhist_plan_execute_argextrema)"""
+        self._execute_values("xhist_plan_execute_argextrema", sample_views, (value_view,), n_rows, n_cols,
+                             (out_values_ptr, out_index_ptr), stream=stream)
 
     def execute_mean_var(self, sample_views, value_view, n_rows, n_cols, out_count_ptr, out_mean_ptr, out_m2_ptr, stream=0):
         """per-bin count (int64), mean and sum of squared deviations M2 (float64; NaN where no value arrived) of the values of

@@ -35,7 +35,7 @@ _range = range
 
 __all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
            "histogram_weighted_quantile", "histogram_cov", "histogram_weighted_cov", "combine_weighted_cov",
-           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt"]
+           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1799,13 +1799,15 @@ def _upload_host(args, values, bins, *extras):
     return [a.broadcast_to(shape) for a in arrays]
 
 
-def _value_views(args, values, axis, bins, backend, *extras):
+def _value_views(args, values, axis, bins, backend, *extras, ordered=False):
     """the [rows, cols] views of broadcast torch tensors or DeviceArrays and of their values (and of the arrays after them, as
     _upload_host takes them), for a per-bin statistic of the values: (plan, native views (samples..., values[, weights or
     second values[, weights]]), the views they were made of (their copies, if any, must outlive the
     kernels: callers hold them until the download), rows, cols, kept axes shape, device, stream).  The kept axes stay in
     place and the reduced ones have extent 1 (then come the bin axes).  The views are those of _bincount's block adapter;
-    layouts no three strides describe are copied."""
+    layouts no three strides describe are copied.  `ordered`: the columns of a row are the reduced axes in ascending axis
+    number, C order (a statistic that reports positions inside the row); otherwise any order that walks memory as one strided
+    dimension will do, and layouts that need a permutation for that are not copied."""
     a0 = args[0]
     ndim = a0.ndim
     do_full_array = (axis is None) or (set(axis) == set(_range(ndim)))
@@ -1815,7 +1817,11 @@ def _value_views(args, values, axis, bins, backend, *extras):
     if backend == "device" and any(c is not None and a.dtype != c for a, c in zip(args, common)):
         raise TypeError("datetime64 DeviceArrays must already have the unit they share with their bin edges")
     arrays = list(args) + [values] + [e for e in extras if e is not None]
-    order = _reduced_order(arrays[0], list(_range(ndim)) if do_full_array else axis)
+    if ordered:
+        axis = axis if do_full_array else sorted(axis)
+        order = list(_range(ndim)) if do_full_array else axis
+    else:
+        order = _reduced_order(arrays[0], list(_range(ndim)) if do_full_array else axis)
     descs = [_collapse(a, axis, do_full_array, order) for a in arrays]
     views = None
     if all(d is not None for d in descs) and len({d[:2] for d in descs}) == 1:
@@ -1935,6 +1941,76 @@ def histogram_extrema(*args, values, bins=None, range=None, axis=None, block_siz
     # in the key-ordered combine on the host (also under XHIST_AMD_DASK_EXCHANGE=rccl: the exchange adds only)
     _, (vmin, vmax), bins, _ = _value_stat("extrema", args, values, bins, range, axis, "histogram_extrema")
     return vmin, vmax, bins
+
+
+def _argextrema_rows(args, values, axis, bins, backend):
+    """(positions, values) of broadcast torch tensors (torch out) or DeviceArrays (numpy out): int64 and float64
+    [2 (min, max), kept axes (reduced ones of extent 1), bins...].  A position is the column of the row the library saw, and
+    those columns are the reduced axes in ascending axis number (_value_views, ordered)."""
+    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, ordered=True)
+    n = m * plan.n_bins
+    shape = (2,) + kept_axes_shape + plan.bins_shape
+    if backend == "torch":
+        torch = _torch()
+        vals = torch.empty(shape, dtype=torch.float64, device=args[0].device)
+        idx = torch.empty(shape, dtype=torch.int64, device=args[0].device)
+        if n > 0:
+            plan.execute_argextrema(nv[:-1], nv[-1], m, c, vals.data_ptr(), idx.data_ptr(), stream=stream)
+        return idx, vals
+    host = np.empty((4, n), np.float64)  # (the positions come down as the int64 bits they are; no arithmetic touches them)
+    if n > 0:
+        buf = _native.DeviceBuffer(device, 4 * n * 8)
+        plan.execute_argextrema(nv[:-1], nv[-1], m, c, buf.ptr, buf.ptr + 2 * n * 8, stream=stream)
+        buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+    return host[2:].view(np.int64).reshape(shape), host[:2].reshape(shape)
+
+
+def _argextrema_block(*all_arrays, axis=None, bins=None):
+    """one dask block (samples..., values), complete along the reduced axes: [4 (vmin, vmax, argmin, argmax), block axes
+    (reduced ones of extent 1), bins...] float64, the two positions as int64 bits"""
+    n = len(all_arrays) - 1
+    arrays = _upload_host(all_arrays[:n], all_arrays[n], bins)
+    idx, vals = _argextrema_rows(arrays[:n], arrays[n], axis, bins, "device")
+    return np.concatenate([vals, idx.view(np.float64)])
+
+
+def histogram_argextrema(*args, values, bins=None, range=None, axis=None, block_size="auto"):
+    """Where each bin's minimum and maximum of ``values`` lie, computed on an MI355X: the position of the first sample that
+    holds the bin's extreme, what ``scipy.stats.binned_statistic`` users get from ``statistic=np.argmin`` as a Python callable
+    on the host.  A position indexes every other field: the depth, the oxygen and the date of each class's coldest sample.
+
+    ``args``, ``bins``, ``range``, ``axis`` and ``values`` are those of :func:`histogram_extrema`, and so are the samples that
+    count, the NaN-value rule and the total order (``-0.0 < +0.0``); ``vmin`` and ``vmax`` equal its outputs bit for bit.
+
+    ``argmin`` / ``argmax`` hold the position of the FIRST counted sample whose value (as float64) is the bin's minimum /
+    maximum, and ``-1`` where the bin is empty.  A position is the C-order flat index over the reduced axes taken in ascending
+    axis number, in the broadcast shape, whatever order ``axis`` lists them in:
+    ``np.unravel_index(argmin, [shape[i] for i in sorted(axis)])`` gives per-axis indices; with ``axis=None`` it is the flat
+    index into the broadcast array.  "First" means smallest position.  The result departs from ``np.nanargmin`` of the bin's
+    values only where the total order does: among ``+0.0`` and ``-0.0`` the minimum is a ``-0.0``.  Exact and deterministic:
+    one pass finds the extremes, a second one takes the smallest position among the samples that equal them.
+    ``block_size`` is accepted and changes nothing.
+
+    Returns ``(argmin, argmax, vmin, vmax, bin_edges)``: int64 and float64 with the shape ``histogram`` gives (kept axes, then
+    bin axes).  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the current stream),
+    DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block: every reduced axis must then be a single
+    chunk (positions of several chunks are not merged)."""
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_argextrema")
+    n_inputs = len(args)
+    if backend == "dask":
+        for a in all_arrays:
+            if any(len(a.chunks[ax]) > 1 for ax in drop_axes):
+                raise ValueError("exact quantiles of several chunks cannot be merged: rechunk the reduced axes of every input into "
+                                 "one chunk (e.g. arr.rechunk({axis: -1}))")
+        res = _values_blockwise(_argextrema_block, 4, all_arrays, bins, axis, drop_axes)
+        res = res[(slice(None),) + tuple(0 if i in drop_axes else slice(None) for i in _range(all_arrays[0].ndim))]
+        idx = res[2:].view(np.int64)
+        return idx[0], idx[1], res[0], res[1], bins
+    arrays, on = _resident(backend, raw, all_arrays, n_inputs, bins)
+    idx, vals = _argextrema_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, on)
+    drop = tuple(a + 1 for a in drop_axes)
+    idx, vals = _drop_axes(idx, drop, backend), _drop_axes(vals, drop, backend)
+    return idx[0], idx[1], vals[0], vals[1], bins
 
 
 def _values_call(args, values, bins, range, axis, name, third=None, fourth=None):

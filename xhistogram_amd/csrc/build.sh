@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build libxhist_amd.so in-tree for gfx950 (cross-compiles without a GPU).  Eighteen translation units (xhist_hot: the small code object a first call loads),
-# compiled in parallel: nine that instantiate the float64 / float32 / mixed-dtype vector, routing and exchange kernels, the per-bin extrema (xhist_extrema), the per-bin mean and variance with the third and fourth moments of histogram_skew_kurt (xhist_meanvar) and their weighted form (xhist_meanvar_w), the per-bin quantiles (xhist_quantile) and their weighted form (xhist_quantile_w), the per-bin covariance of two value arrays (xhist_cov) and its weighted form (xhist_cov_w), and the rest.
+# compiled in parallel: nine that instantiate the float64 / float32 / mixed-dtype vector, routing and exchange kernels, the per-bin extrema and the positions of histogram_argextrema (xhist_extrema), the per-bin mean and variance with the third and fourth moments of histogram_skew_kurt (xhist_meanvar) and their weighted form (xhist_meanvar_w), the per-bin quantiles (xhist_quantile) and their weighted form (xhist_quantile_w), the per-bin covariance of two value arrays (xhist_cov) and its weighted form (xhist_cov_w), and the rest.
 set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 out="${XHIST_BUILD_OUT:-$here/../libxhist_amd.so}"  # (development: XHIST_BUILD_OUT / XHIST_BUILD_FLAGS build an A/B variant next to the library)

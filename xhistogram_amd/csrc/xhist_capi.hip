@@ -277,7 +277,7 @@ static ValuesPlan values_plan(const xhist_plan* p) {
   return pl;
 }
 
-// The checks and the tail the seven entry points share: `out` is the statistic's float64 output validate_arrays checks,
+// The checks and the tail the statistics' entry points share: `out` is the statistic's float64 output validate_arrays checks,
 // `outs_ok` whether the others are given (`outs_missing` the message if not).  run(plan, err, err_cap, desc, desc_cap) launches
 // on the plan's device; the line it writes to `desc` becomes the plan's describe().
 template <class Run>
@@ -309,6 +309,15 @@ extern "C" int xhist_plan_execute_extrema(xhist_plan* p, const xhist_array* samp
                         "out_max is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
                           return xhist_extrema_run(pl, samples, values, n_rows, n_cols, out_min, out_max, accumulate,
                                                    static_cast<hipStream_t>(stream), err, err_cap, desc, desc_cap);
+                        });
+}
+
+extern "C" int xhist_plan_execute_argextrema(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                                             int64_t n_cols, double* out_values, int64_t* out_index, int mem_kind, void* stream) {
+  return execute_values(p, "xhist_plan_execute_argextrema", samples, values, n_rows, n_cols, out_values, out_index != nullptr,
+                        "out_index is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
+                          return xhist_argextrema_run(pl, samples, values, n_rows, n_cols, out_values, out_index,
+                                                      static_cast<hipStream_t>(stream), err, err_cap, desc, desc_cap);
                         });
 }
 

@@ -6,6 +6,10 @@
 //   extrema_fast<ST, D, SCAN>    ST float / double, D 1 / 2, SCAN 1 / 2 / kScanArith          12
 //   extrema_generic<CMP, LDS>    CMP 0 / 1 / 3, slots in LDS or in global memory                6
 //   extrema_prepare, extrema_finalize                                                          2
+// and, for histogram_argextrema's second pass (18 + 2; its first pass is the kernels above):
+//   argext_fast<ST, D, SCAN>     as extrema_fast                                               12
+//   argext_generic<CMP, LDS>     as extrema_generic                                             6
+//   argext_prepare, argext_finalize                                                            2
 #include "xhist_extrema.hip.h"
 
 using namespace xhist;
@@ -33,6 +37,26 @@ __global__ void __launch_bounds__(256) extrema_finalize(uint64_t* kmin, uint64_t
     const uint64_t lo = kmin[i], hi = kmax[i];
     reinterpret_cast<double*>(kmin)[i] = lo == kEmptyMin64 ? nan : extrema_value64(lo);
     reinterpret_cast<double*>(kmax)[i] = hi == kEmptyMax64 ? nan : extrema_value64(hi);
+  }
+}
+
+// histogram_argextrema: the positions' two planes before pass 2 — no position yet
+__global__ void __launch_bounds__(256) argext_prepare(uint64_t* index, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) index[i] = kNoPosition;
+}
+
+// ... and after it: the keys of both planes -> doubles, the markers -> NaN; "no position" -> -1
+__global__ void __launch_bounds__(256) argext_finalize(uint64_t* kmin, uint64_t* kmax, uint64_t* index, int64_t n) {
+  const double nan = __builtin_nan("");
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t lo = kmin[i], hi = kmax[i];
+    reinterpret_cast<double*>(kmin)[i] = lo == kEmptyMin64 ? nan : extrema_value64(lo);
+    reinterpret_cast<double*>(kmax)[i] = hi == kEmptyMax64 ? nan : extrema_value64(hi);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const uint64_t at = index[k * n + i];
+      reinterpret_cast<int64_t*>(index)[k * n + i] = at == kNoPosition ? (int64_t)-1 : (int64_t)at;
+    }
   }
 }
 
@@ -78,5 +102,68 @@ int xhist_extrema_run(const ValuesPlan& pl, const xhist_array* samples, const xh
   }
   XH_VALUES_LAUNCH(extrema_finalize, dim3(grid_io), dim3(256), 0, stream, kmin, kmax, n_out);
   XH_VALUES_LAUNCH_CHECK("extrema_finalize launch");
+  return XHIST_OK;
+}
+
+// pass 2 of histogram_argextrema
+struct ArgextKernels {
+  template <typename ST, int D, int SCAN>
+  static auto fast() -> void (*)(const CovParams) { return argext_fast<ST, D, SCAN>; }
+  template <int CMP, bool LDS>
+  static auto generic() -> void (*)(const CovParams) { return argext_generic<CMP, LDS>; }
+};
+
+// pass 1: a bin's two keys; pass 2: the keys and the two positions.  The larger pass decides family and home for both, so
+// between the 16- and the 32-byte LDS capacity pass 1 runs where pass 2 must, not where histogram_extrema alone would.
+static constexpr ValuesSlots kArgextremaSlots = {{16, 32}, {8, 24}, false};
+
+int xhist_argextrema_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+                         double* out_values, int64_t* out_index, hipStream_t stream, char* err, size_t err_cap, char* desc,
+                         size_t desc_cap) {
+  const int64_t n_out = n_rows * pl.n_bins;
+  uint64_t* kmin = reinterpret_cast<uint64_t*>(out_values);
+  uint64_t* kmax = kmin + n_out;
+  uint64_t* index = reinterpret_cast<uint64_t*>(out_index);
+  const int grid_io = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_out + 255) / 256));
+  XH_VALUES_LAUNCH(extrema_prepare, dim3(grid_io), dim3(256), 0, stream, kmin, kmax, n_out, 0);
+  XH_VALUES_LAUNCH_CHECK("extrema_prepare launch");
+  XH_VALUES_LAUNCH(argext_prepare, dim3(grid_io), dim3(256), 0, stream, index, 2 * n_out);
+  XH_VALUES_LAUNCH_CHECK("argext_prepare launch");
+
+  if (n_cols > 0) {
+    const ValuesChoice c = choose_values(pl, kArgextremaSlots, samples, values, n_cols);
+    const values_fn pass1 = pick_values_kernel<ExtremaKernels>(c, pl);
+    const auto pass2 = pick_values_kernel<ArgextKernels>(c, pl);
+    if (!pass1 || !pass2) {
+      snprintf(err, err_cap, "internal: no argextrema kernel for this combination");
+      return XHIST_ERR_HIP;
+    }
+    const char* lds_what = "argextrema: setting the dynamic LDS size failed";
+    if (int rc = allow_values_lds(pass1, c.lds_bytes[0], lds_what, err, err_cap)) return rc;
+    if (int rc = allow_values_lds(pass2, c.lds_bytes[1], lds_what, err, err_cap)) return rc;
+    // Family and home are the larger pass's; the residency, hence the segments per row, is each pass's own.  Neither result
+    // depends on it, and pass 1's slots are half of pass 2's: with 50 x 50 bins it keeps three workgroups on a CU where pass
+    // 2 keeps one, and runs as fast as histogram_extrema alone (0.77 ms against 0.89 ms for 2e8 float64 pairs).
+    ValuesChoice c1 = c;
+    c1.lds_bytes[1] = 0;
+    const ValuesGeometry g1 = values_geometry(pl, c1, n_rows, n_cols), g = values_geometry(pl, c, n_rows, n_cols);
+    if (int rc = launch_values_pass(pass1, c.lds_bytes[0], "extrema launch", pl, c, g1, samples, values, n_rows, n_cols, kmin, kmax,
+                                    nullptr, stream, err, err_cap))
+      return rc;
+    if (int rc = launch_values_pass(pass2, c.lds_bytes[1], "argext launch", pl, c, g, samples, values, n_rows, n_cols, index,
+                                    index + n_out, kmin, stream, err, err_cap))
+      return rc;
+    if (desc && desc_cap) {
+      const char* fam = c.fast ? "fast" : "generic";
+      const char* home = c.lds ? "lds" : "global";
+      snprintf(desc, desc_cap,
+               "argextrema pass1=extrema_%s slots=%s pass2=argext_%s slots=%s scan=%d block=%d segs=%lld/%lld lds_bytes=%zu/%zu "
+               "tables_in_lds=%d D=%d cmp=%d",
+               fam, home, fam, home, c.scan, g.block, (long long)g1.segs, (long long)g.segs, c.lds_bytes[0], c.lds_bytes[1], (int)c.tables_in_lds,
+               pl.n_dims, values_cmp(pl));
+    }
+  }
+  XH_VALUES_LAUNCH(argext_finalize, dim3(grid_io), dim3(256), 0, stream, kmin, kmax, index, n_out);
+  XH_VALUES_LAUNCH_CHECK("argext_finalize launch");
   return XHIST_OK;
 }

@@ -166,6 +166,107 @@ __global__ void __launch_bounds__(256) extrema_fast(const Params p) {
   values_fast_body<ExtAcc<typename std::conditional<__is_same(ST, float), uint32_t, uint64_t>::type>, ST, D, SCAN>(p);
 }
 
+// ---------------------------------------------------------------------------------------------
+// histogram_argextrema: where a bin's minimum and maximum lie.  Two passes, because no atomic takes a (key, position) pair of
+// 128 bits.  Pass 1 is histogram_extrema's own (extrema_prepare and the binning kernels above) and leaves the keys of every
+// bin's extremes in the two value outputs.  Pass 2 streams the samples and values again: of the samples whose key EQUALS the
+// bin's minimum (maximum) key it keeps the smallest column index, a 64-bit unsigned minimum, so the answer is exact and does
+// not depend on the order of arrival.  A finalize turns the keys into doubles.
+//
+// A bin's slot in pass 2 is [kmin, kmax, imin, imax]: 32 bytes with 64-bit keys, 24 for the fast family on float32 values.
+// The keys are read-only there (init stages them from pass 1's output, which travels as w2_ptr with CovParams::plane between
+// the two key planes); a position starts as ~0, which every column index undercuts and which reads as -1 in the int64 output.
+//
+// Equality, then minimum — and read before you atomic again: a sample goes on only where its key equals one of the slot's two,
+// reads that position, and issues the atomic only where its own is smaller.  On unordered data almost no sample ties with an
+// extreme; on constant or boolean values every sample does, and then the read keeps all but the improving ones (the lowest
+// lanes of a workgroup's first tile) from the atomic unit.  A stale read is never wrong: positions only decrease.
+// ---------------------------------------------------------------------------------------------
+constexpr uint64_t kNoPosition = ~0ull;
+
+template <typename KT>
+struct ArgSlot {
+  KT kmin, kmax;
+  uint64_t imin, imax;
+};
+static_assert(sizeof(ArgSlot<uint64_t>) == 32 && sizeof(ArgSlot<uint32_t>) == 24, "the slot sizes the family rule is given");
+
+// pass 1's 64-bit key of an output bin, as the slot holds it: exact for the 32-bit keys, whose values were float32
+template <typename KT>
+__device__ __forceinline__ KT arg_narrow(uint64_t k);
+template <>
+__device__ __forceinline__ uint64_t arg_narrow<uint64_t>(uint64_t k) { return k; }
+template <>
+__device__ __forceinline__ uint32_t arg_narrow<uint32_t>(uint64_t k) {
+  if (k == kEmptyMin64) return kEmptyMin32;  // (the markers are no values; no sample's key equals one)
+  if (k == kEmptyMax64) return kEmptyMax32;
+  return extrema_key32((float)extrema_value64(k));
+}
+
+template <typename KT>
+struct ArgAcc {
+  using K = ExtKeys<KT>;
+  using slot_t = ArgSlot<KT>;
+  static constexpr bool kCopies = false;
+  static constexpr int kExtra = 0;
+  static constexpr bool kIndex = true;
+  static __device__ __forceinline__ void init(slot_t* slots, const CovParams& p, int64_t row) {
+    const uint64_t* kmin = reinterpret_cast<const uint64_t*>(p.w2_ptr) + row * p.n_bins;  // (the maximum keys: p.plane on)
+    for (uint32_t b = threadIdx.x; b < (uint32_t)p.n_bins; b += blockDim.x) {
+      slot_t e;
+      e.kmin = arg_narrow<KT>(kmin[b]);
+      e.kmax = arg_narrow<KT>(kmin[p.plane + b]);
+      e.imin = e.imax = kNoPosition;
+      slots[b] = e;
+    }
+  }
+  // min(*at, pos) where pos improves on a relaxed read of *at
+  static __device__ __forceinline__ void lds_lower(uint64_t* at, uint64_t pos) {
+    if (pos < __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
+      atomicMin(reinterpret_cast<unsigned long long*>(at), (unsigned long long)pos);
+  }
+  static __device__ __forceinline__ void global_lower(uint64_t* at, uint64_t pos) {
+    if (pos < __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+      atomicMin(reinterpret_cast<unsigned long long*>(at), (unsigned long long)pos);
+  }
+  template <typename V>
+  static __device__ __forceinline__ void lds_add(slot_t* slots, uint32_t bin, V v, uint64_t pos) {
+    const KT k = K::key(v);
+    slot_t* s = slots + bin;
+    const KT lo = s->kmin, hi = s->kmax;  // (nothing writes the keys during the pass)
+    if (k == lo) lds_lower(&s->imin, pos);
+    if (k == hi) lds_lower(&s->imax, pos);
+  }
+  // the positions of row `row`: minima at out, maxima at out2
+  static __device__ __forceinline__ void global_add(const CovParams& p, int64_t row, int64_t bin, double v, uint64_t pos) {
+    const uint64_t k = extrema_key64(v);
+    const uint64_t* keys = reinterpret_cast<const uint64_t*>(p.w2_ptr) + row * p.n_bins + bin;
+    if (k == keys[0]) global_lower(reinterpret_cast<uint64_t*>(p.out) + row * p.n_bins + bin, pos);
+    if (k == keys[p.plane]) global_lower(reinterpret_cast<uint64_t*>(p.out2) + row * p.n_bins + bin, pos);
+  }
+  // (a workgroup may have met a bin's minimum and not its maximum: each position on its own)
+  static __device__ __forceinline__ void flush(const slot_t* slots, const CovParams& p, int64_t row) {
+    uint64_t* imin = reinterpret_cast<uint64_t*>(p.out) + row * p.n_bins;
+    uint64_t* imax = reinterpret_cast<uint64_t*>(p.out2) + row * p.n_bins;
+    for (uint32_t b = threadIdx.x; b < (uint32_t)p.n_bins; b += blockDim.x) {
+      const uint64_t lo = slots[b].imin, hi = slots[b].imax;
+      if (lo != kNoPosition) global_lower(imin + b, lo);
+      if (hi != kNoPosition) global_lower(imax + b, hi);
+    }
+  }
+};
+
+// Pass 2's binning kernels, through the shared skeletons: argext_generic<CMP, LDS> (block 512), argext_fast<ST, D, SCAN>
+// (block 256).  They take CovParams for its plane stride and read no x_* stream.
+template <int CMP, bool LDS>
+__global__ void __launch_bounds__(512) argext_generic(const CovParams p) {
+  values_generic_body<ArgAcc<uint64_t>, CMP, LDS>(p);
+}
+template <typename ST, int D, int SCAN>
+__global__ void __launch_bounds__(256) argext_fast(const CovParams p) {
+  values_fast_body<ArgAcc<typename std::conditional<__is_same(ST, float), uint32_t, uint64_t>::type>, ST, D, SCAN>(p);
+}
+
 }  // namespace xhist
 
 // The three launches on `stream` (prepare, binning, finalize) for DEVICE arrays the caller has validated, n_rows and n_cols
@@ -174,3 +275,10 @@ __global__ void __launch_bounds__(256) extrema_fast(const Params p) {
 int xhist_extrema_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
                       double* out_min, double* out_max, int accumulate, hipStream_t stream, char* err, size_t err_cap, char* desc,
                       size_t desc_cap);
+
+// histogram_argextrema's launches on `stream` (the two prepares, pass 1, pass 2, finalize), under the same conditions.
+// out_values is [2, n_rows, n_bins] (minimum, maximum), out_index [2, n_rows, n_bins] int64 (their positions; -1: empty bin).
+// (Called by xhist_plan_execute_argextrema, xhist_capi.hip.)
+int xhist_argextrema_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+                         double* out_values, int64_t* out_index, hipStream_t stream, char* err, size_t err_cap, char* desc,
+                         size_t desc_cap);

@@ -1,4 +1,4 @@
-// xhist_values.hip.h — what the per-bin statistics of a value array share: histogram_extrema (xhist_extrema.hip.h), the
+// xhist_values.hip.h — what the per-bin statistics of a value array share: histogram_extrema and histogram_argextrema (xhist_extrema.hip.h), the
 // quantiles (xhist_quantile.hip.h) and the moments (xhist_moments.hip.h: histogram_mean_var, histogram_cov and their weighted
 // forms).  The one kernel skeleton per family, into which
 // a statistic plugs an accumulator policy, and the one host-side launcher: the family and LDS rule, the launch geometry, the
@@ -71,12 +71,21 @@ struct CovWParams : CovParams {
 // A policy of two extra streams (kExtra = 2; its kernels take CovWParams, the second value array at p.x_* and the weights at
 // p.y_*) takes both:
 //   lds_add(slots, i, a, b, w)  global_add(p, row, bin, a, b, w)
-// The skeletons choose the streams at compile time (if constexpr).
+// A policy that declares kIndex = true (only with kExtra = 0: histogram_argextrema's second pass, xhist_extrema.hip.h) is handed
+// the sample's column index inside its row as well, a uint64:
+//   lds_add(slots, i, v, col)  global_add(p, row, bin, v, col)
+// The skeletons choose the streams and the index at compile time (if constexpr).
 //
 // The bodies take the kernel's Params as `const Params& __restrict__`.  A body is optimised on its own before it is inlined
 // into its kernel, and without __restrict__ that step must assume the LDS and global atomics may write the Params: the
 // fast arithmetic-edge kernels then held up to 23 more VGPRs, and the generic ones spilled SGPRs to scratch.  With it the
 // body compiles as if written in the kernel, where Params is a private copy nothing else writes.
+
+// whether a policy asks for the sample's column index: its kIndex where it declares one, else no
+template <class Acc, class = void>
+struct acc_wants_index : std::false_type {};
+template <class Acc>
+struct acc_wants_index<Acc, std::void_t<decltype(Acc::kIndex)>> : std::integral_constant<bool, Acc::kIndex> {};
 
 // ---------------------------------------------------------------------------------------------
 // GENERIC family: any dtype per input and for the values, any element strides (broadcast and grouped rows), 1..8 inputs,
@@ -87,6 +96,8 @@ struct CovWParams : CovParams {
 template <class Acc, int CMP, bool LDS, class P>
 __device__ __forceinline__ void values_generic_body(const P& __restrict__ p) {
   constexpr bool W = Acc::kExtra >= 1, W2 = Acc::kExtra == 2;
+  constexpr bool IDX = acc_wants_index<Acc>::value;
+  static_assert(!IDX || !W, "the column index goes to policies without extra streams");
   static_assert(!W || std::is_base_of<WParams, P>::value, "a policy of an extra stream reads the x_* block of WParams");
   static_assert(!W2 || std::is_base_of<CovWParams, P>::value, "a policy of two extra streams reads the y_* block of CovWParams too");
   using CT = typename Dom<CMP>::T;
@@ -146,6 +157,9 @@ __device__ __forceinline__ void values_generic_body(const P& __restrict__ p) {
       const double w = load_as<double>(p.x_ptr, p.x_dt, xi);  // (only for a sample that counts)
       if (LDS) Acc::lds_add(slots, (uint32_t)flat, v, w);
       else Acc::global_add(p, row, flat, v, w);
+    } else if constexpr (IDX) {
+      if (LDS) Acc::lds_add(slots, (uint32_t)flat, v, (uint64_t)i);
+      else Acc::global_add(p, row, flat, v, (uint64_t)i);
     } else {
       if (LDS) Acc::lds_add(slots, (uint32_t)flat, v);  // (one copy of the slots: p.copies_log2 == 0)
       else Acc::global_add(p, row, flat, v);
@@ -176,6 +190,8 @@ constexpr int fast_halves(int tile_bytes, int limit, int unroll) {
 template <class Acc, typename ST, int D, int SCAN, class P>
 __device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
   constexpr bool W = Acc::kExtra >= 1, W2 = Acc::kExtra == 2;
+  constexpr bool IDX = acc_wants_index<Acc>::value;
+  static_assert(!IDX || !W, "the column index goes to policies without extra streams");
   static_assert(!W || std::is_base_of<WParams, P>::value, "a policy of an extra stream reads the x_* block of WParams");
   static_assert(!W2 || std::is_base_of<CovWParams, P>::value, "a policy of two extra streams reads the y_* block of CovWParams too");
   static_assert(__is_same(ST, double) || __is_same(ST, float), "float32 / float64 samples and values");
@@ -277,6 +293,10 @@ __device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
             if (ok) Acc::lds_add(slots, Acc::kCopies ? (flat << p.copies_log2) + mycopy : flat, val, (ST)wv[u][v], (ST)yv[u][v]);
           } else if constexpr (W) {
             if (ok) Acc::lds_add(slots, Acc::kCopies ? (flat << p.copies_log2) + mycopy : flat, val, (ST)wv[u][v]);
+          } else if constexpr (IDX) {
+            if (ok)
+              Acc::lds_add(slots, Acc::kCopies ? (flat << p.copies_log2) + mycopy : flat, val,
+                           (uint64_t)(base + ((int64_t)(h * UH + u) * blockDim.x + tid) * VEC + v));
           } else {
             if (ok) Acc::lds_add(slots, Acc::kCopies ? (flat << p.copies_log2) + mycopy : flat, val);
           }

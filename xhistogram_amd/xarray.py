@@ -14,7 +14,7 @@ from .core import histogram as _core_histogram
 from .core import histogram_two_weights as _core_histogram_two_weights
 
 __all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
-           "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt"]
+           "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt", "histogram_argextrema"]
 
 
 def _xr():
@@ -143,6 +143,37 @@ def histogram_extrema(*args, values, bins=None, range=None, dim=None, block_size
     xr = _xr()
     return (xr.DataArray(vmin, dims=out_dims, coords=coords, name="%s_min" % base),
             xr.DataArray(vmax, dims=out_dims, coords=coords, name="%s_max" % base))
+
+
+def histogram_argextrema(*args, values, bins=None, range=None, dim=None, block_size="auto", keep_coords=False, bin_dim_suffix="_bin"):
+    """Per-bin minimum and maximum of the DataArray ``values`` over the bins of ``args`` and where they lie
+    (:func:`xhistogram_amd.core.histogram_argextrema` with the labels of :func:`histogram`).
+
+    ``args``, ``bins``, ``range``, ``dim``, ``keep_coords``, ``bin_dim_suffix`` and ``values`` are those of
+    :func:`histogram_extrema`.  Returns a dict of DataArrays with the dims and coords ``histogram`` gives: ``<values name>_min``
+    and ``<values name>_max`` (float64), and for every reduced dim ``d`` ``<values name>_argmin_<d>`` and
+    ``<values name>_argmax_<d>``: the int64 index along ``d`` of the first sample that holds the bin's extreme (first in C
+    order over the reduced dims as the broadcast data orders them), ``-1`` in empty bins — what ``DataArray.isel`` takes.
+    The flat positions are unravelled on the host."""
+    from .core import histogram_argextrema as _core_histogram_argextrema
+
+    reduced = []
+    (amin, amax, vmin, vmax), out_dims, coords, base = _values_statistic(
+        "histogram_argextrema", _core_histogram_argextrema, args, values, bins, range, dim, keep_coords, bin_dim_suffix,
+        reduced=reduced, block_size=block_size)
+    xr = _xr()
+    out = {"%s_min" % base: xr.DataArray(vmin, dims=out_dims, coords=coords, name="%s_min" % base),
+           "%s_max" % base: xr.DataArray(vmax, dims=out_dims, coords=coords, name="%s_max" % base)}
+    for which, flat in (("argmin", amin), ("argmax", amax)):
+        if hasattr(flat, "detach"):
+            flat = flat.detach().cpu().numpy()
+        empty = flat < 0
+        stride = 1
+        for d, size in reduced[::-1]:  # (C order: the last reduced dim walks fastest)
+            name = "%s_%s_%s" % (base, which, d)
+            out[name] = xr.DataArray(np.where(empty, -1, (flat // stride) % size), dims=out_dims, coords=coords, name=name)
+            stride *= size
+    return out
 
 
 def histogram_mean_var(*args, values, bins=None, range=None, dim=None, ddof=0, block_size="auto", keep_coords=False,
@@ -290,10 +321,12 @@ def histogram_weighted_cov(*args, values, weights, bins=None, range=None, dim=No
     return {n: xr.DataArray(r, dims=out_dims, coords=coords, name=n) for n, r in zip(names, results)}
 
 
-def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords, bin_dim_suffix, weights=None, second=None, **kw):
+def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords, bin_dim_suffix, weights=None, second=None,
+                      reduced=None, **kw):
     """a per-bin statistic of ``values`` with the labels of :func:`histogram`: (core_fn's arrays, dims, coords, the values'
     name or "values").  ``weights`` (a DataArray or None) is lined up as ``values`` is and passed on as core_fn's weights; so is
-    ``second``, the second of a pair of values that comes with weights of its own, as core_fn's ``second``."""
+    ``second``, the second of a pair of values that comes with weights of its own, as core_fn's ``second``.  ``reduced`` (a
+    list, or None) receives the (name, broadcast size) of every reduced dim, in ascending axis number."""
     xr = _xr()
     data_args = list(args)
     n_data = len(data_args)
@@ -335,6 +368,8 @@ def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords
     else:
         kept_dims = []
         axis = None
+    if reduced is not None:
+        reduced.extend((d, max(int(a.sizes[d]) for a in lined_up)) for d in dims_order if d not in kept_dims)
     *results, edges = core_fn(*arrays, values=v_data, bins=bins, range=range, axis=axis, **kw)
     bin_dims = [a.name + bin_dim_suffix for a in operands[:n_data]]
     out_dims = kept_dims + bin_dims
