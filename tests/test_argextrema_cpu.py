@@ -161,7 +161,7 @@ def test_dask_with_a_chunked_reduced_axis_is_refused_before_any_compute(monkeypa
     monkeypatch.setattr(core, "_upload_host", lambda *a, **k: pytest.fail("device work"))
     arr = _Chunked((4, 6), ((2, 2), (3, 3)))
     monkeypatch.setattr(core, "_values_call", lambda *a, **k: ("dask", [arr, arr], None, [np.linspace(0, 1, 3)], [1], (1,)))
-    with pytest.raises(ValueError, match="rechunk the reduced axes"):
+    with pytest.raises(ValueError, match="positions of several chunks cannot be merged: rechunk the reduced axes"):
         core.histogram_argextrema(arr, values=arr, bins=[np.linspace(0, 1, 3)], axis=1)
 
 
@@ -176,11 +176,13 @@ def test_symbol_and_abi_version():
     assert callable(getattr(_native.Plan, "execute_argextrema"))
 
 
-def test_the_statistic_is_in_neither_stats_table():
-    for table in (core._VALUE_STATS, core._MOMENT4_STATS):
-        assert not any("arg" in name for name in table)
-        assert not any(st.method == "execute_argextrema" for st in table.values())
-    assert callable(core._argextrema_rows) and callable(core._argextrema_block)
+def test_the_statistic_is_an_entry_of_the_stats_table():
+    """(vmin, vmax, argmin, argmax): the two positions int64, the columns in ascending axis order, and no dask step, since
+    positions of several chunks are not merged"""
+    st = core._VALUE_STATS["argextrema"]
+    assert (st.k, st.ints, st.extras, st.method, st.ptrs) == (4, (2, 3), 0, "execute_argextrema", (0, 2))
+    assert st.ordered is True and st.reduce is None
+    assert [name for name, s in core._VALUE_STATS.items() if s.ordered] == ["argextrema"]
 
 
 xhx = importlib.import_module("xhistogram_amd.xarray")

@@ -184,35 +184,92 @@ def test_two_axes_merge_in_c_order(which):
 # the dask steps
 # ---------------------------------------------------------------------------------------------------------------------
 def _aggregates(monkeypatch):
-    """the `aggregate` objects histogram_mean_var (unweighted, weighted) and histogram_cov hand to dask, caught at _value_stat"""
+    """the `aggregate` objects that histogram_mean_var, histogram_cov and histogram_skew_kurt (unweighted, weighted) hand to
+    dask, caught at _value_stat"""
     caught = {}
 
-    def fake(stat, args, values, bins, range, axis, name, aggregate=None, weights=None):
+    def fake(stat, args, values, bins, range, axis, name, aggregate=None, *extras, weights=None, **params):
+        assert len(extras) + (weights is not None) == core._VALUE_STATS[stat].extras and not params
         caught[stat] = aggregate
         return "dask", [np.zeros(1)] * core._VALUE_STATS[stat].k, bins, ()
 
     monkeypatch.setattr(core, "_value_stat", fake)
     x, e = np.zeros(4), np.linspace(0, 1, 3)
-    core.histogram_mean_var(x, values=x, bins=e, ddof=1)
-    core.histogram_mean_var(x, values=x, bins=e, ddof=1, weights=x)
+    for w in (None, x):
+        core.histogram_mean_var(x, values=x, bins=e, ddof=1, weights=w)
+        core.histogram_skew_kurt(x, values=x, bins=e, ddof=1, bias=False, weights=w)
     core.histogram_cov(x, values=(x, x), bins=e, ddof=1)
-    assert sorted(caught) == ["cov", "mean_var", "mean_var_w"]
+    core.histogram_weighted_cov(x, values=(x, x), weights=x, bins=e, ddof=1)
+    assert sorted(caught) == ["cov", "cov_w", "mean_var", "mean_var_w", "skew_kurt", "skew_kurt_w"]
     return caught
+
+
+def _entry_partials(rng, stat, n_parts, empty):
+    """[k, parts, bins] partials shaped as the table entry's dask step takes them: (min, max) pairs for the one step that is no
+    moment merge, else Chan's (x, means..., one moment per pair) or, where the step has pairs=None, Pébay's (x, mean, M2, M3,
+    M4); x is a sum of weights where the step says a partial is present when x != 0"""
+    st = core._VALUE_STATS[stat]
+    if st.reduce is core._extrema_pair_reduce:
+        _, (lo,), (span,) = _partials(rng, n_parts, empty, 1, 1)
+        return np.stack([lo, lo + span])
+    assert st.reduce.func is core._moment_reduce
+    pairs = st.reduce.keywords.get("pairs", ((0, 0),))
+    n_means, n_moments = (1, 3) if pairs is None else (st.k - 1 - len(pairs), len(pairs))
+    x, means, moments = _partials(rng, n_parts, empty, n_means, n_moments, weighted=st.reduce.keywords["present"] is core._weighed)
+    return np.stack([x] + means + moments)
 
 
 def test_reduce_and_aggregate_objects_pickle(monkeypatch):
     rng = np.random.default_rng(5)
-    steps = {"reduce " + name: st.reduce for name, st in core._VALUE_STATS.items()}
+    steps = {"reduce " + name: st.reduce for name, st in core._VALUE_STATS.items() if st.reduce is not None}
+    assert sorted(steps) == ["reduce " + n for n in ("cov", "cov_w", "extrema", "mean_var", "mean_var_w", "skew_kurt", "skew_kurt_w")]
     steps.update(("aggregate " + name, f) for name, f in _aggregates(monkeypatch).items())
-    assert len(steps) == len(core._VALUE_STATS) + 3
+    assert len(steps) == 7 + 6
     for name, f in steps.items():
         g = pickle.loads(pickle.dumps(f))
-        k = core._VALUE_STATS[name.split()[1]].k
-        x, means, moments = _partials(rng, 4, (2,), {2: 1, 3: 1, 6: 2}[k], {2: 0, 3: 1, 6: 3}[k])
-        block = np.stack([x] + means + moments)[:, :, None, :]  # [k, parts, a kept axis, bins]
+        stat = name.split()[1]
+        block = _entry_partials(rng, stat, 4, (2,))[:, :, None, :]  # [k, parts, a kept axis, bins]
         a, b = f(block, axis=(1,), keepdims=False), g(block, axis=(1,), keepdims=False)
-        assert a.shape == (k, 1, N_BINS), name
+        assert a.shape == (core._VALUE_STATS[stat].k, 1, N_BINS), name
         _same_bits(a, b)
+
+
+# the public merge of each entry that has a dask step, and where each of its results lies in the library's order of outputs
+COMBINE = {
+    "extrema": (core.combine_extrema, (0, 1)),
+    "mean_var": (core.combine_mean_var, (0, 1, 2)),
+    "mean_var_w": (core.combine_weighted_mean_var, (0, 1, 2)),
+    "cov": (core.combine_cov, (0, 1, 2, 3, 5, 4)),
+    "cov_w": (core.combine_weighted_cov, (0, 1, 2, 3, 5, 4)),
+    "skew_kurt": (core.combine_skew_kurt, (0, 1, 2, 3, 4)),
+    "skew_kurt_w": (core.combine_weighted_skew_kurt, (0, 1, 2, 3, 4)),
+}
+
+
+@pytest.mark.parametrize("stat", sorted(core._VALUE_STATS))
+def test_every_table_entry_is_wired_and_its_step_is_the_public_merge(stat):
+    from xhistogram_amd import _native
+
+    st = core._VALUE_STATS[stat]
+    assert callable(getattr(_native.Plan, st.method))
+    k = st.k if st.k is not None else 3  # (one output per element of q: any number of them)
+    assert (st.k is None) == ("q" in st.tail) and set(st.tail) <= {"q", "code"}
+    assert st.ptrs and st.ptrs[0] == 0 and list(st.ptrs) == sorted(set(st.ptrs)) and st.ptrs[-1] < k
+    assert all(0 <= i < k for i in st.ints) and st.extras in (0, 1, 2)
+    back = pickle.loads(pickle.dumps(st))
+    assert back[:5] == st[:5] and back[6:] == st[6:] and (back.reduce is None) == (st.reduce is None)
+    if st.reduce is None:
+        assert stat not in COMBINE and st.noun
+        return
+    combine, order = COMBINE[stat]
+    block = _entry_partials(np.random.default_rng(sorted(core._VALUE_STATS).index(stat)), stat, 2, ())
+    for step in (st.reduce, back.reduce):
+        out = step(block, axis=(1,), keepdims=True)
+        assert out.shape == (k, 1, N_BINS) and out.dtype == np.float64
+        want = combine(*[block[i] for i in order], axis=0)
+        assert len(want) == k
+        for i, w in zip(order, want):
+            _same_bits(out[i], w)
 
 
 def test_cov_step_keeps_the_library_order(monkeypatch):

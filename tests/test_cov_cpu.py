@@ -303,7 +303,7 @@ def test_argument_errors_come_before_any_device_work():
         core.histogram_cov(x, values=(x, x), bins=e, weights=x)  # no weighted form
     assert "histogram_cov" in core.__all__
     st = core._VALUE_STATS["cov"]
-    assert (st.k, st.counted, st.weighted, st.method) == (6, True, True, "execute_cov")
+    assert (st.k, st.ints, st.extras, st.method, st.ptrs) == (6, (0,), 1, "execute_cov", (0, 1, 3))
 
 
 def test_symbol_and_abi_version():

@@ -286,7 +286,7 @@ def test_combine_weighted_cov_nan_and_zero_partials():
     np.testing.assert_array_equal(got[3][0], [0.5 + 0.5 + 4.0 * 2 * 2 / 4, 2.0, nan, nan])
     np.testing.assert_array_equal(got[5][0], [-0.5 - 0.5 + 4.0 * 2 * 2 / 4, -2.0, nan, nan])
     assert pickle.loads(pickle.dumps(core._cov_w_reduce)).keywords == core._cov_w_reduce.keywords
-    assert core._cov_w_reduce.func is core._chan_reduce and core._cov_w_reduce.keywords["present"] is core._weighed
+    assert core._cov_w_reduce.func is core._moment_reduce and core._cov_w_reduce.keywords["present"] is core._weighed
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -318,9 +318,9 @@ def test_argument_errors_come_before_any_device_work():
         f(values=(x, x), weights=x, bins=e)  # no samples
     assert "histogram_weighted_cov" in core.__all__ and "combine_weighted_cov" in core.__all__
     st = core._VALUE_STATS["cov_w"]
-    assert (st.k, st.counted, int(st.weighted), st.method, st.ptrs) == (6, False, 2, "execute_cov_weighted", (0, 1, 3))
+    assert (st.k, st.ints, st.extras, st.method, st.ptrs) == (6, (), 2, "execute_cov_weighted", (0, 1, 3))
     st = core._VALUE_STATS["cov"]  # (as tests/test_cov_cpu.py asserts it)
-    assert (st.k, st.counted, st.weighted, st.method) == (6, True, True, "execute_cov")
+    assert (st.k, st.ints, st.extras, st.method, st.ptrs) == (6, (0,), 1, "execute_cov", (0, 1, 3))
     assert "histogram_weighted_cov" in core.histogram_cov.__doc__ and "is not provided" not in core.histogram_cov.__doc__
 
 

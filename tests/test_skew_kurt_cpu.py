@@ -332,7 +332,7 @@ def _partials(rng, n_parts, weighted, empty=()):
 
 
 def _merge_err(parts, present):
-    """core._pebay_merge restated per bin on skew_kurt_exact.Err scalars, in its order of operations: val is what core must
+    """core._pebay_update, as core._merge_partials walks it, restated per bin on skew_kurt_exact.Err scalars, in its order of operations: val is what core must
     give bit for bit; err bounds the distance of the exact merge of the exact partials (each within u of its float64) from
     val, the roundings of every step included"""
     n_parts, n_bins = parts.shape[1:]
@@ -419,7 +419,7 @@ def test_combine_nan_and_zero_partials():
     np.testing.assert_array_equal(cnt[0][0], [4.0, 3.0, 1.0, 0.0])
     np.testing.assert_array_equal(cnt[1][0], [2.0, 5.0, 1.0, nan])
     for f in (core._skew_kurt_reduce, core._skew_kurt_w_reduce):
-        assert pickle.loads(pickle.dumps(f)).keywords == f.keywords and f.func is core._pebay_reduce
+        assert pickle.loads(pickle.dumps(f)).keywords == f.keywords and f.func is core._moment_reduce
     assert core._skew_kurt_w_reduce.keywords["present"] is core._weighed and core._skew_kurt_reduce.keywords["present"] is core._counted
 
 
@@ -452,11 +452,10 @@ def test_argument_errors_come_before_any_device_work():
         f(values=x, bins=e)  # no samples
     for name in ("histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt"):
         assert name in core.__all__
-    st = core._stat_of("skew_kurt")
-    assert (st.k, st.counted, int(st.weighted), st.method, st.ptrs) == (5, True, 0, "execute_skew_kurt", (0, 1, 2))
-    st = core._stat_of("skew_kurt_w")
-    assert (st.k, st.counted, int(st.weighted), st.method, st.ptrs) == (5, False, 1, "execute_skew_kurt_weighted", (0, 1, 2))
-    assert "skew_kurt" not in core._VALUE_STATS  # (that table's walkers take Chan's blocks: these merge by Pébay's update)
+    st = core._VALUE_STATS["skew_kurt"]
+    assert (st.k, st.ints, st.extras, st.method, st.ptrs) == (5, (0,), 0, "execute_skew_kurt", (0, 1, 2))
+    st = core._VALUE_STATS["skew_kurt_w"]
+    assert (st.k, st.ints, st.extras, st.method, st.ptrs) == (5, (), 1, "execute_skew_kurt_weighted", (0, 1, 2))
     doc = f.__doc__
     assert "histogram_mean_var" in doc and "scipy keeps the biased value" in doc and "block_size" in doc
 

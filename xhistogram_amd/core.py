@@ -1847,50 +1847,59 @@ def _value_views(args, values, axis, bins, backend, *extras, ordered=False):
     return plan, nv, views, m, c, kept_axes_shape, device, stream
 
 
-# What the shared paths need of a per-bin statistic of values: its number of outputs (the first an int64 count when
-# `counted`, all others float64), the Plan method that fills them from output pointers, the dask step that merges the
-# partials of blocks that share output rows, how many arrays it reads after the values (1: weights, or histogram_cov's second
-# value array; 2: histogram_weighted_cov's second value array and weights), and, where the Plan method takes blocks of several outputs, the outputs whose pointers it is given.
-_ValueStat = namedtuple("_ValueStat", "k counted method reduce weighted ptrs", defaults=(False, None))
+# What the one path below (_value_rows, _value_block, _value_stat) needs of a per-bin statistic of values, an entry of
+# _VALUE_STATS:
+#   k        the number of outputs, each [rows, bins]; None: one per element of the call's `q`
+#   ints     the outputs that are int64 (all others are float64)
+#   method   the Plan method that fills them
+#   ptrs     the outputs whose pointers the method is given: the outputs are contiguous, in order, so a pointer may stand for
+#            a block of several
+#   extras   how many arrays it reads after the values (weights; a second value array; a second value array, then weights)
+#   reduce   the dask step that merges the partials of blocks that share output rows.  None: they cannot be merged, and every
+#            reduced axis must be one chunk
+#   tail     the names of the per-call parameters the method takes after the pointers
+#   ordered  whether it reports positions inside the row (_value_views, ordered)
+#   noun     what the refusal of several chunks calls the partials that cannot be merged
+_ValueStat = namedtuple("_ValueStat", "k ints method ptrs extras reduce tail ordered noun", defaults=((), False, None))
 
 
-def _value_stat_rows(stat, args, values, axis, bins, backend, *extras):
-    """the statistic's outputs of broadcast torch tensors or DeviceArrays: kept axes in place, reduced axes of extent 1, then
-    the bin axes"""
-    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, *extras)
+def _value_rows(st, args, values, axis, bins, backend, *extras, **params):
+    """the statistic's outputs of broadcast torch tensors (torch out) or DeviceArrays (numpy out) as one float64 block
+    [k, kept axes (reduced ones of extent 1), bins...], its int64 outputs as the bits they are"""
+    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, *extras, ordered=st.ordered)
     n = m * plan.n_bins
-    k, counted = stat.k, int(stat.counted)
+    k = st.k or len(params["q"])
+    shape = (k,) + kept_axes_shape + plan.bins_shape
     if backend == "torch":
         torch = _torch()
-        cnt = [torch.empty(n, dtype=torch.int64, device=args[0].device)] if counted else []
-        out = torch.empty((k - counted, n), dtype=torch.float64, device=args[0].device)
-        ptrs = [t.data_ptr() for t in cnt] + [out.data_ptr() + i * n * 8 for i in _range(k - counted)]
+        out = torch.empty(shape, dtype=torch.float64, device=args[0].device)
     else:
-        buf = _native.DeviceBuffer(device, max(k * n, 1) * 8)
-        ptrs = [buf.ptr + i * n * 8 for i in _range(k)]
-    if n > 0:
-        given = ptrs if stat.ptrs is None else [ptrs[i] for i in stat.ptrs]  # (the outputs are contiguous, in order)
-        getattr(plan, stat.method)(nv[:len(args)], *nv[len(args):], m, c, *given, stream=stream)
-    if backend != "torch":
-        host = np.empty((k, n), np.float64)
-        if n > 0:
-            buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
-        cnt, out = [host[0].view(np.int64)] if counted else [], host[counted:]
-    shape = kept_axes_shape + plan.bins_shape
-    return [a.reshape(shape) for a in cnt + list(out)]
+        out = np.empty(shape, np.float64)
+    if k * n > 0:
+        buf = None if backend == "torch" else _native.DeviceBuffer(device, k * n * 8)
+        base = out.data_ptr() if buf is None else buf.ptr
+        getattr(plan, st.method)(nv[:len(args)], *nv[len(args):], m, c, *[base + i * n * 8 for i in st.ptrs],
+                                 *[params[p] for p in st.tail], stream=stream)
+        if buf is not None:
+            buf.download(out)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+    return out
 
 
-def _value_stat_block(*all_arrays, stat=None, axis=None, bins=None):
-    """one dask block: its statistic as a [k, block axes (reduced ones of extent 1), bins...] float64 numpy array"""
-    st = _stat_of(stat)
-    n = len(all_arrays) - 1 - int(st.weighted)  # (samples..., values[, weights or second values[, weights]])
+def _value_block(*all_arrays, stat=None, axis=None, bins=None, **params):
+    """one dask block (samples..., values, the statistic's extras): its outputs as _value_rows gives them.  Counts that the
+    dask step merges become float64 by value; int64 outputs that are never merged stay the bits they are."""
+    st = _VALUE_STATS[stat]
+    n = len(all_arrays) - 1 - st.extras
     arrays = _upload_host(all_arrays[:n], all_arrays[n], bins, *all_arrays[n + 1:])
-    outs = _value_stat_rows(st, arrays[:n], arrays[n], axis, bins, "device", *arrays[n + 1:])
-    return np.stack([a.astype(np.float64, copy=False) for a in outs])
+    out = _value_rows(st, arrays[:n], arrays[n], axis, bins, "device", *arrays[n + 1:], **params)
+    if st.reduce is not None:
+        for i in st.ints:
+            out[i] = out[i].view(np.int64)
+    return out
 
 
 def _resident(backend, raw, all_arrays, n_inputs, bins):
-    """the arrays a rows function takes, and the backend it takes them as: numpy inputs (`raw`) uploaded to the calling thread's
+    """the arrays _value_rows takes, and the backend it takes them as: numpy inputs (`raw`) uploaded to the calling thread's
     GPU ("device"), torch tensors and DeviceArrays as they are"""
     if backend == "numpy":
         return _upload_host(raw[:n_inputs], raw[n_inputs], bins, *raw[n_inputs + 1:]), "device"
@@ -1898,30 +1907,45 @@ def _resident(backend, raw, all_arrays, n_inputs, bins):
 
 
 def _drop_axes(a, axes, backend):
-    """a rows function's output without its reduced axes (of extent 1)"""
+    """_value_rows' output without its reduced axes (of extent 1)"""
     if backend == "torch":
         return a.reshape([s for i, s in enumerate(a.shape) if i not in axes])
     return a.squeeze(axes)
 
 
-def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, weights=None, fourth=None):
-    """the backends of a per-bin statistic of values: (backend, the outputs with the shape ``histogram`` gives, bin edges,
-    reduced axes).  dask: lazy float64 arrays, the partials merged by stat.reduce and the last step by `aggregate`.  `weights`
-    is the array behind the values, _values_call's `third` (the keyword is the one tests/test_chan_merge_cpu.py catches this
-    function with): the weights, or the second of a pair of values, whose weights are then `fourth`."""
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, weights, fourth)
+def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, *extras, weights=None, **params):
+    """the backends of the per-bin statistic _VALUE_STATS[stat] of values: (backend, the outputs with the shape ``histogram``
+    gives, bin edges, reduced axes).  `extras` are the arrays it reads after the values, in its order, `weights` (None: not
+    given) the last of them, and `params` its per-call parameters.  The outputs are a list of k arrays; the quantiles stay one
+    array behind their q axis.  dask: lazy arrays, the partials merged by the statistic's dask step and the last step by
+    `aggregate`."""
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, *extras, weights)
     n_inputs = len(args)
-    st = _stat_of(stat)
+    st = _VALUE_STATS[stat]
+    k = st.k or len(params["q"])
+    merged = backend == "dask" and st.reduce is not None
     if backend == "dask":
-        import dask.array as dsa
+        if not merged and any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
+            raise ValueError("%s of several chunks cannot be merged: rechunk the reduced axes of every input into "
+                             "one chunk (e.g. arr.rechunk({axis: -1}))" % st.noun)
+        res = _values_blockwise(partial(_value_block, stat=stat, **params), k, all_arrays, bins, axis, drop_axes)
+        if merged:
+            import dask.array as dsa
 
-        partials = _values_blockwise(partial(_value_stat_block, stat=stat), st.k, all_arrays, bins, axis, drop_axes)
-        res = dsa.reduction(partials, st.reduce, aggregate or st.reduce, combine=st.reduce, axis=tuple(ax + 1 for ax in drop_axes),
-                            keepdims=False, dtype=np.float64, concatenate=True, meta=np.array((), np.float64))
-        return backend, [res[i] for i in _range(st.k)], bins, drop_axes
-    arrays, on = _resident(backend, raw, all_arrays, n_inputs, bins)
-    outs = _value_stat_rows(st, arrays[:n_inputs], arrays[n_inputs], axis, bins, on, *arrays[n_inputs + 1:])
-    return backend, [_drop_axes(a, drop_axes, backend) for a in outs], bins, drop_axes
+            res = dsa.reduction(res, st.reduce, aggregate or st.reduce, combine=st.reduce,
+                                axis=tuple(ax + 1 for ax in drop_axes), keepdims=False, dtype=np.float64, concatenate=True,
+                                meta=np.array((), np.float64))
+        else:
+            res = res[(slice(None),) + tuple(0 if i in drop_axes else slice(None) for i in _range(all_arrays[0].ndim))]
+    else:
+        arrays, on = _resident(backend, raw, all_arrays, n_inputs, bins)
+        res = _value_rows(st, arrays[:n_inputs], arrays[n_inputs], axis, bins, on, *arrays[n_inputs + 1:], **params)
+        res = _drop_axes(res, tuple(a + 1 for a in drop_axes), backend)
+    if st.k is not None:
+        res = list(res.unbind(0) if backend == "torch" else res)
+        for i in st.ints:  # (counts that the dask step merged come back by value, every other int64 output as the bits it is)
+            res[i] = res[i].astype(np.int64) if merged else res[i].view(_torch().int64 if backend == "torch" else np.int64)
+    return backend, res, bins, drop_axes
 
 
 def histogram_extrema(*args, values, bins=None, range=None, axis=None, block_size="auto"):
@@ -1941,37 +1965,6 @@ def histogram_extrema(*args, values, bins=None, range=None, axis=None, block_siz
     # in the key-ordered combine on the host (also under XHIST_AMD_DASK_EXCHANGE=rccl: the exchange adds only)
     _, (vmin, vmax), bins, _ = _value_stat("extrema", args, values, bins, range, axis, "histogram_extrema")
     return vmin, vmax, bins
-
-
-def _argextrema_rows(args, values, axis, bins, backend):
-    """(positions, values) of broadcast torch tensors (torch out) or DeviceArrays (numpy out): int64 and float64
-    [2 (min, max), kept axes (reduced ones of extent 1), bins...].  A position is the column of the row the library saw, and
-    those columns are the reduced axes in ascending axis number (_value_views, ordered)."""
-    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, ordered=True)
-    n = m * plan.n_bins
-    shape = (2,) + kept_axes_shape + plan.bins_shape
-    if backend == "torch":
-        torch = _torch()
-        vals = torch.empty(shape, dtype=torch.float64, device=args[0].device)
-        idx = torch.empty(shape, dtype=torch.int64, device=args[0].device)
-        if n > 0:
-            plan.execute_argextrema(nv[:-1], nv[-1], m, c, vals.data_ptr(), idx.data_ptr(), stream=stream)
-        return idx, vals
-    host = np.empty((4, n), np.float64)  # (the positions come down as the int64 bits they are; no arithmetic touches them)
-    if n > 0:
-        buf = _native.DeviceBuffer(device, 4 * n * 8)
-        plan.execute_argextrema(nv[:-1], nv[-1], m, c, buf.ptr, buf.ptr + 2 * n * 8, stream=stream)
-        buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
-    return host[2:].view(np.int64).reshape(shape), host[:2].reshape(shape)
-
-
-def _argextrema_block(*all_arrays, axis=None, bins=None):
-    """one dask block (samples..., values), complete along the reduced axes: [4 (vmin, vmax, argmin, argmax), block axes
-    (reduced ones of extent 1), bins...] float64, the two positions as int64 bits"""
-    n = len(all_arrays) - 1
-    arrays = _upload_host(all_arrays[:n], all_arrays[n], bins)
-    idx, vals = _argextrema_rows(arrays[:n], arrays[n], axis, bins, "device")
-    return np.concatenate([vals, idx.view(np.float64)])
 
 
 def histogram_argextrema(*args, values, bins=None, range=None, axis=None, block_size="auto"):
@@ -1995,35 +1988,22 @@ def histogram_argextrema(*args, values, bins=None, range=None, axis=None, block_
     bin axes).  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the current stream),
     DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block: every reduced axis must then be a single
     chunk (positions of several chunks are not merged)."""
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_argextrema")
-    n_inputs = len(args)
-    if backend == "dask":
-        for a in all_arrays:
-            if any(len(a.chunks[ax]) > 1 for ax in drop_axes):
-                raise ValueError("exact quantiles of several chunks cannot be merged: rechunk the reduced axes of every input into "
-                                 "one chunk (e.g. arr.rechunk({axis: -1}))")
-        res = _values_blockwise(_argextrema_block, 4, all_arrays, bins, axis, drop_axes)
-        res = res[(slice(None),) + tuple(0 if i in drop_axes else slice(None) for i in _range(all_arrays[0].ndim))]
-        idx = res[2:].view(np.int64)
-        return idx[0], idx[1], res[0], res[1], bins
-    arrays, on = _resident(backend, raw, all_arrays, n_inputs, bins)
-    idx, vals = _argextrema_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, on)
-    drop = tuple(a + 1 for a in drop_axes)
-    idx, vals = _drop_axes(idx, drop, backend), _drop_axes(vals, drop, backend)
-    return idx[0], idx[1], vals[0], vals[1], bins
+    # one block of four outputs, (vmin, vmax, argmin, argmax): a position is the column of the row the library saw, and those
+    # columns are the reduced axes in ascending axis number (the entry is `ordered`)
+    _, (vmin, vmax, amin, amax), bins, _ = _value_stat("argextrema", args, values, bins, range, axis, "histogram_argextrema")
+    return amin, amax, vmin, vmax, bins
 
 
-def _values_call(args, values, bins, range, axis, name, third=None, fourth=None):
+def _values_call(args, values, bins, range, axis, name, *extras):
     """the front of a per-bin statistic of values: argument checks before any device work, the backend, the broadcast
-    arrays (samples..., values[, third[, fourth]]: `third` is the weights, or the second of a pair of values; `fourth`, the
-    weights of a pair of values, comes only with `third`), the numpy originals (numpy backend), the edges of the unweighted histogram, the
-    normalised axis and the reduced axes"""
+    arrays (samples..., values, extras...: the arrays the statistic reads after the values, in its order; None: not given),
+    the numpy originals (numpy backend), the edges of the unweighted histogram, the normalised axis and the reduced axes"""
     if values is None:
         raise TypeError("%s needs values" % name)
     if not args:
         raise TypeError("%s needs at least one array of samples" % name)
     _check_values_dtype(values, name)
-    extras = [x for x in (third, fourth) if x is not None]
+    extras = [x for x in extras if x is not None]
     for x in extras:
         _check_values_dtype(x, name)
     n_inputs = len(args)
@@ -2095,40 +2075,6 @@ def _check_ddof(ddof):
     return int(ddof)
 
 
-def _chan_merge(x, means, moments, pairs, axis, present):
-    """Chan's pairwise merge of partial (x, means..., moments...) results over `axis` (kept as axes of extent 1), one partial
-    after another in index order (C order over several axes); x is the count or the sum of weights, present(x) says where a
-    partial (or the running result) holds something, and pairs[m] = (i, j) names the two means whose deviations multiply into
-    moment m's cross term ((0, 0): the M2 of mean 0).  Returns float64 (x, [means], [moments])."""
-    x, *rest = (np.asarray(a, np.float64) for a in [x] + list(means) + list(moments))
-    ax = tuple(sorted(int(a) % x.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
-    kept = [i for i in _range(x.ndim) if i not in ax]
-    keep_shape = tuple(1 if i in ax else x.shape[i] for i in _range(x.ndim))
-
-    def lead(a):
-        a = np.transpose(a, ax + tuple(kept))
-        return a.reshape((-1,) + a.shape[len(ax):])
-
-    x, rest = lead(x), [lead(a) for a in rest]
-    means, moments = rest[:len(means)], rest[len(means):]
-    cx = np.zeros(x.shape[1:])
-    cm = [np.full(x.shape[1:], np.nan) for _ in means]
-    cq = [np.full(x.shape[1:], np.nan) for _ in moments]
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        for k in _range(x.shape[0]):
-            xb = x[k]
-            take = present(xb)
-            first = take & ~present(cx)
-            both = take & present(cx)
-            tot = cx + xb
-            d = [m[k] - c for m, c in zip(means, cm)]
-            q_new = [c + q[k] + d[i] * d[j] * cx * xb / tot for c, q, (i, j) in zip(cq, moments, pairs)]
-            cm = [np.where(first, m[k], np.where(both, c + di * xb / tot, c)) for m, c, di in zip(means, cm, d)]
-            cq = [np.where(first, q[k], np.where(both, new, c)) for q, new, c in zip(moments, q_new, cq)]
-            cx = np.where(take, tot, cx)
-    return cx.reshape(keep_shape), [a.reshape(keep_shape) for a in cm], [a.reshape(keep_shape) for a in cq]
-
-
 def _counted(x):
     """where a partial holds something: a count above 0"""
     return x > 0
@@ -2139,14 +2085,58 @@ def _weighed(x):
     return x != 0
 
 
+def _merge_partials(update, present, x, rest, axis):
+    """The pairwise merge of partial (x, rest...) results over `axis` (kept as axes of extent 1), one partial after another in
+    index order (C order over several axes); x is the count or the sum of weights and present(x) says where a partial (or the
+    running result) holds something.  Where only the partial does, it is taken as it is; where both do, the running values of
+    `rest` become update(cx, xb, tot, running, partial's), with cx and xb the x of the two and tot their sum.  Returns the
+    float64 list [x, rest...]."""
+    x, *rest = (np.asarray(a, np.float64) for a in [x] + list(rest))
+    ax = tuple(sorted(int(a) % x.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
+    kept = [i for i in _range(x.ndim) if i not in ax]
+    keep_shape = tuple(1 if i in ax else x.shape[i] for i in _range(x.ndim))
+
+    def lead(a):
+        a = np.transpose(a, ax + tuple(kept))
+        return a.reshape((-1,) + a.shape[len(ax):])
+
+    x, rest = lead(x), [lead(a) for a in rest]
+    cx = np.zeros(x.shape[1:])
+    cur = [np.full(x.shape[1:], np.nan) for _ in rest]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for k in _range(x.shape[0]):
+            xb, part = x[k], [a[k] for a in rest]
+            take = present(xb)
+            first = take & ~present(cx)
+            both = take & present(cx)
+            tot = cx + xb
+            new = update(cx, xb, tot, cur, part)
+            cur = [np.where(first, p, np.where(both, n, c)) for p, n, c in zip(part, new, cur)]
+            cx = np.where(take, tot, cx)
+    return [a.reshape(keep_shape) for a in [cx] + cur]
+
+
+def _chan_update(cx, xb, tot, cur, part, pairs=((0, 0),)):
+    """Chan's update of running (means..., moments...): pairs[m] = (i, j) names the two means whose deviations multiply into
+    moment m's cross term ((0, 0): the M2 of mean 0), so the means are all but the last len(pairs)"""
+    n_means = len(cur) - len(pairs)
+    d = [m - c for m, c in zip(part[:n_means], cur)]
+    return ([c + di * xb / tot for c, di in zip(cur, d)]
+            + [c + q + d[i] * d[j] * cx * xb / tot for c, q, (i, j) in zip(cur[n_means:], part[n_means:], pairs)])
+
+
+# combine_cov's order of moments (M2_a, M2_b, C_ab), and the order of the library's outputs (M2_a, C_ab, M2_b)
+_COV_PAIRS = ((0, 0), (1, 1), (0, 1))
+_COV_BLOCK_PAIRS = ((0, 0), (0, 1), (1, 1))
+
+
 def combine_mean_var(n, mean, m2, axis):
     """Merge partial (count, mean, M2) results over `axis` (kept as axes of extent 1) with Chan's pairwise formula, one
     partial after another in index order (C order over several axes):
         n = na + nb,  d = mb - ma,  mean = ma + d * nb / n,  M2 = M2a + M2b + d^2 * na * nb / n.
     Partials with n == 0 are skipped; where every partial is empty, mean and M2 are NaN and n is 0.  The reduction of dask's
     partials.  Returns float64 (n, mean, M2)."""
-    n, (mean,), (m2,) = _chan_merge(n, [mean], [m2], [(0, 0)], axis, _counted)
-    return n, mean, m2
+    return tuple(_merge_partials(_chan_update, _counted, n, [mean, m2], axis))
 
 
 def combine_weighted_mean_var(w, mean, m2, axis):
@@ -2155,8 +2145,7 @@ def combine_weighted_mean_var(w, mean, m2, axis):
         W = Wa + Wb,  d = mb - ma,  mean = ma + d * Wb / W,  M2 = M2a + M2b + d^2 * Wa * Wb / W.
     Partials with W == 0 are skipped; a NaN partial (a NaN W among them) makes the bin NaN.  Where every partial has W == 0,
     mean and M2 are NaN and W is 0.  The reduction of dask's weighted partials.  Returns float64 (W, mean, M2)."""
-    w, (mean,), (m2,) = _chan_merge(w, [mean], [m2], [(0, 0)], axis, _weighed)
-    return w, mean, m2
+    return tuple(_merge_partials(_chan_update, _weighed, w, [mean, m2], axis))
 
 
 def _var_of(x, m2, ddof):
@@ -2166,29 +2155,6 @@ def _var_of(x, m2, ddof):
         return torch.where(x > ddof, m2 / (x - ddof).to(torch.float64), torch.full_like(m2, float("nan")))
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(x > ddof, m2 / (x - ddof), np.nan)
-
-
-def _chan_reduce(x, axis=None, keepdims=True, ddof=None, present=_counted, pairs=((0, 0),), **_):
-    """dask.array.reduction step over stacked blocks of partials in the order the library emits them: x, the means, then the
-    moments, `pairs` naming each moment's means as _chan_merge reads them (so their number is that of the means, 1 + the
-    largest index).  With ddof, the last step: the moments divided by x - ddof, here only."""
-    ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
-    n_means = 1 + max(max(p) for p in pairs)
-    cx, cm, cq = _chan_merge(x[0], x[1:1 + n_means], x[1 + n_means:], pairs, tuple(a - 1 for a in ax), present)
-    out = np.stack([cx] + cm + cq)
-    out = out if keepdims else out.squeeze(ax)
-    if ddof is not None:
-        for i in _range(1 + n_means, len(out)):
-            out[i] = _var_of(out[0], out[i], ddof)
-    return out
-
-
-# the steps of (n, mean, M2) and of weighted (W, mean, M2) blocks; an aggregate is the last step, (x, mean, var).  Partials of a
-# module-level function, so that dask can pickle them.
-_mean_var_reduce = partial(_chan_reduce, present=_counted)
-_mean_var_aggregate = partial(_chan_reduce, present=_counted, ddof=0)
-_mean_var_w_reduce = partial(_chan_reduce, present=_weighed)
-_mean_var_w_aggregate = partial(_chan_reduce, present=_weighed, ddof=0)
 
 
 def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, weights=None, block_size="auto"):
@@ -2228,14 +2194,32 @@ def histogram_mean_var(*args, values, bins=None, range=None, axis=None, ddof=0, 
     stat, aggregate = ("mean_var", _mean_var_aggregate) if weights is None else ("mean_var_w", _mean_var_w_aggregate)
     backend, (x, mean, m2), bins, _ = _value_stat(stat, args, values, bins, range, axis, "histogram_mean_var",
                                                  partial(aggregate, ddof=ddof), weights=weights)
-    if backend == "dask":
-        return (x.astype(np.int64) if weights is None else x), mean, m2, bins
-    return x, mean, _var_of(x, m2, ddof), bins
+    return x, mean, (m2 if backend == "dask" else _var_of(x, m2, ddof)), bins
 
 
 # ---------------------------------------------------------------------------------------------
 # per-bin covariance of two value arrays
 # ---------------------------------------------------------------------------------------------
+def _value_pair(values, name, noun):
+    """the (a, b) of ``values=`` in the covariance calls, or their TypeError.  `noun` says what the pair is made of: "arrays"
+    here, "DataArrays" in xarray.py, which writes the pair in capitals and whose own type check answers a None"""
+    if (isinstance(values, (str, bytes)) or not isinstance(values, (tuple, list)) or len(values) != 2
+            or (noun == "arrays" and any(v is None for v in values))):
+        raise TypeError("%s needs values=(%s), a pair of %s" % (name, "A, B" if noun == "DataArrays" else "a, b", noun))
+    return values
+
+
+def _cov_call(stat, name, args, a, b, weights, bins, range, axis, ddof):
+    """histogram_cov and histogram_weighted_cov behind their own checks: the library's (x, mean_a, mean_b, M2_a, C_ab, M2_b)
+    in the order of the public outputs, the moments divided by x - ddof (dask: by the last step of the merge)"""
+    ddof = _check_ddof(ddof)
+    backend, (x, ma, mb, qa, cc, qb), bins, _ = _value_stat(stat, args, a, bins, range, axis, name,
+                                                           partial(_VALUE_STATS[stat].reduce, ddof=ddof), b, weights=weights)
+    if backend == "dask":
+        return x, ma, mb, qa, qb, cc, bins
+    return x, ma, mb, _var_of(x, qa, ddof), _var_of(x, qb, ddof), _var_of(x, cc, ddof), bins
+
+
 def combine_cov(n, mean_a, mean_b, m2_a, m2_b, c_ab, axis):
     """Merge partial (count, mean_a, mean_b, M2_a, M2_b, C_ab) results over `axis` (kept as axes of extent 1) with Chan's
     pairwise formula extended by the co-moment, one partial after another in index order (C order over several axes):
@@ -2243,12 +2227,7 @@ def combine_cov(n, mean_a, mean_b, m2_a, m2_b, c_ab, axis):
         M2 = M2_1 + M2_2 + d^2 * n1 * n2 / n,  C = C1 + C2 + da * db * n1 * n2 / n.
     Partials with n == 0 are skipped; where every partial is empty, the means and moments are NaN and n is 0.  The reduction
     of dask's partials.  Returns float64 (n, mean_a, mean_b, M2_a, M2_b, C_ab)."""
-    n, (ma, mb), (qa, qb, cc) = _chan_merge(n, [mean_a, mean_b], [m2_a, m2_b, c_ab], [(0, 0), (1, 1), (0, 1)], axis, _counted)
-    return n, ma, mb, qa, qb, cc
-
-
-# the step of (n, mean_a, mean_b, M2_a, C_ab, M2_b) blocks, the order of the library's outputs
-_cov_reduce = partial(_chan_reduce, present=_counted, pairs=((0, 0), (0, 1), (1, 1)))
+    return tuple(_merge_partials(partial(_chan_update, pairs=_COV_PAIRS), _counted, n, [mean_a, mean_b, m2_a, m2_b, c_ab], axis))
 
 
 def histogram_cov(*args, values, bins=None, range=None, axis=None, ddof=0, block_size="auto"):
@@ -2279,18 +2258,8 @@ def histogram_cov(*args, values, bins=None, range=None, axis=None, ddof=0, block
     ``histogram`` gives (kept axes, then bin axes).  numpy in -> numpy out, torch in -> torch out on the same device
     (asynchronous on the current stream), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block, the
     partials merged by :func:`combine_cov`."""
-    if isinstance(values, (str, bytes)) or not isinstance(values, (tuple, list)) or len(values) != 2:
-        raise TypeError("histogram_cov needs values=(a, b), a pair of arrays")
-    a, b = values
-    if a is None or b is None:
-        raise TypeError("histogram_cov needs values=(a, b), a pair of arrays")
-    ddof = _check_ddof(ddof)
-    # the second value array travels where histogram_mean_var's weights travel
-    backend, (n, ma, mb, qa, cc, qb), bins, _ = _value_stat("cov", args, a, bins, range, axis, "histogram_cov",
-                                                           partial(_cov_reduce, ddof=ddof), weights=b)
-    if backend == "dask":
-        return n.astype(np.int64), ma, mb, qa, qb, cc, bins
-    return n, ma, mb, _var_of(n, qa, ddof), _var_of(n, qb, ddof), _var_of(n, cc, ddof), bins
+    a, b = _value_pair(values, "histogram_cov", "arrays")
+    return _cov_call("cov", "histogram_cov", args, a, b, None, bins, range, axis, ddof)
 
 
 def combine_weighted_cov(w, mean_a, mean_b, m2_a, m2_b, c_ab, axis):
@@ -2301,12 +2270,7 @@ def combine_weighted_cov(w, mean_a, mean_b, m2_a, m2_b, c_ab, axis):
     Partials with W == 0 are skipped; a NaN partial (a NaN W among them) makes the bin NaN.  Where every partial has W == 0,
     the means and moments are NaN and W is 0.  The reduction of dask's weighted partials.  Returns float64 (W, mean_a, mean_b,
     M2_a, M2_b, C_ab)."""
-    w, (ma, mb), (qa, qb, cc) = _chan_merge(w, [mean_a, mean_b], [m2_a, m2_b, c_ab], [(0, 0), (1, 1), (0, 1)], axis, _weighed)
-    return w, ma, mb, qa, qb, cc
-
-
-# the step of (W, mean_a, mean_b, M2_a, C_ab, M2_b) blocks, the order of the library's outputs
-_cov_w_reduce = partial(_chan_reduce, present=_weighed, pairs=((0, 0), (0, 1), (1, 1)))
+    return tuple(_merge_partials(partial(_chan_update, pairs=_COV_PAIRS), _weighed, w, [mean_a, mean_b, m2_a, m2_b, c_ab], axis))
 
 
 def histogram_weighted_cov(*args, values, weights, bins=None, range=None, axis=None, ddof=0, block_size="auto"):
@@ -2337,20 +2301,10 @@ def histogram_weighted_cov(*args, values, weights, bins=None, range=None, axis=N
     gives (kept axes, then bin axes).  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the
     current stream), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block, the partials merged by
     :func:`combine_weighted_cov`."""
-    if isinstance(values, (str, bytes)) or not isinstance(values, (tuple, list)) or len(values) != 2:
-        raise TypeError("histogram_weighted_cov needs values=(a, b), a pair of arrays")
-    a, b = values
-    if a is None or b is None:
-        raise TypeError("histogram_weighted_cov needs values=(a, b), a pair of arrays")
+    a, b = _value_pair(values, "histogram_weighted_cov", "arrays")
     if weights is None:
         raise TypeError("histogram_weighted_cov needs weights")
-    ddof = _check_ddof(ddof)
-    # the second value array travels where histogram_mean_var's weights travel, the weights behind it
-    backend, (w, ma, mb, qa, cc, qb), bins, _ = _value_stat("cov_w", args, a, bins, range, axis, "histogram_weighted_cov",
-                                                           partial(_cov_w_reduce, ddof=ddof), weights=b, fourth=weights)
-    if backend == "dask":
-        return w, ma, mb, qa, qb, cc, bins
-    return w, ma, mb, _var_of(w, qa, ddof), _var_of(w, qb, ddof), _var_of(w, cc, ddof), bins
+    return _cov_call("cov_w", "histogram_weighted_cov", args, a, b, weights, bins, range, axis, ddof)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2362,42 +2316,18 @@ def _check_flag(name, v):
     return bool(v)
 
 
-def _pebay_merge(x, mean, m2, m3, m4, axis, present):
-    """Pébay's pairwise merge of partial (x, mean, M2, M3, M4) results over `axis` (kept as axes of extent 1), one partial
-    after another in index order, exactly as _chan_merge walks them: x, mean and M2 by _chan_merge's very expressions (so they
-    have its bits), M3 and M4 by the update of :func:`combine_skew_kurt`.  Returns float64 (x, mean, M2, M3, M4)."""
-    x, mean, m2, m3, m4 = (np.asarray(a, np.float64) for a in (x, mean, m2, m3, m4))
-    ax = tuple(sorted(int(a) % x.ndim for a in (axis if isinstance(axis, (tuple, list)) else (axis,))))
-    kept = [i for i in _range(x.ndim) if i not in ax]
-    keep_shape = tuple(1 if i in ax else x.shape[i] for i in _range(x.ndim))
-
-    def lead(a):
-        a = np.transpose(a, ax + tuple(kept))
-        return a.reshape((-1,) + a.shape[len(ax):])
-
-    x, mean, m2, m3, m4 = (lead(a) for a in (x, mean, m2, m3, m4))
-    cx = np.zeros(x.shape[1:])
-    cm, c2, c3, c4 = (np.full(x.shape[1:], np.nan) for _ in _range(4))
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        for k in _range(x.shape[0]):
-            xb = x[k]
-            take = present(xb)
-            first = take & ~present(cx)
-            both = take & present(cx)
-            tot = cx + xb
-            d = mean[k] - cm
-            n2 = c2 + m2[k] + d * d * cx * xb / tot
-            n3 = (c3 + m3[k] + d * d * d * cx * xb * (cx - xb) / (tot * tot)
-                  + 3.0 * d * (cx * m2[k] - xb * c2) / tot)
-            n4 = (c4 + m4[k] + d * d * d * d * cx * xb * (cx * cx - cx * xb + xb * xb) / (tot * tot * tot)
-                  + 6.0 * d * d * (cx * cx * m2[k] + xb * xb * c2) / (tot * tot)
-                  + 4.0 * d * (cx * m3[k] - xb * c3) / tot)
-            cm = np.where(first, mean[k], np.where(both, cm + d * xb / tot, cm))
-            c2 = np.where(first, m2[k], np.where(both, n2, c2))
-            c3 = np.where(first, m3[k], np.where(both, n3, c3))
-            c4 = np.where(first, m4[k], np.where(both, n4, c4))
-            cx = np.where(take, tot, cx)
-    return tuple(a.reshape(keep_shape) for a in (cx, cm, c2, c3, c4))
+def _pebay_update(cx, xb, tot, cur, part):
+    """Pébay's update of running (mean, M2, M3, M4): mean and M2 by _chan_update's very expressions (so they have its bits), M3
+    and M4 by the update of :func:`combine_skew_kurt`"""
+    (cm, c2, c3, c4), (mean, m2, m3, m4) = cur, part
+    d = mean - cm
+    return [cm + d * xb / tot,
+            c2 + m2 + d * d * cx * xb / tot,
+            (c3 + m3 + d * d * d * cx * xb * (cx - xb) / (tot * tot)
+             + 3.0 * d * (cx * m2 - xb * c2) / tot),
+            (c4 + m4 + d * d * d * d * cx * xb * (cx * cx - cx * xb + xb * xb) / (tot * tot * tot)
+             + 6.0 * d * d * (cx * cx * m2 + xb * xb * c2) / (tot * tot)
+             + 4.0 * d * (cx * m3 - xb * c3) / tot)]
 
 
 def combine_skew_kurt(n, mean, m2, m3, m4, axis):
@@ -2409,14 +2339,14 @@ def combine_skew_kurt(n, mean, m2, m3, m4, axis):
         M4 = M4a + M4b + d^4 na nb (na^2 - na nb + nb^2) / n^3 + 6 d^2 (na^2 M2b + nb^2 M2a) / n^2 + 4 d (na M3b - nb M3a) / n.
     Partials with n == 0 are skipped; where every partial is empty, the mean and the moments are NaN and n is 0.  The reduction
     of dask's partials.  Returns float64 (n, mean, M2, M3, M4)."""
-    return _pebay_merge(n, mean, m2, m3, m4, axis, _counted)
+    return tuple(_merge_partials(_pebay_update, _counted, n, [mean, m2, m3, m4], axis))
 
 
 def combine_weighted_skew_kurt(w, mean, m2, m3, m4, axis):
     """:func:`combine_skew_kurt` for weighted partials (W, mean, M2, M3, M4), W in the place of n: partials with W == 0 are
     skipped; a NaN partial (a NaN W among them) makes the bin NaN, as in :func:`combine_weighted_mean_var`, whose W, mean and M2
     these are bit for bit.  Returns float64 (W, mean, M2, M3, M4)."""
-    return _pebay_merge(w, mean, m2, m3, m4, axis, _weighed)
+    return tuple(_merge_partials(_pebay_update, _weighed, w, [mean, m2, m3, m4], axis))
 
 
 def _skew_kurt_of(x, m2, m3, m4, bias, fisher):
@@ -2443,22 +2373,23 @@ def _skew_kurt_of(x, m2, m3, m4, bias, fisher):
     return skew, kurt
 
 
-def _pebay_reduce(x, axis=None, keepdims=True, final=None, present=_counted, **_):
-    """dask.array.reduction step over stacked blocks of (x, mean, M2, M3, M4) partials.  With final = (ddof, bias, fisher), the
-    last step: the moments turned into (var, skew, kurt), here only."""
+def _moment_reduce(x, axis=None, keepdims=True, pairs=((0, 0),), present=_counted, ddof=None, final=None, **_):
+    """dask.array.reduction step over stacked blocks of partials in the order the library emits them: x, the means, then the
+    moments, `pairs` naming each moment's means as _chan_update reads them; pairs=None: (x, mean, M2, M3, M4), merged by
+    _pebay_update.  The last step, here only, has ddof (the moments divided by x - ddof) or, for Pébay's blocks,
+    final = (ddof, bias, fisher) (the moments turned into var, skew and kurt)."""
     ax = tuple(int(a) for a in (axis if isinstance(axis, tuple) else (axis,)))
-    out = np.stack(_pebay_merge(x[0], x[1], x[2], x[3], x[4], tuple(a - 1 for a in ax), present))
+    update = _pebay_update if pairs is None else partial(_chan_update, pairs=pairs)
+    out = np.stack(_merge_partials(update, present, x[0], x[1:], tuple(a - 1 for a in ax)))
     out = out if keepdims else out.squeeze(ax)
+    moments = _range(len(out) - len(pairs), len(out)) if pairs else (2,)
     if final is not None:
         ddof, bias, fisher = final
-        skew, kurt = _skew_kurt_of(out[0], out[2], out[3], out[4], bias, fisher)
-        out[2] = _var_of(out[0], out[2], ddof)
-        out[3], out[4] = skew, kurt
+        out[3], out[4] = _skew_kurt_of(out[0], out[2], out[3], out[4], bias, fisher)
+    if ddof is not None:
+        for i in moments:
+            out[i] = _var_of(out[0], out[i], ddof)
     return out
-
-
-_skew_kurt_reduce = partial(_pebay_reduce, present=_counted)
-_skew_kurt_w_reduce = partial(_pebay_reduce, present=_weighed)
 
 
 def histogram_skew_kurt(*args, values, bins=None, range=None, axis=None, weights=None, ddof=0, bias=True, fisher=True,
@@ -2500,33 +2431,39 @@ def histogram_skew_kurt(*args, values, bins=None, range=None, axis=None, weights
     stat, reduce_ = ("skew_kurt", _skew_kurt_reduce) if weights is None else ("skew_kurt_w", _skew_kurt_w_reduce)
     backend, (x, mean, m2, m3, m4), bins, _ = _value_stat(stat, args, values, bins, range, axis, "histogram_skew_kurt",
                                                          partial(reduce_, final=(ddof, bias, fisher)), weights=weights)
-    if backend == "dask":  # (the aggregate step has turned the moments into var, skew and kurt)
-        return (x.astype(np.int64) if weights is None else x), mean, m2, m3, m4, bins
+    if backend == "dask":  # (the last step of the merge has turned the moments into var, skew and kurt)
+        return x, mean, m2, m3, m4, bins
     skew, kurt = _skew_kurt_of(x, m2, m3, m4, bias, fisher)
     return x, mean, _var_of(x, m2, ddof), skew, kurt, bins
 
 
+# The dask steps of the moment statistics: partials of a module-level function, so that dask can pickle them.  The blocks of
+# the two covariances keep the order of the library's outputs; an aggregate is the last step, (x, mean, var).
+_mean_var_reduce = partial(_moment_reduce, present=_counted)
+_mean_var_aggregate = partial(_moment_reduce, present=_counted, ddof=0)
+_mean_var_w_reduce = partial(_moment_reduce, present=_weighed)
+_mean_var_w_aggregate = partial(_moment_reduce, present=_weighed, ddof=0)
+_cov_reduce = partial(_moment_reduce, present=_counted, pairs=_COV_BLOCK_PAIRS)
+_cov_w_reduce = partial(_moment_reduce, present=_weighed, pairs=_COV_BLOCK_PAIRS)
+_skew_kurt_reduce = partial(_moment_reduce, present=_counted, pairs=None)
+_skew_kurt_w_reduce = partial(_moment_reduce, present=_weighed, pairs=None)
+
 _VALUE_STATS = {
-    "extrema": _ValueStat(2, False, "execute_extrema", _extrema_pair_reduce),
-    "mean_var": _ValueStat(3, True, "execute_mean_var", _mean_var_reduce),
-    "mean_var_w": _ValueStat(3, False, "execute_mean_var_weighted", _mean_var_w_reduce, True),
-    # (count, mean_a, mean_b, M2_a, C_ab, M2_b): the library takes the count, the block of means and the block of moments
-    "cov": _ValueStat(6, True, "execute_cov", _cov_reduce, True, (0, 1, 3)),
-    # (W, mean_a, mean_b, M2_a, C_ab, M2_b), all float64, in the same three blocks; two arrays after the first values
-    "cov_w": _ValueStat(6, False, "execute_cov_weighted", _cov_w_reduce, 2, (0, 1, 3)),
+    "extrema": _ValueStat(2, (), "execute_extrema", (0, 1), 0, _extrema_pair_reduce),
+    # (vmin, vmax, argmin, argmax): the library takes the block of values and the block of positions
+    "argextrema": _ValueStat(4, (2, 3), "execute_argextrema", (0, 2), 0, None, ordered=True, noun="positions"),
+    "mean_var": _ValueStat(3, (0,), "execute_mean_var", (0, 1, 2), 0, _mean_var_reduce),
+    "mean_var_w": _ValueStat(3, (), "execute_mean_var_weighted", (0, 1, 2), 1, _mean_var_w_reduce),
+    # (x, mean_a, mean_b, M2_a, C_ab, M2_b): the library takes x, the block of means and the block of moments
+    "cov": _ValueStat(6, (0,), "execute_cov", (0, 1, 3), 1, _cov_reduce),
+    "cov_w": _ValueStat(6, (), "execute_cov_weighted", (0, 1, 3), 2, _cov_w_reduce),
+    # (x, mean, M2, M3, M4): the library takes x, the mean and the block of three moments
+    "skew_kurt": _ValueStat(5, (0,), "execute_skew_kurt", (0, 1, 2), 0, _skew_kurt_reduce),
+    "skew_kurt_w": _ValueStat(5, (), "execute_skew_kurt_weighted", (0, 1, 2), 1, _skew_kurt_w_reduce),
+    # one output per element of the call's q, in one block
+    "quantile": _ValueStat(None, (), "execute_quantile", (0,), 0, None, ("q", "code"), noun="exact quantiles"),
+    "quantile_w": _ValueStat(None, (), "execute_quantile_weighted", (0,), 1, None, ("q",), noun="exact quantiles"),
 }
-# The statistics of the third and fourth moments, (x, mean, M2, M3, M4): the library takes the first, the mean and the block of
-# three moments.  A table of their own: what walks _VALUE_STATS takes a statistic's partials for extrema pairs or for the
-# (x, means, moments) blocks of Chan's merge, and these merge by Pébay's update (_pebay_reduce).
-_MOMENT4_STATS = {
-    "skew_kurt": _ValueStat(5, True, "execute_skew_kurt", _skew_kurt_reduce, False, (0, 1, 2)),
-    "skew_kurt_w": _ValueStat(5, False, "execute_skew_kurt_weighted", _skew_kurt_w_reduce, True, (0, 1, 2)),
-}
-
-
-def _stat_of(name):
-    """the _ValueStat of a per-bin statistic of values, by the name _value_stat takes"""
-    return _VALUE_STATS[name] if name in _VALUE_STATS else _MOMENT4_STATS[name]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2545,60 +2482,6 @@ def _check_quantile_args(q, method):
     if not (np.all(qf >= 0) and np.all(qf <= 1)):  # (NaN fails both)
         raise ValueError("Quantiles must be in the range [0, 1]")
     return qf, qa.ndim == 0, _native.QUANTILE_METHODS.index(method)
-
-
-def _quantile_rows(args, values, axis, bins, backend, q, code, weights=None):
-    """[len(q), kept axes (reduced ones of extent 1), bins...] float64 quantiles (weighted ones, if weights are given) of
-    broadcast torch tensors (torch out) or DeviceArrays (numpy out)"""
-    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, weights)
-    n = m * plan.n_bins
-    shape = (len(q),) + kept_axes_shape + plan.bins_shape
-
-    def execute(out_ptr):
-        if weights is None:
-            plan.execute_quantile(nv[:-1], nv[-1], m, c, out_ptr, q, code, stream=stream)
-        else:
-            plan.execute_quantile_weighted(nv[:-2], nv[-2], nv[-1], m, c, out_ptr, q, stream=stream)
-
-    if backend == "torch":
-        out = _torch().empty(shape, dtype=_torch().float64, device=args[0].device)
-        if n > 0 and len(q):
-            execute(out.data_ptr())
-        return out
-    host = np.empty(shape, np.float64)
-    if n > 0 and len(q):
-        buf = _native.DeviceBuffer(device, len(q) * n * 8)
-        execute(buf.ptr)
-        buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
-    return host
-
-
-def _quantile_block(*all_arrays, axis=None, bins=None, q=None, code=0, weighted=False):
-    """one dask block (samples..., values[, weights]), complete along the reduced axes: its quantiles [len(q), block axes
-    (reduced ones of extent 1), bins...]"""
-    n = len(all_arrays) - 1 - int(weighted)
-    arrays = _upload_host(all_arrays[:n], all_arrays[n], bins, *all_arrays[n + 1:])
-    return _quantile_rows(arrays[:n], arrays[n], axis, bins, "device", q, code, *arrays[n + 1:])
-
-
-def _quantile_call(args, values, bins, range, axis, name, qf, scalar, code, weights=None):
-    """the backends of the per-bin quantiles qf (checked; `scalar`: q was one), after the function's own argument checks:
-    (quantiles with the shape ``histogram`` gives behind the q axis, bin edges)"""
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, weights)
-    n_inputs = len(args)
-    if backend == "dask":
-        for a in all_arrays:
-            if any(len(a.chunks[ax]) > 1 for ax in drop_axes):
-                raise ValueError("exact quantiles of several chunks cannot be merged: rechunk the reduced axes of every input into "
-                                 "one chunk (e.g. arr.rechunk({axis: -1}))")
-        res = _values_blockwise(partial(_quantile_block, q=qf, code=code, weighted=weights is not None), len(qf), all_arrays, bins,
-                                axis, drop_axes)
-        res = res[(slice(None),) + tuple(0 if i in drop_axes else slice(None) for i in _range(all_arrays[0].ndim))]
-    else:
-        arrays, on = _resident(backend, raw, all_arrays, n_inputs, bins)
-        res = _quantile_rows(arrays[:n_inputs], arrays[n_inputs], axis, bins, on, qf, code, *arrays[n_inputs + 1:])
-        res = _drop_axes(res, tuple(a + 1 for a in drop_axes), backend)
-    return (res[0] if scalar else res), bins
 
 
 def histogram_quantile(*args, values, q, bins=None, range=None, axis=None, method="linear", block_size="auto", weights=None,
@@ -2624,7 +2507,8 @@ def histogram_quantile(*args, values, q, bins=None, range=None, axis=None, metho
     if density is not None:
         raise TypeError("histogram_quantile does not take density")
     qf, scalar, code = _check_quantile_args(q, method)
-    return _quantile_call(args, values, bins, range, axis, "histogram_quantile", qf, scalar, code)
+    _, res, bins, _ = _value_stat("quantile", args, values, bins, range, axis, "histogram_quantile", q=qf, code=code)
+    return (res[0] if scalar else res), bins
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2667,4 +2551,5 @@ def histogram_weighted_quantile(*args, values, weights, q, bins=None, range=None
     if weights is None:
         raise TypeError("histogram_weighted_quantile needs weights")
     qf, scalar, _ = _check_quantile_args(q, "linear")
-    return _quantile_call(args, values, bins, range, axis, "histogram_weighted_quantile", qf, scalar, 0, weights)
+    _, res, bins, _ = _value_stat("quantile_w", args, values, bins, range, axis, "histogram_weighted_quantile", weights=weights, q=qf)
+    return (res[0] if scalar else res), bins

@@ -276,17 +276,12 @@ def histogram_cov(*args, values, bins=None, range=None, dim=None, ddof=0, block_
     of it): ``<a>_<b>_count``, ``<a>_mean``, ``<b>_mean``, ``<a>_var``, ``<b>_var``, ``<a>_<b>_cov``, with ``<a>`` / ``<b>``
     the names of the DataArrays (``a`` / ``b`` for a nameless one).  There is no ``weights`` parameter here: the weighted form
     is :func:`histogram_weighted_cov`."""
-    from .core import histogram_cov as _core_histogram_cov
+    from .core import _value_pair, histogram_cov as _core_histogram_cov
 
-    if isinstance(values, (str, bytes)) or not isinstance(values, (tuple, list)) or len(values) != 2:
-        raise TypeError("histogram_cov needs values=(A, B), a pair of DataArrays")
-    A, B = values
-
-    def pair(*arrays, values, weights, **kw):  # (B is lined up where the weights of the other statistics are)
-        return _core_histogram_cov(*arrays, values=(values, weights), **kw)
-
+    A, B = _value_pair(values, "histogram_cov", "DataArrays")
     results, out_dims, coords, _ = _values_statistic(
-        "histogram_cov", pair, args, A, bins, range, dim, keep_coords, bin_dim_suffix, ddof=ddof, block_size=block_size, weights=B)
+        "histogram_cov", _core_histogram_cov, args, (A, B), bins, range, dim, keep_coords, bin_dim_suffix, ddof=ddof,
+        block_size=block_size, pair=True)
     xr = _xr()
     a, b = A.name or "a", B.name or "b"
     names = ("%s_%s_count" % (a, b), "%s_mean" % a, "%s_mean" % b, "%s_var" % a, "%s_var" % b, "%s_%s_cov" % (a, b))
@@ -301,36 +296,30 @@ def histogram_weighted_cov(*args, values, weights, bins=None, range=None, dim=No
     ``weights`` is a DataArray whose dims are a subset of the data's, aligned and broadcast as ``A`` and ``B`` are (cell areas
     or volumes, ``cos(lat)``).  Returns a dict of six DataArrays named like :func:`histogram_cov`'s, with
     ``<a>_<b>_sum_of_weights`` in place of ``<a>_<b>_count``."""
-    from .core import histogram_weighted_cov as _core_histogram_weighted_cov
+    from .core import _value_pair, histogram_weighted_cov as _core_histogram_weighted_cov
 
-    if isinstance(values, (str, bytes)) or not isinstance(values, (tuple, list)) or len(values) != 2:
-        raise TypeError("histogram_weighted_cov needs values=(A, B), a pair of DataArrays")
+    A, B = _value_pair(values, "histogram_weighted_cov", "DataArrays")
     if weights is None:
         raise TypeError("histogram_weighted_cov needs weights")
-    A, B = values
-
-    def triple(*arrays, values, second, weights, **kw):
-        return _core_histogram_weighted_cov(*arrays, values=(values, second), weights=weights, **kw)
-
     results, out_dims, coords, _ = _values_statistic(
-        "histogram_weighted_cov", triple, args, A, bins, range, dim, keep_coords, bin_dim_suffix, ddof=ddof, block_size=block_size,
-        weights=weights, second=B)
+        "histogram_weighted_cov", _core_histogram_weighted_cov, args, (A, B), bins, range, dim, keep_coords, bin_dim_suffix, ddof=ddof,
+        block_size=block_size, weights=weights, pair=True)
     xr = _xr()
     a, b = A.name or "a", B.name or "b"
     names = ("%s_%s_sum_of_weights" % (a, b), "%s_mean" % a, "%s_mean" % b, "%s_var" % a, "%s_var" % b, "%s_%s_cov" % (a, b))
     return {n: xr.DataArray(r, dims=out_dims, coords=coords, name=n) for n, r in zip(names, results)}
 
 
-def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords, bin_dim_suffix, weights=None, second=None,
-                      reduced=None, **kw):
-    """a per-bin statistic of ``values`` with the labels of :func:`histogram`: (core_fn's arrays, dims, coords, the values'
-    name or "values").  ``weights`` (a DataArray or None) is lined up as ``values`` is and passed on as core_fn's weights; so is
-    ``second``, the second of a pair of values that comes with weights of its own, as core_fn's ``second``.  ``reduced`` (a
-    list, or None) receives the (name, broadcast size) of every reduced dim, in ascending axis number."""
+def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords, bin_dim_suffix, weights=None, reduced=None,
+                      pair=False, **kw):
+    """a per-bin statistic of ``values`` (a DataArray; ``pair``: two of them) with the labels of :func:`histogram`: (core_fn's
+    arrays, dims, coords, the first values' name or "values").  The values and then ``weights`` (a DataArray or None) are lined
+    up with the data and passed on in this order, as core_fn's values and weights.  ``reduced`` (a list, or None) receives the
+    (name, broadcast size) of every reduced dim, in ascending axis number."""
     xr = _xr()
     data_args = list(args)
     n_data = len(data_args)
-    extra = [values] + ([] if second is None else [second]) + ([] if weights is None else [weights])
+    extra = (list(values) if pair else [values]) + ([] if weights is None else [weights])
     for a in data_args + extra:
         if not isinstance(a, xr.DataArray):
             raise TypeError(
@@ -359,9 +348,8 @@ def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords
     arrays = [a.data for a in lined_up]
     if weights is not None:
         kw["weights"] = arrays.pop()
-    if second is not None:
-        kw["second"] = arrays.pop()
-    v_data = arrays.pop()
+    v_data = tuple(arrays[n_data:]) if pair else arrays[n_data]
+    del arrays[n_data:]
     if dim is not None:
         kept_dims = [d for d in dims_order if d not in dim]
         axis = [lined_up[0].get_axis_num(d) for d in dim]
@@ -380,4 +368,4 @@ def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords
         for c in first_coords:
             if c not in coords and set(first[c].dims).issubset(out_dims):
                 coords[c] = first[c]
-    return results, out_dims, coords, values.name or "values"
+    return results, out_dims, coords, extra[0].name or "values"
