@@ -92,15 +92,16 @@ def expected_of(xs_host, edges, a, b, w):
     return cwx.expected(flat[ok], a[ok], b[ok], w[ok], size)
 
 
-def check_exact(xs_host, edges, a, b, w, got, ddof=0, what=""):
-    """got = (W, mean_a, mean_b, var_a, var_b, cov_ab); returns (W, exact) after asserting that a bin took the bit-for-bit path"""
+def check_exact(xs_host, edges, a, b, w, got, ddof=0, what="", need_exact=True):
+    """got = (W, mean_a, mean_b, var_a, var_b, cov_ab); returns (W, exact) after asserting that a bin took the bit-for-bit path
+    (need_exact=False: random cases, which may have no such bin)"""
     W, (ma, mb), moments, bounds, exact = expected_of(xs_host, edges, a, b, w)
     assert np.asarray(got[0]).dtype == F64
     tvc._bits(got[0], W, "W " + what)
     tvc._bits(got[1], ma, "mean_a " + what)
     tvc._bits(got[2], mb, "mean_b " + what)
     cwx.assert_moments((got[3], got[5], got[4]), moments, bounds, exact, W=W, ddof=ddof, what=what)
-    assert split(W, exact, ddof)[0] >= 1, "no bin on the bit-for-bit path (%s)" % what
+    assert not need_exact or split(W, exact, ddof)[0] >= 1, "no bin on the bit-for-bit path (%s)" % what
     return W, exact
 
 

@@ -9,6 +9,7 @@ import pytest
 import exact_weights as ew
 from conftest import assert_hist_equal
 from oracle import oracle_np as onp
+from values_cases import edge_relative, sprinkle
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -58,18 +59,23 @@ def cases(draw):
     return d, shape, axis, dtype, edges, wshape, density, seed, resident, override
 
 
+def random_samples(rng, shape, dtype, edges):
+    """one sample array per edge array, drawn about its edges (values_cases.edge_relative: N(0, 2) samples met no bin of a
+    third of the drawn edge sets); float ones keep the special values they had, NaN, +-inf, +-4 and 0, on about 1/17 of the
+    positions (each position on its own: the one sample of a (1,) array used to be a special value every time)"""
+    args = [edge_relative(rng, shape, e, dtype, specials=False) for e in edges]
+    if np.dtype(dtype).kind == "f":
+        for a in args:
+            sprinkle(rng, a, 17, [np.nan, np.inf, -np.inf, 4.0, -4.0, 0.0])
+    return args
+
+
 @settings(max_examples=300, deadline=None, suppress_health_check=list(HealthCheck))
 @given(cases())
 def test_random_cases_match_oracle(xh, case):
     d, shape, axis, dtype, edges, wshape, density, seed, resident, override = case
     rng = np.random.default_rng(seed)
-    if np.dtype(dtype).kind == "f":
-        args = [(rng.standard_normal(shape) * 2).astype(dtype) for _ in range(d)]
-        for a in args:
-            flat = a.reshape(-1)
-            flat[rng.integers(0, flat.size, max(1, flat.size // 17))] = rng.choice([np.nan, np.inf, -np.inf, 4.0, -4.0, 0.0])
-    else:
-        args = [rng.integers(-5, 6, shape).astype(dtype) for _ in range(d)]
+    args = random_samples(rng, shape, dtype, edges)
     w = None
     if wshape == "full":
         w = rng.uniform(0, 2, shape)
@@ -240,26 +246,28 @@ def mixed_cases(draw):
     return d, rows, cols, dtypes, nbs, kinds, wdtype, axis, seed, resident, override
 
 
+def mixed_samples_and_edges(rng, case):
+    """the sample arrays of a mixed case and their edges: the edges as before (their span by the kind of dtype), the samples
+    drawn about them (values_cases.edge_relative); float ones keep NaN, +-inf and +-3 on about 1/23 of the positions"""
+    d, rows, cols, dtypes, nbs, kinds = case[:6]
+    args, edges = [], []
+    for dt, nb, kind in zip(dtypes, nbs, kinds):
+        lo, hi = (-3.0, 3.0) if np.dtype(dt).kind == "f" else (10.0, 250.0) if dt == np.uint8 else (-50.0, 50.0)
+        e = np.linspace(lo, hi, nb + 1) if kind == "uniform" else np.sort(np.concatenate([[lo, hi], rng.uniform(lo, hi, nb - 1)]))
+        a = edge_relative(rng, (rows, cols), e, dt, specials=False)
+        if np.dtype(dt).kind == "f":
+            sprinkle(rng, a, 23, [np.nan, np.inf, -np.inf, 3.0, -3.0])
+        args.append(a)
+        edges.append(e)
+    return args, edges
+
+
 @settings(max_examples=250, deadline=None, suppress_health_check=list(HealthCheck))
 @given(mixed_cases())
 def test_mixed_dtypes_and_big_histograms_match_oracle(xh, case):
     d, rows, cols, dtypes, nbs, kinds, wdtype, axis, seed, resident, override = case
     rng = np.random.default_rng(seed)
-    args, edges = [], []
-    for dt, nb, kind in zip(dtypes, nbs, kinds):
-        if np.dtype(dt).kind == "f":
-            a = (rng.standard_normal((rows, cols)) * 2).astype(dt)
-            a.reshape(-1)[rng.integers(0, a.size, max(1, a.size // 23))] = rng.choice([np.nan, np.inf, -np.inf, 3.0, -3.0])
-            lo, hi = -3.0, 3.0
-        elif dt == np.uint8:
-            a = rng.integers(0, 256, (rows, cols)).astype(dt)
-            lo, hi = 10.0, 250.0
-        else:
-            a = rng.integers(-60, 61, (rows, cols)).astype(dt)
-            lo, hi = -50.0, 50.0
-        args.append(a)
-        e = np.linspace(lo, hi, nb + 1) if kind == "uniform" else np.sort(np.concatenate([[lo, hi], rng.uniform(lo, hi, nb - 1)]))
-        edges.append(e)
+    args, edges = mixed_samples_and_edges(rng, case)
     w = None
     if wdtype is not None:
         w = rng.uniform(0, 3, (rows, cols))

@@ -117,16 +117,17 @@ def run_moments(core, xs, v, w, edges, axis=1):
     return tuple(_np(o) for o in outs)
 
 
-def check_results(core, xs, edges, v, w, moms, outs, dev=None, ddof=0, bias=True, fisher=True, what=""):
+def check_results(core, xs, edges, v, w, moms, outs, dev=None, ddof=0, bias=True, fisher=True, what="", need_exact=True):
     """moms = (x, mean, M2, M3, M4), outs = (x, mean, var, skew, kurt) of the library against skew_kurt_exact; then
-    histogram_mean_var on the same device arrays dev = (samples, values, weights or None).  Returns (x, exact mask)."""
+    histogram_mean_var on the same device arrays dev = (samples, values, weights or None).  Returns (x, exact mask).
+    need_exact=False: random cases, which may have no bin on the bit-for-bit path."""
     x, mean, moments, bounds, exact = expected_of(xs, edges, v, w)
     for got in (moms, outs):
         gx = np.asarray(got[0]).reshape(-1)
         assert gx.dtype == (np.int64 if w is None else F64), gx.dtype
         np.testing.assert_array_equal(gx, x, err_msg="x " + what)
         tvc._bits(got[1], mean, "mean " + what)
-    assert exact.any(), "no bin on the bit-for-bit path (%s)" % what
+    assert exact.any() or not need_exact, "no bin on the bit-for-bit path (%s)" % what
     for k, name in enumerate(("M2", "M3", "M4")):
         sx.assert_within(moms[2 + k], moments[k], bounds[k], exact, "%s %s" % (name, what))
     want, wb = sx.expected_outputs(x, moments, bounds, ddof, bias, fisher)

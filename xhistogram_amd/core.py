@@ -513,7 +513,7 @@ def _rows_cols(a, axis, do_full_array):
         item = a.element_size()
         if m and c and _nocopy_reshape_strides(tuple(moved.shape), tuple(st * item for st in moved.stride()), (m, c), item) is None:
             moved = _torch_contiguous(moved)  # the reshape needs a copy: ours
-        return moved.reshape(m, -1)
+        return moved.reshape(m, c)  # (not -1: torch cannot infer the columns of a block without rows)
     if _is_devarr(a):
         if do_full_array:
             return a.reshape(1, -1)
@@ -2098,7 +2098,7 @@ def _merge_partials(update, present, x, rest, axis):
 
     def lead(a):
         a = np.transpose(a, ax + tuple(kept))
-        return a.reshape((-1,) + a.shape[len(ax):])
+        return a.reshape((int(np.prod(a.shape[:len(ax)])),) + a.shape[len(ax):])  # (not -1: a kept axis may have extent 0)
 
     x, rest = lead(x), [lead(a) for a in rest]
     cx = np.zeros(x.shape[1:])
