@@ -3,12 +3,7 @@
 // No CPU compute path exists here on purpose: without a HIP device every compute entry point
 // fails with XHIST_ERR_NO_DEVICE.
 #include "xhist_pick.hip.h"
-#include "xhist_extrema.hip.h"
-#include "xhist_meanvar.hip.h"
-#include "xhist_cov.hip.h"
-#include "xhist_cov_w.hip.h"
-#include "xhist_quantile.hip.h"
-#include "xhist_quantile_w.hip.h"
+#include "xhist_values_api.h"
 
 #include <dlfcn.h>
 
@@ -256,7 +251,7 @@ extern "C" int xhist_plan_execute_two_weights(xhist_plan* p, const xhist_array* 
 // ------------------------------------------------------------------------------------------
 // per-bin statistics of a value array: minimum and maximum (xhist_extrema.hip), count, mean and sum of squared deviations
 // (xhist_meanvar.hip, xhist_meanvar_w.hip), quantiles (xhist_quantile.hip, xhist_quantile_w.hip), the covariance of two value
-// arrays (xhist_cov.hip) and its weighted form (xhist_cov_w.hip); the choice and the launches they share: xhist_values.hip.h
+// arrays (xhist_cov.hip) and its weighted form (xhist_cov_w.hip); what this unit shares with theirs: xhist_values_api.h
 // ------------------------------------------------------------------------------------------
 void xhist_log_picked_kernel(const void* fn) { log_picked_kernel(fn); }
 void xhist_log_local_kernel(const void* fn, const char* name) { log_picked_kernel(fn, name); }
@@ -277,12 +272,20 @@ static ValuesPlan values_plan(const xhist_plan* p) {
   return pl;
 }
 
+// the scratch allocator of the statistics' drivers (xhist_values_alloc_fn): ctx is the call's ScratchScope
+static void* values_scratch_alloc(void* ctx, size_t bytes) {
+  void* d = nullptr;
+  return static_cast<ScratchScope*>(ctx)->alloc(&d, bytes ? bytes : 8) == hipSuccess ? d : nullptr;
+}
+
 // The checks and the tail the statistics' entry points share: `out` is the statistic's float64 output validate_arrays checks,
-// `outs_ok` whether the others are given (`outs_missing` the message if not).  run(plan, err, err_cap, desc, desc_cap) launches
-// on the plan's device; the line it writes to `desc` becomes the plan's describe().
+// `outs_ok` whether the others are given (`outs_missing` the message if not); `third` and `fourth` are the streams beyond the
+// values, which the entry point has checked (nullptr: none).  run(call) launches on the plan's device with the record of the
+// call, which lives as long as run does; the line it writes to call.desc becomes the plan's describe().
 template <class Run>
-static int execute_values(xhist_plan* p, const char* name, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
-                          int64_t n_cols, double* out, bool outs_ok, const char* outs_missing, int mem_kind, Run run) {
+static int execute_values(xhist_plan* p, const char* name, const xhist_array* samples, const xhist_array* values,
+                          const xhist_array* third, const xhist_array* fourth, int64_t n_rows, int64_t n_cols, double* out, bool outs_ok,
+                          const char* outs_missing, int mem_kind, void* stream, Run run) {
   if (!values) return fail(XHIST_ERR_INVALID, "values are required");
   if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out, XHIST_F64)) return rc;
   if (!outs_ok && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "%s", outs_missing);
@@ -291,10 +294,13 @@ static int execute_values(xhist_plan* p, const char* name, const xhist_array* sa
   if (n_rows * p->n_bins == 0) return XHIST_OK;
   DeviceGuard g;
   if (int rc = g.set(p->device)) return rc;
-  const ValuesPlan pl = values_plan(p);
   Range r(name);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ScratchScope scratch(s);  // (what the drivers allocate is freed, in stream order, when the call returns)
   char err[256] = {0}, desc[384] = {0};  // (the radix quantile line with its successor field passes 256)
-  const int rc = run(pl, err, sizeof err, desc, sizeof desc);
+  const ValuesCall call = {values_plan(p), samples, values, third, fourth, n_rows, n_cols, s, err, sizeof err, desc, sizeof desc,
+                           values_scratch_alloc, &scratch};
+  const int rc = run(call);
   if (rc != XHIST_OK) return fail(rc, "%s", err);
   if (desc[0]) {
     std::lock_guard<std::mutex> lk(p->mu);
@@ -305,42 +311,23 @@ static int execute_values(xhist_plan* p, const char* name, const xhist_array* sa
 
 extern "C" int xhist_plan_execute_extrema(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
                                           int64_t n_cols, double* out_min, double* out_max, int mem_kind, int accumulate, void* stream) {
-  return execute_values(p, "xhist_plan_execute_extrema", samples, values, n_rows, n_cols, out_min, out_max != nullptr,
-                        "out_max is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-                          return xhist_extrema_run(pl, samples, values, n_rows, n_cols, out_min, out_max, accumulate,
-                                                   static_cast<hipStream_t>(stream), err, err_cap, desc, desc_cap);
-                        });
+  return execute_values(p, "xhist_plan_execute_extrema", samples, values, nullptr, nullptr, n_rows, n_cols, out_min, out_max != nullptr,
+                        "out_max is NULL", mem_kind, stream,
+                        [&](const ValuesCall& k) { return xhist_extrema_run(k, out_min, out_max, accumulate); });
 }
 
 extern "C" int xhist_plan_execute_argextrema(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
                                              int64_t n_cols, double* out_values, int64_t* out_index, int mem_kind, void* stream) {
-  return execute_values(p, "xhist_plan_execute_argextrema", samples, values, n_rows, n_cols, out_values, out_index != nullptr,
-                        "out_index is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-                          return xhist_argextrema_run(pl, samples, values, n_rows, n_cols, out_values, out_index,
-                                                      static_cast<hipStream_t>(stream), err, err_cap, desc, desc_cap);
-                        });
-}
-
-// the float64 block of `n` elements of a two-pass call for its sums of deviations ([n_rows, n_bins] of d or w*d; cov: two such
-// planes), freed with `scratch`; nullptr, with the message in `err` (`what` names the block there), when the allocation fails
-static double* two_pass_scratch(ScratchScope& scratch, int64_t n, const char* what, char* err, size_t err_cap) {
-  double* sd = nullptr;
-  if (scratch.alloc((void**)&sd, (size_t)n * sizeof(double)) == hipSuccess) return sd;
-  snprintf(err, err_cap, "allocation of the %s failed", what);
-  return nullptr;
+  return execute_values(p, "xhist_plan_execute_argextrema", samples, values, nullptr, nullptr, n_rows, n_cols, out_values,
+                        out_index != nullptr, "out_index is NULL", mem_kind, stream,
+                        [&](const ValuesCall& k) { return xhist_argextrema_run(k, out_values, out_index); });
 }
 
 extern "C" int xhist_plan_execute_mean_var(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
                                            int64_t n_cols, int64_t* out_count, double* out_mean, double* out_m2, int mem_kind, void* stream) {
-  return execute_values(p, "xhist_plan_execute_mean_var", samples, values, n_rows, n_cols, out_mean, out_count && out_m2,
-                        "out_count / out_m2 is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-                          hipStream_t s = static_cast<hipStream_t>(stream);
-                          ScratchScope scratch(s);
-                          double* sd = two_pass_scratch(scratch, n_rows * p->n_bins, "mean_var scratch block", err, err_cap);
-                          if (!sd) return (int)XHIST_ERR_NOMEM;
-                          return xhist_meanvar_run(pl, samples, values, n_rows, n_cols, out_count, out_mean, out_m2, sd, s, err, err_cap,
-                                                   desc, desc_cap);
-                        });
+  return execute_values(p, "xhist_plan_execute_mean_var", samples, values, nullptr, nullptr, n_rows, n_cols, out_mean, out_count && out_m2,
+                        "out_count / out_m2 is NULL", mem_kind, stream,
+                        [&](const ValuesCall& k) { return xhist_meanvar_run(k, out_count, out_mean, out_m2); });
 }
 
 extern "C" int xhist_plan_execute_mean_var_weighted(xhist_plan* p, const xhist_array* samples, const xhist_array* values,
@@ -348,29 +335,17 @@ extern "C" int xhist_plan_execute_mean_var_weighted(xhist_plan* p, const xhist_a
                                                     double* out_mean, double* out_m2, int mem_kind, void* stream) {
   if (!weights) return fail(XHIST_ERR_INVALID, "weights are required");
   if (int rc = validate_arrays(p, samples, weights, n_rows, n_cols, out_wsum, XHIST_F64)) return rc;
-  return execute_values(p, "xhist_plan_execute_mean_var_weighted", samples, values, n_rows, n_cols, out_mean, out_m2 != nullptr,
-                        "out_m2 is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-                          hipStream_t s = static_cast<hipStream_t>(stream);
-                          ScratchScope scratch(s);
-                          double* sd = two_pass_scratch(scratch, n_rows * p->n_bins, "weighted mean_var scratch block", err, err_cap);
-                          if (!sd) return (int)XHIST_ERR_NOMEM;
-                          return xhist_meanvar_w_run(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_m2, sd, s, err,
-                                                     err_cap, desc, desc_cap);
-                        });
+  return execute_values(p, "xhist_plan_execute_mean_var_weighted", samples, values, weights, nullptr, n_rows, n_cols, out_mean,
+                        out_m2 != nullptr, "out_m2 is NULL", mem_kind, stream,
+                        [&](const ValuesCall& k) { return xhist_meanvar_w_run(k, out_wsum, out_mean, out_m2); });
 }
 
 extern "C" int xhist_plan_execute_skew_kurt(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
                                             int64_t n_cols, int64_t* out_count, double* out_mean, double* out_moments, int mem_kind,
                                             void* stream) {
-  return execute_values(p, "xhist_plan_execute_skew_kurt", samples, values, n_rows, n_cols, out_mean, out_count && out_moments,
-                        "out_count / out_moments is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-                          hipStream_t s = static_cast<hipStream_t>(stream);
-                          ScratchScope scratch(s);
-                          double* sd = two_pass_scratch(scratch, n_rows * p->n_bins, "skew_kurt scratch block", err, err_cap);
-                          if (!sd) return (int)XHIST_ERR_NOMEM;
-                          return xhist_skew_kurt_run(pl, samples, values, n_rows, n_cols, out_count, out_mean, out_moments, sd, s, err,
-                                                     err_cap, desc, desc_cap);
-                        });
+  return execute_values(p, "xhist_plan_execute_skew_kurt", samples, values, nullptr, nullptr, n_rows, n_cols, out_mean,
+                        out_count && out_moments, "out_count / out_moments is NULL", mem_kind, stream,
+                        [&](const ValuesCall& k) { return xhist_skew_kurt_run(k, out_count, out_mean, out_moments); });
 }
 
 extern "C" int xhist_plan_execute_skew_kurt_weighted(xhist_plan* p, const xhist_array* samples, const xhist_array* values,
@@ -378,15 +353,9 @@ extern "C" int xhist_plan_execute_skew_kurt_weighted(xhist_plan* p, const xhist_
                                                      double* out_mean, double* out_moments, int mem_kind, void* stream) {
   if (!weights) return fail(XHIST_ERR_INVALID, "weights are required");
   if (int rc = validate_arrays(p, samples, weights, n_rows, n_cols, out_wsum, XHIST_F64)) return rc;
-  return execute_values(p, "xhist_plan_execute_skew_kurt_weighted", samples, values, n_rows, n_cols, out_mean, out_moments != nullptr,
-                        "out_moments is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-                          hipStream_t s = static_cast<hipStream_t>(stream);
-                          ScratchScope scratch(s);
-                          double* sd = two_pass_scratch(scratch, n_rows * p->n_bins, "weighted skew_kurt scratch block", err, err_cap);
-                          if (!sd) return (int)XHIST_ERR_NOMEM;
-                          return xhist_skew_kurt_w_run(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_moments, sd, s,
-                                                       err, err_cap, desc, desc_cap);
-                        });
+  return execute_values(p, "xhist_plan_execute_skew_kurt_weighted", samples, values, weights, nullptr, n_rows, n_cols, out_mean,
+                        out_moments != nullptr, "out_moments is NULL", mem_kind, stream,
+                        [&](const ValuesCall& k) { return xhist_skew_kurt_w_run(k, out_wsum, out_mean, out_moments); });
 }
 
 extern "C" int xhist_plan_execute_cov(xhist_plan* p, const xhist_array* samples, const xhist_array* values_a, const xhist_array* values_b,
@@ -394,15 +363,9 @@ extern "C" int xhist_plan_execute_cov(xhist_plan* p, const xhist_array* samples,
                                       int mem_kind, void* stream) {
   if (!values_b) return fail(XHIST_ERR_INVALID, "values_b are required");
   if (int rc = validate_arrays(p, samples, values_b, n_rows, n_cols, out_mean, XHIST_F64)) return rc;
-  return execute_values(p, "xhist_plan_execute_cov", samples, values_a, n_rows, n_cols, out_mean, out_count && out_comoment,
-                        "out_count / out_comoment is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-                          hipStream_t s = static_cast<hipStream_t>(stream);
-                          ScratchScope scratch(s);
-                          double* sd = two_pass_scratch(scratch, 2 * n_rows * p->n_bins, "cov scratch blocks", err, err_cap);
-                          if (!sd) return (int)XHIST_ERR_NOMEM;
-                          return xhist_cov_run(pl, samples, values_a, values_b, n_rows, n_cols, out_count, out_mean, out_comoment, sd, s, err,
-                                               err_cap, desc, desc_cap);
-                        });
+  return execute_values(p, "xhist_plan_execute_cov", samples, values_a, values_b, nullptr, n_rows, n_cols, out_mean,
+                        out_count && out_comoment, "out_count / out_comoment is NULL", mem_kind, stream,
+                        [&](const ValuesCall& k) { return xhist_cov_run(k, out_count, out_mean, out_comoment); });
 }
 
 extern "C" int xhist_plan_execute_cov_weighted(xhist_plan* p, const xhist_array* samples, const xhist_array* values_a,
@@ -412,34 +375,17 @@ extern "C" int xhist_plan_execute_cov_weighted(xhist_plan* p, const xhist_array*
   if (!weights) return fail(XHIST_ERR_INVALID, "weights are required");
   if (int rc = validate_arrays(p, samples, values_b, n_rows, n_cols, out_mean, XHIST_F64)) return rc;
   if (int rc = validate_arrays(p, samples, weights, n_rows, n_cols, out_wsum, XHIST_F64)) return rc;
-  return execute_values(p, "xhist_plan_execute_cov_weighted", samples, values_a, n_rows, n_cols, out_mean, out_comoment != nullptr,
-                        "out_comoment is NULL", mem_kind, [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-                          hipStream_t s = static_cast<hipStream_t>(stream);
-                          ScratchScope scratch(s);
-                          double* sd = two_pass_scratch(scratch, 2 * n_rows * p->n_bins, "weighted cov scratch blocks", err, err_cap);
-                          if (!sd) return (int)XHIST_ERR_NOMEM;
-                          return xhist_cov_w_run(pl, samples, values_a, values_b, weights, n_rows, n_cols, out_wsum, out_mean, out_comoment,
-                                                 sd, s, err, err_cap, desc, desc_cap);
-                        });
-}
-
-// the scratch allocator of the quantile drivers (xhist_quantile_alloc_fn): ctx is the call's ScratchScope
-static void* quantile_scratch_alloc(void* ctx, size_t bytes) {
-  void* d = nullptr;
-  return static_cast<ScratchScope*>(ctx)->alloc(&d, bytes ? bytes : 8) == hipSuccess ? d : nullptr;
+  return execute_values(p, "xhist_plan_execute_cov_weighted", samples, values_a, values_b, weights, n_rows, n_cols, out_mean,
+                        out_comoment != nullptr, "out_comoment is NULL", mem_kind, stream,
+                        [&](const ValuesCall& k) { return xhist_cov_w_run(k, out_wsum, out_mean, out_comoment); });
 }
 
 extern "C" int xhist_plan_execute_quantile(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
                                            int64_t n_cols, const double* q, int n_q, int method, double* out, int mem_kind, void* stream) {
   if (n_q < 1 || !q) return fail(XHIST_ERR_INVALID, "q is NULL or n_q < 1");
   if (method < XHIST_Q_LINEAR || method > XHIST_Q_NEAREST) return fail(XHIST_ERR_INVALID, "unknown quantile method %d", method);
-  return execute_values(p, "xhist_plan_execute_quantile", samples, values, n_rows, n_cols, out, true, "", mem_kind,
-                        [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-                          hipStream_t s = static_cast<hipStream_t>(stream);
-                          ScratchScope scratch(s);
-                          return xhist_quantile_run(pl, samples, values, n_rows, n_cols, q, n_q, method, out, quantile_scratch_alloc,
-                                                    &scratch, s, err, err_cap, desc, desc_cap);
-                        });
+  return execute_values(p, "xhist_plan_execute_quantile", samples, values, nullptr, nullptr, n_rows, n_cols, out, true, "", mem_kind,
+                        stream, [&](const ValuesCall& k) { return xhist_quantile_run(k, q, n_q, method, out); });
 }
 
 extern "C" int xhist_plan_execute_quantile_weighted(xhist_plan* p, const xhist_array* samples, const xhist_array* values,
@@ -448,13 +394,8 @@ extern "C" int xhist_plan_execute_quantile_weighted(xhist_plan* p, const xhist_a
   if (n_q < 1 || !q) return fail(XHIST_ERR_INVALID, "q is NULL or n_q < 1");
   if (!weights) return fail(XHIST_ERR_INVALID, "weights are required");
   if (int rc = validate_arrays(p, samples, weights, n_rows, n_cols, out, XHIST_F64)) return rc;
-  return execute_values(p, "xhist_plan_execute_quantile_weighted", samples, values, n_rows, n_cols, out, true, "", mem_kind,
-                        [&](const ValuesPlan& pl, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-                          hipStream_t s = static_cast<hipStream_t>(stream);
-                          ScratchScope scratch(s);
-                          return xhist_quantile_w_run(pl, samples, values, weights, n_rows, n_cols, q, n_q, out, quantile_scratch_alloc,
-                                                      &scratch, s, err, err_cap, desc, desc_cap);
-                        });
+  return execute_values(p, "xhist_plan_execute_quantile_weighted", samples, values, weights, nullptr, n_rows, n_cols, out, true, "",
+                        mem_kind, stream, [&](const ValuesCall& k) { return xhist_quantile_w_run(k, q, n_q, out); });
 }
 
 // ------------------------------------------------------------------------------------------

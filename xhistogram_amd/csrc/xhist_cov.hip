@@ -40,9 +40,6 @@ struct Cov {
   static constexpr const char *name = "cov", *prefix = "cov", *spelled = "cov";
 };
 
-int xhist_cov_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values_a, const xhist_array* values_b,
-                  int64_t n_rows, int64_t n_cols, int64_t* out_count, double* out_mean, double* out_comoment, double* sd,
-                  hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-  return two_pass_run<Cov>(pl, samples, values_a, values_b, n_rows, n_cols, reinterpret_cast<unsigned long long*>(out_count), out_mean,
-                           out_comoment, sd, stream, err, err_cap, desc, desc_cap);
+int xhist_cov_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2) {
+  return two_pass_run<Cov>(k, static_cast<unsigned long long*>(out_first), out_mean, out_m2);
 }

@@ -32,11 +32,3 @@ __global__ void __launch_bounds__(256) cov_dev_fast(const CovParams p) {
 }
 
 }  // namespace xhist
-
-// The launches of histogram_cov for DEVICE arrays the caller has validated, n_rows * n_bins > 0, the plan's device current
-// (two_pass_run<Cov>, xhist_cov.hip).  out_mean is [2, n_rows, n_bins] (mean_a, mean_b), out_comoment [3, n_rows, n_bins] (M2_a, C_ab, M2_b), `sd`
-// a float64 [2, n_rows, n_bins] block of the caller's for the sums of da and db.  Returns XHIST_OK, or an error status with a
-// message in `err`; `desc` receives a line about the launches.  (Called by xhist_plan_execute_cov, xhist_capi.hip.)
-int xhist_cov_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values_a, const xhist_array* values_b,
-                  int64_t n_rows, int64_t n_cols, int64_t* out_count, double* out_mean, double* out_comoment, double* sd,
-                  hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap);

@@ -41,9 +41,6 @@ struct CovW {
   static constexpr const char *name = "cov_w", *prefix = "covw", *spelled = "weighted cov";
 };
 
-int xhist_cov_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values_a, const xhist_array* values_b,
-                    const xhist_array* weights, int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_comoment,
-                    double* sd, hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-  return two_pass_run<CovW>(pl, samples, values_a, values_b, n_rows, n_cols, out_wsum, out_mean, out_comoment, sd, stream, err, err_cap,
-                            desc, desc_cap, weights);
+int xhist_cov_w_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2) {
+  return two_pass_run<CovW>(k, static_cast<double*>(out_first), out_mean, out_m2);
 }

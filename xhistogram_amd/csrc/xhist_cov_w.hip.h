@@ -33,12 +33,3 @@ __global__ void __launch_bounds__(256) covw_dev_fast(const CovWParams p) {
 }
 
 }  // namespace xhist
-
-// The launches of histogram_weighted_cov for DEVICE arrays the caller has validated, n_rows * n_bins > 0, the plan's device
-// current (two_pass_run<CovW>, xhist_cov_w.hip).  out_wsum is [n_rows, n_bins], out_mean [2, n_rows, n_bins] (mean_a, mean_b),
-// out_comoment [3, n_rows, n_bins] (M2_a, C_ab, M2_b), `sd` a float64 [2, n_rows, n_bins] block of the caller's for the sums
-// of w*da and w*db.  Returns XHIST_OK, or an error status with a message in `err`; `desc` receives a line about the launches.
-// (Called by xhist_plan_execute_cov_weighted, xhist_capi.hip.)
-int xhist_cov_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values_a, const xhist_array* values_b,
-                    const xhist_array* weights, int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_comoment,
-                    double* sd, hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap);

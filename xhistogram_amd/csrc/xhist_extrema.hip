@@ -73,35 +73,28 @@ struct ExtremaKernels {
 // a bin's minimum and maximum keys, in the one pass
 static constexpr ValuesSlots kExtremaSlots = {{16, 0}, {8, 0}, false};
 
-int xhist_extrema_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
-                      double* out_min, double* out_max, int accumulate, hipStream_t stream, char* err, size_t err_cap, char* desc,
-                      size_t desc_cap) {
-  const int64_t n_out = n_rows * pl.n_bins;
+int xhist_extrema_run(const ValuesCall& k, double* out_min, double* out_max, int accumulate) {
+  const ValuesPlan& pl = k.pl;
+  const int64_t n_out = k.n_rows * pl.n_bins;
   uint64_t* kmin = reinterpret_cast<uint64_t*>(out_min);
   uint64_t* kmax = reinterpret_cast<uint64_t*>(out_max);
   const int grid_io = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_out + 255) / 256));
-  XH_VALUES_LAUNCH(extrema_prepare, dim3(grid_io), dim3(256), 0, stream, kmin, kmax, n_out, accumulate);
-  XH_VALUES_LAUNCH_CHECK("extrema_prepare launch");
+  XH_VALUES_LAUNCH(extrema_prepare, dim3(grid_io), dim3(256), 0, k.stream, kmin, kmax, n_out, accumulate);
+  XH_VALUES_LAUNCH_CHECK(k, "extrema_prepare launch");
 
-  if (n_cols > 0) {
-    const ValuesChoice c = choose_values(pl, kExtremaSlots, samples, values, n_cols);
+  if (k.n_cols > 0) {
+    const ValuesChoice c = choose_values(k, kExtremaSlots);
     const values_fn fn = pick_values_kernel<ExtremaKernels>(c, pl);
-    if (!fn) {
-      snprintf(err, err_cap, "internal: no extrema kernel for this combination");
-      return XHIST_ERR_HIP;
-    }
-    if (int rc = allow_values_lds(fn, c.lds_bytes[0], "extrema: setting the dynamic LDS size failed", err, err_cap)) return rc;
-    const ValuesGeometry g = values_geometry(pl, c, n_rows, n_cols);
-    if (int rc = launch_values_pass(fn, c.lds_bytes[0], "extrema launch", pl, c, g, samples, values, n_rows, n_cols, kmin, kmax, nullptr,
-                                    stream, err, err_cap))
-      return rc;
-    if (desc && desc_cap)
-      snprintf(desc, desc_cap, "extrema family=%s slots=%s scan=%d block=%d segs=%lld lds_bytes=%zu tables_in_lds=%d D=%d cmp=%d",
+    if (!fn) return k.fail(XHIST_ERR_HIP, "internal: no extrema kernel for this combination");
+    if (int rc = allow_values_lds(k, fn, c.lds_bytes[0], "extrema: setting the dynamic LDS size failed")) return rc;
+    const ValuesGeometry g = values_geometry(pl, c, k.n_rows, k.n_cols);
+    if (int rc = launch_values_pass(fn, c.lds_bytes[0], "extrema launch", k, c, g, kmin, kmax, nullptr)) return rc;
+    k.describe("extrema family=%s slots=%s scan=%d block=%d segs=%lld lds_bytes=%zu tables_in_lds=%d D=%d cmp=%d",
                c.fast ? "fast" : "generic", c.lds ? "lds" : "global", c.scan, g.block, (long long)g.segs, c.lds_bytes[0],
                (int)c.tables_in_lds, pl.n_dims, values_cmp(pl));
   }
-  XH_VALUES_LAUNCH(extrema_finalize, dim3(grid_io), dim3(256), 0, stream, kmin, kmax, n_out);
-  XH_VALUES_LAUNCH_CHECK("extrema_finalize launch");
+  XH_VALUES_LAUNCH(extrema_finalize, dim3(grid_io), dim3(256), 0, k.stream, kmin, kmax, n_out);
+  XH_VALUES_LAUNCH_CHECK(k, "extrema_finalize launch");
   return XHIST_OK;
 }
 
@@ -117,53 +110,42 @@ struct ArgextKernels {
 // between the 16- and the 32-byte LDS capacity pass 1 runs where pass 2 must, not where histogram_extrema alone would.
 static constexpr ValuesSlots kArgextremaSlots = {{16, 32}, {8, 24}, false};
 
-int xhist_argextrema_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
-                         double* out_values, int64_t* out_index, hipStream_t stream, char* err, size_t err_cap, char* desc,
-                         size_t desc_cap) {
-  const int64_t n_out = n_rows * pl.n_bins;
+int xhist_argextrema_run(const ValuesCall& k, double* out_values, int64_t* out_index) {
+  const ValuesPlan& pl = k.pl;
+  const int64_t n_out = k.n_rows * pl.n_bins;
   uint64_t* kmin = reinterpret_cast<uint64_t*>(out_values);
   uint64_t* kmax = kmin + n_out;
   uint64_t* index = reinterpret_cast<uint64_t*>(out_index);
   const int grid_io = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_out + 255) / 256));
-  XH_VALUES_LAUNCH(extrema_prepare, dim3(grid_io), dim3(256), 0, stream, kmin, kmax, n_out, 0);
-  XH_VALUES_LAUNCH_CHECK("extrema_prepare launch");
-  XH_VALUES_LAUNCH(argext_prepare, dim3(grid_io), dim3(256), 0, stream, index, 2 * n_out);
-  XH_VALUES_LAUNCH_CHECK("argext_prepare launch");
+  XH_VALUES_LAUNCH(extrema_prepare, dim3(grid_io), dim3(256), 0, k.stream, kmin, kmax, n_out, 0);
+  XH_VALUES_LAUNCH_CHECK(k, "extrema_prepare launch");
+  XH_VALUES_LAUNCH(argext_prepare, dim3(grid_io), dim3(256), 0, k.stream, index, 2 * n_out);
+  XH_VALUES_LAUNCH_CHECK(k, "argext_prepare launch");
 
-  if (n_cols > 0) {
-    const ValuesChoice c = choose_values(pl, kArgextremaSlots, samples, values, n_cols);
+  if (k.n_cols > 0) {
+    const ValuesChoice c = choose_values(k, kArgextremaSlots);
     const values_fn pass1 = pick_values_kernel<ExtremaKernels>(c, pl);
     const auto pass2 = pick_values_kernel<ArgextKernels>(c, pl);
-    if (!pass1 || !pass2) {
-      snprintf(err, err_cap, "internal: no argextrema kernel for this combination");
-      return XHIST_ERR_HIP;
-    }
+    if (!pass1 || !pass2) return k.fail(XHIST_ERR_HIP, "internal: no argextrema kernel for this combination");
     const char* lds_what = "argextrema: setting the dynamic LDS size failed";
-    if (int rc = allow_values_lds(pass1, c.lds_bytes[0], lds_what, err, err_cap)) return rc;
-    if (int rc = allow_values_lds(pass2, c.lds_bytes[1], lds_what, err, err_cap)) return rc;
+    if (int rc = allow_values_lds(k, pass1, c.lds_bytes[0], lds_what)) return rc;
+    if (int rc = allow_values_lds(k, pass2, c.lds_bytes[1], lds_what)) return rc;
     // Family and home are the larger pass's; the residency, hence the segments per row, is each pass's own.  Neither result
     // depends on it, and pass 1's slots are half of pass 2's: with 50 x 50 bins it keeps three workgroups on a CU where pass
     // 2 keeps one, and runs as fast as histogram_extrema alone (0.77 ms against 0.89 ms for 2e8 float64 pairs).
     ValuesChoice c1 = c;
     c1.lds_bytes[1] = 0;
-    const ValuesGeometry g1 = values_geometry(pl, c1, n_rows, n_cols), g = values_geometry(pl, c, n_rows, n_cols);
-    if (int rc = launch_values_pass(pass1, c.lds_bytes[0], "extrema launch", pl, c, g1, samples, values, n_rows, n_cols, kmin, kmax,
-                                    nullptr, stream, err, err_cap))
-      return rc;
-    if (int rc = launch_values_pass(pass2, c.lds_bytes[1], "argext launch", pl, c, g, samples, values, n_rows, n_cols, index,
-                                    index + n_out, kmin, stream, err, err_cap))
-      return rc;
-    if (desc && desc_cap) {
-      const char* fam = c.fast ? "fast" : "generic";
-      const char* home = c.lds ? "lds" : "global";
-      snprintf(desc, desc_cap,
-               "argextrema pass1=extrema_%s slots=%s pass2=argext_%s slots=%s scan=%d block=%d segs=%lld/%lld lds_bytes=%zu/%zu "
+    const ValuesGeometry g1 = values_geometry(pl, c1, k.n_rows, k.n_cols), g = values_geometry(pl, c, k.n_rows, k.n_cols);
+    if (int rc = launch_values_pass(pass1, c.lds_bytes[0], "extrema launch", k, c, g1, kmin, kmax, nullptr)) return rc;
+    if (int rc = launch_values_pass(pass2, c.lds_bytes[1], "argext launch", k, c, g, index, index + n_out, kmin)) return rc;
+    const char* fam = c.fast ? "fast" : "generic";
+    const char* home = c.lds ? "lds" : "global";
+    k.describe("argextrema pass1=extrema_%s slots=%s pass2=argext_%s slots=%s scan=%d block=%d segs=%lld/%lld lds_bytes=%zu/%zu "
                "tables_in_lds=%d D=%d cmp=%d",
-               fam, home, fam, home, c.scan, g.block, (long long)g1.segs, (long long)g.segs, c.lds_bytes[0], c.lds_bytes[1], (int)c.tables_in_lds,
-               pl.n_dims, values_cmp(pl));
-    }
+               fam, home, fam, home, c.scan, g.block, (long long)g1.segs, (long long)g.segs, c.lds_bytes[0], c.lds_bytes[1],
+               (int)c.tables_in_lds, pl.n_dims, values_cmp(pl));
   }
-  XH_VALUES_LAUNCH(argext_finalize, dim3(grid_io), dim3(256), 0, stream, kmin, kmax, index, n_out);
-  XH_VALUES_LAUNCH_CHECK("argext_finalize launch");
+  XH_VALUES_LAUNCH(argext_finalize, dim3(grid_io), dim3(256), 0, k.stream, kmin, kmax, index, n_out);
+  XH_VALUES_LAUNCH_CHECK(k, "argext_finalize launch");
   return XHIST_OK;
 }

@@ -1,5 +1,6 @@
 // xhist_extrema.hip.h — per-bin minimum and maximum of a value array (histogram_extrema): the keys, the statistic's policy
-// for the shared kernel skeletons of xhist_values.hip.h, its binning kernels, and the driver of xhist_extrema.hip.
+// for the shared kernel skeletons of xhist_values.hip.h, and its binning kernels (the drivers of xhist_extrema.hip are declared in
+// xhist_values_api.h).
 //
 // Which samples count is decided exactly as for the histogram: the same digitize, the same tables.  What a counted sample
 // contributes is its value, converted to float64 (numpy's astype) and mapped to an order-preserving unsigned key
@@ -268,17 +269,3 @@ __global__ void __launch_bounds__(256) argext_fast(const CovParams p) {
 }
 
 }  // namespace xhist
-
-// The three launches on `stream` (prepare, binning, finalize) for DEVICE arrays the caller has validated, n_rows and n_cols
-// > 0, the plan's device current.  Returns XHIST_OK, or an error status with a message in `err`; `desc` receives a line
-// about the launch.  (Called by xhist_plan_execute_extrema, xhist_capi.hip.)
-int xhist_extrema_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
-                      double* out_min, double* out_max, int accumulate, hipStream_t stream, char* err, size_t err_cap, char* desc,
-                      size_t desc_cap);
-
-// histogram_argextrema's launches on `stream` (the two prepares, pass 1, pass 2, finalize), under the same conditions.
-// out_values is [2, n_rows, n_bins] (minimum, maximum), out_index [2, n_rows, n_bins] int64 (their positions; -1: empty bin).
-// (Called by xhist_plan_execute_argextrema, xhist_capi.hip.)
-int xhist_argextrema_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
-                         double* out_values, int64_t* out_index, hipStream_t stream, char* err, size_t err_cap, char* desc,
-                         size_t desc_cap);

@@ -41,11 +41,8 @@ struct MeanVar {
   static constexpr const char *name = "mean_var", *prefix = "mv", *spelled = "mean_var";
 };
 
-int xhist_meanvar_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
-                      int64_t* out_count, double* out_mean, double* out_m2, double* sd, hipStream_t stream, char* err, size_t err_cap,
-                      char* desc, size_t desc_cap) {
-  return two_pass_run<MeanVar>(pl, samples, values, nullptr, n_rows, n_cols, reinterpret_cast<unsigned long long*>(out_count), out_mean,
-                               out_m2, sd, stream, err, err_cap, desc, desc_cap);
+int xhist_meanvar_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2) {
+  return two_pass_run<MeanVar>(k, static_cast<unsigned long long*>(out_first), out_mean, out_m2);
 }
 
 // ---- histogram_skew_kurt: mean_var's pass 1, then the four sums of pass 2 ------------------------------------------------------
@@ -68,9 +65,6 @@ struct SkewKurt {
   static constexpr const char *name = "skew_kurt", *prefix = "sk", *sum_prefix = "mv", *spelled = "skew_kurt";
 };
 
-int xhist_skew_kurt_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
-                        int64_t* out_count, double* out_mean, double* out_moments, double* sd, hipStream_t stream, char* err,
-                        size_t err_cap, char* desc, size_t desc_cap) {
-  return two_pass_run<SkewKurt>(pl, samples, values, nullptr, n_rows, n_cols, reinterpret_cast<unsigned long long*>(out_count), out_mean,
-                                out_moments, sd, stream, err, err_cap, desc, desc_cap);
+int xhist_skew_kurt_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2) {
+  return two_pass_run<SkewKurt>(k, static_cast<unsigned long long*>(out_first), out_mean, out_m2);
 }

@@ -74,32 +74,3 @@ __global__ void __launch_bounds__(256) skw_dev_fast(const CovParams p) {
 }
 
 }  // namespace xhist
-
-// ---- host side ---------------------------------------------------------------------------------------------------------------
-// The launches of histogram_mean_var for DEVICE arrays the caller has validated, n_rows * n_bins > 0, the plan's device
-// current (two_pass_run<MeanVar>, xhist_meanvar.hip).  `sd` is a float64 [n_rows, n_bins] block of the caller's for the sums of
-// d.  Returns XHIST_OK, or an error status with a message in `err`; `desc` receives a line about the launches.  (Called by
-// xhist_plan_execute_mean_var, xhist_capi.hip.)
-int xhist_meanvar_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
-                      int64_t* out_count, double* out_mean, double* out_m2, double* sd, hipStream_t stream, char* err, size_t err_cap,
-                      char* desc, size_t desc_cap);
-
-// The same for the weighted form (two_pass_run<MeanVarW>, xhist_meanvar_w.hip): `weights` a validated DEVICE array of the
-// samples' logical shape, the sums of weights into out_wsum (float64).  (Called by xhist_plan_execute_mean_var_weighted,
-// xhist_capi.hip.)
-int xhist_meanvar_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
-                        int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_m2, double* sd, hipStream_t stream,
-                        char* err, size_t err_cap, char* desc, size_t desc_cap);
-
-// The launches of histogram_skew_kurt (two_pass_run<SkewKurt>, xhist_meanvar.hip): mean_var's pass 1 and means, then the four
-// sums of pass 2 and moments_finalize4.  out_moments is a float64 [3, n_rows, n_bins] block (M2, M3, M4), `sd` a float64
-// [n_rows, n_bins] block of the caller's for D.  (Called by xhist_plan_execute_skew_kurt, xhist_capi.hip.)
-int xhist_skew_kurt_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
-                        int64_t* out_count, double* out_mean, double* out_moments, double* sd, hipStream_t stream, char* err,
-                        size_t err_cap, char* desc, size_t desc_cap);
-
-// The same for the weighted form (two_pass_run<SkewKurtW>, xhist_meanvar_w.hip).  (Called by
-// xhist_plan_execute_skew_kurt_weighted, xhist_capi.hip.)
-int xhist_skew_kurt_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
-                          int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_moments, double* sd,
-                          hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap);

@@ -43,11 +43,8 @@ struct MeanVarW {
   static constexpr const char *name = "mean_var_w", *prefix = "mvw", *spelled = "weighted mean_var";
 };
 
-int xhist_meanvar_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
-                        int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_m2, double* sd, hipStream_t stream,
-                        char* err, size_t err_cap, char* desc, size_t desc_cap) {
-  return two_pass_run<MeanVarW>(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_m2, sd, stream, err, err_cap, desc,
-                                desc_cap);
+int xhist_meanvar_w_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2) {
+  return two_pass_run<MeanVarW>(k, static_cast<double*>(out_first), out_mean, out_m2);
 }
 
 // ---- the weighted histogram_skew_kurt: the weighted mean_var's pass 1, then the four sums of pass 2 ----------------------------
@@ -70,9 +67,6 @@ struct SkewKurtW {
   static constexpr const char *name = "skew_kurt_w", *prefix = "skw", *sum_prefix = "mvw", *spelled = "weighted skew_kurt";
 };
 
-int xhist_skew_kurt_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
-                          int64_t n_rows, int64_t n_cols, double* out_wsum, double* out_mean, double* out_moments, double* sd,
-                          hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-  return two_pass_run<SkewKurtW>(pl, samples, values, weights, n_rows, n_cols, out_wsum, out_mean, out_moments, sd, stream, err,
-                                 err_cap, desc, desc_cap);
+int xhist_skew_kurt_w_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2) {
+  return two_pass_run<SkewKurtW>(k, static_cast<double*>(out_first), out_mean, out_m2);
 }

@@ -142,13 +142,11 @@ constexpr void (*kShortKernels[3])(const Params, const QStep) = {q_short<0>, q_s
 
 }  // namespace
 
-int xhist_quantile_run(const ValuesPlan& pl_in, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
-                       const double* q, int n_q, int method, double* out, xhist_quantile_alloc_fn alloc, void* alloc_ctx,
-                       hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-  ValuesPlan pl = pl_in;
-  pl.lds_max -= 64;  // (the launch header q_hdr() is static LDS next to the dynamic slots)
-  const QCall k = {pl, samples, values, nullptr, n_rows, n_cols, q, n_q, stream, err, err_cap};
-  const int64_t bins = pl.n_bins;
+int xhist_quantile_run(const ValuesCall& call, const double* q, int n_q, int method, double* out) {
+  const QuantileCall k(call, q, n_q);
+  const ValuesPlan& pl = k.pl;
+  const int64_t bins = pl.n_bins, n_rows = k.n_rows;
+  const hipStream_t stream = k.stream;
   QStep st;
   memset(&st, 0, sizeof st);
   st.bins = bins;
@@ -157,12 +155,11 @@ int xhist_quantile_run(const ValuesPlan& pl_in, const xhist_array* samples, cons
   st.out = out;
 
   // ---- short rows: one workgroup sorts whole rows in LDS -------------------------------------------------------------------
-  if (n_cols <= kQShortCols) {
+  if (k.n_cols <= kQShortCols) {
     QShort sh;
     if (int rc = launch_quantile_short(k, kShortKernels, st, kQShortCols, 12, sh)) return rc;
-    if (desc && desc_cap)
-      snprintf(desc, desc_cap, "quantile family=short rows_per_wg=%lld pairs=%u lds_bytes=%zu groups=%d block=256 D=%d cmp=%d",
-               (long long)sh.R, sh.N, sh.lds, (n_q + kQGroup - 1) / kQGroup, pl.n_dims, values_cmp(pl));
+    k.describe("quantile family=short rows_per_wg=%lld pairs=%u lds_bytes=%zu groups=%d block=256 D=%d cmp=%d", (long long)sh.R, sh.N,
+               sh.lds, (n_q + kQGroup - 1) / kQGroup, pl.n_dims, values_cmp(pl));
     return XHIST_OK;
   }
 
@@ -175,18 +172,16 @@ int xhist_quantile_run(const ValuesPlan& pl_in, const xhist_array* samples, cons
   if (int rc = pick_pass<QWinKernels>(winG, k, win_bytes(G), r.chunk, "window")) return rc;
 
   const size_t n_rb = (size_t)r.chunk * bins;
-  QWin* w0 = static_cast<QWin*>(alloc(alloc_ctx, n_rb * sizeof(QWin)));
-  QWin* wg = static_cast<QWin*>(alloc(alloc_ctx, n_rb * G * sizeof(QWin)));
-  QTgt* tg = static_cast<QTgt*>(alloc(alloc_ctx, n_rb * G * sizeof(QTgt)));
-  unsigned long long* cnt = static_cast<unsigned long long*>(alloc(alloc_ctx, (n_rb * G << d) * 8));
-  uint32_t* flags = static_cast<uint32_t*>(alloc(alloc_ctx, 8 * ((size_t)passes + 8)));
-  if (!w0 || !wg || !tg || !cnt || !flags) {
-    snprintf(err, err_cap, "allocation of the quantile scratch (%zu bytes per chunk) failed", radix_row_bytes(bins, G, d) * r.chunk);
-    return XHIST_ERR_NOMEM;
-  }
+  QWin* w0 = static_cast<QWin*>(k.scratch(n_rb * sizeof(QWin)));
+  QWin* wg = static_cast<QWin*>(k.scratch(n_rb * G * sizeof(QWin)));
+  QTgt* tg = static_cast<QTgt*>(k.scratch(n_rb * G * sizeof(QTgt)));
+  unsigned long long* cnt = static_cast<unsigned long long*>(k.scratch((n_rb * G << d) * 8));
+  uint32_t* flags = static_cast<uint32_t*>(k.scratch(8 * ((size_t)passes + 8)));
+  if (!w0 || !wg || !tg || !cnt || !flags)
+    return k.fail(XHIST_ERR_NOMEM, "allocation of the quantile scratch (%zu bytes per chunk) failed", radix_row_bytes(bins, G, d) * r.chunk);
   const int64_t n_flag_words = (3 + passes + 1) / 2;  // flags: [0] pass 0, [1 + j] digit pass j, [2 + passes] the successor
   XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3(2048), dim3(256), 0, stream, cnt, (int64_t)(n_rb * G << d));
-  XH_VALUES_LAUNCH_CHECK("quantile zeroing launch");
+  XH_VALUES_LAUNCH_CHECK(k, "quantile zeroing launch");
   st.tgt = tg;
   st.win0 = w0;
   st.win = wg;
@@ -199,34 +194,34 @@ int xhist_quantile_run(const ValuesPlan& pl_in, const xhist_array* samples, cons
     st.row0 = r0;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (nr * bins * G + 255) / 256));
     XH_VALUES_LAUNCH(q_window, dim3(grid), dim3(256), 0, stream, st, 0);
-    XH_VALUES_LAUNCH_CHECK("q_window launch");
+    XH_VALUES_LAUNCH_CHECK(k, "q_window launch");
     if (int rc = launch_quantile_pass(win0, k, r0, nr, w0, bins * sizeof(QWin), nullptr, 0, flags, 1, d, "quantile window launch"))
       return rc;
     for (int g0 = 0; g0 < n_q; g0 += G) {
       quantile_group(st, k, g0, G);
       // the flags of the digit passes and of the successor start at zero for every group (pass 0 has run: its flag may go too)
       XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3(1), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(flags), n_flag_words);
-      XH_VALUES_LAUNCH_CHECK("quantile zeroing launch");
+      XH_VALUES_LAUNCH_CHECK(k, "quantile zeroing launch");
       XH_VALUES_LAUNCH(q_init, dim3(grid), dim3(256), 0, stream, st);
-      XH_VALUES_LAUNCH_CHECK("q_init launch");
+      XH_VALUES_LAUNCH_CHECK(k, "q_init launch");
       for (int j = 0; j < passes; ++j) {
         st.pass = j;
         if (int rc = launch_quantile_pass(digit, k, r0, nr, cnt, ((size_t)bins * st.G * 8) << d, tg, sizeof(QTgt), flags + 1 + j, st.G, d,
                                           "quantile digit launch"))
           return rc;
         XH_VALUES_LAUNCH(q_select, dim3(grid), dim3(256), 0, stream, st);
-        XH_VALUES_LAUNCH_CHECK("q_select launch");
+        XH_VALUES_LAUNCH_CHECK(k, "q_select launch");
       }
       st.pass = passes;
       XH_VALUES_LAUNCH(q_window, dim3(grid), dim3(256), 0, stream, st, 1);
-      XH_VALUES_LAUNCH_CHECK("q_window launch");
+      XH_VALUES_LAUNCH_CHECK(k, "q_window launch");
       if (int rc = launch_quantile_pass(winG, k, r0, nr, wg, bins * st.G * sizeof(QWin), nullptr, 0, flags + 2 + passes, st.G, d,
                                         "quantile successor launch"))
         return rc;
       XH_VALUES_LAUNCH(q_finalize, dim3(grid), dim3(256), 0, stream, st);
-      XH_VALUES_LAUNCH_CHECK("q_finalize launch");
+      XH_VALUES_LAUNCH_CHECK(k, "q_finalize launch");
     }
   }
-  describe_quantile_radix(desc, desc_cap, "quantile", k, r, win0, digit, &winG);
+  describe_quantile_radix("quantile", k, r, win0, digit, &winG);
   return XHIST_OK;
 }

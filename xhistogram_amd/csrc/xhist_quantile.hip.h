@@ -1,7 +1,7 @@
 // xhist_quantile.hip.h — exact per-bin quantiles of a value array (histogram_quantile): the state of a selection, the two
 // policies it plugs into the shared kernel skeletons of xhist_values.hip.h, its binning kernels, the short-row kernel, the
 // host steps that the driver of xhist_quantile.hip shares with the weighted one of xhist_quantile_w.hip (templates over the
-// launch-parameter type, at the end), and the driver's declaration.
+// launch-parameter type, at the end; the drivers are declared in xhist_values_api.h).
 //
 // Which samples count is decided exactly as for the histogram: the same digitize, the same tables.  A counted sample whose
 // value (converted to float64) is not NaN contributes the order-preserving key of that value (extrema_key64: unsigned order
@@ -359,21 +359,16 @@ __global__ void __launch_bounds__(256) q_short(const Params p, const QStep st) {
 // ---- host side: the steps the driver shares with the weighted one (xhist_quantile_w.hip) ------------------------------------
 // Templates over the launch-parameter type P (Params, or WParams for the weighted kernels), as launch_values_pass<P> is.
 
-// what stays the same through one call: the plan (its lds_max less the launch header), the inputs (weights nullptr: the
-// unweighted statistic), the quantiles, the stream, and where an error message goes
-struct QCall {
-  const ValuesPlan& pl;
-  const xhist_array *samples, *values, *weights;
-  int64_t n_rows, n_cols;
+// a quantile driver's call: the caller's record with the driver's own copy of the plan (its lds_max less the launch header
+// q_hdr(), static LDS next to the dynamic slots), and the quantiles; `third` the weights (nullptr: the unweighted statistic)
+struct QuantileCall : ValuesCall {
   const double* q;
   int n_q;
-  hipStream_t stream;
-  char* err;
-  size_t err_cap;
+  QuantileCall(const ValuesCall& k, const double* q, int n_q) : ValuesCall(k), q(q), n_q(n_q) { pl.lds_max -= 64; }
   // the statistic in error messages
-  const char* name() const { return weights ? "weighted quantile" : "quantile"; }
+  const char* name() const { return third ? "weighted quantile" : "quantile"; }
   const char* lds_what() const {
-    return weights ? "weighted quantile: setting the dynamic LDS size failed" : "quantile: setting the dynamic LDS size failed";
+    return third ? "weighted quantile: setting the dynamic LDS size failed" : "quantile: setting the dynamic LDS size failed";
   }
 };
 
@@ -387,44 +382,39 @@ struct Pass {
 
 // the pass of kernel set K with `slot` bytes of LDS per bin, over chunks of `rows` rows
 template <class K, class P>
-static int pick_pass(Pass<P>& ps, const QCall& k, size_t slot, int64_t rows, const char* what) {
+static int pick_pass(Pass<P>& ps, const QuantileCall& k, size_t slot, int64_t rows, const char* what) {
   const ValuesSlots sl = {{slot, 0}, {slot, 0}, false};
-  ps.c = choose_values(k.pl, sl, k.samples, k.values, k.n_cols, k.weights);
+  ps.c = choose_values(k, sl);
   ps.fn = pick_values_kernel<K>(ps.c, k.pl);
-  if (!ps.fn) {
-    snprintf(k.err, k.err_cap, "internal: no %s %s kernel for this combination", k.name(), what);
-    return XHIST_ERR_HIP;
-  }
+  if (!ps.fn) return k.fail(XHIST_ERR_HIP, "internal: no %s %s kernel for this combination", k.name(), what);
   ps.g = values_geometry(k.pl, ps.c, rows, k.n_cols);
-  return allow_values_lds(ps.fn, ps.c.lds_bytes[0], k.lds_what(), k.err, k.err_cap);
+  return allow_values_lds(k, ps.fn, ps.c.lds_bytes[0], k.lds_what());
 }
 
 // One binning pass over rows [r0, r0 + nr) of a chunk: `recs` the launch's records (Params::out), `tgt` the targets of
 // `tgt_bytes` each (w2_ptr; nullptr: the pass reads none), `flag` its flag word, T records or targets per bin, digits of d bits.
 template <class P>
-static int launch_quantile_pass(const Pass<P>& ps, const QCall& k, int64_t r0, int64_t nr, void* recs, size_t rec_row_bytes,
+static int launch_quantile_pass(const Pass<P>& ps, const QuantileCall& k, int64_t r0, int64_t nr, void* recs, size_t rec_row_bytes,
                                 const void* tgt, size_t tgt_bytes, uint32_t* flag, int T, int d, const char* what) {
-  char* err = k.err;
-  const size_t err_cap = k.err_cap;
   for (int64_t i = 0; i < nr; i += ps.g.max_rows) {
     const int64_t n = std::min(ps.g.max_rows, nr - i);
     P kp;
-    static_cast<Params&>(kp) = values_params(k.pl, ps.c, ps.g.segs, k.samples, k.values, r0 + i, n, k.n_cols);
-    if constexpr (std::is_same<P, WParams>::value) weights_params(kp, k.weights);
+    static_cast<Params&>(kp) = values_params(k, ps.c, ps.g.segs, r0 + i, n);
+    if constexpr (std::is_same<P, WParams>::value) weights_params(kp, k.third);
     kp.out = static_cast<char*>(recs) + i * rec_row_bytes;
     kp.w2_ptr = reinterpret_cast<const uint64_t*>(tgt ? static_cast<const char*>(tgt) + i * k.pl.n_bins * T * tgt_bytes : nullptr);
     kp.part_counts = flag;
     kp.n_parts = T;
     kp.part_shift = d;
     XH_VALUES_LAUNCH(ps.fn, dim3((unsigned)(n * ps.g.segs)), dim3(ps.g.block), ps.c.lds_bytes[0], k.stream, kp);
-    XH_VALUES_LAUNCH_CHECK(what);
+    XH_VALUES_LAUNCH_CHECK(k, what);
   }
   return XHIST_OK;
 }
 
 // the targets of one group of a step struct (QStep, QWStep): q[g0 .. g0 + G), at most G of them
 template <class Step>
-static void quantile_group(Step& st, const QCall& k, int g0, int G) {
+static void quantile_group(Step& st, const QuantileCall& k, int g0, int G) {
   st.qi0 = g0;
   st.G = std::min(G, k.n_q - g0);
   for (int t = 0; t < st.G; ++t) st.q[t] = k.q[g0 + t];
@@ -439,7 +429,7 @@ struct QRadix {
   int G = 0, d = 0, passes = 0;
   int64_t chunk = 0;
 };
-static inline QRadix quantile_radix(const QCall& k, size_t (*digit_bytes)(int, int), size_t (*radix_row_bytes)(int64_t, int, int)) {
+static inline QRadix quantile_radix(const QuantileCall& k, size_t (*digit_bytes)(int, int), size_t (*radix_row_bytes)(int64_t, int, int)) {
   QRadix r;
   int64_t best = INT64_MAX;
   for (int tier = 0; tier < 3 && !r.G; ++tier) {
@@ -449,7 +439,7 @@ static inline QRadix quantile_radix(const QCall& k, size_t (*digit_bytes)(int, i
         if (cost >= best) continue;
         if (radix_row_bytes(k.pl.n_bins, g, dd) > kQScratchCap && !(g == 1 && dd == 1)) continue;
         const ValuesSlots sl = {{digit_bytes(g, dd), 0}, {digit_bytes(g, dd), 0}, false};
-        const ValuesChoice c = choose_values(k.pl, sl, k.samples, k.values, k.n_cols, k.weights);
+        const ValuesChoice c = choose_values(k, sl);
         if (c.lds != (tier < 2) || (tier == 0 && c.lds_bytes[0] > kQLdsBudget)) continue;
         best = cost;
         r.G = g;
@@ -464,20 +454,19 @@ static inline QRadix quantile_radix(const QCall& k, size_t (*digit_bytes)(int, i
 // the radix family's describe() line (`name`: quantile / weighted_quantile); `succ`: the unweighted family's successor pass
 // (nullptr: the statistic has none), appended as successor=<family>/<home>/<lds_bytes>
 template <class P>
-static void describe_quantile_radix(char* desc, size_t desc_cap, const char* name, const QCall& k, const QRadix& r, const Pass<P>& win0,
-                                    const Pass<P>& digit, const Pass<P>* succ = nullptr) {
-  if (!desc || !desc_cap) return;
+static void describe_quantile_radix(const char* name, const QuantileCall& k, const QRadix& r, const Pass<P>& win0, const Pass<P>& digit,
+                                    const Pass<P>* succ = nullptr) {
   auto fam = [](const Pass<P>& p) { return p.c.fast ? "fast" : "generic"; };
   auto home = [](const Pass<P>& p) { return p.c.lds ? "lds" : "global"; };
-  const int n = snprintf(desc, desc_cap,
+  const int n = snprintf(k.desc, k.desc_cap,
                          "%s family=radix window=%s/%s digits=%s/%s scan=%d/%d d=%d group=%d groups=%d passes=%d chunks=%lld "
                          "rows_per_chunk=%lld block=%d segs=%lld lds_bytes=%zu/%zu D=%d cmp=%d",
                          name, fam(win0), home(win0), fam(digit), home(digit), win0.c.scan, digit.c.scan, r.d, r.G,
                          (k.n_q + r.G - 1) / r.G, r.passes, (long long)((k.n_rows + r.chunk - 1) / r.chunk), (long long)r.chunk,
                          digit.g.block, (long long)digit.g.segs, win0.c.lds_bytes[0], digit.c.lds_bytes[0], k.pl.n_dims,
                          values_cmp(k.pl));
-  if (succ && n > 0 && (size_t)n < desc_cap)
-    snprintf(desc + n, desc_cap - n, " successor=%s/%s/%zu", fam(*succ), home(*succ), succ->c.lds_bytes[0]);
+  if (succ && n > 0 && (size_t)n < k.desc_cap)
+    snprintf(k.desc + n, k.desc_cap - n, " successor=%s/%s/%zu", fam(*succ), home(*succ), succ->c.lds_bytes[0]);
 }
 
 // The short-row family's launches: R whole rows per workgroup of 256 lanes (at most `short_cols` values in all, and R x bins
@@ -489,18 +478,14 @@ struct QShort {
   size_t lds = 0;
 };
 template <class P, class Step>
-static int launch_quantile_short(const QCall& k, void (*const (&fn)[3])(const P, const Step), Step& st, int short_cols,
+static int launch_quantile_short(const QuantileCall& k, void (*const (&fn)[3])(const P, const Step), Step& st, int short_cols,
                                  size_t elem_bytes, QShort& sh) {
-  char* err = k.err;
-  const size_t err_cap = k.err_cap;
   const int64_t R = std::max<int64_t>(1, std::min<int64_t>(short_cols / std::max<int64_t>(k.n_cols, 1), (((int64_t)1 << 32) - 2) / k.pl.n_bins));
   uint32_t N = 2;
   while (N < (uint32_t)(R * k.n_cols)) N <<= 1;
   const size_t lds = (size_t)N * elem_bytes;
   sh = QShort{R, N, lds};
-  if (lds > 48 * 1024)
-    return values_error(err, err_cap, XHIST_ERR_HIP, k.weights ? "internal: weighted short-row LDS" : "internal: short-row LDS",
-                        hipErrorInvalidValue);
+  if (lds > 48 * 1024) return values_error(k, k.third ? "internal: weighted short-row LDS" : "internal: short-row LDS", hipErrorInvalidValue);
   const int cmp = values_cmp(k.pl);
   const auto short_fn = fn[cmp == 0 ? 0 : cmp == 1 ? 1 : 2];
   const int64_t max_wg = ((int64_t)1 << 31) - 1;
@@ -511,26 +496,16 @@ static int launch_quantile_short(const QCall& k, void (*const (&fn)[3])(const P,
       ValuesChoice c;
       c.tab = &k.pl.native;
       P kp;
-      static_cast<Params&>(kp) = values_params(k.pl, c, 1, k.samples, k.values, r0, nr, k.n_cols);
-      if constexpr (std::is_same<P, WParams>::value) weights_params(kp, k.weights);
+      static_cast<Params&>(kp) = values_params(k, c, 1, r0, nr);
+      if constexpr (std::is_same<P, WParams>::value) weights_params(kp, k.third);
       kp.tables_in_lds = 0;  // (the tables are read through L2)
       kp.lane_rows = (int32_t)R;
       kp.slice_n = (int32_t)N;
       XH_VALUES_LAUNCH(short_fn, dim3((unsigned)((nr + R - 1) / R)), dim3(256), lds, k.stream, kp, st);
-      XH_VALUES_LAUNCH_CHECK(k.weights ? "qw_short launch" : "q_short launch");
+      XH_VALUES_LAUNCH_CHECK(k, k.third ? "qw_short launch" : "q_short launch");
     }
   }
   return XHIST_OK;
 }
 
 }  // namespace xhist
-
-// The launches on `stream` for DEVICE arrays the caller has validated, n_rows * n_bins > 0, the plan's device current: q (host,
-// n_q values in [0, 1]) and the method code (XHIST_Q_*) -> out, float64 [n_q, n_rows, n_bins].  Scratch comes from the
-// library's allocator through alloc(bytes) (nullptr: out of memory), freed by the caller after the call.  Returns XHIST_OK, or
-// an error status with a message in `err`; `desc` receives a line about the launches.  (Called by xhist_plan_execute_quantile,
-// xhist_capi.hip.)
-typedef void* (*xhist_quantile_alloc_fn)(void* ctx, size_t bytes);
-int xhist_quantile_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
-                       const double* q, int n_q, int method, double* out, xhist_quantile_alloc_fn alloc, void* alloc_ctx,
-                       hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap);

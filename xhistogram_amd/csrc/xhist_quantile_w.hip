@@ -118,13 +118,11 @@ constexpr void (*kShortKernels[3])(const WParams, const QWStep) = {qw_short<0>, 
 
 }  // namespace
 
-int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
-                         int64_t n_rows, int64_t n_cols, const double* q, int n_q, double* out, xhist_quantile_alloc_fn alloc,
-                         void* alloc_ctx, hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap) {
-  ValuesPlan pl = pl_in;
-  pl.lds_max -= 64;  // (the launch header q_hdr() is static LDS next to the dynamic slots)
-  const QCall k = {pl, samples, values, weights, n_rows, n_cols, q, n_q, stream, err, err_cap};
-  const int64_t bins = pl.n_bins;
+int xhist_quantile_w_run(const ValuesCall& call, const double* q, int n_q, double* out) {
+  const QuantileCall k(call, q, n_q);
+  const ValuesPlan& pl = k.pl;
+  const int64_t bins = pl.n_bins, n_rows = k.n_rows;
+  const hipStream_t stream = k.stream;
   QWStep st;
   memset(&st, 0, sizeof st);
   st.bins = bins;
@@ -132,38 +130,34 @@ int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, co
   st.out = out;
 
   // ---- short rows: one workgroup sorts whole rows in LDS -------------------------------------------------------------------
-  if (n_cols <= kQWShortCols) {
+  if (k.n_cols <= kQWShortCols) {
     QShort sh;
     if (int rc = launch_quantile_short(k, kShortKernels, st, kQWShortCols, 20, sh)) return rc;
-    if (desc && desc_cap)
-      snprintf(desc, desc_cap, "weighted_quantile family=short rows_per_wg=%lld triples=%u lds_bytes=%zu groups=%d block=256 D=%d cmp=%d",
-               (long long)sh.R, sh.N, sh.lds, (n_q + kQGroup - 1) / kQGroup, pl.n_dims, values_cmp(pl));
+    k.describe("weighted_quantile family=short rows_per_wg=%lld triples=%u lds_bytes=%zu groups=%d block=256 D=%d cmp=%d", (long long)sh.R,
+               sh.N, sh.lds, (n_q + kQGroup - 1) / kQGroup, pl.n_dims, values_cmp(pl));
     return XHIST_OK;
   }
 
   // ---- long rows: radix select, by the rule of the unweighted family over the 8-byte sums ------------------------------------
   const QRadix r = quantile_radix(k, digit_bytes, radix_row_bytes);
   const int G = r.G, d = r.d, passes = r.passes;
-  if ((uint64_t)r.chunk * (uint64_t)bins >> 32) {  // (the no-LDS window kernel indexes a launch's records in 32 bits)
-    snprintf(err, err_cap, "weighted quantiles of %lld bins are not supported (at most 2^32 - 1)", (long long)bins);
-    return XHIST_ERR_UNSUPPORTED;
-  }
+  if ((uint64_t)r.chunk * (uint64_t)bins >> 32)  // (the no-LDS window kernel indexes a launch's records in 32 bits)
+    return k.fail(XHIST_ERR_UNSUPPORTED, "weighted quantiles of %lld bins are not supported (at most 2^32 - 1)", (long long)bins);
   Pass<WParams> digit, win0;
   if (int rc = pick_pass<QWDigitKernels>(digit, k, digit_bytes(G, d), r.chunk, "digit")) return rc;
   if (int rc = pick_pass<QWWinKernels>(win0, k, kWinBytes, r.chunk, "window")) return rc;
 
   const size_t n_rb = (size_t)r.chunk * bins;
-  QWWin* w0 = static_cast<QWWin*>(alloc(alloc_ctx, n_rb * sizeof(QWWin)));
-  QWTgt* tg = static_cast<QWTgt*>(alloc(alloc_ctx, n_rb * G * sizeof(QWTgt)));
-  double* sum = static_cast<double*>(alloc(alloc_ctx, (n_rb * G << d) * 8));
-  uint32_t* flags = static_cast<uint32_t*>(alloc(alloc_ctx, 8 * ((size_t)passes + 8)));
-  if (!w0 || !tg || !sum || !flags) {
-    snprintf(err, err_cap, "allocation of the weighted quantile scratch (%zu bytes per chunk) failed", radix_row_bytes(bins, G, d) * r.chunk);
-    return XHIST_ERR_NOMEM;
-  }
+  QWWin* w0 = static_cast<QWWin*>(k.scratch(n_rb * sizeof(QWWin)));
+  QWTgt* tg = static_cast<QWTgt*>(k.scratch(n_rb * G * sizeof(QWTgt)));
+  double* sum = static_cast<double*>(k.scratch((n_rb * G << d) * 8));
+  uint32_t* flags = static_cast<uint32_t*>(k.scratch(8 * ((size_t)passes + 8)));
+  if (!w0 || !tg || !sum || !flags)
+    return k.fail(XHIST_ERR_NOMEM, "allocation of the weighted quantile scratch (%zu bytes per chunk) failed",
+                  radix_row_bytes(bins, G, d) * r.chunk);
   const int64_t n_flag_words = (2 + passes + 1) / 2;  // flags: [1 + j] digit pass j (and the word qw_select writes last)
   XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3(2048), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(sum), (int64_t)(n_rb * G << d));
-  XH_VALUES_LAUNCH_CHECK("weighted quantile zeroing launch");
+  XH_VALUES_LAUNCH_CHECK(k, "weighted quantile zeroing launch");
   st.tgt = tg;
   st.win0 = w0;
   st.sum = sum;
@@ -175,7 +169,7 @@ int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, co
     st.row0 = r0;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (nr * bins * G + 255) / 256));
     XH_VALUES_LAUNCH(qw_window, dim3(grid), dim3(256), 0, stream, st);
-    XH_VALUES_LAUNCH_CHECK("qw_window launch");
+    XH_VALUES_LAUNCH_CHECK(k, "qw_window launch");
     if (int rc = launch_quantile_pass(win0, k, r0, nr, w0, bins * sizeof(QWWin), nullptr, 0, flags, 1, d,
                                       "weighted quantile window launch"))
       return rc;
@@ -183,21 +177,21 @@ int xhist_quantile_w_run(const ValuesPlan& pl_in, const xhist_array* samples, co
       quantile_group(st, k, g0, G);
       // the flags of the digit passes start at zero for every group
       XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3(1), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(flags), n_flag_words);
-      XH_VALUES_LAUNCH_CHECK("weighted quantile zeroing launch");
+      XH_VALUES_LAUNCH_CHECK(k, "weighted quantile zeroing launch");
       XH_VALUES_LAUNCH(qw_init, dim3(grid), dim3(256), 0, stream, st);
-      XH_VALUES_LAUNCH_CHECK("qw_init launch");
+      XH_VALUES_LAUNCH_CHECK(k, "qw_init launch");
       for (int j = 0; j < passes; ++j) {
         st.pass = j;
         if (int rc = launch_quantile_pass(digit, k, r0, nr, sum, ((size_t)bins * st.G * 8) << d, tg, sizeof(QWTgt), flags + 1 + j, st.G, d,
                                           "weighted quantile digit launch"))
           return rc;
         XH_VALUES_LAUNCH(qw_select, dim3(grid), dim3(256), 0, stream, st);
-        XH_VALUES_LAUNCH_CHECK("qw_select launch");
+        XH_VALUES_LAUNCH_CHECK(k, "qw_select launch");
       }
       XH_VALUES_LAUNCH(qw_finalize, dim3(grid), dim3(256), 0, stream, st);
-      XH_VALUES_LAUNCH_CHECK("qw_finalize launch");
+      XH_VALUES_LAUNCH_CHECK(k, "qw_finalize launch");
     }
   }
-  describe_quantile_radix(desc, desc_cap, "weighted_quantile", k, r, win0, digit);
+  describe_quantile_radix("weighted_quantile", k, r, win0, digit);
   return XHIST_OK;
 }

@@ -1,7 +1,7 @@
 // xhist_quantile_w.hip.h — exact weighted per-bin quantiles of a value array (histogram_weighted_quantile, numpy's
 // method="inverted_cdf" with weights): the state of a weighted selection, the two weighted policies it plugs into the shared
-// kernel skeletons of xhist_values.hip.h, its binning kernels, the short-row kernel, and the declaration of the driver of
-// xhist_quantile_w.hip (whose shared host steps are those of xhist_quantile.hip.h).
+// kernel skeletons of xhist_values.hip.h, its binning kernels and the short-row kernel (the driver of xhist_quantile_w.hip is
+// declared in xhist_values_api.h; its shared host steps are those of xhist_quantile.hip.h).
 //
 // Samples, values and keys are those of xhist_quantile.hip.h; every counted sample whose value is not NaN also brings its
 // weight (float64).  Per (row, bin): W = the sum of its weights, C(x) = the sum of the weights of its values <= x.  A target
@@ -314,12 +314,3 @@ __global__ void __launch_bounds__(256) qw_short(const WParams p, const QWStep st
 }
 
 }  // namespace xhist
-
-// The launches on `stream` for DEVICE arrays the caller has validated, n_rows * n_bins > 0, the plan's device current: q (host,
-// n_q values in [0, 1]) -> out, float64 [n_q, n_rows, n_bins].  Scratch comes from the library's allocator through
-// alloc(bytes) (nullptr: out of memory), freed by the caller after the call.  Returns XHIST_OK, or an error status with a
-// message in `err`; `desc` receives a line about the launches.  (Called by xhist_plan_execute_quantile_weighted,
-// xhist_capi.hip.)
-int xhist_quantile_w_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
-                         int64_t n_rows, int64_t n_cols, const double* q, int n_q, double* out, xhist_quantile_alloc_fn alloc,
-                         void* alloc_ctx, hipStream_t stream, char* err, size_t err_cap, char* desc, size_t desc_cap);

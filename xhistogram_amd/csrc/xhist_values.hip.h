@@ -3,6 +3,7 @@
 // forms).  The one kernel skeleton per family, into which
 // a statistic plugs an accumulator policy, and the one host-side launcher: the family and LDS rule, the launch geometry, the
 // Params of a launch, and the one driver of the two-pass statistics (two_pass_run, at the end: mean_var, its weighted form, cov).
+// The host functions take the record of the call (ValuesCall, xhist_values_api.h) and name only what differs per launch.
 //
 // Which samples count is decided exactly as for the histogram: the same digitize, the same tables.  A counted sample whose
 // value is not NaN hands that value to the policy.  The slots of a workgroup sit in LDS behind the staged tables; the generic
@@ -15,15 +16,14 @@
 // policy with kExtra = 2 is handed (a, b, weight) triples, and its kernels take CovWParams.
 //
 // Nothing here instantiates a kernel: the skeletons are templates, and the kernels are instantiated in the statistic's own
-// translation unit only (xhist_capi.hip includes this header for ValuesPlan and must not gain device code).
+// translation unit only.  The C ABI unit does not include this header: what it shares with the statistics' units (ValuesPlan,
+// ValuesCall, the drivers' prototypes) is xhist_values_api.h, which holds no device code.
 #pragma once
 
 #include "xhist_kernels.hip.h"
-
-#include "../../include/xhist_amd.h"
+#include "xhist_values_api.h"
 
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 #include <type_traits>
 
@@ -309,25 +309,7 @@ __device__ __forceinline__ void values_fast_body(const P& __restrict__ p) {
 
 }  // namespace xhist
 
-// ---- host side -------------------------------------------------------------------------------------------------------------
-// What the units need of a plan (filled by xhist_capi.hip's values_plan()): the compare domain, the native (start, cnt)
-// tables, the uint16 tables of the linear scan in the float64 and the float32-threshold domain (blob == nullptr: not built),
-// and whether every dimension has arithmetic edges.
-struct ValuesTables {
-  const xhist::DimTable* dim;
-  const uint64_t* blob;
-  int32_t words;
-  int max_cnt;
-};
-struct ValuesPlan {
-  int n_dims, cmp;
-  int64_t n_bins;
-  int cus;
-  size_t lds_max;
-  bool arith;
-  ValuesTables native, fine64, fine32;
-};
-
+// ---- host side (the plan's view and the call's record: xhist_values_api.h) -----------------------------------------------------
 namespace xhist {
 
 typedef void (*values_fn)(const Params);
@@ -340,15 +322,15 @@ typedef void (*values_fn)(const Params);
     hipLaunchKernelGGL(fn, __VA_ARGS__);                        \
   } while (0)
 
-static inline int values_error(char* err, size_t cap, int code, const char* what, hipError_t e) {
-  snprintf(err, cap, "%s: %s", what, hipGetErrorString(e));
-  return code;
+static inline int values_error(const ValuesCall& k, const char* what, hipError_t e) {
+  return k.fail(XHIST_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
 
-#define XH_VALUES_LAUNCH_CHECK(what)                                                \
-  do {                                                                              \
-    hipError_t e_ = hipGetLastError();                                              \
-    if (e_ != hipSuccess) return values_error(err, err_cap, XHIST_ERR_HIP, what, e_); \
+// after a launch of call `k`: a failed one ends the driver with `what` and HIP's text in k.err
+#define XH_VALUES_LAUNCH_CHECK(k, what)                          \
+  do {                                                           \
+    hipError_t e_ = hipGetLastError();                           \
+    if (e_ != hipSuccess) return values_error(k, what, e_);      \
   } while (0)
 
 static inline int elem_bytes(int dt) {
@@ -381,12 +363,13 @@ static inline int fast_copies_log2(int64_t n_bins, size_t slot, size_t tbytes, s
 }
 
 // fast if eligible, else generic with its slots in LDS, else generic straight into global memory.  The largest slot of the
-// passes decides; every pass takes the family, the home and the copies chosen for it.  `weights` (nullptr: unweighted) must
-// qualify for the fast family as the values do: the sample dtype, unit column stride (or one column), element-aligned; so must
-// `fourth` (nullptr: no fourth stream), and either alone sends the call to the generic family.
-static inline ValuesChoice choose_values(const ValuesPlan& pl, const ValuesSlots& sl, const xhist_array* samples,
-                                         const xhist_array* values, int64_t n_cols, const xhist_array* weights = nullptr,
-                                         const xhist_array* fourth = nullptr) {
+// passes decides; every pass takes the family, the home and the copies chosen for it.  The call's third stream (nullptr: none)
+// must qualify for the fast family as the values do: the sample dtype, unit column stride (or one column), element-aligned; so
+// must its fourth, and either alone sends the call to the generic family.
+static inline ValuesChoice choose_values(const ValuesCall& k, const ValuesSlots& sl) {
+  const ValuesPlan& pl = k.pl;
+  const xhist_array *samples = k.samples, *values = k.values;
+  const int64_t n_cols = k.n_cols;
   ValuesChoice c;
   const int D = pl.n_dims;
   const int sdt = samples[0].dtype;
@@ -396,7 +379,7 @@ static inline ValuesChoice choose_values(const ValuesPlan& pl, const ValuesSlots
   for (int d = 0; d < D && fast_ok; ++d)
     fast_ok = samples[d].dtype == sdt && (samples[d].col_stride == 1 || n_cols == 1) && (uintptr_t)samples[d].data % (size_t)elem_bytes(sdt) == 0;
   if (fast_ok) fast_ok = (values->col_stride == 1 || n_cols == 1) && (uintptr_t)values->data % (size_t)elem_bytes(sdt) == 0;
-  for (const xhist_array* x : {weights, fourth})
+  for (const xhist_array* x : {k.third, k.fourth})
     if (fast_ok && x) fast_ok = x->dtype == sdt && (x->col_stride == 1 || n_cols == 1) && (uintptr_t)x->data % (size_t)elem_bytes(sdt) == 0;
   if (fast_ok) {
     const size_t* bytes = c.f32 ? sl.fast32 : sl.bytes;
@@ -489,16 +472,17 @@ static inline ValuesGeometry values_geometry(const ValuesPlan& pl, const ValuesC
 
 // A kernel's dynamic LDS beyond 48 KiB must be allowed before its first launch; drivers do it for every pass up front.
 template <class F>
-static int allow_values_lds(F fn, size_t lds, const char* what, char* err, size_t err_cap) {
+static int allow_values_lds(const ValuesCall& k, F fn, size_t lds, const char* what) {
   if (lds <= 48 * 1024) return XHIST_OK;
   const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  return e == hipSuccess ? XHIST_OK : values_error(err, err_cap, XHIST_ERR_HIP, what, e);
+  return e == hipSuccess ? XHIST_OK : values_error(k, what, e);
 }
 
-// The Params of a launch over rows [r0, r0 + nr) of the inputs: samples, values, tables and geometry; the outputs (out, out2,
-// w2_ptr) are the caller's to set.
-static inline Params values_params(const ValuesPlan& pl, const ValuesChoice& c, int64_t segs, const xhist_array* samples,
-                                   const xhist_array* values, int64_t r0, int64_t nr, int64_t n_cols) {
+// The Params of a launch over rows [r0, r0 + nr) of the call's inputs: samples, values, tables and geometry; the outputs (out,
+// out2, w2_ptr) are the caller's to set.
+static inline Params values_params(const ValuesCall& k, const ValuesChoice& c, int64_t segs, int64_t r0, int64_t nr) {
+  const ValuesPlan& pl = k.pl;
+  const xhist_array *samples = k.samples, *values = k.values;
   Params kp;
   memset(&kp, 0, sizeof kp);
   for (int d = 0; d < pl.n_dims; ++d) {
@@ -522,7 +506,7 @@ static inline Params values_params(const ValuesPlan& pl, const ValuesChoice& c, 
   kp.table_words = c.table_words;
   kp.tables_in_lds = c.tables_in_lds ? 1 : 0;
   kp.n_rows = nr;
-  kp.n_cols = n_cols;
+  kp.n_cols = k.n_cols;
   kp.n_bins = pl.n_bins;
   kp.segs = (int32_t)segs;
   kp.copies_log2 = c.copies_log2;
@@ -551,28 +535,27 @@ static inline void weights_params(CovWParams& kp, const xhist_array* third, cons
 
 // One binning pass: the launches of row chunks of at most g.max_rows (the grid stays below 2^31 workgroups and 2^32 lanes).  out / out2 / in2 are [n_rows, n_bins] arrays of 8-byte elements,
 // advanced to each chunk's first row (Params::out, out2 and w2_ptr); `what` names the pass in error messages.  A weighted
-// kernel (it takes WParams) reads `weights`; for a CovParams kernel each of the three is the first of several such arrays,
-// n_rows * n_bins elements apart; a CovWParams kernel reads `fourth` as well.
+// kernel (it takes WParams) reads the call's third stream; for a CovParams kernel each of the three is the first of several
+// such arrays, n_rows * n_bins elements apart; a CovWParams kernel reads the fourth stream as well.
 template <class P>
-static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what, const ValuesPlan& pl,
-                              const ValuesChoice& c, const ValuesGeometry& g, const xhist_array* samples, const xhist_array* values,
-                              int64_t n_rows, int64_t n_cols, void* out, void* out2, const void* in2, hipStream_t stream, char* err,
-                              size_t err_cap, const xhist_array* weights = nullptr, const xhist_array* fourth = nullptr) {
-  for (int64_t r0 = 0; r0 < n_rows; r0 += g.max_rows) {
-    const int64_t nr = std::min(g.max_rows, n_rows - r0);
+static int launch_values_pass(void (*fn)(const P), size_t lds, const char* what, const ValuesCall& k, const ValuesChoice& c,
+                              const ValuesGeometry& g, void* out, void* out2, const void* in2) {
+  const int64_t n_bins = k.pl.n_bins;
+  for (int64_t r0 = 0; r0 < k.n_rows; r0 += g.max_rows) {
+    const int64_t nr = std::min(g.max_rows, k.n_rows - r0);
     P kp;
-    static_cast<Params&>(kp) = values_params(pl, c, g.segs, samples, values, r0, nr, n_cols);
-    if constexpr (std::is_base_of<CovWParams, P>::value) weights_params(kp, weights, fourth);
+    static_cast<Params&>(kp) = values_params(k, c, g.segs, r0, nr);
+    if constexpr (std::is_base_of<CovWParams, P>::value) weights_params(kp, k.third, k.fourth);
     else if constexpr (std::is_base_of<WParams, P>::value) {
       static const xhist_array no_stream = {};  // (a CovParams kernel of one value array without weights reads no x_* stream)
-      weights_params(kp, weights ? weights : &no_stream);
+      weights_params(kp, k.third ? k.third : &no_stream);
     }
-    if constexpr (std::is_base_of<CovParams, P>::value) kp.plane = n_rows * pl.n_bins;  // (the whole call's rows, whatever the chunk)
-    kp.w2_ptr = in2 ? static_cast<const uint64_t*>(in2) + r0 * pl.n_bins : nullptr;
-    kp.out = static_cast<uint64_t*>(out) + r0 * pl.n_bins;
-    kp.out2 = static_cast<uint64_t*>(out2) + r0 * pl.n_bins;
-    XH_VALUES_LAUNCH(fn, dim3((unsigned)(nr * g.segs)), dim3(g.block), lds, stream, kp);
-    XH_VALUES_LAUNCH_CHECK(what);
+    if constexpr (std::is_base_of<CovParams, P>::value) kp.plane = k.n_rows * n_bins;  // (the whole call's rows, whatever the chunk)
+    kp.w2_ptr = in2 ? static_cast<const uint64_t*>(in2) + r0 * n_bins : nullptr;
+    kp.out = static_cast<uint64_t*>(out) + r0 * n_bins;
+    kp.out2 = static_cast<uint64_t*>(out2) + r0 * n_bins;
+    XH_VALUES_LAUNCH(fn, dim3((unsigned)(nr * g.segs)), dim3(g.block), lds, k.stream, kp);
+    XH_VALUES_LAUNCH_CHECK(k, what);
   }
   return XHIST_OK;
 }
@@ -587,9 +570,9 @@ struct sum_prefix_of<M, std::void_t<decltype(M::sum_prefix)>> {
   static constexpr const char* value = M::sum_prefix;
 };
 
-// The driver of the two-pass statistics: the zeroing and the five launches on `stream` (pass 1, means, pass 2, finalize).  M
-// names what a statistic brings (xhist_meanvar.hip: MeanVar, xhist_meanvar_w.hip: MeanVarW, xhist_cov.hip: Cov, xhist_cov_w.hip:
-// CovW; SkewKurt and SkewKurtW, next to MeanVar and MeanVarW, whose pass 1 they run):
+// The driver of the two-pass statistics: the scratch block, the zeroing and the five launches on the call's stream (pass 1,
+// means, pass 2, finalize).  M names what a statistic brings (xhist_meanvar.hip: MeanVar, xhist_meanvar_w.hip: MeanVarW,
+// xhist_cov.hip: Cov, xhist_cov_w.hip: CovW; SkewKurt and SkewKurtW, next to MeanVar and MeanVarW, whose pass 1 they run):
 //   Sum, Dev          the kernel sets of the two passes, for pick_values_kernel (each with the Params type of its own kernels)
 //   mean, finalize    the kernels of the steps after them, over the first output (counts or sums of weights)
 //   slots             the ValuesSlots of the two passes
@@ -598,12 +581,15 @@ struct sum_prefix_of<M, std::void_t<decltype(M::sum_prefix)>> {
 //   sum_prefix        (optional) the prefix of pass 1's kernels and of the means' step where they are another statistic's:
 //                     skew_kurt runs mean_var's (mv_sum_*, then sk_dev_*), and the passes' kernels then take different Params
 //   spelled           the statistic where a message spells it out ("weighted mean_var")
-// `first` is out_count or out_wsum; `third` the weights or the second value array, nullptr for a statistic of two streams;
-// `fourth` the weights of a statistic of two value arrays, nullptr for every other.
+// `first` is out_count or out_wsum; the call's third stream the weights or the second value array, its fourth the weights of a
+// statistic of two value arrays.  sd, the sums of deviations between the passes, is the driver's own: planes[3] planes from the
+// call's allocator, the very count it zeroes.
 template <class M, class First>
-static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const xhist_array* values, const xhist_array* third,
-                        int64_t n_rows, int64_t n_cols, First* first, double* out_mean, double* out_m2, double* sd, hipStream_t stream,
-                        char* err, size_t err_cap, char* desc, size_t desc_cap, const xhist_array* fourth = nullptr) {
+static int two_pass_run(const ValuesCall& k, First* first, double* out_mean, double* out_m2) {
+  const ValuesPlan& pl = k.pl;
+  const int64_t n_out = k.n_rows * pl.n_bins;
+  double* const sd = static_cast<double*>(k.scratch((size_t)(M::planes[3] * n_out) * sizeof(double)));
+  if (!sd) return k.fail(XHIST_ERR_NOMEM, "allocation of the %s scratch block%s failed", M::spelled, M::planes[3] > 1 ? "s" : "");
   char buf[48];
   auto what = [&](const char* a, const char* b) {  // "<a><b> launch": only XH_VALUES_LAUNCH_CHECK calls it, after a failed launch
     snprintf(buf, sizeof buf, "%s%s launch", a, b);
@@ -616,51 +602,40 @@ static int two_pass_run(const ValuesPlan& pl, const xhist_array* samples, const 
   snprintf(dev_what, sizeof dev_what, "%s_dev launch", M::prefix);
   const auto mean = M::mean;
   const auto finalize = M::finalize;
-  const int64_t n_out = n_rows * pl.n_bins;
   const int grid_io = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_out + 255) / 256));
   void* const zero[4] = {first, out_mean, out_m2, sd};
-  for (int k = 0; k < 4; ++k) {
-    XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3(grid_io), dim3(256), 0, stream, static_cast<unsigned long long*>(zero[k]), M::planes[k] * n_out);
-    XH_VALUES_LAUNCH_CHECK(what(M::name, " zeroing"));
+  for (int i = 0; i < 4; ++i) {
+    XH_LAUNCH_LOGGED_LOCAL(zero_words, dim3(grid_io), dim3(256), 0, k.stream, static_cast<unsigned long long*>(zero[i]), M::planes[i] * n_out);
+    XH_VALUES_LAUNCH_CHECK(k, what(M::name, " zeroing"));
   }
 
   ValuesChoice c;
   ValuesGeometry g;
   values_fn_of<typename M::Sum> sum = nullptr;
   values_fn_of<typename M::Dev> dev = nullptr;
-  if (n_cols > 0) {
-    c = choose_values(pl, M::slots, samples, values, n_cols, third, fourth);
+  if (k.n_cols > 0) {
+    c = choose_values(k, M::slots);
     sum = pick_values_kernel<typename M::Sum>(c, pl);
     dev = pick_values_kernel<typename M::Dev>(c, pl);
-    if (!sum || !dev) {
-      snprintf(err, err_cap, "internal: no %s kernel for this combination", M::spelled);
-      return XHIST_ERR_HIP;
-    }
-    if (int rc = allow_values_lds(sum, c.lds_bytes[0], lds_what, err, err_cap)) return rc;
-    if (int rc = allow_values_lds(dev, c.lds_bytes[1], lds_what, err, err_cap)) return rc;
-    g = values_geometry(pl, c, n_rows, n_cols);
-    if (int rc = launch_values_pass(sum, c.lds_bytes[0], sum_what, pl, c, g, samples, values, n_rows, n_cols, first, out_mean,
-                                    nullptr, stream, err, err_cap, third, fourth))
-      return rc;
+    if (!sum || !dev) return k.fail(XHIST_ERR_HIP, "internal: no %s kernel for this combination", M::spelled);
+    if (int rc = allow_values_lds(k, sum, c.lds_bytes[0], lds_what)) return rc;
+    if (int rc = allow_values_lds(k, dev, c.lds_bytes[1], lds_what)) return rc;
+    g = values_geometry(pl, c, k.n_rows, k.n_cols);
+    if (int rc = launch_values_pass(sum, c.lds_bytes[0], sum_what, k, c, g, first, out_mean, nullptr)) return rc;
   }
-  XH_VALUES_LAUNCH(mean, dim3(grid_io), dim3(256), 0, stream, first, out_mean, n_out);
-  XH_VALUES_LAUNCH_CHECK(what(prefix1, "_mean"));
-  if (n_cols > 0) {
-    if (int rc = launch_values_pass(dev, c.lds_bytes[1], dev_what, pl, c, g, samples, values, n_rows, n_cols, sd, out_m2,
-                                    out_mean, stream, err, err_cap, third, fourth))
-      return rc;
+  XH_VALUES_LAUNCH(mean, dim3(grid_io), dim3(256), 0, k.stream, first, out_mean, n_out);
+  XH_VALUES_LAUNCH_CHECK(k, what(prefix1, "_mean"));
+  if (k.n_cols > 0) {
+    if (int rc = launch_values_pass(dev, c.lds_bytes[1], dev_what, k, c, g, sd, out_m2, out_mean)) return rc;
   }
-  XH_VALUES_LAUNCH(finalize, dim3(grid_io), dim3(256), 0, stream, first, sd, out_m2, n_out);
-  XH_VALUES_LAUNCH_CHECK(what(M::prefix, "_finalize"));
-  if (desc && desc_cap) {
-    const char* fam = !sum ? "none" : c.fast ? "fast" : "generic";
-    const char* home = !sum ? "none" : c.lds ? "lds" : "global";
-    snprintf(desc, desc_cap,
-             "%s pass1=%s_sum_%s slots=%s pass2=%s_dev_%s slots=%s scan=%d copies=%d block=%d segs=%lld lds_bytes=%zu/%zu "
+  XH_VALUES_LAUNCH(finalize, dim3(grid_io), dim3(256), 0, k.stream, first, sd, out_m2, n_out);
+  XH_VALUES_LAUNCH_CHECK(k, what(M::prefix, "_finalize"));
+  const char* fam = !sum ? "none" : c.fast ? "fast" : "generic";
+  const char* home = !sum ? "none" : c.lds ? "lds" : "global";
+  k.describe("%s pass1=%s_sum_%s slots=%s pass2=%s_dev_%s slots=%s scan=%d copies=%d block=%d segs=%lld lds_bytes=%zu/%zu "
              "tables_in_lds=%d D=%d cmp=%d",
              M::name, prefix1, fam, home, M::prefix, fam, home, c.scan, 1 << c.copies_log2, g.block, (long long)g.segs, c.lds_bytes[0],
              c.lds_bytes[1], (int)c.tables_in_lds, pl.n_dims, values_cmp(pl));
-  }
   return XHIST_OK;
 }
 

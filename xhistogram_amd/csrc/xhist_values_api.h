@@ -1,0 +1,96 @@
+// xhist_values_api.h — what the C ABI unit (xhist_capi.hip) and the units of the per-bin statistics of a value array share on
+// the host: the view of a plan, the record of one call, and the drivers' prototypes.  Declarations only, no device code: the
+// C ABI unit includes this header, each statistic's unit reaches it through xhist_values.hip.h.
+#pragma once
+
+#include "../../include/xhist_amd.h"
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstdarg>
+#include <cstdio>
+
+namespace xhist {
+struct DimTable;
+}
+
+// What the units need of a plan (filled by xhist_capi.hip's values_plan()): the compare domain, the native (start, cnt)
+// tables, the uint16 tables of the linear scan in the float64 and the float32-threshold domain (blob == nullptr: not built),
+// and whether every dimension has arithmetic edges.
+struct ValuesTables {
+  const xhist::DimTable* dim;
+  const uint64_t* blob;
+  int32_t words;
+  int max_cnt;
+};
+struct ValuesPlan {
+  int n_dims, cmp;
+  int64_t n_bins;
+  int cus;
+  size_t lds_max;
+  bool arith;
+  ValuesTables native, fine64, fine32;
+};
+
+// scratch of `bytes` bytes from the library's allocator, freed by the C ABI unit after the call; nullptr: out of memory
+typedef void* (*xhist_values_alloc_fn)(void* ctx, size_t bytes);
+
+// What stays the same through one call (built once by xhist_capi.hip's execute_values, which owns everything it points to):
+// the plan; the input streams (`third`: the weights, or the second value array of the covariances; `fourth`: the weights of
+// the weighted covariance; nullptr where a statistic has none); the shape; the stream; where an error message and the line
+// about the launches go (the latter becomes the plan's describe()); the scratch allocator.
+struct ValuesCall {
+  ValuesPlan pl;
+  const xhist_array *samples, *values, *third, *fourth;
+  int64_t n_rows, n_cols;
+  hipStream_t stream;
+  char* err;
+  size_t err_cap;
+  char* desc;
+  size_t desc_cap;
+  xhist_values_alloc_fn alloc;
+  void* alloc_ctx;
+
+  void* scratch(size_t bytes) const { return alloc(alloc_ctx, bytes); }
+  // the message into `err`; returns `code`
+  __attribute__((format(printf, 3, 4))) int fail(int code, const char* fmt, ...) const {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(err, err_cap, fmt, ap);
+    va_end(ap);
+    return code;
+  }
+  __attribute__((format(printf, 2, 3))) void describe(const char* fmt, ...) const {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(desc, desc_cap, fmt, ap);
+    va_end(ap);
+  }
+};
+
+// The drivers: the launches of one statistic on k.stream, for DEVICE arrays the caller has validated, n_rows * n_bins > 0, the
+// plan's device current.  Each returns XHIST_OK, or an error status with a message in k.err, and writes a line about its
+// launches to k.desc.  Outputs are [n_rows, n_bins] planes of 8-byte elements, or blocks [planes, n_rows, n_bins] of them.
+
+// xhist_extrema.hip: minimum and maximum (prepare, binning, finalize; `accumulate`: the outputs hold an earlier result), and
+// histogram_argextrema (the two prepares, pass 1, pass 2, finalize): out_values [2] (minimum, maximum), out_index [2] int64
+// (their positions; -1: empty bin)
+int xhist_extrema_run(const ValuesCall& k, double* out_min, double* out_max, int accumulate);
+int xhist_argextrema_run(const ValuesCall& k, double* out_values, int64_t* out_index);
+
+// The two-pass statistics (two_pass_run<M> of xhist_values.hip.h, which takes its block for the sums of deviations from
+// k.alloc): out_first is the int64 count, or the float64 sum of weights of a weighted form (k.third, k.fourth for cov).
+//   xhist_meanvar.hip, xhist_meanvar_w.hip   out_mean [1], out_m2 [1]; skew_kurt: out_m2 [3] (M2, M3, M4)
+//   xhist_cov.hip, xhist_cov_w.hip           k.third the second value array; out_mean [2] (mean_a, mean_b), out_m2 [3] (M2_a,
+//                                            C_ab, M2_b)
+int xhist_meanvar_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2);
+int xhist_meanvar_w_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2);
+int xhist_skew_kurt_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2);
+int xhist_skew_kurt_w_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2);
+int xhist_cov_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2);
+int xhist_cov_w_run(const ValuesCall& k, void* out_first, double* out_mean, double* out_m2);
+
+// xhist_quantile.hip, xhist_quantile_w.hip: q (host, n_q values in [0, 1]) and the method code (XHIST_Q_*; the weighted form,
+// k.third its weights, is numpy's inverted_cdf) -> out, float64 [n_q, n_rows, n_bins]
+int xhist_quantile_run(const ValuesCall& k, const double* q, int n_q, int method, double* out);
+int xhist_quantile_w_run(const ValuesCall& k, const double* q, int n_q, double* out);
