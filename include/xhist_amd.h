@@ -301,6 +301,31 @@ int xhist_plan_execute_quantile_weighted(xhist_plan* plan, const xhist_array* sa
                                          const xhist_array* weights, int64_t n_rows, int64_t n_cols, const double* q, int n_q,
                                          double* out, int mem_kind, void* stream);
 
+/* The per-sample maps (added within ABI v11: a new entry, every earlier one unchanged): from a per-bin result back to the
+ * samples.  One 8-byte element per sample, into `out`, a DENSE row-major [n_rows, n_cols] DEVICE block whatever the strides of
+ * the inputs are: element (r, c) is the result of the sample at (r, c) of the views.  Which samples count is exactly what
+ * xhist_plan_execute counts (same digitize, last bin closed, NaN / out-of-range samples dropped, in ANY dimension).
+ *   XHIST_MAP_INDEX    int64: the C-order flat index of the sample's bin over the plan's bin axes (the first input slowest:
+ *                      np.ravel_multi_index), -1 for a sample that is not counted.  values, centre and scale must be NULL.
+ *   XHIST_MAP_TAKE     float64: centre[r, bin], NaN for a sample that is not counted.  values and scale must be NULL.
+ *   XHIST_MAP_ANOMALY  float64: (double)values[r, c] - centre[r, bin], one IEEE subtraction; where scale is given, divided by
+ *                      scale[r, bin], one IEEE division.  NaN for a sample that is not counted; a NaN value stays NaN.
+ *   values: an xhist_array of any real dtype, shaped like the samples (strides 0 broadcast); XHIST_MAP_ANOMALY only.
+ *   centre, scale: contiguous float64 [n_rows, prod(nb_d)] DEVICE tables, read only (the outputs of
+ *   xhist_plan_execute_mean_var, for instance: they need not leave the device).
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Every element of `out` is written exactly once and nothing outside it; nothing is accumulated.  Asynchronous on `stream`.
+ *   A plan without bins (an edge array of a single edge) counts no sample: the block is then filled with -1 / NaN, the NaN
+ *   being the all-ones bit pattern.
+ *   xhist_plan_describe then reads "map op=index|take|anomaly family=fast|generic table=lds|global|none scan=.. cmp=.. segs=..
+ *   block=.. lds_bytes=..": the kernel family and where the table row of a workgroup lives. */
+#define XHIST_MAP_INDEX 0
+#define XHIST_MAP_TAKE 1
+#define XHIST_MAP_ANOMALY 2
+int xhist_plan_execute_map(xhist_plan* plan, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                           int64_t n_cols, int op, const double* centre, const double* scale, void* out, int mem_kind,
+                           void* stream);
+
 /* One-shot form of the two calls above with an internal plan cache keyed on (device, edges). */
 int xhist_bincount_rows(int device, int n_inputs, const xhist_array* samples,
                         const xhist_array* weights, int64_t n_rows, int64_t n_cols,

@@ -32,6 +32,7 @@ CMP_UNSIGNED = 0x200  # | onto CMP_I64 / CMP_PER_DIM: the int64-domain inputs ar
 MEM_HOST, MEM_DEVICE, MEM_HOST_TO_DEVICE = 0, 1, 2
 COMM_ID_BYTES = 128
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
+MAP_INDEX, MAP_TAKE, MAP_ANOMALY = 0, 1, 2  # the ops of xhist_plan_execute_map (XHIST_MAP_*)
 
 _NP_TAG = {
     np.dtype(np.float64): F64, np.dtype(np.float32): F32, np.dtype(np.float16): F16,
@@ -72,7 +73,7 @@ EXPORTS = (
     "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
     "xhist_plan_execute_quantile_weighted", "xhist_plan_execute_cov", "xhist_plan_execute_cov_weighted",
     "xhist_plan_execute_skew_kurt", "xhist_plan_execute_skew_kurt_weighted", "xhist_plan_execute_argextrema",
-    "xhist_bincount_rows",
+    "xhist_plan_execute_map", "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
     "xhist_comm_wait", "xhist_comm_destroy", "xhist_buffer_alloc", "xhist_buffer_free", "xhist_buffer_copy", "xhist_buffer_add", "xhist_buffer_copy_nd",
@@ -166,6 +167,10 @@ def load():
         lib.xhist_plan_execute_quantile_weighted.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64,
             C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+        ]
+        lib.xhist_plan_execute_map.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_int, C.c_void_p,
         ]
         lib.xhist_bincount_rows.argtypes = [
             C.c_int, C.c_int, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_void_p),
@@ -395,6 +400,20 @@ class Plan:
         buffers, asynchronous on `stream` (xhist_plan_execute_argextrema)"""
         self._execute_values("xhist_plan_execute_argextrema", sample_views, (value_view,), n_rows, n_cols,
                              (out_values_ptr, out_index_ptr), stream=stream)
+
+    def execute_map(self, sample_views, value_view, n_rows, n_cols, op, centre_ptr, scale_ptr, out_ptr, stream=0):
+        """one 8-byte element per sample of device-resident views into the dense row-major [n_rows, n_cols] device block at
+        `out_ptr`, asynchronous on `stream` (xhist_plan_execute_map): MAP_INDEX the int64 flat bin index (-1: not counted),
+        MAP_TAKE the float64 centre[row, bin], MAP_ANOMALY float64(value) - centre[row, bin], divided by scale[row, bin] where
+        `scale_ptr` is given (NaN: not counted).  `value_view` is None but for MAP_ANOMALY; the tables are float64
+        [n_rows, bins] device pointers, 0 / None where the op takes none"""
+        check(
+            load().xhist_plan_execute_map(
+                self._h, self._sample_array(sample_views), C.byref(value_view) if value_view is not None else None, int(n_rows),
+                int(n_cols), int(op), C.c_void_p(centre_ptr or 0), C.c_void_p(scale_ptr or 0), C.c_void_p(out_ptr), MEM_DEVICE,
+                C.c_void_p(stream or 0),
+            )
+        )
 
     def execute_mean_var(self, sample_views, value_view, n_rows, n_cols, out_count_ptr, out_mean_ptr, out_m2_ptr, stream=0):
         """per-bin count (int64), mean and sum of squared deviations M2 (float64; NaN where no value arrived) of the values of

@@ -1794,7 +1794,9 @@ def _upload_host(args, values, bins, *extras):
     args, _ = _prepare_dtypes(args, None, [a.dtype for a in args], bins, "numpy")
     dev = _host_device()
     _native.require_device(dev)
-    arrays = [DeviceArray.from_numpy(a, dev) for a in args + [np.asarray(values)] + [np.asarray(e) for e in extras if e is not None]]
+    # (values None: a call that reads the samples alone, bin_index and histogram_lookup)
+    arrays = [DeviceArray.from_numpy(a, dev)
+              for a in args + [np.asarray(v) for v in (values,) if v is not None] + [np.asarray(e) for e in extras if e is not None]]
     shape = np.broadcast_shapes(*[a.shape for a in arrays])
     return [a.broadcast_to(shape) for a in arrays]
 
@@ -1816,7 +1818,7 @@ def _value_views(args, values, axis, bins, backend, *extras, ordered=False):
     cmp_domain, edges, common = _compare_domain(dtypes, bins)
     if backend == "device" and any(c is not None and a.dtype != c for a, c in zip(args, common)):
         raise TypeError("datetime64 DeviceArrays must already have the unit they share with their bin edges")
-    arrays = list(args) + [values] + [e for e in extras if e is not None]
+    arrays = list(args) + [a for a in (values,) + extras if a is not None]  # (values None: the samples alone)
     if ordered:
         axis = axis if do_full_array else sorted(axis)
         order = list(_range(ndim)) if do_full_array else axis
@@ -1994,21 +1996,22 @@ def histogram_argextrema(*args, values, bins=None, range=None, axis=None, block_
     return amin, amax, vmin, vmax, bins
 
 
-def _values_call(args, values, bins, range, axis, name, *extras):
+def _values_call(args, values, bins, range, axis, name, *extras, needs_values=True):
     """the front of a per-bin statistic of values: argument checks before any device work, the backend, the broadcast
     arrays (samples..., values, extras...: the arrays the statistic reads after the values, in its order; None: not given),
-    the numpy originals (numpy backend), the edges of the unweighted histogram, the normalised axis and the reduced axes"""
-    if values is None:
+    the numpy originals (numpy backend), the edges of the unweighted histogram, the normalised axis and the reduced axes.
+    `needs_values` False: a call that reads the samples alone (bin_index, histogram_lookup) passes values None, and the
+    arrays are the samples."""
+    if values is None and needs_values:
         raise TypeError("%s needs values" % name)
     if not args:
         raise TypeError("%s needs at least one array of samples" % name)
-    _check_values_dtype(values, name)
-    extras = [x for x in extras if x is not None]
+    extras = [x for x in (values,) + extras if x is not None]
     for x in extras:
         _check_values_dtype(x, name)
     n_inputs = len(args)
     axis = _normalise_axis(axis, args[0].ndim if hasattr(args[0], "ndim") else np.ndim(args[0]))
-    all_arrays = list(args) + [values] + extras
+    all_arrays = list(args) + extras
     raw = None
     if any(_is_dask(a) for a in all_arrays):
         import dask.array as dsa
@@ -2553,3 +2556,242 @@ def histogram_weighted_quantile(*args, values, weights, q, bins=None, range=None
     qf, scalar, _ = _check_quantile_args(q, "linear")
     _, res, bins, _ = _value_stat("quantile_w", args, values, bins, range, axis, "histogram_weighted_quantile", weights=weights, q=qf)
     return (res[0] if scalar else res), bins
+
+
+# ---------------------------------------------------------------------------------------------
+# per-sample maps: from a per-bin result back to the samples
+# ---------------------------------------------------------------------------------------------
+def _map_out(plan, nv, has_values, m, c, op, centre_ptr, scale_ptr, like, axis, backend, device, stream):
+    """xhist_plan_execute_map over the `ordered` views `nv` of _value_views (samples..., then the values where `has_values`):
+    the dense [m, c] block the kernels write, in the broadcast sample shape of `like` — a torch tensor on its device
+    (asynchronous on `stream`) or a numpy array.  The block's rows are the kept axes in C order and a row's columns the
+    reduced axes in ascending number: it is reshaped, and its axes moved back where `axis` is not trailing.  The kernels are
+    handed this block itself, never a view of something else: a copied output would be lost."""
+    n = plan.n_dims
+    is_index = op == _native.MAP_INDEX
+    shape = tuple(int(s) for s in like.shape)
+    ndim = len(shape)
+    red = list(_range(ndim)) if axis is None or set(axis) == set(_range(ndim)) else sorted(axis)
+    kept = [i for i in _range(ndim) if i not in red]
+    if backend == "torch":
+        torch = _torch()
+        out = torch.empty((m, c), dtype=torch.int64 if is_index else torch.float64, device=like.device)
+    else:
+        out = np.empty((m, c), np.int64 if is_index else np.float64)
+    if m * c > 0:
+        # (a plan without bins counts no sample: the library itself then fills the block with -1 / NaN)
+        buf = None if backend == "torch" else _native.DeviceBuffer(device, m * c * 8)
+        plan.execute_map(nv[:n], nv[n] if has_values else None, m, c, op, centre_ptr, scale_ptr,
+                         out.data_ptr() if buf is None else buf.ptr, stream=stream)
+        if buf is not None:
+            buf.download(out)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+    out = out.reshape([shape[i] for i in kept] + [shape[i] for i in red])
+    if kept and red != list(_range(len(kept), ndim)):
+        back = tuple(_range(len(kept), ndim))
+        out = out.movedim(back, tuple(red)) if backend == "torch" else np.moveaxis(out, back, red)
+    return out
+
+
+def _table_on_device(table, rows, n_bins, backend, like, device):
+    """a per-bin table as contiguous float64 [rows, n_bins] on the samples' device: (what keeps it alive, its pointer)"""
+    if backend == "torch":
+        torch = _torch()
+        t = table if _is_torch(table) else torch.as_tensor(np.array(table, dtype=np.float64, order="C"))  # (a copy: torch takes no read-only arrays)
+        t = t.to(device=like.device, dtype=torch.float64).reshape(rows, n_bins).contiguous()
+        return t, t.data_ptr()
+    if _is_devarr(table):  # (already resident: converted and made contiguous on the device)
+        t = table.to(device).astype(np.float64).contiguous().reshape(rows, n_bins)
+        return t, t.ptr
+    host = table.detach().cpu().numpy() if _is_torch(table) else np.asarray(table)
+    host = np.ascontiguousarray(host, np.float64).reshape(rows, n_bins)
+    buf = _native.DeviceBuffer(device, max(host.nbytes, 8))
+    if host.nbytes:
+        buf.upload(host)
+    return buf, buf.ptr
+
+
+def _bins_shape_if_known(bins, n_inputs):
+    """the number of bins per input where it can be told before the edges are made (None: an estimator's name)"""
+    out = []
+    for b in _ensure_correctly_formatted_bins(bins, n_inputs):
+        if isinstance(b, str):
+            out.append(None)
+        elif np.ndim(b) == 0:
+            out.append(int(b))
+        else:
+            out.append(max(len(b) - 1, 0))
+    return out
+
+
+def _check_table_shape(table, sample_shape, drop_axes, n_per_input):
+    """ValueError unless `table` has the shape ``histogram`` gives: kept axes, then bin axes (None: any extent)"""
+    want = [int(s) for i, s in enumerate(sample_shape) if i not in drop_axes] + list(n_per_input)
+    got = _shape_of(table)
+    if len(got) != len(want) or any(w is not None and g != w for g, w in zip(got, want)):
+        raise ValueError("table has shape %s, but histogram gives %s for these arguments (kept axes, then bin axes)"
+                         % (got, tuple("?" if w is None else w for w in want)))
+
+
+def _shape_of(a):
+    return tuple(int(s) for s in (a.shape if hasattr(a, "shape") else np.shape(a)))
+
+
+def _map_samples(name, args, bins, range, axis):
+    """the front of bin_index and histogram_lookup: _values_call's for a call without values, and the samples resident on a
+    GPU (numpy samples uploaded to the calling thread's)"""
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, None, bins, range, axis, name, needs_values=False)
+    if backend == "numpy":
+        return backend, _upload_host(raw, None, bins), "device", bins, axis, drop_axes
+    return backend, all_arrays, backend, bins, axis, drop_axes
+
+
+def _bin_index_block(*blocks, bins=None):
+    return bin_index(*blocks, bins=bins)[0]
+
+
+def bin_index(*args, bins=None, range=None):
+    """The bin of every sample, computed on an MI355X: the intermediate ``digitize -> ravel_multi_index`` that ``histogram``
+    counts and never shows.
+
+    ``args``, ``bins`` and ``range`` are those of :func:`histogram` (estimator names are allowed: the edges are those of the
+    unweighted ``histogram`` call, and they do not depend on the row, so there is no ``axis``).  ``index`` is int64 in the
+    broadcast shape of ``args``: for a sample ``histogram`` counts, the C-order flat index over the histogram's bin axes,
+    ``np.ravel_multi_index(per-input bins, bins_shape)`` (the same digitize: last bin closed on the right, int64 / datetime
+    and mixed compare domains, joint bins of up to 8 inputs); ``-1`` for every sample it does not count (NaN, outside
+    ``[e_0, e_last]`` in any input).  So ``np.bincount(index[index >= 0], minlength=n_bins).reshape(bins_shape)`` is
+    ``histogram(*args, bins=bins)[0]``, and ``index`` serves ``np.take`` and ``torch.gather`` as the positions of
+    :func:`histogram_argextrema` do.
+
+    Returns ``(index, bin_edges)``.  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the
+    current stream), DeviceArray in -> numpy out, dask in -> a lazy dask array, one task per block (``bins`` must then be
+    numpy arrays of edges)."""
+    if not args:
+        raise TypeError("bin_index needs at least one array of samples")
+    backend, arrays, on, bins, _, _ = _map_samples("bin_index", args, bins, range, None)
+    if backend == "dask":
+        import dask.array as dsa
+
+        ind = tuple(_range(arrays[0].ndim))
+        out = dsa.blockwise(_bin_index_block, ind, *[x for a in arrays for x in (a, ind)], dtype=np.int64, bins=bins,
+                            meta=np.array((), np.int64))
+        return out, bins
+    plan, nv, views, m, c, _, device, stream = _value_views(arrays, None, None, bins, on, ordered=True)
+    out = _map_out(plan, nv, False, m, c, _native.MAP_INDEX, 0, 0, arrays[0], None, on, device, stream)
+    del views
+    return out, bins
+
+
+def _lookup_block(*blocks, axis=None, bins=None):
+    return histogram_lookup(*blocks[:-1], table=blocks[-1], bins=bins, axis=axis)[0]
+
+
+def histogram_lookup(*args, table, bins=None, range=None, axis=None):
+    """A per-bin table read back at every sample, computed on an MI355X: ``out[s] = table[kept index of s, bin of s]`` — the
+    map of each grid point's class mean, or of any per-bin result of this library.
+
+    ``args``, ``bins``, ``range`` and ``axis`` are those of :func:`histogram`, and the bin of a sample is the one
+    :func:`bin_index` gives.  ``table`` (any real dtype, taken as float64) has the shape ``histogram`` gives for these ``args``
+    and ``axis``: kept axes, then bin axes.  ``out`` is float64 in the broadcast shape of ``args``; a sample ``histogram`` does
+    not count reads NaN.  A table of another shape raises ``ValueError`` and a complex or non-real one ``TypeError``, both
+    before any device work.
+
+    Returns ``(out, bin_edges)``.  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the current
+    stream), DeviceArray in -> numpy out, dask in -> a lazy dask array, one task per block of samples: the table is then a
+    dask array chunked like the samples along the kept axes, with every bin axis in one chunk."""
+    if table is None:
+        raise TypeError("histogram_lookup needs a table")
+    if not args:
+        raise TypeError("histogram_lookup needs at least one array of samples")
+    if not hasattr(table, "shape"):
+        table = np.asarray(table)  # (a plain sequence, taken as numpy takes it)
+    _check_values_dtype(table, "histogram_lookup")
+    ndim = len(np.broadcast_shapes(*[_shape_of(a) for a in args]))
+    early_axis = _normalise_axis(axis, ndim)
+    _check_table_shape(table, np.broadcast_shapes(*[_shape_of(a) for a in args]),
+                       tuple(early_axis) if early_axis is not None else tuple(_range(ndim)), _bins_shape_if_known(bins, len(args)))
+    if _is_dask(table) and not any(_is_dask(a) for a in args):
+        import dask.array as dsa
+
+        if any(_is_torch(a) or _is_devarr(a) for a in args):
+            raise TypeError("a dask table goes with dask or numpy samples: compute the table, or pass the samples as dask arrays")
+        args = [dsa.from_array(np.asarray(a), chunks=-1) for a in args]
+    backend, arrays, on, bins, axis, drop_axes = _map_samples("histogram_lookup", args, bins, range, axis)
+    shape = _shape_of(arrays[0])
+    _check_table_shape(table, shape, drop_axes, [len(b) - 1 for b in bins])
+    if backend == "dask":
+        import dask.array as dsa
+
+        ind = tuple(_range(len(shape)))
+        kept = tuple(i for i in ind if i not in drop_axes)
+        t_ind = kept + tuple(_range(len(shape), len(shape) + len(bins)))
+        # the table's blocks are the sample blocks' along the kept axes, and every bin axis is one chunk
+        t_chunks = tuple(arrays[0].chunks[i] for i in kept) + (-1,) * len(bins)
+        table = table.rechunk(t_chunks) if _is_dask(table) else dsa.from_array(np.asarray(table), chunks=t_chunks)
+        out = dsa.blockwise(_lookup_block, ind, *[x for a in arrays for x in (a, ind)], table, t_ind, dtype=np.float64,
+                            concatenate=True, axis=axis, bins=bins, meta=np.array((), np.float64))
+        return out, bins
+    plan, nv, views, m, c, _, device, stream = _value_views(arrays, None, axis, bins, on, ordered=True)
+    keep, ptr = _table_on_device(table, m, plan.n_bins, on, arrays[0], device)
+    out = _map_out(plan, nv, False, m, c, _native.MAP_TAKE, ptr, 0, arrays[0], axis, on, device, stream)
+    del views, keep
+    return out, bins
+
+
+def histogram_anomaly(*args, values, bins=None, range=None, axis=None, weights=None, ddof=0, standardize=False):
+    """Every sample's value relative to the mean of its bin, computed on an MI355X: "oxygen anomaly relative to the mean of
+    its T-S class", and with ``standardize=True`` its z-score.
+
+    ``args``, ``values``, ``bins``, ``range``, ``axis``, ``weights`` and ``ddof`` are those of :func:`histogram_mean_var`, whose
+    kernels compute ``mean`` and ``var`` here as they do there; the tables stay on the device.  ``anomaly`` is float64 in the
+    broadcast shape of the inputs: ``float64(v) - mean[bin]``, one IEEE subtraction, and with ``standardize=True``
+    ``(float64(v) - mean[bin]) / sqrt(var[bin])``, an IEEE division.  A sample ``histogram`` does not count gives NaN and a NaN
+    value stays NaN; everything else is what IEEE gives (``var = 0``: ``+-inf`` or NaN; a bin whose variance is NaN because
+    ``n <= ddof``: NaN).  numpy inputs are uploaded once, for both steps.
+
+    Returns ``(anomaly, bin_edges)``.  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the
+    current stream), DeviceArray in -> numpy out, dask in -> a lazy dask array: the lazy ``histogram_mean_var`` composed with
+    :func:`histogram_lookup`."""
+    ddof = _check_ddof(ddof)
+    standardize = _check_flag("standardize", standardize)
+    n = len(args)
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_anomaly", weights)
+    if backend == "dask":
+        import dask.array as dsa
+
+        _, mean, var, _ = histogram_mean_var(*all_arrays[:n], values=all_arrays[n], bins=bins, axis=axis, ddof=ddof,
+                                             weights=all_arrays[n + 1] if weights is not None else None)
+        out = all_arrays[n].astype(np.float64) - histogram_lookup(*all_arrays[:n], table=mean, bins=bins, axis=axis)[0]
+        if standardize:
+            out = out / histogram_lookup(*all_arrays[:n], table=dsa.sqrt(var), bins=bins, axis=axis)[0]
+        return out, bins
+    arrays, on = _resident(backend, raw, all_arrays, n, bins)
+    st = _VALUE_STATS["mean_var" if weights is None else "mean_var_w"]
+    plan, nv, views, m, c, _, device, stream = _value_views(arrays[:n], arrays[n], axis, bins, on, *arrays[n + 1:], ordered=True)
+    nt = m * plan.n_bins
+    # the block (count or sum of weights, mean, M2) of histogram_mean_var's own call, on the device
+    if on == "torch":
+        torch = _torch()
+        stats = torch.empty((3, m, plan.n_bins), dtype=torch.float64, device=arrays[0].device)
+        base = stats.data_ptr()
+    else:
+        stats = _native.DeviceBuffer(device, max(3 * nt * 8, 8))
+        base = stats.ptr
+    if nt > 0:
+        getattr(plan, st.method)(nv[:n], *nv[n:], m, c, base, base + nt * 8, base + 2 * nt * 8, stream=stream)
+    scale, scale_ptr = None, 0
+    if standardize:
+        # sqrt(var) as histogram_mean_var's callers form it; for numpy and DeviceArray inputs the count and M2 tables (bins, not
+        # samples) pass through the host for that, the means never leave the device
+        if on == "torch":
+            x = stats[0].view(torch.int64) if 0 in st.ints else stats[0]
+            scale, scale_ptr = _table_on_device(torch.sqrt(_var_of(x, stats[2], ddof)), m, plan.n_bins, on, arrays[0], device)
+        else:
+            host = np.empty((3, m, plan.n_bins), np.float64)
+            if nt > 0:
+                stats.download(host)
+            x = host[0].view(np.int64) if 0 in st.ints else host[0]
+            with np.errstate(invalid="ignore"):
+                scale, scale_ptr = _table_on_device(np.sqrt(_var_of(x, host[2], ddof)), m, plan.n_bins, on, arrays[0], device)
+    out = _map_out(plan, nv[:n + 1], True, m, c, _native.MAP_ANOMALY, base + nt * 8, scale_ptr, arrays[0], axis, on, device, stream)
+    del views, stats, scale
+    return out, bins

@@ -281,13 +281,15 @@ static void* values_scratch_alloc(void* ctx, size_t bytes) {
 // The checks and the tail the statistics' entry points share: `out` is the statistic's float64 output validate_arrays checks,
 // `outs_ok` whether the others are given (`outs_missing` the message if not); `third` and `fourth` are the streams beyond the
 // values, which the entry point has checked (nullptr: none).  run(call) launches on the plan's device with the record of the
-// call, which lives as long as run does; the line it writes to call.desc becomes the plan's describe().
+// call, which lives as long as run does; the line it writes to call.desc becomes the plan's describe().  `needs_values` false:
+// the call may come without values (the per-sample maps that read the samples alone).
 template <class Run>
 static int execute_values(xhist_plan* p, const char* name, const xhist_array* samples, const xhist_array* values,
                           const xhist_array* third, const xhist_array* fourth, int64_t n_rows, int64_t n_cols, double* out, bool outs_ok,
-                          const char* outs_missing, int mem_kind, void* stream, Run run) {
-  if (!values) return fail(XHIST_ERR_INVALID, "values are required");
-  if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out, XHIST_F64)) return rc;
+                          const char* outs_missing, int mem_kind, void* stream, Run run, bool needs_values = true) {
+  if (!values && needs_values) return fail(XHIST_ERR_INVALID, "values are required");
+  // (validate_arrays names the output's type by whether there is a second stream; `out` is 8-byte elements either way)
+  if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out, values ? XHIST_F64 : XHIST_I64)) return rc;
   if (!outs_ok && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "%s", outs_missing);
   if (mem_kind != XHIST_MEM_DEVICE)
     return fail(XHIST_ERR_INVALID, "%s takes DEVICE arrays (mem_kind XHIST_MEM_DEVICE); upload host data first", name);
@@ -396,6 +398,30 @@ extern "C" int xhist_plan_execute_quantile_weighted(xhist_plan* p, const xhist_a
   if (int rc = validate_arrays(p, samples, weights, n_rows, n_cols, out, XHIST_F64)) return rc;
   return execute_values(p, "xhist_plan_execute_quantile_weighted", samples, values, weights, nullptr, n_rows, n_cols, out, true, "",
                         mem_kind, stream, [&](const ValuesCall& k) { return xhist_quantile_w_run(k, q, n_q, out); });
+}
+
+// The per-sample maps (xhist_map.hip): the same front; `out` is the dense [n_rows, n_cols] block, so a call without columns
+// has nothing to write.
+extern "C" int xhist_plan_execute_map(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                                      int64_t n_cols, int op, const double* centre, const double* scale, void* out, int mem_kind,
+                                      void* stream) {
+  if (op != XHIST_MAP_INDEX && op != XHIST_MAP_TAKE && op != XHIST_MAP_ANOMALY) return fail(XHIST_ERR_INVALID, "unknown map op %d", op);
+  if (op == XHIST_MAP_ANOMALY && !values) return fail(XHIST_ERR_INVALID, "values are required");
+  if (op != XHIST_MAP_ANOMALY && values) return fail(XHIST_ERR_INVALID, "only XHIST_MAP_ANOMALY takes values");
+  if (op == XHIST_MAP_INDEX && (centre || scale)) return fail(XHIST_ERR_INVALID, "XHIST_MAP_INDEX takes no table");
+  if (op == XHIST_MAP_TAKE && scale) return fail(XHIST_ERR_INVALID, "XHIST_MAP_TAKE takes no scale table");
+  const bool work = p && n_rows > 0 && n_cols > 0 && p->n_bins > 0;
+  const int rc = execute_values(p, "xhist_plan_execute_map", samples, values, nullptr, nullptr, n_rows, n_cols, static_cast<double*>(out),
+                                !work || op == XHIST_MAP_INDEX || centre != nullptr, "the table (centre) is NULL", mem_kind, stream,
+                                [&](const ValuesCall& k) { return xhist_map_run(k, op, centre, scale, out); }, false);
+  if (rc != XHIST_OK || p->n_bins > 0 || n_rows <= 0 || n_cols <= 0) return rc;
+  // A plan without bins (an edge array of a single edge) counts no sample, and the statistics' front has no output row to launch
+  // over: the block is still written, -1 for XHIST_MAP_INDEX and NaN for the others.  Bytes of all ones are both.
+  if (!out) return fail(XHIST_ERR_INVALID, "out is NULL");
+  DeviceGuard g;
+  if (int grc = g.set(p->device)) return grc;
+  HIPC(hipMemsetAsync(out, 0xff, (size_t)n_rows * (size_t)n_cols * 8, static_cast<hipStream_t>(stream)));
+  return XHIST_OK;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -365,7 +365,8 @@ static inline int fast_copies_log2(int64_t n_bins, size_t slot, size_t tbytes, s
 // fast if eligible, else generic with its slots in LDS, else generic straight into global memory.  The largest slot of the
 // passes decides; every pass takes the family, the home and the copies chosen for it.  The call's third stream (nullptr: none)
 // must qualify for the fast family as the values do: the sample dtype, unit column stride (or one column), element-aligned; so
-// must its fourth, and either alone sends the call to the generic family.
+// must its fourth, and either alone sends the call to the generic family.  A call without values (k.values == nullptr: the maps
+// of xhist_map.hip that read the samples alone) is judged by its samples.
 static inline ValuesChoice choose_values(const ValuesCall& k, const ValuesSlots& sl) {
   const ValuesPlan& pl = k.pl;
   const xhist_array *samples = k.samples, *values = k.values;
@@ -374,11 +375,11 @@ static inline ValuesChoice choose_values(const ValuesCall& k, const ValuesSlots&
   const int D = pl.n_dims;
   const int sdt = samples[0].dtype;
   c.f32 = sdt == XHIST_F32;
-  bool fast_ok = pl.cmp == XHIST_CMP_F64 && D <= 2 && (sdt == XHIST_F64 || sdt == XHIST_F32) && values->dtype == sdt &&
+  bool fast_ok = pl.cmp == XHIST_CMP_F64 && D <= 2 && (sdt == XHIST_F64 || sdt == XHIST_F32) && (!values || values->dtype == sdt) &&
                  pl.n_bins < ((int64_t)1 << 24);
   for (int d = 0; d < D && fast_ok; ++d)
     fast_ok = samples[d].dtype == sdt && (samples[d].col_stride == 1 || n_cols == 1) && (uintptr_t)samples[d].data % (size_t)elem_bytes(sdt) == 0;
-  if (fast_ok) fast_ok = (values->col_stride == 1 || n_cols == 1) && (uintptr_t)values->data % (size_t)elem_bytes(sdt) == 0;
+  if (fast_ok && values) fast_ok = (values->col_stride == 1 || n_cols == 1) && (uintptr_t)values->data % (size_t)elem_bytes(sdt) == 0;
   for (const xhist_array* x : {k.third, k.fourth})
     if (fast_ok && x) fast_ok = x->dtype == sdt && (x->col_stride == 1 || n_cols == 1) && (uintptr_t)x->data % (size_t)elem_bytes(sdt) == 0;
   if (fast_ok) {
@@ -494,12 +495,14 @@ static inline Params values_params(const ValuesCall& k, const ValuesChoice& c, i
     kp.s_dt[d] = samples[d].dtype;
     kp.dim[d] = c.tab->dim[d];
   }
-  kp.w_ptr = values->data;
-  kp.w_rs = values->row_stride;
-  kp.w_cs = values->col_stride;
-  kp.w_ir = values->inner_rows;
-  kp.w_os = values->outer_stride;
-  kp.w_dt = values->dtype;
+  if (values) {  // (a call without values leaves the block zeroed: its kernels read none)
+    kp.w_ptr = values->data;
+    kp.w_rs = values->row_stride;
+    kp.w_cs = values->col_stride;
+    kp.w_ir = values->inner_rows;
+    kp.w_os = values->outer_stride;
+    kp.w_dt = values->dtype;
+  }
   kp.row0 = r0;
   kp.n_dims = pl.n_dims;
   kp.tables = c.tab->blob;

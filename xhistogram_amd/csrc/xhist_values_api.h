@@ -36,7 +36,7 @@ struct ValuesPlan {
 typedef void* (*xhist_values_alloc_fn)(void* ctx, size_t bytes);
 
 // What stays the same through one call (built once by xhist_capi.hip's execute_values, which owns everything it points to):
-// the plan; the input streams (`third`: the weights, or the second value array of the covariances; `fourth`: the weights of
+// the plan; the input streams (`values`: nullptr for the maps that read the samples alone; `third`: the weights, or the second value array of the covariances; `fourth`: the weights of
 // the weighted covariance; nullptr where a statistic has none); the shape; the stream; where an error message and the line
 // about the launches go (the latter becomes the plan's describe()); the scratch allocator.
 struct ValuesCall {
@@ -94,3 +94,8 @@ int xhist_cov_w_run(const ValuesCall& k, void* out_first, double* out_mean, doub
 // k.third its weights, is numpy's inverted_cdf) -> out, float64 [n_q, n_rows, n_bins]
 int xhist_quantile_run(const ValuesCall& k, const double* q, int n_q, int method, double* out);
 int xhist_quantile_w_run(const ValuesCall& k, const double* q, int n_q, double* out);
+
+// xhist_map.hip: the per-sample maps.  op is XHIST_MAP_INDEX (k.values nullptr, no table), XHIST_MAP_TAKE (k.values nullptr,
+// centre the table) or XHIST_MAP_ANOMALY (k.values the values, centre the means, scale nullptr or the standard deviations);
+// centre and scale are float64 [n_rows, n_bins], out a dense [n_rows, n_cols] block of 8-byte elements, each written once.
+int xhist_map_run(const ValuesCall& k, int op, const double* centre, const double* scale, void* out);

@@ -14,7 +14,8 @@ from .core import histogram as _core_histogram
 from .core import histogram_two_weights as _core_histogram_two_weights
 
 __all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
-           "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt", "histogram_argextrema"]
+           "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt", "histogram_argextrema", "bin_index", "histogram_lookup",
+           "histogram_anomaly"]
 
 
 def _xr():
@@ -369,3 +370,87 @@ def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords
             if c not in coords and set(first[c].dims).issubset(out_dims):
                 coords[c] = first[c]
     return results, out_dims, coords, extra[0].name or "values"
+
+
+# ---------------------------------------------------------------------------------------------
+# per-sample maps: DataArrays on the broadcast dims of the inputs
+# ---------------------------------------------------------------------------------------------
+def _lined_up(name, data_args, extra):
+    """the inputs of a per-sample map (DataArrays: the named samples, then `extra`), aligned exactly and broadcast by
+    dimension name as :func:`histogram` does: (their data in one dim order, that order, the first operand)"""
+    xr = _xr()
+    for a in list(data_args) + list(extra):
+        if not isinstance(a, xr.DataArray):
+            raise TypeError(
+                "xhistogram.xarray.%s accepts only xarray.DataArray objects but a %s was provided" % (name, type(a).__name__)
+            )
+    for a in data_args:
+        assert a.name is not None, "all arrays must have a name"
+    operands = list(xr.align(*[a.reset_coords(drop=True) for a in list(data_args) + list(extra)], join="exact"))
+    dims_order = []
+    for a in operands:
+        for d in a.dims:
+            if d not in dims_order:
+                dims_order.append(d)
+    arrays = []
+    for a in operands:
+        missing = [d for d in dims_order if d not in a.dims]
+        if missing:
+            a = a.expand_dims({d: 1 for d in missing})
+        if tuple(a.dims) != tuple(dims_order):
+            a = a.transpose(*dims_order)
+        arrays.append(a.data)
+    return arrays, dims_order, operands[0]
+
+
+def _sample_coords(first, dims_order):
+    return {d: first[d] for d in dims_order if d in first.coords}
+
+
+def bin_index(*args, bins=None, range=None):
+    """The bin of every sample (:func:`xhistogram_amd.core.bin_index`): an int64 DataArray on the broadcast dims of ``args``,
+    named ``<first arg>_bin_index``, ``-1`` where ``histogram`` drops the sample."""
+    from .core import bin_index as _core_bin_index
+
+    arrays, dims_order, first = _lined_up("bin_index", args, [])
+    out, _ = _core_bin_index(*arrays, bins=bins, range=range)
+    return _xr().DataArray(out, dims=dims_order, coords=_sample_coords(first, dims_order), name="%s_bin_index" % args[0].name)
+
+
+def histogram_lookup(*args, table, bins=None, range=None, dim=None, bin_dim_suffix="_bin"):
+    """A per-bin DataArray read back at every sample (:func:`xhistogram_amd.core.histogram_lookup`).  ``table`` has the dims
+    :func:`histogram` gives for the same ``args`` and ``dim`` (kept dims and ``<arg name> + bin_dim_suffix``, in any order).
+    Returns a float64 DataArray on the broadcast dims of ``args``, named ``<table name>_lookup`` (``table`` without a name)."""
+    from .core import histogram_lookup as _core_histogram_lookup
+
+    xr = _xr()
+    if not isinstance(table, xr.DataArray):
+        raise TypeError("xhistogram.xarray.histogram_lookup accepts only xarray.DataArray objects but a %s was provided"
+                        % type(table).__name__)
+    arrays, dims_order, first = _lined_up("histogram_lookup", args, [])
+    kept = [d for d in dims_order if dim is not None and d not in dim]
+    want = kept + [a.name + bin_dim_suffix for a in args]
+    if set(table.dims) != set(want):
+        raise ValueError("table has dims %s, but histogram gives %s for these arguments" % (tuple(table.dims), tuple(want)))
+    t = table if tuple(table.dims) == tuple(want) else table.transpose(*want)
+    axis = None if dim is None else [dims_order.index(d) for d in dim]
+    out, _ = _core_histogram_lookup(*arrays, table=t.data, bins=bins, range=range, axis=axis)
+    return xr.DataArray(out, dims=dims_order, coords=_sample_coords(first, dims_order), name="%s_lookup" % (table.name or "table"))
+
+
+def histogram_anomaly(*args, values, bins=None, range=None, dim=None, weights=None, ddof=0, standardize=False):
+    """Every sample's value relative to the mean of its bin (:func:`xhistogram_amd.core.histogram_anomaly`); ``values`` and
+    ``weights`` are lined up as :func:`histogram_mean_var` lines them up.  Returns a float64 DataArray on the broadcast dims of
+    the inputs, named ``<values name>_anomaly`` (``values`` without a name)."""
+    from .core import histogram_anomaly as _core_histogram_anomaly
+
+    if values is None:
+        raise TypeError("histogram_anomaly needs values")
+    extra = [values] + ([] if weights is None else [weights])
+    arrays, dims_order, first = _lined_up("histogram_anomaly", args, extra)
+    n = len(args)
+    axis = None if dim is None else [dims_order.index(d) for d in dim]
+    out, _ = _core_histogram_anomaly(*arrays[:n], values=arrays[n], bins=bins, range=range, axis=axis,
+                                     weights=arrays[n + 1] if weights is not None else None, ddof=ddof, standardize=standardize)
+    return _xr().DataArray(out, dims=dims_order, coords=_sample_coords(first, dims_order),
+                           name="%s_anomaly" % (values.name or "values"))
