@@ -60,7 +60,8 @@ def _rows(a, axis, ndim):
     kept = [i for i in range(ndim) if i not in red]
     moved = np.transpose(a, kept + red)
     m = int(np.prod([a.shape[i] for i in kept], dtype=np.int64))
-    return moved.reshape(m, -1), moved.shape, np.argsort(kept + red)
+    c = int(np.prod([a.shape[i] for i in red], dtype=np.int64))  # (said outright: numpy infers no extent of an array without elements)
+    return moved.reshape(m, c), moved.shape, np.argsort(kept + red)
 
 
 def lookup(samples, edges, table, axis=None):
@@ -112,6 +113,79 @@ def anomaly(samples, edges, values, mean, scale=None, axis=None):
         if scale is not None:
             out = out / lookup(samples, edges, scale, axis)
     return out
+
+
+def variance_star(samples, edges, values, axis=None, ddof=0, weights=None):
+    """(var*, b), each [rows, n_bins]: what histogram_mean_var's variance must be and how far the kernels' may lie from it,
+    from the project's own bounds.  Unweighted: values_exact.expected followed by var_bound; weighted:
+    meanvar_weighted_oracle's exact mode, m2_bound and var_bound (what tests/test_gpu_meanvar_weighted.check_exact applies).
+    b == 0 where the variance is bit for bit (the power-of-two counts of values_exact.m2_exact, the power-of-two sums of
+    weights of the weighted oracle); both NaN where the variance is (no value in the bin, n <= ddof)."""
+    import meanvar_weighted_oracle as mwo
+    import values_exact as vx
+
+    idx = index(samples, edges)
+    n_bins = int(np.prod([len(e) - 1 for e in edges]))
+    i2, _, _ = _rows(idx, axis, idx.ndim)
+    m = i2.shape[0]
+    if idx.size == 0:
+        return np.full((m, n_bins), np.nan), np.full((m, n_bins), np.nan)
+    v2, _, _ = _rows(np.broadcast_to(np.asarray(values).astype(np.float64), idx.shape), axis, idx.ndim)
+    if weights is None:
+        take = i2 >= 0
+        flat = (i2 + np.arange(m, dtype=np.int64)[:, None] * n_bins)[take]
+        cnt, _, m2, bound, pow2 = vx.expected(flat, v2[take], m * n_bins)
+        var, b = vx.var_bound(cnt, m2, bound, ddof)
+    else:
+        xl = [_rows(np.broadcast_to(np.asarray(s), idx.shape), axis, idx.ndim)[0] for s in samples]
+        w2, _, _ = _rows(np.broadcast_to(np.asarray(weights).astype(np.float64), idx.shape), axis, idx.ndim)
+        wsum, mean, m2 = mwo.mean_var_w_rows(xl, edges, v2, w2, exact=True)
+        var, b, pow2 = mwo.var_bound(wsum, m2, mwo.m2_bound(xl, edges, v2, w2, mean), ddof)
+    b = np.where(np.isnan(var), np.nan, np.where(pow2.reshape(var.shape), 0.0, b))
+    return var.reshape(m, n_bins), b.reshape(m, n_bins)
+
+
+def standardized_bracket(a, var, b):
+    """where (float64(v) - mean[bin]) / sqrt(var[bin]) may lie, per sample: `a` the anomaly (exact bits), `var` and `b` the
+    sample's bin's var* and bound (NaN where the sample is not counted or the variance is NaN).
+      must_nan  a or var is NaN: the result is NaN
+      exact     b == 0: the result is `want` = fl(a / fl(sqrt(var*))), IEEE's bit for bit (0 / 0 included: NaN)
+      elsewhere the closed interval [lo, hi] spanned by fl(a / s_lo) and fl(a / s_hi), s_lo = sqrt(max(0, var* - b)) one ulp
+                down and s_hi = sqrt(var* + b) one ulp up; with s_lo == 0 the interval is open towards +-inf on a's side,
+                and NaN (0 / 0) is allowed for a == 0 alone (`nan_ok`)"""
+    a, var, b = (np.asarray(x, np.float64) for x in (a, var, b))
+    must_nan = np.isnan(a) | np.isnan(var)
+    exact = ~must_nan & (b == 0)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        want = a / np.sqrt(var)
+        s_hi = np.nextafter(np.sqrt(var + b), np.inf)
+        s_lo = np.sqrt(np.maximum(var - b, 0.0))
+        s_lo = np.where(s_lo > 0, np.nextafter(s_lo, 0.0), 0.0)
+        e_hi, e_lo = a / s_hi, a / s_lo
+    open_ = ~must_nan & ~exact & (s_lo == 0)
+    zero = np.zeros_like(a)
+    lo = np.where(open_, np.where(a > 0, e_hi, np.where(a < 0, -np.inf, zero)), np.fmin(e_lo, e_hi))
+    hi = np.where(open_, np.where(a > 0, np.inf, np.where(a < 0, e_hi, zero)), np.fmax(e_lo, e_hi))
+    return dict(must_nan=must_nan, exact=exact, want=want, lo=lo, hi=hi, nan_ok=open_ & (a == 0))
+
+
+def assert_standardized(got, a, var, b, what=""):
+    """the standardized anomaly held to standardized_bracket -> (samples held bit for bit, samples held to the interval)"""
+    got = np.asarray(got)
+    assert got.dtype == np.float64 and got.shape == np.shape(a), (what, got.dtype, got.shape, np.shape(a))
+    k = standardized_bracket(a, var, b)
+    gn = np.isnan(got)
+    assert gn[k["must_nan"]].all(), "%s: a number where the sample, the value or the bin's variance gives NaN" % what
+    ex = k["exact"]
+    assert_bits(got[ex], k["want"][ex], what + " (bit for bit)")
+    rest = ~k["must_nan"] & ~ex
+    bad = rest & gn & ~k["nan_ok"]
+    assert not bad.any(), "%s: NaN at %d samples whose bin has a variance" % (what, bad.sum())
+    inside = rest & ~gn
+    bad = inside & ~((k["lo"] <= got) & (got <= k["hi"]))
+    assert not bad.any(), "%s: %d samples outside the bracket, first at %s: %r not in [%r, %r]" % (
+        what, bad.sum(), np.argwhere(bad)[0], got[bad][0], k["lo"][bad][0], k["hi"][bad][0])
+    return int(ex.sum()), int(inside.sum())
 
 
 def assert_bits(got, want, what=""):

@@ -128,3 +128,15 @@ def var_of(wsum, m2, ddof):
     """M2 / (W - ddof), NaN where W <= ddof"""
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(wsum > ddof, m2 / (wsum - ddof), np.nan)
+
+
+def var_bound(wsum, m2, b, ddof):
+    """(var, its bound, exact) from the exact mode's W and M2 and m2_bound's b: var = M2 / (W - ddof) is bit for bit (`exact`)
+    where W is a power of two up to POW2_EXACT and above ddof; elsewhere the kernels' lies within b / (W - ddof) plus the
+    division's and the host's roundings, 4 U |var|"""
+    var = var_of(wsum, m2, ddof)
+    lg = np.log2(np.where(wsum > 0, wsum, 1))
+    pow2 = (wsum > ddof) & (wsum <= POW2_EXACT) & (lg == np.round(lg))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        lim = b / np.where(wsum > ddof, wsum - ddof, 1) + 4 * U * np.abs(var)
+    return var, lim, pow2

@@ -61,14 +61,9 @@ def check_exact(xl, edges, vl, wl, got, ddof=0, what=""):
     gW, gm, gv = (np.asarray(a).reshape(W.shape) for a in got)
     np.testing.assert_array_equal(gW, W, err_msg=what)
     np.testing.assert_array_equal(gm, mean, err_msg=what)
-    var = mwo.var_of(W, m2, ddof)
-    lg = np.log2(np.where(W > 0, W, 1))
-    pow2 = (W > ddof) & (W <= mwo.POW2_EXACT) & (lg == np.round(lg))
+    var, lim, pow2 = mwo.var_bound(W, m2, mwo.m2_bound(xl, edges, vl, wl, mean), ddof)
     np.testing.assert_array_equal(gv[pow2], var[pow2], err_msg=what)
     rest = (W > ddof) & ~pow2
-    b = mwo.m2_bound(xl, edges, vl, wl, mean)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        lim = b / np.where(W > ddof, W - ddof, 1) + 4 * mwo.U * np.abs(var)
     assert np.all(np.abs(gv[rest] - var[rest]) <= lim[rest]), what
     np.testing.assert_array_equal(np.isnan(gv), np.isnan(var), err_msg=what)
     return W

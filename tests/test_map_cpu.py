@@ -1,7 +1,9 @@
 """tests/map_oracle.py held to what it restates, where no GPU is needed: its index against the golden hot-path vectors and
 against np.digitize on edges and special values, its lookup and anomaly on a case small enough to write down, the borders of
 the restated kernel choice, and that every case table of tests/map_cases.py (the GPU module's) lands on the kernel it is meant for.  Also the
-Python front's surface: the symbol, the Plan method, the public functions and their checks before any device work."""
+Python front's surface: the symbol, the Plan method, the public functions and their checks before any device work.  Last, what
+tests/test_gpu_map_properties.py relies on: the conditions of its 120 replayed cases and drawn tables (tallies printed), the
+interval of the standardized anomaly, the closed form of the row-chunk test against the oracle, and the 8-input case."""
 import os
 
 import numpy as np
@@ -274,3 +276,191 @@ def test_values_call_without_values_keeps_the_samples():
     assert backend == "numpy" and len(arrays) == 2 and arrays[1].shape == (2, 3) and axis == [1] and drop == (1,)
     with pytest.raises(TypeError, match="histogram_extrema needs values"):
         core._values_call((x,), None, e[:1], None, None, "histogram_extrema")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# what tests/test_gpu_map_properties.py relies on
+# ---------------------------------------------------------------------------------------------------------------------
+def _replayed(stat):
+    """the 60 cases of `stat` as tests/test_gpu_map_properties.py replays them, built, with what the maps must give on them"""
+    pytest.importorskip("hypothesis")
+    pytest.importorskip("torch")  # (for_each_case lives in a GPU file that imports it; none of this needs a GPU)
+    import test_gpu_values_properties as tgp
+    import values_cases as vc
+
+    if stat not in _REPLAYED:
+        cases = []
+        tgp.for_each_case(stat, tgp.EXAMPLES, cases.append)
+        assert len(cases) == tgp.EXAMPLES
+        _REPLAYED[stat] = [(c, mc.expectations(vc.build(c))) for c in cases]
+    return _REPLAYED[stat]
+
+
+_REPLAYED = {}
+
+
+def _ieee(w, var=None):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return w["anomaly"] / np.sqrt(w["var"] if var is None else var)
+
+
+@pytest.mark.parametrize("stat", mc.MAP_STATS)
+def test_replayed_cases_meet_their_conditions(stat):
+    """the conditions under which the comparisons of test_gpu_map_properties.test_random_cases_match_oracle bite; the tallies
+    are those of that file's docstring (pytest -s prints them)"""
+    import collections
+
+    t = collections.Counter()
+    largest = 0
+    for case, w in _replayed(stat):
+        n = int(np.prod(case["shape"]))
+        largest = max(largest, n)
+        t["without an element"] += n == 0
+        t["a finite mean"] += bool(np.isfinite(w["mean"]).any())
+        t["a finite positive variance"] += bool((np.isfinite(w["var_table"]) & (w["var_table"] > 0)).any())
+        n_exact, n_bracket = mo.assert_standardized(_ieee(w), w["anomaly"], w["var"], w["bound"], repr(case))
+        t["bit-for-bit branch"] += n_exact > 0
+        t["bracket branch"] += n_bracket > 0
+        spec, buf, view, image = mc.table_draw(case)
+        kept, bins = mc.table_shape(case)
+        assert view.shape == image.shape == kept + bins and view.dtype == np.dtype(spec["dtype"])
+        assert np.array_equal(np.asarray(view, F64), image) and image.flags.c_contiguous
+        for k in ("dtype", "container", "laid"):
+            t["%s %s" % (k, spec[k])] += 1
+        if view.ndim > 1 and min(view.shape) > 1:
+            assert view.flags.c_contiguous == (spec["laid"] == "contiguous"), spec
+            t["tables that are not one contiguous block"] += not view.flags.c_contiguous
+        if spec["laid"] == "broadcast":
+            assert not view.flags.writeable and 0 in view.strides
+        if spec["container"] == "list":
+            assert np.shape(view.tolist()) == view.shape
+    print("\n%s: largest case %d elements; %s" % (stat, largest, ", ".join("%s %d" % kv for kv in sorted(t.items()))))
+    assert t["a finite mean"] >= 55 and t["a finite positive variance"] >= 40 and t["without an element"] <= 5
+    assert t["bit-for-bit branch"] >= 10 and t["bracket branch"] >= 10
+    for k, options in (("dtype", mc.TABLE_DTYPES), ("container", mc.TABLE_CONTAINERS), ("laid", mc.TABLE_LAYOUTS)):
+        for o in options:
+            assert t["%s %s" % (k, o)] >= 2, (k, o)
+
+
+@pytest.mark.parametrize("stat", mc.MAP_STATS)
+def test_bracket_holds_what_it_must_and_rejects_a_float32_root(stat):
+    """map_oracle.standardized_bracket on the replayed cases: it contains fl(a / sqrt(var)) for var*, var* + b and var* - b
+    (the variances the project's bounds allow the kernels), and a result made with a float32 square root falls outside
+    wherever that root is not the float64 one to nine digits"""
+    rejected = should = 0
+    for case, w in _replayed(stat):
+        a, var, b = w["anomaly"], w["var"], w["bound"]
+        for v in (var, var + b, np.maximum(var - b, 0.0)):
+            mo.assert_standardized(_ieee(w, v), a, var, b, repr(case))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            root32 = np.sqrt(var.astype(F32)).astype(F64)
+            off = np.isfinite(a) & (a != 0) & (var > 0) & (np.abs(root32 - np.sqrt(var)) > 1e-9 * np.sqrt(var))
+            z32 = a / root32
+        if off.any():
+            should += 1
+            with pytest.raises(AssertionError):
+                mo.assert_standardized(z32, a, var, b)
+            rejected += 1
+    print("\n%s: a float32 square root rejected in %d cases of %d" % (stat, rejected, should))
+    assert rejected >= 10
+
+
+def test_bracket_written_down():
+    nan, inf = np.nan, np.inf
+    a = np.array([3.0, -3.0, 0.0, 0.0, 2.0, -2.0, 0.0, nan, 1.0])
+    var = np.array([4.0, 4.0, 0.0, 4.0, 1e-30, 1e-30, 1e-30, 1.0, nan])
+    b = np.array([0.0, 1.0, 0.0, 1.0, 1e-29, 1e-29, 1e-29, 0.0, nan])
+    k = mo.standardized_bracket(a, var, b)
+    assert k["must_nan"].tolist() == [0, 0, 0, 0, 0, 0, 0, 1, 1] and k["exact"].tolist() == [1, 0, 1, 0, 0, 0, 0, 0, 0]
+    assert k["want"][0] == 1.5 and np.isnan(k["want"][2])  # (0 / 0 is IEEE's NaN, bit-for-bit branch)
+    assert k["lo"][1] < -3.0 / np.sqrt(3.0) and k["hi"][1] > -3.0 / np.sqrt(5.0) and k["hi"][1] < -1.34
+    assert (k["lo"][3], k["hi"][3]) == (0.0, 0.0)
+    assert k["hi"][4] == inf and 1e14 < k["lo"][4] <= 2.0 / np.sqrt(1.1e-29) and k["lo"][5] == -inf and k["hi"][5] < 0
+    assert k["nan_ok"].tolist() == [0, 0, 0, 0, 0, 0, 1, 0, 0]
+    good = np.array([1.5, -1.5, nan, 0.0, 1e20, -inf, nan, nan, nan])
+    assert mo.assert_standardized(good, a, var, b) == (2, 4)
+    for i, wrong in ((0, np.nextafter(1.5, 2.0)), (1, -1.3), (2, 0.0), (4, nan), (5, 1.0), (6, 1e-3), (7, 0.0), (3, nan)):
+        z = good.copy()
+        z[i] = wrong
+        with pytest.raises(AssertionError):
+            mo.assert_standardized(z, a, var, b)
+
+
+@pytest.mark.parametrize("block", [256, 512])
+def test_rows_closed_form_is_the_oracle(block):
+    """map_cases.rows_expected, the expectation of test_more_rows_than_one_launch, against map_oracle run by brute force on the
+    rows themselves: the first 4096 rows, 2048 on each side of the first launch's last row, and the last 4096"""
+    chunk = mc.launch_rows(block, 1)
+    assert chunk == {256: 16_777_215, 512: 8_388_607}[block]
+    n_rows = chunk + mc.ROWS_EXTRA
+    windows = [np.arange(0, 4096), np.arange(chunk - 2048, chunk + 2048), np.arange(n_rows - 4096, n_rows)]
+    for family, op in mc.ROW_CASES:
+        if (family == "fast") != (block == 256):
+            continue
+        edges, xs, vs = mc.rows_data(family, op)
+        assert xs.shape == (mc.P_S, mc.ROWS_COLS) and len(edges[0]) - 1 == mc.ROWS_BINS
+        bin_base = mo.index([xs], edges)
+        assert 0.25 < (bin_base < 0).mean() < 0.45 and set(np.unique(bin_base)) == {-1, 0, 1}
+        if xs.dtype.kind == "f":
+            assert np.isnan(xs).sum() >= 10
+        v_base = None if vs is None else vs.astype(F64)
+        for rows in windows:
+            x_rows = xs[rows % mc.P_S]
+            b = np.arange(mc.ROWS_BINS)[None, :]
+            centre = mc.centre_of(np, rows[:, None], b)
+            scale = mc.scale_of(np, rows[:, None], b, mc.SCALE_LUT)
+            assert centre.shape == scale.shape == (len(rows), mc.ROWS_BINS) and centre.dtype == scale.dtype == F64
+            if op == "index":
+                want = mo.index([x_rows], edges)
+            elif op == "take":
+                want = mo.lookup([x_rows], edges, centre, axis=1)
+            else:
+                want = mo.anomaly([x_rows], edges, vs[rows % mc.P_V], centre, scale, axis=1)
+            got = mc.rows_expected(np, op, rows, bin_base, v_base, mc.SCALE_LUT if op == "anomaly" else None)
+            mo.assert_bits(got, want, "%s %s rows %d.." % (family, op, rows[0]))
+
+
+def test_row_tables_make_the_arithmetic_exact():
+    """centre is a multiple of 2^-3 that depends on the row and on the bin, scale a power of two that depends on both, the
+    periods are coprime, and v - centre and its division by scale are exact: against fractions.Fraction"""
+    import math
+    from fractions import Fraction
+
+    assert math.gcd(mc.P_S, mc.P_V) == 1 and mc.ROWS_COLS != mc.ROWS_BINS and min(mc.ROWS_COLS, mc.ROWS_BINS) > 1
+    r = np.arange(0, 5000)[:, None]
+    b = np.arange(mc.ROWS_BINS)[None, :]
+    c, s = mc.centre_of(np, r, b), mc.scale_of(np, r, b, mc.SCALE_LUT)
+    assert np.all(c * 8 == np.round(c * 8)) and np.all(np.abs(c) < 1024)
+    assert np.all(np.frexp(s)[0] == 0.5)  # powers of two
+    for t in (c, s):
+        assert (t[:, 0] != t[:, 1]).all() and (t[:-1] != t[1:]).all()  # (it depends on the bin, and on the row)
+    rng = np.random.default_rng(7)
+    for family, op in (("fast", "anomaly"), ("generic", "anomaly")):
+        _, _, vs = mc.rows_data(family, op)
+        v = vs.astype(F64).reshape(-1)
+        v = v[~np.isnan(v)]
+        for _ in range(150):
+            vi, ri, bi = float(rng.choice(v)), int(rng.integers(0, 1 << 24)), int(rng.integers(0, 2))
+            ci = float(mc.centre_of(np, np.array(ri), np.array(bi)))
+            si = float(mc.scale_of(np, np.array(ri), np.array(bi), mc.SCALE_LUT))
+            assert Fraction(vi - ci) == Fraction(vi) - Fraction(ci)
+            assert Fraction((vi - ci) / si) == (Fraction(vi) - Fraction(ci)) / Fraction(si)
+
+
+def test_joint_inputs_straddle_32_bits():
+    edges, xs = mc.joint_inputs()
+    assert len(xs) == len(edges) == 8 and all(x.shape == (4099,) and x.dtype == F64 for x in xs)
+    assert int(np.prod([len(e) - 1 for e in edges], dtype=object)) == 17 ** 8 == 6_975_757_441
+    ok, bins = mo.per_input_bins(xs, edges)
+    idx = mo.index(xs, edges)
+    assert idx[:4].tolist() == [(1 << 32) - 1, 1 << 32, 0, 17 ** 8 - 1]
+    assert (idx >= 1 << 32).sum() > 1000 and ((idx >= 0) & (idx < 1 << 32)).sum() > 1000
+    want = np.where(ok, np.ravel_multi_index([np.where(ok, b, 0) for b in bins], (17,) * 8), -1)
+    np.testing.assert_array_equal(idx, want)
+    for d in range(8):  # every input drops samples that every other input counts
+        others = np.ones(4099, bool)
+        for k in range(8):
+            if k != d:
+                others &= mo.per_input_bins([xs[k]], [edges[k]])[0]
+        dropped = ~mo.per_input_bins([xs[d]], [edges[d]])[0]
+        assert (dropped & others).sum() >= 20 and np.isnan(xs[d]).sum() >= 8
