@@ -158,6 +158,29 @@ int xhist_plan_execute_argextrema(xhist_plan* plan, const xhist_array* samples, 
                                   int64_t n_rows, int64_t n_cols, double* out_values, int64_t* out_index,
                                   int mem_kind, void* stream);
 
+/* Per-bin count and sum of `values` that do not depend on the order of arrival (added within ABI v11): which samples count is
+ * exactly what xhist_plan_execute_mean_var counts (a counted sample whose value is not NaN contributes that value converted to
+ * float64), and out_count is its count.  out_total is defined on integers, per (row, bin):
+ *   A = the largest |v| of the bin (pass 1 is xhist_plan_execute_extrema's); E = frexp(A)'s exponent, U = max(E - 96, -1074);
+ *   a value v = s * m * 2^e (m the 53-bit integer significand, e = -1074 for subnormals) becomes q = m << (e - U), or m >> (U - e)
+ *   truncated towards zero (0 once the shift reaches 64); q < 2^96 is split into three unsigned 32-bit limbs, and s * limb_j is
+ *   added into three int64 accumulators; out_total = RN_even((L0 + L1 * 2^32 + L2 * 2^64) * 2^U), one rounding in integer
+ *   arithmetic, overflowing to +-inf as IEEE does, a zero result +0.0.  An empty bin gives +0.0.  A bin that holds an infinity
+ *   gives that infinity, or NaN where it holds both.
+ * The result is the same bits for any order of the samples, launch geometry and run.  Every value within a factor 2^43 of its
+ * bin's largest magnitude is converted exactly, and a bin of such values gets the correctly rounded exact sum; in general
+ * |out_total - exact| <= ulp(out_total) / 2 + n * 2^(E - 96).  No intermediate overflows.
+ *   values: an xhist_array of any real dtype, same logical [n_rows, n_cols] shape as the samples (strides 0 broadcast).
+ *   n_cols must be below 2^31 (the accumulators hold that many limbs): XHIST_ERR_UNSUPPORTED otherwise, before any device work.
+ *   out_count (int64), out_total (float64): contiguous [n_rows, prod(nb_d)] DEVICE buffers, overwritten (no accumulate mode);
+ *   five 8-byte scratch blocks of that size are taken for the call.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Asynchronous on `stream`.  xhist_plan_describe then names the kernel family of each pass and where its slots live
+ *   ("sum pass1=extrema_... pass2=sum_..."). */
+int xhist_plan_execute_sum(xhist_plan* plan, const xhist_array* samples, const xhist_array* values,
+                           int64_t n_rows, int64_t n_cols, int64_t* out_count, double* out_total,
+                           int mem_kind, void* stream);
+
 /* Per-bin count, mean and sum of squared deviations of `values` (ABI v11): which samples count is exactly what
  * xhist_plan_execute counts (same digitize, last bin closed, NaN / out-of-range samples dropped); each counted sample whose
  * value is not NaN contributes that value converted to float64.  Two passes (Chan, Golub & LeVeque): n and S = sum(v), then
@@ -460,6 +483,13 @@ int xhist_scratch_stats(int device, uint64_t* stats, int n);
  * units, which is what tests/test_gpu_exchange.py needs to show that such a call fails fast instead of waiting for a deadline.
  * Asynchronous; replaces nothing of the reference. */
 int xhist_debug_hold_cus(int device, int workgroups, int lds_bytes, int64_t microseconds, void* stream);
+
+/* TEST SUPPORT (added within ABI v11) — xhist_plan_execute_sum's integer arithmetic on the HOST, over one bin: the `n` values
+ * (HOST pointer; NaN ignored) go through the very functions the kernels compile (the unit from the extremes, the limbs, the one
+ * rounding), the accumulators plain int64 additions.  Needs no device; n < 2^31. */
+int xhist_debug_sum_host(const double* values, int64_t n, int64_t* out_count, double* out_total);
+/* ... and the one rounding alone: *out = RN_even((L0 + L1 * 2^32 + L2 * 2^64) * 2^U), -1074 <= U <= 1023. */
+int xhist_debug_sum_round(int64_t L0, int64_t L1, int64_t L2, int U, double* out);
 
 /* free cached plans and scratch on every device */
 int xhist_shutdown(void);

@@ -73,7 +73,8 @@ EXPORTS = (
     "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
     "xhist_plan_execute_quantile_weighted", "xhist_plan_execute_cov", "xhist_plan_execute_cov_weighted",
     "xhist_plan_execute_skew_kurt", "xhist_plan_execute_skew_kurt_weighted", "xhist_plan_execute_argextrema",
-    "xhist_plan_execute_map", "xhist_bincount_rows",
+    "xhist_plan_execute_map", "xhist_plan_execute_sum", "xhist_debug_sum_host", "xhist_debug_sum_round",
+    "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
     "xhist_comm_wait", "xhist_comm_destroy", "xhist_buffer_alloc", "xhist_buffer_free", "xhist_buffer_copy", "xhist_buffer_add", "xhist_buffer_copy_nd",
@@ -142,6 +143,9 @@ def load():
         lib.xhist_plan_execute_argextrema.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
         ]
+        lib.xhist_plan_execute_sum.argtypes = lib.xhist_plan_execute_argextrema.argtypes
+        lib.xhist_debug_sum_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+        lib.xhist_debug_sum_round.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double)]
         lib.xhist_plan_execute_mean_var.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_int, C.c_void_p,
@@ -400,6 +404,13 @@ class Plan:
         buffers, asynchronous on `stream` (xhist_plan_execute_argextrema)"""
         self._execute_values("xhist_plan_execute_argextrema", sample_views, (value_view,), n_rows, n_cols,
                              (out_values_ptr, out_index_ptr), stream=stream)
+
+    def execute_sum(self, sample_views, value_view, n_rows, n_cols, out_count_ptr, out_total_ptr, stream=0):
+        """per-bin count (int64) and order-independent sum (float64; +0.0 where no value arrived) of the values of
+        device-resident views, into device buffers of [n_rows, bins] each, asynchronous on `stream`
+        (xhist_plan_execute_sum); fewer than 2^31 columns"""
+        self._execute_values("xhist_plan_execute_sum", sample_views, (value_view,), n_rows, n_cols, (out_count_ptr, out_total_ptr),
+                             stream=stream)
 
     def execute_map(self, sample_views, value_view, n_rows, n_cols, op, centre_ptr, scale_ptr, out_ptr, stream=0):
         """one 8-byte element per sample of device-resident views into the dense row-major [n_rows, n_cols] device block at

@@ -35,7 +35,7 @@ _range = range
 
 __all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
            "histogram_weighted_quantile", "histogram_cov", "histogram_weighted_cov", "combine_weighted_cov",
-           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema"]
+           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema", "histogram_sum"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1862,7 +1862,8 @@ def _value_views(args, values, axis, bins, backend, *extras, ordered=False):
 #   tail     the names of the per-call parameters the method takes after the pointers
 #   ordered  whether it reports positions inside the row (_value_views, ordered)
 #   noun     what the refusal of several chunks calls the partials that cannot be merged
-_ValueStat = namedtuple("_ValueStat", "k ints method ptrs extras reduce tail ordered noun", defaults=((), False, None))
+#   max_cols the reduced extent per output row it refuses (NotImplementedError, before any device work); None: no limit
+_ValueStat = namedtuple("_ValueStat", "k ints method ptrs extras reduce tail ordered noun max_cols", defaults=((), False, None, None))
 
 
 def _value_rows(st, args, values, axis, bins, backend, *extras, **params):
@@ -1925,6 +1926,12 @@ def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, *ex
     n_inputs = len(args)
     st = _VALUE_STATS[stat]
     k = st.k or len(params["q"])
+    if st.max_cols is not None:
+        shape = all_arrays[0].shape
+        cols = int(np.prod([int(shape[ax]) for ax in drop_axes], dtype=object)) if drop_axes else 1
+        if cols >= st.max_cols:
+            raise NotImplementedError("%s takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
+                                      % (name, st.max_cols, cols))
     merged = backend == "dask" and st.reduce is not None
     if backend == "dask":
         if not merged and any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
@@ -1994,6 +2001,50 @@ def histogram_argextrema(*args, values, bins=None, range=None, axis=None, block_
     # columns are the reduced axes in ascending axis number (the entry is `ordered`)
     _, (vmin, vmax, amin, amax), bins, _ = _value_stat("argextrema", args, values, bins, range, axis, "histogram_argextrema")
     return amin, amax, vmin, vmax, bins
+
+
+def histogram_sum(*args, values, bins=None, range=None, axis=None, weights=None, block_size="auto"):
+    """Per-bin count and sum of ``values``, computed on an MI355X with integer arithmetic: ``scipy.stats.binned_statistic``'s
+    ``"sum"`` (NaN-ignoring), the same bits for any order of the samples, any chunking into rows, any launch geometry and any
+    run.  Volumes, heat content or tracer mass per class can then be compared bit for bit across restarts.
+
+    ``args``, ``bins``, ``range``, ``axis``, ``values`` (any real dtype, taken as float64), the samples that count, the NaN-value
+    rule (a counted sample contributes when its value is not NaN), the broadcasting and the backends are those of
+    :func:`histogram_mean_var`; ``count`` is its int64 count.  ``block_size`` is accepted and changes nothing.
+
+    ``total`` is defined per (row, bin), on integers only:
+
+    1. ``A`` is the largest ``|v|`` of the bin (``max(|vmin|, |vmax|)`` of :func:`histogram_extrema`, which is the first of the
+       two passes).  An empty bin, or ``A == 0``, gives ``+0.0``.
+    2. ``E`` is ``frexp(A)``'s exponent (``|v| < 2**E``), ``U = max(E - 96, -1074)``; the unit is ``2**U``.
+    3. A value ``v = s * m * 2**e`` (``m`` the 53-bit integer significand, ``e = -1074`` for subnormals) becomes
+       ``q = m << (e - U)``, or ``m >> (U - e)`` truncated towards zero where ``e < U`` (0 once the shift reaches 64).
+       ``q < 2**96`` is split into three unsigned 32-bit limbs, and ``s * limb_j`` is added into three int64 accumulators.
+    4. A row has fewer than 2^31 samples, so ``S = L0 + L1 * 2**32 + L2 * 2**64`` fits a signed 128-bit integer.
+    5. ``total = RN_even(S * 2**U)``: one rounding, in integer arithmetic, overflowing to ``+-inf`` as IEEE does; a zero
+       result is ``+0.0``.
+    6. A bin that holds an infinity gives that infinity, or NaN where it holds both; its finite values are skipped.
+
+    Values whose lowest set bit lies at or above ``2**U`` are converted exactly: every value within a factor ``2**43`` of its
+    bin's largest magnitude, and every value where ``E - 96 <= -1074`` (subnormals are exact).  A bin of such values gets the
+    correctly rounded exact sum, ``math.fsum`` bit for bit.  In general ``|total - exact| <= ulp(total) / 2 + n * 2**(E - 96)``,
+    the second term below ``2**-12`` ulp of the bin's largest magnitude.  No intermediate overflows:
+    ``[1.5e308, 1.5e308, -1.5e308]`` gives ``1.5e308``.  ``histogram_sum(x, values=w)[1]`` is a reproducible weighted histogram
+    that ignores NaN weights instead of letting them poison the bin.
+
+    ``weights`` is refused (``TypeError``): the product of two float64 numbers is not a float64 number, so multiply them into
+    ``values``.  A reduced extent of 2^31 samples or more per output row is a ``NotImplementedError``.  Both, and complex
+    values, are refused before any device work.
+
+    Returns ``(count, total, bin_edges)``: count int64, total float64, with the shape ``histogram`` gives (kept axes, then bin
+    axes).  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the current stream), DeviceArray
+    in -> numpy out, dask in -> lazy dask arrays, one task per block: every reduced axis must then be a single chunk (the
+    integer accumulators of several chunks are not merged)."""
+    if weights is not None:
+        raise TypeError("histogram_sum does not take weights: multiply them into values (the product of two float64 numbers is "
+                        "not a float64 number, so the weighted sum is another statistic)")
+    _, (count, total), bins, _ = _value_stat("sum", args, values, bins, range, axis, "histogram_sum")
+    return count, total, bins
 
 
 def _values_call(args, values, bins, range, axis, name, *extras, needs_values=True):
@@ -2453,6 +2504,8 @@ _skew_kurt_w_reduce = partial(_moment_reduce, present=_weighed, pairs=None)
 
 _VALUE_STATS = {
     "extrema": _ValueStat(2, (), "execute_extrema", (0, 1), 0, _extrema_pair_reduce),
+    # (count, total): integer accumulators of several chunks are not kept, so there is no merge
+    "sum": _ValueStat(2, (0,), "execute_sum", (0, 1), 0, None, noun="reproducible sums", max_cols=1 << 31),
     # (vmin, vmax, argmin, argmax): the library takes the block of values and the block of positions
     "argextrema": _ValueStat(4, (2, 3), "execute_argextrema", (0, 2), 0, None, ordered=True, noun="positions"),
     "mean_var": _ValueStat(3, (0,), "execute_mean_var", (0, 1, 2), 0, _mean_var_reduce),

@@ -325,6 +325,12 @@ extern "C" int xhist_plan_execute_argextrema(xhist_plan* p, const xhist_array* s
                         [&](const ValuesCall& k) { return xhist_argextrema_run(k, out_values, out_index); });
 }
 
+extern "C" int xhist_plan_execute_sum(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                                      int64_t n_cols, int64_t* out_count, double* out_total, int mem_kind, void* stream) {
+  return execute_values(p, "xhist_plan_execute_sum", samples, values, nullptr, nullptr, n_rows, n_cols, out_total, out_count != nullptr,
+                        "out_count is NULL", mem_kind, stream, [&](const ValuesCall& k) { return xhist_sum_run(k, out_count, out_total); });
+}
+
 extern "C" int xhist_plan_execute_mean_var(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
                                            int64_t n_cols, int64_t* out_count, double* out_mean, double* out_m2, int mem_kind, void* stream) {
   return execute_values(p, "xhist_plan_execute_mean_var", samples, values, nullptr, nullptr, n_rows, n_cols, out_mean, out_count && out_m2,

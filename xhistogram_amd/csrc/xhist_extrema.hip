@@ -98,6 +98,34 @@ int xhist_extrema_run(const ValuesCall& k, double* out_min, double* out_max, int
   return XHIST_OK;
 }
 
+// Pass 1 of a statistic of another unit that starts from a bin's extremes (histogram_sum, xhist_sum.hip): extrema_prepare and
+// the binning kernel of the choice `c` that the statistic's larger pass made.  The residency, hence the segments per row
+// (*segs), is this pass's own: its slots as histogram_extrema keeps them, one copy (*lds_bytes).
+int xhist_extrema_pass1(const ValuesCall& k, const ValuesChoice& c, uint64_t* kmin, uint64_t* kmax, int64_t* segs, size_t* lds_bytes) {
+  const ValuesPlan& pl = k.pl;
+  const int64_t n_out = k.n_rows * pl.n_bins;
+  const int grid_io = (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n_out + 255) / 256));
+  XH_VALUES_LAUNCH(extrema_prepare, dim3(grid_io), dim3(256), 0, k.stream, kmin, kmax, n_out, 0);
+  XH_VALUES_LAUNCH_CHECK(k, "extrema_prepare launch");
+  *segs = 0;
+  *lds_bytes = 0;
+  if (k.n_cols <= 0) return XHIST_OK;
+  ValuesChoice c1 = c;
+  if (c.lds_bytes[0]) {
+    const size_t own = (size_t)pl.n_bins * (c.fast && c.f32 ? kExtremaSlots.fast32[0] : kExtremaSlots.bytes[0]);
+    if (c.lds) c1.lds_bytes[0] = c.lds_bytes[0] - (own << c.copies_log2) + own;  // (the tables, and one copy of the slots)
+  }
+  c1.lds_bytes[1] = 0;
+  c1.copies_log2 = 0;
+  const values_fn fn = pick_values_kernel<ExtremaKernels>(c1, pl);
+  if (!fn) return k.fail(XHIST_ERR_HIP, "internal: no extrema kernel for this combination");
+  if (int rc = allow_values_lds(k, fn, c1.lds_bytes[0], "extrema: setting the dynamic LDS size failed")) return rc;
+  const ValuesGeometry g1 = values_geometry(pl, c1, k.n_rows, k.n_cols);
+  *segs = g1.segs;
+  *lds_bytes = c1.lds_bytes[0];
+  return launch_values_pass(fn, c1.lds_bytes[0], "extrema launch", k, c1, g1, kmin, kmax, nullptr);
+}
+
 // pass 2 of histogram_argextrema
 struct ArgextKernels {
   template <typename ST, int D, int SCAN>

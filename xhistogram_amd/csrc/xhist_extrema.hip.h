@@ -269,3 +269,8 @@ __global__ void __launch_bounds__(256) argext_fast(const CovParams p) {
 }
 
 }  // namespace xhist
+
+// xhist_extrema.hip, for the units whose statistic starts from a bin's extremes (xhist_sum.hip): pass 1 as histogram_argextrema
+// runs it, the keys left in kmin / kmax [n_rows, n_bins]; *segs and *lds_bytes: its segments per row and its LDS bytes (0: no columns, no binning launch)
+int xhist_extrema_pass1(const ValuesCall& k, const xhist::ValuesChoice& c, uint64_t* kmin, uint64_t* kmax, int64_t* segs,
+                        size_t* lds_bytes);

@@ -78,6 +78,11 @@ struct ValuesCall {
 int xhist_extrema_run(const ValuesCall& k, double* out_min, double* out_max, int accumulate);
 int xhist_argextrema_run(const ValuesCall& k, double* out_values, int64_t* out_index);
 
+// xhist_sum.hip: histogram_sum, the per-bin sum that does not depend on the order of arrival (pass 1 is histogram_extrema's,
+// pass 2 adds integer limbs, a finalize rounds once): out_count int64, out_total float64; five planes of scratch from k.alloc.
+// XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31, before any launch.
+int xhist_sum_run(const ValuesCall& k, int64_t* out_count, double* out_total);
+
 // The two-pass statistics (two_pass_run<M> of xhist_values.hip.h, which takes its block for the sums of deviations from
 // k.alloc): out_first is the int64 count, or the float64 sum of weights of a weighted form (k.third, k.fourth for cov).
 //   xhist_meanvar.hip, xhist_meanvar_w.hip   out_mean [1], out_m2 [1]; skew_kurt: out_m2 [3] (M2, M3, M4)

@@ -15,7 +15,7 @@ from .core import histogram_two_weights as _core_histogram_two_weights
 
 __all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
            "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt", "histogram_argextrema", "bin_index", "histogram_lookup",
-           "histogram_anomaly"]
+           "histogram_anomaly", "histogram_sum"]
 
 
 def _xr():
@@ -198,6 +198,23 @@ def histogram_mean_var(*args, values, bins=None, range=None, dim=None, ddof=0, b
     first = "count" if weights is None else "sum_of_weights"
     return tuple(xr.DataArray(a, dims=out_dims, coords=coords, name="%s_%s" % (base, suffix))
                  for a, suffix in ((cnt, first), (mean, "mean"), (var, "var")))
+
+
+def histogram_sum(*args, values, bins=None, range=None, dim=None, block_size="auto", keep_coords=False, bin_dim_suffix="_bin"):
+    """Per-bin count and order-independent sum of the DataArray ``values`` over the bins of ``args``
+    (:func:`xhistogram_amd.core.histogram_sum` with the labels of :func:`histogram`).
+
+    ``args``, ``bins``, ``range``, ``dim``, ``keep_coords``, ``bin_dim_suffix`` and ``values`` are those of
+    :func:`histogram_mean_var`; there are no ``weights`` (multiply them into ``values``).  Returns ``(count, total)``: two
+    DataArrays with the dims and coords ``histogram`` gives for the same ``args``, ``bins`` and ``dim``, named
+    ``<values name>_count`` / ``<values name>_sum`` (``values`` when the DataArray has no name)."""
+    from .core import histogram_sum as _core_histogram_sum
+
+    (cnt, total), out_dims, coords, base = _values_statistic(
+        "histogram_sum", _core_histogram_sum, args, values, bins, range, dim, keep_coords, bin_dim_suffix, block_size=block_size)
+    xr = _xr()
+    return (xr.DataArray(cnt, dims=out_dims, coords=coords, name="%s_count" % base),
+            xr.DataArray(total, dims=out_dims, coords=coords, name="%s_sum" % base))
 
 
 def histogram_skew_kurt(*args, values, bins=None, range=None, dim=None, weights=None, ddof=0, bias=True, fisher=True,
