@@ -349,6 +349,30 @@ int xhist_plan_execute_map(xhist_plan* plan, const xhist_array* samples, const x
                            int64_t n_cols, int op, const double* centre, const double* scale, void* out, int mem_kind,
                            void* stream);
 
+/* bin_order (added within ABI v11: a new entry, every earlier one unchanged): the stable group-by of every row's samples by
+ * bin, a counting sort of the keys xhist_plan_execute_map gives with XHIST_MAP_INDEX (the same samples count, in the same
+ * bins; a sample that is not counted has key -1, which sorts behind every bin).  With B = prod(nb_d), per row r:
+ *   out_order[r, :]    int64, a permutation of 0 .. n_cols - 1: the columns sorted by key, columns of equal keys ascending
+ *                      (np.argsort(key, kind="stable") with -1 replaced by B).
+ *   out_offsets[r, b]  int64, b = 0 .. B: the number of columns whose key is below b.  The columns of bin b are
+ *                      out_order[r, out_offsets[r, b] : out_offsets[r, b + 1]], the columns that are not counted
+ *                      out_order[r, out_offsets[r, B] :], and the differences of a row are xhist_plan_execute's counts.
+ *   out_order, out_offsets: contiguous DEVICE blocks [n_rows, n_cols] and [n_rows, B + 1]; every element of both is written
+ *   exactly once and nothing outside them.  n_cols == 0 gives offsets of 0.  A plan without bins (an edge array of a single
+ *   edge) gives out_offsets [n_rows, 1] of 0 and out_order[r, c] = c.
+ *   n_cols must be below 2^31 and (B + 1) * 4 bytes must fit the LDS of a workgroup (B <= 40959 on an MI355X):
+ *   XHIST_ERR_UNSUPPORTED otherwise, before any launch.
+ *   Scratch of the call: n_rows * n_cols * 8 bytes of keys and a counter table of at most a quarter of that wherever a row is
+ *   cut into several chunks, with 1/64 of the table again for the totals of 64 chunks (n_rows * (B + 1) * 4 bytes where a row
+ *   is one chunk).
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Exact and deterministic: no result depends on the order in which waves arrive.  Asynchronous on `stream`.
+ *   xhist_plan_describe then reads "group keys=fast|generic bits=.. waves=.. block=.. chunks=.. chunk=.. lds_bytes=..
+ *   rows_per_launch=.. D=.. cmp=..": the kernel family that made the keys, the ballots of a step, the waves of a workgroup,
+ *   and how a row was cut. */
+int xhist_plan_execute_group(xhist_plan* plan, const xhist_array* samples, int64_t n_rows, int64_t n_cols,
+                             int64_t* out_order, int64_t* out_offsets, int mem_kind, void* stream);
+
 /* One-shot form of the two calls above with an internal plan cache keyed on (device, edges). */
 int xhist_bincount_rows(int device, int n_inputs, const xhist_array* samples,
                         const xhist_array* weights, int64_t n_rows, int64_t n_cols,

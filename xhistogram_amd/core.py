@@ -35,7 +35,7 @@ _range = range
 
 __all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
            "histogram_weighted_quantile", "histogram_cov", "histogram_weighted_cov", "combine_weighted_cov",
-           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema", "histogram_sum"]
+           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema", "histogram_sum", "bin_order"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2848,3 +2848,107 @@ def histogram_anomaly(*args, values, bins=None, range=None, axis=None, weights=N
     out = _map_out(plan, nv[:n + 1], True, m, c, _native.MAP_ANOMALY, base + nt * 8, scale_ptr, arrays[0], axis, on, device, stream)
     del views, stats, scale
     return out, bins
+
+
+# ---------------------------------------------------------------------------------------------
+# bin_order: the samples grouped by bin
+# ---------------------------------------------------------------------------------------------
+_ORDER_MAX_COLS = 1 << 31
+
+
+def _order_rows(arrays, axis, bins, on):
+    """xhist_plan_execute_group over the `ordered` views of broadcast torch tensors or DeviceArrays: (order [kept axes, c],
+    offsets [kept axes, B + 1]), int64, torch tensors on the samples' device (asynchronous on the current stream) or numpy
+    arrays.  The kernels are handed these blocks themselves."""
+    plan, nv, views, m, c, _, device, stream = _value_views(arrays, None, axis, bins, on, ordered=True)
+    shape = tuple(int(s) for s in arrays[0].shape)
+    ndim = len(shape)
+    red = list(_range(ndim)) if axis is None or set(axis) == set(_range(ndim)) else sorted(axis)
+    kept = tuple(shape[i] for i in _range(ndim) if i not in red)
+    nb1 = plan.n_bins + 1
+    if on == "torch":
+        torch = _torch()
+        order = torch.empty((m, c), dtype=torch.int64, device=arrays[0].device)
+        offsets = torch.empty((m, nb1), dtype=torch.int64, device=arrays[0].device)
+        if m > 0:
+            plan.execute_group(nv, m, c, order.data_ptr(), offsets.data_ptr(), stream=stream)
+    else:
+        order, offsets = np.empty((m, c), np.int64), np.empty((m, nb1), np.int64)
+        if m > 0:
+            buf = _native.DeviceBuffer(device, (m * c + m * nb1) * 8)
+            plan.execute_group(nv, m, c, buf.ptr, buf.ptr + m * c * 8, stream=stream)
+            both = np.empty(m * c + m * nb1, np.int64)
+            buf.download(both)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+            order[...] = both[:m * c].reshape(m, c)
+            offsets[...] = both[m * c:].reshape(m, nb1)
+    del views
+    return order.reshape(kept + (c,)), offsets.reshape(kept + (nb1,))
+
+
+def _bin_order_block(*blocks, axis=None, bins=None):
+    """one dask block: a row's order and its offsets side by side, int64 [kept axes (reduced ones of extent 1), c + B + 1]"""
+    order, offsets, _ = bin_order(*blocks, bins=bins, axis=axis)
+    packed = np.concatenate([order, offsets], axis=-1)
+    shape = [1 if i in axis else int(s) for i, s in enumerate(blocks[0].shape)]
+    return packed.reshape(shape + [packed.shape[-1]])
+
+
+def bin_order(*args, bins=None, range=None, axis=None):
+    """The samples grouped by bin, computed on an MI355X: a stable counting sort of the positions by :func:`bin_index`, the CSR
+    form (``order`` and ``offsets``) that makes any per-bin function one line of numpy or torch —
+    ``np.split(v[order], offsets[1:-1])``, ``np.maximum.reduceat``, ``torch.segment_reduce`` — what
+    ``scipy.stats.binned_statistic(statistic=<callable>)`` does on the host.
+
+    ``args``, ``bins``, ``range`` and ``axis`` are those of :func:`histogram`; the samples that count, the digitize, the compare
+    domains, the joint bins of up to 8 inputs and the estimator names are those of :func:`bin_index`.  With ``B`` the number of
+    bins, ``c`` the product of the reduced extents and ``kept`` the kept axes' shape, ``order`` is int64 ``kept + (c,)`` and
+    ``offsets`` int64 ``kept + (B + 1,)``.  A position is what :func:`histogram_argextrema` calls one: the C-order flat index
+    over the reduced axes in ascending axis number, whatever order ``axis`` lists them in (``axis=None``: the flat index into the
+    broadcast array).  Per kept index, with ``key[p]`` the bin index at position ``p`` and ``-1`` replaced by ``B``:
+
+    * ``order = np.argsort(key, kind="stable")``, a permutation of ``0 .. c - 1``;
+    * ``offsets[b] = #{p : key[p] < b}`` for ``b = 0 .. B``;
+    * the positions of bin ``b`` are ``order[offsets[b]:offsets[b + 1]]``, ascending, and the samples ``histogram`` drops are
+      ``order[offsets[B]:]``, ascending;
+    * ``np.diff(offsets)`` reshaped to the bins' shape is ``histogram(...)[0]``.
+
+    A plan without bins (one edge) gives ``offsets == [0]`` and ``order == arange(c)``; ``c == 0`` an empty ``order`` and
+    offsets of 0.  Exact and deterministic: nothing depends on the order in which waves arrive.  A reduced extent of 2^31
+    samples or more per row, and more than 40 959 bins (one 4-byte counter per bin and one more in the 160 KiB of LDS of a
+    workgroup), raise ``NotImplementedError``.
+
+    Returns ``(order, offsets, bin_edges)``.  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on
+    the current stream), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block over the kept axes: every
+    reduced axis must then be a single chunk, and ``bins`` numpy arrays of edges."""
+    if not args:
+        raise TypeError("bin_order needs at least one array of samples")
+    for a in args:
+        dt = a.dtype if hasattr(a, "dtype") else np.asarray(a).dtype
+        if getattr(dt, "is_complex", False) or getattr(dt, "kind", "") == "c":
+            raise TypeError("complex samples have no order: bin_order takes real samples")
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, None, bins, range, axis, "bin_order", needs_values=False)
+    shape = tuple(int(s) for s in all_arrays[0].shape)
+    cols = int(np.prod([shape[ax] for ax in drop_axes], dtype=object)) if drop_axes else 1
+    if cols >= _ORDER_MAX_COLS:
+        raise NotImplementedError("bin_order takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
+                                  % (_ORDER_MAX_COLS, cols))
+    if backend == "dask":
+        if any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
+            raise ValueError("group orders of several chunks cannot be merged: rechunk the reduced axes of every input into "
+                             "one chunk (e.g. arr.rechunk({axis: -1}))")
+        import dask.array as dsa
+
+        ndim = len(shape)
+        n_bins = int(np.prod([len(b) - 1 for b in bins], dtype=object))
+        ind = tuple(_range(ndim))
+        packed = dsa.blockwise(_bin_order_block, ind + (ndim,), *[x for a in all_arrays for x in (a, ind)], dtype=np.int64,
+                               new_axes={ndim: cols + n_bins + 1}, adjust_chunks={ax: (lambda extent: 1) for ax in drop_axes},
+                               axis=list(drop_axes), bins=bins, meta=np.array((), np.int64))
+        packed = packed[tuple(0 if i in drop_axes else slice(None) for i in _range(ndim)) + (slice(None),)]
+        return packed[..., :cols], packed[..., cols:], bins
+    if backend == "numpy":
+        arrays, on = _upload_host(raw, None, bins), "device"
+    else:
+        arrays, on = all_arrays, backend
+    order, offsets = _order_rows(arrays, axis, bins, on)
+    return order, offsets, bins

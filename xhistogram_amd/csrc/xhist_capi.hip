@@ -430,6 +430,28 @@ extern "C" int xhist_plan_execute_map(xhist_plan* p, const xhist_array* samples,
   return XHIST_OK;
 }
 
+// bin_order (xhist_group.hip): the same front without values.  A plan without bins drops every sample: one offset of 0 per row,
+// and every row's order is its positions (the statistics' front has no output row to launch over, as for the maps).
+extern "C" int xhist_plan_execute_group(xhist_plan* p, const xhist_array* samples, int64_t n_rows, int64_t n_cols, int64_t* out_order,
+                                        int64_t* out_offsets, int mem_kind, void* stream) {
+  if (p && n_cols >= ((int64_t)1 << 31))
+    return fail(XHIST_ERR_UNSUPPORTED, "bin_order takes fewer than 2^31 samples per output row (a row's offsets are held in 32 bits), got %lld",
+                (long long)n_cols);
+  const bool work = p && n_rows > 0 && n_cols > 0;
+  if (work && !out_order) return fail(XHIST_ERR_INVALID, "out_order is NULL");
+  static int64_t no_columns;  // (what validate_arrays sees of a call without columns: the block has no element)
+  const int rc = execute_values(p, "xhist_plan_execute_group", samples, nullptr, nullptr, nullptr, n_rows, n_cols,
+                                reinterpret_cast<double*>(out_order ? out_order : &no_columns), out_offsets != nullptr, "out_offsets is NULL",
+                                mem_kind, stream, [&](const ValuesCall& k) { return xhist_group_run(k, out_order, out_offsets); }, false);
+  if (rc != XHIST_OK || p->n_bins > 0 || n_rows <= 0) return rc;
+  if (!out_offsets) return fail(XHIST_ERR_INVALID, "out_offsets is NULL");
+  DeviceGuard g;
+  if (int grc = g.set(p->device)) return grc;
+  if (int grc = xhist_group_no_bins(n_rows, n_cols, out_order, out_offsets, static_cast<hipStream_t>(stream)))
+    return fail(grc, "xhist_plan_execute_group: the launch over a plan without bins failed");
+  return XHIST_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // one-shot form with a plan cache
 // ------------------------------------------------------------------------------------------

@@ -104,3 +104,11 @@ int xhist_quantile_w_run(const ValuesCall& k, const double* q, int n_q, double* 
 // centre the table) or XHIST_MAP_ANOMALY (k.values the values, centre the means, scale nullptr or the standard deviations);
 // centre and scale are float64 [n_rows, n_bins], out a dense [n_rows, n_cols] block of 8-byte elements, each written once.
 int xhist_map_run(const ValuesCall& k, int op, const double* centre, const double* scale, void* out);
+
+// xhist_group.hip: bin_order, the stable group-by of a row's samples by bin (k.values nullptr).  out_order is a dense int64
+// [n_rows, n_cols] block, out_offsets int64 [n_rows, n_bins + 1]; every element of both is written exactly once.  The keys are
+// xhist_map_run's XHIST_MAP_INDEX block, in scratch from k.alloc with the counter table.  XHIST_ERR_UNSUPPORTED for k.n_cols >=
+// 2^31 and for (n_bins + 1) * 4 bytes beyond the LDS of a workgroup, before any launch.  xhist_group_no_bins: a plan without
+// bins, which the statistics' front does not launch over (offsets [n_rows, 1] of zeros, every row's order its positions).
+int xhist_group_run(const ValuesCall& k, int64_t* out_order, int64_t* out_offsets);
+int xhist_group_no_bins(int64_t n_rows, int64_t n_cols, int64_t* out_order, int64_t* out_offsets, hipStream_t stream);

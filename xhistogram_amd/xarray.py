@@ -15,7 +15,7 @@ from .core import histogram_two_weights as _core_histogram_two_weights
 
 __all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
            "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt", "histogram_argextrema", "bin_index", "histogram_lookup",
-           "histogram_anomaly", "histogram_sum"]
+           "histogram_anomaly", "histogram_sum", "bin_order"]
 
 
 def _xr():
@@ -471,3 +471,22 @@ def histogram_anomaly(*args, values, bins=None, range=None, dim=None, weights=No
                                      weights=arrays[n + 1] if weights is not None else None, ddof=ddof, standardize=standardize)
     return _xr().DataArray(out, dims=dims_order, coords=_sample_coords(first, dims_order),
                            name="%s_anomaly" % (values.name or "values"))
+
+
+def bin_order(*args, bins=None, range=None, dim=None):
+    """The samples grouped by bin (:func:`xhistogram_amd.core.bin_order`): two int64 DataArrays on the kept dims (those not in
+    ``dim``; none for ``dim=None``), ``<first arg>_bin_order`` with a new last dim ``<first arg>_order`` (the positions over the
+    dims of ``dim`` in the inputs' broadcast dim order, sorted stably by bin, dropped samples last) and ``<first arg>_bin_offsets``
+    with a new last dim ``<first arg>_bin_offset`` (where each bin's run starts; the last entry: where the dropped samples
+    start)."""
+    from .core import bin_order as _core_bin_order
+
+    arrays, dims_order, first = _lined_up("bin_order", args, [])
+    kept = [d for d in dims_order if dim is not None and d not in dim]
+    axis = None if dim is None else [dims_order.index(d) for d in dim]
+    order, offsets, _ = _core_bin_order(*arrays, bins=bins, range=range, axis=axis)
+    name = args[0].name
+    coords = _sample_coords(first, kept)
+    xr = _xr()
+    return (xr.DataArray(order, dims=kept + ["%s_order" % name], coords=coords, name="%s_bin_order" % name),
+            xr.DataArray(offsets, dims=kept + ["%s_bin_offset" % name], coords=coords, name="%s_bin_offsets" % name))
