@@ -373,6 +373,34 @@ int xhist_plan_execute_map(xhist_plan* plan, const xhist_array* samples, const x
 int xhist_plan_execute_group(xhist_plan* plan, const xhist_array* samples, int64_t n_rows, int64_t n_cols,
                              int64_t* out_order, int64_t* out_offsets, int mem_kind, void* stream);
 
+/* bin_sort (added within ABI v11: a new entry, every earlier one unchanged): every row's samples grouped by bin as
+ * xhist_plan_execute_group groups them and, inside each bin, sorted by value.  With key[c] the bin key of column c (-1 replaced
+ * by B) and vk[c] the order-preserving uint64 key of values[c] taken as float64 (unsigned order is the total order of the values
+ * with -0.0 < +0.0; its bits are complemented when `descending` is nonzero; 2^64 - 1 for a NaN in either direction, so NaN is
+ * last in its bin either way), per row r:
+ *   out_order[r, :]    int64, a permutation of 0 .. n_cols - 1: np.lexsort((vk, key)), by bin, then by value, ties in
+ *                      ascending column.  The columns that are not counted, out_order[r, out_offsets[r, B] :], are sorted by
+ *                      value too.
+ *   out_offsets[r, b]  int64, b = 0 .. B: the number of columns whose key is below b, as xhist_plan_execute_group's.
+ *   out_order, out_offsets: contiguous DEVICE blocks [n_rows, n_cols] and [n_rows, B + 1]; every element of both is written
+ *   exactly once and nothing outside them.  n_cols == 0 gives offsets of 0.  A plan without bins gives out_offsets
+ *   [n_rows, 1] of 0 and every row sorted by value.
+ *   values: any real dtype, any strides.  n_cols must be below 2^31 and B + 1 at most 2^32: XHIST_ERR_UNSUPPORTED otherwise,
+ *   before any launch.  There is no bound from the LDS: a stable least-significant-digit radix sort on 8-bit digits, first of
+ *   the value keys (digits the dtype of the values makes constant are not launched: 8 passes for float64 and 64-bit integers,
+ *   5 for float32, 3 for float16, 6 / 4 / 3 / 2 for integers of 32 / 16 / 8 bits and bool), then of the gathered bin keys in
+ *   ceil(log2(B + 1) / 8) passes, every pass with 256 counters per wave.
+ *   Scratch of the call: 32 bytes per sample (8 of bin keys, two blocks of 8-byte keys, two of 4-byte positions; 24 for a plan
+ *   without bins) and at most 256 MiB of counters, 1 KiB per (row, chunk) of a launch.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Exact and deterministic: the place of a record is a function of the keys alone.  Asynchronous on `stream`.
+ *   xhist_plan_describe then reads "sort keys=fast|generic|none value_passes=.. bin_passes=.. waves=.. block=.. chunks=..
+ *   chunk=.. slices=.. rows_per_launch=.. D=.. cmp=.. vdtype=..": the kernel family that made the bin keys (none: a plan
+ *   without bins or a call without columns), the passes of each phase, and how a row was cut. */
+int xhist_plan_execute_sort(xhist_plan* plan, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                            int64_t n_cols, int descending, int64_t* out_order, int64_t* out_offsets, int mem_kind,
+                            void* stream);
+
 /* One-shot form of the two calls above with an internal plan cache keyed on (device, edges). */
 int xhist_bincount_rows(int device, int n_inputs, const xhist_array* samples,
                         const xhist_array* weights, int64_t n_rows, int64_t n_cols,

@@ -73,7 +73,7 @@ EXPORTS = (
     "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
     "xhist_plan_execute_quantile_weighted", "xhist_plan_execute_cov", "xhist_plan_execute_cov_weighted",
     "xhist_plan_execute_skew_kurt", "xhist_plan_execute_skew_kurt_weighted", "xhist_plan_execute_argextrema",
-    "xhist_plan_execute_map", "xhist_plan_execute_group", "xhist_plan_execute_sum", "xhist_debug_sum_host", "xhist_debug_sum_round",
+    "xhist_plan_execute_map", "xhist_plan_execute_group", "xhist_plan_execute_sort", "xhist_plan_execute_sum", "xhist_debug_sum_host", "xhist_debug_sum_round",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -178,6 +178,10 @@ def load():
         ]
         lib.xhist_plan_execute_group.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+        ]
+        lib.xhist_plan_execute_sort.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+            C.c_void_p,
         ]
         lib.xhist_bincount_rows.argtypes = [
             C.c_int, C.c_int, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_void_p),
@@ -434,6 +438,18 @@ class Plan:
         (xhist_plan_execute_group): int64 [n_rows, n_cols], per row the columns sorted by bin_index's key (-1 last, equal keys in
         ascending column), and int64 [n_rows, bins + 1], the number of columns whose key is below b; fewer than 2^31 columns"""
         self._execute_values("xhist_plan_execute_group", sample_views, (), n_rows, n_cols, (out_order_ptr, out_offsets_ptr), stream=stream)
+
+    def execute_sort(self, sample_views, value_view, n_rows, n_cols, descending, out_order_ptr, out_offsets_ptr, stream=0):
+        """every row's columns grouped by bin and sorted by value inside each bin, of device-resident views, asynchronous on
+        `stream` (xhist_plan_execute_sort): int64 [n_rows, n_cols], per row the columns sorted by bin_index's key (-1 last), then
+        by the value's order-preserving key (`descending`: largest first; NaN last either way), ties in ascending column, and
+        int64 [n_rows, bins + 1], the number of columns whose key is below b; fewer than 2^31 columns"""
+        check(
+            load().xhist_plan_execute_sort(
+                self._h, self._sample_array(sample_views), C.byref(value_view), int(n_rows), int(n_cols), 1 if descending else 0,
+                C.c_void_p(out_order_ptr), C.c_void_p(out_offsets_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
+            )
+        )
 
     def execute_mean_var(self, sample_views, value_view, n_rows, n_cols, out_count_ptr, out_mean_ptr, out_m2_ptr, stream=0):
         """per-bin count (int64), mean and sum of squared deviations M2 (float64; NaN where no value arrived) of the values of

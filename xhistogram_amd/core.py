@@ -35,7 +35,7 @@ _range = range
 
 __all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
            "histogram_weighted_quantile", "histogram_cov", "histogram_weighted_cov", "combine_weighted_cov",
-           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema", "histogram_sum", "bin_order"]
+           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema", "histogram_sum", "bin_order", "bin_sort"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2951,4 +2951,121 @@ def bin_order(*args, bins=None, range=None, axis=None):
     else:
         arrays, on = all_arrays, backend
     order, offsets = _order_rows(arrays, axis, bins, on)
+    return order, offsets, bins
+
+
+# ---------------------------------------------------------------------------------------------
+# bin_sort: the samples grouped by bin, sorted by value inside each bin
+# ---------------------------------------------------------------------------------------------
+_SORT_MAX_BINS = (1 << 32) - 1
+
+
+def _sort_rows(arrays, values, axis, bins, on, descending):
+    """xhist_plan_execute_sort over the `ordered` views of broadcast torch tensors or DeviceArrays and their values: (order
+    [kept axes, c], offsets [kept axes, B + 1]), int64, torch tensors on the samples' device (asynchronous on the current
+    stream) or numpy arrays.  The kernels are handed these blocks themselves."""
+    plan, nv, views, m, c, _, device, stream = _value_views(arrays, values, axis, bins, on, ordered=True)
+    n = len(arrays)
+    shape = tuple(int(s) for s in arrays[0].shape)
+    ndim = len(shape)
+    red = list(_range(ndim)) if axis is None or set(axis) == set(_range(ndim)) else sorted(axis)
+    kept = tuple(shape[i] for i in _range(ndim) if i not in red)
+    nb1 = plan.n_bins + 1
+    if on == "torch":
+        torch = _torch()
+        order = torch.empty((m, c), dtype=torch.int64, device=arrays[0].device)
+        offsets = torch.empty((m, nb1), dtype=torch.int64, device=arrays[0].device)
+        if m > 0:
+            plan.execute_sort(nv[:n], nv[n], m, c, descending, order.data_ptr(), offsets.data_ptr(), stream=stream)
+    else:
+        order, offsets = np.empty((m, c), np.int64), np.empty((m, nb1), np.int64)
+        if m > 0:
+            buf = _native.DeviceBuffer(device, (m * c + m * nb1) * 8)
+            plan.execute_sort(nv[:n], nv[n], m, c, descending, buf.ptr, buf.ptr + m * c * 8, stream=stream)
+            both = np.empty(m * c + m * nb1, np.int64)
+            buf.download(both)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+            order[...] = both[:m * c].reshape(m, c)
+            offsets[...] = both[m * c:].reshape(m, nb1)
+    del views
+    return order.reshape(kept + (c,)), offsets.reshape(kept + (nb1,))
+
+
+def _bin_sort_block(*blocks, axis=None, bins=None, descending=False):
+    """one dask block (samples..., values): a row's order and its offsets side by side, int64 [kept axes (reduced ones of extent
+    1), c + B + 1]"""
+    order, offsets, _ = bin_sort(*blocks[:-1], values=blocks[-1], bins=bins, axis=axis, descending=descending)
+    packed = np.concatenate([order, offsets], axis=-1)
+    shape = [1 if i in axis else int(s) for i, s in enumerate(blocks[0].shape)]
+    return packed.reshape(shape + [packed.shape[-1]])
+
+
+def bin_sort(*args, values, bins=None, range=None, axis=None, descending=False):
+    """The samples grouped by bin and, inside each bin, sorted by value, computed on an MI355X: :func:`bin_order`'s CSR form
+    (``order`` and ``offsets``) with value order inside every segment — the k warmest samples of a class, trimmed and
+    winsorized means, ranks and percentile-of-score, quantile mapping, quantiles at many ``q`` at once and run lengths of the
+    values are then one line of numpy or torch each.
+
+    ``args``, ``bins``, ``range`` and ``axis``, the samples that count, the compare domains, the joint bins of up to 8 inputs, the
+    estimator names and the meaning of a position are :func:`bin_order`'s.  ``values`` broadcasts against the inputs as
+    :func:`histogram_extrema`'s does, may have any real dtype and is taken as float64; a complex dtype is a ``TypeError``.
+    With ``B`` the number of bins, ``c`` the product of the reduced extents and ``kept`` the kept axes' shape, ``order`` is int64
+    ``kept + (c,)`` and ``offsets`` int64 ``kept + (B + 1,)``.  Per kept index, with ``key[p]`` the bin index at position ``p``
+    and ``-1`` replaced by ``B``, and ``vk[p]`` the key :func:`extrema_keys` gives ``values[p]`` (the total order of the values
+    with ``-0.0 < +0.0``), its bits complemented when ``descending``, and ``2**64 - 1`` for a NaN value in either direction, so
+    that NaN is last in its bin either way:
+
+    * ``order = np.lexsort((vk, key))``: by bin, then by value, ties in ascending position;
+    * ``offsets[b] = #{p : key[p] < b}`` for ``b = 0 .. B``.
+
+    So, for ``B <= 40959``, ``offsets`` equals :func:`bin_order`'s bit for bit, and ``np.sort(order[offsets[b]:offsets[b + 1]])``
+    is its segment; the samples ``histogram`` drops, ``order[offsets[B]:]``, are sorted by value too;
+    ``values[order[offsets[b]]]`` of a bin with a non-NaN value is :func:`histogram_extrema`'s ``vmin`` and ``order[offsets[b]]``
+    :func:`histogram_argextrema`'s ``argmin`` (``vmax`` and ``argmax`` with ``descending=True``); and with ``n`` non-NaN values in a
+    bin, ``values[order[offsets[b] + floor(q * (n - 1))]]`` is ``histogram_quantile(method="lower")``.
+
+    A plan without bins (one edge) gives ``offsets == [0]`` and the whole row sorted by value; ``c == 0`` an empty ``order`` and
+    offsets of 0.  Exact and deterministic: a stable radix sort on 8-bit digits whose every placement is a function of the keys
+    alone.  There is no bound of 40 959 bins: every pass keeps 256 counters per wave, whatever ``B`` is.  A reduced extent of
+    2^31 samples or more per row, and ``B + 1 > 2**32``, raise ``NotImplementedError`` before any device work.  There are no
+    ``weights``.
+
+    Returns ``(order, offsets, bin_edges)``.  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on
+    the current stream, no host synchronisation), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block
+    over the kept axes: every reduced axis must then be a single chunk, and ``bins`` numpy arrays of edges."""
+    if not args:
+        raise TypeError("bin_sort needs at least one array of samples")
+    if values is None:
+        raise TypeError("bin_sort needs values")
+    descending = _check_flag("descending", descending)
+    for a in args:
+        dt = a.dtype if hasattr(a, "dtype") else np.asarray(a).dtype
+        if getattr(dt, "is_complex", False) or getattr(dt, "kind", "") == "c":
+            raise TypeError("complex samples have no order: bin_sort takes real samples")
+    if not hasattr(values, "dtype"):
+        values = np.asarray(values)
+    n = len(args)
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "bin_sort")
+    shape = tuple(int(s) for s in all_arrays[0].shape)
+    cols = int(np.prod([shape[ax] for ax in drop_axes], dtype=object)) if drop_axes else 1
+    if cols >= _ORDER_MAX_COLS:
+        raise NotImplementedError("bin_sort takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
+                                  % (_ORDER_MAX_COLS, cols))
+    n_bins = int(np.prod([max(len(b) - 1, 0) for b in bins], dtype=object))
+    if n_bins > _SORT_MAX_BINS:
+        raise NotImplementedError("bin_sort takes at most 2^32 - 1 = %d bins, got %d" % (_SORT_MAX_BINS, n_bins))
+    if backend == "dask":
+        if any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
+            raise ValueError("sorted orders of several chunks cannot be merged: rechunk the reduced axes of every input into "
+                             "one chunk (e.g. arr.rechunk({axis: -1}))")
+        import dask.array as dsa
+
+        ndim = len(shape)
+        ind = tuple(_range(ndim))
+        packed = dsa.blockwise(_bin_sort_block, ind + (ndim,), *[x for a in all_arrays for x in (a, ind)], dtype=np.int64,
+                               new_axes={ndim: cols + n_bins + 1}, adjust_chunks={ax: (lambda extent: 1) for ax in drop_axes},
+                               axis=list(drop_axes), bins=bins, descending=descending, meta=np.array((), np.int64))
+        packed = packed[tuple(0 if i in drop_axes else slice(None) for i in _range(ndim)) + (slice(None),)]
+        return packed[..., :cols], packed[..., cols:], bins
+    arrays, on = _resident(backend, raw, all_arrays, n, bins)
+    order, offsets = _sort_rows(arrays[:n], arrays[n], axis, bins, on, descending)
     return order, offsets, bins

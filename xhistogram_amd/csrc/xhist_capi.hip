@@ -452,6 +452,37 @@ extern "C" int xhist_plan_execute_group(xhist_plan* p, const xhist_array* sample
   return XHIST_OK;
 }
 
+// bin_sort (xhist_sort.hip): bin_order's front with values.  A plan without bins still has work to do, the whole row sorted by
+// value: the statistics' front has no output row to launch over, so the record of that call is made here.
+extern "C" int xhist_plan_execute_sort(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+                                       int descending, int64_t* out_order, int64_t* out_offsets, int mem_kind, void* stream) {
+  if (p && n_cols >= ((int64_t)1 << 31))
+    return fail(XHIST_ERR_UNSUPPORTED, "bin_sort takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), got %lld",
+                (long long)n_cols);
+  if (p && p->n_bins + 1 > ((int64_t)1 << 32))
+    return fail(XHIST_ERR_UNSUPPORTED, "bin_sort takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
+                (long long)p->n_bins);
+  const bool work = p && n_rows > 0 && n_cols > 0;
+  if (work && !out_order) return fail(XHIST_ERR_INVALID, "out_order is NULL");
+  static int64_t no_columns;  // (what validate_arrays sees of a call without columns: the block has no element)
+  const int rc = execute_values(p, "xhist_plan_execute_sort", samples, values, nullptr, nullptr, n_rows, n_cols,
+                                reinterpret_cast<double*>(out_order ? out_order : &no_columns), out_offsets != nullptr, "out_offsets is NULL",
+                                mem_kind, stream, [&](const ValuesCall& k) { return xhist_sort_run(k, descending, out_order, out_offsets); });
+  if (rc != XHIST_OK || p->n_bins > 0 || n_rows <= 0) return rc;
+  if (!out_offsets) return fail(XHIST_ERR_INVALID, "out_offsets is NULL");
+  DeviceGuard g;
+  if (int grc = g.set(p->device)) return grc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ScratchScope scratch(s);
+  char err[256] = {0}, desc[384] = {0};
+  const ValuesCall call = {values_plan(p), samples, values, nullptr, nullptr, n_rows, n_cols, s, err, sizeof err, desc, sizeof desc,
+                           values_scratch_alloc, &scratch};
+  if (int src = xhist_sort_run(call, descending, out_order, out_offsets)) return fail(src, "%s", err);
+  std::lock_guard<std::mutex> lk(p->mu);
+  p->desc = desc;
+  return XHIST_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // one-shot form with a plan cache
 // ------------------------------------------------------------------------------------------

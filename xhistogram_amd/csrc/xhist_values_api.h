@@ -112,3 +112,10 @@ int xhist_map_run(const ValuesCall& k, int op, const double* centre, const doubl
 // bins, which the statistics' front does not launch over (offsets [n_rows, 1] of zeros, every row's order its positions).
 int xhist_group_run(const ValuesCall& k, int64_t* out_order, int64_t* out_offsets);
 int xhist_group_no_bins(int64_t n_rows, int64_t n_cols, int64_t* out_order, int64_t* out_offsets, hipStream_t stream);
+
+// xhist_sort.hip: bin_sort, a row's samples grouped by bin and sorted by value inside each bin (k.values the values; `descending`
+// nonzero: largest first, NaN still last).  The outputs are bin_order's; every element of both is written exactly once.  A
+// stable radix sort on 8-bit digits of (value key, position), then of the gathered bin keys: 32 bytes of scratch per sample
+// from k.alloc.  Unlike the other drivers it also takes a plan without bins (n_bins 0: the whole row sorted by value, one
+// offset of 0 per row).  XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for n_bins + 1 > 2^32, before any launch.
+int xhist_sort_run(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets);

@@ -15,7 +15,7 @@ from .core import histogram_two_weights as _core_histogram_two_weights
 
 __all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
            "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt", "histogram_argextrema", "bin_index", "histogram_lookup",
-           "histogram_anomaly", "histogram_sum", "bin_order"]
+           "histogram_anomaly", "histogram_sum", "bin_order", "bin_sort"]
 
 
 def _xr():
@@ -489,4 +489,27 @@ def bin_order(*args, bins=None, range=None, dim=None):
     coords = _sample_coords(first, kept)
     xr = _xr()
     return (xr.DataArray(order, dims=kept + ["%s_order" % name], coords=coords, name="%s_bin_order" % name),
+            xr.DataArray(offsets, dims=kept + ["%s_bin_offset" % name], coords=coords, name="%s_bin_offsets" % name))
+
+
+def bin_sort(*args, values, bins=None, range=None, dim=None, descending=False):
+    """The samples grouped by bin and sorted by value inside each bin (:func:`xhistogram_amd.core.bin_sort`); ``values`` is
+    lined up as :func:`histogram_extrema` lines it up.  Two int64 DataArrays on the kept dims (those not in ``dim``; none for
+    ``dim=None``): ``<values name>_bin_sort`` with a new last dim ``<values name>_order`` (the positions over the dims of
+    ``dim`` in the inputs' broadcast dim order, by bin, then by value, NaN last in its bin, dropped samples last) and
+    ``<values name>_bin_offsets`` with a new last dim ``<values name>_bin_offset`` (where each bin's run starts; the last entry:
+    where the dropped samples start).  ``values`` without a name is called ``values``."""
+    from .core import bin_sort as _core_bin_sort
+
+    if values is None:
+        raise TypeError("bin_sort needs values")
+    arrays, dims_order, first = _lined_up("bin_sort", args, [values])
+    n = len(args)
+    kept = [d for d in dims_order if dim is not None and d not in dim]
+    axis = None if dim is None else [dims_order.index(d) for d in dim]
+    order, offsets, _ = _core_bin_sort(*arrays[:n], values=arrays[n], bins=bins, range=range, axis=axis, descending=descending)
+    name = values.name or "values"
+    coords = _sample_coords(first, kept)
+    xr = _xr()
+    return (xr.DataArray(order, dims=kept + ["%s_order" % name], coords=coords, name="%s_bin_sort" % name),
             xr.DataArray(offsets, dims=kept + ["%s_bin_offset" % name], coords=coords, name="%s_bin_offsets" % name))
