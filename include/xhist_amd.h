@@ -401,6 +401,47 @@ int xhist_plan_execute_sort(xhist_plan* plan, const xhist_array* samples, const 
                             int64_t n_cols, int descending, int64_t* out_order, int64_t* out_offsets, int mem_kind,
                             void* stream);
 
+/* bin_rank (added within ABI v11: a new entry, every earlier one unchanged): the rank of every sample's value among the values
+ * of its bin.  Per row r, with S the columns of bin b that xhist_plan_execute counts and whose value, taken as float64, is not
+ * NaN, n = |S|, the values of S in ascending order (descending when `descending` is nonzero) and ties decided by IEEE == (so
+ * -0.0 and +0.0 tie), for a column c of S with value v: lt the number of values of S strictly before v in that order, eq the
+ * number equal to v, d the number of distinct values up to and including v, D the number of distinct values of S.
+ *   out[r, c] = (2 lt + eq + 1) / 2   XHIST_RANK_AVERAGE
+ *               lt + 1                XHIST_RANK_MIN
+ *               lt + eq               XHIST_RANK_MAX
+ *               d                     XHIST_RANK_DENSE
+ *               i - out_offsets[r, b] + 1 for out_order[r, i] == c of xhist_plan_execute_sort on the same arguments
+ *                                     XHIST_RANK_ORDINAL: ties in ascending column, -0.0 before +0.0 (after it when descending)
+ *   and with `pct` nonzero that rank divided once, in IEEE float64, by n (by D for XHIST_RANK_DENSE).  NaN (0x7ff8000000000000)
+ *   for a column that is not counted and for a column whose value is NaN.  Every rank is an integer or a half-integer below
+ *   2^31: every result is exact.
+ *   out: a contiguous DEVICE block [n_rows, n_cols] of float64, a row's columns in position order; every element is written
+ *   exactly once and nothing outside it.  A plan without bins counts no sample: the block is filled with NaN, the all-ones bit
+ *   pattern.
+ *   values: any real dtype, any strides.  An unknown method is XHIST_ERR_INVALID.  n_cols must be below 2^31 and B + 1 at most
+ *   2^32: XHIST_ERR_UNSUPPORTED otherwise, before any launch.
+ *   The call is xhist_plan_execute_sort into scratch and six kernels over its sorted order: head and NaN bits of every sorted
+ *   position from two ballots per 64 positions (the only gather of the values), a scan of the head words per row in three
+ *   launches (tiles of 1024 words), the divisors per (row, bin) when pct, and the ranks scattered to out.  No kernel waits for
+ *   another workgroup.
+ *   Scratch of the call, on top of xhist_plan_execute_sort's: 8 bytes per sample of order, n_rows * (B + 1) * 8 bytes of
+ *   offsets, 28 bytes per 64 samples of a row (two 8-byte words of bits and three uint32), 12 bytes per 65536 samples of a row
+ *   (a tile's three uint32), and n_rows * B * 8 bytes of divisors when pct; XHIST_ERR_NOMEM where it cannot be had.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Exact and deterministic.  Asynchronous on `stream`.
+ *   xhist_plan_describe then reads "rank method=average|min|max|dense|ordinal pct=.. descending=.. words=.. rows_per_launch=..
+ *   | " followed by xhist_plan_execute_sort's own line ("none" for a call without columns): the words of 64 positions of a
+ *   row and the rows of one launch. */
+typedef enum {
+  XHIST_RANK_AVERAGE = 0,
+  XHIST_RANK_MIN,
+  XHIST_RANK_MAX,
+  XHIST_RANK_DENSE,
+  XHIST_RANK_ORDINAL
+} xhist_rank_method;
+int xhist_plan_execute_rank(xhist_plan* plan, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
+                            int64_t n_cols, int method, int descending, int pct, double* out, int mem_kind, void* stream);
+
 /* One-shot form of the two calls above with an internal plan cache keyed on (device, edges). */
 int xhist_bincount_rows(int device, int n_inputs, const xhist_array* samples,
                         const xhist_array* weights, int64_t n_rows, int64_t n_cols,

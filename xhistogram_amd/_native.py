@@ -33,6 +33,8 @@ MEM_HOST, MEM_DEVICE, MEM_HOST_TO_DEVICE = 0, 1, 2
 COMM_ID_BYTES = 128
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 0, 1, 2
 MAP_INDEX, MAP_TAKE, MAP_ANOMALY = 0, 1, 2  # the ops of xhist_plan_execute_map (XHIST_MAP_*)
+RANK_AVERAGE, RANK_MIN, RANK_MAX, RANK_DENSE, RANK_ORDINAL = 0, 1, 2, 3, 4  # the methods of xhist_plan_execute_rank (XHIST_RANK_*)
+RANK_METHODS = {"average": RANK_AVERAGE, "min": RANK_MIN, "max": RANK_MAX, "dense": RANK_DENSE, "ordinal": RANK_ORDINAL}
 
 _NP_TAG = {
     np.dtype(np.float64): F64, np.dtype(np.float32): F32, np.dtype(np.float16): F16,
@@ -73,7 +75,7 @@ EXPORTS = (
     "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
     "xhist_plan_execute_quantile_weighted", "xhist_plan_execute_cov", "xhist_plan_execute_cov_weighted",
     "xhist_plan_execute_skew_kurt", "xhist_plan_execute_skew_kurt_weighted", "xhist_plan_execute_argextrema",
-    "xhist_plan_execute_map", "xhist_plan_execute_group", "xhist_plan_execute_sort", "xhist_plan_execute_sum", "xhist_debug_sum_host", "xhist_debug_sum_round",
+    "xhist_plan_execute_map", "xhist_plan_execute_group", "xhist_plan_execute_sort", "xhist_plan_execute_rank", "xhist_plan_execute_sum", "xhist_debug_sum_host", "xhist_debug_sum_round",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -181,6 +183,10 @@ def load():
         ]
         lib.xhist_plan_execute_sort.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+            C.c_void_p,
+        ]
+        lib.xhist_plan_execute_rank.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
             C.c_void_p,
         ]
         lib.xhist_bincount_rows.argtypes = [
@@ -448,6 +454,18 @@ class Plan:
             load().xhist_plan_execute_sort(
                 self._h, self._sample_array(sample_views), C.byref(value_view), int(n_rows), int(n_cols), 1 if descending else 0,
                 C.c_void_p(out_order_ptr), C.c_void_p(out_offsets_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
+            )
+        )
+
+    def execute_rank(self, sample_views, value_view, n_rows, n_cols, method, descending, pct, out_ptr, stream=0):
+        """the rank of every column's value among the non-NaN values of its bin, of device-resident views, asynchronous on
+        `stream` (xhist_plan_execute_rank): float64 into the dense row-major [n_rows, n_cols] device block at `out_ptr`, NaN for
+        a column that is not counted or whose value is NaN.  `method` is a RANK_* code; `descending`: largest first; `pct`: divided
+        by the bin's number of non-NaN values (of distinct ones for RANK_DENSE); fewer than 2^31 columns"""
+        check(
+            load().xhist_plan_execute_rank(
+                self._h, self._sample_array(sample_views), C.byref(value_view), int(n_rows), int(n_cols), int(method),
+                1 if descending else 0, 1 if pct else 0, C.c_void_p(out_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
             )
         )
 

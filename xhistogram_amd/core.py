@@ -35,7 +35,7 @@ _range = range
 
 __all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
            "histogram_weighted_quantile", "histogram_cov", "histogram_weighted_cov", "combine_weighted_cov",
-           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema", "histogram_sum", "bin_order", "bin_sort"]
+           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema", "histogram_sum", "bin_order", "bin_sort", "bin_rank"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2615,13 +2615,22 @@ def histogram_weighted_quantile(*args, values, weights, q, bins=None, range=None
 # per-sample maps: from a per-bin result back to the samples
 # ---------------------------------------------------------------------------------------------
 def _map_out(plan, nv, has_values, m, c, op, centre_ptr, scale_ptr, like, axis, backend, device, stream):
-    """xhist_plan_execute_map over the `ordered` views `nv` of _value_views (samples..., then the values where `has_values`):
-    the dense [m, c] block the kernels write, in the broadcast sample shape of `like` — a torch tensor on its device
-    (asynchronous on `stream`) or a numpy array.  The block's rows are the kept axes in C order and a row's columns the
+    """xhist_plan_execute_map over the `ordered` views `nv` of _value_views (samples..., then the values where `has_values`),
+    into the block of _sample_block"""
+    n = plan.n_dims
+
+    def run(out_ptr):
+        plan.execute_map(nv[:n], nv[n] if has_values else None, m, c, op, centre_ptr, scale_ptr, out_ptr, stream=stream)
+
+    return _sample_block(run, m, c, op == _native.MAP_INDEX, like, axis, backend, device)
+
+
+def _sample_block(run, m, c, is_index, like, axis, backend, device):
+    """The dense [m, c] block of 8-byte elements (int64 where `is_index`, else float64) that `run(pointer)` has the kernels
+    write, one element per sample, in the broadcast sample shape of `like` — a torch tensor on its device (asynchronous on the
+    call's stream) or a numpy array.  The block's rows are the kept axes in C order and a row's columns the
     reduced axes in ascending number: it is reshaped, and its axes moved back where `axis` is not trailing.  The kernels are
     handed this block itself, never a view of something else: a copied output would be lost."""
-    n = plan.n_dims
-    is_index = op == _native.MAP_INDEX
     shape = tuple(int(s) for s in like.shape)
     ndim = len(shape)
     red = list(_range(ndim)) if axis is None or set(axis) == set(_range(ndim)) else sorted(axis)
@@ -2634,8 +2643,7 @@ def _map_out(plan, nv, has_values, m, c, op, centre_ptr, scale_ptr, like, axis, 
     if m * c > 0:
         # (a plan without bins counts no sample: the library itself then fills the block with -1 / NaN)
         buf = None if backend == "torch" else _native.DeviceBuffer(device, m * c * 8)
-        plan.execute_map(nv[:n], nv[n] if has_values else None, m, c, op, centre_ptr, scale_ptr,
-                         out.data_ptr() if buf is None else buf.ptr, stream=stream)
+        run(out.data_ptr() if buf is None else buf.ptr)
         if buf is not None:
             buf.download(out)  # (waits for the kernels: the views' keepalive copies are not needed after this)
     out = out.reshape([shape[i] for i in kept] + [shape[i] for i in red])
@@ -3069,3 +3077,92 @@ def bin_sort(*args, values, bins=None, range=None, axis=None, descending=False):
     arrays, on = _resident(backend, raw, all_arrays, n, bins)
     order, offsets = _sort_rows(arrays[:n], arrays[n], axis, bins, on, descending)
     return order, offsets, bins
+
+
+# ---------------------------------------------------------------------------------------------
+# bin_rank: the rank of each sample's value inside its bin
+# ---------------------------------------------------------------------------------------------
+def _bin_rank_block(*blocks, axis=None, bins=None, method="average", descending=False, pct=False):
+    return bin_rank(*blocks[:-1], values=blocks[-1], bins=bins, axis=axis, method=method, descending=descending, pct=pct)[0]
+
+
+def bin_rank(*args, values, bins=None, range=None, axis=None, method="average", descending=False, pct=False):
+    """The rank of every sample's value among the values of its bin, computed on an MI355X: the per-sample rank,
+    percentile-of-score and empirical CDF value inside a class — ``pandas.Series.groupby(bin).rank(...)`` and
+    ``scipy.stats.rankdata`` per bin on the host; the input of quantile mapping, of Spearman correlation per class and of
+    rank-based outlier masks.
+
+    ``args``, ``bins``, ``range``, ``axis`` and ``values``, the samples that count, the compare domains, the joint bins of up to
+    8 inputs, the estimator names, the broadcasting and ``values`` taken as float64 are :func:`bin_sort`'s; a complex dtype is a
+    ``TypeError``.  ``rank`` is float64 in the broadcast shape of the inputs, as :func:`histogram_anomaly`'s output is.  It is
+    NaN for a sample ``histogram`` does not count (out of range, or NaN in any input) and for a sample whose value is NaN
+    (pandas ``na_option="keep"``, scipy ``nan_policy="omit"``).
+
+    Per kept index, let ``S`` be the counted samples of a bin whose value is not NaN and ``n = len(S)``, in ascending order of
+    value (descending with ``descending=True``), ties decided by IEEE ``==``, so ``-0.0`` and ``+0.0`` tie.  For a sample with
+    value ``v``, with ``lt`` the number of values of ``S`` strictly before ``v`` in that order, ``eq`` the number equal to ``v``,
+    ``d`` the number of distinct values up to and including ``v`` and ``D`` the number of distinct values of ``S``:
+
+    * ``"average"``: ``(2 * lt + eq + 1) / 2`` (scipy and pandas ``average``);
+    * ``"min"``: ``lt + 1``; ``"max"``: ``lt + eq``; ``"dense"``: ``d``;
+    * ``"ordinal"``: its place in :func:`bin_sort`'s segment, ``i - offsets[b] + 1`` for ``order[i] == position`` (scipy
+      ``ordinal``, pandas ``first``): ties in ascending position, and ``-0.0`` before ``+0.0`` (after it when descending).
+
+    With ``pct=True`` the rank is divided once, in IEEE float64, by ``n`` (by ``D`` for ``"dense"``), as pandas
+    ``rank(pct=True)`` divides.  Every rank is an integer or a half-integer below 2^31, so every result is exact, and the call
+    is deterministic.  So ``pct=True, method="max"`` is the bin's empirical CDF at the sample
+    (``scipy.stats.percentileofscore(kind="weak") / 100``), ``(min - 1) / n`` is ``kind="strict"`` and ``average / n`` is
+    ``kind="rank"``; the samples of ``min`` rank 1 are those whose value ``==`` :func:`histogram_extrema`'s ``vmin`` (``vmax``
+    when descending); and the largest ``max`` rank of a bin is :func:`histogram_mean_var`'s ``count``.
+
+    A plan without bins (one edge) counts no sample: all NaN.  Extents of 0 give empty outputs.  An unknown ``method`` raises
+    ``ValueError``; a reduced extent of 2^31 samples or more per row, and ``B + 1 > 2**32``, raise ``NotImplementedError``; all
+    before any device work.  There are no ``weights``.
+
+    Returns ``(rank, bin_edges)``.  numpy in -> numpy out (uploaded once), torch in -> torch out on the same device
+    (asynchronous on the current stream, no host synchronisation), DeviceArray in -> numpy out, dask in -> a lazy dask array,
+    one task per block over the kept axes: every reduced axis must then be a single chunk, and ``bins`` numpy arrays of
+    edges."""
+    if not args:
+        raise TypeError("bin_rank needs at least one array of samples")
+    if values is None:
+        raise TypeError("bin_rank needs values")
+    if not isinstance(method, str) or method not in _native.RANK_METHODS:
+        raise ValueError("unknown rank method %r: one of %s" % (method, ", ".join(_native.RANK_METHODS)))
+    descending = _check_flag("descending", descending)
+    pct = _check_flag("pct", pct)
+    for a in args:
+        dt = a.dtype if hasattr(a, "dtype") else np.asarray(a).dtype
+        if getattr(dt, "is_complex", False) or getattr(dt, "kind", "") == "c":
+            raise TypeError("complex samples have no order: bin_rank takes real samples")
+    if not hasattr(values, "dtype"):
+        values = np.asarray(values)
+    n = len(args)
+    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "bin_rank")
+    shape = tuple(int(s) for s in all_arrays[0].shape)
+    cols = int(np.prod([shape[ax] for ax in drop_axes], dtype=object)) if drop_axes else 1
+    if cols >= _ORDER_MAX_COLS:
+        raise NotImplementedError("bin_rank takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
+                                  % (_ORDER_MAX_COLS, cols))
+    n_bins = int(np.prod([max(len(b) - 1, 0) for b in bins], dtype=object))
+    if n_bins > _SORT_MAX_BINS:
+        raise NotImplementedError("bin_rank takes at most 2^32 - 1 = %d bins, got %d" % (_SORT_MAX_BINS, n_bins))
+    if backend == "dask":
+        if any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
+            raise ValueError("ranks of several chunks cannot be merged: rechunk the reduced axes of every input into "
+                             "one chunk (e.g. arr.rechunk({axis: -1}))")
+        import dask.array as dsa
+
+        ind = tuple(_range(len(shape)))
+        out = dsa.blockwise(_bin_rank_block, ind, *[x for a in all_arrays for x in (a, ind)], dtype=np.float64, axis=list(drop_axes),
+                            bins=bins, method=method, descending=descending, pct=pct, meta=np.array((), np.float64))
+        return out, bins
+    arrays, on = _resident(backend, raw, all_arrays, n, bins)
+    plan, nv, views, m, c, _, device, stream = _value_views(arrays[:n], arrays[n], axis, bins, on, ordered=True)
+
+    def run(out_ptr):
+        plan.execute_rank(nv[:n], nv[n], m, c, _native.RANK_METHODS[method], descending, pct, out_ptr, stream=stream)
+
+    out = _sample_block(run, m, c, False, arrays[0], axis, on, device)
+    del views
+    return out, bins

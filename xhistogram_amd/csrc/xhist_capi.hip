@@ -483,6 +483,29 @@ extern "C" int xhist_plan_execute_sort(xhist_plan* p, const xhist_array* samples
   return XHIST_OK;
 }
 
+// bin_rank (xhist_rank.hip): the maps' front, with values.  A plan without bins counts no sample and the statistics' front has no
+// output row to launch over: the block is filled with NaN here, bytes of all ones, as for the maps.
+extern "C" int xhist_plan_execute_rank(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+                                       int method, int descending, int pct, double* out, int mem_kind, void* stream) {
+  if (method < XHIST_RANK_AVERAGE || method > XHIST_RANK_ORDINAL) return fail(XHIST_ERR_INVALID, "unknown rank method %d", method);
+  if (p && n_cols >= ((int64_t)1 << 31))
+    return fail(XHIST_ERR_UNSUPPORTED, "bin_rank takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), got %lld",
+                (long long)n_cols);
+  if (p && p->n_bins + 1 > ((int64_t)1 << 32))
+    return fail(XHIST_ERR_UNSUPPORTED, "bin_rank takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
+                (long long)p->n_bins);
+  const bool work = p && n_rows > 0 && n_cols > 0;
+  if (work && !out) return fail(XHIST_ERR_INVALID, "out is NULL");
+  static double no_columns;  // (what validate_arrays sees of a call without columns: the block has no element)
+  const int rc = execute_values(p, "xhist_plan_execute_rank", samples, values, nullptr, nullptr, n_rows, n_cols, out ? out : &no_columns, true,
+                                "", mem_kind, stream, [&](const ValuesCall& k) { return xhist_rank_run(k, method, descending, pct, out); });
+  if (rc != XHIST_OK || p->n_bins > 0 || !work) return rc;
+  DeviceGuard g;
+  if (int grc = g.set(p->device)) return grc;
+  HIPC(hipMemsetAsync(out, 0xff, (size_t)n_rows * (size_t)n_cols * 8, static_cast<hipStream_t>(stream)));
+  return XHIST_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // one-shot form with a plan cache
 // ------------------------------------------------------------------------------------------

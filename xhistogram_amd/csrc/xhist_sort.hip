@@ -77,6 +77,12 @@ static const char* sort_dtype_name(int dt) {
 }  // namespace
 
 int xhist_sort_run(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets) {
+  return xhist_sort_run_keys(k, descending, out_order, out_offsets, nullptr);
+}
+
+// The driver.  `hand` (nullptr: nobody asks) receives what bin_rank builds on: the sorted bin keys the last pass of a call with
+// bins wrote beside the order (scratch of the call, alive until the call returns) and the rows of a launch.
+int xhist_sort_run_keys(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets, SortHandover* hand) {
   const ValuesPlan& pl = k.pl;
   const int64_t nb = pl.n_bins, nb1 = nb + 1;
   if (k.n_cols >= ((int64_t)1 << 31))
@@ -189,6 +195,10 @@ int xhist_sort_run(const ValuesCall& k, int descending, int64_t* out_order, int6
                        k.n_cols, nb);
       XH_VALUES_LAUNCH_CHECK(k, "sort_offsets launch");
     }
+  }
+  if (hand) {
+    hand->keys = bin_passes > 0 ? kbuf[(value_passes + bin_passes) & 1] : nullptr;  // (every batch of rows ends in the same buffer)
+    hand->rows_per_launch = g.max_rows;
   }
   k.describe("sort keys=%s value_passes=%d bin_passes=%d waves=%d block=%d chunks=%lld chunk=%lld slices=%lld rows_per_launch=%lld D=%d cmp=%d "
              "vdtype=%s", family, value_passes, bin_passes, kSortWaves, block, (long long)g.chunks, (long long)g.chunk, (long long)g.slices,

@@ -119,3 +119,21 @@ int xhist_group_no_bins(int64_t n_rows, int64_t n_cols, int64_t* out_order, int6
 // from k.alloc.  Unlike the other drivers it also takes a plan without bins (n_bins 0: the whole row sorted by value, one
 // offset of 0 per row).  XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for n_bins + 1 > 2^32, before any launch.
 int xhist_sort_run(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets);
+// what bin_rank takes over from the sort (`hand` nullptr: xhist_sort_run itself): the sorted bin keys [n_rows, n_cols], each in
+// [0, n_bins], in scratch of the call (nullptr for a plan without bins), and the rows of one launch
+struct SortHandover {
+  const uint64_t* keys;
+  int64_t rows_per_launch;
+};
+int xhist_sort_run_keys(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets, SortHandover* hand);
+
+// xhist_rank.hip: bin_rank, the rank of every sample's value among the non-NaN values of its bin (k.values the values; method
+// an XHIST_RANK_* code; `descending` nonzero: largest first; `pct` nonzero: divided by the bin's count of non-NaN values, by its
+// distinct values for XHIST_RANK_DENSE).  out is a dense float64 [n_rows, n_cols] block in position order, every element
+// written exactly once; NaN for a sample that is not counted and for a NaN value.  It runs xhist_sort_run_keys into scratch and
+// six kernels over the sorted order.  Scratch from k.alloc, one block on top of the sort's 32 bytes per sample: 8 bytes per
+// sample of order, n_rows * (n_bins + 1) * 8 bytes of offsets, 28 bytes per 64 samples of head and NaN words with their three
+// uint32 scalars, 12 bytes per 65536 samples of tile scalars, and n_rows * n_bins * 8 bytes of divisors when pct.  Like the
+// sort it takes a plan without bins (all NaN).
+// XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for n_bins + 1 > 2^32, XHIST_ERR_INVALID for an unknown method, before any launch.
+int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, double* out);

@@ -15,7 +15,7 @@ from .core import histogram_two_weights as _core_histogram_two_weights
 
 __all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
            "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt", "histogram_argextrema", "bin_index", "histogram_lookup",
-           "histogram_anomaly", "histogram_sum", "bin_order", "bin_sort"]
+           "histogram_anomaly", "histogram_sum", "bin_order", "bin_sort", "bin_rank"]
 
 
 def _xr():
@@ -513,3 +513,19 @@ def bin_sort(*args, values, bins=None, range=None, dim=None, descending=False):
     xr = _xr()
     return (xr.DataArray(order, dims=kept + ["%s_order" % name], coords=coords, name="%s_bin_sort" % name),
             xr.DataArray(offsets, dims=kept + ["%s_bin_offset" % name], coords=coords, name="%s_bin_offsets" % name))
+
+
+def bin_rank(*args, values, bins=None, range=None, dim=None, method="average", descending=False, pct=False):
+    """The rank of every sample's value among the values of its bin (:func:`xhistogram_amd.core.bin_rank`); ``values`` is lined up
+    as :func:`histogram_extrema` lines it up.  Returns a float64 DataArray on the broadcast dims of the inputs, named
+    ``<values name>_bin_rank`` (``values`` without a name)."""
+    from .core import bin_rank as _core_bin_rank
+
+    if values is None:
+        raise TypeError("bin_rank needs values")
+    arrays, dims_order, first = _lined_up("bin_rank", args, [values])
+    n = len(args)
+    axis = None if dim is None else [dims_order.index(d) for d in dim]
+    out, _ = _core_bin_rank(*arrays[:n], values=arrays[n], bins=bins, range=range, axis=axis, method=method, descending=descending,
+                            pct=pct)
+    return _xr().DataArray(out, dims=dims_order, coords=_sample_coords(first, dims_order), name="%s_bin_rank" % (values.name or "values"))
