@@ -1,5 +1,6 @@
 """bin_order on the CPU: what `order` and `offsets` must be for an array of bin indices, stated with numpy's own stable sort,
-and the host's launch geometry (xhist_group.hip's group_geometry) with the describe() line it leads to, restated.
+and the host's launch geometry (xhist_group.hip's group_geometry, over xhist_runs.hip.h's runs_geometry) with the describe() line
+it leads to, restated.
 
 Everything here is integer work: every comparison made with it is bit for bit."""
 import re

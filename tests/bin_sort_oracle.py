@@ -1,6 +1,6 @@
 """bin_sort on the CPU: what `order` and `offsets` must be for bin indices and values, stated with np.lexsort over
-core.extrema_keys, and the host's launch geometry, pass table (xhist_sort.hip's sort_geometry and sort_value_shift) and
-describe() line, restated.
+core.extrema_keys, and the host's launch geometry (xhist_runs.hip.h's runs_geometry with the constants xhist_sort.hip hands it),
+pass table (xhist_sort.hip's sort_value_shift) and describe() line, restated.
 
 Everything here is integer work: every comparison made with it is bit for bit."""
 import re

@@ -2859,16 +2859,55 @@ def histogram_anomaly(*args, values, bins=None, range=None, axis=None, weights=N
 
 
 # ---------------------------------------------------------------------------------------------
-# bin_order: the samples grouped by bin
+# bin_order, bin_sort and bin_rank: the samples grouped by bin, their one call path
 # ---------------------------------------------------------------------------------------------
 _ORDER_MAX_COLS = 1 << 31
+_SORT_MAX_BINS = (1 << 32) - 1
 
 
-def _order_rows(arrays, axis, bins, on):
-    """xhist_plan_execute_group over the `ordered` views of broadcast torch tensors or DeviceArrays: (order [kept axes, c],
+# what _grouped_call returns: _values_call's six, then the samples per output row and the number of bins
+_Grouped = namedtuple("_Grouped", "backend arrays raw bins axis drop_axes cols n_bins")
+
+
+def _grouped_call(name, noun, args, values, bins, range, axis, needs_values=True, max_bins=None, check=None):
+    """The front of bin_order (`needs_values` False, values None), bin_sort and bin_rank, all of it before any device work: the
+    argument checks (`check`: the caller's own, run in their place among them), _values_call, and the refusals of 2^31 samples
+    or more per output row, of more than `max_bins` bins (None: no bound here) and of dask inputs whose reduced axes are cut
+    (`noun`: what then cannot be merged).  Returns a _Grouped."""
+    if not args:
+        raise TypeError("%s needs at least one array of samples" % name)
+    if values is None and needs_values:
+        raise TypeError("%s needs values" % name)
+    if check is not None:
+        check()
+    for a in args:
+        dt = a.dtype if hasattr(a, "dtype") else np.asarray(a).dtype
+        if getattr(dt, "is_complex", False) or getattr(dt, "kind", "") == "c":
+            raise TypeError("complex samples have no order: %s takes real samples" % name)
+    if values is not None and not hasattr(values, "dtype"):
+        values = np.asarray(values)
+    call = _values_call(args, values, bins, range, axis, name, needs_values=needs_values)
+    backend, all_arrays, _, bins, _, drop_axes = call
+    shape = tuple(int(s) for s in all_arrays[0].shape)
+    cols = int(np.prod([shape[ax] for ax in drop_axes], dtype=object)) if drop_axes else 1
+    if cols >= _ORDER_MAX_COLS:
+        raise NotImplementedError("%s takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
+                                  % (name, _ORDER_MAX_COLS, cols))
+    n_bins = int(np.prod([max(len(b) - 1, 0) for b in bins], dtype=object))
+    if max_bins is not None and n_bins > max_bins:
+        raise NotImplementedError("%s takes at most 2^32 - 1 = %d bins, got %d" % (name, max_bins, n_bins))
+    if backend == "dask" and any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
+        raise ValueError("%s of several chunks cannot be merged: rechunk the reduced axes of every input into "
+                         "one chunk (e.g. arr.rechunk({axis: -1}))" % noun)
+    return _Grouped(*call, cols, n_bins)
+
+
+def _order_offsets_rows(run, arrays, values, axis, bins, on):
+    """`run(plan, nv, m, c, order_ptr, offsets_ptr, stream)`, the caller's Plan method, over the `ordered` views `nv` of
+    broadcast torch tensors or DeviceArrays (samples..., then the values; None: the samples alone): (order [kept axes, c],
     offsets [kept axes, B + 1]), int64, torch tensors on the samples' device (asynchronous on the current stream) or numpy
     arrays.  The kernels are handed these blocks themselves."""
-    plan, nv, views, m, c, _, device, stream = _value_views(arrays, None, axis, bins, on, ordered=True)
+    plan, nv, views, m, c, _, device, stream = _value_views(arrays, values, axis, bins, on, ordered=True)
     shape = tuple(int(s) for s in arrays[0].shape)
     ndim = len(shape)
     red = list(_range(ndim)) if axis is None or set(axis) == set(_range(ndim)) else sorted(axis)
@@ -2879,12 +2918,12 @@ def _order_rows(arrays, axis, bins, on):
         order = torch.empty((m, c), dtype=torch.int64, device=arrays[0].device)
         offsets = torch.empty((m, nb1), dtype=torch.int64, device=arrays[0].device)
         if m > 0:
-            plan.execute_group(nv, m, c, order.data_ptr(), offsets.data_ptr(), stream=stream)
+            run(plan, nv, m, c, order.data_ptr(), offsets.data_ptr(), stream)
     else:
         order, offsets = np.empty((m, c), np.int64), np.empty((m, nb1), np.int64)
         if m > 0:
             buf = _native.DeviceBuffer(device, (m * c + m * nb1) * 8)
-            plan.execute_group(nv, m, c, buf.ptr, buf.ptr + m * c * 8, stream=stream)
+            run(plan, nv, m, c, buf.ptr, buf.ptr + m * c * 8, stream)
             both = np.empty(m * c + m * nb1, np.int64)
             buf.download(both)  # (waits for the kernels: the views' keepalive copies are not needed after this)
             order[...] = both[:m * c].reshape(m, c)
@@ -2893,12 +2932,30 @@ def _order_rows(arrays, axis, bins, on):
     return order.reshape(kept + (c,)), offsets.reshape(kept + (nb1,))
 
 
-def _bin_order_block(*blocks, axis=None, bins=None):
-    """one dask block: a row's order and its offsets side by side, int64 [kept axes (reduced ones of extent 1), c + B + 1]"""
-    order, offsets, _ = bin_order(*blocks, bins=bins, axis=axis)
+def _packed_block(order, offsets, like, axis):
+    """one dask block of _packed_blockwise: a row's order and its offsets side by side, int64 [kept axes (reduced ones of extent
+    1), c + B + 1], for the block `like` of samples"""
     packed = np.concatenate([order, offsets], axis=-1)
-    shape = [1 if i in axis else int(s) for i, s in enumerate(blocks[0].shape)]
+    shape = [1 if i in axis else int(s) for i, s in enumerate(like.shape)]
     return packed.reshape(shape + [packed.shape[-1]])
+
+
+def _packed_blockwise(block_fn, all_arrays, drop_axes, cols, n_bins, **params):
+    """dask: one task per block over the kept axes, each `block_fn`'s _packed_block; (order, offsets), lazy"""
+    import dask.array as dsa
+
+    ndim = all_arrays[0].ndim
+    ind = tuple(_range(ndim))
+    packed = dsa.blockwise(block_fn, ind + (ndim,), *[x for a in all_arrays for x in (a, ind)], dtype=np.int64,
+                           new_axes={ndim: cols + n_bins + 1}, adjust_chunks={ax: (lambda extent: 1) for ax in drop_axes},
+                           axis=list(drop_axes), meta=np.array((), np.int64), **params)
+    packed = packed[tuple(0 if i in drop_axes else slice(None) for i in _range(ndim)) + (slice(None),)]
+    return packed[..., :cols], packed[..., cols:]
+
+
+def _bin_order_block(*blocks, axis=None, bins=None):
+    """one dask block (samples...)"""
+    return _packed_block(*bin_order(*blocks, bins=bins, axis=axis)[:2], blocks[0], axis)
 
 
 def bin_order(*args, bins=None, range=None, axis=None):
@@ -2928,83 +2985,27 @@ def bin_order(*args, bins=None, range=None, axis=None):
     Returns ``(order, offsets, bin_edges)``.  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on
     the current stream), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block over the kept axes: every
     reduced axis must then be a single chunk, and ``bins`` numpy arrays of edges."""
-    if not args:
-        raise TypeError("bin_order needs at least one array of samples")
-    for a in args:
-        dt = a.dtype if hasattr(a, "dtype") else np.asarray(a).dtype
-        if getattr(dt, "is_complex", False) or getattr(dt, "kind", "") == "c":
-            raise TypeError("complex samples have no order: bin_order takes real samples")
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, None, bins, range, axis, "bin_order", needs_values=False)
-    shape = tuple(int(s) for s in all_arrays[0].shape)
-    cols = int(np.prod([shape[ax] for ax in drop_axes], dtype=object)) if drop_axes else 1
-    if cols >= _ORDER_MAX_COLS:
-        raise NotImplementedError("bin_order takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
-                                  % (_ORDER_MAX_COLS, cols))
-    if backend == "dask":
-        if any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
-            raise ValueError("group orders of several chunks cannot be merged: rechunk the reduced axes of every input into "
-                             "one chunk (e.g. arr.rechunk({axis: -1}))")
-        import dask.array as dsa
-
-        ndim = len(shape)
-        n_bins = int(np.prod([len(b) - 1 for b in bins], dtype=object))
-        ind = tuple(_range(ndim))
-        packed = dsa.blockwise(_bin_order_block, ind + (ndim,), *[x for a in all_arrays for x in (a, ind)], dtype=np.int64,
-                               new_axes={ndim: cols + n_bins + 1}, adjust_chunks={ax: (lambda extent: 1) for ax in drop_axes},
-                               axis=list(drop_axes), bins=bins, meta=np.array((), np.int64))
-        packed = packed[tuple(0 if i in drop_axes else slice(None) for i in _range(ndim)) + (slice(None),)]
-        return packed[..., :cols], packed[..., cols:], bins
-    if backend == "numpy":
-        arrays, on = _upload_host(raw, None, bins), "device"
+    g = _grouped_call("bin_order", "group orders", args, None, bins, range, axis, needs_values=False)
+    bins, axis = g.bins, g.axis
+    if g.backend == "dask":
+        return _packed_blockwise(_bin_order_block, g.arrays, g.drop_axes, g.cols, g.n_bins, bins=bins) + (bins,)
+    if g.backend == "numpy":
+        arrays, on = _upload_host(g.raw, None, bins), "device"
     else:
-        arrays, on = all_arrays, backend
-    order, offsets = _order_rows(arrays, axis, bins, on)
-    return order, offsets, bins
+        arrays, on = g.arrays, g.backend
+
+    def run(plan, nv, m, c, order_ptr, offsets_ptr, stream):
+        plan.execute_group(nv, m, c, order_ptr, offsets_ptr, stream=stream)
+
+    return _order_offsets_rows(run, arrays, None, axis, bins, on) + (bins,)
 
 
 # ---------------------------------------------------------------------------------------------
 # bin_sort: the samples grouped by bin, sorted by value inside each bin
 # ---------------------------------------------------------------------------------------------
-_SORT_MAX_BINS = (1 << 32) - 1
-
-
-def _sort_rows(arrays, values, axis, bins, on, descending):
-    """xhist_plan_execute_sort over the `ordered` views of broadcast torch tensors or DeviceArrays and their values: (order
-    [kept axes, c], offsets [kept axes, B + 1]), int64, torch tensors on the samples' device (asynchronous on the current
-    stream) or numpy arrays.  The kernels are handed these blocks themselves."""
-    plan, nv, views, m, c, _, device, stream = _value_views(arrays, values, axis, bins, on, ordered=True)
-    n = len(arrays)
-    shape = tuple(int(s) for s in arrays[0].shape)
-    ndim = len(shape)
-    red = list(_range(ndim)) if axis is None or set(axis) == set(_range(ndim)) else sorted(axis)
-    kept = tuple(shape[i] for i in _range(ndim) if i not in red)
-    nb1 = plan.n_bins + 1
-    if on == "torch":
-        torch = _torch()
-        order = torch.empty((m, c), dtype=torch.int64, device=arrays[0].device)
-        offsets = torch.empty((m, nb1), dtype=torch.int64, device=arrays[0].device)
-        if m > 0:
-            plan.execute_sort(nv[:n], nv[n], m, c, descending, order.data_ptr(), offsets.data_ptr(), stream=stream)
-    else:
-        order, offsets = np.empty((m, c), np.int64), np.empty((m, nb1), np.int64)
-        if m > 0:
-            buf = _native.DeviceBuffer(device, (m * c + m * nb1) * 8)
-            plan.execute_sort(nv[:n], nv[n], m, c, descending, buf.ptr, buf.ptr + m * c * 8, stream=stream)
-            both = np.empty(m * c + m * nb1, np.int64)
-            buf.download(both)  # (waits for the kernels: the views' keepalive copies are not needed after this)
-            order[...] = both[:m * c].reshape(m, c)
-            offsets[...] = both[m * c:].reshape(m, nb1)
-    del views
-    return order.reshape(kept + (c,)), offsets.reshape(kept + (nb1,))
-
-
 def _bin_sort_block(*blocks, axis=None, bins=None, descending=False):
-    """one dask block (samples..., values): a row's order and its offsets side by side, int64 [kept axes (reduced ones of extent
-    1), c + B + 1]"""
-    order, offsets, _ = bin_sort(*blocks[:-1], values=blocks[-1], bins=bins, axis=axis, descending=descending)
-    packed = np.concatenate([order, offsets], axis=-1)
-    shape = [1 if i in axis else int(s) for i, s in enumerate(blocks[0].shape)]
-    return packed.reshape(shape + [packed.shape[-1]])
+    """one dask block (samples..., values)"""
+    return _packed_block(*bin_sort(*blocks[:-1], values=blocks[-1], bins=bins, axis=axis, descending=descending)[:2], blocks[0], axis)
 
 
 def bin_sort(*args, values, bins=None, range=None, axis=None, descending=False):
@@ -3040,43 +3041,19 @@ def bin_sort(*args, values, bins=None, range=None, axis=None, descending=False):
     Returns ``(order, offsets, bin_edges)``.  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on
     the current stream, no host synchronisation), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block
     over the kept axes: every reduced axis must then be a single chunk, and ``bins`` numpy arrays of edges."""
-    if not args:
-        raise TypeError("bin_sort needs at least one array of samples")
-    if values is None:
-        raise TypeError("bin_sort needs values")
-    descending = _check_flag("descending", descending)
-    for a in args:
-        dt = a.dtype if hasattr(a, "dtype") else np.asarray(a).dtype
-        if getattr(dt, "is_complex", False) or getattr(dt, "kind", "") == "c":
-            raise TypeError("complex samples have no order: bin_sort takes real samples")
-    if not hasattr(values, "dtype"):
-        values = np.asarray(values)
+    g = _grouped_call("bin_sort", "sorted orders", args, values, bins, range, axis, max_bins=_SORT_MAX_BINS,
+                      check=lambda: _check_flag("descending", descending))
+    bins, axis, descending = g.bins, g.axis, bool(descending)
+    if g.backend == "dask":
+        return _packed_blockwise(_bin_sort_block, g.arrays, g.drop_axes, g.cols, g.n_bins, bins=bins,
+                                 descending=descending) + (bins,)
     n = len(args)
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "bin_sort")
-    shape = tuple(int(s) for s in all_arrays[0].shape)
-    cols = int(np.prod([shape[ax] for ax in drop_axes], dtype=object)) if drop_axes else 1
-    if cols >= _ORDER_MAX_COLS:
-        raise NotImplementedError("bin_sort takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
-                                  % (_ORDER_MAX_COLS, cols))
-    n_bins = int(np.prod([max(len(b) - 1, 0) for b in bins], dtype=object))
-    if n_bins > _SORT_MAX_BINS:
-        raise NotImplementedError("bin_sort takes at most 2^32 - 1 = %d bins, got %d" % (_SORT_MAX_BINS, n_bins))
-    if backend == "dask":
-        if any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
-            raise ValueError("sorted orders of several chunks cannot be merged: rechunk the reduced axes of every input into "
-                             "one chunk (e.g. arr.rechunk({axis: -1}))")
-        import dask.array as dsa
+    arrays, on = _resident(g.backend, g.raw, g.arrays, n, bins)
 
-        ndim = len(shape)
-        ind = tuple(_range(ndim))
-        packed = dsa.blockwise(_bin_sort_block, ind + (ndim,), *[x for a in all_arrays for x in (a, ind)], dtype=np.int64,
-                               new_axes={ndim: cols + n_bins + 1}, adjust_chunks={ax: (lambda extent: 1) for ax in drop_axes},
-                               axis=list(drop_axes), bins=bins, descending=descending, meta=np.array((), np.int64))
-        packed = packed[tuple(0 if i in drop_axes else slice(None) for i in _range(ndim)) + (slice(None),)]
-        return packed[..., :cols], packed[..., cols:], bins
-    arrays, on = _resident(backend, raw, all_arrays, n, bins)
-    order, offsets = _sort_rows(arrays[:n], arrays[n], axis, bins, on, descending)
-    return order, offsets, bins
+    def run(plan, nv, m, c, order_ptr, offsets_ptr, stream):
+        plan.execute_sort(nv[:n], nv[n], m, c, descending, order_ptr, offsets_ptr, stream=stream)
+
+    return _order_offsets_rows(run, arrays[:n], arrays[n], axis, bins, on) + (bins,)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -3123,41 +3100,24 @@ def bin_rank(*args, values, bins=None, range=None, axis=None, method="average", 
     (asynchronous on the current stream, no host synchronisation), DeviceArray in -> numpy out, dask in -> a lazy dask array,
     one task per block over the kept axes: every reduced axis must then be a single chunk, and ``bins`` numpy arrays of
     edges."""
-    if not args:
-        raise TypeError("bin_rank needs at least one array of samples")
-    if values is None:
-        raise TypeError("bin_rank needs values")
-    if not isinstance(method, str) or method not in _native.RANK_METHODS:
-        raise ValueError("unknown rank method %r: one of %s" % (method, ", ".join(_native.RANK_METHODS)))
-    descending = _check_flag("descending", descending)
-    pct = _check_flag("pct", pct)
-    for a in args:
-        dt = a.dtype if hasattr(a, "dtype") else np.asarray(a).dtype
-        if getattr(dt, "is_complex", False) or getattr(dt, "kind", "") == "c":
-            raise TypeError("complex samples have no order: bin_rank takes real samples")
-    if not hasattr(values, "dtype"):
-        values = np.asarray(values)
+    def check():
+        if not isinstance(method, str) or method not in _native.RANK_METHODS:
+            raise ValueError("unknown rank method %r: one of %s" % (method, ", ".join(_native.RANK_METHODS)))
+        _check_flag("descending", descending)
+        _check_flag("pct", pct)
+
+    g = _grouped_call("bin_rank", "ranks", args, values, bins, range, axis, max_bins=_SORT_MAX_BINS, check=check)
+    bins, axis, descending, pct = g.bins, g.axis, bool(descending), bool(pct)
     n = len(args)
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "bin_rank")
-    shape = tuple(int(s) for s in all_arrays[0].shape)
-    cols = int(np.prod([shape[ax] for ax in drop_axes], dtype=object)) if drop_axes else 1
-    if cols >= _ORDER_MAX_COLS:
-        raise NotImplementedError("bin_rank takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
-                                  % (_ORDER_MAX_COLS, cols))
-    n_bins = int(np.prod([max(len(b) - 1, 0) for b in bins], dtype=object))
-    if n_bins > _SORT_MAX_BINS:
-        raise NotImplementedError("bin_rank takes at most 2^32 - 1 = %d bins, got %d" % (_SORT_MAX_BINS, n_bins))
-    if backend == "dask":
-        if any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
-            raise ValueError("ranks of several chunks cannot be merged: rechunk the reduced axes of every input into "
-                             "one chunk (e.g. arr.rechunk({axis: -1}))")
+    if g.backend == "dask":
         import dask.array as dsa
 
-        ind = tuple(_range(len(shape)))
-        out = dsa.blockwise(_bin_rank_block, ind, *[x for a in all_arrays for x in (a, ind)], dtype=np.float64, axis=list(drop_axes),
-                            bins=bins, method=method, descending=descending, pct=pct, meta=np.array((), np.float64))
+        ind = tuple(_range(g.arrays[0].ndim))
+        out = dsa.blockwise(_bin_rank_block, ind, *[x for a in g.arrays for x in (a, ind)], dtype=np.float64,
+                            axis=list(g.drop_axes), bins=bins, method=method, descending=descending, pct=pct,
+                            meta=np.array((), np.float64))
         return out, bins
-    arrays, on = _resident(backend, raw, all_arrays, n, bins)
+    arrays, on = _resident(g.backend, g.raw, g.arrays, n, bins)
     plan, nv, views, m, c, _, device, stream = _value_views(arrays[:n], arrays[n], axis, bins, on, ordered=True)
 
     def run(out_ptr):

@@ -1,12 +1,14 @@
 // xhist_group.hip — bin_order, the stable group-by of the samples by bin: the kernels of xhist_group.hip.h, instantiated here and
-// nowhere else, the geometry of their launches and the driver that orders them.
+// nowhere else, the geometry of their launches and the driver that orders them; and the three kernels of the engine's scan
+// (xhist_runs.hip.h), which bin_sort's passes reach through xhist_runs_scan.
 //
-// Instantiations (10):
+// Instantiations (13):
 //   group_count<W>, group_scatter<W>                        W 1 / 2 / 4 waves per workgroup     6
-//   group_totals, group_scan, group_bases, group_identity                                       4
+//   group_totals<WIDTH>, group_scan<WIDTH>, group_bases<WIDTH>   WIDTH 0 / 256 (bin_sort's passes)      6
+//   group_identity                                                                              1
 //
 // Step 0 is bin_index itself: xhist_map_run(k, XHIST_MAP_INDEX) writes the int64 keys of the call into a scratch block, so every
-// dtype, layout, compare domain and input count of bin_index is bin_order's.  Steps 1 to 3 (xhist_group.hip.h) read that block.
+// dtype, layout, compare domain and input count of bin_index is bin_order's.  The engine reads that block.
 //
 // Scratch of a call, from k.scratch:  n_rows * n_cols * 8 bytes of keys  +  n_rows * chunks * (B + 1) * 4 bytes of counters  +,
 // where a row is cut, n_rows * ceil(chunks / 64) * (B + 1) * 4 bytes of slice totals.
@@ -16,51 +18,82 @@
 
 #include <cstring>
 
+namespace xhist {
+
+// the engine's scan, for bin_order and for every pass of bin_sort: WIDTH 0 reads the width from the parameters, WIDTH 256 is
+// the radix pass's (and bin_order's with 255 bins), whose index arithmetic then folds as it did in the sort's own kernels
+template <int WIDTH>
+__global__ void __launch_bounds__(256) group_totals(const RunsParams p) {
+  runs_slices_body<false, WIDTH>(p);
+}
+template <int WIDTH>
+__global__ void __launch_bounds__(256) group_scan(const RunsParams p) {
+  runs_scan_body<WIDTH>(p);
+}
+template <int WIDTH>
+__global__ void __launch_bounds__(256) group_bases(const RunsParams p) {
+  runs_slices_body<true, WIDTH>(p);
+}
+
+}  // namespace xhist
+
 using namespace xhist;
 
 namespace {
 
-struct GroupGeometry {
-  int waves = 1, bits = 0;
-  int64_t chunks = 0, chunk = 0, slices = 0, max_rows = 0;
-  size_t lds_bytes = 0;
+// The launch geometry of a call, n_cols > 0 and (B + 1) * 4 <= pl.lds_max (runs_geometry's, with):
+//   waves     the most of 4 / 2 / 1 waves per workgroup whose counters fit the LDS a workgroup may take
+//   per_cu    what a CU's 160 KiB hold of such waves, at most 32
+//   a chunk of at least 2 * (B + 1) positions: the counter table then stays at or below a quarter of the key block's bytes, and
+//   zeroing, writing and scanning a chunk's counters stays below the work of its samples; a chunk is whole steps of 64
+//   positions, so a row of a few thousand samples in few bins is already cut
+struct GroupGeometry : RunsGeometry {
+  int waves, bits;
+  size_t lds_bytes;
 };
 
-// The launch geometry of a call, n_cols > 0 and (B + 1) * 4 <= pl.lds_max:
-//   waves     the most of 4 / 2 / 1 waves per workgroup whose counters fit the LDS a workgroup may take
-//   chunks    (a) rows that fill the device alone get one chunk each; (b) fewer rows are cut until cus * per_cu waves exist,
-//             per_cu = what a CU's 160 KiB hold of them, at most 32; (c) never so far that a chunk is shorter than 2 * (B + 1)
-//             positions: the counter table then stays at or below a quarter of the key block's bytes, and zeroing, writing and
-//             scanning a chunk's counters stays below the work of its samples; (d) a chunk is whole steps of 64 positions, so a
-//             row of a few thousand samples in few bins is already cut
-//   max_rows  rows per launch: workgroups below 2^31 and lanes below 2^32, for the (row, chunk) grid and for group_scan's rows
 static GroupGeometry group_geometry(const ValuesPlan& pl, int64_t n_rows, int64_t n_cols) {
-  GroupGeometry g;
   const int64_t nb1 = pl.n_bins + 1;
   const size_t wave_lds = (size_t)nb1 * 4;
-  g.waves = 4 * wave_lds <= pl.lds_max ? 4 : 2 * wave_lds <= pl.lds_max ? 2 : 1;
-  g.lds_bytes = g.waves * wave_lds;
-  while (((int64_t)1 << g.bits) < nb1) ++g.bits;
+  const int waves = 4 * wave_lds <= pl.lds_max ? 4 : 2 * wave_lds <= pl.lds_max ? 2 : 1;
+  int bits = 0;
+  while (((int64_t)1 << bits) < nb1) ++bits;
   const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(32, (int64_t)(160 * 1024 / wave_lds)));
-  const int64_t target = (int64_t)pl.cus * per_cu;
-  const int64_t steps = (n_cols + kGroupStep - 1) / kGroupStep;
-  int64_t want = std::min<int64_t>(steps, (target + n_rows - 1) / n_rows);
-  want = std::max<int64_t>(1, std::min<int64_t>(want, n_cols / (2 * nb1)));
-  g.chunk = ((n_cols + want - 1) / want + kGroupStep - 1) / kGroupStep * kGroupStep;
-  g.chunks = (n_cols + g.chunk - 1) / g.chunk;
-  g.slices = g.chunks == 1 ? 1 : (g.chunks + kGroupSlice - 1) / kGroupSlice;
-  const int64_t max_units = (((int64_t)1 << 32) - 1) / (kGroupStep * g.waves) * g.waves;
-  g.max_rows = std::max<int64_t>(1, std::min<int64_t>(max_units / g.chunks, (((int64_t)1 << 32) - 1) / 256));
-  return g;
+  return GroupGeometry{runs_geometry(pl.cus, per_cu, 2 * nb1, waves, 0, nb1, n_rows, n_cols), waves, bits, waves * wave_lds};
 }
-
-constexpr int64_t kSliceGrid = 4096;  // workgroups of group_totals / group_bases, 16 to a CU of 256: they walk their units grid-strided
 
 typedef void (*group_fn)(const GroupParams);
 static group_fn count_kernel(int w) { return w == 4 ? group_count<4> : w == 2 ? group_count<2> : group_count<1>; }
 static group_fn scatter_kernel(int w) { return w == 4 ? group_scatter<4> : w == 2 ? group_scatter<2> : group_scatter<1>; }
 
 }  // namespace
+
+int xhist_runs_scan(const ValuesCall& k, const RunsParams& p, const char* who) {
+  // the slices' workgroups: a unit per (row, tile of slots, slice), at most kRunsSliceGrid workgroups walking them
+  const int block = runs_scan_block(p.width);
+  const int64_t units = p.n_rows * ((p.width + block - 1) / block) * p.slices;
+  const unsigned slice_grid = (unsigned)std::min<int64_t>(units, kRunsSliceGrid);
+  typedef void (*scan_fn)(const RunsParams);
+  const bool fixed = p.width == 256;
+  const scan_fn totals = fixed ? group_totals<256> : group_totals<0>, scan = fixed ? group_scan<256> : group_scan<0>,
+                bases = fixed ? group_bases<256> : group_bases<0>;
+  char what[48];  // "<who>_<step> launch": only XH_VALUES_LAUNCH_CHECK reads it, after a failed launch
+  auto step = [&](const char* name) {
+    snprintf(what, sizeof what, "%s_%s launch", who, name);
+    return what;
+  };
+  if (p.chunks > 1) {
+    XH_VALUES_LAUNCH(totals, dim3(slice_grid), dim3(block), 0, k.stream, p);
+    XH_VALUES_LAUNCH_CHECK(k, step("totals"));
+  }
+  XH_VALUES_LAUNCH(scan, dim3((unsigned)p.n_rows), dim3(block), 0, k.stream, p);
+  XH_VALUES_LAUNCH_CHECK(k, step("scan"));
+  if (p.chunks > 1) {
+    XH_VALUES_LAUNCH(bases, dim3(slice_grid), dim3(block), 0, k.stream, p);
+    XH_VALUES_LAUNCH_CHECK(k, step("bases"));
+  }
+  return XHIST_OK;
+}
 
 int xhist_group_run(const ValuesCall& k, int64_t* out_order, int64_t* out_offsets) {
   const ValuesPlan& pl = k.pl;
@@ -91,41 +124,15 @@ int xhist_group_run(const ValuesCall& k, int64_t* out_order, int64_t* out_offset
   const group_fn count = count_kernel(g.waves), scatter = scatter_kernel(g.waves);
   if (int rc = allow_values_lds(k, count, g.lds_bytes, "group: setting the dynamic LDS size failed")) return rc;
   if (int rc = allow_values_lds(k, scatter, g.lds_bytes, "group: setting the dynamic LDS size failed")) return rc;
-  const int block = kGroupStep * g.waves;
-  const int scan_block = nb1 <= 64 ? 64 : 256;
+  const int block = kRunsStep * g.waves;
   for (int64_t r0 = 0; r0 < k.n_rows; r0 += g.max_rows) {
-    const int64_t nr = std::min(g.max_rows, k.n_rows - r0);
     GroupParams kp;
+    kp.runs = {cnt + r0 * g.chunks * nb1, part + r0 * g.slices * nb1, out_offsets + r0 * nb1, std::min(g.max_rows, k.n_rows - r0),
+               k.n_cols, g.chunk, (int32_t)g.chunks, (int32_t)g.slices, (int32_t)nb1};
     kp.keys = keys + r0 * k.n_cols;
-    kp.cnt = cnt + r0 * g.chunks * nb1;
-    kp.part = part + r0 * g.slices * nb1;
     kp.order = out_order + r0 * k.n_cols;
-    kp.offsets = out_offsets + r0 * nb1;
-    kp.n_rows = nr;
-    kp.n_cols = k.n_cols;
-    kp.chunk = g.chunk;
-    kp.chunks = (int32_t)g.chunks;
-    kp.slices = (int32_t)g.slices;
-    kp.nb1 = (int32_t)nb1;
     kp.bits = g.bits;
-    const unsigned grid = (unsigned)((nr * g.chunks + g.waves - 1) / g.waves);
-    XH_VALUES_LAUNCH(count, dim3(grid), dim3(block), g.lds_bytes, k.stream, kp);
-    XH_VALUES_LAUNCH_CHECK(k, "group_count launch");
-    // the slices' workgroups: a unit per (row, tile of bins, slice), at most kSliceGrid workgroups walking them
-    const int64_t units = nr * ((nb1 + scan_block - 1) / scan_block) * g.slices;
-    const unsigned slice_grid = (unsigned)std::min<int64_t>(units, kSliceGrid);
-    if (g.chunks > 1) {
-      XH_VALUES_LAUNCH(group_totals, dim3(slice_grid), dim3(scan_block), 0, k.stream, kp);
-      XH_VALUES_LAUNCH_CHECK(k, "group_totals launch");
-    }
-    XH_VALUES_LAUNCH(group_scan, dim3((unsigned)nr), dim3(scan_block), 0, k.stream, kp);
-    XH_VALUES_LAUNCH_CHECK(k, "group_scan launch");
-    if (g.chunks > 1) {
-      XH_VALUES_LAUNCH(group_bases, dim3(slice_grid), dim3(scan_block), 0, k.stream, kp);
-      XH_VALUES_LAUNCH_CHECK(k, "group_bases launch");
-    }
-    XH_VALUES_LAUNCH(scatter, dim3(grid), dim3(block), g.lds_bytes, k.stream, kp);
-    XH_VALUES_LAUNCH_CHECK(k, "group_scatter launch");
+    if (int rc = runs_pass(k, count, scatter, g.waves, g.lds_bytes, kp, "group")) return rc;
   }
   k.describe("group keys=%s bits=%d waves=%d block=%d chunks=%lld chunk=%lld lds_bytes=%zu rows_per_launch=%lld D=%d cmp=%d", family,
              g.bits, g.waves, block, (long long)g.chunks, (long long)g.chunk, g.lds_bytes, (long long)g.max_rows, pl.n_dims, values_cmp(pl));

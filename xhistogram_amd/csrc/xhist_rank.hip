@@ -4,7 +4,7 @@
 // Instantiations (6): rank_heads, rank_totals, rank_scan, rank_words, rank_bins, rank_apply.  The method and whether the call is
 // pct are kernel-uniform parameters, not template axes; rank_bins is launched only for pct.
 //
-// The driver runs bin_sort's own driver (xhist_sort_run_keys) into scratch order and offsets blocks and takes over the sorted bin
+// The driver runs bin_sort's own driver (xhist_sort_run) into scratch order and offsets blocks and takes over the sorted bin
 // keys its last pass wrote.  Then, per batch of the sort's rows_per_launch rows, a chain of plain launches: rank_heads,
 // rank_totals, rank_scan, rank_words, rank_bins (pct), rank_apply.  A call without columns or a plan without bins fills out with
 // NaN (bytes of all ones) and launches nothing.
@@ -58,7 +58,7 @@ int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, dou
   uint32_t* const part = scalars + 3 * nw;  // (every batch of rows uses its head)
 
   SortHandover hand = {nullptr, 0};
-  if (int rc = xhist_sort_run_keys(k, descending, order, offsets, &hand)) return rc;
+  if (int rc = xhist_sort_run(k, descending, order, offsets, &hand)) return rc;
   if (!hand.keys || hand.rows_per_launch < 1) return k.fail(XHIST_ERR_HIP, "internal: the sort handed over no bin keys");
   char sort_line[384];
   snprintf(sort_line, sizeof sort_line, "%s", k.desc);
@@ -66,13 +66,7 @@ int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, dou
   for (int64_t r0 = 0; r0 < k.n_rows; r0 += hand.rows_per_launch) {
     const int64_t nr = std::min(hand.rows_per_launch, k.n_rows - r0);
     RankParams rp;
-    rp.v_ptr = k.values->data;
-    rp.v_rs = k.values->row_stride;
-    rp.v_cs = k.values->col_stride;
-    rp.v_ir = k.values->inner_rows;
-    rp.v_os = k.values->outer_stride;
-    rp.row0 = r0;
-    rp.v_dt = k.values->dtype;
+    rp.v = values_read(*k.values, r0);
     rp.method = method;
     rp.order = order + r0 * k.n_cols;
     rp.keys = hand.keys + r0 * k.n_cols;

@@ -37,11 +37,10 @@ constexpr int kRankPer = 4;                          // consecutive words of one
 constexpr int kRankTile = 256 * kRankPer;            // words of one tile: what one workgroup of 256 threads scans at a time
 constexpr uint64_t kRankNaN = 0x7ff8000000000000ull;  // the quiet NaN of np.nan
 
-// one launch over rows [r0, r0 + n_rows) of the call: every pointer but v_ptr is pre-advanced to r0 (`row0` is r0 for the values)
+// one launch over rows [r0, r0 + n_rows) of the call: every pointer is pre-advanced to r0 (for the values, v.row0 is r0)
 struct RankParams {
-  const void* v_ptr;  // the values, an xhist_array as sort_keys reads it
-  int64_t v_rs, v_cs, v_ir, v_os, row0;
-  int32_t v_dt, method;
+  ValuesRead v;  // the values, as sort_keys reads them
+  int32_t method;
   const int64_t* order;    // [n_rows, n_cols]
   const uint64_t* keys;    // [n_rows, n_cols] the sorted bin keys
   const int64_t* offsets;  // [n_rows, nb + 1]
@@ -70,18 +69,18 @@ __device__ __forceinline__ void rank_heads_body(const RankParams& __restrict__ p
   for (int64_t u = (int64_t)blockIdx.x * kRankWaves + wave; u < units; u += (int64_t)gridDim.x * kRankWaves) {  // (uniform in a wave)
     const int64_t row = u / p.words, i = (u % p.words) * 64 + lane;
     const bool in = i < p.n_cols;
-    const int64_t r0 = row * p.n_cols, voff = row_offset(p.row0 + row, p.v_rs, p.v_ir, p.v_os);
+    const int64_t r0 = row * p.n_cols, voff = row_offset(p.v.row0 + row, p.v.rs, p.v.ir, p.v.os);
     uint64_t b = 0;
     double v = 0.0;
     if (in) {
       b = p.keys[r0 + i];
-      v = load_as<double>(p.v_ptr, p.v_dt, voff + p.order[r0 + i] * p.v_cs);
+      v = load_as<double>(p.v.ptr, p.v.dt, voff + p.order[r0 + i] * p.v.cs);
     }
     uint64_t bp = __shfl_up((unsigned long long)b, 1);
     double vp = __shfl_up(v, 1);
     if (lane == 0 && i > 0) {  // (i <= n_cols - 1 here: a word has at least one position)
       bp = p.keys[r0 + i - 1];
-      vp = load_as<double>(p.v_ptr, p.v_dt, voff + p.order[r0 + i - 1] * p.v_cs);
+      vp = load_as<double>(p.v.ptr, p.v.dt, voff + p.order[r0 + i - 1] * p.v.cs);
     }
     const bool head = in && (i == 0 || b != bp || !(v == vp));
     const uint64_t hw = __ballot(head), nw = __ballot(in && v != v);

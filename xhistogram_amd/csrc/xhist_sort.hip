@@ -1,8 +1,10 @@
 // xhist_sort.hip — bin_sort, the samples grouped by bin and sorted by value inside each bin: the kernels of xhist_sort.hip.h,
-// instantiated here and nowhere else, the geometry of their launches and the driver that orders them.
+// instantiated here and nowhere else, the constants of their launch geometry (runs_geometry's) and the driver that orders them.
 //
-// Instantiations (8): sort_keys, sort_gather, sort_count, sort_totals, sort_scan, sort_bases, sort_scatter, sort_offsets.
-// Whether a scatter writes keys, uint32 positions or the int64 order is a kernel-uniform parameter, not a template axis.
+// Instantiations (5): sort_keys, sort_gather, sort_count, sort_scatter, sort_offsets.  sort_count and sort_scatter are the count
+// and scatter bodies of xhist_runs.hip.h on SortParams; the scan between them is xhist_runs_scan, whose three kernels
+// xhist_group.hip defines.  Whether a scatter writes keys, uint32 positions or the int64 order is a kernel-uniform parameter,
+// not a template axis.
 //
 // Step 0 is bin_index itself: xhist_map_run(k, XHIST_MAP_INDEX) writes the int64 bin keys of the call into a scratch block, so
 // every dtype, layout, compare domain and input count of bin_index is bin_sort's.  Phase A sorts (value key, position) by the
@@ -24,33 +26,10 @@ using namespace xhist;
 
 namespace {
 
+constexpr int64_t kSortPerCu = 32;                   // waves the geometry wants on a CU
 constexpr int64_t kSortMinChunk = 512;               // positions of a chunk, unless the row is shorter
 constexpr int64_t kSortCounterBytes = 256ll << 20;   // counters of one launch's rows
-constexpr int64_t kSortSliceGrid = 4096;             // workgroups of sort_totals / sort_bases: they walk their units grid-strided
 constexpr int64_t kSortFlatGrid = 8192;              // workgroups of the grid-strided kernels over all samples
-
-struct SortGeometry {
-  int64_t chunks = 0, chunk = 0, slices = 0, max_rows = 0;
-};
-
-// The launch geometry of a call, n_cols > 0:
-//   chunks    rows that fill the device alone get one chunk each; fewer rows are cut until cus * 32 waves exist, never into
-//             chunks shorter than kSortMinChunk positions; a chunk is whole steps of 64 positions
-//   max_rows  rows per launch: workgroups below 2^31, lanes below 2^32, and counters within kSortCounterBytes
-static SortGeometry sort_geometry(int cus, int64_t n_rows, int64_t n_cols) {
-  SortGeometry g;
-  const int64_t target = (int64_t)cus * 32;
-  const int64_t steps = (n_cols + kSortStep - 1) / kSortStep;
-  int64_t want = std::min<int64_t>(steps, (target + n_rows - 1) / n_rows);
-  want = std::max<int64_t>(1, std::min<int64_t>(want, n_cols / kSortMinChunk));
-  g.chunk = ((n_cols + want - 1) / want + kSortStep - 1) / kSortStep * kSortStep;
-  g.chunks = (n_cols + g.chunk - 1) / g.chunk;
-  g.slices = g.chunks == 1 ? 1 : (g.chunks + kSortSlice - 1) / kSortSlice;
-  const int64_t max_units = (((int64_t)1 << 32) - 1) / (kSortStep * kSortWaves) * kSortWaves;
-  g.max_rows = std::min<int64_t>(max_units / g.chunks, (((int64_t)1 << 32) - 1) / 256);
-  g.max_rows = std::max<int64_t>(1, std::min<int64_t>(g.max_rows, kSortCounterBytes / (g.chunks * kSortDigits * 4)));
-  return g;
-}
 
 // The low bits of a value key that every value of the dtype shares up to the sign: a value of the dtype, taken as float64, has
 // that many zero bits at the bottom of its mantissa, so a key's low bits are all zeros (value >= +0.0 ascending) or all ones,
@@ -76,13 +55,9 @@ static const char* sort_dtype_name(int dt) {
 
 }  // namespace
 
-int xhist_sort_run(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets) {
-  return xhist_sort_run_keys(k, descending, out_order, out_offsets, nullptr);
-}
-
 // The driver.  `hand` (nullptr: nobody asks) receives what bin_rank builds on: the sorted bin keys the last pass of a call with
 // bins wrote beside the order (scratch of the call, alive until the call returns) and the rows of a launch.
-int xhist_sort_run_keys(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets, SortHandover* hand) {
+int xhist_sort_run(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets, SortHandover* hand) {
   const ValuesPlan& pl = k.pl;
   const int64_t nb = pl.n_bins, nb1 = nb + 1;
   if (k.n_cols >= ((int64_t)1 << 31))
@@ -104,7 +79,8 @@ int xhist_sort_run_keys(const ValuesCall& k, int descending, int64_t* out_order,
       return XHIST_OK;
     }
   }
-  const SortGeometry g = sort_geometry(pl.cus, k.n_rows, k.n_cols);
+  // (n_cols > 0.  Rows shorter than kSortMinChunk are one chunk; the counters of one launch stay within kSortCounterBytes.)
+  const RunsGeometry g = runs_geometry(pl.cus, kSortPerCu, kSortMinChunk, kSortWaves, kSortCounterBytes, kSortDigits, k.n_rows, k.n_cols);
   const int64_t n = k.n_rows * k.n_cols, launch_rows = std::min(g.max_rows, k.n_rows);
   int64_t* const binkeys = nb > 0 ? static_cast<int64_t*>(k.scratch((size_t)n * 8)) : nullptr;
   uint64_t* kbuf[2] = {static_cast<uint64_t*>(k.scratch((size_t)n * 8)), static_cast<uint64_t*>(k.scratch((size_t)n * 8))};
@@ -125,30 +101,14 @@ int xhist_sort_run_keys(const ValuesCall& k, int descending, int64_t* out_order,
   }
 
   const unsigned flat_grid = (unsigned)std::min<int64_t>(kSortFlatGrid, (n + 255) / 256);
-  {
-    SortKeyParams sp;
-    sp.v_ptr = k.values->data;
-    sp.v_rs = k.values->row_stride;
-    sp.v_cs = k.values->col_stride;
-    sp.v_ir = k.values->inner_rows;
-    sp.v_os = k.values->outer_stride;
-    sp.row0 = 0;
-    sp.v_dt = vdt;
-    sp.descending = descending ? 1 : 0;
-    sp.keys = kbuf[0];
-    sp.pos = pbuf[0];
-    sp.n_rows = k.n_rows;
-    sp.n_cols = k.n_cols;
-    XH_VALUES_LAUNCH(sort_keys, dim3(flat_grid), dim3(256), 0, k.stream, sp);
-    XH_VALUES_LAUNCH_CHECK(k, "sort_keys launch");
-  }
+  const SortKeyParams sp = {values_read(*k.values, 0), descending ? 1 : 0, kbuf[0], pbuf[0], k.n_rows, k.n_cols};
+  XH_VALUES_LAUNCH(sort_keys, dim3(flat_grid), dim3(256), 0, k.stream, sp);
+  XH_VALUES_LAUNCH_CHECK(k, "sort_keys launch");
 
-  const int block = kSortStep * kSortWaves;
+  const int block = kRunsStep * kSortWaves;
   const size_t lds = (size_t)kSortWaves * kSortDigits * 4;
   for (int64_t r0 = 0; r0 < k.n_rows; r0 += g.max_rows) {
     const int64_t nr = std::min(g.max_rows, k.n_rows - r0), at = r0 * k.n_cols;
-    const unsigned grid = (unsigned)((nr * g.chunks + kSortWaves - 1) / kSortWaves);
-    const unsigned slice_grid = (unsigned)std::min<int64_t>(nr * g.slices, kSortSliceGrid);
     const unsigned batch_grid = (unsigned)std::min<int64_t>(kSortFlatGrid, (nr * (k.n_cols + 1) + 255) / 256);
     int cur = 0;  // the buffers that hold the records
     for (int pass = 0; pass < value_passes + bin_passes; ++pass) {
@@ -161,33 +121,14 @@ int xhist_sort_run_keys(const ValuesCall& k, int descending, int64_t* out_order,
         XH_VALUES_LAUNCH_CHECK(k, "sort_gather launch");
       }
       SortParams kp;
+      kp.runs = {cnt, part, nullptr, nr, k.n_cols, g.chunk, (int32_t)g.chunks, (int32_t)g.slices, kSortDigits};
       kp.kin = kbuf[cur] + at;
       kp.pin = pbuf[cur] + at;
       kp.kout = (last ? bin_passes > 0 : !last_of_a) ? kbuf[cur ^ 1] + at : nullptr;
       kp.pout = last ? nullptr : pbuf[cur ^ 1] + at;
       kp.order = last ? out_order + at : nullptr;
-      kp.cnt = cnt;
-      kp.part = part;
-      kp.n_rows = nr;
-      kp.n_cols = k.n_cols;
-      kp.chunk = g.chunk;
-      kp.chunks = (int32_t)g.chunks;
-      kp.slices = (int32_t)g.slices;
       kp.shift = 8 * (phase_b ? pass - value_passes : first_digit + pass);
-      XH_VALUES_LAUNCH(sort_count, dim3(grid), dim3(block), lds, k.stream, kp);
-      XH_VALUES_LAUNCH_CHECK(k, "sort_count launch");
-      if (g.chunks > 1) {
-        XH_VALUES_LAUNCH(sort_totals, dim3(slice_grid), dim3(256), 0, k.stream, kp);
-        XH_VALUES_LAUNCH_CHECK(k, "sort_totals launch");
-      }
-      XH_VALUES_LAUNCH(sort_scan, dim3((unsigned)nr), dim3(256), 0, k.stream, kp);
-      XH_VALUES_LAUNCH_CHECK(k, "sort_scan launch");
-      if (g.chunks > 1) {
-        XH_VALUES_LAUNCH(sort_bases, dim3(slice_grid), dim3(256), 0, k.stream, kp);
-        XH_VALUES_LAUNCH_CHECK(k, "sort_bases launch");
-      }
-      XH_VALUES_LAUNCH(sort_scatter, dim3(grid), dim3(block), lds, k.stream, kp);
-      XH_VALUES_LAUNCH_CHECK(k, "sort_scatter launch");
+      if (int rc = runs_pass(k, sort_count, sort_scatter, kSortWaves, lds, kp, "sort")) return rc;
       cur ^= 1;
     }
     if (bin_passes > 0) {

@@ -55,6 +55,17 @@ struct CovWParams : CovParams {
   int32_t y_dt;
 };
 
+// The values of a call as a kernel outside the skeletons reads them (sort_keys, rank_heads): the call's xhist_array, advanced to
+// no row.  Element (r, c) of a launch whose first row is `row0` is ptr[row_offset(row0 + r, rs, ir, os) + c * cs], dtype dt.
+struct ValuesRead {
+  const void* ptr;
+  int64_t rs, cs, ir, os, row0;
+  int32_t dt;
+};
+static inline ValuesRead values_read(const xhist_array& a, int64_t row0) {
+  return ValuesRead{a.data, a.row_stride, a.col_stride, a.inner_rows, a.outer_stride, row0, a.dtype};
+}
+
 // An accumulator policy `Acc` is one statistic's (one pass's) use of the slots:
 //   slot_t                    one bin's LDS slot
 //   kCopies                   the fast family keeps 2^p.copies_log2 copies of every slot, lane i adding into copy

@@ -12,6 +12,7 @@
 
 namespace xhist {
 struct DimTable;
+struct RunsParams;
 }
 
 // What the units need of a plan (filled by xhist_capi.hip's values_plan()): the compare domain, the native (start, cnt)
@@ -112,25 +113,29 @@ int xhist_map_run(const ValuesCall& k, int op, const double* centre, const doubl
 // bins, which the statistics' front does not launch over (offsets [n_rows, 1] of zeros, every row's order its positions).
 int xhist_group_run(const ValuesCall& k, int64_t* out_order, int64_t* out_offsets);
 int xhist_group_no_bins(int64_t n_rows, int64_t n_cols, int64_t* out_order, int64_t* out_offsets, hipStream_t stream);
+// xhist_group.hip: the scan of the count / scan / scatter engine (xhist_runs.hip.h) for one batch of rows, whose kernels that unit
+// alone defines: totals where a row is cut into several chunks, scan, bases where it is cut.  It turns the counters the count
+// kernel wrote into the bases the scatter kernel reads, and writes p.offsets where that is not nullptr.  A width of 256 runs the
+// instantiations with that width fixed.  `who` ("group", "sort") names the caller in the message of a failed launch.
+int xhist_runs_scan(const ValuesCall& k, const xhist::RunsParams& p, const char* who);
 
 // xhist_sort.hip: bin_sort, a row's samples grouped by bin and sorted by value inside each bin (k.values the values; `descending`
 // nonzero: largest first, NaN still last).  The outputs are bin_order's; every element of both is written exactly once.  A
 // stable radix sort on 8-bit digits of (value key, position), then of the gathered bin keys: 32 bytes of scratch per sample
 // from k.alloc.  Unlike the other drivers it also takes a plan without bins (n_bins 0: the whole row sorted by value, one
 // offset of 0 per row).  XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for n_bins + 1 > 2^32, before any launch.
-int xhist_sort_run(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets);
-// what bin_rank takes over from the sort (`hand` nullptr: xhist_sort_run itself): the sorted bin keys [n_rows, n_cols], each in
-// [0, n_bins], in scratch of the call (nullptr for a plan without bins), and the rows of one launch
+// `hand` (nullptr: nobody asks) receives what bin_rank takes over from the sort: the sorted bin keys [n_rows, n_cols], each in
+// [0, n_bins], in scratch of the call (nullptr for a plan without bins), and the rows of one launch.
 struct SortHandover {
   const uint64_t* keys;
   int64_t rows_per_launch;
 };
-int xhist_sort_run_keys(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets, SortHandover* hand);
+int xhist_sort_run(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets, SortHandover* hand = nullptr);
 
 // xhist_rank.hip: bin_rank, the rank of every sample's value among the non-NaN values of its bin (k.values the values; method
 // an XHIST_RANK_* code; `descending` nonzero: largest first; `pct` nonzero: divided by the bin's count of non-NaN values, by its
 // distinct values for XHIST_RANK_DENSE).  out is a dense float64 [n_rows, n_cols] block in position order, every element
-// written exactly once; NaN for a sample that is not counted and for a NaN value.  It runs xhist_sort_run_keys into scratch and
+// written exactly once; NaN for a sample that is not counted and for a NaN value.  It runs xhist_sort_run into scratch and
 // six kernels over the sorted order.  Scratch from k.alloc, one block on top of the sort's 32 bytes per sample: 8 bytes per
 // sample of order, n_rows * (n_bins + 1) * 8 bytes of offsets, 28 bytes per 64 samples of head and NaN words with their three
 // uint32 scalars, 12 bytes per 65536 samples of tile scalars, and n_rows * n_bins * 8 bytes of divisors when pct.  Like the
