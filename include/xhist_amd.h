@@ -442,6 +442,41 @@ typedef enum {
 int xhist_plan_execute_rank(xhist_plan* plan, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
                             int64_t n_cols, int method, int descending, int pct, double* out, int mem_kind, void* stream);
 
+/* histogram_mode (added within ABI v11: a new entry, every earlier one unchanged): per bin the most frequent value, how often it
+ * occurs and how many different values there are: the statistic of categorical values.  Per row r and bin b, with S the columns
+ * of bin b that xhist_plan_execute counts and whose value, taken as float64, is not NaN, and equality of values decided by IEEE
+ * == (so -0.0 and +0.0 are one value):
+ *   out_count[r, b]      = |S|, xhist_plan_execute_mean_var's count bit for bit
+ *   out_nunique[r, b]    = the number of distinct values of S
+ *   out_mode_count[r, b] = the largest number of columns of S that hold one value
+ *   out_mode[r, b]       = that value; among several values that occur that often the smallest.  Its bits are those of the
+ *                          first column of the value in xhist_plan_execute_sort's ascending order on the same arguments: where
+ *                          the value is a zero that S holds with both signs, -0.0.
+ *   An empty bin (|S| == 0, a bin of only NaN values included) gets 0, 0, 0 and NaN (0x7ff8000000000000).
+ *   The four outputs are contiguous DEVICE blocks [n_rows, B], int64 but out_mode, which is float64; every element of each is
+ *   written exactly once and nothing outside them.  A NULL output is XHIST_ERR_INVALID.
+ *   values: any real dtype, any strides.  n_cols must be below 2^31 and B + 1 at most 2^32: XHIST_ERR_UNSUPPORTED otherwise,
+ *   before any launch.
+ *   The call is xhist_plan_execute_sort into scratch, the head and NaN bits and the scan of the head words of
+ *   xhist_plan_execute_rank, and two kernels over them.  In the sorted order the columns of one value of one bin are a run
+ *   between two head bits.  One wave per 64 positions packs every run that starts there as (length << 32 | 2^32 - 1 - start),
+ *   takes the maximum per bin across its lanes and issues at most one 64-bit atomic maximum per (64 positions, bin), and only
+ *   where it improves on the slot it read first; the maximum of integers does not depend on the order of arrival.  One thread
+ *   per (row, bin) then finds the end of the bin's non-NaN values by bisection, takes the distinct values as a difference of two
+ *   head counts and gathers the one value at the winning run's start.  No kernel waits for another workgroup.  A call without
+ *   columns launches the second kernel alone.
+ *   Scratch of the call, on top of xhist_plan_execute_sort's: xhist_plan_execute_rank's without the divisors, that is 8 bytes
+ *   per sample of order, n_rows * (B + 1) * 8 bytes of offsets, 28 bytes per 64 samples of a row and 12 bytes per 65536 samples
+ *   of a row; XHIST_ERR_NOMEM where it cannot be had.  The slots of the atomic maximum are the out_mode_count block itself,
+ *   zeroed by the call and finished in place.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Exact and deterministic.  Asynchronous on `stream`.
+ *   xhist_plan_describe then reads "mode words=.. rows_per_launch=.. | " followed by xhist_plan_execute_sort's own line ("none"
+ *   for a call without columns): the words of 64 positions of a row and the rows of one launch. */
+int xhist_plan_execute_mode(xhist_plan* plan, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+                            int64_t* out_count, int64_t* out_nunique, double* out_mode, int64_t* out_mode_count, int mem_kind,
+                            void* stream);
+
 /* One-shot form of the two calls above with an internal plan cache keyed on (device, edges). */
 int xhist_bincount_rows(int device, int n_inputs, const xhist_array* samples,
                         const xhist_array* weights, int64_t n_rows, int64_t n_cols,

@@ -75,7 +75,7 @@ EXPORTS = (
     "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
     "xhist_plan_execute_quantile_weighted", "xhist_plan_execute_cov", "xhist_plan_execute_cov_weighted",
     "xhist_plan_execute_skew_kurt", "xhist_plan_execute_skew_kurt_weighted", "xhist_plan_execute_argextrema",
-    "xhist_plan_execute_map", "xhist_plan_execute_group", "xhist_plan_execute_sort", "xhist_plan_execute_rank", "xhist_plan_execute_sum", "xhist_debug_sum_host", "xhist_debug_sum_round",
+    "xhist_plan_execute_map", "xhist_plan_execute_group", "xhist_plan_execute_sort", "xhist_plan_execute_rank", "xhist_plan_execute_mode", "xhist_plan_execute_sum", "xhist_debug_sum_host", "xhist_debug_sum_round",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -146,6 +146,10 @@ def load():
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
         ]
         lib.xhist_plan_execute_sum.argtypes = lib.xhist_plan_execute_argextrema.argtypes
+        lib.xhist_plan_execute_mode.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_int, C.c_void_p,
+        ]
         lib.xhist_debug_sum_host.argtypes = [C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
         lib.xhist_debug_sum_round.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double)]
         lib.xhist_plan_execute_mean_var.argtypes = [
@@ -424,6 +428,15 @@ class Plan:
         (xhist_plan_execute_sum); fewer than 2^31 columns"""
         self._execute_values("xhist_plan_execute_sum", sample_views, (value_view,), n_rows, n_cols, (out_count_ptr, out_total_ptr),
                              stream=stream)
+
+    def execute_mode(self, sample_views, value_view, n_rows, n_cols, out_count_ptr, out_nunique_ptr, out_mode_ptr, out_mode_count_ptr,
+                     stream=0):
+        """per bin the number of non-NaN values (int64), the number of distinct ones (int64), the most frequent value (float64,
+        the smallest of the most frequent ones; NaN where no value arrived) and how often it occurs (int64) of device-resident
+        views, into device buffers of [n_rows, bins] each, asynchronous on `stream` (xhist_plan_execute_mode); fewer than 2^31
+        columns"""
+        self._execute_values("xhist_plan_execute_mode", sample_views, (value_view,), n_rows, n_cols,
+                             (out_count_ptr, out_nunique_ptr, out_mode_ptr, out_mode_count_ptr), stream=stream)
 
     def execute_map(self, sample_views, value_view, n_rows, n_cols, op, centre_ptr, scale_ptr, out_ptr, stream=0):
         """one 8-byte element per sample of device-resident views into the dense row-major [n_rows, n_cols] device block at

@@ -35,7 +35,8 @@ _range = range
 
 __all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
            "histogram_weighted_quantile", "histogram_cov", "histogram_weighted_cov", "combine_weighted_cov",
-           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema", "histogram_sum", "bin_order", "bin_sort", "bin_rank"]
+           "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema", "histogram_sum", "bin_order", "bin_sort", "bin_rank",
+           "histogram_mode"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1916,15 +1917,18 @@ def _drop_axes(a, axes, backend):
     return a.squeeze(axes)
 
 
-def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, *extras, weights=None, **params):
+def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, *extras, weights=None, check=None, **params):
     """the backends of the per-bin statistic _VALUE_STATS[stat] of values: (backend, the outputs with the shape ``histogram``
     gives, bin edges, reduced axes).  `extras` are the arrays it reads after the values, in its order, `weights` (None: not
     given) the last of them, and `params` its per-call parameters.  The outputs are a list of k arrays; the quantiles stay one
     array behind their q axis.  dask: lazy arrays, the partials merged by the statistic's dask step and the last step by
-    `aggregate`."""
+    `aggregate`.  `check(shape, drop_axes, bins)` (None: none) is the caller's own refusal by the broadcast shape and the edges
+    alone, made before any device work on the samples."""
     backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, *extras, weights)
     n_inputs = len(args)
     st = _VALUE_STATS[stat]
+    if check is not None:
+        check(all_arrays[0].shape, drop_axes, bins)
     k = st.k or len(params["q"])
     if st.max_cols is not None:
         shape = all_arrays[0].shape
@@ -2519,6 +2523,8 @@ _VALUE_STATS = {
     # one output per element of the call's q, in one block
     "quantile": _ValueStat(None, (), "execute_quantile", (0,), 0, None, ("q", "code"), noun="exact quantiles"),
     "quantile_w": _ValueStat(None, (), "execute_quantile_weighted", (0,), 1, None, ("q",), noun="exact quantiles"),
+    # (count, nunique, mode, mode_count): the runs of several chunks are not kept, so there is no merge
+    "mode": _ValueStat(4, (0, 1, 3), "execute_mode", (0, 1, 2, 3), 0, None, noun="modes"),
 }
 
 
@@ -2859,6 +2865,51 @@ def histogram_anomaly(*args, values, bins=None, range=None, axis=None, weights=N
 
 
 # ---------------------------------------------------------------------------------------------
+# histogram_mode: per-bin mode, its count and the number of distinct values
+# ---------------------------------------------------------------------------------------------
+def histogram_mode(*args, values, bins=None, range=None, axis=None, weights=None, block_size="auto"):
+    """Per-bin most frequent value of ``values``, how often it occurs and how many different values there are, computed on an
+    MI355X: the statistic of categorical values (water-mass class, land-cover type, cloud regime, a quality flag, any rounded
+    field), for which a mean is meaningless.  ``scipy.stats.mode`` or ``np.unique`` on each of ``np.split(v[order], offsets)``
+    on the host, ``pandas.Series.groupby(bin).agg(["nunique", mode])``.
+
+    ``args``, ``bins``, ``range``, ``axis`` and ``values`` (any real dtype, taken as float64; a complex dtype is a
+    ``TypeError``), the samples that count, the compare domains, the joint bins of up to 8 inputs, the estimator names and the
+    broadcasting are those of :func:`histogram_extrema`.  NaN values are ignored (``nan_policy="omit"``), and two values are one
+    where IEEE ``==`` says so: ``-0.0`` and ``+0.0`` are one value.  ``block_size`` is accepted and changes nothing.
+
+    Per (kept index, bin), over the ``n`` non-NaN values of the counted samples:
+
+    * ``count`` is ``n``, int64: :func:`histogram_mean_var`'s ``count`` bit for bit;
+    * ``nunique`` is the number of distinct values, int64, 0 for an empty bin;
+    * ``mode_count`` is the largest number of samples that hold one value, int64, 0 for an empty bin;
+    * ``mode`` is that value, float64.  Among several values that occur ``mode_count`` times the smallest wins
+      (``scipy.stats.mode``, ``pandas.Series.mode()[0]``).  It is NaN (``0x7ff8000000000000``) where ``n == 0``.  Its bits are
+      those of the value's first sample in :func:`bin_sort`'s ascending order: a zero that the bin holds with both signs is
+      reported as ``-0.0``.
+
+    So ``nunique`` is the largest ``bin_rank(method="dense")`` of the bin, ``mode_count`` the largest ``max - min + 1`` over its
+    ``"max"`` and ``"min"`` ranks, and ``mode == vmin`` of :func:`histogram_extrema` where every value of the bin is distinct.
+    Exact and deterministic: the samples are sorted as :func:`bin_sort` sorts them, a value's samples are then one run, and the
+    longest run of a bin is an integer maximum that does not depend on the order of arrival.
+
+    ``weights`` is refused (``NotImplementedError``; a weighted mode is another statistic), there is no ``descending``.  A
+    reduced extent of 2^31 samples or more per output row, and ``B + 1 > 2**32`` bins, raise ``NotImplementedError``.  All of
+    these, and complex values, are refused before any device work.
+
+    Returns ``(count, nunique, mode, mode_count, bin_edges)`` with the shape ``histogram`` gives (kept axes, then bin axes).
+    numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the current stream), DeviceArray in ->
+    numpy out, dask in -> lazy dask arrays, one task per block: every reduced axis must then be a single chunk (the modes of
+    several chunks are not merged)."""
+    if weights is not None:
+        raise NotImplementedError("histogram_mode does not take weights: the value with the largest sum of weights is another "
+                                  "statistic")
+    _, (count, nunique, mode, mode_count), bins, _ = _value_stat("mode", args, values, bins, range, axis, "histogram_mode",
+                                                                check=partial(_check_grouped_sizes, "histogram_mode", _SORT_MAX_BINS))
+    return count, nunique, mode, mode_count, bins
+
+
+# ---------------------------------------------------------------------------------------------
 # bin_order, bin_sort and bin_rank: the samples grouped by bin, their one call path
 # ---------------------------------------------------------------------------------------------
 _ORDER_MAX_COLS = 1 << 31
@@ -2867,6 +2918,20 @@ _SORT_MAX_BINS = (1 << 32) - 1
 
 # what _grouped_call returns: _values_call's six, then the samples per output row and the number of bins
 _Grouped = namedtuple("_Grouped", "backend arrays raw bins axis drop_axes cols n_bins")
+
+
+def _check_grouped_sizes(name, max_bins, shape, drop_axes, bins):
+    """NotImplementedError for 2^31 samples or more per output row and for more than `max_bins` bins (None: no bound here), the
+    limits of the sorted order, from the broadcast shape and the edges alone: (samples per output row, number of bins)"""
+    shape = tuple(int(s) for s in shape)
+    cols = int(np.prod([shape[ax] for ax in drop_axes], dtype=object)) if drop_axes else 1
+    if cols >= _ORDER_MAX_COLS:
+        raise NotImplementedError("%s takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
+                                  % (name, _ORDER_MAX_COLS, cols))
+    n_bins = int(np.prod([max(len(b) - 1, 0) for b in bins], dtype=object))
+    if max_bins is not None and n_bins > max_bins:
+        raise NotImplementedError("%s takes at most 2^32 - 1 = %d bins, got %d" % (name, max_bins, n_bins))
+    return cols, n_bins
 
 
 def _grouped_call(name, noun, args, values, bins, range, axis, needs_values=True, max_bins=None, check=None):
@@ -2888,14 +2953,7 @@ def _grouped_call(name, noun, args, values, bins, range, axis, needs_values=True
         values = np.asarray(values)
     call = _values_call(args, values, bins, range, axis, name, needs_values=needs_values)
     backend, all_arrays, _, bins, _, drop_axes = call
-    shape = tuple(int(s) for s in all_arrays[0].shape)
-    cols = int(np.prod([shape[ax] for ax in drop_axes], dtype=object)) if drop_axes else 1
-    if cols >= _ORDER_MAX_COLS:
-        raise NotImplementedError("%s takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
-                                  % (name, _ORDER_MAX_COLS, cols))
-    n_bins = int(np.prod([max(len(b) - 1, 0) for b in bins], dtype=object))
-    if max_bins is not None and n_bins > max_bins:
-        raise NotImplementedError("%s takes at most 2^32 - 1 = %d bins, got %d" % (name, max_bins, n_bins))
+    cols, n_bins = _check_grouped_sizes(name, max_bins, all_arrays[0].shape, drop_axes, bins)
     if backend == "dask" and any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
         raise ValueError("%s of several chunks cannot be merged: rechunk the reduced axes of every input into "
                          "one chunk (e.g. arr.rechunk({axis: -1}))" % noun)

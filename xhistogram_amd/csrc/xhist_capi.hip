@@ -506,6 +506,22 @@ extern "C" int xhist_plan_execute_rank(xhist_plan* p, const xhist_array* samples
   return XHIST_OK;
 }
 
+// histogram_mode (xhist_rank.hip): the statistics' front, four [n_rows, n_bins] planes.  The sort's two size limits are refused
+// here as well, before the front looks at anything else.
+extern "C" int xhist_plan_execute_mode(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+                                       int64_t* out_count, int64_t* out_nunique, double* out_mode, int64_t* out_mode_count, int mem_kind,
+                                       void* stream) {
+  if (p && n_cols >= ((int64_t)1 << 31))
+    return fail(XHIST_ERR_UNSUPPORTED, "histogram_mode takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), "
+                                       "got %lld", (long long)n_cols);
+  if (p && p->n_bins + 1 > ((int64_t)1 << 32))
+    return fail(XHIST_ERR_UNSUPPORTED, "histogram_mode takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
+                (long long)p->n_bins);
+  return execute_values(p, "xhist_plan_execute_mode", samples, values, nullptr, nullptr, n_rows, n_cols, out_mode,
+                        out_count && out_nunique && out_mode_count, "out_count / out_nunique / out_mode_count is NULL", mem_kind, stream,
+                        [&](const ValuesCall& k) { return xhist_mode_run(k, out_count, out_nunique, out_mode, out_mode_count); });
+}
+
 // ------------------------------------------------------------------------------------------
 // one-shot form with a plan cache
 // ------------------------------------------------------------------------------------------

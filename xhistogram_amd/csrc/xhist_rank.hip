@@ -1,18 +1,21 @@
-// xhist_rank.hip — bin_rank, the rank of every sample's value among the non-NaN values of its bin: the kernels of
-// xhist_rank.hip.h, instantiated here and nowhere else, and the driver that orders them behind the sort.
+// xhist_rank.hip — bin_rank, the rank of every sample's value among the non-NaN values of its bin, and histogram_mode, each bin's
+// most frequent value: the kernels of xhist_rank.hip.h and xhist_mode.hip.h, instantiated here and nowhere else, and the two
+// drivers that order them behind the sort.
 //
-// Instantiations (6): rank_heads, rank_totals, rank_scan, rank_words, rank_bins, rank_apply.  The method and whether the call is
-// pct are kernel-uniform parameters, not template axes; rank_bins is launched only for pct.
+// Instantiations (8): rank_heads, rank_totals, rank_scan, rank_words, rank_bins, rank_apply, mode_runs, mode_finish.  The method
+// and whether the call is pct are kernel-uniform parameters, not template axes; rank_bins is launched only for pct.
 //
-// The driver runs bin_sort's own driver (xhist_sort_run) into scratch order and offsets blocks and takes over the sorted bin
+// Both drivers run bin_sort's own driver (xhist_sort_run) into scratch order and offsets blocks and take over the sorted bin
 // keys its last pass wrote.  Then, per batch of the sort's rows_per_launch rows, a chain of plain launches: rank_heads,
-// rank_totals, rank_scan, rank_words, rank_bins (pct), rank_apply.  A call without columns or a plan without bins fills out with
-// NaN (bytes of all ones) and launches nothing.
+// rank_totals, rank_scan, rank_words (sorted_domain_run, which both share), and then rank_bins (pct), rank_apply for bin_rank, a
+// fill of the slots with 0, mode_runs, mode_finish for histogram_mode.  A bin_rank call without columns or a plan without bins
+// fills out with NaN (bytes of all ones) and launches nothing; a histogram_mode call without columns launches mode_finish alone.
 //
 // Scratch of a call, from k.scratch, on top of the sort's 32 bytes per sample: 8 bytes per sample of order, n_rows * (B + 1) * 8
 // bytes of offsets, per 64 samples of a row 28 bytes (the head word, the NaN word, and before / last / next), per 65536 samples
-// of a row 12 bytes more (a tile's three scalars), and n_rows * B * 8 bytes of divisors when pct.
-#include "xhist_rank.hip.h"
+// of a row 12 bytes more (a tile's three scalars), and n_rows * B * 8 bytes of divisors when pct.  histogram_mode takes the same
+// without the divisors and nothing more: its slots are the out_mode_count block.
+#include "xhist_mode.hip.h"
 
 using namespace xhist;
 
@@ -25,30 +28,24 @@ static const char* rank_method_name(int method) {
   return method >= XHIST_RANK_AVERAGE && method <= XHIST_RANK_ORDINAL ? names[method] : "?";
 }
 
-}  // namespace
+// what sorted_domain_run tells its caller about the call: the words of a row, the rows of one launch, the sort's describe() line
+struct SortedDomain {
+  int64_t words, rows_per_launch;
+  char sort_line[384];
+};
 
-int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, double* out) {
-  const ValuesPlan& pl = k.pl;
-  const int64_t nb = pl.n_bins, nb1 = nb + 1;
-  if (method < XHIST_RANK_AVERAGE || method > XHIST_RANK_ORDINAL) return k.fail(XHIST_ERR_INVALID, "unknown rank method %d", method);
-  if (k.n_cols >= ((int64_t)1 << 31))
-    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_rank takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), "
-                                         "got %lld", (long long)k.n_cols);
-  if (nb1 > ((int64_t)1 << 32))
-    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_rank takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
-                  (long long)nb);
-  const int64_t n = k.n_rows * k.n_cols;
-  if (k.n_cols == 0 || nb == 0) {
-    if (n > 0 && hipMemsetAsync(out, 0xff, (size_t)n * 8, k.stream) != hipSuccess) return k.fail(XHIST_ERR_HIP, "rank: filling out with NaN failed");
-    k.describe("rank method=%s pct=%d descending=%d words=0 rows_per_launch=0 | none", rank_method_name(method), pct ? 1 : 0,
-               descending ? 1 : 0);
-    return XHIST_OK;
-  }
+// What bin_rank and histogram_mode share, for a call with columns and bins: one scratch block for all of it (a call's scope
+// holds few blocks, and the sort takes seven; the 8-byte parts first, `pct`: with the block of divisors), the sort into it, and
+// per batch of the sort's rows_per_launch rows the four launches that build the sorted domain; then tail(rp, r0, nr, word_grid),
+// the caller's own launches over that batch, which returns a status.
+template <class Tail>
+static int sorted_domain_run(const ValuesCall& k, const char* who, int method, int descending, bool pct, double* out, SortedDomain& dom,
+                             Tail tail) {
+  const int64_t nb = k.pl.n_bins, nb1 = nb + 1, n = k.n_rows * k.n_cols;
   const int64_t words = (k.n_cols + 63) / 64, nw = k.n_rows * words, tiles = (words + kRankTile - 1) / kRankTile;
-  // one block for all of it (a call's scope holds few blocks, and the sort takes seven): the 8-byte parts first
   const size_t n_off = (size_t)(k.n_rows * nb1), n_div = pct ? (size_t)(k.n_rows * nb) : 0, n_part = (size_t)(k.n_rows * tiles) * 3;
   char* const block = static_cast<char*>(k.scratch(((size_t)n + n_off + 2 * (size_t)nw + n_div) * 8 + ((size_t)nw * 3 + n_part) * 4));
-  if (!block) return k.fail(XHIST_ERR_NOMEM, "allocation of the rank scratch block failed");
+  if (!block) return k.fail(XHIST_ERR_NOMEM, "allocation of the %s scratch block failed", who);
   int64_t* const order = reinterpret_cast<int64_t*>(block);
   int64_t* const offsets = order + n;
   uint64_t* const headw = reinterpret_cast<uint64_t*>(offsets + n_off);
@@ -60,8 +57,9 @@ int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, dou
   SortHandover hand = {nullptr, 0};
   if (int rc = xhist_sort_run(k, descending, order, offsets, &hand)) return rc;
   if (!hand.keys || hand.rows_per_launch < 1) return k.fail(XHIST_ERR_HIP, "internal: the sort handed over no bin keys");
-  char sort_line[384];
-  snprintf(sort_line, sizeof sort_line, "%s", k.desc);
+  snprintf(dom.sort_line, sizeof dom.sort_line, "%s", k.desc);
+  dom.words = words;
+  dom.rows_per_launch = hand.rows_per_launch;
 
   for (int64_t r0 = 0; r0 < k.n_rows; r0 += hand.rows_per_launch) {
     const int64_t nr = std::min(hand.rows_per_launch, k.n_rows - r0);
@@ -77,7 +75,7 @@ int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, dou
     rp.last = scalars + nw + r0 * words;
     rp.next = scalars + 2 * nw + r0 * words;
     rp.div = pct ? div + r0 * nb : nullptr;
-    rp.out = out + r0 * k.n_cols;
+    rp.out = out ? out + r0 * k.n_cols : nullptr;
     rp.n_rows = nr;
     rp.n_cols = k.n_cols;
     rp.words = words;
@@ -94,6 +92,32 @@ int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, dou
     XH_VALUES_LAUNCH_CHECK(k, "rank_scan launch");
     XH_VALUES_LAUNCH(rank_words, dim3(tile_grid), dim3(256), 0, k.stream, rp);
     XH_VALUES_LAUNCH_CHECK(k, "rank_words launch");
+    if (int rc = tail(rp, r0, nr, word_grid)) return rc;
+  }
+  return XHIST_OK;
+}
+
+}  // namespace
+
+int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, double* out) {
+  const ValuesPlan& pl = k.pl;
+  const int64_t nb = pl.n_bins;
+  if (method < XHIST_RANK_AVERAGE || method > XHIST_RANK_ORDINAL) return k.fail(XHIST_ERR_INVALID, "unknown rank method %d", method);
+  if (k.n_cols >= ((int64_t)1 << 31))
+    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_rank takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), "
+                                         "got %lld", (long long)k.n_cols);
+  if (nb + 1 > ((int64_t)1 << 32))
+    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_rank takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
+                  (long long)nb);
+  const int64_t n = k.n_rows * k.n_cols;
+  if (k.n_cols == 0 || nb == 0) {
+    if (n > 0 && hipMemsetAsync(out, 0xff, (size_t)n * 8, k.stream) != hipSuccess) return k.fail(XHIST_ERR_HIP, "rank: filling out with NaN failed");
+    k.describe("rank method=%s pct=%d descending=%d words=0 rows_per_launch=0 | none", rank_method_name(method), pct ? 1 : 0,
+               descending ? 1 : 0);
+    return XHIST_OK;
+  }
+  SortedDomain dom;
+  const int rc = sorted_domain_run(k, "rank", method, descending, pct != 0, out, dom, [&](const RankParams& rp, int64_t, int64_t nr, unsigned word_grid) {
     if (pct) {
       const unsigned bin_grid = (unsigned)std::min<int64_t>(kRankFlatGrid, (nr * nb + 255) / 256);
       XH_VALUES_LAUNCH(rank_bins, dim3(bin_grid), dim3(256), 0, k.stream, rp);
@@ -101,8 +125,55 @@ int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, dou
     }
     XH_VALUES_LAUNCH(rank_apply, dim3(word_grid), dim3(64 * kRankWaves), 0, k.stream, rp);
     XH_VALUES_LAUNCH_CHECK(k, "rank_apply launch");
-  }
+    return (int)XHIST_OK;
+  });
+  if (rc != XHIST_OK) return rc;
   k.describe("rank method=%s pct=%d descending=%d words=%lld rows_per_launch=%lld | %s", rank_method_name(method), pct ? 1 : 0,
-             descending ? 1 : 0, (long long)words, (long long)hand.rows_per_launch, sort_line);
+             descending ? 1 : 0, (long long)dom.words, (long long)dom.rows_per_launch, dom.sort_line);
+  return XHIST_OK;
+}
+
+int xhist_mode_run(const ValuesCall& k, int64_t* out_count, int64_t* out_nunique, double* out_mode, int64_t* out_mode_count) {
+  const int64_t nb = k.pl.n_bins;
+  if (k.n_cols >= ((int64_t)1 << 31))
+    return k.fail(XHIST_ERR_UNSUPPORTED, "histogram_mode takes fewer than 2^31 samples per output row (a row's positions are held in 32 "
+                                         "bits), got %lld", (long long)k.n_cols);
+  if (nb + 1 > ((int64_t)1 << 32))
+    return k.fail(XHIST_ERR_UNSUPPORTED, "histogram_mode takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
+                  (long long)nb);
+  auto params = [&](const RankParams& rp, int64_t r0) {
+    ModeParams mp;
+    mp.r = rp;
+    mp.slots = reinterpret_cast<uint64_t*>(out_mode_count + r0 * nb);
+    mp.out_count = out_count + r0 * nb;
+    mp.out_nunique = out_nunique + r0 * nb;
+    mp.out_mode = out_mode + r0 * nb;
+    mp.out_mode_count = out_mode_count + r0 * nb;
+    return mp;
+  };
+  auto finish = [&](const ModeParams& mp) {
+    const unsigned bin_grid = (unsigned)std::min<int64_t>(kRankFlatGrid, (mp.r.n_rows * nb + 255) / 256);
+    XH_VALUES_LAUNCH(mode_finish, dim3(bin_grid), dim3(256), 0, k.stream, mp);
+    XH_VALUES_LAUNCH_CHECK(k, "mode_finish launch");
+    return (int)XHIST_OK;
+  };
+  if (k.n_cols == 0) {  // every bin is empty: mode_finish reads nothing but the shape
+    RankParams rp = {};
+    rp.n_rows = k.n_rows;
+    rp.nb = nb;
+    if (int rc = finish(params(rp, 0))) return rc;
+    k.describe("mode words=0 rows_per_launch=0 | none");
+    return XHIST_OK;
+  }
+  SortedDomain dom;
+  const int rc = sorted_domain_run(k, "mode", XHIST_RANK_MIN, 0, false, nullptr, dom, [&](const RankParams& rp, int64_t r0, int64_t nr, unsigned word_grid) {
+    const ModeParams mp = params(rp, r0);
+    if (hipMemsetAsync(mp.slots, 0, (size_t)(nr * nb) * 8, k.stream) != hipSuccess) return k.fail(XHIST_ERR_HIP, "mode: zeroing the slots failed");
+    XH_VALUES_LAUNCH(mode_runs, dim3(word_grid), dim3(64 * kRankWaves), 0, k.stream, mp);
+    XH_VALUES_LAUNCH_CHECK(k, "mode_runs launch");
+    return finish(mp);
+  });
+  if (rc != XHIST_OK) return rc;
+  k.describe("mode words=%lld rows_per_launch=%lld | %s", (long long)dom.words, (long long)dom.rows_per_launch, dom.sort_line);
   return XHIST_OK;
 }

@@ -142,3 +142,12 @@ int xhist_sort_run(const ValuesCall& k, int descending, int64_t* out_order, int6
 // sort it takes a plan without bins (all NaN).
 // XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for n_bins + 1 > 2^32, XHIST_ERR_INVALID for an unknown method, before any launch.
 int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, double* out);
+
+// xhist_rank.hip: histogram_mode, per (row, bin) the number of non-NaN values, the number of distinct ones (IEEE ==), the most
+// frequent value (the smallest of the most frequent ones, with the bits of its first sample in the sort's ascending order) and
+// how often it occurs (k.values the values).  Four [n_rows, n_bins] planes, int64 but out_mode; an empty bin gets 0, 0, NaN
+// (0x7ff8000000000000) and 0; every element is written exactly once.  It runs xhist_sort_run into scratch, the four kernels
+// that build bin_rank's sorted domain and two of its own.  Scratch from k.alloc is bin_rank's without the divisors; the slots
+// of the atomic maximum are the out_mode_count block, zeroed by the call.  XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for
+// n_bins + 1 > 2^32, before any launch.
+int xhist_mode_run(const ValuesCall& k, int64_t* out_count, int64_t* out_nunique, double* out_mode, int64_t* out_mode_count);

@@ -15,7 +15,7 @@ from .core import histogram_two_weights as _core_histogram_two_weights
 
 __all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
            "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt", "histogram_argextrema", "bin_index", "histogram_lookup",
-           "histogram_anomaly", "histogram_sum", "bin_order", "bin_sort", "bin_rank"]
+           "histogram_anomaly", "histogram_sum", "bin_order", "bin_sort", "bin_rank", "histogram_mode"]
 
 
 def _xr():
@@ -215,6 +215,23 @@ def histogram_sum(*args, values, bins=None, range=None, dim=None, block_size="au
     xr = _xr()
     return (xr.DataArray(cnt, dims=out_dims, coords=coords, name="%s_count" % base),
             xr.DataArray(total, dims=out_dims, coords=coords, name="%s_sum" % base))
+
+
+def histogram_mode(*args, values, bins=None, range=None, dim=None, block_size="auto", keep_coords=False, bin_dim_suffix="_bin"):
+    """Per-bin most frequent value of the DataArray ``values`` over the bins of ``args``, how often it occurs and how many
+    different values there are (:func:`xhistogram_amd.core.histogram_mode` with the labels of :func:`histogram`).
+
+    ``args``, ``bins``, ``range``, ``dim``, ``keep_coords``, ``bin_dim_suffix`` and ``values`` are those of
+    :func:`histogram_mean_var`; there are no ``weights``.  Returns ``(count, nunique, mode, mode_count)``: four DataArrays with
+    the dims and coords ``histogram`` gives for the same ``args``, ``bins`` and ``dim``, named ``<values name>_count`` /
+    ``_nunique`` / ``_mode`` / ``_mode_count`` (``values`` when the DataArray has no name)."""
+    from .core import histogram_mode as _core_histogram_mode
+
+    results, out_dims, coords, base = _values_statistic(
+        "histogram_mode", _core_histogram_mode, args, values, bins, range, dim, keep_coords, bin_dim_suffix, block_size=block_size)
+    xr = _xr()
+    return tuple(xr.DataArray(a, dims=out_dims, coords=coords, name="%s_%s" % (base, suffix))
+                 for a, suffix in zip(results, ("count", "nunique", "mode", "mode_count")))
 
 
 def histogram_skew_kurt(*args, values, bins=None, range=None, dim=None, weights=None, ddof=0, bias=True, fisher=True,
