@@ -477,6 +477,45 @@ int xhist_plan_execute_mode(xhist_plan* plan, const xhist_array* samples, const 
                             int64_t* out_count, int64_t* out_nunique, double* out_mode, int64_t* out_mode_count, int mem_kind,
                             void* stream);
 
+/* bin_unique (added within ABI v11: a new entry, every earlier one unchanged): per row the distinct values of every bin and how
+ * often each occurs, in CSR form: np.unique(v_bin, return_counts=True, return_inverse=True) per bin.  Per row r and bin b, with S
+ * the columns of bin b that xhist_plan_execute counts and whose value, taken as float64, is not NaN, and equality of values
+ * decided by IEEE == (so -0.0 and +0.0 are one value); B the number of bins, W = size:
+ *   out_offsets[r, b]  = the number of distinct values in the bins below b, for b = 0 .. B; np.diff of a row is
+ *                        xhist_plan_execute_mode's out_nunique bit for bit, and U = out_offsets[r, B] the row's number of
+ *                        distinct (bin, value) pairs.  It always tells the truth, whatever `size` is.
+ *   out_uniques[r, u]  for out_offsets[r, b] <= u < out_offsets[r, b + 1]: the distinct values of S, ascending.  The bits of an
+ *                        entry are those of the value's first column in xhist_plan_execute_sort's ascending order on the same
+ *                        arguments: a zero that S holds with both signs reads -0.0.
+ *   out_counts[r, u]   = the number of columns of S whose value == out_uniques[r, u]
+ *   Entries min(U, W) <= u < W are padding: 0x7ff8000000000000 in out_uniques and 0 in out_counts.  Entries u >= W are stored
+ *   nowhere: silent truncation, which the caller sees as out_offsets[r, B] > size.
+ *   out_inverse[r, c]  (NULL: none) = the entry u of column c's value, also where u >= W; -1 for a column that is not counted
+ *                        and for a column whose value is NaN.
+ *   out_offsets is a contiguous DEVICE block [n_rows, B + 1] of int64, out_uniques [n_rows, size] of float64, out_counts
+ *   [n_rows, size] of int64, out_inverse [n_rows, n_cols] of int64 with a row's columns in position order.  Every element of
+ *   each is written and nothing outside them.  A NULL out_offsets, and with size > 0 a NULL out_uniques or out_counts, is
+ *   XHIST_ERR_INVALID, and so is a negative size.  A plan without bins gives offsets of 0, padding only and an inverse of -1; a
+ *   call without columns offsets of 0 and padding only.
+ *   values: any real dtype, any strides.  n_cols must be below 2^31 and B + 1 at most 2^32: XHIST_ERR_UNSUPPORTED otherwise,
+ *   before any launch.
+ *   The call is xhist_plan_execute_sort into scratch, the head and NaN bits and the scan of the head words of
+ *   xhist_plan_execute_rank, and up to five kernels over them.  Inside a bin the values precede the NaNs and a bin's first
+ *   position is a head, so the entry of a position is the offset of its bin plus the heads from the bin's start up to it.  One
+ *   thread per (row, bin) writes the bin's distinct values into out_offsets, one workgroup per row scans them in place, one wave
+ *   per 64 positions stores the value (the one gather besides the head pass's) and the run length of every head below W, the
+ *   padding is written, and with an inverse one wave per 64 positions scatters the entries.  No kernel waits for another
+ *   workgroup and none issues an atomic.
+ *   Scratch of the call, on top of xhist_plan_execute_sort's: xhist_plan_execute_rank's without the divisors; XHIST_ERR_NOMEM
+ *   where it cannot be had.
+ *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
+ *   Exact and deterministic.  Asynchronous on `stream`, no synchronisation with the host.
+ *   xhist_plan_describe then reads "unique size=.. inverse=0|1 words=.. rows_per_launch=.. | " followed by
+ *   xhist_plan_execute_sort's own line ("none" for a call without columns). */
+int xhist_plan_execute_unique(xhist_plan* plan, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+                              int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets, int64_t* out_inverse,
+                              int mem_kind, void* stream);
+
 /* One-shot form of the two calls above with an internal plan cache keyed on (device, edges). */
 int xhist_bincount_rows(int device, int n_inputs, const xhist_array* samples,
                         const xhist_array* weights, int64_t n_rows, int64_t n_cols,

@@ -75,7 +75,7 @@ EXPORTS = (
     "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
     "xhist_plan_execute_quantile_weighted", "xhist_plan_execute_cov", "xhist_plan_execute_cov_weighted",
     "xhist_plan_execute_skew_kurt", "xhist_plan_execute_skew_kurt_weighted", "xhist_plan_execute_argextrema",
-    "xhist_plan_execute_map", "xhist_plan_execute_group", "xhist_plan_execute_sort", "xhist_plan_execute_rank", "xhist_plan_execute_mode", "xhist_plan_execute_sum", "xhist_debug_sum_host", "xhist_debug_sum_round",
+    "xhist_plan_execute_map", "xhist_plan_execute_group", "xhist_plan_execute_sort", "xhist_plan_execute_rank", "xhist_plan_execute_mode", "xhist_plan_execute_unique", "xhist_plan_execute_sum", "xhist_debug_sum_host", "xhist_debug_sum_round",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -192,6 +192,10 @@ def load():
         lib.xhist_plan_execute_rank.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
             C.c_void_p,
+        ]
+        lib.xhist_plan_execute_unique.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_int, C.c_void_p,
         ]
         lib.xhist_bincount_rows.argtypes = [
             C.c_int, C.c_int, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_void_p),
@@ -479,6 +483,22 @@ class Plan:
             load().xhist_plan_execute_rank(
                 self._h, self._sample_array(sample_views), C.byref(value_view), int(n_rows), int(n_cols), int(method),
                 1 if descending else 0, 1 if pct else 0, C.c_void_p(out_ptr), MEM_DEVICE, C.c_void_p(stream or 0),
+            )
+        )
+
+    def execute_unique(self, sample_views, value_view, n_rows, n_cols, size, out_uniques_ptr, out_counts_ptr, out_offsets_ptr,
+                       out_inverse_ptr=None, stream=0):
+        """per row the distinct non-NaN values of every bin, ascending (float64 [n_rows, size]), how many columns hold each
+        (int64 [n_rows, size]) and the number of distinct values in the bins below b (int64 [n_rows, bins + 1]) of
+        device-resident views, asynchronous on `stream` (xhist_plan_execute_unique).  Entries from min(offsets[r, bins], size) on
+        are padding (NaN and 0); entries from `size` on are stored nowhere.  `out_inverse_ptr` (None / 0: none): int64 into the
+        dense row-major [n_rows, n_cols] block, the entry of every column's value, -1 for a column that is not counted or whose
+        value is NaN; fewer than 2^31 columns"""
+        check(
+            load().xhist_plan_execute_unique(
+                self._h, self._sample_array(sample_views), C.byref(value_view), int(n_rows), int(n_cols), int(size),
+                C.c_void_p(out_uniques_ptr or 0), C.c_void_p(out_counts_ptr or 0), C.c_void_p(out_offsets_ptr or 0),
+                C.c_void_p(out_inverse_ptr or 0), MEM_DEVICE, C.c_void_p(stream or 0),
             )
         )
 

@@ -36,7 +36,7 @@ _range = range
 __all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
            "histogram_weighted_quantile", "histogram_cov", "histogram_weighted_cov", "combine_weighted_cov",
            "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema", "histogram_sum", "bin_order", "bin_sort", "bin_rank",
-           "histogram_mode"]
+           "histogram_mode", "bin_unique"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2652,6 +2652,13 @@ def _sample_block(run, m, c, is_index, like, axis, backend, device):
         run(out.data_ptr() if buf is None else buf.ptr)
         if buf is not None:
             buf.download(out)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+    return _sample_shape(out, shape, kept, red, backend)
+
+
+def _sample_shape(out, shape, kept, red, backend):
+    """a dense [rows, cols] block, its rows the kept axes in C order and a row's columns the reduced axes in ascending number,
+    in the broadcast sample shape `shape`"""
+    ndim = len(shape)
     out = out.reshape([shape[i] for i in kept] + [shape[i] for i in red])
     if kept and red != list(_range(len(kept), ndim)):
         back = tuple(_range(len(kept), ndim))
@@ -3184,3 +3191,131 @@ def bin_rank(*args, values, bins=None, range=None, axis=None, method="average", 
     out = _sample_block(run, m, c, False, arrays[0], axis, on, device)
     del views
     return out, bins
+
+
+# ---------------------------------------------------------------------------------------------
+# bin_unique: each bin's distinct values and their counts (CSR)
+# ---------------------------------------------------------------------------------------------
+def _check_size(size):
+    """ValueError unless `size` is None or an integer >= 0 (a bool is not one)"""
+    if size is None:
+        return
+    if isinstance(size, (bool, np.bool_)) or not isinstance(size, (int, np.integer)) or size < 0:
+        raise ValueError("size must be None or an integer >= 0, got %r" % (size,))
+
+
+def _bin_unique_block(*blocks, axis=None, bins=None, size=None):
+    """one dask block (samples..., values): uniques (as the bits they are) and counts side by side, then the offsets"""
+    uniques, counts, offsets, _ = bin_unique(*blocks[:-1], values=blocks[-1], bins=bins, axis=axis, size=size)
+    return _packed_block(np.concatenate([np.ascontiguousarray(uniques).view(np.int64), counts], axis=-1), offsets, blocks[0], axis)
+
+
+def _bin_unique_inverse_block(*blocks, axis=None, bins=None):
+    return bin_unique(*blocks[:-1], values=blocks[-1], bins=bins, axis=axis, size=0, return_inverse=True)[3]
+
+
+def _float64_bits(block):
+    return np.ascontiguousarray(block).view(np.float64)
+
+
+def bin_unique(*args, values, bins=None, range=None, axis=None, size=None, return_inverse=False):
+    """The distinct values of every bin and how often each occurs, in CSR form, computed on an MI355X:
+    ``np.unique(v_bin, return_counts=True, return_inverse=True)`` per bin, ``pandas.groupby(bin).value_counts()`` — the census
+    of each class, the composition of each band, a contingency table whose categories are not known in advance, per-bin
+    entropy, and the code of every sample for a later :func:`histogram_lookup`.
+
+    ``args``, ``bins``, ``range``, ``axis`` and ``values`` (any real dtype, taken as float64; a complex dtype is a
+    ``TypeError``), the samples that count, the compare domains, the joint bins of up to 8 inputs, the estimator names and the
+    broadcasting are those of :func:`histogram_mode`; the meaning of a position and the two size limits are
+    :func:`bin_sort`'s.  NaN values are ignored, and two values are one where IEEE ``==`` says so: ``-0.0`` and ``+0.0`` are one
+    value.
+
+    With ``B`` the number of bins, ``c`` the reduced samples per kept index, ``kept`` the kept axes' shape and ``W`` the output
+    width (``c`` when ``size is None``, else ``size``), per kept index:
+
+    * ``offsets``, int64 ``kept + (B + 1,)``: ``offsets[b]`` is the number of distinct non-NaN values in the bins below ``b``;
+      ``np.diff(offsets)`` is :func:`histogram_mode`'s ``nunique`` bit for bit and ``U = offsets[B]`` the row's number of
+      distinct (bin, value) pairs.  ``offsets`` always tells the truth, whatever ``size`` is.
+    * ``uniques``, float64 ``kept + (W,)``: ``uniques[offsets[b]:offsets[b + 1]]`` are bin ``b``'s distinct values, ascending.
+      The bits of an entry are those of the value's first sample in :func:`bin_sort`'s ascending order: a zero the bin holds
+      with both signs reads ``-0.0``, as :func:`histogram_mode` reports it.
+    * ``counts``, int64 ``kept + (W,)``: ``counts[u]`` is the number of counted samples of that bin whose value ``==``
+      ``uniques[u]``.
+    * Entries ``min(U, W) <= u < W`` are padding: NaN (``0x7ff8000000000000``) in ``uniques`` and ``0`` in ``counts``.
+    * ``inverse``, only with ``return_inverse=True``: int64 in the broadcast shape of the inputs, as :func:`bin_rank`'s output
+      is.  The index ``u`` into the row's ``uniques`` for a counted sample with a non-NaN value, ``-1`` for every other sample;
+      the true index even where ``u >= W``.
+
+    ``size`` exists because ``c`` is the only bound known without a host synchronisation, and categorical data has
+    ``U << c``.  With ``size=k`` entries ``u >= k`` are written nowhere: silent truncation, as ``jnp.unique(size=)`` does, which
+    the caller sees as ``offsets[..., B] > k``.  There is no synchronisation and no error from the device.
+
+    So, per kept index: the segment sums of ``counts`` are :func:`histogram_mode`'s ``count``; a segment's largest count is its
+    ``mode_count`` and the first entry that holds it its ``mode``, by bits; ``uniques[offsets[b]]`` ``==``
+    :func:`histogram_extrema`'s ``vmin`` and the segment's last entry ``==`` its ``vmax``; on counted non-NaN samples
+    ``inverse == offsets[bin_index] + bin_rank(method="dense") - 1`` and ``uniques[inverse] == values``; and
+    ``np.bincount(inverse[inverse >= 0], minlength=U) == counts[:U]``.  Exact and deterministic: the samples are sorted as
+    :func:`bin_sort` sorts them, and every output is an integer or the bits of an input value.
+
+    A plan without bins (one edge) gives ``offsets == [0]``, padding only and an ``inverse`` of ``-1``; ``c == 0`` gives empty or
+    all-padding outputs and offsets of 0.  ``size`` is ``None`` or an integer ``>= 0`` (anything else, a bool included, is a
+    ``ValueError``); there are no ``weights`` and no ``descending``.  A reduced extent of 2^31 samples or more per row, and
+    ``B + 1 > 2**32``, raise ``NotImplementedError``.  All refusals happen before any device work.
+
+    Returns ``(uniques, counts, offsets, bin_edges)``, with ``return_inverse`` ``(uniques, counts, offsets, inverse,
+    bin_edges)``.  numpy in -> numpy out (uploaded once, one download), torch in -> torch out on the same device (asynchronous
+    on the current stream, no host synchronisation), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per
+    block over the kept axes: every reduced axis must then be a single chunk, and ``bins`` numpy arrays of edges."""
+    def check():
+        _check_size(size)
+        _check_flag("return_inverse", return_inverse)
+
+    g = _grouped_call("bin_unique", "distinct values", args, values, bins, range, axis, max_bins=_SORT_MAX_BINS, check=check)
+    bins, axis, return_inverse = g.bins, g.axis, bool(return_inverse)
+    size = None if size is None else int(size)
+    n = len(args)
+    if g.backend == "dask":
+        import dask.array as dsa
+
+        width = g.cols if size is None else size
+        both, offsets = _packed_blockwise(_bin_unique_block, g.arrays, g.drop_axes, 2 * width, g.n_bins, bins=bins, size=width)
+        uniques = both[..., :width].map_blocks(_float64_bits, dtype=np.float64, meta=np.array((), np.float64))
+        out = (uniques, both[..., width:], offsets)
+        if return_inverse:
+            ind = tuple(_range(g.arrays[0].ndim))
+            out += (dsa.blockwise(_bin_unique_inverse_block, ind, *[x for a in g.arrays for x in (a, ind)], dtype=np.int64,
+                                  axis=list(g.drop_axes), bins=bins, meta=np.array((), np.int64)),)
+        return out + (bins,)
+    arrays, on = _resident(g.backend, g.raw, g.arrays, n, bins)
+    plan, nv, views, m, c, _, device, stream = _value_views(arrays[:n], arrays[n], axis, bins, on, ordered=True)
+    shape = tuple(int(s) for s in arrays[0].shape)
+    ndim = len(shape)
+    red = list(_range(ndim)) if axis is None or set(axis) == set(_range(ndim)) else sorted(axis)
+    kept = [i for i in _range(ndim) if i not in red]
+    width = c if size is None else size
+    nb1 = plan.n_bins + 1
+    n_inv = c if return_inverse else 0
+    if on == "torch":
+        torch = _torch()
+        like = dict(dtype=torch.int64, device=arrays[0].device)
+        uniques = torch.empty((m, width), dtype=torch.float64, device=arrays[0].device)
+        counts, offsets, inverse = torch.empty((m, width), **like), torch.empty((m, nb1), **like), torch.empty((m, n_inv), **like)
+        if m > 0:
+            plan.execute_unique(nv[:n], nv[n], m, c, width, uniques.data_ptr(), counts.data_ptr(), offsets.data_ptr(),
+                                inverse.data_ptr() if return_inverse else None, stream=stream)
+    else:
+        cuts = np.cumsum([0, m * width, m * width, m * nb1, m * n_inv])
+        host = np.empty(int(cuts[-1]), np.int64)
+        if m > 0:
+            buf = _native.DeviceBuffer(device, host.nbytes)
+            ptrs = [buf.ptr + 8 * int(at) for at in cuts[:4]]
+            plan.execute_unique(nv[:n], nv[n], m, c, width, ptrs[0], ptrs[1], ptrs[2], ptrs[3] if return_inverse else None, stream=stream)
+            buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
+        uniques = host[cuts[0]:cuts[1]].view(np.float64).reshape(m, width)
+        counts, offsets, inverse = (host[cuts[i]:cuts[i + 1]].reshape(m, w) for i, w in ((1, width), (2, nb1), (3, n_inv)))
+    del views
+    lead = tuple(shape[i] for i in kept)
+    out = (uniques.reshape(lead + (width,)), counts.reshape(lead + (width,)), offsets.reshape(lead + (nb1,)))
+    if return_inverse:
+        out += (_sample_shape(inverse, shape, kept, red, on),)
+    return out + (bins,)

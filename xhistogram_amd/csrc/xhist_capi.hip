@@ -522,6 +522,32 @@ extern "C" int xhist_plan_execute_mode(xhist_plan* p, const xhist_array* samples
                         [&](const ValuesCall& k) { return xhist_mode_run(k, out_count, out_nunique, out_mode, out_mode_count); });
 }
 
+// bin_unique (xhist_rank.hip): bin_rank's front with four blocks.  A plan without bins has no entry and counts no sample, and the
+// statistics' front has no output row to launch over: offsets of 0, padding and an inverse of -1 are written from here.
+extern "C" int xhist_plan_execute_unique(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
+                                         int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets, int64_t* out_inverse,
+                                         int mem_kind, void* stream) {
+  if (size < 0) return fail(XHIST_ERR_INVALID, "bin_unique takes a size of 0 or more, got %lld", (long long)size);
+  if (p && n_cols >= ((int64_t)1 << 31))
+    return fail(XHIST_ERR_UNSUPPORTED, "bin_unique takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), "
+                                       "got %lld", (long long)n_cols);
+  if (p && p->n_bins + 1 > ((int64_t)1 << 32))
+    return fail(XHIST_ERR_UNSUPPORTED, "bin_unique takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
+                (long long)p->n_bins);
+  if (p && n_rows > 0 && !out_offsets) return fail(XHIST_ERR_INVALID, "out_offsets is NULL");
+  if (p && n_rows > 0 && size > 0 && !(out_uniques && out_counts)) return fail(XHIST_ERR_INVALID, "out_uniques / out_counts is NULL");
+  static double no_rows;  // (what validate_arrays sees of a call without rows: the block has no element)
+  const int rc = execute_values(p, "xhist_plan_execute_unique", samples, values, nullptr, nullptr, n_rows, n_cols,
+                                out_offsets ? reinterpret_cast<double*>(out_offsets) : &no_rows, true, "", mem_kind, stream,
+                                [&](const ValuesCall& k) { return xhist_unique_run(k, size, out_uniques, out_counts, out_offsets, out_inverse); });
+  if (rc != XHIST_OK || p->n_bins > 0 || n_rows <= 0) return rc;
+  DeviceGuard g;
+  if (int grc = g.set(p->device)) return grc;
+  if (int grc = xhist_unique_no_bins(n_rows, n_cols, size, out_uniques, out_counts, out_offsets, out_inverse, static_cast<hipStream_t>(stream)))
+    return fail(grc, "xhist_plan_execute_unique: the launches over a plan without bins failed");
+  return XHIST_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // one-shot form with a plan cache
 // ------------------------------------------------------------------------------------------

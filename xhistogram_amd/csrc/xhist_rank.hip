@@ -1,21 +1,27 @@
-// xhist_rank.hip — bin_rank, the rank of every sample's value among the non-NaN values of its bin, and histogram_mode, each bin's
-// most frequent value: the kernels of xhist_rank.hip.h and xhist_mode.hip.h, instantiated here and nowhere else, and the two
-// drivers that order them behind the sort.
+// xhist_rank.hip — bin_rank, the rank of every sample's value among the non-NaN values of its bin, histogram_mode, each bin's
+// most frequent value, and bin_unique, each bin's distinct values and their counts: the kernels of xhist_rank.hip.h,
+// xhist_mode.hip.h and xhist_unique.hip.h, instantiated here and nowhere else, and the three drivers that order them behind the
+// sort.
 //
-// Instantiations (8): rank_heads, rank_totals, rank_scan, rank_words, rank_bins, rank_apply, mode_runs, mode_finish.  The method
-// and whether the call is pct are kernel-uniform parameters, not template axes; rank_bins is launched only for pct.
+// Instantiations (13): rank_heads, rank_totals, rank_scan, rank_words, rank_bins, rank_apply, mode_runs, mode_finish, unique_bins,
+// unique_scan, unique_runs, unique_pad, unique_inverse.  The method and whether the call is pct are kernel-uniform parameters,
+// not template axes; rank_bins is launched only for pct, unique_inverse only for a call with an inverse.
 //
 // Both drivers run bin_sort's own driver (xhist_sort_run) into scratch order and offsets blocks and take over the sorted bin
 // keys its last pass wrote.  Then, per batch of the sort's rows_per_launch rows, a chain of plain launches: rank_heads,
 // rank_totals, rank_scan, rank_words (sorted_domain_run, which both share), and then rank_bins (pct), rank_apply for bin_rank, a
 // fill of the slots with 0, mode_runs, mode_finish for histogram_mode.  A bin_rank call without columns or a plan without bins
 // fills out with NaN (bytes of all ones) and launches nothing; a histogram_mode call without columns launches mode_finish alone.
+// bin_unique's tail is unique_bins, unique_scan, unique_runs, unique_pad (a width above 0) and unique_inverse (an inverse); a call
+// without columns or a plan without bins zeroes the offsets and launches unique_pad alone.
 //
 // Scratch of a call, from k.scratch, on top of the sort's 32 bytes per sample: 8 bytes per sample of order, n_rows * (B + 1) * 8
 // bytes of offsets, per 64 samples of a row 28 bytes (the head word, the NaN word, and before / last / next), per 65536 samples
 // of a row 12 bytes more (a tile's three scalars), and n_rows * B * 8 bytes of divisors when pct.  histogram_mode takes the same
-// without the divisors and nothing more: its slots are the out_mode_count block.
+// without the divisors and nothing more: its slots are the out_mode_count block.  bin_unique takes the same again: its distinct
+// counts and their scan live in out_offsets.
 #include "xhist_mode.hip.h"
+#include "xhist_unique.hip.h"
 
 using namespace xhist;
 
@@ -175,5 +181,81 @@ int xhist_mode_run(const ValuesCall& k, int64_t* out_count, int64_t* out_nunique
   });
   if (rc != XHIST_OK) return rc;
   k.describe("mode words=%lld rows_per_launch=%lld | %s", (long long)dom.words, (long long)dom.rows_per_launch, dom.sort_line);
+  return XHIST_OK;
+}
+
+// a call without columns, or a plan without bins: no entry and no counted sample.  Offsets of 0, padding over the whole width,
+// an inverse of -1 (bytes of all ones).
+static int unique_nothing(int64_t n_rows, int64_t n_cols, int64_t nb, int64_t size, double* out_uniques, int64_t* out_counts,
+                          int64_t* out_offsets, int64_t* out_inverse, hipStream_t stream) {
+  if (hipMemsetAsync(out_offsets, 0, (size_t)(n_rows * (nb + 1)) * 8, stream) != hipSuccess) return XHIST_ERR_HIP;
+  if (size > 0) {
+    UniqueParams up = {};
+    up.r.n_rows = n_rows;
+    up.r.nb = nb;
+    up.out_offsets = out_offsets;
+    up.out_uniques = out_uniques;
+    up.out_counts = out_counts;
+    up.width = size;
+    const int64_t chunks = (size + kUniquePadChunk - 1) / kUniquePadChunk;
+    XH_VALUES_LAUNCH(unique_pad, dim3((unsigned)std::min<int64_t>(kRankFlatGrid, n_rows * chunks)), dim3(256), 0, stream, up);
+    if (hipGetLastError() != hipSuccess) return XHIST_ERR_HIP;
+  }
+  if (out_inverse && n_rows * n_cols > 0 && hipMemsetAsync(out_inverse, 0xff, (size_t)(n_rows * n_cols) * 8, stream) != hipSuccess)
+    return XHIST_ERR_HIP;
+  return XHIST_OK;
+}
+
+int xhist_unique_no_bins(int64_t n_rows, int64_t n_cols, int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets,
+                         int64_t* out_inverse, hipStream_t stream) {
+  return unique_nothing(n_rows, n_cols, 0, size, out_uniques, out_counts, out_offsets, out_inverse, stream);
+}
+
+int xhist_unique_run(const ValuesCall& k, int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets,
+                     int64_t* out_inverse) {
+  const int64_t nb = k.pl.n_bins, nb1 = nb + 1;
+  if (size < 0) return k.fail(XHIST_ERR_INVALID, "bin_unique takes a size of 0 or more, got %lld", (long long)size);
+  if (k.n_cols >= ((int64_t)1 << 31))
+    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_unique takes fewer than 2^31 samples per output row (a row's positions are held in 32 "
+                                         "bits), got %lld", (long long)k.n_cols);
+  if (nb1 > ((int64_t)1 << 32))
+    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_unique takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
+                  (long long)nb);
+  if (k.n_cols == 0) {
+    if (unique_nothing(k.n_rows, 0, nb, size, out_uniques, out_counts, out_offsets, nullptr, k.stream) != XHIST_OK)
+      return k.fail(XHIST_ERR_HIP, "unique: writing the outputs of a call without columns failed");
+    k.describe("unique size=%lld inverse=%d words=0 rows_per_launch=0 | none", (long long)size, out_inverse ? 1 : 0);
+    return XHIST_OK;
+  }
+  SortedDomain dom;
+  const int rc = sorted_domain_run(k, "unique", XHIST_RANK_DENSE, 0, false, nullptr, dom, [&](const RankParams& rp, int64_t r0, int64_t nr, unsigned word_grid) {
+    UniqueParams up;
+    up.r = rp;
+    up.out_offsets = out_offsets + r0 * nb1;
+    up.out_uniques = out_uniques ? out_uniques + r0 * size : nullptr;
+    up.out_counts = out_counts ? out_counts + r0 * size : nullptr;
+    up.out_inverse = out_inverse ? out_inverse + r0 * k.n_cols : nullptr;
+    up.width = size;
+    const unsigned bin_grid = (unsigned)std::min<int64_t>(kRankFlatGrid, (nr * nb + 255) / 256);
+    XH_VALUES_LAUNCH(unique_bins, dim3(bin_grid), dim3(256), 0, k.stream, up);
+    XH_VALUES_LAUNCH_CHECK(k, "unique_bins launch");
+    XH_VALUES_LAUNCH(unique_scan, dim3((unsigned)nr), dim3(256), 0, k.stream, up);
+    XH_VALUES_LAUNCH_CHECK(k, "unique_scan launch");
+    if (size > 0) {
+      XH_VALUES_LAUNCH(unique_runs, dim3(word_grid), dim3(64 * kRankWaves), 0, k.stream, up);
+      XH_VALUES_LAUNCH_CHECK(k, "unique_runs launch");
+      const int64_t chunks = (size + kUniquePadChunk - 1) / kUniquePadChunk;
+      XH_VALUES_LAUNCH(unique_pad, dim3((unsigned)std::min<int64_t>(kRankFlatGrid, nr * chunks)), dim3(256), 0, k.stream, up);
+      XH_VALUES_LAUNCH_CHECK(k, "unique_pad launch");
+    }
+    if (out_inverse) {
+      XH_VALUES_LAUNCH(unique_inverse, dim3(word_grid), dim3(64 * kRankWaves), 0, k.stream, up);
+      XH_VALUES_LAUNCH_CHECK(k, "unique_inverse launch");
+    }
+    return (int)XHIST_OK;
+  });
+  if (rc != XHIST_OK) return rc;
+  k.describe("unique size=%lld inverse=%d words=%lld rows_per_launch=%lld | %s", (long long)size, out_inverse ? 1 : 0,
+             (long long)dom.words, (long long)dom.rows_per_launch, dom.sort_line);
   return XHIST_OK;
 }

@@ -151,3 +151,18 @@ int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, dou
 // of the atomic maximum are the out_mode_count block, zeroed by the call.  XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for
 // n_bins + 1 > 2^32, before any launch.
 int xhist_mode_run(const ValuesCall& k, int64_t* out_count, int64_t* out_nunique, double* out_mode, int64_t* out_mode_count);
+
+// xhist_rank.hip: bin_unique, per row the distinct non-NaN values of every bin in CSR form (k.values the values; equality is
+// IEEE ==).  out_offsets int64 [n_rows, n_bins + 1]: the distinct values in the bins below b, always the truth; out_uniques
+// float64 and out_counts int64 [n_rows, size]: a bin's values ascending, each with the bits of its first sample in the sort's
+// ascending order, and how many samples hold it; entries from min(out_offsets[r, n_bins], size) on are padding (0x7ff8000000000000
+// and 0), entries from `size` on are stored nowhere; out_inverse (nullptr: none) int64 [n_rows, n_cols] in position order: the
+// sample's entry, beyond `size` too, -1 for a sample that is not counted and for a NaN value.  Every element of every output is
+// written and nothing outside them.  It runs xhist_sort_run into scratch, the four kernels that build bin_rank's sorted domain
+// and up to five of its own; scratch from k.alloc is bin_rank's without the divisors.  XHIST_ERR_INVALID for a negative size,
+// XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for n_bins + 1 > 2^32, before any launch.  xhist_unique_no_bins: a plan without
+// bins, which the statistics' front does not launch over (offsets [n_rows, 1] of zeros, padding, an inverse of -1).
+int xhist_unique_run(const ValuesCall& k, int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets,
+                     int64_t* out_inverse);
+int xhist_unique_no_bins(int64_t n_rows, int64_t n_cols, int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets,
+                         int64_t* out_inverse, hipStream_t stream);

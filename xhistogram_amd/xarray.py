@@ -15,7 +15,7 @@ from .core import histogram_two_weights as _core_histogram_two_weights
 
 __all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
            "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt", "histogram_argextrema", "bin_index", "histogram_lookup",
-           "histogram_anomaly", "histogram_sum", "bin_order", "bin_sort", "bin_rank", "histogram_mode"]
+           "histogram_anomaly", "histogram_sum", "bin_order", "bin_sort", "bin_rank", "histogram_mode", "bin_unique"]
 
 
 def _xr():
@@ -546,3 +546,31 @@ def bin_rank(*args, values, bins=None, range=None, dim=None, method="average", d
     out, _ = _core_bin_rank(*arrays[:n], values=arrays[n], bins=bins, range=range, axis=axis, method=method, descending=descending,
                             pct=pct)
     return _xr().DataArray(out, dims=dims_order, coords=_sample_coords(first, dims_order), name="%s_bin_rank" % (values.name or "values"))
+
+
+def bin_unique(*args, values, bins=None, range=None, dim=None, size=None, return_inverse=False):
+    """The distinct values of every bin and how often each occurs (:func:`xhistogram_amd.core.bin_unique`); ``values`` is lined
+    up as :func:`bin_sort` lines it up.  DataArrays on the kept dims (those not in ``dim``; none for ``dim=None``):
+    ``<values name>_unique`` (float64) and ``<values name>_unique_counts`` (int64) with a new last dim ``<values name>_unique``
+    (a row's entries, bin by bin, ascending inside each bin, then padding), and ``<values name>_unique_offsets`` (int64) with a
+    new last dim ``<values name>_bin_offset`` (where each bin's entries start; the last entry: how many there are).  With
+    ``return_inverse`` a fourth, ``<values name>_unique_inverse`` (int64) on the broadcast dims of the inputs: every sample's
+    entry, ``-1`` where it has none.  ``values`` without a name is called ``values``."""
+    from .core import bin_unique as _core_bin_unique
+
+    if values is None:
+        raise TypeError("bin_unique needs values")
+    arrays, dims_order, first = _lined_up("bin_unique", args, [values])
+    n = len(args)
+    kept = [d for d in dims_order if dim is not None and d not in dim]
+    axis = None if dim is None else [dims_order.index(d) for d in dim]
+    res = _core_bin_unique(*arrays[:n], values=arrays[n], bins=bins, range=range, axis=axis, size=size, return_inverse=return_inverse)
+    name = values.name or "values"
+    coords = _sample_coords(first, kept)
+    xr = _xr()
+    out = (xr.DataArray(res[0], dims=kept + ["%s_unique" % name], coords=coords, name="%s_unique" % name),
+           xr.DataArray(res[1], dims=kept + ["%s_unique" % name], coords=coords, name="%s_unique_counts" % name),
+           xr.DataArray(res[2], dims=kept + ["%s_bin_offset" % name], coords=coords, name="%s_unique_offsets" % name))
+    if len(res) == 5:
+        out += (xr.DataArray(res[3], dims=dims_order, coords=_sample_coords(first, dims_order), name="%s_unique_inverse" % name),)
+    return out
