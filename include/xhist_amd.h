@@ -340,8 +340,9 @@ int xhist_plan_execute_quantile_weighted(xhist_plan* plan, const xhist_array* sa
  *   Every element of `out` is written exactly once and nothing outside it; nothing is accumulated.  Asynchronous on `stream`.
  *   A plan without bins (an edge array of a single edge) counts no sample: the block is then filled with -1 / NaN, the NaN
  *   being the all-ones bit pattern.
- *   xhist_plan_describe then reads "map op=index|take|anomaly family=fast|generic table=lds|global|none scan=.. cmp=.. segs=..
- *   block=.. lds_bytes=..": the kernel family and where the table row of a workgroup lives. */
+ *   xhist_plan_describe then reads "map op=index|take|anomaly family=fast|generic|none table=lds|global|none scan=.. cmp=..
+ *   segs=.. block=.. lds_bytes=..": the kernel family (none: a plan without bins or a call without columns) and where the table
+ *   row of a workgroup lives. */
 #define XHIST_MAP_INDEX 0
 #define XHIST_MAP_TAKE 1
 #define XHIST_MAP_ANOMALY 2
@@ -367,9 +368,9 @@ int xhist_plan_execute_map(xhist_plan* plan, const xhist_array* samples, const x
  *   is one chunk).
  *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
  *   Exact and deterministic: no result depends on the order in which waves arrive.  Asynchronous on `stream`.
- *   xhist_plan_describe then reads "group keys=fast|generic bits=.. waves=.. block=.. chunks=.. chunk=.. lds_bytes=..
- *   rows_per_launch=.. D=.. cmp=..": the kernel family that made the keys, the ballots of a step, the waves of a workgroup,
- *   and how a row was cut. */
+ *   xhist_plan_describe then reads "group keys=fast|generic|none bits=.. waves=.. block=.. chunks=.. chunk=.. lds_bytes=..
+ *   rows_per_launch=.. D=.. cmp=..": the kernel family that made the keys (none: a plan without bins or a call without
+ *   columns), the ballots of a step, the waves of a workgroup, and how a row was cut. */
 int xhist_plan_execute_group(xhist_plan* plan, const xhist_array* samples, int64_t n_rows, int64_t n_cols,
                              int64_t* out_order, int64_t* out_offsets, int mem_kind, void* stream);
 
@@ -430,8 +431,8 @@ int xhist_plan_execute_sort(xhist_plan* plan, const xhist_array* samples, const 
  *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
  *   Exact and deterministic.  Asynchronous on `stream`.
  *   xhist_plan_describe then reads "rank method=average|min|max|dense|ordinal pct=.. descending=.. words=.. rows_per_launch=..
- *   | " followed by xhist_plan_execute_sort's own line ("none" for a call without columns): the words of 64 positions of a
- *   row and the rows of one launch. */
+ *   | " followed by xhist_plan_execute_sort's own line ("none" for a call without columns or a plan without bins): the words of
+ *   64 positions of a row and the rows of one launch. */
 typedef enum {
   XHIST_RANK_AVERAGE = 0,
   XHIST_RANK_MIN,
@@ -511,7 +512,7 @@ int xhist_plan_execute_mode(xhist_plan* plan, const xhist_array* samples, const 
  *   mem_kind must be XHIST_MEM_DEVICE (host data: upload it first); anything else is XHIST_ERR_INVALID.
  *   Exact and deterministic.  Asynchronous on `stream`, no synchronisation with the host.
  *   xhist_plan_describe then reads "unique size=.. inverse=0|1 words=.. rows_per_launch=.. | " followed by
- *   xhist_plan_execute_sort's own line ("none" for a call without columns). */
+ *   xhist_plan_execute_sort's own line ("none" for a call without columns or a plan without bins). */
 int xhist_plan_execute_unique(xhist_plan* plan, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
                               int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets, int64_t* out_inverse,
                               int mem_kind, void* stream);

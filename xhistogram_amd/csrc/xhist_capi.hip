@@ -278,22 +278,49 @@ static void* values_scratch_alloc(void* ctx, size_t bytes) {
   return static_cast<ScratchScope*>(ctx)->alloc(&d, bytes ? bytes : 8) == hipSuccess ? d : nullptr;
 }
 
-// The checks and the tail the statistics' entry points share: `out` is the statistic's float64 output validate_arrays checks,
-// `outs_ok` whether the others are given (`outs_missing` the message if not); `third` and `fourth` are the streams beyond the
-// values, which the entry point has checked (nullptr: none).  run(call) launches on the plan's device with the record of the
-// call, which lives as long as run does; the line it writes to call.desc becomes the plan's describe().  `needs_values` false:
-// the call may come without values (the per-sample maps that read the samples alone).
+// What an entry point tells the front about its call:
+//   needs_values  the call may not come without values (false: the per-sample maps and bin_order, which read the samples alone)
+//   dense         false: the outputs are [n_rows, n_bins] planes, `out` is the one validate_arrays checks, and a call without rows
+//                 or a plan without bins has nothing to do.  true: they are dense [n_rows, n_cols] or CSR blocks, of which a plan
+//                 without bins and a call without columns still have elements: only a call without rows returns before the
+//                 driver, `out` is not looked at, and `outs_ok` speaks for every output
+//   sorted        the public name of a call that builds the sorted order, under which the front refuses that order's limits before
+//                 it looks at anything else; nullptr: the call builds none
+struct ValuesShape {
+  bool needs_values, dense;
+  const char* sorted;
+};
+static constexpr ValuesShape kPlanes = {true, false, nullptr};
+
+// The two limits of the sorted order (xhist_sort.hip), on the columns of a row and on the bins, under the caller's public name.
+// bin_order sorts by no value (`by_value` false) and has the first alone, of its offsets; its limit on the bins depends on the
+// plan's LDS and stays in xhist_group_run.
+static int sorted_order_limits(const char* who, bool by_value, int64_t n_cols, int64_t n_bins) {
+  if (n_cols >= ((int64_t)1 << 31))
+    return fail(XHIST_ERR_UNSUPPORTED, "%s takes fewer than 2^31 samples per output row (a row's %s are held in 32 bits), got %lld", who,
+                by_value ? "positions" : "offsets", (long long)n_cols);
+  if (by_value && n_bins + 1 > ((int64_t)1 << 32))
+    return fail(XHIST_ERR_UNSUPPORTED, "%s takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld", who, (long long)n_bins);
+  return XHIST_OK;
+}
+
+// The checks and the tail the statistics' entry points share: `out` is the float64 plane validate_arrays checks (nullptr for a
+// dense call), `outs_ok` whether the other outputs are given (`outs_missing` the message if not); `third` and `fourth` are the
+// streams beyond the values, which the entry point has checked (nullptr: none).  run(call) launches on the plan's device with the
+// record of the call, which lives as long as run does; the line it writes to call.desc becomes the plan's describe().
 template <class Run>
 static int execute_values(xhist_plan* p, const char* name, const xhist_array* samples, const xhist_array* values,
                           const xhist_array* third, const xhist_array* fourth, int64_t n_rows, int64_t n_cols, double* out, bool outs_ok,
-                          const char* outs_missing, int mem_kind, void* stream, Run run, bool needs_values = true) {
-  if (!values && needs_values) return fail(XHIST_ERR_INVALID, "values are required");
+                          const char* outs_missing, int mem_kind, void* stream, Run run, const ValuesShape& shape = kPlanes) {
+  if (p && shape.sorted)
+    if (int rc = sorted_order_limits(shape.sorted, shape.needs_values, n_cols, p->n_bins)) return rc;
+  if (!values && shape.needs_values) return fail(XHIST_ERR_INVALID, "values are required");
   // (validate_arrays names the output's type by whether there is a second stream; `out` is 8-byte elements either way)
-  if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out, values ? XHIST_F64 : XHIST_I64)) return rc;
-  if (!outs_ok && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "%s", outs_missing);
+  if (int rc = validate_arrays(p, samples, values, n_rows, n_cols, out, values ? XHIST_F64 : XHIST_I64, shape.dense)) return rc;
+  if (!outs_ok && (shape.dense || n_rows * p->n_bins > 0)) return fail(XHIST_ERR_INVALID, "%s", outs_missing);
   if (mem_kind != XHIST_MEM_DEVICE)
     return fail(XHIST_ERR_INVALID, "%s takes DEVICE arrays (mem_kind XHIST_MEM_DEVICE); upload host data first", name);
-  if (n_rows * p->n_bins == 0) return XHIST_OK;
+  if (n_rows == 0 || (!shape.dense && p->n_bins == 0)) return XHIST_OK;
   DeviceGuard g;
   if (int rc = g.set(p->device)) return rc;
   Range r(name);
@@ -406,8 +433,8 @@ extern "C" int xhist_plan_execute_quantile_weighted(xhist_plan* p, const xhist_a
                         mem_kind, stream, [&](const ValuesCall& k) { return xhist_quantile_w_run(k, q, n_q, out); });
 }
 
-// The per-sample maps (xhist_map.hip): the same front; `out` is the dense [n_rows, n_cols] block, so a call without columns
-// has nothing to write.
+// The per-sample maps (xhist_map.hip): a dense call that may come without values; `out` is the [n_rows, n_cols] block.  (A call
+// without columns names its block all the same where the plan has bins, as it has since the maps came.)
 extern "C" int xhist_plan_execute_map(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows,
                                       int64_t n_cols, int op, const double* centre, const double* scale, void* out, int mem_kind,
                                       void* stream) {
@@ -416,136 +443,63 @@ extern "C" int xhist_plan_execute_map(xhist_plan* p, const xhist_array* samples,
   if (op != XHIST_MAP_ANOMALY && values) return fail(XHIST_ERR_INVALID, "only XHIST_MAP_ANOMALY takes values");
   if (op == XHIST_MAP_INDEX && (centre || scale)) return fail(XHIST_ERR_INVALID, "XHIST_MAP_INDEX takes no table");
   if (op == XHIST_MAP_TAKE && scale) return fail(XHIST_ERR_INVALID, "XHIST_MAP_TAKE takes no scale table");
-  const bool work = p && n_rows > 0 && n_cols > 0 && p->n_bins > 0;
-  const int rc = execute_values(p, "xhist_plan_execute_map", samples, values, nullptr, nullptr, n_rows, n_cols, static_cast<double*>(out),
-                                !work || op == XHIST_MAP_INDEX || centre != nullptr, "the table (centre) is NULL", mem_kind, stream,
-                                [&](const ValuesCall& k) { return xhist_map_run(k, op, centre, scale, out); }, false);
-  if (rc != XHIST_OK || p->n_bins > 0 || n_rows <= 0 || n_cols <= 0) return rc;
-  // A plan without bins (an edge array of a single edge) counts no sample, and the statistics' front has no output row to launch
-  // over: the block is still written, -1 for XHIST_MAP_INDEX and NaN for the others.  Bytes of all ones are both.
-  if (!out) return fail(XHIST_ERR_INVALID, "out is NULL");
-  DeviceGuard g;
-  if (int grc = g.set(p->device)) return grc;
-  HIPC(hipMemsetAsync(out, 0xff, (size_t)n_rows * (size_t)n_cols * 8, static_cast<hipStream_t>(stream)));
-  return XHIST_OK;
+  const bool rows = p && n_rows > 0, work = rows && n_cols > 0 && p->n_bins > 0;
+  const char* const missing = rows && (n_cols > 0 || p->n_bins > 0) && !out       ? "out is NULL"
+                              : work && op != XHIST_MAP_INDEX && !centre ? "the table (centre) is NULL"
+                                                                         : nullptr;
+  return execute_values(p, "xhist_plan_execute_map", samples, values, nullptr, nullptr, n_rows, n_cols, nullptr, !missing, missing, mem_kind,
+                        stream, [&](const ValuesCall& k) { return xhist_map_run(k, op, centre, scale, out); }, {false, true, nullptr});
 }
 
-// bin_order (xhist_group.hip): the same front without values.  A plan without bins drops every sample: one offset of 0 per row,
-// and every row's order is its positions (the statistics' front has no output row to launch over, as for the maps).
+// bin_order (xhist_group.hip): a dense call without values, the order [n_rows, n_cols] and the offsets [n_rows, n_bins + 1].
 extern "C" int xhist_plan_execute_group(xhist_plan* p, const xhist_array* samples, int64_t n_rows, int64_t n_cols, int64_t* out_order,
                                         int64_t* out_offsets, int mem_kind, void* stream) {
-  if (p && n_cols >= ((int64_t)1 << 31))
-    return fail(XHIST_ERR_UNSUPPORTED, "bin_order takes fewer than 2^31 samples per output row (a row's offsets are held in 32 bits), got %lld",
-                (long long)n_cols);
-  const bool work = p && n_rows > 0 && n_cols > 0;
-  if (work && !out_order) return fail(XHIST_ERR_INVALID, "out_order is NULL");
-  static int64_t no_columns;  // (what validate_arrays sees of a call without columns: the block has no element)
-  const int rc = execute_values(p, "xhist_plan_execute_group", samples, nullptr, nullptr, nullptr, n_rows, n_cols,
-                                reinterpret_cast<double*>(out_order ? out_order : &no_columns), out_offsets != nullptr, "out_offsets is NULL",
-                                mem_kind, stream, [&](const ValuesCall& k) { return xhist_group_run(k, out_order, out_offsets); }, false);
-  if (rc != XHIST_OK || p->n_bins > 0 || n_rows <= 0) return rc;
-  if (!out_offsets) return fail(XHIST_ERR_INVALID, "out_offsets is NULL");
-  DeviceGuard g;
-  if (int grc = g.set(p->device)) return grc;
-  if (int grc = xhist_group_no_bins(n_rows, n_cols, out_order, out_offsets, static_cast<hipStream_t>(stream)))
-    return fail(grc, "xhist_plan_execute_group: the launch over a plan without bins failed");
-  return XHIST_OK;
+  const char* const missing = n_rows > 0 && n_cols > 0 && !out_order ? "out_order is NULL" : n_rows > 0 && !out_offsets ? "out_offsets is NULL" : nullptr;
+  return execute_values(p, "xhist_plan_execute_group", samples, nullptr, nullptr, nullptr, n_rows, n_cols, nullptr, !missing, missing, mem_kind,
+                        stream, [&](const ValuesCall& k) { return xhist_group_run(k, out_order, out_offsets); }, {false, true, "bin_order"});
 }
 
-// bin_sort (xhist_sort.hip): bin_order's front with values.  A plan without bins still has work to do, the whole row sorted by
-// value: the statistics' front has no output row to launch over, so the record of that call is made here.
+// bin_sort (xhist_sort.hip): bin_order's call with values.
 extern "C" int xhist_plan_execute_sort(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
                                        int descending, int64_t* out_order, int64_t* out_offsets, int mem_kind, void* stream) {
-  if (p && n_cols >= ((int64_t)1 << 31))
-    return fail(XHIST_ERR_UNSUPPORTED, "bin_sort takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), got %lld",
-                (long long)n_cols);
-  if (p && p->n_bins + 1 > ((int64_t)1 << 32))
-    return fail(XHIST_ERR_UNSUPPORTED, "bin_sort takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
-                (long long)p->n_bins);
-  const bool work = p && n_rows > 0 && n_cols > 0;
-  if (work && !out_order) return fail(XHIST_ERR_INVALID, "out_order is NULL");
-  static int64_t no_columns;  // (what validate_arrays sees of a call without columns: the block has no element)
-  const int rc = execute_values(p, "xhist_plan_execute_sort", samples, values, nullptr, nullptr, n_rows, n_cols,
-                                reinterpret_cast<double*>(out_order ? out_order : &no_columns), out_offsets != nullptr, "out_offsets is NULL",
-                                mem_kind, stream, [&](const ValuesCall& k) { return xhist_sort_run(k, descending, out_order, out_offsets); });
-  if (rc != XHIST_OK || p->n_bins > 0 || n_rows <= 0) return rc;
-  if (!out_offsets) return fail(XHIST_ERR_INVALID, "out_offsets is NULL");
-  DeviceGuard g;
-  if (int grc = g.set(p->device)) return grc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ScratchScope scratch(s);
-  char err[256] = {0}, desc[384] = {0};
-  const ValuesCall call = {values_plan(p), samples, values, nullptr, nullptr, n_rows, n_cols, s, err, sizeof err, desc, sizeof desc,
-                           values_scratch_alloc, &scratch};
-  if (int src = xhist_sort_run(call, descending, out_order, out_offsets)) return fail(src, "%s", err);
-  std::lock_guard<std::mutex> lk(p->mu);
-  p->desc = desc;
-  return XHIST_OK;
+  const char* const missing = n_rows > 0 && n_cols > 0 && !out_order ? "out_order is NULL" : n_rows > 0 && !out_offsets ? "out_offsets is NULL" : nullptr;
+  return execute_values(p, "xhist_plan_execute_sort", samples, values, nullptr, nullptr, n_rows, n_cols, nullptr, !missing, missing, mem_kind,
+                        stream, [&](const ValuesCall& k) { return xhist_sort_run(k, descending, out_order, out_offsets); },
+                        {true, true, "bin_sort"});
 }
 
-// bin_rank (xhist_rank.hip): the maps' front, with values.  A plan without bins counts no sample and the statistics' front has no
-// output row to launch over: the block is filled with NaN here, bytes of all ones, as for the maps.
+// bin_rank (xhist_rank.hip): a dense call with values, `out` the [n_rows, n_cols] block.  The method is refused here, ahead of
+// the sorted order's limits.
 extern "C" int xhist_plan_execute_rank(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
                                        int method, int descending, int pct, double* out, int mem_kind, void* stream) {
   if (method < XHIST_RANK_AVERAGE || method > XHIST_RANK_ORDINAL) return fail(XHIST_ERR_INVALID, "unknown rank method %d", method);
-  if (p && n_cols >= ((int64_t)1 << 31))
-    return fail(XHIST_ERR_UNSUPPORTED, "bin_rank takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), got %lld",
-                (long long)n_cols);
-  if (p && p->n_bins + 1 > ((int64_t)1 << 32))
-    return fail(XHIST_ERR_UNSUPPORTED, "bin_rank takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
-                (long long)p->n_bins);
-  const bool work = p && n_rows > 0 && n_cols > 0;
-  if (work && !out) return fail(XHIST_ERR_INVALID, "out is NULL");
-  static double no_columns;  // (what validate_arrays sees of a call without columns: the block has no element)
-  const int rc = execute_values(p, "xhist_plan_execute_rank", samples, values, nullptr, nullptr, n_rows, n_cols, out ? out : &no_columns, true,
-                                "", mem_kind, stream, [&](const ValuesCall& k) { return xhist_rank_run(k, method, descending, pct, out); });
-  if (rc != XHIST_OK || p->n_bins > 0 || !work) return rc;
-  DeviceGuard g;
-  if (int grc = g.set(p->device)) return grc;
-  HIPC(hipMemsetAsync(out, 0xff, (size_t)n_rows * (size_t)n_cols * 8, static_cast<hipStream_t>(stream)));
-  return XHIST_OK;
+  return execute_values(p, "xhist_plan_execute_rank", samples, values, nullptr, nullptr, n_rows, n_cols, nullptr,
+                        out || n_rows <= 0 || n_cols <= 0, "out is NULL", mem_kind, stream,
+                        [&](const ValuesCall& k) { return xhist_rank_run(k, method, descending, pct, out); }, {true, true, "bin_rank"});
 }
 
-// histogram_mode (xhist_rank.hip): the statistics' front, four [n_rows, n_bins] planes.  The sort's two size limits are refused
-// here as well, before the front looks at anything else.
+// histogram_mode (xhist_rank.hip): four [n_rows, n_bins] planes behind the sorted order's limits.
 extern "C" int xhist_plan_execute_mode(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
                                        int64_t* out_count, int64_t* out_nunique, double* out_mode, int64_t* out_mode_count, int mem_kind,
                                        void* stream) {
-  if (p && n_cols >= ((int64_t)1 << 31))
-    return fail(XHIST_ERR_UNSUPPORTED, "histogram_mode takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), "
-                                       "got %lld", (long long)n_cols);
-  if (p && p->n_bins + 1 > ((int64_t)1 << 32))
-    return fail(XHIST_ERR_UNSUPPORTED, "histogram_mode takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
-                (long long)p->n_bins);
   return execute_values(p, "xhist_plan_execute_mode", samples, values, nullptr, nullptr, n_rows, n_cols, out_mode,
                         out_count && out_nunique && out_mode_count, "out_count / out_nunique / out_mode_count is NULL", mem_kind, stream,
-                        [&](const ValuesCall& k) { return xhist_mode_run(k, out_count, out_nunique, out_mode, out_mode_count); });
+                        [&](const ValuesCall& k) { return xhist_mode_run(k, out_count, out_nunique, out_mode, out_mode_count); },
+                        {true, false, "histogram_mode"});
 }
 
-// bin_unique (xhist_rank.hip): bin_rank's front with four blocks.  A plan without bins has no entry and counts no sample, and the
-// statistics' front has no output row to launch over: offsets of 0, padding and an inverse of -1 are written from here.
+// bin_unique (xhist_rank.hip): a dense call with values and four blocks, the inverse optional.  The size is refused here, ahead
+// of the sorted order's limits.
 extern "C" int xhist_plan_execute_unique(xhist_plan* p, const xhist_array* samples, const xhist_array* values, int64_t n_rows, int64_t n_cols,
                                          int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets, int64_t* out_inverse,
                                          int mem_kind, void* stream) {
   if (size < 0) return fail(XHIST_ERR_INVALID, "bin_unique takes a size of 0 or more, got %lld", (long long)size);
-  if (p && n_cols >= ((int64_t)1 << 31))
-    return fail(XHIST_ERR_UNSUPPORTED, "bin_unique takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), "
-                                       "got %lld", (long long)n_cols);
-  if (p && p->n_bins + 1 > ((int64_t)1 << 32))
-    return fail(XHIST_ERR_UNSUPPORTED, "bin_unique takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
-                (long long)p->n_bins);
-  if (p && n_rows > 0 && !out_offsets) return fail(XHIST_ERR_INVALID, "out_offsets is NULL");
-  if (p && n_rows > 0 && size > 0 && !(out_uniques && out_counts)) return fail(XHIST_ERR_INVALID, "out_uniques / out_counts is NULL");
-  static double no_rows;  // (what validate_arrays sees of a call without rows: the block has no element)
-  const int rc = execute_values(p, "xhist_plan_execute_unique", samples, values, nullptr, nullptr, n_rows, n_cols,
-                                out_offsets ? reinterpret_cast<double*>(out_offsets) : &no_rows, true, "", mem_kind, stream,
-                                [&](const ValuesCall& k) { return xhist_unique_run(k, size, out_uniques, out_counts, out_offsets, out_inverse); });
-  if (rc != XHIST_OK || p->n_bins > 0 || n_rows <= 0) return rc;
-  DeviceGuard g;
-  if (int grc = g.set(p->device)) return grc;
-  if (int grc = xhist_unique_no_bins(n_rows, n_cols, size, out_uniques, out_counts, out_offsets, out_inverse, static_cast<hipStream_t>(stream)))
-    return fail(grc, "xhist_plan_execute_unique: the launches over a plan without bins failed");
-  return XHIST_OK;
+  const char* const missing = n_rows > 0 && !out_offsets                             ? "out_offsets is NULL"
+                              : n_rows > 0 && size > 0 && !(out_uniques && out_counts) ? "out_uniques / out_counts is NULL"
+                                                                                       : nullptr;
+  return execute_values(p, "xhist_plan_execute_unique", samples, values, nullptr, nullptr, n_rows, n_cols, nullptr, !missing, missing, mem_kind,
+                        stream, [&](const ValuesCall& k) { return xhist_unique_run(k, size, out_uniques, out_counts, out_offsets, out_inverse); },
+                        {true, true, "bin_unique"});
 }
 
 // ------------------------------------------------------------------------------------------

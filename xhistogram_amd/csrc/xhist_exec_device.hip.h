@@ -5,8 +5,9 @@
 // ------------------------------------------------------------------------------------------
 // device-resident execute
 // ------------------------------------------------------------------------------------------
+// `out_checked`: the caller answers for its outputs itself (they are no [n_rows, n_bins] planes), and `out` is not looked at
 static int validate_arrays(const xhist_plan* p, const xhist_array* samples, const xhist_array* weights, int64_t n_rows,
-                           int64_t n_cols, const void* out, int out_dtype) {
+                           int64_t n_cols, const void* out, int out_dtype, bool out_checked = false) {
   if (!p) return fail(XHIST_ERR_INVALID, "plan is NULL");
   if (!samples) return fail(XHIST_ERR_INVALID, "samples is NULL");
   if (n_rows < 0 || n_cols < 0) return fail(XHIST_ERR_INVALID, "negative shape");
@@ -33,7 +34,7 @@ static int validate_arrays(const xhist_plan* p, const xhist_array* samples, cons
   } else if (out_dtype != XHIST_I64) {
     return fail(XHIST_ERR_INVALID, "unweighted histograms are int64 (out_dtype XHIST_I64)");
   }
-  if (!out && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "out is NULL");
+  if (!out_checked && !out && n_rows * p->n_bins > 0) return fail(XHIST_ERR_INVALID, "out is NULL");
   return XHIST_OK;
 }
 

@@ -8,7 +8,9 @@
 //   group_identity                                                                              1
 //
 // Step 0 is bin_index itself: xhist_map_run(k, XHIST_MAP_INDEX) writes the int64 keys of the call into a scratch block, so every
-// dtype, layout, compare domain and input count of bin_index is bin_order's.  The engine reads that block.
+// dtype, layout, compare domain and input count of bin_index is bin_order's.  The engine reads that block.  A call without columns
+// and a plan without bins run neither: the driver zeroes the offsets, and where there are columns group_identity writes every
+// row's positions as its order.
 //
 // Scratch of a call, from k.scratch:  n_rows * n_cols * 8 bytes of keys  +  n_rows * chunks * (B + 1) * 4 bytes of counters  +,
 // where a row is cut, n_rows * ceil(chunks / 64) * (B + 1) * 4 bytes of slice totals.
@@ -98,16 +100,18 @@ int xhist_runs_scan(const ValuesCall& k, const RunsParams& p, const char* who) {
 int xhist_group_run(const ValuesCall& k, int64_t* out_order, int64_t* out_offsets) {
   const ValuesPlan& pl = k.pl;
   const int64_t nb1 = pl.n_bins + 1;
-  if (k.n_cols >= ((int64_t)1 << 31))
-    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_order takes fewer than 2^31 samples per output row (a row's offsets are held in 32 bits), "
-                                         "got %lld", (long long)k.n_cols);
   if ((size_t)nb1 * 4 > pl.lds_max)
     return k.fail(XHIST_ERR_UNSUPPORTED, "bin_order takes at most %lld bins (a wave keeps one 4-byte counter per bin and one more in the "
                                          "%zu bytes of LDS of a workgroup), got %lld",
                   (long long)(pl.lds_max / 4 - 1), pl.lds_max, (long long)pl.n_bins);
-  if (k.n_cols == 0) {
+  if (k.n_cols == 0 || pl.n_bins == 0) {
     if (hipMemsetAsync(out_offsets, 0, (size_t)(k.n_rows * nb1) * 8, k.stream) != hipSuccess)
       return k.fail(XHIST_ERR_HIP, "group: zeroing the offsets failed");
+    if (const int64_t n = k.n_rows * k.n_cols) {  // a plan without bins drops every sample: every row's order is its positions
+      const int grid = (int)std::min<int64_t>(2048, (n + 255) / 256);
+      XH_VALUES_LAUNCH(group_identity, dim3(grid), dim3(256), 0, k.stream, out_order, k.n_cols, n);
+      XH_VALUES_LAUNCH_CHECK(k, "group_identity launch");
+    }
     k.describe("group keys=none bits=0 waves=0 block=0 chunks=0 chunk=0 lds_bytes=0 rows_per_launch=0 D=%d cmp=%d", pl.n_dims, values_cmp(pl));
     return XHIST_OK;
   }
@@ -136,16 +140,5 @@ int xhist_group_run(const ValuesCall& k, int64_t* out_order, int64_t* out_offset
   }
   k.describe("group keys=%s bits=%d waves=%d block=%d chunks=%lld chunk=%lld lds_bytes=%zu rows_per_launch=%lld D=%d cmp=%d", family,
              g.bits, g.waves, block, (long long)g.chunks, (long long)g.chunk, g.lds_bytes, (long long)g.max_rows, pl.n_dims, values_cmp(pl));
-  return XHIST_OK;
-}
-
-int xhist_group_no_bins(int64_t n_rows, int64_t n_cols, int64_t* out_order, int64_t* out_offsets, hipStream_t stream) {
-  if (hipMemsetAsync(out_offsets, 0, (size_t)n_rows * 8, stream) != hipSuccess) return XHIST_ERR_HIP;
-  const int64_t n = n_rows * n_cols;
-  if (n > 0) {
-    const int grid = (int)std::min<int64_t>(2048, (n + 255) / 256);
-    XH_VALUES_LAUNCH(group_identity, dim3(grid), dim3(256), 0, stream, out_order, n_cols, n);
-    if (hipGetLastError() != hipSuccess) return XHIST_ERR_HIP;
-  }
   return XHIST_OK;
 }

@@ -25,7 +25,10 @@ static const char* map_op_name(int op) { return op == kMapIndex ? "index" : op =
 
 int xhist_map_run(const ValuesCall& k, int op, const double* centre, const double* scale, void* out) {
   const ValuesPlan& pl = k.pl;
-  if (k.n_cols == 0) {
+  if (k.n_cols == 0 || pl.n_bins == 0) {
+    // a plan without bins counts no sample: -1 for XHIST_MAP_INDEX and NaN for the others.  Bytes of all ones are both.
+    if (k.n_cols > 0 && hipMemsetAsync(out, 0xff, (size_t)(k.n_rows * k.n_cols) * 8, k.stream) != hipSuccess)
+      return k.fail(XHIST_ERR_HIP, "map: filling out failed");
     k.describe("map op=%s family=none table=none scan=0 cmp=%d segs=0 block=0 lds_bytes=0 tables_in_lds=0 scale=%d D=%d", map_op_name(op),
                values_cmp(pl), scale ? 1 : 0, pl.n_dims);
     return XHIST_OK;

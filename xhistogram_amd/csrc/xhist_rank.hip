@@ -13,7 +13,9 @@
 // fill of the slots with 0, mode_runs, mode_finish for histogram_mode.  A bin_rank call without columns or a plan without bins
 // fills out with NaN (bytes of all ones) and launches nothing; a histogram_mode call without columns launches mode_finish alone.
 // bin_unique's tail is unique_bins, unique_scan, unique_runs, unique_pad (a width above 0) and unique_inverse (an inverse); a call
-// without columns or a plan without bins zeroes the offsets and launches unique_pad alone.
+// without columns or a plan without bins zeroes the offsets and launches unique_pad alone.  Each of these empty cases is its
+// driver's own branch and leaves its own "none" line; the C ABI's front has refused the sorted order's two limits, an unknown
+// method and a negative size before a driver runs.
 //
 // Scratch of a call, from k.scratch, on top of the sort's 32 bytes per sample: 8 bytes per sample of order, n_rows * (B + 1) * 8
 // bytes of offsets, per 64 samples of a row 28 bytes (the head word, the NaN word, and before / last / next), per 65536 samples
@@ -108,13 +110,6 @@ static int sorted_domain_run(const ValuesCall& k, const char* who, int method, i
 int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, double* out) {
   const ValuesPlan& pl = k.pl;
   const int64_t nb = pl.n_bins;
-  if (method < XHIST_RANK_AVERAGE || method > XHIST_RANK_ORDINAL) return k.fail(XHIST_ERR_INVALID, "unknown rank method %d", method);
-  if (k.n_cols >= ((int64_t)1 << 31))
-    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_rank takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), "
-                                         "got %lld", (long long)k.n_cols);
-  if (nb + 1 > ((int64_t)1 << 32))
-    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_rank takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
-                  (long long)nb);
   const int64_t n = k.n_rows * k.n_cols;
   if (k.n_cols == 0 || nb == 0) {
     if (n > 0 && hipMemsetAsync(out, 0xff, (size_t)n * 8, k.stream) != hipSuccess) return k.fail(XHIST_ERR_HIP, "rank: filling out with NaN failed");
@@ -141,12 +136,6 @@ int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, dou
 
 int xhist_mode_run(const ValuesCall& k, int64_t* out_count, int64_t* out_nunique, double* out_mode, int64_t* out_mode_count) {
   const int64_t nb = k.pl.n_bins;
-  if (k.n_cols >= ((int64_t)1 << 31))
-    return k.fail(XHIST_ERR_UNSUPPORTED, "histogram_mode takes fewer than 2^31 samples per output row (a row's positions are held in 32 "
-                                         "bits), got %lld", (long long)k.n_cols);
-  if (nb + 1 > ((int64_t)1 << 32))
-    return k.fail(XHIST_ERR_UNSUPPORTED, "histogram_mode takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
-                  (long long)nb);
   auto params = [&](const RankParams& rp, int64_t r0) {
     ModeParams mp;
     mp.r = rp;
@@ -206,24 +195,12 @@ static int unique_nothing(int64_t n_rows, int64_t n_cols, int64_t nb, int64_t si
   return XHIST_OK;
 }
 
-int xhist_unique_no_bins(int64_t n_rows, int64_t n_cols, int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets,
-                         int64_t* out_inverse, hipStream_t stream) {
-  return unique_nothing(n_rows, n_cols, 0, size, out_uniques, out_counts, out_offsets, out_inverse, stream);
-}
-
 int xhist_unique_run(const ValuesCall& k, int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets,
                      int64_t* out_inverse) {
   const int64_t nb = k.pl.n_bins, nb1 = nb + 1;
-  if (size < 0) return k.fail(XHIST_ERR_INVALID, "bin_unique takes a size of 0 or more, got %lld", (long long)size);
-  if (k.n_cols >= ((int64_t)1 << 31))
-    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_unique takes fewer than 2^31 samples per output row (a row's positions are held in 32 "
-                                         "bits), got %lld", (long long)k.n_cols);
-  if (nb1 > ((int64_t)1 << 32))
-    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_unique takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
-                  (long long)nb);
-  if (k.n_cols == 0) {
-    if (unique_nothing(k.n_rows, 0, nb, size, out_uniques, out_counts, out_offsets, nullptr, k.stream) != XHIST_OK)
-      return k.fail(XHIST_ERR_HIP, "unique: writing the outputs of a call without columns failed");
+  if (k.n_cols == 0 || nb == 0) {
+    if (unique_nothing(k.n_rows, k.n_cols, nb, size, out_uniques, out_counts, out_offsets, out_inverse, k.stream) != XHIST_OK)
+      return k.fail(XHIST_ERR_HIP, "unique: writing the outputs of a call without columns or bins failed");
     k.describe("unique size=%lld inverse=%d words=0 rows_per_launch=0 | none", (long long)size, out_inverse ? 1 : 0);
     return XHIST_OK;
   }

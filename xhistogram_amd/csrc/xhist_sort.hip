@@ -59,13 +59,7 @@ static const char* sort_dtype_name(int dt) {
 // bins wrote beside the order (scratch of the call, alive until the call returns) and the rows of a launch.
 int xhist_sort_run(const ValuesCall& k, int descending, int64_t* out_order, int64_t* out_offsets, SortHandover* hand) {
   const ValuesPlan& pl = k.pl;
-  const int64_t nb = pl.n_bins, nb1 = nb + 1;
-  if (k.n_cols >= ((int64_t)1 << 31))
-    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_sort takes fewer than 2^31 samples per output row (a row's positions are held in 32 bits), "
-                                         "got %lld", (long long)k.n_cols);
-  if (nb1 > ((int64_t)1 << 32))
-    return k.fail(XHIST_ERR_UNSUPPORTED, "bin_sort takes at most 2^32 - 1 bins (a bin key is sorted in four 8-bit digits), got %lld",
-                  (long long)nb);
+  const int64_t nb = pl.n_bins, nb1 = nb + 1;  // (n_cols < 2^31 and nb1 <= 2^32: the front has refused the rest)
   const int vdt = k.values->dtype;
   int bin_bits = 0;
   while (((int64_t)1 << bin_bits) < nb1) ++bin_bits;

@@ -69,9 +69,16 @@ struct ValuesCall {
   }
 };
 
-// The drivers: the launches of one statistic on k.stream, for DEVICE arrays the caller has validated, n_rows * n_bins > 0, the
-// plan's device current.  Each returns XHIST_OK, or an error status with a message in k.err, and writes a line about its
-// launches to k.desc.  Outputs are [n_rows, n_bins] planes of 8-byte elements, or blocks [planes, n_rows, n_bins] of them.
+// The drivers: the launches of one statistic on k.stream, for DEVICE arrays the caller has validated, the plan's device current.
+// Each returns XHIST_OK, or an error status with a message in k.err, and writes a line about its launches to k.desc.  They are
+// reached through execute_values alone, under one of two contracts:
+//   planes  outputs are [n_rows, n_bins] planes of 8-byte elements, or blocks [planes, n_rows, n_bins] of them: n_rows * n_bins > 0,
+//           n_cols >= 0
+//   dense   outputs are dense [n_rows, n_cols] or CSR blocks (xhist_map_run, xhist_group_run, xhist_sort_run, xhist_rank_run,
+//           xhist_unique_run): n_rows > 0, n_cols >= 0 and n_bins >= 0.  A call without columns and a plan without bins are the
+//           driver's own branches: it writes every element the outputs still have and a line with "none" in it.
+// For the drivers behind the sorted order (sort, rank, mode, unique; group for the first) the front has refused n_cols >= 2^31
+// and n_bins + 1 > 2^32, XHIST_ERR_UNSUPPORTED, and an unknown rank method and a negative size, XHIST_ERR_INVALID.
 
 // xhist_extrema.hip: minimum and maximum (prepare, binning, finalize; `accumulate`: the outputs hold an earlier result), and
 // histogram_argextrema (the two prepares, pass 1, pass 2, finalize): out_values [2] (minimum, maximum), out_index [2] int64
@@ -103,16 +110,16 @@ int xhist_quantile_w_run(const ValuesCall& k, const double* q, int n_q, double* 
 
 // xhist_map.hip: the per-sample maps.  op is XHIST_MAP_INDEX (k.values nullptr, no table), XHIST_MAP_TAKE (k.values nullptr,
 // centre the table) or XHIST_MAP_ANOMALY (k.values the values, centre the means, scale nullptr or the standard deviations);
-// centre and scale are float64 [n_rows, n_bins], out a dense [n_rows, n_cols] block of 8-byte elements, each written once.
+// centre and scale are float64 [n_rows, n_bins], out a dense [n_rows, n_cols] block of 8-byte elements, each written once (a
+// plan without bins: bytes of all ones, -1 and NaN).
 int xhist_map_run(const ValuesCall& k, int op, const double* centre, const double* scale, void* out);
 
 // xhist_group.hip: bin_order, the stable group-by of a row's samples by bin (k.values nullptr).  out_order is a dense int64
 // [n_rows, n_cols] block, out_offsets int64 [n_rows, n_bins + 1]; every element of both is written exactly once.  The keys are
-// xhist_map_run's XHIST_MAP_INDEX block, in scratch from k.alloc with the counter table.  XHIST_ERR_UNSUPPORTED for k.n_cols >=
-// 2^31 and for (n_bins + 1) * 4 bytes beyond the LDS of a workgroup, before any launch.  xhist_group_no_bins: a plan without
-// bins, which the statistics' front does not launch over (offsets [n_rows, 1] of zeros, every row's order its positions).
+// xhist_map_run's XHIST_MAP_INDEX block, in scratch from k.alloc with the counter table.  A plan without bins: offsets
+// [n_rows, 1] of zeros, every row's order its positions.  XHIST_ERR_UNSUPPORTED for (n_bins + 1) * 4 bytes beyond the LDS of a
+// workgroup, before any launch.
 int xhist_group_run(const ValuesCall& k, int64_t* out_order, int64_t* out_offsets);
-int xhist_group_no_bins(int64_t n_rows, int64_t n_cols, int64_t* out_order, int64_t* out_offsets, hipStream_t stream);
 // xhist_group.hip: the scan of the count / scan / scatter engine (xhist_runs.hip.h) for one batch of rows, whose kernels that unit
 // alone defines: totals where a row is cut into several chunks, scan, bases where it is cut.  It turns the counters the count
 // kernel wrote into the bases the scatter kernel reads, and writes p.offsets where that is not nullptr.  A width of 256 runs the
@@ -122,8 +129,7 @@ int xhist_runs_scan(const ValuesCall& k, const xhist::RunsParams& p, const char*
 // xhist_sort.hip: bin_sort, a row's samples grouped by bin and sorted by value inside each bin (k.values the values; `descending`
 // nonzero: largest first, NaN still last).  The outputs are bin_order's; every element of both is written exactly once.  A
 // stable radix sort on 8-bit digits of (value key, position), then of the gathered bin keys: 32 bytes of scratch per sample
-// from k.alloc.  Unlike the other drivers it also takes a plan without bins (n_bins 0: the whole row sorted by value, one
-// offset of 0 per row).  XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for n_bins + 1 > 2^32, before any launch.
+// from k.alloc.  A plan without bins: the whole row sorted by value, one offset of 0 per row.
 // `hand` (nullptr: nobody asks) receives what bin_rank takes over from the sort: the sorted bin keys [n_rows, n_cols], each in
 // [0, n_bins], in scratch of the call (nullptr for a plan without bins), and the rows of one launch.
 struct SortHandover {
@@ -138,9 +144,8 @@ int xhist_sort_run(const ValuesCall& k, int descending, int64_t* out_order, int6
 // written exactly once; NaN for a sample that is not counted and for a NaN value.  It runs xhist_sort_run into scratch and
 // six kernels over the sorted order.  Scratch from k.alloc, one block on top of the sort's 32 bytes per sample: 8 bytes per
 // sample of order, n_rows * (n_bins + 1) * 8 bytes of offsets, 28 bytes per 64 samples of head and NaN words with their three
-// uint32 scalars, 12 bytes per 65536 samples of tile scalars, and n_rows * n_bins * 8 bytes of divisors when pct.  Like the
-// sort it takes a plan without bins (all NaN).
-// XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for n_bins + 1 > 2^32, XHIST_ERR_INVALID for an unknown method, before any launch.
+// uint32 scalars, 12 bytes per 65536 samples of tile scalars, and n_rows * n_bins * 8 bytes of divisors when pct.  A plan
+// without bins: all NaN, bytes of all ones.
 int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, double* out);
 
 // xhist_rank.hip: histogram_mode, per (row, bin) the number of non-NaN values, the number of distinct ones (IEEE ==), the most
@@ -148,8 +153,7 @@ int xhist_rank_run(const ValuesCall& k, int method, int descending, int pct, dou
 // how often it occurs (k.values the values).  Four [n_rows, n_bins] planes, int64 but out_mode; an empty bin gets 0, 0, NaN
 // (0x7ff8000000000000) and 0; every element is written exactly once.  It runs xhist_sort_run into scratch, the four kernels
 // that build bin_rank's sorted domain and two of its own.  Scratch from k.alloc is bin_rank's without the divisors; the slots
-// of the atomic maximum are the out_mode_count block, zeroed by the call.  XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for
-// n_bins + 1 > 2^32, before any launch.
+// of the atomic maximum are the out_mode_count block, zeroed by the call.
 int xhist_mode_run(const ValuesCall& k, int64_t* out_count, int64_t* out_nunique, double* out_mode, int64_t* out_mode_count);
 
 // xhist_rank.hip: bin_unique, per row the distinct non-NaN values of every bin in CSR form (k.values the values; equality is
@@ -159,10 +163,7 @@ int xhist_mode_run(const ValuesCall& k, int64_t* out_count, int64_t* out_nunique
 // and 0), entries from `size` on are stored nowhere; out_inverse (nullptr: none) int64 [n_rows, n_cols] in position order: the
 // sample's entry, beyond `size` too, -1 for a sample that is not counted and for a NaN value.  Every element of every output is
 // written and nothing outside them.  It runs xhist_sort_run into scratch, the four kernels that build bin_rank's sorted domain
-// and up to five of its own; scratch from k.alloc is bin_rank's without the divisors.  XHIST_ERR_INVALID for a negative size,
-// XHIST_ERR_UNSUPPORTED for k.n_cols >= 2^31 and for n_bins + 1 > 2^32, before any launch.  xhist_unique_no_bins: a plan without
-// bins, which the statistics' front does not launch over (offsets [n_rows, 1] of zeros, padding, an inverse of -1).
+// and up to five of its own; scratch from k.alloc is bin_rank's without the divisors.  A call without columns and a plan without
+// bins: offsets of zeros, padding, an inverse of -1.  size >= 0.
 int xhist_unique_run(const ValuesCall& k, int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets,
                      int64_t* out_inverse);
-int xhist_unique_no_bins(int64_t n_rows, int64_t n_cols, int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets,
-                         int64_t* out_inverse, hipStream_t stream);
