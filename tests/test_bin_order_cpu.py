@@ -208,7 +208,7 @@ def test_public_surface():
 
 
 def _no_device_work(monkeypatch, core):
-    for fn in ("_upload_host", "_value_views", "_get_plan", "_order_offsets_rows"):
+    for fn in ("_upload_host", "_value_views", "_get_plan", "_order_offsets_rows", "_launch_outputs"):
         monkeypatch.setattr(core, fn, lambda *a, **k: pytest.fail("device work"))
 
 
@@ -240,6 +240,76 @@ def test_refusals_before_any_device_work(monkeypatch):
     monkeypatch.setattr(core, "_values_call", lambda *a, **k: ("dask", [arr], None, e, [1], (1,)))
     with pytest.raises(ValueError, match="group orders of several chunks cannot be merged: rechunk the reduced axes"):
         core.bin_order(arr, bins=e, axis=1)
+
+
+@pytest.mark.parametrize("axis", [None, 2, 0, (0, 2), (2, 0), (1,)], ids=str)
+def test_sample_shape_undoes_rows_of(monkeypatch, axis):
+    """_value_views derives the kept and the reduced axes once; _sample_shape, fed those, puts a [rows, cols] block back where
+    the oracle's rows_of took it from"""
+    from xhistogram_amd import _native, core
+
+    class _Plan:
+        n_dims, n_bins, bins_shape = 1, 2, (2,)
+
+    a = np.arange(3 * 4 * 5).reshape(3, 4, 5)
+    like = type("_Like", (), dict(shape=a.shape, ndim=3, dtype=np.dtype(np.float64), device=0))()  # (a DeviceArray's face)
+
+    def rows_cols(arr, ax, full):
+        rows = bo.rows_of(a, ax)
+        return rows.reshape(-1, rows.shape[-1])
+
+    # no GPU: no device, no plan, no native views; every array takes the general route, a [rows, cols] block
+    monkeypatch.setattr(_native, "require_device", lambda device: None)
+    monkeypatch.setattr(_native, "make_view", lambda *v: v)
+    monkeypatch.setattr(core, "_get_plan", lambda *a: _Plan())
+    monkeypatch.setattr(core, "_collapse", lambda *a: None)
+    monkeypatch.setattr(core, "_rows_cols", rows_cols)
+    monkeypatch.setattr(core, "_strided_view", lambda block, backend: (block,))
+    rec = core._value_views([like], None, core._normalise_axis(axis, 3), [np.linspace(0, 1, 3)], "device", ordered=True)
+    red = list(range(3)) if axis is None else sorted(np.atleast_1d(axis).tolist())
+    assert list(rec.red) == red and list(rec.kept) == [i for i in range(3) if i not in red]
+    assert rec.kept_shape == tuple(1 if i in red else a.shape[i] for i in range(3))
+    rows = bo.rows_of(a, axis)
+    assert (rec.m, rec.c) == (rows.size // rows.shape[-1], rows.shape[-1]) and rec.backend == "device" and rec.like is like
+    np.testing.assert_array_equal(core._sample_shape(rows.reshape(rec.m, rec.c), a.shape, rec.kept, rec.red, "device"), a)
+
+
+def test_each_refusal_text_is_raised_from_one_function(monkeypatch):
+    """the limit of 2^31 samples per output row and the refusal of cut reduced axes: one function each, which the per-bin
+    statistics and the per-sample calls both go through"""
+    from xhistogram_amd import core
+
+    class Marker(Exception):
+        pass
+
+    def raise_marker(*a, **k):
+        raise Marker()
+
+    _no_device_work(monkeypatch, core)
+    e = [np.linspace(0, 1, 3)]
+    text = open(core.__file__).read()
+    assert text.count("samples per output row, got") == 1 and text.count("of several chunks cannot be merged") == 1
+    arr = _Shaped((3, 1 << 31))
+    calls = (lambda: core.histogram_sum(arr, values=arr, bins=e, axis=1), lambda: core.bin_order(arr, bins=e, axis=1))
+    for n_arrays, call in zip((2, 1), calls):
+        monkeypatch.setattr(core, "_values_call", lambda *a, n=n_arrays, **k: ("device", [arr] * n, None, e, [1], (1,)))
+        with pytest.raises(NotImplementedError, match=r"fewer than 2\^31 = 2147483648 samples per output row"):
+            call()
+    cut = _Shaped((4, 6), ((2, 2), (3, 3)))
+    for n_arrays, call in zip((2, 1), (lambda: core.histogram_sum(cut, values=cut, bins=e, axis=1), lambda: core.bin_order(cut, bins=e, axis=1))):
+        monkeypatch.setattr(core, "_values_call", lambda *a, n=n_arrays, **k: ("dask", [cut] * n, None, e, [1], (1,)))
+        with pytest.raises(ValueError, match="of several chunks cannot be merged"):
+            call()
+    monkeypatch.setattr(core, "_check_one_chunk", raise_marker)
+    for n_arrays, call in zip((2, 1), (lambda: core.histogram_sum(cut, values=cut, bins=e, axis=1), lambda: core.bin_order(cut, bins=e, axis=1))):
+        monkeypatch.setattr(core, "_values_call", lambda *a, n=n_arrays, **k: ("dask", [cut] * n, None, e, [1], (1,)))
+        with pytest.raises(Marker):
+            call()
+    monkeypatch.setattr(core, "_check_sizes", raise_marker)
+    for n_arrays, call in zip((2, 1), calls):
+        monkeypatch.setattr(core, "_values_call", lambda *a, n=n_arrays, **k: ("device", [arr] * n, None, e, [1], (1,)))
+        with pytest.raises(Marker):
+            call()
 
 
 def test_dask_with_a_cut_reduced_axis_is_refused_before_any_compute(monkeypatch):

@@ -212,7 +212,7 @@ def test_public_surface():
 
 
 def _no_device_work(monkeypatch, core):
-    for fn in ("_upload_host", "_value_views", "_get_plan", "_sample_block", "_resident"):
+    for fn in ("_upload_host", "_value_views", "_get_plan", "_sample_block", "_launch_outputs", "_resident"):
         monkeypatch.setattr(core, fn, lambda *a, **k: pytest.fail("device work"))
 
 

@@ -271,7 +271,7 @@ def test_public_surface():
 
 
 def _no_device_work(monkeypatch, core):
-    for fn in ("_upload_host", "_value_views", "_get_plan", "_order_offsets_rows", "_resident"):
+    for fn in ("_upload_host", "_value_views", "_get_plan", "_order_offsets_rows", "_launch_outputs", "_resident"):
         monkeypatch.setattr(core, fn, lambda *a, **k: pytest.fail("device work"))
 
 

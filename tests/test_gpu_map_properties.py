@@ -1,7 +1,7 @@
 """Property, thread and row-chunk tests of the three per-sample maps (bin_index, histogram_lookup, histogram_anomaly) on an
 MI355X: what tests/test_gpu_values_properties.py is to the ten per-bin statistics.  tests/test_gpu_map.py builds each case for
-one kernel; these walk the Python front of the maps (core._map_out, _table_on_device, _check_table_shape, the ordered route
-through _value_views) and the row-chunk loop of xhist_map_run, which is a copy of its own and not launch_values_pass.  Every
+one kernel; these walk the Python front of the maps (core._sample_call, _map_out, _launch_outputs, _table_on_device,
+_check_table_shape, the ordered route through _value_views) and the row-chunk loop of xhist_map_run, which is a copy of its own and not launch_values_pass.  Every
 comparison is bit for bit but one, the standardized anomaly on counts whose M2 rounds, which is held to an interval made of
 the project's existing bounds (map_oracle.standardized_bracket); there is no new tolerance.
 
@@ -146,7 +146,7 @@ def check_blocks(core, case):
     shape, d, edges = case["shape"], built.d, built.edges
     ndim = len(shape)
     rng = np.random.default_rng(case["seed"] + 2)
-    axis = onp.normalise_axis(case["axis"], ndim)  # (what _map_samples hands on)
+    axis = onp.normalise_axis(case["axis"], ndim)  # (what _sample_call hands on)
     red = set(vc.reduced_axes(case))
     kept = [i for i in range(ndim) if i not in red]
     cuts = [cuts_of(rng, n) for n in shape]

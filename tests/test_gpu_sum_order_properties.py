@@ -1,7 +1,7 @@
 """Property, thread, scratch and row-batch tests of histogram_sum and bin_order on an MI355X: what
 tests/test_gpu_values_properties.py is to the ten per-bin statistics and tests/test_gpu_map_properties.py to the maps.
 tests/test_gpu_sum.py and tests/test_gpu_bin_order.py build each case for one launch variant on contiguous arrays; these walk what
-feeds the launchers (core._value_views, _value_rows, _value_block, _upload_host, core._order_offsets_rows, _bin_order_block) and the row
+feeds the launchers (core._value_views, _value_rows, _value_block, _upload_host, core._order_offsets_rows, _launch_outputs, _bin_order_block) and the row
 loop of launch_values_pass, whose second iteration no other test reaches.  Every comparison is bit for bit or integer equality
 (totals by sum_cases.same_bits: zeros by value, NaN by place); there is no tolerance.  The cases, their data and what they
 claim are tests/sum_order_cases.py's, held to the oracles by tests/test_sum_order_cases_cpu.py.

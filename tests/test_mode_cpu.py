@@ -168,8 +168,8 @@ def test_the_table_entry():
     from xhistogram_amd import core
 
     st = core._VALUE_STATS["mode"]
-    assert (st.k, st.ints, st.method, st.ptrs, st.extras, st.reduce, st.tail, st.ordered, st.noun, st.max_cols) == (
-        4, (0, 1, 3), "execute_mode", (0, 1, 2, 3), 0, None, (), False, "modes", None)
+    assert (st.k, st.ints, st.method, st.ptrs, st.extras, st.reduce, st.tail, st.ordered, st.noun, st.max_cols, st.max_bins) == (
+        4, (0, 1, 3), "execute_mode", (0, 1, 2, 3), 0, None, (), False, "modes", 1 << 31, (1 << 32) - 1)  # (bin_sort's two limits)
     assert pickle.loads(pickle.dumps(st)) == st
     block = pickle.loads(pickle.dumps(partial(core._value_block, stat="mode")))  # (what a dask task carries)
     assert block.keywords == {"stat": "mode"}

@@ -234,8 +234,10 @@ def test_symbol_and_abi_versions_agree():
 def test_the_statistic_is_an_entry_of_the_stats_table():
     st = core._VALUE_STATS["sum"]
     assert (st.k, st.ints, st.method, st.ptrs, st.extras, st.reduce, st.noun) == (2, (0,), "execute_sum", (0, 1), 0, None, "reproducible sums")
-    assert st.max_cols == 1 << 31 and not st.ordered
-    assert [n for n, s in core._VALUE_STATS.items() if s.max_cols is not None] == ["sum"]
+    assert st.max_cols == 1 << 31 and st.max_bins is None and not st.ordered
+    # the only entries with a limit: the sum's rows, and the mode's rows and bins (those of bin_sort)
+    assert {n: (s.max_cols, s.max_bins) for n, s in core._VALUE_STATS.items() if s.max_cols is not None or s.max_bins is not None} == {
+        "sum": (1 << 31, None), "mode": (1 << 31, (1 << 32) - 1)}
     assert "histogram_sum" in core.__all__ and not hasattr(core, "combine_sum")
 
 

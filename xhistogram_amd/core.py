@@ -16,6 +16,7 @@ package: without the native library and a GPU the compute call raises.
 
 from __future__ import annotations
 
+import math
 import os
 import re
 import threading
@@ -1802,27 +1803,41 @@ def _upload_host(args, values, bins, *extras):
     return [a.broadcast_to(shape) for a in arrays]
 
 
+# What one launch over [rows, cols] views needs, as _value_views makes it:
+#   plan        the Plan of the edges on the samples' device
+#   nv          the native views (samples..., values[, weights or second values[, weights]])
+#   keep        the views they were made of: their copies, if any, must outlive the kernels (_launch_outputs holds them)
+#   m, c        rows and columns
+#   kept_shape  the sample shape with the reduced extents 1 (the kept axes stay in place; then come the bin axes)
+#   red, kept   the reduced axes in ascending number and the kept axes
+#   device, stream, backend ("torch" or "device")
+#   like        the first array of samples: what outputs look like (shape, torch device)
+_Launch = namedtuple("_Launch", "plan nv keep m c kept_shape red kept device stream backend like")
+
+
 def _value_views(args, values, axis, bins, backend, *extras, ordered=False):
     """the [rows, cols] views of broadcast torch tensors or DeviceArrays and of their values (and of the arrays after them, as
-    _upload_host takes them), for a per-bin statistic of the values: (plan, native views (samples..., values[, weights or
-    second values[, weights]]), the views they were made of (their copies, if any, must outlive the
-    kernels: callers hold them until the download), rows, cols, kept axes shape, device, stream).  The kept axes stay in
-    place and the reduced ones have extent 1 (then come the bin axes).  The views are those of _bincount's block adapter;
-    layouts no three strides describe are copied.  `ordered`: the columns of a row are the reduced axes in ascending axis
-    number, C order (a statistic that reports positions inside the row); otherwise any order that walks memory as one strided
-    dimension will do, and layouts that need a permutation for that are not copied."""
+    _upload_host takes them), for a per-bin statistic of the values or a per-sample output: a _Launch.  The views are those
+    of _bincount's block adapter; layouts no three strides describe are copied.  `ordered`: the columns of a row are the
+    reduced axes in ascending axis number, C order (a statistic that reports positions inside the row); otherwise any order
+    that walks memory as one strided dimension will do, and layouts that need a permutation for that are not copied."""
     a0 = args[0]
     ndim = a0.ndim
     do_full_array = (axis is None) or (set(axis) == set(_range(ndim)))
-    kept_axes_shape = (1,) * ndim if do_full_array else tuple(int(a0.shape[i]) if i not in axis else 1 for i in _range(ndim))
+    if do_full_array:
+        red, kept, kept_axes_shape = tuple(_range(ndim)), (), (1,) * ndim
+    else:
+        red = tuple(sorted(axis))
+        kept = tuple(i for i in _range(ndim) if i not in red)
+        kept_axes_shape = tuple(1 if i in red else int(a0.shape[i]) for i in _range(ndim))
     dtypes = [_np_dtype_of(a) for a in args]
     cmp_domain, edges, common = _compare_domain(dtypes, bins)
     if backend == "device" and any(c is not None and a.dtype != c for a, c in zip(args, common)):
         raise TypeError("datetime64 DeviceArrays must already have the unit they share with their bin edges")
     arrays = list(args) + [a for a in (values,) + extras if a is not None]  # (values None: the samples alone)
     if ordered:
-        axis = axis if do_full_array else sorted(axis)
-        order = list(_range(ndim)) if do_full_array else axis
+        axis = axis if do_full_array else list(red)
+        order = list(red)
     else:
         order = _reduced_order(arrays[0], list(_range(ndim)) if do_full_array else axis)
     descs = [_collapse(a, axis, do_full_array, order) for a in arrays]
@@ -1847,7 +1862,34 @@ def _value_views(args, values, axis, bins, backend, *extras, ordered=False):
     _native.require_device(device)
     plan = _get_plan(edges, cmp_domain, device)
     nv = [_native.make_view(*v[:6]) for v in views]
-    return plan, nv, views, m, c, kept_axes_shape, device, stream
+    return _Launch(plan, nv, views, m, c, kept_axes_shape, red, kept, device, stream, backend, a0)
+
+
+def _launch_outputs(rec, blocks, run):
+    """The outputs of one launch: `blocks` is a list of (shape, np.int64 or np.float64), and `run(pointers)` has the kernels
+    write each dense block at its pointer; it is called exactly when the blocks hold any element at all (a plan without bins
+    counts no sample: the library itself then fills the blocks).  torch: one tensor per block on the samples' device,
+    asynchronous on the call's stream.  Otherwise: one DeviceBuffer and one download for all blocks, and the blocks are views
+    of that one host array.  The kernels are handed these blocks themselves, never a view of something else: a copied
+    output would be lost.  `rec`, and with it the keep-alive copies of the views, lives until the launch is enqueued (torch)
+    or the download has waited for the kernels."""
+    if rec.backend == "torch":
+        torch = _torch()
+        device = rec.like.device
+        outs = [torch.empty(shape, dtype=torch.int64 if dt is np.int64 else torch.float64, device=device) for shape, dt in blocks]
+        if any(0 not in shape for shape, _ in blocks):  # (a block holds an element unless one of its extents is 0)
+            run([o.data_ptr() for o in outs])
+        return outs
+    cuts = [0]
+    for shape, _ in blocks:
+        cuts.append(cuts[-1] + math.prod(shape))
+    host = np.empty(cuts[-1], np.int64)
+    if cuts[-1] > 0:
+        buf = _native.DeviceBuffer(rec.device, host.nbytes)
+        run([buf.ptr + 8 * at for at in cuts[:-1]])
+        buf.download(host)
+    return [(host[a:b] if dt is np.int64 else host[a:b].view(np.float64)).reshape(shape)
+            for a, b, (shape, dt) in zip(cuts, cuts[1:], blocks)]
 
 
 # What the one path below (_value_rows, _value_block, _value_stat) needs of a per-bin statistic of values, an entry of
@@ -1864,29 +1906,27 @@ def _value_views(args, values, axis, bins, backend, *extras, ordered=False):
 #   ordered  whether it reports positions inside the row (_value_views, ordered)
 #   noun     what the refusal of several chunks calls the partials that cannot be merged
 #   max_cols the reduced extent per output row it refuses (NotImplementedError, before any device work); None: no limit
-_ValueStat = namedtuple("_ValueStat", "k ints method ptrs extras reduce tail ordered noun max_cols", defaults=((), False, None, None))
+#   max_bins the number of bins beyond which it refuses, in the same way and only next to max_cols; None: no limit
+_ValueStat = namedtuple("_ValueStat", "k ints method ptrs extras reduce tail ordered noun max_cols max_bins",
+                        defaults=((), False, None, None, None))
+
+# the limits of the sorted order: samples per output row, and bins (B + 1 keys in 32 bits)
+_ORDER_MAX_COLS = 1 << 31
+_SORT_MAX_BINS = (1 << 32) - 1
 
 
 def _value_rows(st, args, values, axis, bins, backend, *extras, **params):
     """the statistic's outputs of broadcast torch tensors (torch out) or DeviceArrays (numpy out) as one float64 block
     [k, kept axes (reduced ones of extent 1), bins...], its int64 outputs as the bits they are"""
-    plan, nv, views, m, c, kept_axes_shape, device, stream = _value_views(args, values, axis, bins, backend, *extras, ordered=st.ordered)
-    n = m * plan.n_bins
+    rec = _value_views(args, values, axis, bins, backend, *extras, ordered=st.ordered)
+    n = rec.m * rec.plan.n_bins
     k = st.k or len(params["q"])
-    shape = (k,) + kept_axes_shape + plan.bins_shape
-    if backend == "torch":
-        torch = _torch()
-        out = torch.empty(shape, dtype=torch.float64, device=args[0].device)
-    else:
-        out = np.empty(shape, np.float64)
-    if k * n > 0:
-        buf = None if backend == "torch" else _native.DeviceBuffer(device, k * n * 8)
-        base = out.data_ptr() if buf is None else buf.ptr
-        getattr(plan, st.method)(nv[:len(args)], *nv[len(args):], m, c, *[base + i * n * 8 for i in st.ptrs],
-                                 *[params[p] for p in st.tail], stream=stream)
-        if buf is not None:
-            buf.download(out)  # (waits for the kernels: the views' keepalive copies are not needed after this)
-    return out
+
+    def run(ptrs):
+        getattr(rec.plan, st.method)(rec.nv[:len(args)], *rec.nv[len(args):], rec.m, rec.c, *[ptrs[0] + i * n * 8 for i in st.ptrs],
+                                     *[params[p] for p in st.tail], stream=rec.stream)
+
+    return _launch_outputs(rec, [((k,) + rec.kept_shape + rec.plan.bins_shape, np.float64)], run)[0]
 
 
 def _value_block(*all_arrays, stat=None, axis=None, bins=None, **params):
@@ -1903,11 +1943,32 @@ def _value_block(*all_arrays, stat=None, axis=None, bins=None, **params):
 
 
 def _resident(backend, raw, all_arrays, n_inputs, bins):
-    """the arrays _value_rows takes, and the backend it takes them as: numpy inputs (`raw`) uploaded to the calling thread's
-    GPU ("device"), torch tensors and DeviceArrays as they are"""
+    """the arrays _value_views takes, and the backend it takes them as: numpy inputs (`raw`: samples..., then the values and
+    what follows them, if any) uploaded to the calling thread's GPU ("device"), torch tensors and DeviceArrays as they are"""
     if backend == "numpy":
-        return _upload_host(raw[:n_inputs], raw[n_inputs], bins, *raw[n_inputs + 1:]), "device"
+        rest = raw[n_inputs:] or [None]
+        return _upload_host(raw[:n_inputs], rest[0], bins, *rest[1:]), "device"
     return all_arrays, backend
+
+
+def _check_sizes(name, shape, drop_axes, bins, max_cols, max_bins=None):
+    """NotImplementedError for `max_cols` samples or more per output row and for more than `max_bins` bins (None: no bound),
+    from the broadcast shape and the edges alone: (samples per output row, number of bins)"""
+    cols = math.prod(int(shape[ax]) for ax in drop_axes)
+    if cols >= max_cols:
+        raise NotImplementedError("%s takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
+                                  % (name, max_cols, cols))
+    n_bins = math.prod(max(len(b) - 1, 0) for b in bins)
+    if max_bins is not None and n_bins > max_bins:
+        raise NotImplementedError("%s takes at most 2^32 - 1 = %d bins, got %d" % (name, max_bins, n_bins))
+    return cols, n_bins
+
+
+def _check_one_chunk(noun, all_arrays, drop_axes):
+    """ValueError for dask inputs whose reduced axes are cut, where there is no merge of the partials (`noun`) of the chunks"""
+    if any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
+        raise ValueError("%s of several chunks cannot be merged: rechunk the reduced axes of every input into "
+                         "one chunk (e.g. arr.rechunk({axis: -1}))" % noun)
 
 
 def _drop_axes(a, axes, backend):
@@ -1917,30 +1978,22 @@ def _drop_axes(a, axes, backend):
     return a.squeeze(axes)
 
 
-def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, *extras, weights=None, check=None, **params):
+def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, *extras, weights=None, **params):
     """the backends of the per-bin statistic _VALUE_STATS[stat] of values: (backend, the outputs with the shape ``histogram``
     gives, bin edges, reduced axes).  `extras` are the arrays it reads after the values, in its order, `weights` (None: not
     given) the last of them, and `params` its per-call parameters.  The outputs are a list of k arrays; the quantiles stay one
     array behind their q axis.  dask: lazy arrays, the partials merged by the statistic's dask step and the last step by
-    `aggregate`.  `check(shape, drop_axes, bins)` (None: none) is the caller's own refusal by the broadcast shape and the edges
-    alone, made before any device work on the samples."""
+    `aggregate`.  The entry's size limits are refused before any device work on the samples."""
     backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, *extras, weights)
     n_inputs = len(args)
     st = _VALUE_STATS[stat]
-    if check is not None:
-        check(all_arrays[0].shape, drop_axes, bins)
     k = st.k or len(params["q"])
     if st.max_cols is not None:
-        shape = all_arrays[0].shape
-        cols = int(np.prod([int(shape[ax]) for ax in drop_axes], dtype=object)) if drop_axes else 1
-        if cols >= st.max_cols:
-            raise NotImplementedError("%s takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
-                                      % (name, st.max_cols, cols))
+        _check_sizes(name, all_arrays[0].shape, drop_axes, bins, st.max_cols, st.max_bins)
     merged = backend == "dask" and st.reduce is not None
     if backend == "dask":
-        if not merged and any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
-            raise ValueError("%s of several chunks cannot be merged: rechunk the reduced axes of every input into "
-                             "one chunk (e.g. arr.rechunk({axis: -1}))" % st.noun)
+        if not merged:
+            _check_one_chunk(st.noun, all_arrays, drop_axes)
         res = _values_blockwise(partial(_value_block, stat=stat, **params), k, all_arrays, bins, axis, drop_axes)
         if merged:
             import dask.array as dsa
@@ -2509,7 +2562,7 @@ _skew_kurt_w_reduce = partial(_moment_reduce, present=_weighed, pairs=None)
 _VALUE_STATS = {
     "extrema": _ValueStat(2, (), "execute_extrema", (0, 1), 0, _extrema_pair_reduce),
     # (count, total): integer accumulators of several chunks are not kept, so there is no merge
-    "sum": _ValueStat(2, (0,), "execute_sum", (0, 1), 0, None, noun="reproducible sums", max_cols=1 << 31),
+    "sum": _ValueStat(2, (0,), "execute_sum", (0, 1), 0, None, noun="reproducible sums", max_cols=_ORDER_MAX_COLS),
     # (vmin, vmax, argmin, argmax): the library takes the block of values and the block of positions
     "argextrema": _ValueStat(4, (2, 3), "execute_argextrema", (0, 2), 0, None, ordered=True, noun="positions"),
     "mean_var": _ValueStat(3, (0,), "execute_mean_var", (0, 1, 2), 0, _mean_var_reduce),
@@ -2524,7 +2577,8 @@ _VALUE_STATS = {
     "quantile": _ValueStat(None, (), "execute_quantile", (0,), 0, None, ("q", "code"), noun="exact quantiles"),
     "quantile_w": _ValueStat(None, (), "execute_quantile_weighted", (0,), 1, None, ("q",), noun="exact quantiles"),
     # (count, nunique, mode, mode_count): the runs of several chunks are not kept, so there is no merge
-    "mode": _ValueStat(4, (0, 1, 3), "execute_mode", (0, 1, 2, 3), 0, None, noun="modes"),
+    "mode": _ValueStat(4, (0, 1, 3), "execute_mode", (0, 1, 2, 3), 0, None, noun="modes", max_cols=_ORDER_MAX_COLS,
+                       max_bins=_SORT_MAX_BINS),
 }
 
 
@@ -2620,47 +2674,30 @@ def histogram_weighted_quantile(*args, values, weights, q, bins=None, range=None
 # ---------------------------------------------------------------------------------------------
 # per-sample maps: from a per-bin result back to the samples
 # ---------------------------------------------------------------------------------------------
-def _map_out(plan, nv, has_values, m, c, op, centre_ptr, scale_ptr, like, axis, backend, device, stream):
-    """xhist_plan_execute_map over the `ordered` views `nv` of _value_views (samples..., then the values where `has_values`),
-    into the block of _sample_block"""
-    n = plan.n_dims
+def _map_out(rec, has_values, op, centre_ptr, scale_ptr):
+    """xhist_plan_execute_map over the `ordered` launch `rec` (samples..., then the values where `has_values`), one element
+    per sample"""
+    n = rec.plan.n_dims
 
-    def run(out_ptr):
-        plan.execute_map(nv[:n], nv[n] if has_values else None, m, c, op, centre_ptr, scale_ptr, out_ptr, stream=stream)
+    def run(ptrs):
+        rec.plan.execute_map(rec.nv[:n], rec.nv[n] if has_values else None, rec.m, rec.c, op, centre_ptr, scale_ptr, ptrs[0],
+                             stream=rec.stream)
 
-    return _sample_block(run, m, c, op == _native.MAP_INDEX, like, axis, backend, device)
+    return _sample_block(rec, np.int64 if op == _native.MAP_INDEX else np.float64, run)
 
 
-def _sample_block(run, m, c, is_index, like, axis, backend, device):
-    """The dense [m, c] block of 8-byte elements (int64 where `is_index`, else float64) that `run(pointer)` has the kernels
-    write, one element per sample, in the broadcast sample shape of `like` — a torch tensor on its device (asynchronous on the
-    call's stream) or a numpy array.  The block's rows are the kept axes in C order and a row's columns the
-    reduced axes in ascending number: it is reshaped, and its axes moved back where `axis` is not trailing.  The kernels are
-    handed this block itself, never a view of something else: a copied output would be lost."""
-    shape = tuple(int(s) for s in like.shape)
-    ndim = len(shape)
-    red = list(_range(ndim)) if axis is None or set(axis) == set(_range(ndim)) else sorted(axis)
-    kept = [i for i in _range(ndim) if i not in red]
-    if backend == "torch":
-        torch = _torch()
-        out = torch.empty((m, c), dtype=torch.int64 if is_index else torch.float64, device=like.device)
-    else:
-        out = np.empty((m, c), np.int64 if is_index else np.float64)
-    if m * c > 0:
-        # (a plan without bins counts no sample: the library itself then fills the block with -1 / NaN)
-        buf = None if backend == "torch" else _native.DeviceBuffer(device, m * c * 8)
-        run(out.data_ptr() if buf is None else buf.ptr)
-        if buf is not None:
-            buf.download(out)  # (waits for the kernels: the views' keepalive copies are not needed after this)
-    return _sample_shape(out, shape, kept, red, backend)
+def _sample_block(rec, dtype, run):
+    """the [m, c] block that `run([pointer])` has the kernels write, one element per sample of the `ordered` launch `rec`, in
+    the broadcast sample shape"""
+    return _sample_shape(_launch_outputs(rec, [((rec.m, rec.c), dtype)], run)[0], _shape_of(rec.like), rec.kept, rec.red, rec.backend)
 
 
 def _sample_shape(out, shape, kept, red, backend):
     """a dense [rows, cols] block, its rows the kept axes in C order and a row's columns the reduced axes in ascending number,
-    in the broadcast sample shape `shape`"""
+    in the broadcast sample shape `shape`: reshaped, and its axes moved back where the reduced axes are not trailing"""
     ndim = len(shape)
     out = out.reshape([shape[i] for i in kept] + [shape[i] for i in red])
-    if kept and red != list(_range(len(kept), ndim)):
+    if kept and tuple(red) != tuple(_range(len(kept), ndim)):
         back = tuple(_range(len(kept), ndim))
         out = out.movedim(back, tuple(red)) if backend == "torch" else np.moveaxis(out, back, red)
     return out
@@ -2710,13 +2747,47 @@ def _shape_of(a):
     return tuple(int(s) for s in (a.shape if hasattr(a, "shape") else np.shape(a)))
 
 
-def _map_samples(name, args, bins, range, axis):
-    """the front of bin_index and histogram_lookup: _values_call's for a call without values, and the samples resident on a
-    GPU (numpy samples uploaded to the calling thread's)"""
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, None, bins, range, axis, name, needs_values=False)
-    if backend == "numpy":
-        return backend, _upload_host(raw, None, bins), "device", bins, axis, drop_axes
-    return backend, all_arrays, backend, bins, axis, drop_axes
+# what _sample_call returns: the caller's backend; the broadcast arrays (samples..., values, extras...), resident on a GPU
+# unless they are dask arrays; `on`, the backend _value_views takes them as; the edges, the normalised axis and the reduced
+# axes; and, for the grouped calls, the samples per output row and the number of bins
+_SampleCall = namedtuple("_SampleCall", "backend arrays on bins axis drop_axes cols n_bins")
+
+
+def _sample_call(name, args, values, bins, range, axis, *extras, needs_values=True, check=None, noun=None, max_bins=None):
+    """The front of the functions that return something per sample or per row, all of it before any device work: the caller's
+    own `check`, _values_call (`needs_values` False and values None: the samples alone) and, for the calls that group the
+    samples by bin (`noun`: what dask chunks of theirs cannot be merged), the refusals of complex samples, of 2^31 samples or
+    more per output row, of more than `max_bins` bins (None: no bound here) and of dask inputs whose reduced axes are cut.
+    Then numpy inputs are uploaded, once.  Returns a _SampleCall."""
+    if check is not None:
+        check()
+    if noun is not None:
+        for a in args:
+            dt = a.dtype if hasattr(a, "dtype") else np.asarray(a).dtype
+            if getattr(dt, "is_complex", False) or getattr(dt, "kind", "") == "c":
+                raise TypeError("complex samples have no order: %s takes real samples" % name)
+    if values is not None and not hasattr(values, "dtype"):
+        values = np.asarray(values)
+    backend, arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, *extras, needs_values=needs_values)
+    cols = n_bins = None
+    if noun is not None:
+        cols, n_bins = _check_sizes(name, arrays[0].shape, drop_axes, bins, _ORDER_MAX_COLS, max_bins)
+        if backend == "dask":
+            _check_one_chunk(noun, arrays, drop_axes)
+    on = backend
+    if backend != "dask":
+        arrays, on = _resident(backend, raw, arrays, len(args), bins)
+    return _SampleCall(backend, arrays, on, bins, axis, drop_axes, cols, n_bins)
+
+
+def _sample_blockwise(block_fn, arrays, dtype, *extra, **params):
+    """dask: one task per block of the broadcast `arrays`, each `block_fn`'s output on the samples' own index; `extra` are
+    further (operand, index) pairs"""
+    import dask.array as dsa
+
+    ind = tuple(_range(arrays[0].ndim))
+    return dsa.blockwise(block_fn, ind, *[x for a in arrays for x in (a, ind)], *extra, dtype=dtype, meta=np.array((), dtype),
+                         **params)
 
 
 def _bin_index_block(*blocks, bins=None):
@@ -2739,20 +2810,11 @@ def bin_index(*args, bins=None, range=None):
     Returns ``(index, bin_edges)``.  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the
     current stream), DeviceArray in -> numpy out, dask in -> a lazy dask array, one task per block (``bins`` must then be
     numpy arrays of edges)."""
-    if not args:
-        raise TypeError("bin_index needs at least one array of samples")
-    backend, arrays, on, bins, _, _ = _map_samples("bin_index", args, bins, range, None)
-    if backend == "dask":
-        import dask.array as dsa
-
-        ind = tuple(_range(arrays[0].ndim))
-        out = dsa.blockwise(_bin_index_block, ind, *[x for a in arrays for x in (a, ind)], dtype=np.int64, bins=bins,
-                            meta=np.array((), np.int64))
-        return out, bins
-    plan, nv, views, m, c, _, device, stream = _value_views(arrays, None, None, bins, on, ordered=True)
-    out = _map_out(plan, nv, False, m, c, _native.MAP_INDEX, 0, 0, arrays[0], None, on, device, stream)
-    del views
-    return out, bins
+    f = _sample_call("bin_index", args, None, bins, range, None, needs_values=False)
+    if f.backend == "dask":
+        return _sample_blockwise(_bin_index_block, f.arrays, np.int64, bins=f.bins), f.bins
+    rec = _value_views(f.arrays, None, None, f.bins, f.on, ordered=True)
+    return _map_out(rec, False, _native.MAP_INDEX, 0, 0), f.bins
 
 
 def _lookup_block(*blocks, axis=None, bins=None):
@@ -2789,26 +2851,22 @@ def histogram_lookup(*args, table, bins=None, range=None, axis=None):
         if any(_is_torch(a) or _is_devarr(a) for a in args):
             raise TypeError("a dask table goes with dask or numpy samples: compute the table, or pass the samples as dask arrays")
         args = [dsa.from_array(np.asarray(a), chunks=-1) for a in args]
-    backend, arrays, on, bins, axis, drop_axes = _map_samples("histogram_lookup", args, bins, range, axis)
+    f = _sample_call("histogram_lookup", args, None, bins, range, axis, needs_values=False)
+    arrays, bins, axis = f.arrays, f.bins, f.axis
     shape = _shape_of(arrays[0])
-    _check_table_shape(table, shape, drop_axes, [len(b) - 1 for b in bins])
-    if backend == "dask":
+    _check_table_shape(table, shape, f.drop_axes, [len(b) - 1 for b in bins])
+    if f.backend == "dask":
         import dask.array as dsa
 
-        ind = tuple(_range(len(shape)))
-        kept = tuple(i for i in ind if i not in drop_axes)
+        kept = tuple(i for i in _range(len(shape)) if i not in f.drop_axes)
         t_ind = kept + tuple(_range(len(shape), len(shape) + len(bins)))
         # the table's blocks are the sample blocks' along the kept axes, and every bin axis is one chunk
         t_chunks = tuple(arrays[0].chunks[i] for i in kept) + (-1,) * len(bins)
         table = table.rechunk(t_chunks) if _is_dask(table) else dsa.from_array(np.asarray(table), chunks=t_chunks)
-        out = dsa.blockwise(_lookup_block, ind, *[x for a in arrays for x in (a, ind)], table, t_ind, dtype=np.float64,
-                            concatenate=True, axis=axis, bins=bins, meta=np.array((), np.float64))
-        return out, bins
-    plan, nv, views, m, c, _, device, stream = _value_views(arrays, None, axis, bins, on, ordered=True)
-    keep, ptr = _table_on_device(table, m, plan.n_bins, on, arrays[0], device)
-    out = _map_out(plan, nv, False, m, c, _native.MAP_TAKE, ptr, 0, arrays[0], axis, on, device, stream)
-    del views, keep
-    return out, bins
+        return _sample_blockwise(_lookup_block, arrays, np.float64, table, t_ind, concatenate=True, axis=axis, bins=bins), bins
+    rec = _value_views(arrays, None, axis, bins, f.on, ordered=True)
+    keep, ptr = _table_on_device(table, rec.m, rec.plan.n_bins, f.on, arrays[0], rec.device)  # (`keep` outlives the launch)
+    return _map_out(rec, False, _native.MAP_TAKE, ptr, 0), bins
 
 
 def histogram_anomaly(*args, values, bins=None, range=None, axis=None, weights=None, ddof=0, standardize=False):
@@ -2828,19 +2886,20 @@ def histogram_anomaly(*args, values, bins=None, range=None, axis=None, weights=N
     ddof = _check_ddof(ddof)
     standardize = _check_flag("standardize", standardize)
     n = len(args)
-    backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, "histogram_anomaly", weights)
-    if backend == "dask":
+    f = _sample_call("histogram_anomaly", args, values, bins, range, axis, weights)
+    arrays, on, bins, axis = f.arrays, f.on, f.bins, f.axis
+    if f.backend == "dask":
         import dask.array as dsa
 
-        _, mean, var, _ = histogram_mean_var(*all_arrays[:n], values=all_arrays[n], bins=bins, axis=axis, ddof=ddof,
-                                             weights=all_arrays[n + 1] if weights is not None else None)
-        out = all_arrays[n].astype(np.float64) - histogram_lookup(*all_arrays[:n], table=mean, bins=bins, axis=axis)[0]
+        _, mean, var, _ = histogram_mean_var(*arrays[:n], values=arrays[n], bins=bins, axis=axis, ddof=ddof,
+                                             weights=arrays[n + 1] if weights is not None else None)
+        out = arrays[n].astype(np.float64) - histogram_lookup(*arrays[:n], table=mean, bins=bins, axis=axis)[0]
         if standardize:
-            out = out / histogram_lookup(*all_arrays[:n], table=dsa.sqrt(var), bins=bins, axis=axis)[0]
+            out = out / histogram_lookup(*arrays[:n], table=dsa.sqrt(var), bins=bins, axis=axis)[0]
         return out, bins
-    arrays, on = _resident(backend, raw, all_arrays, n, bins)
     st = _VALUE_STATS["mean_var" if weights is None else "mean_var_w"]
-    plan, nv, views, m, c, _, device, stream = _value_views(arrays[:n], arrays[n], axis, bins, on, *arrays[n + 1:], ordered=True)
+    rec = _value_views(arrays[:n], arrays[n], axis, bins, on, *arrays[n + 1:], ordered=True)
+    plan, nv, m, c, device, stream = rec.plan, rec.nv, rec.m, rec.c, rec.device, rec.stream
     nt = m * plan.n_bins
     # the block (count or sum of weights, mean, M2) of histogram_mean_var's own call, on the device
     if on == "torch":
@@ -2866,9 +2925,8 @@ def histogram_anomaly(*args, values, bins=None, range=None, axis=None, weights=N
             x = host[0].view(np.int64) if 0 in st.ints else host[0]
             with np.errstate(invalid="ignore"):
                 scale, scale_ptr = _table_on_device(np.sqrt(_var_of(x, host[2], ddof)), m, plan.n_bins, on, arrays[0], device)
-    out = _map_out(plan, nv[:n + 1], True, m, c, _native.MAP_ANOMALY, base + nt * 8, scale_ptr, arrays[0], axis, on, device, stream)
-    del views, stats, scale
-    return out, bins
+    # (`stats` and `scale` outlive the launch)
+    return _map_out(rec, True, _native.MAP_ANOMALY, base + nt * 8, scale_ptr), bins
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2911,90 +2969,22 @@ def histogram_mode(*args, values, bins=None, range=None, axis=None, weights=None
     if weights is not None:
         raise NotImplementedError("histogram_mode does not take weights: the value with the largest sum of weights is another "
                                   "statistic")
-    _, (count, nunique, mode, mode_count), bins, _ = _value_stat("mode", args, values, bins, range, axis, "histogram_mode",
-                                                                check=partial(_check_grouped_sizes, "histogram_mode", _SORT_MAX_BINS))
+    _, (count, nunique, mode, mode_count), bins, _ = _value_stat("mode", args, values, bins, range, axis, "histogram_mode")
     return count, nunique, mode, mode_count, bins
 
 
 # ---------------------------------------------------------------------------------------------
 # bin_order, bin_sort and bin_rank: the samples grouped by bin, their one call path
 # ---------------------------------------------------------------------------------------------
-_ORDER_MAX_COLS = 1 << 31
-_SORT_MAX_BINS = (1 << 32) - 1
+def _row_shape(rec, width):
+    """[kept axes, width]: one row of `width` per kept index of the launch `rec`"""
+    return tuple(int(rec.like.shape[i]) for i in rec.kept) + (width,)
 
 
-# what _grouped_call returns: _values_call's six, then the samples per output row and the number of bins
-_Grouped = namedtuple("_Grouped", "backend arrays raw bins axis drop_axes cols n_bins")
-
-
-def _check_grouped_sizes(name, max_bins, shape, drop_axes, bins):
-    """NotImplementedError for 2^31 samples or more per output row and for more than `max_bins` bins (None: no bound here), the
-    limits of the sorted order, from the broadcast shape and the edges alone: (samples per output row, number of bins)"""
-    shape = tuple(int(s) for s in shape)
-    cols = int(np.prod([shape[ax] for ax in drop_axes], dtype=object)) if drop_axes else 1
-    if cols >= _ORDER_MAX_COLS:
-        raise NotImplementedError("%s takes fewer than 2^31 = %d samples per output row, got %d: split the reduced axes"
-                                  % (name, _ORDER_MAX_COLS, cols))
-    n_bins = int(np.prod([max(len(b) - 1, 0) for b in bins], dtype=object))
-    if max_bins is not None and n_bins > max_bins:
-        raise NotImplementedError("%s takes at most 2^32 - 1 = %d bins, got %d" % (name, max_bins, n_bins))
-    return cols, n_bins
-
-
-def _grouped_call(name, noun, args, values, bins, range, axis, needs_values=True, max_bins=None, check=None):
-    """The front of bin_order (`needs_values` False, values None), bin_sort and bin_rank, all of it before any device work: the
-    argument checks (`check`: the caller's own, run in their place among them), _values_call, and the refusals of 2^31 samples
-    or more per output row, of more than `max_bins` bins (None: no bound here) and of dask inputs whose reduced axes are cut
-    (`noun`: what then cannot be merged).  Returns a _Grouped."""
-    if not args:
-        raise TypeError("%s needs at least one array of samples" % name)
-    if values is None and needs_values:
-        raise TypeError("%s needs values" % name)
-    if check is not None:
-        check()
-    for a in args:
-        dt = a.dtype if hasattr(a, "dtype") else np.asarray(a).dtype
-        if getattr(dt, "is_complex", False) or getattr(dt, "kind", "") == "c":
-            raise TypeError("complex samples have no order: %s takes real samples" % name)
-    if values is not None and not hasattr(values, "dtype"):
-        values = np.asarray(values)
-    call = _values_call(args, values, bins, range, axis, name, needs_values=needs_values)
-    backend, all_arrays, _, bins, _, drop_axes = call
-    cols, n_bins = _check_grouped_sizes(name, max_bins, all_arrays[0].shape, drop_axes, bins)
-    if backend == "dask" and any(len(a.chunks[ax]) > 1 for a in all_arrays for ax in drop_axes):
-        raise ValueError("%s of several chunks cannot be merged: rechunk the reduced axes of every input into "
-                         "one chunk (e.g. arr.rechunk({axis: -1}))" % noun)
-    return _Grouped(*call, cols, n_bins)
-
-
-def _order_offsets_rows(run, arrays, values, axis, bins, on):
-    """`run(plan, nv, m, c, order_ptr, offsets_ptr, stream)`, the caller's Plan method, over the `ordered` views `nv` of
-    broadcast torch tensors or DeviceArrays (samples..., then the values; None: the samples alone): (order [kept axes, c],
-    offsets [kept axes, B + 1]), int64, torch tensors on the samples' device (asynchronous on the current stream) or numpy
-    arrays.  The kernels are handed these blocks themselves."""
-    plan, nv, views, m, c, _, device, stream = _value_views(arrays, values, axis, bins, on, ordered=True)
-    shape = tuple(int(s) for s in arrays[0].shape)
-    ndim = len(shape)
-    red = list(_range(ndim)) if axis is None or set(axis) == set(_range(ndim)) else sorted(axis)
-    kept = tuple(shape[i] for i in _range(ndim) if i not in red)
-    nb1 = plan.n_bins + 1
-    if on == "torch":
-        torch = _torch()
-        order = torch.empty((m, c), dtype=torch.int64, device=arrays[0].device)
-        offsets = torch.empty((m, nb1), dtype=torch.int64, device=arrays[0].device)
-        if m > 0:
-            run(plan, nv, m, c, order.data_ptr(), offsets.data_ptr(), stream)
-    else:
-        order, offsets = np.empty((m, c), np.int64), np.empty((m, nb1), np.int64)
-        if m > 0:
-            buf = _native.DeviceBuffer(device, (m * c + m * nb1) * 8)
-            run(plan, nv, m, c, buf.ptr, buf.ptr + m * c * 8, stream)
-            both = np.empty(m * c + m * nb1, np.int64)
-            buf.download(both)  # (waits for the kernels: the views' keepalive copies are not needed after this)
-            order[...] = both[:m * c].reshape(m, c)
-            offsets[...] = both[m * c:].reshape(m, nb1)
-    del views
-    return order.reshape(kept + (c,)), offsets.reshape(kept + (nb1,))
+def _order_offsets_rows(rec, run):
+    """(order [kept axes, c], offsets [kept axes, B + 1]), int64, that `run([order_ptr, offsets_ptr])`, the caller's Plan
+    method over the `ordered` launch `rec`, has the kernels write"""
+    return tuple(_launch_outputs(rec, [(_row_shape(rec, rec.c), np.int64), (_row_shape(rec, rec.plan.n_bins + 1), np.int64)], run))
 
 
 def _packed_block(order, offsets, like, axis):
@@ -3050,19 +3040,15 @@ def bin_order(*args, bins=None, range=None, axis=None):
     Returns ``(order, offsets, bin_edges)``.  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on
     the current stream), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block over the kept axes: every
     reduced axis must then be a single chunk, and ``bins`` numpy arrays of edges."""
-    g = _grouped_call("bin_order", "group orders", args, None, bins, range, axis, needs_values=False)
-    bins, axis = g.bins, g.axis
-    if g.backend == "dask":
-        return _packed_blockwise(_bin_order_block, g.arrays, g.drop_axes, g.cols, g.n_bins, bins=bins) + (bins,)
-    if g.backend == "numpy":
-        arrays, on = _upload_host(g.raw, None, bins), "device"
-    else:
-        arrays, on = g.arrays, g.backend
+    f = _sample_call("bin_order", args, None, bins, range, axis, needs_values=False, noun="group orders")
+    if f.backend == "dask":
+        return _packed_blockwise(_bin_order_block, f.arrays, f.drop_axes, f.cols, f.n_bins, bins=f.bins) + (f.bins,)
+    rec = _value_views(f.arrays, None, f.axis, f.bins, f.on, ordered=True)
 
-    def run(plan, nv, m, c, order_ptr, offsets_ptr, stream):
-        plan.execute_group(nv, m, c, order_ptr, offsets_ptr, stream=stream)
+    def run(ptrs):
+        rec.plan.execute_group(rec.nv, rec.m, rec.c, *ptrs, stream=rec.stream)
 
-    return _order_offsets_rows(run, arrays, None, axis, bins, on) + (bins,)
+    return _order_offsets_rows(rec, run) + (f.bins,)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -3106,19 +3092,19 @@ def bin_sort(*args, values, bins=None, range=None, axis=None, descending=False):
     Returns ``(order, offsets, bin_edges)``.  numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on
     the current stream, no host synchronisation), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per block
     over the kept axes: every reduced axis must then be a single chunk, and ``bins`` numpy arrays of edges."""
-    g = _grouped_call("bin_sort", "sorted orders", args, values, bins, range, axis, max_bins=_SORT_MAX_BINS,
-                      check=lambda: _check_flag("descending", descending))
-    bins, axis, descending = g.bins, g.axis, bool(descending)
-    if g.backend == "dask":
-        return _packed_blockwise(_bin_sort_block, g.arrays, g.drop_axes, g.cols, g.n_bins, bins=bins,
-                                 descending=descending) + (bins,)
+    f = _sample_call("bin_sort", args, values, bins, range, axis, noun="sorted orders", max_bins=_SORT_MAX_BINS,
+                     check=lambda: _check_flag("descending", descending))
+    descending = bool(descending)
+    if f.backend == "dask":
+        return _packed_blockwise(_bin_sort_block, f.arrays, f.drop_axes, f.cols, f.n_bins, bins=f.bins,
+                                 descending=descending) + (f.bins,)
     n = len(args)
-    arrays, on = _resident(g.backend, g.raw, g.arrays, n, bins)
+    rec = _value_views(f.arrays[:n], f.arrays[n], f.axis, f.bins, f.on, ordered=True)
 
-    def run(plan, nv, m, c, order_ptr, offsets_ptr, stream):
-        plan.execute_sort(nv[:n], nv[n], m, c, descending, order_ptr, offsets_ptr, stream=stream)
+    def run(ptrs):
+        rec.plan.execute_sort(rec.nv[:n], rec.nv[n], rec.m, rec.c, descending, *ptrs, stream=rec.stream)
 
-    return _order_offsets_rows(run, arrays[:n], arrays[n], axis, bins, on) + (bins,)
+    return _order_offsets_rows(rec, run) + (f.bins,)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -3171,26 +3157,19 @@ def bin_rank(*args, values, bins=None, range=None, axis=None, method="average", 
         _check_flag("descending", descending)
         _check_flag("pct", pct)
 
-    g = _grouped_call("bin_rank", "ranks", args, values, bins, range, axis, max_bins=_SORT_MAX_BINS, check=check)
-    bins, axis, descending, pct = g.bins, g.axis, bool(descending), bool(pct)
+    f = _sample_call("bin_rank", args, values, bins, range, axis, noun="ranks", max_bins=_SORT_MAX_BINS, check=check)
+    descending, pct = bool(descending), bool(pct)
     n = len(args)
-    if g.backend == "dask":
-        import dask.array as dsa
+    if f.backend == "dask":
+        return _sample_blockwise(_bin_rank_block, f.arrays, np.float64, axis=list(f.drop_axes), bins=f.bins, method=method,
+                                 descending=descending, pct=pct), f.bins
+    rec = _value_views(f.arrays[:n], f.arrays[n], f.axis, f.bins, f.on, ordered=True)
 
-        ind = tuple(_range(g.arrays[0].ndim))
-        out = dsa.blockwise(_bin_rank_block, ind, *[x for a in g.arrays for x in (a, ind)], dtype=np.float64,
-                            axis=list(g.drop_axes), bins=bins, method=method, descending=descending, pct=pct,
-                            meta=np.array((), np.float64))
-        return out, bins
-    arrays, on = _resident(g.backend, g.raw, g.arrays, n, bins)
-    plan, nv, views, m, c, _, device, stream = _value_views(arrays[:n], arrays[n], axis, bins, on, ordered=True)
+    def run(ptrs):
+        rec.plan.execute_rank(rec.nv[:n], rec.nv[n], rec.m, rec.c, _native.RANK_METHODS[method], descending, pct, ptrs[0],
+                              stream=rec.stream)
 
-    def run(out_ptr):
-        plan.execute_rank(nv[:n], nv[n], m, c, _native.RANK_METHODS[method], descending, pct, out_ptr, stream=stream)
-
-    out = _sample_block(run, m, c, False, arrays[0], axis, on, device)
-    del views
-    return out, bins
+    return _sample_block(rec, np.float64, run), f.bins
 
 
 # ---------------------------------------------------------------------------------------------
@@ -3270,52 +3249,30 @@ def bin_unique(*args, values, bins=None, range=None, axis=None, size=None, retur
         _check_size(size)
         _check_flag("return_inverse", return_inverse)
 
-    g = _grouped_call("bin_unique", "distinct values", args, values, bins, range, axis, max_bins=_SORT_MAX_BINS, check=check)
-    bins, axis, return_inverse = g.bins, g.axis, bool(return_inverse)
+    f = _sample_call("bin_unique", args, values, bins, range, axis, noun="distinct values", max_bins=_SORT_MAX_BINS, check=check)
+    bins, return_inverse = f.bins, bool(return_inverse)
     size = None if size is None else int(size)
     n = len(args)
-    if g.backend == "dask":
-        import dask.array as dsa
-
-        width = g.cols if size is None else size
-        both, offsets = _packed_blockwise(_bin_unique_block, g.arrays, g.drop_axes, 2 * width, g.n_bins, bins=bins, size=width)
+    if f.backend == "dask":
+        width = f.cols if size is None else size
+        both, offsets = _packed_blockwise(_bin_unique_block, f.arrays, f.drop_axes, 2 * width, f.n_bins, bins=bins, size=width)
         uniques = both[..., :width].map_blocks(_float64_bits, dtype=np.float64, meta=np.array((), np.float64))
         out = (uniques, both[..., width:], offsets)
         if return_inverse:
-            ind = tuple(_range(g.arrays[0].ndim))
-            out += (dsa.blockwise(_bin_unique_inverse_block, ind, *[x for a in g.arrays for x in (a, ind)], dtype=np.int64,
-                                  axis=list(g.drop_axes), bins=bins, meta=np.array((), np.int64)),)
+            out += (_sample_blockwise(_bin_unique_inverse_block, f.arrays, np.int64, axis=list(f.drop_axes), bins=bins),)
         return out + (bins,)
-    arrays, on = _resident(g.backend, g.raw, g.arrays, n, bins)
-    plan, nv, views, m, c, _, device, stream = _value_views(arrays[:n], arrays[n], axis, bins, on, ordered=True)
-    shape = tuple(int(s) for s in arrays[0].shape)
-    ndim = len(shape)
-    red = list(_range(ndim)) if axis is None or set(axis) == set(_range(ndim)) else sorted(axis)
-    kept = [i for i in _range(ndim) if i not in red]
-    width = c if size is None else size
-    nb1 = plan.n_bins + 1
-    n_inv = c if return_inverse else 0
-    if on == "torch":
-        torch = _torch()
-        like = dict(dtype=torch.int64, device=arrays[0].device)
-        uniques = torch.empty((m, width), dtype=torch.float64, device=arrays[0].device)
-        counts, offsets, inverse = torch.empty((m, width), **like), torch.empty((m, nb1), **like), torch.empty((m, n_inv), **like)
-        if m > 0:
-            plan.execute_unique(nv[:n], nv[n], m, c, width, uniques.data_ptr(), counts.data_ptr(), offsets.data_ptr(),
-                                inverse.data_ptr() if return_inverse else None, stream=stream)
-    else:
-        cuts = np.cumsum([0, m * width, m * width, m * nb1, m * n_inv])
-        host = np.empty(int(cuts[-1]), np.int64)
-        if m > 0:
-            buf = _native.DeviceBuffer(device, host.nbytes)
-            ptrs = [buf.ptr + 8 * int(at) for at in cuts[:4]]
-            plan.execute_unique(nv[:n], nv[n], m, c, width, ptrs[0], ptrs[1], ptrs[2], ptrs[3] if return_inverse else None, stream=stream)
-            buf.download(host)  # (waits for the kernels: the views' keepalive copies are not needed after this)
-        uniques = host[cuts[0]:cuts[1]].view(np.float64).reshape(m, width)
-        counts, offsets, inverse = (host[cuts[i]:cuts[i + 1]].reshape(m, w) for i, w in ((1, width), (2, nb1), (3, n_inv)))
-    del views
-    lead = tuple(shape[i] for i in kept)
-    out = (uniques.reshape(lead + (width,)), counts.reshape(lead + (width,)), offsets.reshape(lead + (nb1,)))
+    rec = _value_views(f.arrays[:n], f.arrays[n], f.axis, bins, f.on, ordered=True)
+    width = rec.c if size is None else size
+    # (a call without an inverse: its block has no column, and the library is told so with a NULL pointer)
+    blocks = [(_row_shape(rec, width), np.float64), (_row_shape(rec, width), np.int64), (_row_shape(rec, rec.plan.n_bins + 1), np.int64),
+              ((rec.m, rec.c if return_inverse else 0), np.int64)]
+
+    def run(ptrs):
+        rec.plan.execute_unique(rec.nv[:n], rec.nv[n], rec.m, rec.c, width, *ptrs[:3], ptrs[3] if return_inverse else None,
+                                stream=rec.stream)
+
+    uniques, counts, offsets, inverse = _launch_outputs(rec, blocks, run)
+    out = (uniques, counts, offsets)
     if return_inverse:
-        out += (_sample_shape(inverse, shape, kept, red, on),)
+        out += (_sample_shape(inverse, _shape_of(rec.like), rec.kept, rec.red, rec.backend),)
     return out + (bins,)

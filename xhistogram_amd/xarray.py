@@ -409,9 +409,10 @@ def _values_statistic(name, core_fn, args, values, bins, range, dim, keep_coords
 # ---------------------------------------------------------------------------------------------
 # per-sample maps: DataArrays on the broadcast dims of the inputs
 # ---------------------------------------------------------------------------------------------
-def _lined_up(name, data_args, extra):
+def _lined_up(name, data_args, extra, dim=None):
     """the inputs of a per-sample map (DataArrays: the named samples, then `extra`), aligned exactly and broadcast by
-    dimension name as :func:`histogram` does: (their data in one dim order, that order, the first operand)"""
+    dimension name as :func:`histogram` does: (their data in one dim order, that order, the kept dims (those not in `dim`;
+    none for ``dim=None``), the axes of `dim` in that order (None: all), the samples' coordinates on those dims)"""
     xr = _xr()
     for a in list(data_args) + list(extra):
         if not isinstance(a, xr.DataArray):
@@ -434,11 +435,15 @@ def _lined_up(name, data_args, extra):
         if tuple(a.dims) != tuple(dims_order):
             a = a.transpose(*dims_order)
         arrays.append(a.data)
-    return arrays, dims_order, operands[0]
+    kept = [d for d in dims_order if dim is not None and d not in dim]
+    axis = None if dim is None else [dims_order.index(d) for d in dim]
+    first = operands[0]
+    return arrays, dims_order, kept, axis, {d: first[d] for d in dims_order if d in first.coords}
 
 
-def _sample_coords(first, dims_order):
-    return {d: first[d] for d in dims_order if d in first.coords}
+def _row_array(data, kept, coords, last_dim, name):
+    """a per-row output: a DataArray on the kept dims, with the samples' coordinates on them, and a new last dim"""
+    return _xr().DataArray(data, dims=kept + [last_dim], coords={d: coords[d] for d in kept if d in coords}, name=name)
 
 
 def bin_index(*args, bins=None, range=None):
@@ -446,9 +451,9 @@ def bin_index(*args, bins=None, range=None):
     named ``<first arg>_bin_index``, ``-1`` where ``histogram`` drops the sample."""
     from .core import bin_index as _core_bin_index
 
-    arrays, dims_order, first = _lined_up("bin_index", args, [])
+    arrays, dims_order, _, _, coords = _lined_up("bin_index", args, [])
     out, _ = _core_bin_index(*arrays, bins=bins, range=range)
-    return _xr().DataArray(out, dims=dims_order, coords=_sample_coords(first, dims_order), name="%s_bin_index" % args[0].name)
+    return _xr().DataArray(out, dims=dims_order, coords=coords, name="%s_bin_index" % args[0].name)
 
 
 def histogram_lookup(*args, table, bins=None, range=None, dim=None, bin_dim_suffix="_bin"):
@@ -461,15 +466,13 @@ def histogram_lookup(*args, table, bins=None, range=None, dim=None, bin_dim_suff
     if not isinstance(table, xr.DataArray):
         raise TypeError("xhistogram.xarray.histogram_lookup accepts only xarray.DataArray objects but a %s was provided"
                         % type(table).__name__)
-    arrays, dims_order, first = _lined_up("histogram_lookup", args, [])
-    kept = [d for d in dims_order if dim is not None and d not in dim]
+    arrays, dims_order, kept, axis, coords = _lined_up("histogram_lookup", args, [], dim)
     want = kept + [a.name + bin_dim_suffix for a in args]
     if set(table.dims) != set(want):
         raise ValueError("table has dims %s, but histogram gives %s for these arguments" % (tuple(table.dims), tuple(want)))
     t = table if tuple(table.dims) == tuple(want) else table.transpose(*want)
-    axis = None if dim is None else [dims_order.index(d) for d in dim]
     out, _ = _core_histogram_lookup(*arrays, table=t.data, bins=bins, range=range, axis=axis)
-    return xr.DataArray(out, dims=dims_order, coords=_sample_coords(first, dims_order), name="%s_lookup" % (table.name or "table"))
+    return xr.DataArray(out, dims=dims_order, coords=coords, name="%s_lookup" % (table.name or "table"))
 
 
 def histogram_anomaly(*args, values, bins=None, range=None, dim=None, weights=None, ddof=0, standardize=False):
@@ -481,13 +484,11 @@ def histogram_anomaly(*args, values, bins=None, range=None, dim=None, weights=No
     if values is None:
         raise TypeError("histogram_anomaly needs values")
     extra = [values] + ([] if weights is None else [weights])
-    arrays, dims_order, first = _lined_up("histogram_anomaly", args, extra)
+    arrays, dims_order, _, axis, coords = _lined_up("histogram_anomaly", args, extra, dim)
     n = len(args)
-    axis = None if dim is None else [dims_order.index(d) for d in dim]
     out, _ = _core_histogram_anomaly(*arrays[:n], values=arrays[n], bins=bins, range=range, axis=axis,
                                      weights=arrays[n + 1] if weights is not None else None, ddof=ddof, standardize=standardize)
-    return _xr().DataArray(out, dims=dims_order, coords=_sample_coords(first, dims_order),
-                           name="%s_anomaly" % (values.name or "values"))
+    return _xr().DataArray(out, dims=dims_order, coords=coords, name="%s_anomaly" % (values.name or "values"))
 
 
 def bin_order(*args, bins=None, range=None, dim=None):
@@ -498,15 +499,11 @@ def bin_order(*args, bins=None, range=None, dim=None):
     start)."""
     from .core import bin_order as _core_bin_order
 
-    arrays, dims_order, first = _lined_up("bin_order", args, [])
-    kept = [d for d in dims_order if dim is not None and d not in dim]
-    axis = None if dim is None else [dims_order.index(d) for d in dim]
+    arrays, _, kept, axis, coords = _lined_up("bin_order", args, [], dim)
     order, offsets, _ = _core_bin_order(*arrays, bins=bins, range=range, axis=axis)
     name = args[0].name
-    coords = _sample_coords(first, kept)
-    xr = _xr()
-    return (xr.DataArray(order, dims=kept + ["%s_order" % name], coords=coords, name="%s_bin_order" % name),
-            xr.DataArray(offsets, dims=kept + ["%s_bin_offset" % name], coords=coords, name="%s_bin_offsets" % name))
+    return (_row_array(order, kept, coords, "%s_order" % name, "%s_bin_order" % name),
+            _row_array(offsets, kept, coords, "%s_bin_offset" % name, "%s_bin_offsets" % name))
 
 
 def bin_sort(*args, values, bins=None, range=None, dim=None, descending=False):
@@ -520,16 +517,12 @@ def bin_sort(*args, values, bins=None, range=None, dim=None, descending=False):
 
     if values is None:
         raise TypeError("bin_sort needs values")
-    arrays, dims_order, first = _lined_up("bin_sort", args, [values])
+    arrays, _, kept, axis, coords = _lined_up("bin_sort", args, [values], dim)
     n = len(args)
-    kept = [d for d in dims_order if dim is not None and d not in dim]
-    axis = None if dim is None else [dims_order.index(d) for d in dim]
     order, offsets, _ = _core_bin_sort(*arrays[:n], values=arrays[n], bins=bins, range=range, axis=axis, descending=descending)
     name = values.name or "values"
-    coords = _sample_coords(first, kept)
-    xr = _xr()
-    return (xr.DataArray(order, dims=kept + ["%s_order" % name], coords=coords, name="%s_bin_sort" % name),
-            xr.DataArray(offsets, dims=kept + ["%s_bin_offset" % name], coords=coords, name="%s_bin_offsets" % name))
+    return (_row_array(order, kept, coords, "%s_order" % name, "%s_bin_sort" % name),
+            _row_array(offsets, kept, coords, "%s_bin_offset" % name, "%s_bin_offsets" % name))
 
 
 def bin_rank(*args, values, bins=None, range=None, dim=None, method="average", descending=False, pct=False):
@@ -540,12 +533,11 @@ def bin_rank(*args, values, bins=None, range=None, dim=None, method="average", d
 
     if values is None:
         raise TypeError("bin_rank needs values")
-    arrays, dims_order, first = _lined_up("bin_rank", args, [values])
+    arrays, dims_order, _, axis, coords = _lined_up("bin_rank", args, [values], dim)
     n = len(args)
-    axis = None if dim is None else [dims_order.index(d) for d in dim]
     out, _ = _core_bin_rank(*arrays[:n], values=arrays[n], bins=bins, range=range, axis=axis, method=method, descending=descending,
                             pct=pct)
-    return _xr().DataArray(out, dims=dims_order, coords=_sample_coords(first, dims_order), name="%s_bin_rank" % (values.name or "values"))
+    return _xr().DataArray(out, dims=dims_order, coords=coords, name="%s_bin_rank" % (values.name or "values"))
 
 
 def bin_unique(*args, values, bins=None, range=None, dim=None, size=None, return_inverse=False):
@@ -560,17 +552,13 @@ def bin_unique(*args, values, bins=None, range=None, dim=None, size=None, return
 
     if values is None:
         raise TypeError("bin_unique needs values")
-    arrays, dims_order, first = _lined_up("bin_unique", args, [values])
+    arrays, dims_order, kept, axis, coords = _lined_up("bin_unique", args, [values], dim)
     n = len(args)
-    kept = [d for d in dims_order if dim is not None and d not in dim]
-    axis = None if dim is None else [dims_order.index(d) for d in dim]
     res = _core_bin_unique(*arrays[:n], values=arrays[n], bins=bins, range=range, axis=axis, size=size, return_inverse=return_inverse)
     name = values.name or "values"
-    coords = _sample_coords(first, kept)
-    xr = _xr()
-    out = (xr.DataArray(res[0], dims=kept + ["%s_unique" % name], coords=coords, name="%s_unique" % name),
-           xr.DataArray(res[1], dims=kept + ["%s_unique" % name], coords=coords, name="%s_unique_counts" % name),
-           xr.DataArray(res[2], dims=kept + ["%s_bin_offset" % name], coords=coords, name="%s_unique_offsets" % name))
+    out = (_row_array(res[0], kept, coords, "%s_unique" % name, "%s_unique" % name),
+           _row_array(res[1], kept, coords, "%s_unique" % name, "%s_unique_counts" % name),
+           _row_array(res[2], kept, coords, "%s_bin_offset" % name, "%s_unique_offsets" % name))
     if len(res) == 5:
-        out += (xr.DataArray(res[3], dims=dims_order, coords=_sample_coords(first, dims_order), name="%s_unique_inverse" % name),)
+        out += (_xr().DataArray(res[3], dims=dims_order, coords=coords, name="%s_unique_inverse" % name),)
     return out
