@@ -517,6 +517,66 @@ int xhist_plan_execute_unique(xhist_plan* plan, const xhist_array* samples, cons
                               int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets, int64_t* out_inverse,
                               int mem_kind, void* stream);
 
+/* bin_weighted_unique (added within ABI v11: a new entry, every earlier one unchanged): xhist_plan_execute_unique with a weight
+ * per column and one output more, for samples that are not equal (a grid cell's area or volume).  out_uniques, out_counts,
+ * out_offsets and out_inverse are xhist_plan_execute_unique's on the same arguments, bit for bit, with its rules for `size`,
+ * padding and truncation.
+ *   out_weight_sums[r, u] = the float64 sum of float64(weights[r, c]) over the columns c that out_counts[r, u] counts.  A
+ *                           column whose value is NaN belongs to no entry, whatever its weight.  Padding entries are +0.0,
+ *                           entries u >= size are stored nowhere.  Weights are not checked: a zero weight still counts in
+ *                           out_counts, negative weights add, a NaN weight makes its own entry NaN and no other, and +inf and
+ *                           -inf in one entry give NaN.
+ *   out_weight_sums is a contiguous DEVICE block [n_rows, size] of float64; every element is written and nothing outside it.
+ *   With size > 0 a NULL out_uniques, out_counts or out_weight_sums is XHIST_ERR_INVALID, and so are a NULL out_offsets, NULL
+ *   weights and a negative size.  weights: any real dtype, any strides (stride 0: broadcast).
+ *   The order of the additions is part of the interface.  The columns of an entry are one run of the sorted order, in ascending
+ *   column inside it.  One wave per 64 positions gathers the weights (the call's only gather of them), takes an inclusive
+ *   segmented sum between the head bits in six shuffle steps, stores every run that starts and ends inside its 64 positions,
+ *   and leaves two sums: of the lanes before its first head and from its last head on.  A segmented scan over these, in tiles of
+ *   1024 words as the scan of the head words goes, gives every word the sum of the run that enters it, and the word in which
+ *   that run ends stores it.  There is no floating-point atomic, no kernel waits for another workgroup, and the tree of a run
+ *   depends on its first and last sorted position in its row alone: the same bits run to run, on any stream, for any grid and
+ *   any rows_per_launch, with and without an inverse and for any size.  On weights whose partial sums are all exact in float64
+ *   every sum is the exact one; otherwise it is within 2 * gamma(n) * sum |w| of it, n the entry's count.
+ *   Scratch of the call, on top of xhist_plan_execute_unique's and only for size > 0: 16 bytes per 64 samples of a row and 16
+ *   bytes per 65536 samples of a row; XHIST_ERR_NOMEM where it cannot be had.
+ *   mem_kind must be XHIST_MEM_DEVICE; anything else is XHIST_ERR_INVALID.  Asynchronous on `stream`, no synchronisation with
+ *   the host.
+ *   xhist_plan_describe then reads "wunique size=.. inverse=0|1 words=.. rows_per_launch=.. | " followed by
+ *   xhist_plan_execute_sort's own line ("none" for a call without columns or a plan without bins). */
+int xhist_plan_execute_unique_weighted(xhist_plan* plan, const xhist_array* samples, const xhist_array* values,
+                                       const xhist_array* weights, int64_t n_rows, int64_t n_cols, int64_t size, double* out_uniques,
+                                       int64_t* out_counts, double* out_weight_sums, int64_t* out_offsets, int64_t* out_inverse,
+                                       int mem_kind, void* stream);
+
+/* histogram_weighted_mode (added within ABI v11: a new entry, every earlier one unchanged): per bin the value that carries the
+ * most weight.  out_count and out_nunique are xhist_plan_execute_mode's, bit for bit.  With the entries of bin b as
+ * xhist_plan_execute_unique_weighted gives them for size = n_cols:
+ *   out_mode_weight[r, b] = the largest out_weight_sums entry of the bin, compared as IEEE compares (-0.0 and +0.0 are equal);
+ *                           bitwise the first entry of the segment that holds the maximum
+ *   out_mode[r, b]        = out_uniques of that entry, by bits: among equal sums the smallest value
+ *   Where any entry sum of the bin is NaN, both are 0x7ff8000000000000.  An empty bin (a bin of only NaN values included) gets
+ *   0, 0, NaN (0x7ff8000000000000) and +0.0.  With all weights 1 out_mode is xhist_plan_execute_mode's by bits and
+ *   out_mode_weight == out_mode_count.
+ *   The four outputs are contiguous DEVICE blocks [n_rows, B], int64 the first two, float64 the others; every element of each
+ *   is written exactly once and nothing outside them.  A NULL output and NULL weights are XHIST_ERR_INVALID.  n_cols must be
+ *   below 2^31 and B + 1 at most 2^32: XHIST_ERR_UNSUPPORTED otherwise, before any launch.
+ *   The call is xhist_plan_execute_mode's up to the scan of the head words, then the run sums of
+ *   xhist_plan_execute_unique_weighted, each stored at its run's first sorted position, and three kernels: one wave per 64
+ *   positions takes the maximum per bin of an order-preserving 64-bit key of the sums (-0.0 as +0.0, NaN the largest) and issues
+ *   at most one 64-bit integer atomic maximum per (64 positions, bin), read first; a second walk has the runs whose key equals
+ *   the slot take an integer atomic minimum of their start; one thread per (row, bin) writes the four outputs and gathers the
+ *   one value.  Integer atomics only: neither result depends on the order of arrival.
+ *   Scratch of the call, on top of xhist_plan_execute_mode's: 8 bytes per sample, 16 bytes per 64 samples of a row and 16 bytes
+ *   per 65536 samples of a row; XHIST_ERR_NOMEM where it cannot be had.  The slots of the atomics are the out_mode_weight and
+ *   out_mode blocks, filled by the call and finished in place.
+ *   mem_kind must be XHIST_MEM_DEVICE.  Deterministic.  Asynchronous on `stream`.
+ *   xhist_plan_describe then reads "wmode words=.. rows_per_launch=.. | " followed by xhist_plan_execute_sort's own line ("none"
+ *   for a call without columns). */
+int xhist_plan_execute_mode_weighted(xhist_plan* plan, const xhist_array* samples, const xhist_array* values, const xhist_array* weights,
+                                     int64_t n_rows, int64_t n_cols, int64_t* out_count, int64_t* out_nunique, double* out_mode,
+                                     double* out_mode_weight, int mem_kind, void* stream);
+
 /* One-shot form of the two calls above with an internal plan cache keyed on (device, edges). */
 int xhist_bincount_rows(int device, int n_inputs, const xhist_array* samples,
                         const xhist_array* weights, int64_t n_rows, int64_t n_cols,

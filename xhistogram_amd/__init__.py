@@ -5,7 +5,7 @@ digitize -> joint index -> scatter-add kernel lives in ``libxhist_amd.so`` (csrc
 include/xhist_amd.h).  There is no CPU implementation in this package.
 """
 
-from .core import histogram  # noqa: F401
+from .core import bin_weighted_unique, histogram, histogram_weighted_mode  # noqa: F401
 
 __version__ = "0.1.0"
-__all__ = ["histogram"]
+__all__ = ["histogram", "bin_weighted_unique", "histogram_weighted_mode"]

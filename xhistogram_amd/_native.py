@@ -75,7 +75,7 @@ EXPORTS = (
     "xhist_plan_execute_mean_var", "xhist_plan_execute_mean_var_weighted", "xhist_plan_execute_quantile",
     "xhist_plan_execute_quantile_weighted", "xhist_plan_execute_cov", "xhist_plan_execute_cov_weighted",
     "xhist_plan_execute_skew_kurt", "xhist_plan_execute_skew_kurt_weighted", "xhist_plan_execute_argextrema",
-    "xhist_plan_execute_map", "xhist_plan_execute_group", "xhist_plan_execute_sort", "xhist_plan_execute_rank", "xhist_plan_execute_mode", "xhist_plan_execute_unique", "xhist_plan_execute_sum", "xhist_debug_sum_host", "xhist_debug_sum_round",
+    "xhist_plan_execute_map", "xhist_plan_execute_group", "xhist_plan_execute_sort", "xhist_plan_execute_rank", "xhist_plan_execute_mode", "xhist_plan_execute_unique", "xhist_plan_execute_unique_weighted", "xhist_plan_execute_mode_weighted", "xhist_plan_execute_sum", "xhist_debug_sum_host", "xhist_debug_sum_round",
     "xhist_bincount_rows",
     "xhist_minmax", "xhist_moments", "xhist_plan_set_param", "xhist_plan_describe", "xhist_plan_profile_read",
     "xhist_comm_unique_id", "xhist_comm_create", "xhist_comm_info", "xhist_comm_allreduce", "xhist_comm_allgather",
@@ -196,6 +196,14 @@ def load():
         lib.xhist_plan_execute_unique.argtypes = [
             C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
             C.c_void_p, C.c_int, C.c_void_p,
+        ]
+        lib.xhist_plan_execute_unique_weighted.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+        ]
+        lib.xhist_plan_execute_mode_weighted.argtypes = [
+            C.c_void_p, C.POINTER(XhistArray), C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
         ]
         lib.xhist_bincount_rows.argtypes = [
             C.c_int, C.c_int, C.POINTER(XhistArray), C.POINTER(XhistArray), C.c_int64, C.c_int64, C.POINTER(C.c_void_p),
@@ -501,6 +509,28 @@ class Plan:
                 C.c_void_p(out_inverse_ptr or 0), MEM_DEVICE, C.c_void_p(stream or 0),
             )
         )
+
+    def execute_unique_weighted(self, sample_views, value_view, weight_view, n_rows, n_cols, size, out_uniques_ptr, out_counts_ptr,
+                                out_weight_sums_ptr, out_offsets_ptr, out_inverse_ptr=None, stream=0):
+        """execute_unique with a weight per column and one block more, float64 [n_rows, size]: the float64 sum of the weights of
+        the columns each entry counts, +0.0 in the padding; the same bits for any stream, batch of rows, size and with or
+        without an inverse (xhist_plan_execute_unique_weighted)"""
+        check(
+            load().xhist_plan_execute_unique_weighted(
+                self._h, self._sample_array(sample_views), C.byref(value_view), C.byref(weight_view), int(n_rows), int(n_cols),
+                int(size), C.c_void_p(out_uniques_ptr or 0), C.c_void_p(out_counts_ptr or 0), C.c_void_p(out_weight_sums_ptr or 0),
+                C.c_void_p(out_offsets_ptr or 0), C.c_void_p(out_inverse_ptr or 0), MEM_DEVICE, C.c_void_p(stream or 0),
+            )
+        )
+
+    def execute_mode_weighted(self, sample_views, value_view, weight_view, n_rows, n_cols, out_count_ptr, out_nunique_ptr, out_mode_ptr,
+                              out_mode_weight_ptr, stream=0):
+        """per bin the number of non-NaN values (int64), the number of distinct ones (int64), the value whose columns' weights
+        have the largest float64 sum (float64, the smallest among equal sums; NaN where no value arrived) and that sum (float64)
+        of device-resident views, into device buffers of [n_rows, bins] each, asynchronous on `stream`
+        (xhist_plan_execute_mode_weighted); fewer than 2^31 columns"""
+        self._execute_values("xhist_plan_execute_mode_weighted", sample_views, (value_view, weight_view), n_rows, n_cols,
+                             (out_count_ptr, out_nunique_ptr, out_mode_ptr, out_mode_weight_ptr), stream=stream)
 
     def execute_mean_var(self, sample_views, value_view, n_rows, n_cols, out_count_ptr, out_mean_ptr, out_m2_ptr, stream=0):
         """per-bin count (int64), mean and sum of squared deviations M2 (float64; NaN where no value arrived) of the values of

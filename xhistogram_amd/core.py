@@ -37,7 +37,7 @@ _range = range
 __all__ = ["histogram", "histogram_two_weights", "histogram_extrema", "histogram_mean_var", "histogram_quantile",
            "histogram_weighted_quantile", "histogram_cov", "histogram_weighted_cov", "combine_weighted_cov",
            "histogram_skew_kurt", "combine_skew_kurt", "combine_weighted_skew_kurt", "histogram_argextrema", "histogram_sum", "bin_order", "bin_sort", "bin_rank",
-           "histogram_mode", "bin_unique"]
+           "histogram_mode", "bin_unique", "bin_weighted_unique", "histogram_weighted_mode"]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1932,7 +1932,7 @@ def _value_rows(st, args, values, axis, bins, backend, *extras, **params):
 def _value_block(*all_arrays, stat=None, axis=None, bins=None, **params):
     """one dask block (samples..., values, the statistic's extras): its outputs as _value_rows gives them.  Counts that the
     dask step merges become float64 by value; int64 outputs that are never merged stay the bits they are."""
-    st = _VALUE_STATS[stat]
+    st = _stat_entry(stat)
     n = len(all_arrays) - 1 - st.extras
     arrays = _upload_host(all_arrays[:n], all_arrays[n], bins, *all_arrays[n + 1:])
     out = _value_rows(st, arrays[:n], arrays[n], axis, bins, "device", *arrays[n + 1:], **params)
@@ -1986,7 +1986,7 @@ def _value_stat(stat, args, values, bins, range, axis, name, aggregate=None, *ex
     `aggregate`.  The entry's size limits are refused before any device work on the samples."""
     backend, all_arrays, raw, bins, axis, drop_axes = _values_call(args, values, bins, range, axis, name, *extras, weights)
     n_inputs = len(args)
-    st = _VALUE_STATS[stat]
+    st = _stat_entry(stat)
     k = st.k or len(params["q"])
     if st.max_cols is not None:
         _check_sizes(name, all_arrays[0].shape, drop_axes, bins, st.max_cols, st.max_bins)
@@ -2581,6 +2581,19 @@ _VALUE_STATS = {
                        max_bins=_SORT_MAX_BINS),
 }
 
+# The statistics behind the sorted order that read weights: (count, nunique, mode, mode_weight).  They are entries of the same
+# kind and take the same path (_stat_entry looks in both); they are kept beside _VALUE_STATS only because that table's keys and
+# its entries with a size limit are pinned by the CPU tests of the earlier statistics, which a new feature leaves as they are.
+# Once those tests list the weighted twins, this dict folds into the table above.
+_SORTED_WEIGHTED_STATS = {
+    "mode_w": _ValueStat(4, (0, 1), "execute_mode_weighted", (0, 1, 2, 3), 1, None, noun="modes", max_cols=_ORDER_MAX_COLS,
+                         max_bins=_SORT_MAX_BINS),
+}
+
+
+def _stat_entry(stat):
+    return _SORTED_WEIGHTED_STATS[stat] if stat in _SORTED_WEIGHTED_STATS else _VALUE_STATS[stat]
+
 
 # ---------------------------------------------------------------------------------------------
 # per-bin quantiles of a value array
@@ -2973,6 +2986,42 @@ def histogram_mode(*args, values, bins=None, range=None, axis=None, weights=None
     return count, nunique, mode, mode_count, bins
 
 
+def histogram_weighted_mode(*args, values, weights, bins=None, range=None, axis=None):
+    """Per-bin value of ``values`` that carries the most weight, computed on an MI355X: :func:`histogram_mode` for samples that
+    are not equal — the dominant land-cover type of an elevation band by area, the dominant water mass of a T–S class by volume.
+    ``pandas.Series(w).groupby([bin, v]).sum()`` and an ``idxmax`` per bin on the host.
+
+    ``args``, ``bins``, ``range``, ``axis`` and ``values`` are :func:`histogram_mode`'s.  ``weights`` broadcasts against the
+    inputs as ``values`` does, may have any real dtype and is taken as float64; a complex dtype, ``None`` and a missing
+    ``weights`` are a ``TypeError``.  Weights are not checked: a zero weight still counts, negative weights add.
+
+    Per (kept index, bin), with the bin's entries as :func:`bin_weighted_unique` gives them:
+
+    * ``count`` and ``nunique`` are :func:`histogram_mode`'s, bit for bit;
+    * ``mode_weight`` is the largest ``weight_sums`` entry of the bin, float64, compared as IEEE compares (``-0.0 == +0.0``);
+      bitwise it is the first entry of the segment that holds the maximum;
+    * ``mode`` is the value of that entry (its bits are ``uniques``' bits): among equal sums the smallest value wins,
+      :func:`histogram_mode`'s rule;
+    * if any entry sum of the bin is NaN, both ``mode`` and ``mode_weight`` are NaN (``0x7ff8000000000000``);
+    * an empty bin gets ``0``, ``0``, NaN and ``+0.0``.
+
+    With all weights 1, ``mode`` is :func:`histogram_mode`'s ``mode`` by bits and ``mode_weight == mode_count``.  Deterministic:
+    the sums are :func:`bin_weighted_unique`'s, a fixed tree of float64 additions per value, and the maximum over them is taken
+    with integer atomics on an order-preserving key, which do not depend on the order of arrival.
+
+    There is no ``descending``.  A reduced extent of 2^31 samples or more per output row, and ``B + 1 > 2**32`` bins, raise
+    ``NotImplementedError``; all refusals happen before any device work.
+
+    Returns ``(count, nunique, mode, mode_weight, bin_edges)`` with the shape ``histogram`` gives (kept axes, then bin axes).
+    numpy in -> numpy out, torch in -> torch out on the same device (asynchronous on the current stream), DeviceArray in ->
+    numpy out, dask in -> lazy dask arrays, one task per block: every reduced axis must then be a single chunk."""
+    if weights is None:
+        raise TypeError("histogram_weighted_mode needs weights")
+    _, (count, nunique, mode, mode_weight), bins, _ = _value_stat("mode_w", args, values, bins, range, axis, "histogram_weighted_mode",
+                                                                  weights=weights)
+    return count, nunique, mode, mode_weight, bins
+
+
 # ---------------------------------------------------------------------------------------------
 # bin_order, bin_sort and bin_rank: the samples grouped by bin, their one call path
 # ---------------------------------------------------------------------------------------------
@@ -3245,34 +3294,97 @@ def bin_unique(*args, values, bins=None, range=None, axis=None, size=None, retur
     bin_edges)``.  numpy in -> numpy out (uploaded once, one download), torch in -> torch out on the same device (asynchronous
     on the current stream, no host synchronisation), DeviceArray in -> numpy out, dask in -> lazy dask arrays, one task per
     block over the kept axes: every reduced axis must then be a single chunk, and ``bins`` numpy arrays of edges."""
+    return _bin_unique("bin_unique", args, values, None, bins, range, axis, size, return_inverse)
+
+
+def _bin_unique(name, args, values, weights, bins, range, axis, size, return_inverse):
+    """bin_unique (`weights` None) and bin_weighted_unique: the outputs without weight_sums, or with it behind counts"""
     def check():
         _check_size(size)
         _check_flag("return_inverse", return_inverse)
 
-    f = _sample_call("bin_unique", args, values, bins, range, axis, noun="distinct values", max_bins=_SORT_MAX_BINS, check=check)
+    weighted = weights is not None
+    f = _sample_call(name, args, values, bins, range, axis, *((weights,) if weighted else ()), noun="distinct values",
+                     max_bins=_SORT_MAX_BINS, check=check)
     bins, return_inverse = f.bins, bool(return_inverse)
     size = None if size is None else int(size)
     n = len(args)
     if f.backend == "dask":
         width = f.cols if size is None else size
-        both, offsets = _packed_blockwise(_bin_unique_block, f.arrays, f.drop_axes, 2 * width, f.n_bins, bins=bins, size=width)
-        uniques = both[..., :width].map_blocks(_float64_bits, dtype=np.float64, meta=np.array((), np.float64))
-        out = (uniques, both[..., width:], offsets)
+        k = 3 if weighted else 2
+        both, offsets = _packed_blockwise(_bin_weighted_unique_block if weighted else _bin_unique_block, f.arrays, f.drop_axes, k * width,
+                                          f.n_bins, bins=bins, size=width)
+        floats = [both[..., i * width:(i + 1) * width].map_blocks(_float64_bits, dtype=np.float64, meta=np.array((), np.float64))
+                  for i in ((0, 2) if weighted else (0,))]
+        out = (floats[0], both[..., width:2 * width]) + tuple(floats[1:]) + (offsets,)
         if return_inverse:
-            out += (_sample_blockwise(_bin_unique_inverse_block, f.arrays, np.int64, axis=list(f.drop_axes), bins=bins),)
+            out += (_sample_blockwise(_bin_unique_inverse_block, f.arrays[:n + 1], np.int64, axis=list(f.drop_axes), bins=bins),)
         return out + (bins,)
-    rec = _value_views(f.arrays[:n], f.arrays[n], f.axis, bins, f.on, ordered=True)
+    rec = _value_views(f.arrays[:n], f.arrays[n], f.axis, bins, f.on, *f.arrays[n + 1:], ordered=True)
     width = rec.c if size is None else size
     # (a call without an inverse: its block has no column, and the library is told so with a NULL pointer)
-    blocks = [(_row_shape(rec, width), np.float64), (_row_shape(rec, width), np.int64), (_row_shape(rec, rec.plan.n_bins + 1), np.int64),
-              ((rec.m, rec.c if return_inverse else 0), np.int64)]
+    blocks = [(_row_shape(rec, width), np.float64), (_row_shape(rec, width), np.int64)]
+    blocks += [(_row_shape(rec, width), np.float64)] if weighted else []
+    blocks += [(_row_shape(rec, rec.plan.n_bins + 1), np.int64), ((rec.m, rec.c if return_inverse else 0), np.int64)]
 
     def run(ptrs):
-        rec.plan.execute_unique(rec.nv[:n], rec.nv[n], rec.m, rec.c, width, *ptrs[:3], ptrs[3] if return_inverse else None,
-                                stream=rec.stream)
+        method = rec.plan.execute_unique_weighted if weighted else rec.plan.execute_unique
+        method(rec.nv[:n], *rec.nv[n:], rec.m, rec.c, width, *ptrs[:-1], ptrs[-1] if return_inverse else None, stream=rec.stream)
 
-    uniques, counts, offsets, inverse = _launch_outputs(rec, blocks, run)
-    out = (uniques, counts, offsets)
+    *out, inverse = _launch_outputs(rec, blocks, run)
+    out = tuple(out)
     if return_inverse:
         out += (_sample_shape(inverse, _shape_of(rec.like), rec.kept, rec.red, rec.backend),)
     return out + (bins,)
+
+
+def _bin_weighted_unique_block(*blocks, axis=None, bins=None, size=None):
+    """one dask block (samples..., values, weights): uniques, counts and weight_sums (the float64 ones as the bits they are) side
+    by side, then the offsets"""
+    uniques, counts, sums, offsets, _ = bin_weighted_unique(*blocks[:-2], values=blocks[-2], weights=blocks[-1], bins=bins, axis=axis,
+                                                            size=size)
+    bits = [np.ascontiguousarray(a).view(np.int64) for a in (uniques, sums)]
+    return _packed_block(np.concatenate([bits[0], counts, bits[1]], axis=-1), offsets, blocks[0], axis)
+
+
+def bin_weighted_unique(*args, values, weights, bins=None, range=None, axis=None, size=None, return_inverse=False):
+    """The distinct values of every bin, how often each occurs and how much weight each carries, in CSR form, computed on an
+    MI355X: :func:`bin_unique` for samples that are not equal — a land-cover composition by area per elevation band, a water-mass
+    census by volume per T–S class.  ``pandas.Series(w).groupby([bin, v]).sum()``, or :func:`bin_sort`, a gather of the weights
+    and ``np.add.reduceat`` over the run starts on the host.
+
+    Every argument but ``weights`` is :func:`bin_unique`'s, and ``uniques``, ``counts``, ``offsets`` and ``inverse`` are its
+    outputs bit for bit, with every ``size``, padding and truncation rule.  ``weights`` broadcasts against the inputs as
+    ``values`` does, may have any real dtype and is taken as float64; a complex dtype, ``None`` and a missing ``weights`` are a
+    ``TypeError``.
+
+    ``weight_sums`` is float64 ``kept + (W,)``: ``weight_sums[u]`` is the float64 sum of the weights of the counted samples of
+    that bin whose value ``==`` ``uniques[u]``, the samples ``counts[u]`` counts.  A counted sample with a NaN value belongs to
+    no entry, whatever its weight.  Padding entries ``min(U, W) <= u < W`` are ``+0.0``; entries ``u >= W`` are stored nowhere.
+    Weights are not checked: a zero weight still counts in ``counts``, negative weights add, a NaN weight makes its own entry's
+    sum NaN and no other, ``+inf`` and ``-inf`` in one entry give NaN.
+
+    The order of the additions is part of the interface.  The samples of an entry are one run of :func:`bin_sort`'s order, in
+    ascending position; the run is summed over a fixed tree that depends only on where its first and last sorted position lie
+    against the words of 64 positions and the tiles of 65 536 positions of the row.  There is no floating-point atomic.  So
+    ``weight_sums`` has the same bits run to run, on any stream, however the rows are batched, with and without an inverse, for
+    any ``size``, and :func:`histogram_weighted_mode`'s ``mode_weight`` is bitwise the first maximal entry of its segment.  On
+    weights whose partial sums are all exact in float64 every sum equals ``math.fsum``; otherwise it is within
+    ``2 * gamma(n) * sum(abs(w))`` of it, ``n`` the entry's count.
+
+    So, per kept index: with all weights 1 ``weight_sums == counts``; on exactly summable weights
+    ``np.bincount(inverse[inverse >= 0], weights=w[inverse >= 0], minlength=U) == weight_sums[:U]``, and the segment sums of
+    ``weight_sums`` are ``histogram(..., weights=w)`` where no value is NaN.
+
+    The refusals and the empty cases are :func:`bin_unique`'s, all before any device work; there is no ``descending``.
+
+    Returns ``(uniques, counts, weight_sums, offsets, bin_edges)``, with ``return_inverse`` ``(uniques, counts, weight_sums,
+    offsets, inverse, bin_edges)``.  numpy in -> numpy out (uploaded once, one download), torch in -> torch out on the same
+    device (asynchronous on the current stream, no host synchronisation), DeviceArray in -> numpy out, dask in -> lazy dask
+    arrays, one task per block over the kept axes: every reduced axis must then be a single chunk, and ``bins`` numpy arrays of
+    edges."""
+    if weights is None:
+        raise TypeError("bin_weighted_unique needs weights")
+    if not hasattr(weights, "dtype"):
+        weights = np.asarray(weights)
+    return _bin_unique("bin_weighted_unique", args, values, weights, bins, range, axis, size, return_inverse)

@@ -502,6 +502,42 @@ extern "C" int xhist_plan_execute_unique(xhist_plan* p, const xhist_array* sampl
                         {true, true, "bin_unique"});
 }
 
+// bin_weighted_unique (xhist_rank.hip): bin_unique's call with weights and one block more.
+extern "C" int xhist_plan_execute_unique_weighted(xhist_plan* p, const xhist_array* samples, const xhist_array* values,
+                                                  const xhist_array* weights, int64_t n_rows, int64_t n_cols, int64_t size,
+                                                  double* out_uniques, int64_t* out_counts, double* out_weight_sums, int64_t* out_offsets,
+                                                  int64_t* out_inverse, int mem_kind, void* stream) {
+  if (size < 0) return fail(XHIST_ERR_INVALID, "bin_weighted_unique takes a size of 0 or more, got %lld", (long long)size);
+  if (p)
+    if (int rc = sorted_order_limits("bin_weighted_unique", true, n_cols, p->n_bins)) return rc;
+  if (!weights) return fail(XHIST_ERR_INVALID, "weights are required");
+  if (int rc = validate_arrays(p, samples, weights, n_rows, n_cols, nullptr, XHIST_F64, true)) return rc;
+  const char* const missing = n_rows > 0 && !out_offsets ? "out_offsets is NULL"
+                              : n_rows > 0 && size > 0 && !(out_uniques && out_counts && out_weight_sums)
+                                  ? "out_uniques / out_counts / out_weight_sums is NULL"
+                                  : nullptr;
+  return execute_values(p, "xhist_plan_execute_unique_weighted", samples, values, weights, nullptr, n_rows, n_cols, nullptr, !missing, missing,
+                        mem_kind, stream,
+                        [&](const ValuesCall& k) {
+                          return xhist_unique_w_run(k, size, out_uniques, out_counts, out_weight_sums, out_offsets, out_inverse);
+                        },
+                        {true, true, "bin_weighted_unique"});
+}
+
+// histogram_weighted_mode (xhist_rank.hip): histogram_mode's call with weights, out_mode_weight in place of out_mode_count.
+extern "C" int xhist_plan_execute_mode_weighted(xhist_plan* p, const xhist_array* samples, const xhist_array* values,
+                                                const xhist_array* weights, int64_t n_rows, int64_t n_cols, int64_t* out_count,
+                                                int64_t* out_nunique, double* out_mode, double* out_mode_weight, int mem_kind, void* stream) {
+  if (p)
+    if (int rc = sorted_order_limits("histogram_weighted_mode", true, n_cols, p->n_bins)) return rc;
+  if (!weights) return fail(XHIST_ERR_INVALID, "weights are required");
+  if (int rc = validate_arrays(p, samples, weights, n_rows, n_cols, out_mode_weight, XHIST_F64)) return rc;
+  return execute_values(p, "xhist_plan_execute_mode_weighted", samples, values, weights, nullptr, n_rows, n_cols, out_mode,
+                        out_count && out_nunique && out_mode_weight, "out_count / out_nunique / out_mode_weight is NULL", mem_kind, stream,
+                        [&](const ValuesCall& k) { return xhist_mode_w_run(k, out_count, out_nunique, out_mode, out_mode_weight); },
+                        {true, false, "histogram_weighted_mode"});
+}
+
 // ------------------------------------------------------------------------------------------
 // one-shot form with a plan cache
 // ------------------------------------------------------------------------------------------

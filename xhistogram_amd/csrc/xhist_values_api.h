@@ -75,9 +75,9 @@ struct ValuesCall {
 //   planes  outputs are [n_rows, n_bins] planes of 8-byte elements, or blocks [planes, n_rows, n_bins] of them: n_rows * n_bins > 0,
 //           n_cols >= 0
 //   dense   outputs are dense [n_rows, n_cols] or CSR blocks (xhist_map_run, xhist_group_run, xhist_sort_run, xhist_rank_run,
-//           xhist_unique_run): n_rows > 0, n_cols >= 0 and n_bins >= 0.  A call without columns and a plan without bins are the
+//           xhist_unique_run, xhist_unique_w_run): n_rows > 0, n_cols >= 0 and n_bins >= 0.  A call without columns and a plan without bins are the
 //           driver's own branches: it writes every element the outputs still have and a line with "none" in it.
-// For the drivers behind the sorted order (sort, rank, mode, unique; group for the first) the front has refused n_cols >= 2^31
+// For the drivers behind the sorted order (sort, rank, mode, unique and the weighted twins of the last two; group for the first) the front has refused n_cols >= 2^31
 // and n_bins + 1 > 2^32, XHIST_ERR_UNSUPPORTED, and an unknown rank method and a negative size, XHIST_ERR_INVALID.
 
 // xhist_extrema.hip: minimum and maximum (prepare, binning, finalize; `accumulate`: the outputs hold an earlier result), and
@@ -167,3 +167,18 @@ int xhist_mode_run(const ValuesCall& k, int64_t* out_count, int64_t* out_nunique
 // bins: offsets of zeros, padding, an inverse of -1.  size >= 0.
 int xhist_unique_run(const ValuesCall& k, int64_t size, double* out_uniques, int64_t* out_counts, int64_t* out_offsets,
                      int64_t* out_inverse);
+
+// xhist_rank.hip: bin_weighted_unique, xhist_unique_run with k.third the weights (any real dtype, taken as float64) and one block
+// more, out_weight_sums float64 [n_rows, size]: the float64 sum of the weights of the samples out_counts counts, +0.0 in the
+// padding.  The sum of a run is a fixed tree of additions over its samples in the sort's order (xhist_wruns.hip.h): no atomic,
+// and the same bits for any grid, batch of rows, width and stream.  Five kernels more for a width above 0, and 16 bytes of scratch
+// per 64 samples and per 65536 samples of a row.  out_weight_sums may be nullptr where size == 0.
+int xhist_unique_w_run(const ValuesCall& k, int64_t size, double* out_uniques, int64_t* out_counts, double* out_weight_sums,
+                       int64_t* out_offsets, int64_t* out_inverse);
+
+// xhist_rank.hip: histogram_weighted_mode, xhist_mode_run's out_count and out_nunique, and per (row, bin) the value whose samples'
+// weights (k.third) have the largest float64 sum (IEEE compare, the smallest value among equal sums) and that sum, bitwise what
+// xhist_unique_w_run stores for the entry; both 0x7ff8000000000000 where a sum of the bin is NaN; an empty bin gets 0, 0, NaN and
+// +0.0.  Four [n_rows, n_bins] planes, every element written exactly once.  The sums go to 8 bytes of scratch per sample; the
+// slots of the integer atomics are the out_mode_weight and out_mode blocks, filled by the call and finished in place.
+int xhist_mode_w_run(const ValuesCall& k, int64_t* out_count, int64_t* out_nunique, double* out_mode, double* out_mode_weight);

@@ -15,7 +15,7 @@ from .core import histogram_two_weights as _core_histogram_two_weights
 
 __all__ = ["histogram", "histogram_extrema", "histogram_mean_var", "histogram_quantile", "histogram_weighted_quantile",
            "histogram_cov", "histogram_weighted_cov", "histogram_skew_kurt", "histogram_argextrema", "bin_index", "histogram_lookup",
-           "histogram_anomaly", "histogram_sum", "bin_order", "bin_sort", "bin_rank", "histogram_mode", "bin_unique"]
+           "histogram_anomaly", "histogram_sum", "bin_order", "bin_sort", "bin_rank", "histogram_mode", "bin_unique", "bin_weighted_unique", "histogram_weighted_mode"]
 
 
 def _xr():
@@ -232,6 +232,26 @@ def histogram_mode(*args, values, bins=None, range=None, dim=None, block_size="a
     xr = _xr()
     return tuple(xr.DataArray(a, dims=out_dims, coords=coords, name="%s_%s" % (base, suffix))
                  for a, suffix in zip(results, ("count", "nunique", "mode", "mode_count")))
+
+
+def histogram_weighted_mode(*args, values, weights, bins=None, range=None, dim=None, keep_coords=False, bin_dim_suffix="_bin"):
+    """Per-bin value of the DataArray ``values`` that carries the most weight over the bins of ``args``
+    (:func:`xhistogram_amd.core.histogram_weighted_mode` with the labels of :func:`histogram`).
+
+    ``weights`` is a DataArray whose dims are a subset of the data's, aligned and broadcast as ``values`` is (cell areas or
+    volumes, ``cos(lat)``).  Returns ``(count, nunique, mode, mode_weight)``: four DataArrays with the dims and coords
+    ``histogram`` gives, named ``<values name>_count`` / ``_nunique`` / ``_weighted_mode`` / ``_mode_weight`` (``values`` when
+    the DataArray has no name)."""
+    from .core import histogram_weighted_mode as _core_histogram_weighted_mode
+
+    if weights is None:
+        raise TypeError("histogram_weighted_mode needs weights")
+    results, out_dims, coords, base = _values_statistic(
+        "histogram_weighted_mode", _core_histogram_weighted_mode, args, values, bins, range, dim, keep_coords, bin_dim_suffix,
+        weights=weights)
+    xr = _xr()
+    return tuple(xr.DataArray(a, dims=out_dims, coords=coords, name="%s_%s" % (base, suffix))
+                 for a, suffix in zip(results, ("count", "nunique", "weighted_mode", "mode_weight")))
 
 
 def histogram_skew_kurt(*args, values, bins=None, range=None, dim=None, weights=None, ddof=0, bias=True, fisher=True,
@@ -561,4 +581,30 @@ def bin_unique(*args, values, bins=None, range=None, dim=None, size=None, return
            _row_array(res[2], kept, coords, "%s_bin_offset" % name, "%s_unique_offsets" % name))
     if len(res) == 5:
         out += (_xr().DataArray(res[3], dims=dims_order, coords=coords, name="%s_unique_inverse" % name),)
+    return out
+
+
+def bin_weighted_unique(*args, values, weights, bins=None, range=None, dim=None, size=None, return_inverse=False):
+    """The distinct values of every bin, how often each occurs and how much weight each carries
+    (:func:`xhistogram_amd.core.bin_weighted_unique`); ``values`` and then ``weights`` (cell areas or volumes, ``cos(lat)``) are
+    lined up as :func:`bin_sort` lines its values up.  :func:`bin_unique`'s DataArrays, and behind the counts
+    ``<values name>_unique_weight_sums`` (float64) on the same new last dim ``<values name>_unique``: ``(unique, counts,
+    weight_sums, offsets)``, with ``return_inverse`` the inverse after them."""
+    from .core import bin_weighted_unique as _core_bin_weighted_unique
+
+    if values is None:
+        raise TypeError("bin_weighted_unique needs values")
+    if weights is None:
+        raise TypeError("bin_weighted_unique needs weights")
+    arrays, dims_order, kept, axis, coords = _lined_up("bin_weighted_unique", args, [values, weights], dim)
+    n = len(args)
+    res = _core_bin_weighted_unique(*arrays[:n], values=arrays[n], weights=arrays[n + 1], bins=bins, range=range, axis=axis, size=size,
+                                    return_inverse=return_inverse)
+    name = values.name or "values"
+    out = (_row_array(res[0], kept, coords, "%s_unique" % name, "%s_unique" % name),
+           _row_array(res[1], kept, coords, "%s_unique" % name, "%s_unique_counts" % name),
+           _row_array(res[2], kept, coords, "%s_unique" % name, "%s_unique_weight_sums" % name),
+           _row_array(res[3], kept, coords, "%s_bin_offset" % name, "%s_unique_offsets" % name))
+    if len(res) == 6:
+        out += (_xr().DataArray(res[4], dims=dims_order, coords=coords, name="%s_unique_inverse" % name),)
     return out
